@@ -8,7 +8,8 @@
 A "step" is one complete fit (multimodal_video_mocap) of one synthetic 300-frame x 50-marker sequence.
 Sequences are independent in the reference (one call per sequence, own betas), so ranks shard sequences
 with no data-path collective (weak scaling: every rank fits K sequences); the only collectives are the
-timing barrier and a max-reduce of the elapsed time.  One JSON line is printed by rank 0.
+timing barrier and a max-reduce of the elapsed time.  One JSON line is printed by rank 0; its `ms_per_step` is the
+wall time of one timed step.  `--dump-outputs DIR` writes the arrays the last timed fit returned to DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -103,7 +104,45 @@ def parse():
     ap.add_argument("--hypothesis-lockstep", action="store_true",
                     help="step the yaw hypotheses as one lock-step batch instead of one host thread + stream each "
                          "(multimodal_video_mocap(execution={'hypothesis_lockstep': True}); same results)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what rank 0's last timed fit returned (multimodal_video_mocap's "
+                         "arrays) as DIR/<name>.npy in float32 / float64, at most 64 MB in all, plus DIR/manifest.json; "
+                         "the inputs are seeded, so two builds run with the same arguments can be compared array by array")
     return ap.parse_args()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out, out_dir, seed=0):
+    """Write the arrays of one fit's output dict (what a caller of multimodal_video_mocap receives) as float32 / float64
+    .npy files.  Should they exceed DUMP_LIMIT_BYTES, the same fixed, seeded sample of frames (first axis) is kept of
+    every array."""
+    arrays = {}
+    for name, v in out.items():
+        if name == "mocap_markers":
+            v = v.get_points()
+        if isinstance(v, torch.Tensor):
+            v = v.detach().cpu().numpy()
+        v = np.asarray(v) if isinstance(v, (np.ndarray, float, int, np.number)) else None
+        if v is None or v.dtype.kind not in "biuf":
+            continue
+        arrays[name] = v.astype(np.float32 if v.dtype == np.float32 or v.dtype == np.float16 else np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    rows = None
+    if total > DUMP_LIMIT_BYTES:
+        n = max(a.shape[0] for a in arrays.values() if a.ndim)
+        keep = max(1, int(n * 0.95 * DUMP_LIMIT_BYTES / total))  # headroom for .npy headers and unsampled arrays
+        rows = np.sort(np.random.default_rng(seed).choice(n, size=keep, replace=False))
+        arrays = {k: (a[rows] if a.ndim and a.shape[0] == n else a) for k, a in arrays.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    manifest = {"arrays": {k: {"shape": list(a.shape), "dtype": str(a.dtype)} for k, a in arrays.items()},
+                "sampled_frames": None if rows is None else rows.tolist()}
+    with open(os.path.join(out_dir, "manifest.json"), "w") as fh:
+        json.dump(manifest, fh, indent=1, sort_keys=True)
+    return sorted(arrays)
 
 
 MODE = "sequences"
@@ -328,6 +367,8 @@ def packaged_cfg_full():
 def main():
     global MODE, LANES, TRANSPORT
     args = parse()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
     MODE = args.mode
     LANES = args.collective_lanes
     TRANSPORT = args.collective_transport
@@ -502,6 +543,10 @@ def main():
                      if cg0 else None,
                      "per_rank": host_all if world > 1 else None},
         }
+        if args.dump_outputs:
+            # what the timed path computed in its last step (rank 0's last timed sequence), before any further leg runs
+            result["dumped_outputs"] = {"dir": args.dump_outputs, "step": args.warmup + args.steps - 1,
+                                        "arrays": dump_outputs(fits[-1][0], args.dump_outputs)}
         if MODE in ("shared_betas", "frames"):
             n_g = sum(b_["gathers"] - a_["gathers"] for a_, b_ in zip(coll0, coll1))
             t_g = sum(b_["seconds"] - a_["seconds"] for a_, b_ in zip(coll0, coll1))

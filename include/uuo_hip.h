@@ -37,7 +37,7 @@ typedef struct uuo_fit uuo_fit_t;     /* per-sequence workspace (F frames, M mar
 
 const char* uuo_last_error(void);
 /* 3 since uuo_problem_t grew `w_soft` / `soft_tau` (2) and `n_corners` / `d_bary` (3), round 4; a binding checks it before it
- * hands structures over */
+ * hands structures over.  (`robust_sigma`, appended last, left it at 3: a binding must zero the structure it fills.) */
 int uuo_abi_version(void);
 
 /* ---- model ------------------------------------------------------------------------------------
@@ -163,6 +163,15 @@ typedef struct {
    * n_corners = 0 or 1: the one-hot placement of the shipped configs, d_assign [M], d_bary unused. */
   int32_t n_corners;
   const float* d_bary;
+  /* EXTENSION (not reference behaviour; unlabeled captures carry ghost points that the plain square lets pull on the body
+   * without bound): each data item's square s replaced by the Geman-McClure term of SMPLify's GMoF,
+   *   rho(s) = s sigma^2 / (sigma^2 + s)   (-> s as sigma -> inf, -> sigma^2 as s -> inf),   rho'(s) = (sigma^2 / (sigma^2 + s))^2
+   *   UUO_STAGE_CHAMFER s = min_v |x - v|^2 (the assignment is unchanged: rho is monotone), same mask and 1 / sum mask
+   *   UUO_STAGE_PART    the same over the candidate's vertices, same 1 / (F M)
+   *   UUO_STAGE_MARKER  s = (|x - vm| - d0)^2, one-hot and three-corner placements, same mask and 1 / (F M)
+   * Separate kernel instantiations (the plain ones are unchanged); available inside lock-step batches.  Needs w_soft = 0.
+   * robust_sigma = 0: the reference's square. */
+  float robust_sigma;        /* sigma in metres (>= 0, finite) */
 } uuo_problem_t;
 
 int uuo_fit_create(uuo_model_t* model, int F, int M, uuo_fit_t** out);

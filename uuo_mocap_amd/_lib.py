@@ -27,6 +27,7 @@ class UuoProblem(ctypes.Structure):
         ("pose_cache_id", ctypes.c_uint64),
         ("w_soft", c_float), ("soft_tau", c_float),   # EXTENSION: soft-assignment data term (part / chamfer stage)
         ("n_corners", c_int32), ("d_bary", c_void_p),  # marker stage on a three-corner (barycentric) placement
+        ("robust_sigma", c_float),                     # EXTENSION: Geman-McClure data terms (0 = the reference's square)
     ]
 
 

@@ -54,6 +54,7 @@ struct BwdArgs {
   float cg;               // 2*w_data / normaliser
   float cpose;            // 2*w_pose / (F*207)
   float d0;
+  float rs2;              // robust_sigma^2 of the Geman-McClure data term (ROBUST instantiations only; extension)
   // outputs
   uuo_gptr<float> g_pose;
   uuo_gptr<float> g_root;
@@ -249,6 +250,9 @@ __device__ unsigned long long g_bwd_stamps[4096 * BWD_NSTAMP];
 #else
 #define BWD_STAMP(i) do {} while (0)
 #endif
+// EXTENSION: the Geman-McClure weight of a data item's square s (SMPLify's GMoF): rho(s) = s q, rho'(s) = q^2
+__device__ __forceinline__ float gmof_q(float sig2, float s) { return sig2 / (sig2 + s); }
+
 #define BWD_NW 4  // waves per frame block: one per SIMD, so up to three blocks share a CU at 168 VGPRs.  (6 waves -- 24 item
                   // slots, 3 rounds for M = 50 instead of 4 -- place 2,2,1,1 waves on the SIMDs and a second block no longer
                   // fits at 3 waves per SIMD: 300 blocks then run in two rounds on 256 CUs, 24.8 -> 38.5 us.  8 waves need
@@ -282,8 +286,12 @@ __device__ unsigned long long g_bwd_stamps[4096 * BWD_NSTAMP];
 // instantiation, so that the sparse kernel of the fitted stages keeps its register allocation (168 VGPRs, no spill)
 // ITEMS (general kernel only): the items are (vertex, upstream gradient) pairs handed over by another kernel; another separate
 // instantiation, for the same reason
-template <bool PART = false, int NWV = BWD_NW, bool DENSE = false, bool ITEMS = false>
+// ROBUST (EXTENSION, uuo_problem_t.robust_sigma > 0): every data item's square s enters as the Geman-McClure term
+// rho(s) = s q, d rho / d s = q^2 with q = sigma^2 / (sigma^2 + s) (gmof_q); instantiated separately so that the plain kernels
+// keep their code and register allocation
+template <bool PART = false, int NWV = BWD_NW, bool DENSE = false, bool ITEMS = false, bool ROBUST = false>
 __device__ __forceinline__ void bwd_body(const BwdArgs& a) {
+  static_assert(!ROBUST || (!DENSE && !ITEMS), "the robust data term is formed on the sparse items (k_bary_fwd for item mode)");
   static_assert(!(PART && DENSE), "the part stage's dense sums come through the runtime `pre` pointer");
   static_assert(!ITEMS || (!PART && !DENSE), "item mode belongs to the general sparse kernel");
   static_assert(NWV == BWD_NW || (PART && NWV == 1), "one-wave blocks exist for the part stage only");
@@ -529,12 +537,24 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a) {
       } else if (a.stage == UUO_STAGE_MARKER) {
         const float rr = sqrtf((dx * dx + dy * dy) + dz * dz);
         const float e = rr - a.d0;
-        loss_item = wgt * (e * e);
-        const float sc = (rr > 0.f) ? (-a.cg * wgt * e / rr) : 0.f;
+        float lw = wgt, gw = wgt;  // weights of the loss and of its gradient (the plain square: both the mask)
+        if constexpr (ROBUST) {
+          const float q = gmof_q(a.rs2, e * e);
+          lw = wgt * q;
+          gw = wgt * (q * q);
+        }
+        loss_item = lw * (e * e);
+        const float sc = (rr > 0.f) ? (-a.cg * gw * e / rr) : 0.f;
         g[0] = sc * dx; g[1] = sc * dy; g[2] = sc * dz;
       } else {
-        loss_item = wgt * d2;
-        const float sc = -a.cg * wgt;
+        float lw = wgt, gw = wgt;
+        if constexpr (ROBUST) {  // (d2 is the search's distance: the one that picked the vertex)
+          const float q = gmof_q(a.rs2, d2);
+          lw = wgt * q;
+          gw = wgt * (q * q);
+        }
+        loss_item = lw * d2;
+        const float sc = -a.cg * gw;
         g[0] = sc * dx; g[1] = sc * dy; g[2] = sc * dz;
       }
       float dvp[3];
@@ -884,6 +904,14 @@ __global__ __launch_bounds__(BWD_NW * 64) __attribute__((amdgpu_waves_per_eu(3, 
   UUO_BATCH_PICK(BwdArgs, batch)
   bwd_body<false>(a);
 }
+// EXTENSION: the same with the Geman-McClure data term (uuo_problem_t.robust_sigma > 0)
+__global__ __launch_bounds__(BWD_NW * 64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_bwd_sparse_r(BwdArgs a) {
+  bwd_body<false, BWD_NW, false, false, true>(a);
+}
+__global__ __launch_bounds__(BWD_NW * 64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_bwd_sparse_b_r(const BwdArgs* __restrict__ batch) {
+  UUO_BATCH_PICK(BwdArgs, batch)
+  bwd_body<false, BWD_NW, false, false, true>(a);
+}
 // the kinematic tail alone, on the sums of a dense backward (dense_bwd.hip)
 __global__ __launch_bounds__(BWD_NW * 64) void k_bwd_dense(BwdArgs a) { bwd_body<false, BWD_NW, true>(a); }
 // the sparse kernel on (vertex, upstream gradient) items (the marker stage on a three-corner placement, k_bary_fwd before it)
@@ -907,11 +935,14 @@ struct BaryFwdArgs {
   uuo_gptr<const int> assign3;   // [M][3]
   uuo_gptr<const float> bary;    // [M][3]
   float cg, d0;
+  float rs2;                     // robust_sigma^2 (k_bary_fwd_r only; extension)
   uuo_gptr<float> frames;        // [F][FrameLds]: left for k_bwd_items of the same evaluation
   uuo_gptr<float> up_items;      // [F][3 M][3]
   uuo_gptr<float> item_loss;     // [F]
 };
-__global__ __launch_bounds__(BWD_NW * 64) void k_bary_fwd(BaryFwdArgs a) {
+// ROBUST (EXTENSION): the term is w rho((|x - vm| - d0)^2), Geman-McClure (gmof_q); a separate instantiation, k_bary_fwd_r
+template <bool ROBUST>
+__device__ __forceinline__ void bary_fwd_body(const BaryFwdArgs& a) {
   constexpr int NT = BWD_NW * 64, SLOTS = BWD_NW * 4;
   __shared__ FrameLds L;
   __shared__ float sA[UUO_NUM_JOINTS * 12];
@@ -1005,8 +1036,14 @@ __global__ __launch_bounds__(BWD_NW * 64) void k_bary_fwd(BaryFwdArgs a) {
     const float dx = px[0] - vm[0], dy = px[1] - vm[1], dz = px[2] - vm[2];
     const float rr = sqrtf((dx * dx + dy * dy) + dz * dz);
     const float e = rr - a.d0;
-    acc_loss += wgt * (e * e);
-    const float sc = (rr > 0.f) ? (-a.cg * wgt * e / rr) : 0.f;
+    float lw = wgt, gw = wgt;
+    if constexpr (ROBUST) {
+      const float q = gmof_q(a.rs2, e * e);
+      lw = wgt * q;
+      gw = wgt * (q * q);
+    }
+    acc_loss += lw * (e * e);
+    const float sc = (rr > 0.f) ? (-a.cg * gw * e / rr) : 0.f;
     if (in && sl < 9) {  // sub-lane 3 k + c writes component c of corner k's item
       const int k = sl / 3, c = sl - 3 * k;
       const float gc = sc * ((c == 0) ? dx : ((c == 1) ? dy : dz));
@@ -1022,6 +1059,8 @@ __global__ __launch_bounds__(BWD_NW * 64) void k_bary_fwd(BaryFwdArgs a) {
     a.item_loss[f] = t;
   }
 }
+__global__ __launch_bounds__(BWD_NW * 64) void k_bary_fwd(BaryFwdArgs a) { bary_fwd_body<false>(a); }
+__global__ __launch_bounds__(BWD_NW * 64) void k_bary_fwd_r(BaryFwdArgs a) { bary_fwd_body<true>(a); }
 // part stage on its cached pose blend: a fraction of the registers and two thirds of the LDS of the general kernel
 // two forms: one wave per frame for <= 16 markers (the candidate search: four items per pass), four waves per frame above
 // that (hmr_full.yaml: 50 markers on the full skeleton would be 13 passes of one wave)
@@ -1034,6 +1073,17 @@ __global__ __launch_bounds__(BWD_NW * 64) void k_bwd_part(BwdArgs a) { bwd_body<
 __global__ __launch_bounds__(BWD_NW * 64) void k_bwd_part_b(const BwdArgs* __restrict__ batch) {
   UUO_BATCH_PICK(BwdArgs, batch)
   bwd_body<true>(a);
+}
+// EXTENSION: the four part-stage forms with the Geman-McClure data term
+__global__ __launch_bounds__(64) void k_bwd_part1_r(BwdArgs a) { bwd_body<true, 1, false, false, true>(a); }
+__global__ __launch_bounds__(64) void k_bwd_part1_b_r(const BwdArgs* __restrict__ batch) {
+  UUO_BATCH_PICK(BwdArgs, batch)
+  bwd_body<true, 1, false, false, true>(a);
+}
+__global__ __launch_bounds__(BWD_NW * 64) void k_bwd_part_r(BwdArgs a) { bwd_body<true, BWD_NW, false, false, true>(a); }
+__global__ __launch_bounds__(BWD_NW * 64) void k_bwd_part_b_r(const BwdArgs* __restrict__ batch) {
+  UUO_BATCH_PICK(BwdArgs, batch)
+  bwd_body<true, BWD_NW, false, false, true>(a);
 }
 
 __global__ __launch_bounds__(1024) void k_finalize(FinArgs a) { finalize_body<1024, false>(a); }
@@ -1051,6 +1101,13 @@ int uuo_batched_launch_closure(int op, hipStream_t s, const void* d_args, int co
       hipLaunchKernelGGL(k_bwd_part1_b, dim3(gx, 1, count), dim3(64), 0, s, (const BwdArgs*)d_args);
     else
       hipLaunchKernelGGL(k_bwd_part_b, dim3(gx, 1, count), dim3(BWD_NW * 64), 0, s, (const BwdArgs*)d_args);
+  } else if (op == UUO_OP_BWD_R) {
+    hipLaunchKernelGGL(k_bwd_sparse_b_r, dim3(gx, gy, count), dim3(BWD_NW * 64), 0, s, (const BwdArgs*)d_args);
+  } else if (op == UUO_OP_BWD_PART_R) {
+    if (gy == 1)
+      hipLaunchKernelGGL(k_bwd_part1_b_r, dim3(gx, 1, count), dim3(64), 0, s, (const BwdArgs*)d_args);
+    else
+      hipLaunchKernelGGL(k_bwd_part_b_r, dim3(gx, 1, count), dim3(BWD_NW * 64), 0, s, (const BwdArgs*)d_args);
   } else if (op == UUO_OP_FIN) {
     hipLaunchKernelGGL(k_finalize_b, dim3(gx, gy, count), dim3(1024), 0, s, (const FinArgs*)d_args);
   } else {
@@ -1124,6 +1181,13 @@ static int validate_problem(const uuo_fit* fit, const uuo_problem_t* p) {
   UUO_REQUIRE(p->w_soft == 0.f || (p->soft_tau > 0.f && p->stage != UUO_STAGE_MARKER), "closure: w_soft (soft-assignment data term, extension) needs soft_tau > 0 and the chamfer or part stage");
   UUO_REQUIRE(p->w_soft == 0.f || p->stage != UUO_STAGE_PART || (p->pose_cache_id != 0 && p->M <= 16),
               "closure: the part stage's soft-assignment term needs a pose cache id and M <= 16");
+  {  // EXTENSION: Geman-McClure data terms; sigma^2 must be a positive finite fp32 number for the kernels' q = sigma^2 / (sigma^2 + s)
+    const float sg = p->robust_sigma, sg2 = sg * sg;
+    UUO_REQUIRE(sg == 0.f || (sg > 0.f && sg2 > 0.f && sg2 <= 3.0e38f),
+                "closure: robust_sigma (Geman-McClure data term, extension) must be 0 (off) or a positive finite number of metres "
+                "whose square is a normal fp32 value");
+    UUO_REQUIRE(sg == 0.f || p->w_soft == 0.f, "closure: robust_sigma is not built for the soft-assignment data term (w_soft)");
+  }
   return 0;
 }
 
@@ -1505,6 +1569,9 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
   a.cg = (float)(2.0 * data_c);
   a.cpose = (p->stage == UUO_STAGE_PART) ? 0.f : (float)(2.0 * (double)p->w_pose / ((double)F * 207.0));
   a.d0 = p->marker_distance;
+  // EXTENSION: Geman-McClure data terms run on the *_r instantiations (validate_problem: sigma^2 is a normal fp32 value)
+  const bool robust = p->robust_sigma > 0.f;
+  a.rs2 = robust ? (float)((double)p->robust_sigma * (double)p->robust_sigma) : 0.f;
   a.g_pose = (p->stage == UUO_STAGE_PART) ? nullptr : d_grad + gl.off_pose;
   a.g_root = (p->stage == UUO_STAGE_MARKER) ? d_grad + gl.off_root : nullptr;
   a.g_z = (p->stage == UUO_STAGE_CHAMFER) ? d_grad + gl.off_z : nullptr;
@@ -1544,7 +1611,14 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
     a.C = fit->pose_cache;
     a.pre = soft ? fit->soft_pre : nullptr;
     const int waves = M <= 16 ? 1 : BWD_NW;
-    if (!uuo_record(UUO_OP_BWD_PART, F, waves, a)) {
+    if (robust) {
+      if (!uuo_record(UUO_OP_BWD_PART_R, F, waves, a)) {
+        if (waves == 1)
+          hipLaunchKernelGGL(k_bwd_part1_r, dim3(F), dim3(64), 0, s, a);
+        else
+          hipLaunchKernelGGL(k_bwd_part_r, dim3(F), dim3(BWD_NW * 64), 0, s, a);
+      }
+    } else if (!uuo_record(UUO_OP_BWD_PART, F, waves, a)) {
       if (waves == 1)
         hipLaunchKernelGGL(k_bwd_part1, dim3(F), dim3(64), 0, s, a);
       else
@@ -1568,10 +1642,14 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
     b.bary = p->d_bary;
     b.cg = a.cg;
     b.d0 = p->marker_distance;
+    b.rs2 = a.rs2;
     b.frames = fit->frames;
     b.up_items = items;
     b.item_loss = item_loss;
-    hipLaunchKernelGGL(k_bary_fwd, dim3(F), dim3(BWD_NW * 64), 0, s, b);
+    if (robust)
+      hipLaunchKernelGGL(k_bary_fwd_r, dim3(F), dim3(BWD_NW * 64), 0, s, b);
+    else
+      hipLaunchKernelGGL(k_bary_fwd, dim3(F), dim3(BWD_NW * 64), 0, s, b);
     a.M = 3 * M;
     a.up_items = items;
     a.item_loss = item_loss;
@@ -1603,7 +1681,11 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
       a.fin_counter = reinterpret_cast<unsigned*>(fit->scalars + 32);
       fin_fused = true;
     }
-    if (!uuo_record(UUO_OP_BWD, F, 1, a)) hipLaunchKernelGGL(k_bwd_sparse, dim3(F), dim3(BWD_NW * 64), 0, s, a);
+    if (robust) {
+      if (!uuo_record(UUO_OP_BWD_R, F, 1, a)) hipLaunchKernelGGL(k_bwd_sparse_r, dim3(F), dim3(BWD_NW * 64), 0, s, a);
+    } else if (!uuo_record(UUO_OP_BWD, F, 1, a)) {
+      hipLaunchKernelGGL(k_bwd_sparse, dim3(F), dim3(BWD_NW * 64), 0, s, a);
+    }
   }
   UUO_HIP_CHECK(hipGetLastError());
   if (!fin_fused) {

@@ -331,6 +331,8 @@ enum {
   UUO_OP_NN_CULL,
   UUO_OP_BWD,
   UUO_OP_BWD_PART,         // k_bwd_part: the part stage on its cached pose blend
+  UUO_OP_BWD_R,            // EXTENSION: k_bwd_sparse / k_bwd_part with the Geman-McClure data term (robust_sigma > 0)
+  UUO_OP_BWD_PART_R,
   UUO_OP_FIN,
   UUO_OP_COUNT
 };

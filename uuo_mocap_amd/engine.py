@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import itertools
+import math
 import threading
 from collections import OrderedDict
 from ctypes import byref, c_float, c_void_p
@@ -589,6 +590,21 @@ class _StageProblem:
         return float(ms.value)
 
 
+def stage_robust_sigma(config: Dict, stage: str) -> float:
+    """EXTENSION: stages.<stage>.robust_sigma (metres) of a config -- the Geman-McClure data term of the stage
+    (uuo_problem_t.robust_sigma).  Absent or 0 = off (the reference's square); negative or non-finite values are refused, and so
+    is a robust term together with the soft-assignment term `soft_chamfer`, which has no robust form."""
+    st = config["stages"][stage]
+    v = st.get("robust_sigma", 0.0)
+    v = 0.0 if v is None else float(v)
+    if not math.isfinite(v) or v < 0.0:
+        raise ValueError("stages.%s.robust_sigma must be 0 (off) or a positive number of metres (got %r)" % (stage, v))
+    if v > 0.0 and float((st.get("losses") or {}).get("soft_chamfer", 0.0)) != 0.0:
+        raise NotImplementedError("stages.%s: robust_sigma (Geman-McClure data term) is not built for the soft-assignment "
+                                  "term soft_chamfer; use one or the other" % stage)
+    return v
+
+
 def _cfg_weights(losses: Dict, data_key: str):
     return (float(losses.get(data_key, 0.0)), float(losses.get("reg_pose_body", 0.0)),
             float(losses.get("reg_betas", 0.0)))
@@ -607,7 +623,9 @@ class ChamferProblem(_StageProblem):
         if not config["stages"]["chamfer"]["yaw_lock"]:
             raise NotImplementedError("stages.chamfer.yaw_lock False is not a shipped configuration")
         wd, wp, wb = _cfg_weights(losses, "full_chamfer")
+        sigma = stage_robust_sigma(config, "chamfer")
         super().__init__(smpl_inference.device_model, markers, o_pose_body, o_betas, root_orient, wd, wp, wb)
+        self.problem.robust_sigma = sigma  # EXTENSION: Geman-McClure data term (0 = off)
         # EXTENSION (not in the reference): soft assignment of every marker to the body's vertices, fused closure with the dense
         # backward on the matrix pipe (csrc/dense_bwd.hip); not available inside lock-step batches
         w_soft = float(losses.get("soft_chamfer", 0.0))
@@ -642,7 +660,9 @@ class MarkerProblem(_StageProblem):
         if st.get("use_sdf"):
             raise NotImplementedError("stages.marker.use_sdf is off in every shipped config")
         wd, wp, wb = _cfg_weights(st["losses"], "marker")
+        sigma = stage_robust_sigma(config, "marker")
         super().__init__(smpl_inference.device_model, markers, o_pose_body, o_betas, None, wd, wp, wb, assign=assign)
+        self.problem.robust_sigma = sigma  # EXTENSION: Geman-McClure data term (0 = off)
         if bary is not None:
             if self.assign.dim() != 2 or tuple(self.assign.shape) != (self.M, 3) or tuple(bary.shape) != (self.M, 3):
                 raise ValueError("a three-corner placement takes assign [M, 3] and bary [M, 3]")
@@ -678,11 +698,13 @@ class PartProblem(_StageProblem):
         unsupported = set(losses) - {"chamfer", "reg_betas", "soft_chamfer"}
         if unsupported:
             raise NotImplementedError("part-stage losses outside the shipped configs: %s" % sorted(unsupported))
+        sigma = stage_robust_sigma(config, "part")
         super().__init__(smpl_inference.device_model, markers, pose_body, o_betas, root_orient,
                          float(losses.get("chamfer", 0.0)), 0.0, float(losses.get("reg_betas", 0.0)),
                          subset=vertex_indices, own_workspace=own_workspace)
         # the body pose is a constant of this problem: let the library compute its pose-corrective blend once
         self.problem.pose_cache_id = next(_POSE_CACHE_IDS)
+        self.problem.robust_sigma = sigma  # EXTENSION: Geman-McClure data term (0 = off)
         # EXTENSION (not in the reference): soft assignment of every marker to the candidate's vertices, fused (k_part_soft)
         w_soft = float(losses.get("soft_chamfer", 0.0))
         if w_soft != 0.0:

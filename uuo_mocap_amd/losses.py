@@ -137,3 +137,44 @@ def MarkerLoss(markers, virtual_markers, marker_weights, marker_distance):
     """[F,M] squared deviation of the marker-to-skin distance from `marker_distance`, masked."""
     gap = torch.norm(markers - virtual_markers, dim=-1) - marker_distance
     return gap ** 2 * marker_weights
+
+
+def gmof(s: torch.Tensor, sigma: float) -> torch.Tensor:
+    """EXTENSION, not reference behaviour: the Geman-McClure term of SMPLify's GMoF on a squared residual s (sigma in metres),
+    rho(s) = s sigma^2 / (sigma^2 + s): ~ s for s << sigma^2, bounded by sigma^2.  sigma = 0 returns s unchanged (the
+    reference's square).  What the fused closures apply per data item (uuo_problem_t.robust_sigma)."""
+    if not sigma:
+        return s
+    sig2 = float(sigma) * float(sigma)
+    return s * (sig2 / (sig2 + s))
+
+
+def gmof_grad(s: torch.Tensor, sigma: float) -> torch.Tensor:
+    """d gmof / d s = (sigma^2 / (sigma^2 + s))^2 (1 for sigma = 0)."""
+    if not sigma:
+        return torch.ones_like(s)
+    sig2 = float(sigma) * float(sigma)
+    return (sig2 / (sig2 + s)) ** 2
+
+
+def robust_weighted_chamfer_distance(x: torch.Tensor, y: torch.Tensor, x_weights: torch.Tensor, sigma: float):
+    """EXTENSION: `weighted_chamfer_distance` with every marker's squared nearest-vertex distance d passed through gmof."""
+    d, _ = knn_points_k1(x, y)
+    w = x_weights.to(d.dtype) if x_weights.dtype != d.dtype else x_weights
+    wsum = x_weights.sum()
+    if wsum == 0.0:
+        return (x.sum() * 0.0), None
+    return (gmof(d, sigma) * w).sum() / wsum, None
+
+
+def robust_chamfer_distance(x: torch.Tensor, y: torch.Tensor, sigma: float):
+    """EXTENSION: the part stage's one-directional `chamfer_distance(x, y, single_directional=True)` (mean over the clouds of
+    the mean over the points, unmasked) with every squared nearest-vertex distance passed through gmof."""
+    d, _ = knn_points_k1(x, y)                          # [N, P1]
+    return gmof(d, sigma).sum(1).div(float(max(x.shape[1], 1))).sum() / float(max(x.shape[0], 1)), None
+
+
+def RobustMarkerLoss(markers, virtual_markers, marker_weights, marker_distance, sigma: float):
+    """EXTENSION: `MarkerLoss` with the squared deviation passed through gmof."""
+    gap = torch.norm(markers - virtual_markers, dim=-1) - marker_distance
+    return gmof(gap ** 2, sigma) * marker_weights

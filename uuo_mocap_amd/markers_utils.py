@@ -17,8 +17,8 @@ import torch
 
 from .body_model import SMPL_JOINT_NAMES
 from .device_lbfgs import DeviceLBFGS
-from .engine import _f32, PART_SOFT_MAX_MARKERS, PartProblem, set_workspace_group, set_workspace_slot, worker_pool, worker_streams, workspace_group
-from .losses import chamfer_distance, soft_chamfer_distance
+from .engine import _f32, PART_SOFT_MAX_MARKERS, PartProblem, set_workspace_group, stage_robust_sigma, set_workspace_slot, worker_pool, worker_streams, workspace_group
+from .losses import chamfer_distance, robust_chamfer_distance, soft_chamfer_distance
 from .transforms import compute_root_orient_z
 
 LAST_STATS: Dict[str, list] = {}
@@ -27,7 +27,8 @@ LAST_STATS: Dict[str, list] = {}
 # multimodal_video_mocap.  These were environment variables in round 2: the product path reads no environment now.
 EXECUTION_DEFAULTS = {"subtree_lockstep": True, "subtree_batch": 256, "subtree_threads": 4,
                       "hypothesis_lockstep": False, "hypothesis_threads": 4, "batch_trivial_hypotheses": True,
-                      "part_soft_fused": True, "chamfer_soft_fused": True, "marker_bary_fused": True}
+                      "part_soft_fused": True, "chamfer_soft_fused": True, "marker_bary_fused": True,
+                      "robust_fused": True}
 
 
 def merge_execution(config: Dict, execution: Dict = None) -> Dict:
@@ -257,6 +258,10 @@ def find_best_part_fits(
     # terms and the candidate markers fit its instantiations; execution["part_soft_fused"] = False keeps the operator-composed
     # closure (the fused one's checker)
     soft_fused = extra == {"soft_chamfer"} and markers.is_cuda and bool(exe["part_soft_fused"])
+    # EXTENSION: Geman-McClure data term (stages.part.robust_sigma > 0) -- the fused part closures carry it; candidate SELECTION
+    # below keeps the reference's plain two-directional chamfer score.  execution["robust_fused"] = False composes it (checker).
+    sigma = stage_robust_sigma(config, "part")
+    robust_composed = sigma > 0.0 and not bool(exe["robust_fused"])
     if not any(float(st["losses"].get(k, 0.0)) != 0.0 for k in ("chamfer", "soft_chamfer")):
         raise ValueError("the part stage needs a data term: stages.part.losses.chamfer (reference) or soft_chamfer (extension)")
     if "reproject" in extra and any(v is None for v in (joints_2d_gt, focal_length, reproject_mask, camera_center,
@@ -385,7 +390,9 @@ def find_best_part_fits(
                 z_root_c, out = forward()
                 verts_sub = out["vertices"][:, vertex_indices].contiguous()
                 loss = 0
-                if float(st["losses"].get("chamfer", 0.0)) != 0.0:  # (a child config switches the hard term off with weight 0)
+                if float(st["losses"].get("chamfer", 0.0)) != 0.0 and sigma > 0.0:  # EXTENSION: the robust term, composed
+                    loss = loss + robust_chamfer_distance(markers_subset, verts_sub, sigma)[0] * st["losses"]["chamfer"]
+                elif float(st["losses"].get("chamfer", 0.0)) != 0.0:  # (a child config switches the hard term off with weight 0)
                     loss = loss + chamfer_distance(markers_subset, verts_sub, single_directional=True)[0] * st["losses"]["chamfer"]
                 if float(st["losses"].get("soft_chamfer", 0.0)) != 0.0:  # EXTENSION: soft assignment of every marker to the candidate's vertices
                     loss = loss + soft_chamfer_distance(markers_subset, verts_sub, float(st.get("soft_tau", 2.5e-4)))[0] * \
@@ -454,13 +461,14 @@ def find_best_part_fits(
                 out.append({"stats": stt, "distance": dval, "x": xs[c0 + k], "prob": probs[c0 + k]})
         return out
 
-    if extra:
+    general = bool(extra) or robust_composed
+    if general:
         fit_subtree = fit_subtree_general
 
     n_threads = min(len(subtrees), max(1, int(exe["subtree_threads"])))
-    if extra:
+    if general:
         n_threads = 1  # autograd graphs of concurrent candidates would share the engine's forward scratch
-    lockstep = (not extra and iter_fn is None and device.type == "cuda" and len(subtrees) > 1
+    lockstep = (not general and iter_fn is None and device.type == "cuda" and len(subtrees) > 1
                 and bool(exe["subtree_lockstep"]))
     if lockstep:
         results = fit_subtrees_lockstep()

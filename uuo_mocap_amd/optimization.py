@@ -12,9 +12,9 @@ import torch
 import torch.nn.functional as F
 
 from .device_lbfgs import DeviceLBFGS
-from .engine import MARKER_DISTANCE, ChamferProblem, MarkerProblem
-from .losses import (MarkerLoss, chamfer_distance, soft_weighted_chamfer_distance,  # noqa: F401  (re-exported)
-                     weighted_chamfer_distance)
+from .engine import MARKER_DISTANCE, ChamferProblem, MarkerProblem, stage_robust_sigma
+from .losses import (MarkerLoss, RobustMarkerLoss, chamfer_distance, robust_weighted_chamfer_distance,  # noqa: F401  (re-exported)
+                     soft_weighted_chamfer_distance, weighted_chamfer_distance)
 from .smpl import SmplInference
 from .transforms import compute_root_orient_y, compute_root_orient_z, normalize_rot  # noqa: F401
 
@@ -65,7 +65,7 @@ def optim_chamfer(
         # EXTENSION: the soft-assignment data term has a fused closure (dense backward on the matrix pipe, csrc/dense_bwd.hip);
         # execution.chamfer_soft_fused: False keeps the operator-composed closure, its checker
         fused_losses = _CHAMFER_FUSED_LOSSES | {"soft_chamfer"}
-    if (set(st["losses"]) - fused_losses) or not st["yaw_lock"]:
+    if (set(st["losses"]) - fused_losses) or not st["yaw_lock"] or not _robust_fused(config, "chamfer"):
         return _optim_chamfer_general(markers, pose_body, o_pose_body, betas, o_betas, root_orient, trans, marker_labels,
                                       smpl_inference, config, initial_angle, repeat, verbose, iter_fn)
     from .parallel import frame_shard
@@ -169,11 +169,19 @@ def _optim_markers_frame_sharded(fs, markers, pose_body, o_pose_body, betas, o_b
     return None
 
 
+def _robust_fused(config: Dict, stage: str) -> bool:
+    """False when the stage's EXTENSION Geman-McClure data term (stages.<stage>.robust_sigma > 0) is to run on the closure
+    composed from the operators (execution.robust_fused: False, the fused closures' checker); True otherwise."""
+    return stage_robust_sigma(config, stage) == 0.0 or bool((config.get("execution") or {}).get("robust_fused", True))
+
+
 def lockstep_supported(config: Dict, stage: str) -> bool:
     """True when `stage` ("chamfer" / "marker") of this configuration runs on the fused device closure with the L-BFGS
     driver, i.e. when independent solves of it can be stepped together (engine.solve_batch)."""
     st = config["stages"][stage]
     if str(config["optimizer"].get("type", "lbfgs")).lower() != "lbfgs":
+        return False
+    if not _robust_fused(config, stage):
         return False
     if stage == "chamfer":
         return not (set(st["losses"]) - _CHAMFER_FUSED_LOSSES) and bool(st["yaw_lock"])
@@ -290,6 +298,7 @@ def _optim_chamfer_general(markers, pose_body, o_pose_body, betas, o_betas, root
     unknown = set(w) - _CHAMFER_FUSED_LOSSES - {"part_chamfer", "trans_vel", "ground", "soft_chamfer"}
     if unknown:
         raise NotImplementedError("chamfer-stage losses that cannot run in the reference: %s" % sorted(unknown))
+    sigma = stage_robust_sigma(config, "chamfer")  # EXTENSION: Geman-McClure data term (0 = the reference's square)
     device = root_orient.device
     num_frames = pose_body.shape[0]
     root_fixed = root_orient.detach().clone()
@@ -318,7 +327,9 @@ def _optim_chamfer_general(markers, pose_body, o_pose_body, betas, o_betas, root
         if "part_chamfer" in w:
             loss = loss + chamfer_distance_by_part(markers, out["vertices"], marker_labels, lbs_weights,
                                                    single_directional=st["single_directional"]) * w["part_chamfer"]
-        if "full_chamfer" in w:
+        if "full_chamfer" in w and sigma > 0.0:  # EXTENSION: the fused closures' robust term, composed (their checker)
+            loss = loss + robust_weighted_chamfer_distance(markers, out["vertices"], mask, sigma)[0] * w["full_chamfer"]
+        elif "full_chamfer" in w:
             loss = loss + weighted_chamfer_distance(x=markers, y=out["vertices"], x_weights=mask,
                                                     single_directional=st["single_directional"])[0] * w["full_chamfer"]
         if "soft_chamfer" in w:  # EXTENSION (not in the reference): soft-assignment data term, temperature stages.chamfer.soft_tau
@@ -387,6 +398,9 @@ def optim_markers(
     fs = frame_shard()
     sharded = fs is not None and fs.active
     bary = None
+    if not _robust_fused(config, "marker"):  # EXTENSION: execution.robust_fused: False -- the composed closure, the fused one's checker
+        return _optim_markers_general(markers, pose_body, o_pose_body, betas, o_betas, root_orient, trans, one_hot,
+                                      smpl_inference, config, verbose, iter_fn, initial_angle, repeat)
     if not bool(((rows_nz == 1) & (one_hot.sum(dim=1) == 1.0)).all()):
         # barycentric placement (compute_locations.use_barycentric): up to three weighted vertices per marker.  Fused closure
         # (k_bary_fwd + k_bwd_items) when it is that and nothing else; execution.marker_bary_fused: False, more than three
@@ -435,6 +449,7 @@ def _optim_markers_general(markers, pose_body, o_pose_body, betas, o_betas, root
         raise NotImplementedError("marker-stage losses outside the shipped configs: %s" % sorted(unsupported))
     if st.get("use_sdf"):
         raise NotImplementedError("stages.marker.use_sdf is off in every shipped config")
+    sigma = stage_robust_sigma(config, "marker")  # EXTENSION: Geman-McClure data term (0 = the reference's square)
     num_frames = pose_body.shape[0]
     leaves = [pose_body, betas, root_orient, trans]
     params = [p.detach().clone().requires_grad_(True) for p in leaves]
@@ -453,7 +468,10 @@ def _optim_markers_general(markers, pose_body, o_pose_body, betas, o_betas, root
                              root_orient=normalize_rot(p_root), trans=p_trans)
         virtual = torch.einsum("mv,fvc->fmc", coords, out["vertices"])
         loss = 0
-        if "marker" in st["losses"]:
+        if "marker" in st["losses"] and sigma > 0.0:
+            loss = loss + torch.mean(RobustMarkerLoss(markers=markers, virtual_markers=virtual, marker_weights=weights,
+                                                      marker_distance=MARKER_DISTANCE, sigma=sigma)) * st["losses"]["marker"]
+        elif "marker" in st["losses"]:
             loss = loss + torch.mean(MarkerLoss(markers=markers, virtual_markers=virtual, marker_weights=weights,
                                                 marker_distance=MARKER_DISTANCE)) * st["losses"]["marker"]
         if "reg_pose_body" in st["losses"]:

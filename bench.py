@@ -10,6 +10,11 @@ Sequences are independent in the reference (one call per sequence, own betas), s
 with no data-path collective (weak scaling: every rank fits K sequences); the only collectives are the
 timing barrier and a max-reduce of the elapsed time.  One JSON line is printed by rank 0; its `ms_per_step` is the
 wall time of one timed step.  `--dump-outputs DIR` writes the arrays the last timed fit returned to DIR/<name>.npy.
+
+A plain run does what the headline needs and nothing else: set-up, warm-up, the timed steps, the dump, the line.  `--full`
+adds everything else the benchmark measures or checks after the timed steps: fit quality against the synthetic ground truth,
+the roofline of the dominant kernel, the latency of one sequence alone, the other shipped configurations and the CPU baseline
+(`--no-other-configs` / `--no-cpu-baseline` leave those two out of a --full run).
 """
 from __future__ import annotations
 
@@ -72,15 +77,20 @@ def parse():
                          "flight); 0: the solver's host threads always spin while they wait for the GPU's reports; > 0: they "
                          "spin --wait-spin-us and then sleep this long at a time (parallel.set_wait_policy)")
     ap.add_argument("--wait-spin-us", type=float, default=10.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check what the headline does not need: fit_quality, "
+                         "roofline, latency_one_sequence, other_configs, cpu_baseline (several minutes); a plain run reports "
+                         "the timed steps alone")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the cpu_baseline leg")
     ap.add_argument("--roofline-only", action="store_true",
                     help="only the timing loops of the roofline section (one warm-up fit): the command profiled into "
                          "profiles/r1_roofline_kernel_stats.csv")
-    ap.add_argument("--cpu-evals", type=int, default=20, help="closure evaluations per stage type timed on the CPU")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the hmr_full / hmr_part / mht_rotation legs")
+    ap.add_argument("--cpu-evals", type=int, default=20, help="closure evaluations per stage type timed on the CPU (--full)")
+    ap.add_argument("--no-other-configs", action="store_true",
+                    help="--full without the hmr_full / hmr_part / mht_rotation / soft legs")
     ap.add_argument("--soft-operator-fit", action="store_true",
-                    help="also time ONE hmr_part_soft fit on the operator-composed closure (the fused soft closure's checker; "
-                         "~20 s): other_configs.hmr_part_soft.operator_composed_ms_per_step")
+                    help="with --full, also time ONE hmr_part_soft fit on the operator-composed closure (the fused soft "
+                         "closure's checker; ~20 s): other_configs.hmr_part_soft.operator_composed_ms_per_step")
     ap.add_argument("--mode", default="sequences", choices=["sequences", "hypotheses", "shared_betas", "frames"],
                     help="how N ranks share the work (SURVEY.md 8e): sequences = independent sequences per rank, no data-path "
                          "collective (default; weak scaling); hypotheses = every step is ONE sequence whose yaw hypotheses "
@@ -364,6 +374,20 @@ def packaged_cfg_full():
     return packaged_config("video_mocap")
 
 
+def host_map(fn, items):
+    """[fn(x) for x in items] on a pool of host threads, one per CPU of this rank's share of the quota.  For the synthetic
+    sequences: make_sequence spends 1-2 s per 300-frame sequence in numpy einsum, which releases the GIL, and depends on its
+    arguments alone, so the pool returns the same sequences, in order, in a fraction of the time."""
+    from concurrent.futures import ThreadPoolExecutor
+
+    from uuo_mocap_amd.parallel import host_cpu_budget
+
+    items = list(items)
+    local_world = max(1, int(os.environ.get("LOCAL_WORLD_SIZE", "1")))  # torchrun: the ranks of this host share the quota
+    with ThreadPoolExecutor(max(1, min(len(items), host_cpu_budget() // local_world))) as pool:
+        return list(pool.map(fn, items))
+
+
 def main():
     global MODE, LANES, TRANSPORT
     args = parse()
@@ -424,9 +448,9 @@ def main():
     # the data: a timed step must not repeat a warm-up step)
     seed_base = 0 if MODE in ("hypotheses", "frames") else rank * n_seq   # these modes: all ranks work on the SAME sequences
     # shared_betas mode: step i of every rank is a different sequence of ONE subject (same ground-truth shape)
-    seqs = [make_sequence(tables, seed=seed_base + i, num_frames=F, num_markers=10 if limb else M, limb_only=limb,
-                          subject_seed=(5000 + i) if MODE == "shared_betas" else None)
-            for i in range(n_seq)]
+    seqs = host_map(lambda i: make_sequence(tables, seed=seed_base + i, num_frames=F, num_markers=10 if limb else M,
+                                            limb_only=limb, subject_seed=(5000 + i) if MODE == "shared_betas" else None),
+                    range(n_seq))
 
     if args.roofline_only:
         # no fit: the dominant kernel and the chamfer closure alone on an idle GPU (the command behind
@@ -474,16 +498,17 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    # fit quality of every timed step of this rank against the synthetic ground truth (outside the timed region)
-    quality = [fit_quality(smpl, sq, out, dev) for sq, (out, _) in zip(seqs[args.warmup:n_seq], fits)]
-    q_mean = {k: float(np.mean([q[k] for q in quality])) for k in quality[0]}
-    q_worst = {k: float(np.max([q[k] for q in quality])) for k in quality[0]}
-    if world > 1:
-        # every rank fitted different sequences: report the mean / worst over the whole job
-        gathered = [None] * world
-        dist.all_gather_object(gathered, (q_mean, q_worst))
-        q_mean = {k: float(np.mean([g[0][k] for g in gathered])) for k in q_mean}
-        q_worst = {k: float(np.max([g[1][k] for g in gathered])) for k in q_worst}
+    if args.full:
+        # fit quality of every timed step of this rank against the synthetic ground truth (outside the timed region)
+        quality = [fit_quality(smpl, sq, out, dev) for sq, (out, _) in zip(seqs[args.warmup:n_seq], fits)]
+        q_mean = {k: float(np.mean([q[k] for q in quality])) for k in quality[0]}
+        q_worst = {k: float(np.max([q[k] for q in quality])) for k in quality[0]}
+        if world > 1:
+            # every rank fitted different sequences: report the mean / worst over the whole job
+            gathered = [None] * world
+            dist.all_gather_object(gathered, (q_mean, q_worst))
+            q_mean = {k: float(np.mean([g[0][k] for g in gathered])) for k in q_mean}
+            q_worst = {k: float(np.max([g[1][k] for g in gathered])) for k in q_worst}
 
     # host side of every rank's timed region (its own cgroup view; ranks of one box share one quota)
     host_mine = {"rank": rank, "torch_threads": host_threads,
@@ -498,19 +523,6 @@ def main():
         total_evals = sum(sum(eval_counts(s).values()) for s in all_stats)
         frames = (1 if MODE in ("hypotheses", "frames") else world) * args.steps * F
         value = frames / elapsed
-        roofline = measure_roofline(smpl, seqs[-1], dev, F)
-        # whole-fit arithmetic rate: SURVEY 8d's algorithmic FLOPs of every closure evaluation the timed fits executed
-        # (rank 0's counts; all ranks run the same workload) over the wall time, against the FP32 peak
-        n_sub = int(tables.v_template.shape[0])
-        fit_flops = 0.0
-        for st in all_stats:
-            c = eval_counts(st)
-            fit_flops += F * (c["chamfer"] * CHAMFER_FLOPS_PER_FRAME_EVAL + c["marker"] * MARKER_FLOPS_PER_FRAME_EVAL)
-            for ps in st.get("part", []):
-                fit_flops += F * ps["n_eval"] * part_flops_per_frame_eval(ps.get("n_subset", n_sub),
-                                                                           ps.get("n_markers", M))
-        roofline["fit_frac"] = fit_flops / elapsed / (PEAK_FP32_TFLOPS * 1e12)
-        roofline["fit_achieved"] = fit_flops / elapsed / 1e12
         result = {
             "metric": "mocap frames/sec fitted (300-frame seq, 50 markers)",
             "value": value, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -524,13 +536,9 @@ def main():
                        **({"EXPERIMENT_history_size": args.history_size} if args.history_size > 0 else {})},
             "closure_evals_per_step": total_evals / max(args.steps, 1), "closure_evals_last_step": n_eval,
             "frame_evals_per_s": world * total_evals * F / elapsed if world == 1 else None,
-            "fit_quality": {"mean": q_mean, "worst": q_worst, "steps": len(quality) * world,
-                            "against": "synthetic ground truth (float64 SMPL equations, uuo_mocap_amd/synthetic.py); "
-                                       "HMR stand-in starts 100 deg off in yaw with 0.1 rad pose / 0.5 shape noise"},
             "stages_last_step": stage_summary(all_stats[-1]),
             "stage_ms_last": {l: round(1e3 * (t - p_), 2) for (l, t), p_ in
                               zip(all_stats[-1]["timeline"], [0.0] + [t for _, t in all_stats[-1]["timeline"][:-1]])},
-            "roofline": roofline,
             # host side of the timed region (this process' cgroup): CPU seconds burnt by the polling / orchestrating threads
             # and whether the CPU quota throttled them (parallel.limit_host_threads explains why that matters)
             "host": {"cpu_quota": host_cpu_budget(), "torch_threads": host_threads,
@@ -554,11 +562,30 @@ def main():
                 "transport": type(REDUCERS[0]).__name__ if REDUCERS else None, "lanes": LANES,
                 "gathers_timed": n_g, "mean_gather_us": 1e6 * t_g / n_g if n_g else None,
                 "note": "rank 0's time inside gathers (message copy + waiting for the slowest rank) over the timed fits"}
-        if world == 1 and MODE == "sequences":
+        if args.full:
+            result["fit_quality"] = {
+                "mean": q_mean, "worst": q_worst, "steps": len(quality) * world,
+                "against": "synthetic ground truth (float64 SMPL equations, uuo_mocap_amd/synthetic.py); "
+                           "HMR stand-in starts 100 deg off in yaw with 0.1 rad pose / 0.5 shape noise"}
+            roofline = measure_roofline(smpl, seqs[-1], dev, F)
+            # whole-fit arithmetic rate: SURVEY 8d's algorithmic FLOPs of every closure evaluation the timed fits executed
+            # (rank 0's counts; all ranks run the same workload) over the wall time, against the FP32 peak
+            n_sub = int(tables.v_template.shape[0])
+            fit_flops = 0.0
+            for st in all_stats:
+                c = eval_counts(st)
+                fit_flops += F * (c["chamfer"] * CHAMFER_FLOPS_PER_FRAME_EVAL + c["marker"] * MARKER_FLOPS_PER_FRAME_EVAL)
+                for ps in st.get("part", []):
+                    fit_flops += F * ps["n_eval"] * part_flops_per_frame_eval(ps.get("n_subset", n_sub),
+                                                                               ps.get("n_markers", M))
+            roofline["fit_frac"] = fit_flops / elapsed / (PEAK_FP32_TFLOPS * 1e12)
+            roofline["fit_achieved"] = fit_flops / elapsed / 1e12
+            result["roofline"] = roofline
+        if args.full and world == 1 and MODE == "sequences":
             # latency of ONE sequence alone on the GPU (--inflight 1) beside the throughput headline (three in flight)
             n_lat = min(3, args.steps)
-            seqs_l = [make_sequence(tables, seed=3000 + i, num_frames=F, num_markers=10 if limb else M, limb_only=limb)
-                      for i in range(n_lat)]
+            seqs_l = host_map(lambda i: make_sequence(tables, seed=3000 + i, num_frames=F, num_markers=10 if limb else M,
+                                                      limb_only=limb), range(n_lat))
             with contextlib.redirect_stdout(io.StringIO()):
                 torch.cuda.synchronize(dev)
                 t3 = time.perf_counter()
@@ -569,7 +596,7 @@ def main():
                 "sequences_in_flight": 1, "steps": n_lat, "ms_per_fit": 1e3 * dt3 / n_lat, "value": n_lat * F / dt3,
                 "unit": "frames/s",
                 "closure_evals_per_step": sum(sum(eval_counts(st_).values()) for _, st_ in fits_l) / n_lat}
-        if world == 1 and args.config == "video_mocap" and not args.no_other_configs:
+        if args.full and world == 1 and args.config == "video_mocap" and not args.no_other_configs:
             # the other shipped configurations on sequences of the same size, beside the headline (not the metric's
             # workload): hmr_full.yaml = BASELINE configs[1] as written (part stage on the full skeleton only: SURVEY F9),
             # hmr_part.yaml = configs[2] (10 markers on one limb, sub-tree search), mht_rotation.yaml = configs[4]'s
@@ -579,8 +606,9 @@ def main():
             for name in ("hmr_full", "hmr_part", "mht_rotation", "hmr_part_soft", "video_mocap_soft"):
                 cfg_o = packaged_config(name)
                 limb_o = name in ("hmr_part", "hmr_part_soft")
-                seqs_o = [make_sequence(tables, seed=1000 + i, num_frames=F, num_markers=10 if limb_o else M,
-                                        limb_only=limb_o) for i in range(n_other + 1)]
+                seqs_o = host_map(lambda i: make_sequence(tables, seed=1000 + i, num_frames=F,
+                                                          num_markers=10 if limb_o else M, limb_only=limb_o),
+                                  range(n_other + 1))
                 with contextlib.redirect_stdout(io.StringIO()):
                     fit_once(smpl, seqs_o[0], cfg_o, dev)
                     torch.cuda.synchronize(dev)
@@ -594,8 +622,9 @@ def main():
                 flight = None
                 if args.inflight > 1:
                     n_fl = 2 * args.inflight
-                    seqs_f = [make_sequence(tables, seed=2000 + i, num_frames=F, num_markers=10 if limb_o else M,
-                                            limb_only=limb_o) for i in range(args.inflight + n_fl)]
+                    seqs_f = host_map(lambda i: make_sequence(tables, seed=2000 + i, num_frames=F,
+                                                              num_markers=10 if limb_o else M, limb_only=limb_o),
+                                      range(args.inflight + n_fl))
                     with contextlib.redirect_stdout(io.StringIO()):
                         fit_many(seqs_f[:args.inflight], lambda sq: fit_once(smpl, sq, cfg_o, dev), inflight=args.inflight,
                                  device=dev, wait_policy=fit_wait)  # (the workspaces of the other workspace groups)
@@ -638,7 +667,7 @@ def main():
                     torch.cuda.synchronize(dev)
                     dt = time.perf_counter() - t1
                 result["other_configs"]["hmr_part_soft"]["operator_composed_ms_per_step"] = 1e3 * dt
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             torch.set_num_threads(host_cpu_budget())  # the CPU leg gets every CPU of the quota (nothing else runs now)
             result["cpu_baseline"] = cpu_baseline(tables, seqs[-1], cfg, n_eval, args.cpu_evals, host_cpu_budget())
             torch.set_num_threads(host_threads)

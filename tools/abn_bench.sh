@@ -10,7 +10,8 @@ for r in $(seq 1 $R); do
     python - <<PY
 import json
 d=json.loads(open("gpurun_out/r4/ab_${v}_$r.json").read().strip().splitlines()[-1])
-print("$v round $r: %.1f frames/s  %.1f ms/step  %.0f evals/step  %.3f M frame-evals/s  latency %.1f ms" % (d["value"], d["ms_per_step"], d["closure_evals_per_step"], d["frame_evals_per_s"] / 1e6, d.get("latency_one_sequence", {}).get("ms_per_fit", 0)))
+lat = d.get("latency_one_sequence")  # bench args with --full
+print("$v round $r: %.1f frames/s  %.1f ms/step  %.0f evals/step  %.3f M frame-evals/s%s" % (d["value"], d["ms_per_step"], d["closure_evals_per_step"], d["frame_evals_per_s"] / 1e6, "  latency %.1f ms" % lat["ms_per_fit"] if lat else ""))
 PY
   done
 done

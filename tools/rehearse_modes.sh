@@ -5,7 +5,7 @@ set -e
 mkdir -p gpurun_out/r4
 run() {  # ranks, mode, extra flags, tag
   UUO_BENCH_SHARE_GPU=1 timeout -k 10 500 python -m torch.distributed.run --nnodes=1 --nproc-per-node $1 --master-addr 127.0.0.1 \
-    --master-port $((29520 + RANDOM % 400)) bench.py --gpus $1 --steps ${STEPS:-4} --warmup 1 --mode $2 $3 \
+    --master-port $((29520 + RANDOM % 400)) bench.py --gpus $1 --steps ${STEPS:-4} --warmup 1 --mode $2 $3 --full \
     --no-cpu-baseline --no-other-configs > gpurun_out/r4/mode_${1}rank_$4.json 2> gpurun_out/r4/mode_${1}rank_$4.err
   python - <<PY
 import json

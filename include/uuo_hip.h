@@ -176,6 +176,15 @@ typedef struct {
 
 int uuo_fit_create(uuo_model_t* model, int F, int M, uuo_fit_t** out);
 int uuo_fit_destroy(uuo_fit_t* fit);
+/* EXTENSION (not reference behaviour; the reference fits every frame on its own, and its temporal terms stop in a debugger):
+ * a joint-acceleration smoothness term on the 24 kinematic joints J_t = G_j^t + trans_t of the chamfer and marker stages,
+ *   a_t = J_t - 2 J_{t+1} + J_{t+2} (t = 0 .. F-3),   loss += w sum_t |a_t|^2 / ((F - 2) 72)
+ * in units of m^2 per frame^2: the weight belongs to the frame rate of the sequence handed over.  F < 3: no terms.
+ * A setting of the WORKSPACE (0 at creation) that applies to every uuo_closure_eval, uuo_lbfgs_solve, uuo_lbfgs_solve_shared
+ * and uuo_time_closure on `fit` until it is set again; workspaces shared by several problems need it set before each call.
+ * Refused (at evaluation) for the part stage and with w_soft != 0, and inside lock-step batches (uuo_batch_*).
+ * w >= 0, finite. */
+int uuo_fit_set_joint_accel(uuo_fit_t* fit, float w);
 /* number of parameters of a stage at (F): 211F+10 / 219F+10 / 3F+11 */
 int uuo_problem_num_params(const uuo_problem_t* p);
 

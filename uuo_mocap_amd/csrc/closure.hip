@@ -2,6 +2,7 @@
 // (reference optimization.py:187-275 chamfer, :329-394 marker, markers/markers_utils.py:454-562 part).
 // Only the <= M vertices a frame's markers touch carry gradient, so the backward is a gather-LBS over those
 // vertices instead of the reference's dense autograd GEMMs.
+#include <cstddef>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
@@ -84,6 +85,7 @@ struct BwdArgs {
   // fused finalize (k_bwd_sparse): the block that finishes LAST sums the per-frame partials and reports (see bwd_body's tail)
   uuo_gptr<unsigned> fin_counter;   // blocks of this launch that have published their partials (null: k_finalize follows)
   FinArgs fin;
+  float acc_w;  // EXTENSION (ACCEL instantiations only): w_accel / ((F - 2) 72), the joint-acceleration term's coefficient
 };
 
 // ----------------------------------------------------------------------------------------------------
@@ -96,7 +98,9 @@ struct BwdArgs {
 // 1024 / NT groups one after the other.  COHERENT: the partials were written by OTHER blocks of the running kernel (fused
 // finalize at the end of k_bwd_sparse): they are read with agent-scope loads (sc1: not served from this XCD's L2) and the
 // report is written without a cache write-back (see bwd_body's tail).
-template <int NT, bool COHERENT>
+// ACCEL (EXTENSION): slot 3 of every frame holds that frame's share of the joint-acceleration term, already scaled (bwd_body);
+// it joins the loss.  A separate instantiation (k_finalize_t), so that k_finalize keeps its code.
+template <int NT, bool COHERENT, bool ACCEL = false>
 __device__ __forceinline__ void finalize_body(const FinArgs& a) {
   __builtin_amdgcn_s_setprio(3);  // latency-bound kernel: do not queue behind co-resident MFMA waves
   __shared__ double sh[32][32];
@@ -167,7 +171,11 @@ __device__ __forceinline__ void finalize_body(const FinArgs& a) {
       s2 += (double)gb * (double)gb;
       sm = fmax(sm, fabs((double)gb));
     }
-    const float lossf = (float)(a.closs * sh[0][0] + a.cpose * sh[0][2] + a.cbetas * bsq);
+    float lossf;
+    if constexpr (ACCEL)
+      lossf = (float)(a.closs * sh[0][0] + a.cpose * sh[0][2] + a.cbetas * bsq + sh[0][3]);
+    else
+      lossf = (float)(a.closs * sh[0][0] + a.cpose * sh[0][2] + a.cbetas * bsq);
     a.loss[0] = lossf;
     // the statistics of this problem's OWN parameters (everything but the shape vector), for solves that share the betas
     // with other ranks (uuo_lbfgs_solve_shared: the betas' gradient is summed over the ranks before it enters any norm)
@@ -289,9 +297,18 @@ __device__ __forceinline__ float gmof_q(float sig2, float s) { return sig2 / (si
 // ROBUST (EXTENSION, uuo_problem_t.robust_sigma > 0): every data item's square s enters as the Geman-McClure term
 // rho(s) = s q, d rho / d s = q^2 with q = sigma^2 / (sigma^2 + s) (gmof_q); instantiated separately so that the plain kernels
 // keep their code and register allocation
-template <bool PART = false, int NWV = BWD_NW, bool DENSE = false, bool ITEMS = false, bool ROBUST = false>
+// ACCEL (EXTENSION, uuo_fit_set_joint_accel > 0, F >= 3): the joint-acceleration smoothness term over the 24 kinematic joints
+// J_t = G_j^t + trans_t,  a_t = J_t - 2 J_{t+1} + J_{t+2} (t = 0 .. F-3),  loss += acc_w sum_t |a_t|^2,
+// dL/dJ_f = 2 acc_w (a_{f-2} - 2 a_{f-1} + a_f) (terms outside 0 .. F-3 dropped).  Block f reads G^t and trans of frames
+// f-2 .. f+2 (a.frames: every frame's FrameLds, left by the forward of this evaluation; trans from the parameters), feeds
+// dL/dJ_f in where SmplInference.forward's joint gradient enters (sdGt; the translation gets its sum) and writes its own
+// acc_w |a_f|^2 to slot 3 of its partials (k_finalize_t adds it to the loss).  Everything downstream -- the kinematic sweep, the
+// Gram-Schmidt backward, the priors, the solver's fused statistics -- is the existing code.  Separate instantiations.
+template <bool PART = false, int NWV = BWD_NW, bool DENSE = false, bool ITEMS = false, bool ROBUST = false, bool ACCEL = false>
 __device__ __forceinline__ void bwd_body(const BwdArgs& a) {
   static_assert(!ROBUST || (!DENSE && !ITEMS), "the robust data term is formed on the sparse items (k_bary_fwd for item mode)");
+  static_assert(!ACCEL || (!PART && !DENSE && NWV == BWD_NW), "the joint-acceleration term is built for the fitted stages' "
+                "sparse kernels (chamfer, marker) only");
   static_assert(!(PART && DENSE), "the part stage's dense sums come through the runtime `pre` pointer");
   static_assert(!ITEMS || (!PART && !DENSE), "item mode belongs to the general sparse kernel");
   static_assert(NWV == BWD_NW || (PART && NWV == 1), "one-wave blocks exist for the part stage only");
@@ -313,6 +330,9 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a) {
   __shared__ float sstat[28][4];  // per writer: g.d, sum|g|, g.g, max|g| (0..22 body joints, 23 root/z, 24..26 transl)
   __shared__ int s_lvl_n[UUO_MAX_DEPTH], s_lvl_j[UUO_MAX_DEPTH][UUO_LEVEL_W], s_lvl_p[UUO_MAX_DEPTH][UUO_LEVEL_W];
   __shared__ int s_nch[UUO_NUM_JOINTS], s_ch[UUO_NUM_JOINTS][4];
+  // ACCEL: [5][75] G^t (72) and trans (3) of frames f-2 .. f+2 (zeros outside the sequence), then [72] dL/dJ_f, [72] |a_f|^2 terms
+  constexpr int ACC_W = 75, ACC_UJ = 5 * ACC_W, ACC_AA = ACC_UJ + 72;
+  __shared__ float s_acc[ACCEL ? ACC_AA + 72 : 1];
 
   const int f = blockIdx.x;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -340,6 +360,15 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a) {
     __syncthreads();
   } else {
     frame_forward(a.src, a.tree, f, L);
+  }
+  if constexpr (ACCEL) {  // (a.frames is set for every ACCEL launch; the __syncthreads below publishes the window)
+    constexpr int NW = sizeof(FrameLds) / 4, GT = offsetof(FrameLds, Gt) / 4;
+    for (int i = tid; i < 5 * ACC_W; i += NT) {
+      const int t = i / ACC_W, k = i - t * ACC_W, ft = f - 2 + t;
+      float v = 0.f;
+      if (ft >= 0 && ft < F) v = (k < 72) ? a.frames[(size_t)ft * NW + GT + k] : a.src.trans[(size_t)ft * 3 + (k - 72)];
+      s_acc[i] = v;
+    }
   }
   if (tid < UUO_NUM_JOINTS) frame_skin_matrix(L, tid, sA + tid * 12);
   if (!PART && tid < UUO_KB) {
@@ -665,7 +694,27 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a) {
     } else {
       const int r = e - 9;
       // joints 0..23 of SMPL.forward are the world translations G_j^t (+ transl): their upstream gradient enters here
-      const float uj = (a.stage == UUO_STAGE_UPSTREAM && a.up_joints) ? a.up_joints[((size_t)f * 45 + jj) * 3 + r] : 0.f;
+      float uj = (a.stage == UUO_STAGE_UPSTREAM && a.up_joints) ? a.up_joints[((size_t)f * 45 + jj) * 3 + r] : 0.f;
+      if constexpr (ACCEL) {
+        // a_{f-2+i} (i = 0, 1, 2) from window frames i .. i+2, G^t and trans differenced apart (trans is metres large)
+        const int k = jj * 3 + r;
+        float w[5], tw[5];
+#pragma unroll
+        for (int i = 0; i < 5; ++i) {
+          w[i] = s_acc[i * ACC_W + k];
+          tw[i] = s_acc[i * ACC_W + 72 + r];
+        }
+        float ac[3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+          const int t0 = f - 2 + i;
+          const float ai = ((w[i] - 2.f * w[i + 1]) + w[i + 2]) + ((tw[i] - 2.f * tw[i + 1]) + tw[i + 2]);
+          ac[i] = (t0 >= 0 && t0 <= F - 3) ? ai : 0.f;
+        }
+        uj = (2.f * a.acc_w) * ((ac[0] - 2.f * ac[1]) + ac[2]);
+        s_acc[ACC_UJ + k] = uj;
+        s_acc[ACC_AA + k] = ac[2] * ac[2];
+      }
       const float dAt0 = sdA[jj * 12 + 3], dAt1 = sdA[jj * 12 + 7], dAt2 = sdA[jj * 12 + 11];
       sdGt[jj][r] = sdA[jj * 12 + r * 4 + 3] + uj;
       sdJ[jj][r] = -(fmaf(L.GR[jj][6 + r], dAt2, fmaf(L.GR[jj][3 + r], dAt1, L.GR[jj][r] * dAt0)));
@@ -845,6 +894,9 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a) {
     if (a.stage == UUO_STAGE_UPSTREAM && a.up_joints) {
       for (int jj = 0; jj < UUO_NUM_JOINTS; ++jj) gt += a.up_joints[((size_t)f * 45 + jj) * 3 + c];
     }
+    if constexpr (ACCEL) {  // J_j = G_j^t + trans: the translation takes the sum of the joints' gradients
+      for (int jj = 0; jj < UUO_NUM_JOINTS; ++jj) gt += s_acc[ACC_UJ + jj * 3 + c];
+    }
     a.g_trans[(size_t)f * 3 + c] = gt;
     sstat[24 + c][0] = gt * dpre[0];
     sstat[24 + c][1] = fabsf(gt); sstat[24 + c][2] = gt * gt; sstat[24 + c][3] = fabsf(gt);
@@ -869,6 +921,13 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a) {
     BWD_FP_STORE(2, ps);
     if (a.stage != UUO_STAGE_PART) BWD_FP_STORE(1, 0.f);
   }
+  if constexpr (ACCEL) {
+    if (tid == 64) {  // (another wave than the one above) this frame's share of the joint-acceleration term, fixed order
+      float s = 0.f;
+      for (int k = 0; k < 72; ++k) s += s_acc[ACC_AA + k];
+      BWD_FP_STORE(3, a.acc_w * s);
+    }
+  }
   BWD_STAMP(10);
 #if UUO_FIN_FUSED_BUILT
   if constexpr (!PART) {
@@ -886,7 +945,7 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a) {
       __syncthreads();
       if (s_arrived == (unsigned)a.h.gx - 1u) {
         if (tid == 0) __hip_atomic_store(a.fin_counter.get(), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // next launch
-        finalize_body<NT, true>(a.fin);
+        finalize_body<NT, true, ACCEL>(a.fin);
       }
     }
   }
@@ -912,10 +971,19 @@ __global__ __launch_bounds__(BWD_NW * 64) __attribute__((amdgpu_waves_per_eu(3, 
   UUO_BATCH_PICK(BwdArgs, batch)
   bwd_body<false, BWD_NW, false, false, true>(a);
 }
+// EXTENSION: the two with the joint-acceleration smoothness term (uuo_fit_set_joint_accel; no lock-step batch forms)
+__global__ __launch_bounds__(BWD_NW * 64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_bwd_sparse_t(BwdArgs a) {
+  bwd_body<false, BWD_NW, false, false, false, true>(a);
+}
+__global__ __launch_bounds__(BWD_NW * 64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_bwd_sparse_r_t(BwdArgs a) {
+  bwd_body<false, BWD_NW, false, false, true, true>(a);
+}
 // the kinematic tail alone, on the sums of a dense backward (dense_bwd.hip)
 __global__ __launch_bounds__(BWD_NW * 64) void k_bwd_dense(BwdArgs a) { bwd_body<false, BWD_NW, true>(a); }
 // the sparse kernel on (vertex, upstream gradient) items (the marker stage on a three-corner placement, k_bary_fwd before it)
 __global__ __launch_bounds__(BWD_NW * 64) void k_bwd_items(BwdArgs a) { bwd_body<false, BWD_NW, false, true>(a); }
+// EXTENSION: the same with the joint-acceleration term (k_bary_fwd / k_bary_fwd_r before it, plain or robust)
+__global__ __launch_bounds__(BWD_NW * 64) void k_bwd_items_t(BwdArgs a) { bwd_body<false, BWD_NW, false, true, false, true>(a); }
 
 // ----------------------------------------------------------------------------------------------------
 // Marker stage on a three-corner (barycentric) placement (reference optimization.py:345-351 with the placement of
@@ -1087,6 +1155,8 @@ __global__ __launch_bounds__(BWD_NW * 64) void k_bwd_part_b_r(const BwdArgs* __r
 }
 
 __global__ __launch_bounds__(1024) void k_finalize(FinArgs a) { finalize_body<1024, false>(a); }
+// EXTENSION: with the joint-acceleration term's per-frame shares (after the *_t backward kernels)
+__global__ __launch_bounds__(1024) void k_finalize_t(FinArgs a) { finalize_body<1024, false, true>(a); }
 __global__ __launch_bounds__(1024) void k_finalize_b(const FinArgs* __restrict__ batch) {
   UUO_BATCH_PICK(FinArgs, batch)
   finalize_body<1024, false>(a);
@@ -1188,6 +1258,21 @@ static int validate_problem(const uuo_fit* fit, const uuo_problem_t* p) {
                 "whose square is a normal fp32 value");
     UUO_REQUIRE(sg == 0.f || p->w_soft == 0.f, "closure: robust_sigma is not built for the soft-assignment data term (w_soft)");
   }
+  // EXTENSION: the joint-acceleration term of the workspace (uuo_fit_set_joint_accel) is built for the fitted stages' sparse
+  // closures only
+  UUO_REQUIRE(fit->joint_accel == 0.f || p->stage != UUO_STAGE_PART,
+              "closure: the joint-acceleration term (uuo_fit_set_joint_accel, extension) is not built for the part stage");
+  UUO_REQUIRE(fit->joint_accel == 0.f || p->w_soft == 0.f,
+              "closure: the joint-acceleration term (uuo_fit_set_joint_accel, extension) is not built for the soft-assignment "
+              "data term (w_soft)");
+  return 0;
+}
+
+extern "C" int uuo_fit_set_joint_accel(uuo_fit_t* fit, float w) {
+  UUO_REQUIRE(fit, "uuo_fit_set_joint_accel: null fit");
+  UUO_REQUIRE(w == 0.f || (w > 0.f && w <= 3.0e38f), "uuo_fit_set_joint_accel: the weight must be 0 (off) or a positive finite number");
+  UUO_REQUIRE(w == 0.f || !uuo_recorder, "uuo_fit_set_joint_accel: lock-step batches do not carry the joint-acceleration term");
+  fit->joint_accel = w;
   return 0;
 }
 
@@ -1584,6 +1669,10 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
   a.stop = bwd_stop;
   a.dir = d_dir;
   a.off_pose = gl.off_pose; a.off_root = gl.off_root; a.off_z = gl.off_z; a.off_trans = gl.off_trans;
+  // EXTENSION: the joint-acceleration term runs on the *_t instantiations; with fewer than three frames it has no terms
+  const bool accel = fit->joint_accel != 0.f && F >= 3;
+  UUO_REQUIRE(!accel || !uuo_recorder, "closure: lock-step batches do not carry the joint-acceleration term");
+  a.acc_w = accel ? (float)((double)fit->joint_accel / ((double)(F - 2) * 72.0)) : 0.f;
   a.h.gx = F;
   a.h.gy = 1;
   FinArgs fa;
@@ -1654,7 +1743,10 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
     a.up_items = items;
     a.item_loss = item_loss;
     a.frames = fit->frames;
-    hipLaunchKernelGGL(k_bwd_items, dim3(F), dim3(BWD_NW * 64), 0, s, a);
+    if (accel)
+      hipLaunchKernelGGL(k_bwd_items_t, dim3(F), dim3(BWD_NW * 64), 0, s, a);
+    else
+      hipLaunchKernelGGL(k_bwd_items, dim3(F), dim3(BWD_NW * 64), 0, s, a);
   } else if (soft && p->stage == UUO_STAGE_CHAMFER) {
     // EXTENSION: soft-assignment data term of the chamfer stage.  The forward above has skinned the vertices and run the exact
     // search (dmin, the hard assignment); the soft minimum gives EVERY vertex within reach of a marker a gradient, so the
@@ -1681,7 +1773,20 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
       a.fin_counter = reinterpret_cast<unsigned*>(fit->scalars + 32);
       fin_fused = true;
     }
-    if (robust) {
+    if (accel) {
+      // EXTENSION: the block of frame f reads its neighbours' world joints.  The marker stage's closure has no forward of its
+      // own (its backward re-runs each frame's kinematic chain): a pose-prep launch leaves every frame's FrameLds first, and the
+      // backward blocks start from them
+      if (p->stage == UUO_STAGE_MARKER) {
+        rc = uuo_launch_pose_prep(m, s, F, src, fit->pfaT, fit->A, nullptr, fit->frames);
+        if (rc) return rc;
+        a.frames = fit->frames;
+      }
+      if (robust)
+        hipLaunchKernelGGL(k_bwd_sparse_r_t, dim3(F), dim3(BWD_NW * 64), 0, s, a);
+      else
+        hipLaunchKernelGGL(k_bwd_sparse_t, dim3(F), dim3(BWD_NW * 64), 0, s, a);
+    } else if (robust) {
       if (!uuo_record(UUO_OP_BWD_R, F, 1, a)) hipLaunchKernelGGL(k_bwd_sparse_r, dim3(F), dim3(BWD_NW * 64), 0, s, a);
     } else if (!uuo_record(UUO_OP_BWD, F, 1, a)) {
       hipLaunchKernelGGL(k_bwd_sparse, dim3(F), dim3(BWD_NW * 64), 0, s, a);
@@ -1689,7 +1794,10 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
   }
   UUO_HIP_CHECK(hipGetLastError());
   if (!fin_fused) {
-    if (!uuo_record(UUO_OP_FIN, 1, 1, fa)) hipLaunchKernelGGL(k_finalize, dim3(1), dim3(1024), 0, s, fa);
+    if (accel)
+      hipLaunchKernelGGL(k_finalize_t, dim3(1), dim3(1024), 0, s, fa);
+    else if (!uuo_record(UUO_OP_FIN, 1, 1, fa))
+      hipLaunchKernelGGL(k_finalize, dim3(1), dim3(1024), 0, s, fa);
     UUO_HIP_CHECK(hipGetLastError());
   }
 

@@ -189,6 +189,7 @@ struct uuo_fit {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   float mask_sum = 0.f;  // host copy of sum(mask) (chamfer normaliser), refreshed by uuo_ensure_mask
   bool shared_pose_cache = false;  // pose_cache belongs to a uuo_batch (not freed with the fit)
+  float joint_accel = 0.f;  // EXTENSION: weight of the joint-acceleration term (uuo_fit_set_joint_accel; 0 = off)
 };
 
 // ---- dense backward of the skinning (dense_bwd.hip) ---------------------------------------------------------------------

@@ -161,6 +161,9 @@ def solve_batch(problems, xs, max_iter: int, lr: float = 1.0, tolerance_grad: fl
     assert len(problems) == len(xs) and len(problems) > 0
     p0 = problems[0]
     model = p0.model
+    if any(p.joint_accel != 0.0 for p in problems):
+        raise NotImplementedError("lock-step batches do not carry the joint-acceleration term (joint_accel, extension): "
+                                  "solve such problems one by one")
     for p, x in zip(problems, xs):
         assert p.stage == p0.stage and p.F == p0.F and p.M == p0.M and p.model is model
         assert x.is_cuda and x.dtype == torch.float32 and x.numel() == p.n and x.is_contiguous()
@@ -431,6 +434,14 @@ class _StageProblem:
         p.marker_distance = MARKER_DISTANCE
         self.problem = p
         self.n = int(self.lib.uuo_problem_num_params(byref(p)))
+        # EXTENSION: weight of the joint-acceleration term (ChamferProblem / MarkerProblem), a setting of the WORKSPACE in
+        # the library (uuo_fit_set_joint_accel): _arm() puts it there before every call that evaluates on it
+        self.joint_accel = 0.0
+
+    def _arm(self):
+        """Sets this problem's joint-acceleration weight (0 without the term) on its workspace.  The workspace is shared by
+        every problem of the same (F, M) on this thread, so this runs right before each library call that evaluates on it."""
+        check(self.lib.uuo_fit_set_joint_accel(self.fit, c_float(self.joint_accel)), "uuo_fit_set_joint_accel")
 
     def _need_workspace(self):
         if self.fit is None:  # created for a lock-step batch only: give it the thread's workspace on first standalone use
@@ -447,6 +458,7 @@ class _StageProblem:
         if want_nn and self.stage != UUO_STAGE_MARKER:
             nn = torch.empty((self.F, self.M), dtype=torch.int32, device=self.device)
         with torch.cuda.device(self.device):
+            self._arm()
             check(self.lib.uuo_closure_eval(self.fit, current_stream(self.device), byref(self.problem), _ptr(x),
                                             _ptr(loss), _ptr(grad), _ptr(nn)), "uuo_closure_eval")
         return float(loss.item()), grad, nn
@@ -475,6 +487,7 @@ class _StageProblem:
 
         cb = EVAL_CALLBACK(on_eval) if (callback is not None or point_callback is not None) else None
         with torch.cuda.device(self.device):
+            self._arm()
             check(self.lib.uuo_lbfgs_solve(self.fit, current_stream(self.device), byref(self.problem), _ptr(x),
                                            byref(opt), byref(stats), ctypes.cast(cb, c_void_p) if cb else None, None),
                   "uuo_lbfgs_solve")
@@ -516,6 +529,7 @@ class _StageProblem:
         shared = UuoShared(gather_c, user, int(reducer.rank), world)
         cb = EVAL_CALLBACK(lambda user, i, loss, d_x_eval: callback(i, loss)) if callback is not None else None
         with torch.cuda.device(self.device):
+            self._arm()
             rc = self.lib.uuo_lbfgs_solve_shared(self.fit, current_stream(self.device), byref(self.problem), _ptr(x),
                                                  byref(opt), byref(stats), byref(shared),
                                                  ctypes.cast(cb, c_void_p) if cb else None, None)
@@ -567,6 +581,7 @@ class _StageProblem:
         stream = current_stream(self.device)
         for i in range(int(num_steps)):
             with torch.cuda.device(self.device):
+                self._arm()
                 check(self.lib.uuo_closure_eval(self.fit, stream, byref(self.problem), _ptr(p), _ptr(loss), _ptr(grad),
                                                 None), "uuo_closure_eval")
             if callback is not None or i == 0 or i == num_steps - 1:
@@ -585,6 +600,7 @@ class _StageProblem:
         self._need_workspace()
         ms = c_float(0.0)
         with torch.cuda.device(self.device):
+            self._arm()
             check(self.lib.uuo_time_closure(self.fit, current_stream(self.device), byref(self.problem), _ptr(x),
                                             int(iters), int(dominant_only), byref(ms)), "uuo_time_closure")
         return float(ms.value)
@@ -605,6 +621,17 @@ def stage_robust_sigma(config: Dict, stage: str) -> float:
     return v
 
 
+def stage_joint_accel(config: Dict, stage: str) -> float:
+    """EXTENSION: stages.<stage>.losses.joint_accel of a config -- the weight of the joint-acceleration smoothness term of the
+    chamfer or marker stage (uuo_fit_set_joint_accel), in units of m^2 per frame^2 of the sequence the stage is handed.  Absent
+    or 0 = off; negative or non-finite weights are refused.  (The part stage refuses the key with its other unknown losses.)"""
+    v = (config["stages"][stage].get("losses") or {}).get("joint_accel", 0.0)
+    v = 0.0 if v is None else float(v)
+    if not math.isfinite(v) or v < 0.0:
+        raise ValueError("stages.%s.losses.joint_accel must be 0 (off) or a positive weight (got %r)" % (stage, v))
+    return v
+
+
 def _cfg_weights(losses: Dict, data_key: str):
     return (float(losses.get(data_key, 0.0)), float(losses.get("reg_pose_body", 0.0)),
             float(losses.get("reg_betas", 0.0)))
@@ -617,15 +644,20 @@ class ChamferProblem(_StageProblem):
 
     def __init__(self, smpl_inference, markers, o_pose_body, o_betas, root_orient, config):
         losses = config["stages"]["chamfer"]["losses"]
-        unsupported = set(losses) - {"full_chamfer", "reg_pose_body", "reg_betas", "soft_chamfer"}
+        unsupported = set(losses) - {"full_chamfer", "reg_pose_body", "reg_betas", "soft_chamfer", "joint_accel"}
         if unsupported:
             raise NotImplementedError("chamfer-stage losses outside the shipped configs: %s" % sorted(unsupported))
+        w_accel = stage_joint_accel(config, "chamfer")
+        if w_accel > 0.0 and float(losses.get("soft_chamfer", 0.0)) != 0.0:
+            raise NotImplementedError("stages.chamfer: the fused joint-acceleration term (joint_accel) is not built for the "
+                                      "soft-assignment closure; optim_chamfer composes that combination from the operators")
         if not config["stages"]["chamfer"]["yaw_lock"]:
             raise NotImplementedError("stages.chamfer.yaw_lock False is not a shipped configuration")
         wd, wp, wb = _cfg_weights(losses, "full_chamfer")
         sigma = stage_robust_sigma(config, "chamfer")
         super().__init__(smpl_inference.device_model, markers, o_pose_body, o_betas, root_orient, wd, wp, wb)
         self.problem.robust_sigma = sigma  # EXTENSION: Geman-McClure data term (0 = off)
+        self.joint_accel = w_accel  # EXTENSION: joint-acceleration term (0 = off)
         # EXTENSION (not in the reference): soft assignment of every marker to the body's vertices, fused closure with the dense
         # backward on the matrix pipe (csrc/dense_bwd.hip); not available inside lock-step batches
         w_soft = float(losses.get("soft_chamfer", 0.0))
@@ -654,15 +686,17 @@ class MarkerProblem(_StageProblem):
         """`assign` [M] vertex ids (the one-hot placement of the shipped configs), or -- with `bary` [M, 3] -- [M, 3] corner
         vertex ids of a three-corner (barycentric) placement: virtual marker m = sum_k bary[m, k] v[assign[m, k]]."""
         st = config["stages"]["marker"]
-        unsupported = set(st["losses"]) - {"marker", "reg_pose_body", "reg_betas"}
+        unsupported = set(st["losses"]) - {"marker", "reg_pose_body", "reg_betas", "joint_accel"}
         if unsupported:
             raise NotImplementedError("marker-stage losses outside the shipped configs: %s" % sorted(unsupported))
         if st.get("use_sdf"):
             raise NotImplementedError("stages.marker.use_sdf is off in every shipped config")
         wd, wp, wb = _cfg_weights(st["losses"], "marker")
         sigma = stage_robust_sigma(config, "marker")
+        w_accel = stage_joint_accel(config, "marker")
         super().__init__(smpl_inference.device_model, markers, o_pose_body, o_betas, None, wd, wp, wb, assign=assign)
         self.problem.robust_sigma = sigma  # EXTENSION: Geman-McClure data term (0 = off)
+        self.joint_accel = w_accel  # EXTENSION: joint-acceleration term (0 = off)
         if bary is not None:
             if self.assign.dim() != 2 or tuple(self.assign.shape) != (self.M, 3) or tuple(bary.shape) != (self.M, 3):
                 raise ValueError("a three-corner placement takes assign [M, 3] and bary [M, 3]")

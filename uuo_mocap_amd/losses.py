@@ -178,3 +178,14 @@ def RobustMarkerLoss(markers, virtual_markers, marker_weights, marker_distance, 
     """EXTENSION: `MarkerLoss` with the squared deviation passed through gmof."""
     gap = torch.norm(markers - virtual_markers, dim=-1) - marker_distance
     return gmof(gap ** 2, sigma) * marker_weights
+
+
+def joint_accel_loss(joints: torch.Tensor) -> torch.Tensor:
+    """EXTENSION (not in the reference): the joint-acceleration smoothness term of the fused chamfer and marker closures
+    (uuo_fit_set_joint_accel) on joint positions [F, J, 3] -- F.mse_loss of the second differences
+    a_t = J_t - 2 J_{t+1} + J_{t+2}, t = 0 .. F-3, against zero, i.e. sum_t |a_t|^2 / ((F - 2) 3 J).  Units: m^2 per frame^2.
+    With fewer than three frames there are no terms and the value is 0."""
+    if joints.shape[0] < 3:
+        return joints.sum() * 0.0
+    a = joints[:-2] - 2.0 * joints[1:-1] + joints[2:]
+    return torch.mean(a * a)

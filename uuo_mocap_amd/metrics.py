@@ -48,6 +48,17 @@ def compute_MPJVE_joints(pred_joints: torch.Tensor, gt_joints: torch.Tensor, fre
     return _velocity_error(pred_joints, gt_joints, freq, joints_ids)
 
 
+def compute_accel_error(pred_joints: torch.Tensor, gt_joints: torch.Tensor, freq: float) -> torch.Tensor:
+    """Acceleration error (HMMR's "accel error"; not a metric of the reference): mean over frames 1 .. F-2 and joints of
+    |a_pred - a_gt|, a_t = (x_{t-1} - 2 x_t + x_{t+1}) freq^2, in m/s^2 for positions in metres and `freq` in frames per
+    second.  pred_joints, gt_joints [F, J, 3] with F >= 3."""
+    if pred_joints.shape != gt_joints.shape or pred_joints.dim() != 3 or pred_joints.shape[0] < 3:
+        raise ValueError("compute_accel_error: joints [F, J, 3] of equal shape with F >= 3 expected (got %s and %s)"
+                         % (tuple(pred_joints.shape), tuple(gt_joints.shape)))
+    accel = lambda x: (x[:-2] - 2.0 * x[1:-1] + x[2:]) * (float(freq) ** 2)
+    return torch.mean(torch.norm(accel(pred_joints) - accel(gt_joints), dim=-1))
+
+
 def compute_PA_MPJPE(pred_joints: torch.Tensor, gt_joints: torch.Tensor) -> torch.Tensor:
     return compute_MPJPE(compute_similarity_transform(pred_joints, gt_joints), gt_joints)
 

@@ -12,9 +12,9 @@ import torch
 import torch.nn.functional as F
 
 from .device_lbfgs import DeviceLBFGS
-from .engine import MARKER_DISTANCE, ChamferProblem, MarkerProblem, stage_robust_sigma
-from .losses import (MarkerLoss, RobustMarkerLoss, chamfer_distance, robust_weighted_chamfer_distance,  # noqa: F401  (re-exported)
-                     soft_weighted_chamfer_distance, weighted_chamfer_distance)
+from .engine import MARKER_DISTANCE, ChamferProblem, MarkerProblem, stage_joint_accel, stage_robust_sigma
+from .losses import (MarkerLoss, RobustMarkerLoss, chamfer_distance, joint_accel_loss,  # noqa: F401  (re-exported)
+                     robust_weighted_chamfer_distance, soft_weighted_chamfer_distance, weighted_chamfer_distance)
 from .smpl import SmplInference
 from .transforms import compute_root_orient_y, compute_root_orient_z, normalize_rot  # noqa: F401
 
@@ -65,7 +65,11 @@ def optim_chamfer(
         # EXTENSION: the soft-assignment data term has a fused closure (dense backward on the matrix pipe, csrc/dense_bwd.hip);
         # execution.chamfer_soft_fused: False keeps the operator-composed closure, its checker
         fused_losses = _CHAMFER_FUSED_LOSSES | {"soft_chamfer"}
-    if (set(st["losses"]) - fused_losses) or not st["yaw_lock"] or not _robust_fused(config, "chamfer"):
+    if "soft_chamfer" in fused_losses and stage_joint_accel(config, "chamfer") > 0.0:
+        # EXTENSION: the joint-acceleration term has no instantiation of the dense backward (k_bwd_dense): composed closure
+        fused_losses = _CHAMFER_FUSED_LOSSES
+    if (set(st["losses"]) - fused_losses) or not st["yaw_lock"] or not _robust_fused(config, "chamfer") or \
+            not _temporal_fused(config, "chamfer"):
         return _optim_chamfer_general(markers, pose_body, o_pose_body, betas, o_betas, root_orient, trans, marker_labels,
                                       smpl_inference, config, initial_angle, repeat, verbose, iter_fn)
     from .parallel import frame_shard
@@ -124,6 +128,7 @@ def _optim_chamfer_frame_sharded(fs, markers, pose_body, o_pose_body, betas, o_b
                                  config, iter_fn):
     """optim_chamfer's fused solve spread over ranks by frame blocks (parallel.shard_frames); same in-place contract, every
     rank ends with the full result."""
+    _refuse_sharded_joint_accel(config, "chamfer")
     if iter_fn is not None:
         raise NotImplementedError("frame sharding: no per-evaluation iter_fn")
     F = int(markers.shape[0])
@@ -150,6 +155,7 @@ def _optim_chamfer_frame_sharded(fs, markers, pose_body, o_pose_body, betas, o_b
 def _optim_markers_frame_sharded(fs, markers, pose_body, o_pose_body, betas, o_betas, root_orient, trans, assign,
                                  smpl_inference, config, iter_fn):
     """optim_markers' fused solve (one-hot placement) spread over ranks by frame blocks; same in-place contract."""
+    _refuse_sharded_joint_accel(config, "marker")
     if iter_fn is not None:
         raise NotImplementedError("frame sharding: no per-evaluation iter_fn")
     F = int(markers.shape[0])
@@ -175,6 +181,18 @@ def _robust_fused(config: Dict, stage: str) -> bool:
     return stage_robust_sigma(config, stage) == 0.0 or bool((config.get("execution") or {}).get("robust_fused", True))
 
 
+def _temporal_fused(config: Dict, stage: str) -> bool:
+    """False when the stage's EXTENSION joint-acceleration term (stages.<stage>.losses.joint_accel > 0) is to run on the
+    closure composed from the operators (execution.temporal_fused: False, the fused closures' checker); True otherwise."""
+    return stage_joint_accel(config, stage) == 0.0 or bool((config.get("execution") or {}).get("temporal_fused", True))
+
+
+def _refuse_sharded_joint_accel(config: Dict, stage: str):
+    if stage_joint_accel(config, stage) > 0.0:
+        raise NotImplementedError("stages.%s.losses.joint_accel (extension) couples neighbouring frames, across the ranks' "
+                                  "frame blocks too: it is not built for frame-block sharding (parallel.shard_frames)" % stage)
+
+
 def lockstep_supported(config: Dict, stage: str) -> bool:
     """True when `stage` ("chamfer" / "marker") of this configuration runs on the fused device closure with the L-BFGS
     driver, i.e. when independent solves of it can be stepped together (engine.solve_batch)."""
@@ -183,9 +201,11 @@ def lockstep_supported(config: Dict, stage: str) -> bool:
         return False
     if not _robust_fused(config, stage):
         return False
+    if stage_joint_accel(config, stage) > 0.0:  # EXTENSION: lock-step batches do not carry the joint-acceleration term
+        return False
     if stage == "chamfer":
         return not (set(st["losses"]) - _CHAMFER_FUSED_LOSSES) and bool(st["yaw_lock"])
-    return not (set(st["losses"]) - {"marker", "reg_pose_body", "reg_betas"}) and not st.get("use_sdf")
+    return not (set(st["losses"]) - {"marker", "reg_pose_body", "reg_betas", "joint_accel"}) and not st.get("use_sdf")
 
 
 def optim_chamfer_lockstep(markers, hyps, o_pose_body, o_betas, smpl_inference, config):
@@ -282,7 +302,7 @@ def _solve(prob, x, config, stage: str, lr: float, verbose_tag: str, verbose: bo
 
 
 #: chamfer-stage loss terms the device solver fuses (the only ones the shipped configs enable)
-_CHAMFER_FUSED_LOSSES = {"full_chamfer", "reg_pose_body", "reg_betas"}
+_CHAMFER_FUSED_LOSSES = {"full_chamfer", "reg_pose_body", "reg_betas", "joint_accel"}
 
 
 def _optim_chamfer_general(markers, pose_body, o_pose_body, betas, o_betas, root_orient, trans, marker_labels,
@@ -299,6 +319,7 @@ def _optim_chamfer_general(markers, pose_body, o_pose_body, betas, o_betas, root
     if unknown:
         raise NotImplementedError("chamfer-stage losses that cannot run in the reference: %s" % sorted(unknown))
     sigma = stage_robust_sigma(config, "chamfer")  # EXTENSION: Geman-McClure data term (0 = the reference's square)
+    w_accel = stage_joint_accel(config, "chamfer")  # EXTENSION: joint-acceleration term
     device = root_orient.device
     num_frames = pose_body.shape[0]
     root_fixed = root_orient.detach().clone()
@@ -344,6 +365,8 @@ def _optim_chamfer_general(markers, pose_body, o_pose_body, betas, o_betas, root
             loss = loss + torch.mean(F.relu(-out["joints"][..., 2])) * w["ground"]
         if "reg_betas" in w:
             loss = loss + F.mse_loss(p_betas, o_betas) * w["reg_betas"]
+        if "joint_accel" in w:  # EXTENSION: the fused closures' joint-acceleration term, composed (their checker)
+            loss = loss + joint_accel_loss(out["joints"][:, :24]) * w_accel
         loss.backward()
         if verbose:
             print("Chamfer", n_eval[0], float(loss))
@@ -398,7 +421,8 @@ def optim_markers(
     fs = frame_shard()
     sharded = fs is not None and fs.active
     bary = None
-    if not _robust_fused(config, "marker"):  # EXTENSION: execution.robust_fused: False -- the composed closure, the fused one's checker
+    if not _robust_fused(config, "marker") or not _temporal_fused(config, "marker"):
+        # EXTENSION: execution.robust_fused / temporal_fused: False -- the composed closure, the fused one's checker
         return _optim_markers_general(markers, pose_body, o_pose_body, betas, o_betas, root_orient, trans, one_hot,
                                       smpl_inference, config, verbose, iter_fn, initial_angle, repeat)
     if not bool(((rows_nz == 1) & (one_hot.sum(dim=1) == 1.0)).all()):
@@ -444,12 +468,13 @@ def _optim_markers_general(markers, pose_body, o_pose_body, betas, o_betas, root
     path composes the same closure from the differentiable HIP operators (SmplInference forward / uuo_smpl_backward)
     and drives it with torch.optim.LBFGS like the reference.  Mutates the four leaves in place."""
     st = config["stages"]["marker"]
-    unsupported = set(st["losses"]) - {"marker", "reg_pose_body", "reg_betas"}
+    unsupported = set(st["losses"]) - {"marker", "reg_pose_body", "reg_betas", "joint_accel"}
     if unsupported:
         raise NotImplementedError("marker-stage losses outside the shipped configs: %s" % sorted(unsupported))
     if st.get("use_sdf"):
         raise NotImplementedError("stages.marker.use_sdf is off in every shipped config")
     sigma = stage_robust_sigma(config, "marker")  # EXTENSION: Geman-McClure data term (0 = the reference's square)
+    w_accel = stage_joint_accel(config, "marker")  # EXTENSION: joint-acceleration term
     num_frames = pose_body.shape[0]
     leaves = [pose_body, betas, root_orient, trans]
     params = [p.detach().clone().requires_grad_(True) for p in leaves]
@@ -478,6 +503,8 @@ def _optim_markers_general(markers, pose_body, o_pose_body, betas, o_betas, root
             loss = loss + F.mse_loss(p_pose, o_pose_body) * st["losses"]["reg_pose_body"]
         if "reg_betas" in st["losses"]:
             loss = loss + F.mse_loss(p_betas, o_betas) * st["losses"]["reg_betas"]
+        if "joint_accel" in st["losses"]:  # EXTENSION: the fused closures' joint-acceleration term, composed (their checker)
+            loss = loss + joint_accel_loss(out["joints"][:, :24]) * w_accel
         loss.backward()
         if verbose:
             print("Marker", n_eval[0], float(loss))

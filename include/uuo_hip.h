@@ -172,6 +172,17 @@ typedef struct {
    * Separate kernel instantiations (the plain ones are unchanged); available inside lock-step batches.  Needs w_soft = 0.
    * robust_sigma = 0: the reference's square. */
   float robust_sigma;        /* sigma in metres (>= 0, finite) */
+  /* EXTENSION (not reference behaviour; MoSh's latent markers -- the reference's stages.marker.use_sdf appends virtual markers
+   * to its parameters, a path it cannot run): marker stage only.  w_offsets > 0 appends one rest-space offset o_m per marker
+   * column, shared by all frames and skinned with the body, to the parameters:
+   *   x = [pose 207F | betas 10 | root 9F | trans 3F | offsets 3M]
+   *   virtual marker  vm[f,m] = sum_k b[m,k] (T_R[f,a[m,k]] (vp[f,a[m,k]] + o_m) + T_t[f,a[m,k]]) + trans_f
+   *   loss = w_data (1/(F M)) sum mask rho(|x - vm|^2)  (marker_distance leaves the data term: the offset carries the stand-off)
+   *        + w_offsets (1/M) sum_m (|o_m| - marker_distance)^2  + the pose and shape priors as before
+   * One-hot and three-corner placements, with robust_sigma and the joint-acceleration term.  Refused for the chamfer and part
+   * stages, inside lock-step batches (uuo_batch_*) and by uuo_lbfgs_solve_shared.  0: off (and uuo_problem_num_params, the
+   * packing and every result are those without the field).  >= 0, finite. */
+  float w_offsets;
 } uuo_problem_t;
 
 int uuo_fit_create(uuo_model_t* model, int F, int M, uuo_fit_t** out);
@@ -185,7 +196,7 @@ int uuo_fit_destroy(uuo_fit_t* fit);
  * Refused (at evaluation) for the part stage and with w_soft != 0, and inside lock-step batches (uuo_batch_*).
  * w >= 0, finite. */
 int uuo_fit_set_joint_accel(uuo_fit_t* fit, float w);
-/* number of parameters of a stage at (F): 211F+10 / 219F+10 / 3F+11 */
+/* number of parameters of a stage at (F): 211F+10 / 219F+10 / 3F+11; the marker stage with w_offsets != 0: 219F+10+3M */
 int uuo_problem_num_params(const uuo_problem_t* p);
 
 /* One closure evaluation at d_x: writes loss to d_loss[0] and the flat gradient to d_grad.

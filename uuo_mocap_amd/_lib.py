@@ -29,6 +29,32 @@ class UuoProblem(ctypes.Structure):
         ("n_corners", c_int32), ("d_bary", c_void_p),  # marker stage on a three-corner (barycentric) placement
         ("robust_sigma", c_float),                     # EXTENSION: Geman-McClure data terms (0 = the reference's square)
     ]
+    # EXTENSION: uuo_problem_t.w_offsets (latent per-marker offsets of the marker stage; 0 = off), the C structure's last
+    # field.  It sits in the 4 bytes of tail padding after robust_sigma, so sizeof and every other offset stay as they were
+    # (ABI 3); `_fields_` keeps ending at robust_sigma and the field is named by the descriptor below (same .offset / .size
+    # as a ctypes field).
+    w_offsets = None  # (set below: needs the finished class)
+
+
+class _TailFloat:
+    """A float member of a ctypes structure at a fixed byte offset (inside its tail padding)."""
+
+    size = 4
+
+    def __init__(self, offset: int):
+        self.offset = offset
+
+    def __get__(self, obj, owner=None):
+        if obj is None:
+            return self
+        return c_float.from_buffer(obj, self.offset).value
+
+    def __set__(self, obj, value):
+        c_float.from_buffer(obj, self.offset).value = value
+
+
+UuoProblem.w_offsets = _TailFloat(UuoProblem.robust_sigma.offset + 4)
+assert UuoProblem.w_offsets.offset + 4 <= ctypes.sizeof(UuoProblem)
 
 
 class UuoLbfgsOptions(ctypes.Structure):
@@ -130,6 +156,7 @@ _DEBUG_SIGNATURES = {
     "uuo_debug_small_coeffs": (c_int, [c_int, c_int, c_int, c_void_p]),
     "uuo_debug_time_small": (c_int, [c_int, c_int, c_int, POINTER(c_float)]),
     "uuo_debug_index_map": (c_int, [c_int, c_int, c_int, c_void_p]),
+    "uuo_debug_problem_index_map": (c_int, [POINTER(UuoProblem), c_int, c_void_p]),
     "uuo_debug_staging_script": (c_int, [c_void_p, c_int, ctypes.c_longlong, c_void_p]),
 }
 

@@ -235,6 +235,8 @@ extern "C" int uuo_batch_solve(uuo_batch_t* b, void* stream, const uuo_problem_t
   int rc = 0;
   for (int i = 0; i < nb; ++i) {
     UUO_REQUIRE(problems[i].stage == b->stage, "uuo_batch_solve: every problem must be of the batch's stage");
+    UUO_REQUIRE(problems[i].w_offsets == 0.f, "uuo_batch_solve: lock-step batches do not carry the latent marker offsets "
+                "(w_offsets, extension)");
     rc = uuo_validate_problem(b->fits[i], &problems[i]);
     if (rc) return rc;
     UUO_REQUIRE(d_xs[i] != nullptr, "uuo_batch_solve: null parameter vector");
@@ -399,6 +401,9 @@ extern "C" int uuo_batch_part_scores(uuo_batch_t* b, void* stream, const uuo_pro
   const int F = b->F;
   std::vector<BatchCo> cos(nb);  // only their recorders are used
   int rc = 0;
+  for (int i = 0; i < nb; ++i)
+    UUO_REQUIRE(problems[i].w_offsets == 0.f, "uuo_batch_part_scores: lock-step batches do not carry the latent marker offsets "
+                "(w_offsets, extension)");
   for (int i = 0; i < nb && rc == 0; ++i) {
     rc = uuo_validate_problem(b->fits[i], &problems[i]);
     if (rc) break;

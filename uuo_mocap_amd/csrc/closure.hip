@@ -86,7 +86,46 @@ struct BwdArgs {
   uuo_gptr<unsigned> fin_counter;   // blocks of this launch that have published their partials (null: k_finalize follows)
   FinArgs fin;
   float acc_w;  // EXTENSION (ACCEL instantiations only): w_accel / ((F - 2) 72), the joint-acceleration term's coefficient
+  // EXTENSION (OFFS instantiations only): latent per-marker offsets (uuo_problem_t.w_offsets)
+  uuo_gptr<const float> offs;  // [markers][3] the offsets o_m (rest space), from the parameters
+  uuo_gptr<float> offs_part;   // [F][M][3] out: d loss / d o of every item (T^T g), summed over frames by k_finalize_o
+  int offs_k;                  // items per marker: 1 (one-hot) or 3 (item mode on a three-corner placement)
 };
+
+// EXTENSION: the offsets' share of the finalize (k_finalize_o / k_finalize_to, uuo_problem_t.w_offsets)
+struct OffsFinArgs {
+  uuo_gptr<const float> part;  // [F][M K][3] per-item d loss / d o left by the OFFS backward kernels
+  uuo_gptr<const float> o;     // [M][3] the offsets
+  uuo_gptr<float> g;           // [M][3] out: their gradient (a dense run of the solver's packing)
+  uuo_gptr<const float> dir;   // optional: the direction's entries of the offsets
+  int M, K;                    // markers, items per marker (1 one-hot, 3 three-corner)
+  double cprior;               // w_offsets / M
+  float d0;                    // the prior's stand-off length (marker_distance)
+};
+
+// the offsets' data gradient of one (marker, component): frames grp, grp + G, ... of the per-item partials, K items per marker
+// summed per frame in fp32, the frames in double, in a fixed order; 16 frames (16 K loads) in flight per round
+template <int K>
+__device__ __forceinline__ double offs_frame_sum(const float* __restrict__ base, int grp, int G, int F, size_t frame_stride) {
+  double acc = 0.0;
+  for (int f0 = grp; f0 < F; f0 += 16 * G) {
+    float v[16][K];
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+      const int f = f0 + G * u;
+#pragma unroll
+      for (int k = 0; k < K; ++k) v[u][k] = (f < F) ? base[(size_t)f * frame_stride + 3 * k] : 0.f;
+    }
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+      float s = v[u][0];
+#pragma unroll
+      for (int k = 1; k < K; ++k) s += v[u][k];
+      acc += (double)s;
+    }
+  }
+  return acc;
+}
 
 // ----------------------------------------------------------------------------------------------------
 // K_D  finalize: sums the per-frame partials in a fixed order (double accumulators), adds the shape
@@ -100,8 +139,13 @@ struct BwdArgs {
 // report is written without a cache write-back (see bwd_body's tail).
 // ACCEL (EXTENSION): slot 3 of every frame holds that frame's share of the joint-acceleration term, already scaled (bwd_body);
 // it joins the loss.  A separate instantiation (k_finalize_t), so that k_finalize keeps its code.
-template <int NT, bool COHERENT, bool ACCEL = false>
-__device__ __forceinline__ void finalize_body(const FinArgs& a) {
+// OFFS (EXTENSION, uuo_problem_t.w_offsets > 0): `ob` describes the latent marker offsets.  Their data gradient is the sum of
+// the per-item partials over frames and over a marker's items (no atomics: groups of frames summed in double in a fixed order,
+// then the groups in order); the prior w/M sum_m (|o_m| - d0)^2 adds (2 w/M)(|o_m| - d0) o_m/|o_m| (0 at o_m = 0) and its loss.
+// The offsets' entries join the loss and the fused statistics.  Separate instantiations (k_finalize_o, k_finalize_to).
+template <int NT, bool COHERENT, bool ACCEL = false, bool OFFS = false>
+__device__ __forceinline__ void finalize_body(const FinArgs& a, const OffsFinArgs* ob = nullptr) {
+  static_assert(!OFFS || (NT == 1024 && !COHERENT), "the offsets' reduction is built for the separate 1024-thread finalize");
   __builtin_amdgcn_s_setprio(3);  // latency-bound kernel: do not queue behind co-resident MFMA waves
   __shared__ double sh[32][32];
   const int tid = threadIdx.x;
@@ -159,6 +203,63 @@ __device__ __forceinline__ void finalize_body(const FinArgs& a) {
     sh[0][tid] = s;
   }
   __syncthreads();
+  // OFFS: {g.d, sum|g|, g.g, max|g|, prior sum (|o| - d0)^2} over the offsets' entries, for thread 0 below
+  double so_tot[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  if constexpr (OFFS) {
+    __shared__ double so_grp[1024];
+    __shared__ double so_st[5][32];
+    __shared__ double so_sum[5];
+    const OffsFinArgs& o = *ob;
+    const int C = 3 * o.M, MK = o.M * o.K;
+    double t_sd = 0.0, t_s1 = 0.0, t_s2 = 0.0, t_sm = 0.0, t_pl = 0.0;
+    for (int i0 = 0; i0 < C; i0 += 1024) {  // chunks of <= 1024 entries; G groups of frames per entry
+      const int Cc = min(C - i0, 1024), G = 1024 / Cc;
+      if (tid < G * Cc) {
+        const int grp = tid / Cc, i = i0 + (tid - grp * Cc), mk = i / 3, c = i - 3 * mk;
+        const float* base = o.part.get() + (size_t)mk * o.K * 3 + c;
+        so_grp[tid] = (o.K == 3) ? offs_frame_sum<3>(base, grp, G, a.F, (size_t)MK * 3)
+                                 : offs_frame_sum<1>(base, grp, G, a.F, (size_t)MK * 3);
+      }
+      __syncthreads();
+      if (tid < Cc) {
+        const int i = i0 + tid, mk = i / 3, c = i - 3 * mk;
+        double s = so_grp[tid];
+        for (int grp = 1; grp < G; ++grp) s += so_grp[grp * Cc + tid];
+        const float o0 = o.o[mk * 3], o1 = o.o[mk * 3 + 1], o2 = o.o[mk * 3 + 2];
+        const double r = sqrt((double)o0 * o0 + (double)o1 * o1 + (double)o2 * o2), e = r - (double)o.d0;
+        const double oc = (c == 0) ? o0 : ((c == 1) ? o1 : o2);
+        if (r > 0.0) s += 2.0 * o.cprior * e * oc / r;
+        if (c == 0) t_pl += e * e;
+        const float gf = (float)s;
+        o.g[i] = gf;
+        if (o.dir) t_sd += (double)gf * (double)o.dir[i];
+        t_s1 += fabs((double)gf);
+        t_s2 += (double)gf * (double)gf;
+        t_sm = fmax(t_sm, fabs((double)gf));
+      }
+      __syncthreads();
+    }
+    // fixed-order reduction of the threads' statistics: 32 runs of 32 threads, then the runs
+    const double tv[5] = {t_sd, t_s1, t_s2, t_sm, t_pl};
+    for (int q = 0; q < 5; ++q) {
+      so_grp[tid] = tv[q];
+      __syncthreads();
+      if (tid < 32) {
+        double s = 0.0;
+        for (int u = 0; u < 32; ++u) s = (q == 3) ? fmax(s, so_grp[tid * 32 + u]) : s + so_grp[tid * 32 + u];
+        so_st[q][tid] = s;
+      }
+      __syncthreads();
+    }
+    if (tid < 5) {
+      double s = 0.0;
+      for (int u = 0; u < 32; ++u) s = (tid == 3) ? fmax(s, so_st[tid][u]) : s + so_st[tid][u];
+      so_sum[tid] = s;
+    }
+    __syncthreads();
+    if (tid == 0)
+      for (int q = 0; q < 5; ++q) so_tot[q] = so_sum[q];
+  }
   if (tid == 0) {
     double bsq = 0.0, sd = sh[0][16], s1 = sh[0][17], s2 = sh[0][18], sm = sh[0][19];
     for (int l = 0; l < 10; ++l) {
@@ -172,14 +273,27 @@ __device__ __forceinline__ void finalize_body(const FinArgs& a) {
       sm = fmax(sm, fabs((double)gb));
     }
     float lossf;
-    if constexpr (ACCEL)
+    if constexpr (OFFS) {
+      sd += so_tot[0];
+      s1 += so_tot[1];
+      s2 += so_tot[2];
+      sm = fmax(sm, so_tot[3]);
+      const double l = a.closs * sh[0][0] + a.cpose * sh[0][2] + a.cbetas * bsq + ob->cprior * so_tot[4];
+      lossf = (float)(ACCEL ? l + sh[0][3] : l);
+    } else if constexpr (ACCEL) {
       lossf = (float)(a.closs * sh[0][0] + a.cpose * sh[0][2] + a.cbetas * bsq + sh[0][3]);
-    else
+    } else {
       lossf = (float)(a.closs * sh[0][0] + a.cpose * sh[0][2] + a.cbetas * bsq);
+    }
     a.loss[0] = lossf;
     // the statistics of this problem's OWN parameters (everything but the shape vector), for solves that share the betas
     // with other ranks (uuo_lbfgs_solve_shared: the betas' gradient is summed over the ranks before it enters any norm)
     double own1 = sh[0][17], own2 = sh[0][18], ownm = sh[0][19];
+    if constexpr (OFFS) {
+      own1 += so_tot[1];
+      own2 += so_tot[2];
+      ownm = fmax(ownm, so_tot[3]);
+    }
     float gb_local[10];
 #pragma unroll
     for (int l = 0; l < 10; ++l) gb_local[l] = (float)(sh[0][4 + l] + 2.0 * a.cbetas * ((double)pb[l] - (double)po[l]));
@@ -304,8 +418,15 @@ __device__ __forceinline__ float gmof_q(float sig2, float s) { return sig2 / (si
 // dL/dJ_f in where SmplInference.forward's joint gradient enters (sdGt; the translation gets its sum) and writes its own
 // acc_w |a_f|^2 to slot 3 of its partials (k_finalize_t adds it to the loss).  Everything downstream -- the kinematic sweep, the
 // Gram-Schmidt backward, the priors, the solver's fused statistics -- is the existing code.  Separate instantiations.
-template <bool PART = false, int NWV = BWD_NW, bool DENSE = false, bool ITEMS = false, bool ROBUST = false, bool ACCEL = false>
+// OFFS (EXTENSION, uuo_problem_t.w_offsets > 0): latent per-marker offsets.  Item mm belongs to marker mm / offs_k; its
+// rest-space position is vp + o_m wherever it enters (the skinned position and the dA outer product), and its d loss / d o =
+// T^T g (dvp, which the blend gradients use too) goes to offs_part[f][mm] for k_finalize_o.  The host launches these with
+// d0 = 0 (the offset carries the stand-off), so the marker branch is the plain square.  Separate instantiations.
+template <bool PART = false, int NWV = BWD_NW, bool DENSE = false, bool ITEMS = false, bool ROBUST = false, bool ACCEL = false,
+          bool OFFS = false>
 __device__ __forceinline__ void bwd_body(const BwdArgs& a) {
+  static_assert(!OFFS || (!PART && !DENSE && NWV == BWD_NW), "the latent marker offsets are built for the marker stage's "
+                "sparse kernels only");
   static_assert(!ROBUST || (!DENSE && !ITEMS), "the robust data term is formed on the sparse items (k_bary_fwd for item mode)");
   static_assert(!ACCEL || (!PART && !DENSE && NWV == BWD_NW), "the joint-acceleration term is built for the fitted stages' "
                 "sparse kernels (chamfer, marker) only");
@@ -443,6 +564,7 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a) {
       float x0, x1, x2, wgt, d2, vt0, vt1, vt2, st0, st1, st2;
       int4 wi;
       float4 ww;
+      float o[OFFS ? 3 : 1];  // OFFS: the item's marker offset
     };
     auto fetch16 = [&](int m, Item16& q) {
       // items past M (or masked out) are processed with weight 0 on vertex 0: every contribution is scaled by it
@@ -510,6 +632,10 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a) {
       q.st2 = (sl < 10) ? ps[20] : 0.f;
       q.wi = *reinterpret_cast<const int4*>(a.Wi + (size_t)vi * 4);
       q.ww = *reinterpret_cast<const float4*>(a.Ww + (size_t)vi * 4);
+      if constexpr (OFFS) {
+        const float* po = a.offs + (size_t)(mm / a.offs_k) * 3;
+        q.o[0] = po[0]; q.o[1] = po[1]; q.o[2] = po[2];
+      }
     };
     auto row_sum = [](float v) {  // sum over the 16 lanes of the DPP row, left on every lane of the row
       v += dpp_rot<0x128>(v);
@@ -539,6 +665,11 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a) {
         vp[0] = row_sum(s0) + (cur.vt0 + row_sum(cur.st0 * beta_s));
         vp[1] = row_sum(s1) + (cur.vt1 + row_sum(cur.st1 * beta_s));
         vp[2] = row_sum(s2) + (cur.vt2 + row_sum(cur.st2 * beta_s));
+      }
+      if constexpr (OFFS) {  // the item's rest-space point: vertex + its marker's offset (transform and dA operand below)
+        vp[0] += cur.o[0];
+        vp[1] += cur.o[1];
+        vp[2] += cur.o[2];
       }
       float T[12];
 #pragma unroll
@@ -589,6 +720,10 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a) {
       float dvp[3];
 #pragma unroll
       for (int c = 0; c < 3; ++c) dvp[c] = fmaf(T[8 + c], g[2], fmaf(T[4 + c], g[1], T[c] * g[0]));
+      if constexpr (OFFS) {  // d loss / d o of this item (sub-lanes 0..2 store one component each)
+        const int mi = slot + SLOTS * r;
+        if (mi < M && sl < 3) a.offs_part[((size_t)f * M + mi) * 3 + sl] = (sl == 0) ? dvp[0] : ((sl == 1) ? dvp[1] : dvp[2]);
+      }
       if constexpr (!PART) {
 #pragma unroll
         for (int t = 0; t < 13; ++t)
@@ -984,6 +1119,24 @@ __global__ __launch_bounds__(BWD_NW * 64) void k_bwd_dense(BwdArgs a) { bwd_body
 __global__ __launch_bounds__(BWD_NW * 64) void k_bwd_items(BwdArgs a) { bwd_body<false, BWD_NW, false, true>(a); }
 // EXTENSION: the same with the joint-acceleration term (k_bary_fwd / k_bary_fwd_r before it, plain or robust)
 __global__ __launch_bounds__(BWD_NW * 64) void k_bwd_items_t(BwdArgs a) { bwd_body<false, BWD_NW, false, true, false, true>(a); }
+// EXTENSION: latent per-marker offsets (uuo_problem_t.w_offsets): the one-hot marker closure -- plain, robust, with the
+// joint-acceleration term, both -- and the item kernels of the three-corner placement (k_bary_fwd_o / _ro before them)
+__global__ __launch_bounds__(BWD_NW * 64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_bwd_sparse_o(BwdArgs a) {
+  bwd_body<false, BWD_NW, false, false, false, false, true>(a);
+}
+__global__ __launch_bounds__(BWD_NW * 64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_bwd_sparse_r_o(BwdArgs a) {
+  bwd_body<false, BWD_NW, false, false, true, false, true>(a);
+}
+__global__ __launch_bounds__(BWD_NW * 64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_bwd_sparse_t_o(BwdArgs a) {
+  bwd_body<false, BWD_NW, false, false, false, true, true>(a);
+}
+__global__ __launch_bounds__(BWD_NW * 64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_bwd_sparse_r_t_o(BwdArgs a) {
+  bwd_body<false, BWD_NW, false, false, true, true, true>(a);
+}
+__global__ __launch_bounds__(BWD_NW * 64) void k_bwd_items_o(BwdArgs a) { bwd_body<false, BWD_NW, false, true, false, false, true>(a); }
+__global__ __launch_bounds__(BWD_NW * 64) void k_bwd_items_t_o(BwdArgs a) {
+  bwd_body<false, BWD_NW, false, true, false, true, true>(a);
+}
 
 // ----------------------------------------------------------------------------------------------------
 // Marker stage on a three-corner (barycentric) placement (reference optimization.py:345-351 with the placement of
@@ -1007,9 +1160,11 @@ struct BaryFwdArgs {
   uuo_gptr<float> frames;        // [F][FrameLds]: left for k_bwd_items of the same evaluation
   uuo_gptr<float> up_items;      // [F][3 M][3]
   uuo_gptr<float> item_loss;     // [F]
+  uuo_gptr<const float> offs;    // [M][3] latent marker offsets (OFFS instantiations only; extension)
 };
 // ROBUST (EXTENSION): the term is w rho((|x - vm| - d0)^2), Geman-McClure (gmof_q); a separate instantiation, k_bary_fwd_r
-template <bool ROBUST>
+// OFFS (EXTENSION, uuo_problem_t.w_offsets > 0): every corner is skinned at vp + o_m (k_bary_fwd_o / _ro; launched with d0 = 0)
+template <bool ROBUST, bool OFFS = false>
 __device__ __forceinline__ void bary_fwd_body(const BaryFwdArgs& a) {
   constexpr int NT = BWD_NW * 64, SLOTS = BWD_NW * 4;
   __shared__ FrameLds L;
@@ -1061,6 +1216,10 @@ __device__ __forceinline__ void bary_fwd_body(const BaryFwdArgs& a) {
     const int mm = in ? m : 0;
     const float wgt = in ? a.mask[(size_t)f * M + mm] : 0.f;
     float vm[3] = {0.f, 0.f, 0.f}, bk[3];
+    float om[3] = {0.f, 0.f, 0.f};
+    if constexpr (OFFS) {
+      om[0] = a.offs[mm * 3]; om[1] = a.offs[mm * 3 + 1]; om[2] = a.offs[mm * 3 + 2];
+    }
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
       int vi = a.assign3[mm * 3 + k];
@@ -1080,6 +1239,11 @@ __device__ __forceinline__ void bary_fwd_body(const BaryFwdArgs& a) {
       vp[0] = row_sum(s0) + (a.vt[(size_t)vi * 3] + row_sum(st0 * beta_s));
       vp[1] = row_sum(s1) + (a.vt[(size_t)vi * 3 + 1] + row_sum(st1 * beta_s));
       vp[2] = row_sum(s2) + (a.vt[(size_t)vi * 3 + 2] + row_sum(st2 * beta_s));
+      if constexpr (OFFS) {
+        vp[0] += om[0];
+        vp[1] += om[1];
+        vp[2] += om[2];
+      }
       const int4 wi = *reinterpret_cast<const int4*>(a.Wi + (size_t)vi * 4);
       const float4 w4 = *reinterpret_cast<const float4*>(a.Ww + (size_t)vi * 4);
       const int wj[4] = {wi.x, wi.y, wi.z, wi.w};
@@ -1129,6 +1293,9 @@ __device__ __forceinline__ void bary_fwd_body(const BaryFwdArgs& a) {
 }
 __global__ __launch_bounds__(BWD_NW * 64) void k_bary_fwd(BaryFwdArgs a) { bary_fwd_body<false>(a); }
 __global__ __launch_bounds__(BWD_NW * 64) void k_bary_fwd_r(BaryFwdArgs a) { bary_fwd_body<true>(a); }
+// EXTENSION: with the latent marker offsets (uuo_problem_t.w_offsets)
+__global__ __launch_bounds__(BWD_NW * 64) void k_bary_fwd_o(BaryFwdArgs a) { bary_fwd_body<false, true>(a); }
+__global__ __launch_bounds__(BWD_NW * 64) void k_bary_fwd_ro(BaryFwdArgs a) { bary_fwd_body<true, true>(a); }
 // part stage on its cached pose blend: a fraction of the registers and two thirds of the LDS of the general kernel
 // two forms: one wave per frame for <= 16 markers (the candidate search: four items per pass), four waves per frame above
 // that (hmr_full.yaml: 50 markers on the full skeleton would be 13 passes of one wave)
@@ -1157,6 +1324,9 @@ __global__ __launch_bounds__(BWD_NW * 64) void k_bwd_part_b_r(const BwdArgs* __r
 __global__ __launch_bounds__(1024) void k_finalize(FinArgs a) { finalize_body<1024, false>(a); }
 // EXTENSION: with the joint-acceleration term's per-frame shares (after the *_t backward kernels)
 __global__ __launch_bounds__(1024) void k_finalize_t(FinArgs a) { finalize_body<1024, false, true>(a); }
+// EXTENSION: with the latent marker offsets (after the *_o backward kernels), without and with the joint-acceleration term
+__global__ __launch_bounds__(1024) void k_finalize_o(FinArgs a, OffsFinArgs o) { finalize_body<1024, false, false, true>(a, &o); }
+__global__ __launch_bounds__(1024) void k_finalize_to(FinArgs a, OffsFinArgs o) { finalize_body<1024, false, true, true>(a, &o); }
 __global__ __launch_bounds__(1024) void k_finalize_b(const FinArgs* __restrict__ batch) {
   UUO_BATCH_PICK(FinArgs, batch)
   finalize_body<1024, false>(a);
@@ -1193,6 +1363,7 @@ int uuo_batched_launch_closure(int op, hipStream_t s, const void* d_args, int co
 struct StageLayout {
   int n, off_trans, off_z, off_betas, off_pose, off_root;
   int gs_pose = 9, gs_root = 9;  // floats per rotation
+  int off_offs = -1;             // EXTENSION: the latent marker offsets (problem_layout; -1 = absent)
 };
 
 // `compact`: the SOLVER's packing of the gradient / direction / history vectors (never of the parameters themselves): the
@@ -1232,9 +1403,23 @@ static StageLayout stage_layout(int stage, int F, bool compact = false) {
   return s;
 }
 
+// EXTENSION: does this problem carry the latent marker offsets (uuo_problem_t.w_offsets; validate_problem checks the rest)?
+static bool has_offsets(const uuo_problem_t* p) { return p->stage == UUO_STAGE_MARKER && p->w_offsets != 0.f && p->M > 0; }
+
+// stage_layout of a problem: the marker stage with latent offsets appends them, 3 M floats after trans, in both packings (the
+// compact packing leaves out rotation rows only)
+static StageLayout problem_layout(const uuo_problem_t* p, bool compact = false) {
+  StageLayout s = stage_layout(p->stage, p->F, compact);
+  if (has_offsets(p)) {
+    s.off_offs = s.n;
+    s.n += 3 * p->M;
+  }
+  return s;
+}
+
 extern "C" int uuo_problem_num_params(const uuo_problem_t* p) {
   if (!p || p->F <= 0 || p->stage < 0 || p->stage > 2) return -22;
-  return stage_layout(p->stage, p->F).n;
+  return problem_layout(p).n;
 }
 
 static int validate_problem(const uuo_fit* fit, const uuo_problem_t* p) {
@@ -1265,6 +1450,13 @@ static int validate_problem(const uuo_fit* fit, const uuo_problem_t* p) {
   UUO_REQUIRE(fit->joint_accel == 0.f || p->w_soft == 0.f,
               "closure: the joint-acceleration term (uuo_fit_set_joint_accel, extension) is not built for the soft-assignment "
               "data term (w_soft)");
+  // EXTENSION: latent marker offsets
+  UUO_REQUIRE(p->w_offsets == 0.f || (p->w_offsets > 0.f && p->w_offsets <= 3.0e38f),
+              "closure: w_offsets (latent marker offsets, extension) must be 0 (off) or a positive finite weight");
+  UUO_REQUIRE(p->w_offsets == 0.f || p->stage == UUO_STAGE_MARKER,
+              "closure: w_offsets (latent marker offsets, extension) is built for the marker stage only");
+  UUO_REQUIRE(p->w_offsets == 0.f || !uuo_recorder,
+              "closure: lock-step batches do not carry the latent marker offsets (w_offsets, extension)");
   return 0;
 }
 
@@ -1451,7 +1643,7 @@ static int closure_forward(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, 
 int uuo_validate_problem(const uuo_fit* fit, const uuo_problem_t* p) { return validate_problem(fit, p); }
 
 int uuo_closure_forward_at(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, const float* d_x) {
-  const StageLayout lay = stage_layout(p->stage, p->F);
+  const StageLayout lay = problem_layout(p);
   const UuoPoseSrc src = stage_pose_src(p, lay, d_x);
   return closure_forward(fit, s, p, src, true);
 }
@@ -1575,8 +1767,7 @@ UuoIndexMap uuo_stage_index_map(const uuo_problem_t* p, bool compact) {
   UuoIndexMap m;
   std::memset(&m, 0, sizeof(m));
   if (!compact) return m;
-  const int F = p->F;
-  const StageLayout full = stage_layout(p->stage, F), c = stage_layout(p->stage, F, true);
+  const StageLayout full = problem_layout(p), c = problem_layout(p, true);
   auto add = [&](int cb, int fo, int k69) {
     m.cb[m.nseg] = cb;
     m.fo[m.nseg] = fo;
@@ -1590,7 +1781,8 @@ UuoIndexMap uuo_stage_index_map(const uuo_problem_t* p, bool compact) {
     add(0, 0, 1);                          // body rotations
     add(c.off_betas, full.off_betas, 0);   // betas
     add(c.off_root, full.off_root, 1);     // root rotations
-    add(c.off_trans, full.off_trans, 0);   // trans
+    add(c.off_trans, full.off_trans, 0);   // trans, and the latent marker offsets (extension) that follow it densely in both
+                                           // packings (c.off_offs - c.off_trans == full.off_offs - full.off_trans == 3F): one run
   }
   m.cb[m.nseg] = c.n;
   m.n_act = c.n;
@@ -1605,8 +1797,8 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
   int rc = 0;
   const uuo_model* m = fit->model;
   const int F = p->F, M = p->M;
-  const StageLayout lay = stage_layout(p->stage, F);            // the parameters: always the reference's packing
-  const StageLayout gl = stage_layout(p->stage, F, compact);    // gradient and direction: the solver's packing
+  const StageLayout lay = problem_layout(p);            // the parameters: always the reference's packing
+  const StageLayout gl = problem_layout(p, compact);    // gradient and direction: the solver's packing
   const UuoPoseSrc src = stage_pose_src(p, lay, d_x);
   const bool soft_chamfer = p->stage == UUO_STAGE_CHAMFER && p->w_soft != 0.f;
   bool have_vp = false;
@@ -1653,7 +1845,10 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
   a.raw_root = (p->stage == UUO_STAGE_MARKER) ? d_x + lay.off_root : nullptr;
   a.cg = (float)(2.0 * data_c);
   a.cpose = (p->stage == UUO_STAGE_PART) ? 0.f : (float)(2.0 * (double)p->w_pose / ((double)F * 207.0));
-  a.d0 = p->marker_distance;
+  // EXTENSION: latent marker offsets -- the *_o instantiations, d0 = 0 in the data term (the offsets carry the stand-off)
+  const bool offs = has_offsets(p);
+  UUO_REQUIRE(!offs || !uuo_recorder, "closure: lock-step batches do not carry the latent marker offsets");
+  a.d0 = offs ? 0.f : p->marker_distance;
   // EXTENSION: Geman-McClure data terms run on the *_r instantiations (validate_problem: sigma^2 is a normal fp32 value)
   const bool robust = p->robust_sigma > 0.f;
   a.rs2 = robust ? (float)((double)p->robust_sigma * (double)p->robust_sigma) : 0.f;
@@ -1694,6 +1889,23 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
   fa.rep_seq = report ? report->seq : 0ull;
   fa.h.gx = 1;
   fa.h.gy = 1;
+  OffsFinArgs oa;
+  std::memset(&oa, 0, sizeof(oa));
+  if (offs) {
+    // per-item partials [F][items][3]: items = M (one-hot) or 3 M (three-corner); allocated on the first such evaluation
+    if (!fit->offs_part) UUO_HIP_CHECK(hipMalloc((void**)&fit->offs_part, (size_t)F * 3 * M * 3 * sizeof(float)));
+    a.offs = d_x + lay.off_offs;
+    a.offs_part = fit->offs_part;
+    a.offs_k = (p->n_corners == 3) ? 3 : 1;
+    oa.part = fit->offs_part;
+    oa.o = d_x + lay.off_offs;
+    oa.g = d_grad + gl.off_offs;
+    oa.dir = d_dir ? d_dir + gl.off_offs : nullptr;
+    oa.M = M;
+    oa.K = a.offs_k;
+    oa.cprior = (double)p->w_offsets / (double)M;
+    oa.d0 = p->marker_distance;
+  }
   bool fin_fused = false;
   const int part_general = UUO_ENV_INT("UUO_PART_GENERAL_BWD", 0);  // debug flavour only: the general kernel, for comparison
   if (p->stage == UUO_STAGE_PART && p->pose_cache_id != 0 && fit->pose_cache_id == p->pose_cache_id && !part_general) {
@@ -1730,12 +1942,15 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
     b.assign3 = p->d_assign;
     b.bary = p->d_bary;
     b.cg = a.cg;
-    b.d0 = p->marker_distance;
+    b.d0 = a.d0;
     b.rs2 = a.rs2;
+    b.offs = a.offs;
     b.frames = fit->frames;
     b.up_items = items;
     b.item_loss = item_loss;
-    if (robust)
+    if (offs)
+      hipLaunchKernelGGL(robust ? k_bary_fwd_ro : k_bary_fwd_o, dim3(F), dim3(BWD_NW * 64), 0, s, b);
+    else if (robust)
       hipLaunchKernelGGL(k_bary_fwd_r, dim3(F), dim3(BWD_NW * 64), 0, s, b);
     else
       hipLaunchKernelGGL(k_bary_fwd, dim3(F), dim3(BWD_NW * 64), 0, s, b);
@@ -1743,7 +1958,9 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
     a.up_items = items;
     a.item_loss = item_loss;
     a.frames = fit->frames;
-    if (accel)
+    if (offs)
+      hipLaunchKernelGGL(accel ? k_bwd_items_t_o : k_bwd_items_o, dim3(F), dim3(BWD_NW * 64), 0, s, a);
+    else if (accel)
       hipLaunchKernelGGL(k_bwd_items_t, dim3(F), dim3(BWD_NW * 64), 0, s, a);
     else
       hipLaunchKernelGGL(k_bwd_items, dim3(F), dim3(BWD_NW * 64), 0, s, a);
@@ -1768,12 +1985,23 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
 #define UUO_FIN_FUSED 1  // (0: A/B builds of tools/build_variant.sh)
 #endif
     const int fin_unfused = UUO_ENV_INT("UUO_FIN_UNFUSED", !UUO_FIN_FUSED);  // debug flavour only: the separate k_finalize, for comparison
-    if (!fin_unfused) {
+    if (!fin_unfused && !offs) {  // (the offsets' reduction lives in the separate k_finalize_o)
       a.fin = fa;
       a.fin_counter = reinterpret_cast<unsigned*>(fit->scalars + 32);
       fin_fused = true;
     }
-    if (accel) {
+    if (offs) {
+      // EXTENSION: latent marker offsets (the marker stage's one-hot closure); with the joint-acceleration term the pose-prep
+      // launch below comes first for the same reason as there
+      if (accel) {
+        rc = uuo_launch_pose_prep(m, s, F, src, fit->pfaT, fit->A, nullptr, fit->frames);
+        if (rc) return rc;
+        a.frames = fit->frames;
+        hipLaunchKernelGGL(robust ? k_bwd_sparse_r_t_o : k_bwd_sparse_t_o, dim3(F), dim3(BWD_NW * 64), 0, s, a);
+      } else {
+        hipLaunchKernelGGL(robust ? k_bwd_sparse_r_o : k_bwd_sparse_o, dim3(F), dim3(BWD_NW * 64), 0, s, a);
+      }
+    } else if (accel) {
       // EXTENSION: the block of frame f reads its neighbours' world joints.  The marker stage's closure has no forward of its
       // own (its backward re-runs each frame's kinematic chain): a pose-prep launch leaves every frame's FrameLds first, and the
       // backward blocks start from them
@@ -1794,7 +2022,9 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
   }
   UUO_HIP_CHECK(hipGetLastError());
   if (!fin_fused) {
-    if (accel)
+    if (offs)
+      hipLaunchKernelGGL(accel ? k_finalize_to : k_finalize_o, dim3(1), dim3(1024), 0, s, fa, oa);
+    else if (accel)
       hipLaunchKernelGGL(k_finalize_t, dim3(1), dim3(1024), 0, s, fa);
     else if (!uuo_record(UUO_OP_FIN, 1, 1, fa))
       hipLaunchKernelGGL(k_finalize, dim3(1), dim3(1024), 0, s, fa);
@@ -1821,7 +2051,7 @@ extern "C" int uuo_time_closure(uuo_fit_t* fit, void* stream, const uuo_problem_
   if (rc) return rc;
   UUO_REQUIRE(d_x && ms_per_eval && iters > 0, "uuo_time_closure: bad arguments");
   hipStream_t s = (hipStream_t)stream;
-  const StageLayout lay = stage_layout(p->stage, p->F);
+  const StageLayout lay = problem_layout(p);
   float* loss = fit->scalars + 8;
   float* grad = fit->vecs;  // work vector 0
   rc = uuo_ensure_mask(fit, s, p);
@@ -1880,6 +2110,14 @@ extern "C" int uuo_debug_index_map(int stage, int F, int compact, int* h_out) {
   p.F = F;
   const UuoIndexMap m = uuo_stage_index_map(&p, compact != 0 && stage != UUO_STAGE_PART);
   const int n = m.nseg ? m.n_act : stage_layout(stage, F).n;
+  for (int c = 0; c < n; ++c) h_out[c] = m.full(c);
+  return n;
+}
+// the same for a whole problem (stage, F, M, w_offsets: the latent marker offsets' coordinates included)
+extern "C" int uuo_debug_problem_index_map(const uuo_problem_t* p, int compact, int* h_out) {
+  UUO_REQUIRE(p && p->stage >= 0 && p->stage <= 2 && p->F > 0 && h_out, "uuo_debug_problem_index_map: bad arguments");
+  const UuoIndexMap m = uuo_stage_index_map(p, compact != 0 && p->stage != UUO_STAGE_PART);
+  const int n = m.nseg ? m.n_act : problem_layout(p).n;
   for (int c = 0; c < n; ++c) h_out[c] = m.full(c);
   return n;
 }

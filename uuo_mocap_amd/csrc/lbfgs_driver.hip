@@ -689,7 +689,7 @@ int fit_create_impl(uuo_model_t* model, int F, int M, uuo_fit_t** out, bool sync
   fit->F = F;
   fit->M = M;
   fit->nFT = (F + UUO_FT - 1) / UUO_FT;
-  fit->n_max = 219 * F + 10;
+  fit->n_max = 219 * F + 10 + 3 * M;
   const int nFT = fit->nFT;
   // one device allocation and one zero fill for the whole workspace (a lock-step batch creates hundreds of these)
   hipError_t e = hipSuccess;
@@ -743,6 +743,7 @@ extern "C" int uuo_fit_destroy(uuo_fit_t* fit) {
   if (fit->soft_gV) (void)hipFree(fit->soft_gV);
   if (fit->soft_sm) (void)hipFree(fit->soft_sm);
   if (fit->bary_items) (void)hipFree(fit->bary_items);
+  if (fit->offs_part) (void)hipFree(fit->offs_part);
   if (fit->dbg_verts) (void)hipFree(fit->dbg_verts);
   if (fit->ev0) (void)hipEventDestroy(fit->ev0);
   if (fit->ev1) (void)hipEventDestroy(fit->ev1);
@@ -795,6 +796,9 @@ static int shared_prepare(uuo_fit_t* fit, hipStream_t s, const uuo_problem_t* p,
   UUO_REQUIRE(d_x && opt && stats, "uuo_lbfgs_solve_shared: null argument");
   UUO_REQUIRE(opt->max_iter > 0, "uuo_lbfgs_solve_shared: max_iter must be positive");
   UUO_REQUIRE(uuo_recorder == nullptr, "uuo_lbfgs_solve_shared: not inside a lock-step batch");
+  // EXTENSION: the per-evaluation exchange carries the betas' share only, not the latent marker offsets
+  UUO_REQUIRE(p->w_offsets == 0.f, "uuo_lbfgs_solve_shared: shared-betas solves do not carry the latent marker offsets (w_offsets, "
+              "extension)");
   const int hist = opt->history_size > 0 ? opt->history_size : 100;
   const int n_params = uuo_problem_num_params(p);
   LbWs* w = (LbWs*)fit->lbws;

@@ -158,7 +158,7 @@ struct UuoPoseSrc {
 struct uuo_fit {
   uuo_model* model = nullptr;
   int F = 0, M = 0, nFT = 0;
-  int n_max = 0;  // 219F+10
+  int n_max = 0;  // 219F+10+3M (the marker stage with latent offsets: the largest parameter vector of the workspace)
   // closure workspace
   float* pfaT = nullptr;            // [nFT][14][64][4]: A operand (pose features | betas) in MFMA-operand order
   void* pfa16 = nullptr;            // [nFT][7][2][64][8] halfs: the same operand * UUO_SK16_ASCALE as two fp16 planes (k_skin3)
@@ -173,6 +173,7 @@ struct uuo_fit {
   float* soft_sm = nullptr;
   float* dbg_verts = nullptr;          // debug flavour, UUO_SKIN_F16_CHECK: the fp32 kernel's vertices and boxes beside k_skin3's (first use)
   float* bary_items = nullptr;         // marker stage on a three-corner placement: [F][3 M][3] corner items + [F] loss sums (first use)
+  float* offs_part = nullptr;          // EXTENSION, latent marker offsets: [F][<= 3 M][3] per-item d loss / d o (first use)
   int* nn_flags = nullptr;          // [F][8] survivor counts of the pruned nearest-neighbour search (debug / tests)
   unsigned long long* nn = nullptr; // [F][M] packed (dist bits << 32 | idx)
   float* frame_part = nullptr;      // [F][UUO_FP]: loss, dz, pose sq, dbeta[10], gradient statistics

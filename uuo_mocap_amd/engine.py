@@ -164,6 +164,9 @@ def solve_batch(problems, xs, max_iter: int, lr: float = 1.0, tolerance_grad: fl
     if any(p.joint_accel != 0.0 for p in problems):
         raise NotImplementedError("lock-step batches do not carry the joint-acceleration term (joint_accel, extension): "
                                   "solve such problems one by one")
+    if any(p.problem.w_offsets != 0.0 for p in problems):
+        raise NotImplementedError("lock-step batches do not carry the latent marker offsets (latent_offsets, extension): "
+                                  "solve such problems one by one")
     for p, x in zip(problems, xs):
         assert p.stage == p0.stage and p.F == p0.F and p.M == p0.M and p.model is model
         assert x.is_cuda and x.dtype == torch.float32 and x.numel() == p.n and x.is_contiguous()
@@ -632,6 +635,18 @@ def stage_joint_accel(config: Dict, stage: str) -> float:
     return v
 
 
+def stage_latent_offsets(config: Dict) -> float:
+    """EXTENSION: stages.marker.losses.latent_offsets of a config -- the weight w of the latent per-marker offsets of the marker
+    stage (uuo_problem_t.w_offsets): one rest-space offset per marker column, shared by all frames and skinned with the body,
+    with the prior w (1/M) sum_m (|o_m| - MARKER_DISTANCE)^2.  Absent or 0 = off; negative or non-finite weights are refused.
+    (The chamfer and part stages refuse the key with their other unknown losses.)"""
+    v = (config["stages"]["marker"].get("losses") or {}).get("latent_offsets", 0.0)
+    v = 0.0 if v is None else float(v)
+    if not math.isfinite(v) or v < 0.0:
+        raise ValueError("stages.marker.losses.latent_offsets must be 0 (off) or a positive weight (got %r)" % (v,))
+    return v
+
+
 def _cfg_weights(losses: Dict, data_key: str):
     return (float(losses.get(data_key, 0.0)), float(losses.get("reg_pose_body", 0.0)),
             float(losses.get("reg_betas", 0.0)))
@@ -686,7 +701,7 @@ class MarkerProblem(_StageProblem):
         """`assign` [M] vertex ids (the one-hot placement of the shipped configs), or -- with `bary` [M, 3] -- [M, 3] corner
         vertex ids of a three-corner (barycentric) placement: virtual marker m = sum_k bary[m, k] v[assign[m, k]]."""
         st = config["stages"]["marker"]
-        unsupported = set(st["losses"]) - {"marker", "reg_pose_body", "reg_betas", "joint_accel"}
+        unsupported = set(st["losses"]) - {"marker", "reg_pose_body", "reg_betas", "joint_accel", "latent_offsets"}
         if unsupported:
             raise NotImplementedError("marker-stage losses outside the shipped configs: %s" % sorted(unsupported))
         if st.get("use_sdf"):
@@ -694,9 +709,13 @@ class MarkerProblem(_StageProblem):
         wd, wp, wb = _cfg_weights(st["losses"], "marker")
         sigma = stage_robust_sigma(config, "marker")
         w_accel = stage_joint_accel(config, "marker")
+        w_offsets = stage_latent_offsets(config)
         super().__init__(smpl_inference.device_model, markers, o_pose_body, o_betas, None, wd, wp, wb, assign=assign)
         self.problem.robust_sigma = sigma  # EXTENSION: Geman-McClure data term (0 = off)
         self.joint_accel = w_accel  # EXTENSION: joint-acceleration term (0 = off)
+        if w_offsets > 0.0:  # EXTENSION: latent per-marker offsets, 3 M more parameters after trans
+            self.problem.w_offsets = w_offsets
+            self.n = int(self.lib.uuo_problem_num_params(byref(self.problem)))
         if bary is not None:
             if self.assign.dim() != 2 or tuple(self.assign.shape) != (self.M, 3) or tuple(bary.shape) != (self.M, 3):
                 raise ValueError("a three-corner placement takes assign [M, 3] and bary [M, 3]")
@@ -706,14 +725,51 @@ class MarkerProblem(_StageProblem):
         elif self.assign.dim() != 1 or self.assign.numel() != self.M:
             raise ValueError("a one-hot placement takes assign [M]")
 
-    def pack(self, pose_body, betas, root_orient, trans):
-        return torch.cat([_f32(pose_body, "pose").reshape(-1), _f32(betas, "betas").reshape(-1),
-                          _f32(root_orient, "root").reshape(-1), _f32(trans, "trans").reshape(-1)]).contiguous()
+    @property
+    def has_offsets(self) -> bool:
+        """EXTENSION: True when this problem carries the latent marker offsets (stages.marker.losses.latent_offsets > 0)."""
+        return self.problem.w_offsets != 0.0
+
+    def pack(self, pose_body, betas, root_orient, trans, offsets=None):
+        """x = [pose | betas | root | trans], and with the latent marker offsets `offsets` [M, 3] after them (zeros if None)."""
+        parts = [_f32(pose_body, "pose").reshape(-1), _f32(betas, "betas").reshape(-1),
+                 _f32(root_orient, "root").reshape(-1), _f32(trans, "trans").reshape(-1)]
+        if self.has_offsets:
+            parts.append(torch.zeros(3 * self.M, dtype=torch.float32, device=self.device) if offsets is None
+                         else _f32(offsets, "offsets").reshape(-1))
+        elif offsets is not None:
+            raise ValueError("offsets given to a marker problem without latent_offsets")
+        return torch.cat(parts).contiguous()
 
     def unpack(self, x):
+        """(pose, betas, root, trans), and the offsets [M, 3] as a fifth block when the problem carries them."""
         F = self.F
-        return (x[:207 * F].reshape(F, 23, 3, 3), x[207 * F:207 * F + 10].reshape(1, 10),
-                x[207 * F + 10:216 * F + 10].reshape(F, 1, 3, 3), x[216 * F + 10:].reshape(F, 3))
+        out = (x[:207 * F].reshape(F, 23, 3, 3), x[207 * F:207 * F + 10].reshape(1, 10),
+               x[207 * F + 10:216 * F + 10].reshape(F, 1, 3, 3), x[216 * F + 10:219 * F + 10].reshape(F, 3))
+        if self.has_offsets:
+            return out + (x[219 * F + 10:].reshape(self.M, 3),)
+        return out
+
+    def offsets_start(self, x: torch.Tensor) -> torch.Tensor:
+        """EXTENSION: the start value of the latent marker offsets at the parameters `x` (their own entries are ignored):
+        o_m = MARKER_DISTANCE u_m with u_m the unit vector of -g_m, g the offsets' block of the gradient of the plain data term
+        alone at o = 0 (no priors, no robust or joint-acceleration term) -- -(2 w_data / (F M)) sum_f mask T_R^T (x - v), the
+        masked mean residual in the marker's local frame.  A marker with no valid frame starts at 0 (and stays there).  One
+        closure evaluation on this problem's workspace; [M, 3] on the device."""
+        assert self.has_offsets and x.numel() == self.n
+        p = self.problem
+        saved = (p.w_pose, p.w_betas, p.robust_sigma, self.joint_accel)
+        x0 = x.detach().clone()
+        x0[219 * self.F + 10:] = 0.0
+        try:
+            p.w_pose, p.w_betas, p.robust_sigma, self.joint_accel = 0.0, 0.0, 0.0, 0.0
+            _, grad, _ = self.evaluate(x0, want_nn=False)
+        finally:
+            p.w_pose, p.w_betas, p.robust_sigma, self.joint_accel = saved
+        g = grad[-3 * self.M:].reshape(self.M, 3).double()
+        norm = torch.linalg.norm(g, dim=1, keepdim=True)
+        u = torch.where(norm > 0.0, -g / torch.where(norm > 0.0, norm, torch.ones_like(norm)), torch.zeros_like(g))
+        return (MARKER_DISTANCE * u).float().contiguous()
 
 
 #: most markers per frame the fused soft-assignment part closure (k_part_soft) is instantiated for

@@ -17,7 +17,8 @@ import numpy as np
 import torch
 
 from . import markers_utils, optimization
-from .engine import set_workspace_group, set_workspace_slot, worker_pool, worker_streams, workspace_group
+from .engine import (set_workspace_group, set_workspace_slot, stage_latent_offsets, worker_pool, worker_streams,
+                     workspace_group)
 from .markers_utils import find_best_part_fits, get_aabb, get_aabb_volume, segment_rigid
 from .optimization import (compute_marker_labels_from_coords, compute_nearest_points, get_marker_mask,
                            optim_chamfer, optim_markers, weighted_chamfer_distance)
@@ -304,6 +305,8 @@ def multimodal_video_mocap(
         pose_f = torch.from_numpy(r["pose_body"]).to(device).requires_grad_(True)
         betas_f = torch.from_numpy(r["betas"][None]).to(device).requires_grad_(True)
         final_np, final_stats = None, []
+        # EXTENSION: the latent marker offsets of the last final marker solve (None: the term is off or no such solve ran)
+        offsets_f = None
         for stage_i in range(config["stage_repeats"]):
             pose_stage = torch.clone(pose_f).detach().requires_grad_(False)
             if "progress" in print_options:
@@ -322,16 +325,20 @@ def multimodal_video_mocap(
                                                                                           config["stage_repeats"]))
                 root_f = root_f.clone().detach().requires_grad_(True)
                 pose_f = pose_f.clone().detach().requires_grad_(True)
+                offs = (torch.zeros((markers.shape[1], 3), dtype=torch.float32, device=device)
+                        if stage_latent_offsets(config) > 0.0 else None)
                 optim_markers(markers=markers, pose_body=pose_f, o_pose_body=pose_stage, betas=betas_f,
                               o_betas=o_betas, root_orient=root_f, trans=trans_f, barycentric_coords_one_hot=one_hot,
                               img_mask=img_mask, smpl_inference=smpl_inference, config=config, initial_angle=0,
-                              repeat=1, verbose=verbose, iter_fn=save_iter_fn)
+                              repeat=1, verbose=verbose, iter_fn=save_iter_fn,
+                              **({} if offs is None else {"marker_offsets": offs}))
+                offsets_f = offs
                 final_stats.append(optimization.last_stats("marker"))
             root_f = normalize_rot(root_f).clone().detach().requires_grad_(True)
             pose_f = normalize_rot(pose_f).clone().detach().requires_grad_(True)
             final_np = _np_dict(trans=trans_f, root_orient=root_f, betas=betas_f[0], pose_body=pose_f)
         return {"trans": trans_f, "root_orient": root_f, "pose_body": pose_f, "betas": betas_f, "np": final_np,
-                "stats": final_stats, "labels": labels}
+                "stats": final_stats, "labels": labels, "marker_offsets": offsets_f}
 
     def fit_hypothesis(index: int, root_orient_angle: float, stream, marker_labels=marker_labels):
         """One yaw hypothesis (reference multimodal.py:463-574): chamfer L-BFGS -> placement -> marker L-BFGS.
@@ -590,6 +597,8 @@ def multimodal_video_mocap(
     mocap_markers.set_points(markers.detach().cpu().numpy())
     output["mocap_markers"] = mocap_markers
     output["markers_labels"] = marker_labels
+    if fin["marker_offsets"] is not None:  # EXTENSION: [M, 3] rest-space offsets (metres) in mocap_markers' column order
+        output["marker_offsets"] = fin["marker_offsets"].detach().cpu()
     if save_stages:
         output["stages"] = {}
         if config["find_best_part_fits"]:

@@ -12,7 +12,8 @@ import torch
 import torch.nn.functional as F
 
 from .device_lbfgs import DeviceLBFGS
-from .engine import MARKER_DISTANCE, ChamferProblem, MarkerProblem, stage_joint_accel, stage_robust_sigma
+from .engine import (MARKER_DISTANCE, ChamferProblem, MarkerProblem, stage_joint_accel, stage_latent_offsets,
+                     stage_robust_sigma)
 from .losses import (MarkerLoss, RobustMarkerLoss, chamfer_distance, joint_accel_loss,  # noqa: F401  (re-exported)
                      robust_weighted_chamfer_distance, soft_weighted_chamfer_distance, weighted_chamfer_distance)
 from .smpl import SmplInference
@@ -156,6 +157,7 @@ def _optim_markers_frame_sharded(fs, markers, pose_body, o_pose_body, betas, o_b
                                  smpl_inference, config, iter_fn):
     """optim_markers' fused solve (one-hot placement) spread over ranks by frame blocks; same in-place contract."""
     _refuse_sharded_joint_accel(config, "marker")
+    _refuse_latent_offsets(config, "frame-block sharding (parallel.shard_frames)")
     if iter_fn is not None:
         raise NotImplementedError("frame sharding: no per-evaluation iter_fn")
     F = int(markers.shape[0])
@@ -187,6 +189,12 @@ def _temporal_fused(config: Dict, stage: str) -> bool:
     return stage_joint_accel(config, stage) == 0.0 or bool((config.get("execution") or {}).get("temporal_fused", True))
 
 
+def _refuse_latent_offsets(config: Dict, route: str):
+    if stage_latent_offsets(config) > 0.0:
+        raise NotImplementedError("stages.marker.losses.latent_offsets (latent marker offsets, extension) is built for the fused "
+                                  "marker closures only, not for %s" % route)
+
+
 def _refuse_sharded_joint_accel(config: Dict, stage: str):
     if stage_joint_accel(config, stage) > 0.0:
         raise NotImplementedError("stages.%s.losses.joint_accel (extension) couples neighbouring frames, across the ranks' "
@@ -203,9 +211,12 @@ def lockstep_supported(config: Dict, stage: str) -> bool:
         return False
     if stage_joint_accel(config, stage) > 0.0:  # EXTENSION: lock-step batches do not carry the joint-acceleration term
         return False
+    if stage == "marker" and stage_latent_offsets(config) > 0.0:  # EXTENSION: nor the latent marker offsets
+        return False
     if stage == "chamfer":
         return not (set(st["losses"]) - _CHAMFER_FUSED_LOSSES) and bool(st["yaw_lock"])
-    return not (set(st["losses"]) - {"marker", "reg_pose_body", "reg_betas", "joint_accel"}) and not st.get("use_sdf")
+    return not (set(st["losses"]) - {"marker", "reg_pose_body", "reg_betas", "joint_accel", "latent_offsets"}) and \
+        not st.get("use_sdf")
 
 
 def optim_chamfer_lockstep(markers, hyps, o_pose_body, o_betas, smpl_inference, config):
@@ -409,9 +420,13 @@ def optim_markers(
     repeat: int = 0,
     verbose: bool = False,
     iter_fn: Callable = None,
+    marker_offsets: torch.Tensor = None,
 ):
     """Marker (inverse kinematics) stage: L-BFGS over [pose_body, betas, root_orient, trans], lr 1.0, with the
-    fixed marker -> vertex placement given as a one-hot [M, V] matrix.  Mutates the four leaves in place."""
+    fixed marker -> vertex placement given as a one-hot [M, V] matrix.  Mutates the four leaves in place.
+    EXTENSION: with stages.marker.losses.latent_offsets > 0 the solve also fits one rest-space offset per marker column
+    (uuo_problem_t.w_offsets), started from MarkerProblem.offsets_start; `marker_offsets` ([M, 3], optional) receives the
+    fitted offsets in place."""
     one_hot = barycentric_coords_one_hot
     if one_hot.dim() != 2 or one_hot.shape[1] != smpl_inference.device_model.V:
         raise ValueError("barycentric_coords_one_hot must be [M, %d]" % smpl_inference.device_model.V)
@@ -441,21 +456,29 @@ def optim_markers(
                                             smpl_inference, config, iter_fn)
     prob = MarkerProblem(smpl_inference, markers, o_pose_body, o_betas, assign, config, bary=None if bary is None else bary[1])
     x = prob.pack(pose_body, betas, root_orient, trans)
+    if prob.has_offsets:  # EXTENSION: latent marker offsets, every solve from the data-driven start value
+        from .parallel import shared_betas_reducer
+
+        if shared_betas_reducer() is not None:
+            _refuse_latent_offsets(config, "shared betas (parallel.shared_betas)")
+        x[219 * prob.F + 10:] = prob.offsets_start(x).reshape(-1)
     point_cb = None
     if iter_fn is not None:
         def point_cb(i, loss, x_eval):  # closure_stage_marker_pose's iter_fn call (:382-391)
-            e_pose, e_betas, e_root, e_trans = prob.unpack(x_eval)
+            e_pose, e_betas, e_root, e_trans = prob.unpack(x_eval)[:4]
             iter_fn(stage="marker_" + str(repeat), iteration=i, initial_angle=np.array([initial_angle]),
                     pose_body=normalize_rot(e_pose).numpy(), betas=e_betas.numpy().copy(), trans=e_trans.numpy().copy(),
                     root_orient=normalize_rot(e_root).numpy())
 
     stats = _solve(prob, x, config, "marker", 1.0, "Marker", verbose, point_cb)
-    new_pose, new_betas, new_root, new_trans = prob.unpack(x)
+    new_pose, new_betas, new_root, new_trans = prob.unpack(x)[:4]
     with torch.no_grad():
         pose_body.copy_(new_pose)
         betas.copy_(new_betas)
         root_orient.copy_(new_root)
         trans.copy_(new_trans)
+        if marker_offsets is not None and prob.has_offsets:
+            marker_offsets.copy_(prob.unpack(x)[4].to(device=marker_offsets.device, dtype=marker_offsets.dtype))
     LAST_STATS["marker"] = stats
     _tls_stats.marker = stats
     return None
@@ -467,8 +490,10 @@ def _optim_markers_general(markers, pose_body, o_pose_body, betas, o_betas, root
     markers = coords @ vertices).  The fused device solver covers the one-hot placements of the shipped configs; this
     path composes the same closure from the differentiable HIP operators (SmplInference forward / uuo_smpl_backward)
     and drives it with torch.optim.LBFGS like the reference.  Mutates the four leaves in place."""
+    _refuse_latent_offsets(config, "the closure composed from the operators (more than three non-zeros per placement row, "
+                           "execution.robust_fused / temporal_fused / marker_bary_fused: False)")
     st = config["stages"]["marker"]
-    unsupported = set(st["losses"]) - {"marker", "reg_pose_body", "reg_betas", "joint_accel"}
+    unsupported = set(st["losses"]) - {"marker", "reg_pose_body", "reg_betas", "joint_accel", "latent_offsets"}
     if unsupported:
         raise NotImplementedError("marker-stage losses outside the shipped configs: %s" % sorted(unsupported))
     if st.get("use_sdf"):

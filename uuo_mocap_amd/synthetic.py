@@ -112,10 +112,16 @@ class SyntheticSequence:
 
 def make_sequence(tables: SmplTables, seed: int = 0, num_frames: int = 300, num_markers: int = 50,
                   limb_only: bool = False, yaw_offset_deg: float = 100.0, dropout: float = 0.02,
-                  hmr_pose_noise: float = 0.1, hmr_beta_noise: float = 0.5, subject_seed: int = None) -> SyntheticSequence:
+                  hmr_pose_noise: float = 0.1, hmr_beta_noise: float = 0.5, subject_seed: int = None,
+                  standoff_tilt_deg: float = 0.0, standoff_mm=(9.5, 9.5)) -> SyntheticSequence:
     """One synthetic sequence: smooth GT motion, unlabeled-but-tracked markers 9.5 mm off the
     surface with 1 mm noise and block dropout, and an HMR stand-in (noisy pose/shape, wrong yaw).  `subject_seed` fixes the
-    ground-truth shape independently of `seed`: sequences of ONE subject (the shared-betas extension fits them together)."""
+    ground-truth shape independently of `seed`: sequences of ONE subject (the shared-betas extension fits them together).
+    Marker m sits at its vertex + T_R o_m, o_m a rest-space offset skinned with the vertex's blended rotation; by default
+    o_m = 9.5 mm along the outward direction.  A stand-off capture (EXTENSION tests of the latent marker offsets):
+    `standoff_tilt_deg` > 0 tilts every direction off the outward one by up to that angle about a random axis, and
+    `standoff_mm` = (lo, hi) draws every length uniformly from [lo, hi] mm.  gt["marker_offsets"] holds the o_m [M, 3]
+    (metres, column order)."""
     F, M = num_frames, num_markers
     s = 7919 * (seed + 1)
     t = np.arange(F, dtype=np.float64) / max(F, 1)
@@ -165,7 +171,18 @@ def make_sequence(tables: SmplTables, seed: int = 0, num_frames: int = 300, num_
     out_dir = vt[pick] - (a + tt[:, None] * ab)
     out_dir /= np.maximum(np.linalg.norm(out_dir, axis=1, keepdims=True), 1e-9)
     out_world = np.einsum("fmab,mb->fma", T_R[:, pick], out_dir)
-    markers = verts[:, pick] + 0.0095 * out_world + 0.001 * hash_normal(s + 9, F, M, 3)
+    if standoff_tilt_deg == 0.0 and tuple(standoff_mm) == (9.5, 9.5):
+        offsets = 0.0095 * out_dir
+        markers = verts[:, pick] + 0.0095 * out_world + 0.001 * hash_normal(s + 9, F, M, 3)
+    else:  # stand-off capture: tilted directions, per-marker lengths (own hash streams: the other arrays do not change)
+        r = hash_normal(s + 15, M, 3)
+        perp = r - np.sum(r * out_dir, axis=1, keepdims=True) * out_dir
+        perp /= np.maximum(np.linalg.norm(perp, axis=1, keepdims=True), 1e-9)
+        ang = np.deg2rad(float(standoff_tilt_deg)) * hash_uniform(s + 16, M)
+        dirs = np.cos(ang)[:, None] * out_dir + np.sin(ang)[:, None] * perp
+        lo, hi = (float(v) * 1e-3 for v in standoff_mm)
+        offsets = (lo + (hi - lo) * hash_uniform(s + 17, M))[:, None] * dirs
+        markers = verts[:, pick] + np.einsum("fmab,mb->fma", T_R[:, pick], offsets) + 0.001 * hash_normal(s + 9, F, M, 3)
     perm = np.argsort(hash_uniform(s + 10, M), kind="stable")
     markers = markers[:, perm]
     # block dropout: (marker, 10-frame block) zeroed (style of reference markers/markers_noise.py:39-66)
@@ -201,6 +218,7 @@ def make_sequence(tables: SmplTables, seed: int = 0, num_frames: int = 300, num_
         "rot": rot.astype(np.float32), "betas": beta_gt.astype(np.float32), "trans": trans.astype(np.float32),
         "verts": verts.astype(np.float32), "joints": joints.astype(np.float32),
         "marker_vids": pick[perm],
+        "marker_offsets": offsets[perm].astype(np.float32),
     }
     return SyntheticSequence(img_smpl=img, markers=SyntheticMarkers(markers.astype(np.float32), 30.0), gt=gt)
 

@@ -196,6 +196,18 @@ int uuo_fit_destroy(uuo_fit_t* fit);
  * Refused (at evaluation) for the part stage and with w_soft != 0, and inside lock-step batches (uuo_batch_*).
  * w >= 0, finite. */
 int uuo_fit_set_joint_accel(uuo_fit_t* fit, float w);
+/* EXTENSION (not reference behaviour; the reference's foot_contact / foot_velocity terms sit on its part stage, assume a floor
+ * at z = 0 and are enabled in no shipped config): a contact-gated foot-lock term on the feet (SMPL joints 10 and 11,
+ * J_t = G_j^t + trans_t) of the chamfer and marker stages, with contact labels c[F][2] in [0, 1] (left, right) and the gate
+ * g[t][s] = c[t][s] c[t-1][s]:
+ *   v[t][s] = J[t][foot_s] - J[t-1][foot_s] (t = 1 .. F-1, all three components),   loss += w sum_t sum_s g[t][s] |v[t][s]|^2 / ((F - 1) 6)
+ * in units of m^2 per frame^2, like the joint-acceleration term: the weight belongs to the frame rate of the sequence handed
+ * over.  No floor height is assumed.  F < 2: no terms.
+ * A setting of the WORKSPACE (0 / null at creation) with the lifetime rules of uuo_fit_set_joint_accel.  `d_contacts` is a
+ * device pointer to [F][2] floats that the caller keeps alive and may rewrite; it is read at every evaluation, not copied.  It
+ * may be null only with w == 0.  Refused (at evaluation) for the part stage and with w_soft != 0, and inside lock-step batches
+ * (uuo_batch_*).  w >= 0, finite. */
+int uuo_fit_set_foot_lock(uuo_fit_t* fit, float w, const float* d_contacts);
 /* number of parameters of a stage at (F): 211F+10 / 219F+10 / 3F+11; the marker stage with w_offsets != 0: 219F+10+3M */
 int uuo_problem_num_params(const uuo_problem_t* p);
 

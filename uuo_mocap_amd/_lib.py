@@ -114,6 +114,7 @@ _SIGNATURES = {
     "uuo_fit_create": (c_int, [c_void_p, c_int, c_int, POINTER(c_void_p)]),
     "uuo_fit_destroy": (c_int, [c_void_p]),
     "uuo_fit_set_joint_accel": (c_int, [c_void_p, c_float]),  # EXTENSION: joint-acceleration term of the workspace
+    "uuo_fit_set_foot_lock": (c_int, [c_void_p, c_float, c_void_p]),  # EXTENSION: foot-lock term of the workspace, its contacts
     "uuo_problem_num_params": (c_int, [POINTER(UuoProblem)]),
     "uuo_closure_eval": (c_int, [c_void_p, c_void_p, POINTER(UuoProblem), c_void_p, c_void_p, c_void_p, c_void_p]),
     "uuo_lbfgs_solve": (c_int, [c_void_p, c_void_p, POINTER(UuoProblem), c_void_p, POINTER(UuoLbfgsOptions),

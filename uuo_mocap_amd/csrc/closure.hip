@@ -86,10 +86,12 @@ struct BwdArgs {
   uuo_gptr<unsigned> fin_counter;   // blocks of this launch that have published their partials (null: k_finalize follows)
   FinArgs fin;
   float acc_w;  // EXTENSION (ACCEL instantiations only): w_accel / ((F - 2) 72), the joint-acceleration term's coefficient
+  float lock_w;  // EXTENSION (ACCEL instantiations only): w_lock / ((F - 1) 6), the foot-lock term's coefficient (0 = off)
   // EXTENSION (OFFS instantiations only): latent per-marker offsets (uuo_problem_t.w_offsets)
   uuo_gptr<const float> offs;  // [markers][3] the offsets o_m (rest space), from the parameters
   uuo_gptr<float> offs_part;   // [F][M][3] out: d loss / d o of every item (T^T g), summed over frames by k_finalize_o
   int offs_k;                  // items per marker: 1 (one-hot) or 3 (item mode on a three-corner placement)
+  uuo_gptr<const float> contacts;  // EXTENSION (ACCEL instantiations, lock_w != 0): foot-contact labels [F][2] in [0, 1]
 };
 
 // EXTENSION: the offsets' share of the finalize (k_finalize_o / k_finalize_to, uuo_problem_t.w_offsets)
@@ -418,6 +420,12 @@ __device__ __forceinline__ float gmof_q(float sig2, float s) { return sig2 / (si
 // dL/dJ_f in where SmplInference.forward's joint gradient enters (sdGt; the translation gets its sum) and writes its own
 // acc_w |a_f|^2 to slot 3 of its partials (k_finalize_t adds it to the loss).  Everything downstream -- the kinematic sweep, the
 // Gram-Schmidt backward, the priors, the solver's fused statistics -- is the existing code.  Separate instantiations.
+// The same instantiations carry the contact-gated foot-lock term (EXTENSION, uuo_fit_set_foot_lock > 0, F >= 2) under the
+// block-uniform lock_w != 0: on the feet (joints 10, 11; s = 0, 1) with the contact labels c[F][2] and the gate
+// g[t][s] = c[t][s] c[t-1][s],  v[t][s] = J[t][foot_s] - J[t-1][foot_s] (t = 1 .. F-1),  loss += lock_w sum g |v|^2,
+// dL/dJ[f][foot_s] = 2 lock_w (g[f] v[f] - g[f+1] v[f+1]) (terms outside 1 .. F-1 dropped).  Block f forms g[f] and g[f+1] of
+// both feet beside the window load (parked in s_acc where the feet's dL/dJ and |a|^2 entries land later: no more LDS), takes
+// v from the window's frames f-1 .. f+1, adds dL/dJ to uj and lock_w g[f] |v[f]|^2 to slot 3.  Either coefficient may be 0.
 // OFFS (EXTENSION, uuo_problem_t.w_offsets > 0): latent per-marker offsets.  Item mm belongs to marker mm / offs_k; its
 // rest-space position is vp + o_m wherever it enters (the skinned position and the dA outer product), and its d loss / d o =
 // T^T g (dvp, which the blend gradients use too) goes to offs_part[f][mm] for k_finalize_o.  The host launches these with
@@ -489,6 +497,12 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a) {
       float v = 0.f;
       if (ft >= 0 && ft < F) v = (k < 72) ? a.frames[(size_t)ft * NW + GT + k] : a.src.trans[(size_t)ft * 3 + (k - 72)];
       s_acc[i] = v;
+    }
+    if (a.lock_w != 0.f && tid >= NT - 6) {  // foot-lock gates g[f], g[f+1] of (foot s, component r), for the thread that forms uj
+      const int q = tid - (NT - 6), sft = q / 3, k = (10 + sft) * 3 + (q - sft * 3);
+      const float c0 = a.contacts[(size_t)f * 2 + sft];
+      s_acc[ACC_UJ + k] = (f >= 1) ? c0 * a.contacts[(size_t)(f - 1) * 2 + sft] : 0.f;
+      s_acc[ACC_AA + k] = (f + 1 < F) ? a.contacts[(size_t)(f + 1) * 2 + sft] * c0 : 0.f;
     }
   }
   if (tid < UUO_NUM_JOINTS) frame_skin_matrix(L, tid, sA + tid * 12);
@@ -847,6 +861,14 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a) {
           ac[i] = (t0 >= 0 && t0 <= F - 3) ? ai : 0.f;
         }
         uj = (2.f * a.acc_w) * ((ac[0] - 2.f * ac[1]) + ac[2]);
+        if (a.lock_w != 0.f && (jj == 10 || jj == 11)) {
+          // foot lock: v[f] and v[f+1] from window frames 1 .. 3, differenced apart like the accelerations; the gates were
+          // parked in this thread's own two entries; g[f] |v[f]|^2 goes where only this thread read (frame f-2 of the window)
+          const float g0 = s_acc[ACC_UJ + k], g1 = s_acc[ACC_AA + k];
+          const float v0 = (w[2] - w[1]) + (tw[2] - tw[1]), v1 = (w[3] - w[2]) + (tw[3] - tw[2]);
+          uj += (2.f * a.lock_w) * (g0 * v0 - g1 * v1);
+          s_acc[k] = g0 * (v0 * v0);
+        }
         s_acc[ACC_UJ + k] = uj;
         s_acc[ACC_AA + k] = ac[2] * ac[2];
       }
@@ -1060,7 +1082,13 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a) {
     if (tid == 64) {  // (another wave than the one above) this frame's share of the joint-acceleration term, fixed order
       float s = 0.f;
       for (int k = 0; k < 72; ++k) s += s_acc[ACC_AA + k];
-      BWD_FP_STORE(3, a.acc_w * s);
+      float share = a.acc_w * s;
+      if (a.lock_w != 0.f) {  // the foot-lock term's t = f share (g[f] = 0 at f = 0)
+        float sl = 0.f;
+        for (int k = 30; k < 36; ++k) sl += s_acc[k];
+        share += a.lock_w * sl;
+      }
+      BWD_FP_STORE(3, share);
     }
   }
   BWD_STAMP(10);
@@ -1450,6 +1478,12 @@ static int validate_problem(const uuo_fit* fit, const uuo_problem_t* p) {
   UUO_REQUIRE(fit->joint_accel == 0.f || p->w_soft == 0.f,
               "closure: the joint-acceleration term (uuo_fit_set_joint_accel, extension) is not built for the soft-assignment "
               "data term (w_soft)");
+  // EXTENSION: the foot-lock term of the workspace (uuo_fit_set_foot_lock) likewise
+  UUO_REQUIRE(fit->foot_lock == 0.f || p->stage != UUO_STAGE_PART,
+              "closure: the foot-lock term (uuo_fit_set_foot_lock, extension) is not built for the part stage");
+  UUO_REQUIRE(fit->foot_lock == 0.f || p->w_soft == 0.f,
+              "closure: the foot-lock term (uuo_fit_set_foot_lock, extension) is not built for the soft-assignment data term "
+              "(w_soft)");
   // EXTENSION: latent marker offsets
   UUO_REQUIRE(p->w_offsets == 0.f || (p->w_offsets > 0.f && p->w_offsets <= 3.0e38f),
               "closure: w_offsets (latent marker offsets, extension) must be 0 (off) or a positive finite weight");
@@ -1465,6 +1499,16 @@ extern "C" int uuo_fit_set_joint_accel(uuo_fit_t* fit, float w) {
   UUO_REQUIRE(w == 0.f || (w > 0.f && w <= 3.0e38f), "uuo_fit_set_joint_accel: the weight must be 0 (off) or a positive finite number");
   UUO_REQUIRE(w == 0.f || !uuo_recorder, "uuo_fit_set_joint_accel: lock-step batches do not carry the joint-acceleration term");
   fit->joint_accel = w;
+  return 0;
+}
+
+extern "C" int uuo_fit_set_foot_lock(uuo_fit_t* fit, float w, const float* d_contacts) {
+  UUO_REQUIRE(fit, "uuo_fit_set_foot_lock: null fit");
+  UUO_REQUIRE(w == 0.f || (w > 0.f && w <= 3.0e38f), "uuo_fit_set_foot_lock: the weight must be 0 (off) or a positive finite number");
+  UUO_REQUIRE(w == 0.f || d_contacts, "uuo_fit_set_foot_lock: a positive weight needs the contact labels [F][2] on the device");
+  UUO_REQUIRE(w == 0.f || !uuo_recorder, "uuo_fit_set_foot_lock: lock-step batches do not carry the foot-lock term");
+  fit->foot_lock = w;
+  fit->foot_contacts = (w == 0.f) ? nullptr : d_contacts;
   return 0;
 }
 
@@ -1868,6 +1912,12 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
   const bool accel = fit->joint_accel != 0.f && F >= 3;
   UUO_REQUIRE(!accel || !uuo_recorder, "closure: lock-step batches do not carry the joint-acceleration term");
   a.acc_w = accel ? (float)((double)fit->joint_accel / ((double)(F - 2) * 72.0)) : 0.f;
+  // EXTENSION: the foot-lock term rides on the same instantiations (either coefficient may be 0 there); F < 2: no terms
+  const bool lock = fit->foot_lock != 0.f && F >= 2;
+  UUO_REQUIRE(!lock || !uuo_recorder, "closure: lock-step batches do not carry the foot-lock term");
+  a.lock_w = lock ? (float)((double)fit->foot_lock / ((double)(F - 1) * 6.0)) : 0.f;
+  a.contacts = lock ? fit->foot_contacts : nullptr;
+  const bool temporal = accel || lock;
   a.h.gx = F;
   a.h.gy = 1;
   FinArgs fa;
@@ -1959,8 +2009,8 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
     a.item_loss = item_loss;
     a.frames = fit->frames;
     if (offs)
-      hipLaunchKernelGGL(accel ? k_bwd_items_t_o : k_bwd_items_o, dim3(F), dim3(BWD_NW * 64), 0, s, a);
-    else if (accel)
+      hipLaunchKernelGGL(temporal ? k_bwd_items_t_o : k_bwd_items_o, dim3(F), dim3(BWD_NW * 64), 0, s, a);
+    else if (temporal)
       hipLaunchKernelGGL(k_bwd_items_t, dim3(F), dim3(BWD_NW * 64), 0, s, a);
     else
       hipLaunchKernelGGL(k_bwd_items, dim3(F), dim3(BWD_NW * 64), 0, s, a);
@@ -1993,7 +2043,7 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
     if (offs) {
       // EXTENSION: latent marker offsets (the marker stage's one-hot closure); with the joint-acceleration term the pose-prep
       // launch below comes first for the same reason as there
-      if (accel) {
+      if (temporal) {
         rc = uuo_launch_pose_prep(m, s, F, src, fit->pfaT, fit->A, nullptr, fit->frames);
         if (rc) return rc;
         a.frames = fit->frames;
@@ -2001,7 +2051,7 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
       } else {
         hipLaunchKernelGGL(robust ? k_bwd_sparse_r_o : k_bwd_sparse_o, dim3(F), dim3(BWD_NW * 64), 0, s, a);
       }
-    } else if (accel) {
+    } else if (temporal) {
       // EXTENSION: the block of frame f reads its neighbours' world joints.  The marker stage's closure has no forward of its
       // own (its backward re-runs each frame's kinematic chain): a pose-prep launch leaves every frame's FrameLds first, and the
       // backward blocks start from them
@@ -2023,8 +2073,8 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
   UUO_HIP_CHECK(hipGetLastError());
   if (!fin_fused) {
     if (offs)
-      hipLaunchKernelGGL(accel ? k_finalize_to : k_finalize_o, dim3(1), dim3(1024), 0, s, fa, oa);
-    else if (accel)
+      hipLaunchKernelGGL(temporal ? k_finalize_to : k_finalize_o, dim3(1), dim3(1024), 0, s, fa, oa);
+    else if (temporal)
       hipLaunchKernelGGL(k_finalize_t, dim3(1), dim3(1024), 0, s, fa);
     else if (!uuo_record(UUO_OP_FIN, 1, 1, fa))
       hipLaunchKernelGGL(k_finalize, dim3(1), dim3(1024), 0, s, fa);

@@ -191,6 +191,8 @@ struct uuo_fit {
   float mask_sum = 0.f;  // host copy of sum(mask) (chamfer normaliser), refreshed by uuo_ensure_mask
   bool shared_pose_cache = false;  // pose_cache belongs to a uuo_batch (not freed with the fit)
   float joint_accel = 0.f;  // EXTENSION: weight of the joint-acceleration term (uuo_fit_set_joint_accel; 0 = off)
+  float foot_lock = 0.f;    // EXTENSION: weight of the foot-lock term (uuo_fit_set_foot_lock; 0 = off) and its contact labels
+  const float* foot_contacts = nullptr;  // [F][2] on the device, the caller's (read at evaluation)
 };
 
 // ---- dense backward of the skinning (dense_bwd.hip) ---------------------------------------------------------------------

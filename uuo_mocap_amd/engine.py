@@ -167,6 +167,9 @@ def solve_batch(problems, xs, max_iter: int, lr: float = 1.0, tolerance_grad: fl
     if any(p.problem.w_offsets != 0.0 for p in problems):
         raise NotImplementedError("lock-step batches do not carry the latent marker offsets (latent_offsets, extension): "
                                   "solve such problems one by one")
+    if any(p.foot_lock != 0.0 for p in problems):
+        raise NotImplementedError("lock-step batches do not carry the foot-lock term (foot_lock, extension): "
+                                  "solve such problems one by one")
     for p, x in zip(problems, xs):
         assert p.stage == p0.stage and p.F == p0.F and p.M == p0.M and p.model is model
         assert x.is_cuda and x.dtype == torch.float32 and x.numel() == p.n and x.is_contiguous()
@@ -440,11 +443,29 @@ class _StageProblem:
         # EXTENSION: weight of the joint-acceleration term (ChamferProblem / MarkerProblem), a setting of the WORKSPACE in
         # the library (uuo_fit_set_joint_accel): _arm() puts it there before every call that evaluates on it
         self.joint_accel = 0.0
+        # EXTENSION: weight and contact labels of the foot-lock term (ChamferProblem / MarkerProblem), armed the same way
+        # (uuo_fit_set_foot_lock); _set_foot_lock decides once, at construction, whether the term has anything to act on
+        self.foot_lock = 0.0
+        self.foot_contacts = None
+
+    def _set_foot_lock(self, w: float, contacts):
+        """EXTENSION: keeps a contiguous float32 device copy of the checked contact labels and the weight the workspace is
+        armed with: `w` when the labels gate at least one (frame pair, foot), else 0 -- a capture without video contacts (no
+        labels, or none that holds over two consecutive frames) runs the plain kernels, bit for bit."""
+        if contacts is None:
+            return
+        self.foot_contacts = contacts.to(device=self.device, dtype=torch.float32).contiguous()
+        if w > 0.0 and self.F >= 2 and bool((contacts[1:] * contacts[:-1]).any()):
+            self.foot_lock = float(w)
 
     def _arm(self):
-        """Sets this problem's joint-acceleration weight (0 without the term) on its workspace.  The workspace is shared by
-        every problem of the same (F, M) on this thread, so this runs right before each library call that evaluates on it."""
+        """Sets this problem's joint-acceleration and foot-lock weights (0 without the terms) on its workspace.  The workspace
+        is shared by every problem of the same (F, M) on this thread, so this runs right before each library call that
+        evaluates on it."""
         check(self.lib.uuo_fit_set_joint_accel(self.fit, c_float(self.joint_accel)), "uuo_fit_set_joint_accel")
+        check(self.lib.uuo_fit_set_foot_lock(self.fit, c_float(self.foot_lock),
+                                             self.foot_contacts.data_ptr() if self.foot_lock != 0.0 else None),
+              "uuo_fit_set_foot_lock")
 
     def _need_workspace(self):
         if self.fit is None:  # created for a lock-step batch only: give it the thread's workspace on first standalone use
@@ -647,6 +668,30 @@ def stage_latent_offsets(config: Dict) -> float:
     return v
 
 
+def stage_foot_lock(config: Dict, stage: str) -> float:
+    """EXTENSION: stages.<stage>.losses.foot_lock of a config -- the weight of the contact-gated foot-lock term of the chamfer
+    or marker stage (uuo_fit_set_foot_lock), in units of m^2 per frame^2 of the sequence the stage is handed.  Absent or 0 =
+    off; negative or non-finite weights are refused.  (The part stage refuses the key with its other unknown losses.)"""
+    v = (config["stages"][stage].get("losses") or {}).get("foot_lock", 0.0)
+    v = 0.0 if v is None else float(v)
+    if not math.isfinite(v) or v < 0.0:
+        raise ValueError("stages.%s.losses.foot_lock must be 0 (off) or a positive weight (got %r)" % (stage, v))
+    return v
+
+
+def check_foot_contacts(foot_contacts, num_frames=None):
+    """EXTENSION: the foot-lock term's contact labels as a float32 host tensor [F, 2] (left, right foot; None stays None).
+    Shape, finiteness and the range [0, 1] are checked on the host: ValueError before anything touches the device."""
+    if foot_contacts is None:
+        return None
+    c = torch.as_tensor(foot_contacts).detach().to(device="cpu", dtype=torch.float32)
+    if c.dim() != 2 or c.shape[1] != 2 or (num_frames is not None and c.shape[0] != int(num_frames)):
+        raise ValueError("foot_contacts: [F, 2] with the markers' F = %s expected (got %s)" % (num_frames, tuple(c.shape)))
+    if not bool(torch.isfinite(c).all()) or bool((c < 0.0).any()) or bool((c > 1.0).any()):
+        raise ValueError("foot_contacts: finite labels in [0, 1] expected")
+    return c
+
+
 def _cfg_weights(losses: Dict, data_key: str):
     return (float(losses.get(data_key, 0.0)), float(losses.get("reg_pose_body", 0.0)),
             float(losses.get("reg_betas", 0.0)))
@@ -657,15 +702,20 @@ class ChamferProblem(_StageProblem):
 
     stage = UUO_STAGE_CHAMFER
 
-    def __init__(self, smpl_inference, markers, o_pose_body, o_betas, root_orient, config):
+    def __init__(self, smpl_inference, markers, o_pose_body, o_betas, root_orient, config, foot_contacts=None):
         losses = config["stages"]["chamfer"]["losses"]
-        unsupported = set(losses) - {"full_chamfer", "reg_pose_body", "reg_betas", "soft_chamfer", "joint_accel"}
+        unsupported = set(losses) - {"full_chamfer", "reg_pose_body", "reg_betas", "soft_chamfer", "joint_accel", "foot_lock"}
         if unsupported:
             raise NotImplementedError("chamfer-stage losses outside the shipped configs: %s" % sorted(unsupported))
         w_accel = stage_joint_accel(config, "chamfer")
         if w_accel > 0.0 and float(losses.get("soft_chamfer", 0.0)) != 0.0:
             raise NotImplementedError("stages.chamfer: the fused joint-acceleration term (joint_accel) is not built for the "
                                       "soft-assignment closure; optim_chamfer composes that combination from the operators")
+        w_lock = stage_foot_lock(config, "chamfer")
+        if w_lock > 0.0 and float(losses.get("soft_chamfer", 0.0)) != 0.0:
+            raise NotImplementedError("stages.chamfer: the fused foot-lock term (foot_lock) is not built for the "
+                                      "soft-assignment closure; optim_chamfer composes that combination from the operators")
+        contacts = check_foot_contacts(foot_contacts, None if markers is None else markers.shape[0])
         if not config["stages"]["chamfer"]["yaw_lock"]:
             raise NotImplementedError("stages.chamfer.yaw_lock False is not a shipped configuration")
         wd, wp, wb = _cfg_weights(losses, "full_chamfer")
@@ -673,6 +723,7 @@ class ChamferProblem(_StageProblem):
         super().__init__(smpl_inference.device_model, markers, o_pose_body, o_betas, root_orient, wd, wp, wb)
         self.problem.robust_sigma = sigma  # EXTENSION: Geman-McClure data term (0 = off)
         self.joint_accel = w_accel  # EXTENSION: joint-acceleration term (0 = off)
+        self._set_foot_lock(w_lock, contacts)  # EXTENSION: foot-lock term (weight 0 without gated contacts)
         # EXTENSION (not in the reference): soft assignment of every marker to the body's vertices, fused closure with the dense
         # backward on the matrix pipe (csrc/dense_bwd.hip); not available inside lock-step batches
         w_soft = float(losses.get("soft_chamfer", 0.0))
@@ -697,11 +748,11 @@ class MarkerProblem(_StageProblem):
 
     stage = UUO_STAGE_MARKER
 
-    def __init__(self, smpl_inference, markers, o_pose_body, o_betas, assign, config, bary=None):
+    def __init__(self, smpl_inference, markers, o_pose_body, o_betas, assign, config, bary=None, foot_contacts=None):
         """`assign` [M] vertex ids (the one-hot placement of the shipped configs), or -- with `bary` [M, 3] -- [M, 3] corner
         vertex ids of a three-corner (barycentric) placement: virtual marker m = sum_k bary[m, k] v[assign[m, k]]."""
         st = config["stages"]["marker"]
-        unsupported = set(st["losses"]) - {"marker", "reg_pose_body", "reg_betas", "joint_accel", "latent_offsets"}
+        unsupported = set(st["losses"]) - {"marker", "reg_pose_body", "reg_betas", "joint_accel", "latent_offsets", "foot_lock"}
         if unsupported:
             raise NotImplementedError("marker-stage losses outside the shipped configs: %s" % sorted(unsupported))
         if st.get("use_sdf"):
@@ -709,10 +760,13 @@ class MarkerProblem(_StageProblem):
         wd, wp, wb = _cfg_weights(st["losses"], "marker")
         sigma = stage_robust_sigma(config, "marker")
         w_accel = stage_joint_accel(config, "marker")
+        w_lock = stage_foot_lock(config, "marker")
+        contacts = check_foot_contacts(foot_contacts, None if markers is None else markers.shape[0])
         w_offsets = stage_latent_offsets(config)
         super().__init__(smpl_inference.device_model, markers, o_pose_body, o_betas, None, wd, wp, wb, assign=assign)
         self.problem.robust_sigma = sigma  # EXTENSION: Geman-McClure data term (0 = off)
         self.joint_accel = w_accel  # EXTENSION: joint-acceleration term (0 = off)
+        self._set_foot_lock(w_lock, contacts)  # EXTENSION: foot-lock term (weight 0 without gated contacts)
         if w_offsets > 0.0:  # EXTENSION: latent per-marker offsets, 3 M more parameters after trans
             self.problem.w_offsets = w_offsets
             self.n = int(self.lib.uuo_problem_num_params(byref(self.problem)))
@@ -753,19 +807,19 @@ class MarkerProblem(_StageProblem):
     def offsets_start(self, x: torch.Tensor) -> torch.Tensor:
         """EXTENSION: the start value of the latent marker offsets at the parameters `x` (their own entries are ignored):
         o_m = MARKER_DISTANCE u_m with u_m the unit vector of -g_m, g the offsets' block of the gradient of the plain data term
-        alone at o = 0 (no priors, no robust or joint-acceleration term) -- -(2 w_data / (F M)) sum_f mask T_R^T (x - v), the
+        alone at o = 0 (no priors, no robust, joint-acceleration or foot-lock term) -- -(2 w_data / (F M)) sum_f mask T_R^T (x - v), the
         masked mean residual in the marker's local frame.  A marker with no valid frame starts at 0 (and stays there).  One
         closure evaluation on this problem's workspace; [M, 3] on the device."""
         assert self.has_offsets and x.numel() == self.n
         p = self.problem
-        saved = (p.w_pose, p.w_betas, p.robust_sigma, self.joint_accel)
+        saved = (p.w_pose, p.w_betas, p.robust_sigma, self.joint_accel, self.foot_lock)
         x0 = x.detach().clone()
         x0[219 * self.F + 10:] = 0.0
         try:
-            p.w_pose, p.w_betas, p.robust_sigma, self.joint_accel = 0.0, 0.0, 0.0, 0.0
+            p.w_pose, p.w_betas, p.robust_sigma, self.joint_accel, self.foot_lock = 0.0, 0.0, 0.0, 0.0, 0.0
             _, grad, _ = self.evaluate(x0, want_nn=False)
         finally:
-            p.w_pose, p.w_betas, p.robust_sigma, self.joint_accel = saved
+            p.w_pose, p.w_betas, p.robust_sigma, self.joint_accel, self.foot_lock = saved
         g = grad[-3 * self.M:].reshape(self.M, 3).double()
         norm = torch.linalg.norm(g, dim=1, keepdim=True)
         u = torch.where(norm > 0.0, -g / torch.where(norm > 0.0, norm, torch.ones_like(norm)), torch.zeros_like(g))

@@ -189,3 +189,17 @@ def joint_accel_loss(joints: torch.Tensor) -> torch.Tensor:
         return joints.sum() * 0.0
     a = joints[:-2] - 2.0 * joints[1:-1] + joints[2:]
     return torch.mean(a * a)
+
+
+def foot_lock_loss(joints: torch.Tensor, contacts: torch.Tensor) -> torch.Tensor:
+    """EXTENSION (not in the reference): the contact-gated foot-lock term of the fused chamfer and marker closures
+    (uuo_fit_set_foot_lock) on joint positions [F, >= 12, 3] and contact labels [F, 2] in [0, 1] (left, right foot) --
+    mean(g[..., None] * v^2) with v[t, s] = J[t, foot_s] - J[t-1, foot_s] (feet: joints 10 and 11, all three components) and
+    the gate g[t, s] = c[t, s] c[t-1, s], t = 1 .. F-1, i.e. sum g |v|^2 / ((F - 1) 6).  Units: m^2 per frame^2.  With fewer
+    than two frames there are no terms and the value is 0."""
+    if joints.shape[0] < 2:
+        return joints.sum() * 0.0
+    contacts = contacts.to(device=joints.device, dtype=joints.dtype)
+    v = joints[1:, 10:12] - joints[:-1, 10:12]
+    g = contacts[1:] * contacts[:-1]
+    return torch.mean(g[..., None] * (v * v))

@@ -59,6 +59,23 @@ def compute_accel_error(pred_joints: torch.Tensor, gt_joints: torch.Tensor, freq
     return torch.mean(torch.norm(accel(pred_joints) - accel(gt_joints), dim=-1))
 
 
+def compute_foot_skate(joints: torch.Tensor, contacts: torch.Tensor, freq: float) -> torch.Tensor:
+    """Foot skate (not a metric of the reference): mean speed |J_t - J_{t-1}| freq of the feet (joints 10 and 11) over the
+    (t, foot) pairs in contact in both frames (c_t c_{t-1} = 1), in m/s for positions in metres and `freq` in frames per
+    second.  joints [F, >= 24, 3], contacts [F, 2] (left, right).  0.0 when no pair is in contact."""
+    if joints.dim() != 3 or joints.shape[1] < 24 or joints.shape[2] != 3 or tuple(contacts.shape) != (joints.shape[0], 2):
+        raise ValueError("compute_foot_skate: joints [F, >= 24, 3] and contacts [F, 2] expected (got %s and %s)"
+                         % (tuple(joints.shape), tuple(contacts.shape)))
+    if joints.shape[0] < 2:
+        return joints.new_zeros(())
+    contacts = contacts.to(device=joints.device, dtype=joints.dtype)
+    gate = (contacts[1:] * contacts[:-1]) == 1.0
+    if not bool(gate.any()):
+        return joints.new_zeros(())
+    speed = torch.norm(joints[1:, 10:12] - joints[:-1, 10:12], dim=-1) * float(freq)
+    return speed[gate].mean()
+
+
 def compute_PA_MPJPE(pred_joints: torch.Tensor, gt_joints: torch.Tensor) -> torch.Tensor:
     return compute_MPJPE(compute_similarity_transform(pred_joints, gt_joints), gt_joints)
 

@@ -330,7 +330,7 @@ def multimodal_video_mocap(
                 optim_markers(markers=markers, pose_body=pose_f, o_pose_body=pose_stage, betas=betas_f,
                               o_betas=o_betas, root_orient=root_f, trans=trans_f, barycentric_coords_one_hot=one_hot,
                               img_mask=img_mask, smpl_inference=smpl_inference, config=config, initial_angle=0,
-                              repeat=1, verbose=verbose, iter_fn=save_iter_fn,
+                              repeat=1, verbose=verbose, iter_fn=save_iter_fn, foot_contacts=o_foot_contacts,
                               **({} if offs is None else {"marker_offsets": offs}))
                 offsets_f = offs
                 final_stats.append(optimization.last_stats("marker"))
@@ -362,7 +362,8 @@ def multimodal_video_mocap(
                               o_betas=o_betas, root_orient=z_root, trans=trans_angle,
                               marker_labels=torch.from_numpy(np.asarray(marker_labels)).to(device),
                               img_mask=img_mask, smpl_inference=smpl_inference, initial_angle=root_orient_angle,
-                              repeat=0, config=config, verbose=verbose, iter_fn=save_iter_fn)
+                              repeat=0, config=config, verbose=verbose, iter_fn=save_iter_fn,
+                              foot_contacts=o_foot_contacts)
                 local["chamfer_stats"] = optimization.last_stats("chamfer")
             local["chamfer"] = _np_dict(trans=trans_angle, root_orient=normalize_rot(z_root), betas=betas_angle[0],
                                         pose_body=normalize_rot(pose_angle))
@@ -385,7 +386,7 @@ def multimodal_video_mocap(
                               o_betas=o_betas, root_orient=z_root, trans=trans_angle,
                               barycentric_coords_one_hot=one_hot, img_mask=img_mask, smpl_inference=smpl_inference,
                               config=config, initial_angle=root_orient_angle, repeat=0, verbose=verbose,
-                              iter_fn=save_iter_fn)
+                              iter_fn=save_iter_fn, foot_contacts=o_foot_contacts)
                 local["marker_stats"] = optimization.last_stats("marker")
             if not run_chamfer and not run_marker:
                 # nothing was optimised: the marker-stage record is the chamfer-stage record (both hold the normalised
@@ -457,7 +458,8 @@ def multimodal_video_mocap(
                     optim_markers(markers=markers, pose_body=h["pose_body"], o_pose_body=o_pose_body, betas=h["betas"],
                                   o_betas=o_betas, root_orient=h["root_orient"], trans=h["trans"],
                                   barycentric_coords_one_hot=oh, img_mask=img_mask, smpl_inference=smpl_inference,
-                                  config=config, initial_angle=angle, repeat=0, verbose=verbose)
+                                  config=config, initial_angle=angle, repeat=0, verbose=verbose,
+                                  foot_contacts=o_foot_contacts)
                     all_stats.append(optimization.last_stats("marker"))
             for local, stt in zip(locals_, all_stats):
                 local["marker_stats"] = stt

@@ -12,9 +12,9 @@ import torch
 import torch.nn.functional as F
 
 from .device_lbfgs import DeviceLBFGS
-from .engine import (MARKER_DISTANCE, ChamferProblem, MarkerProblem, stage_joint_accel, stage_latent_offsets,
-                     stage_robust_sigma)
-from .losses import (MarkerLoss, RobustMarkerLoss, chamfer_distance, joint_accel_loss,  # noqa: F401  (re-exported)
+from .engine import (MARKER_DISTANCE, ChamferProblem, MarkerProblem, check_foot_contacts, stage_foot_lock, stage_joint_accel,
+                     stage_latent_offsets, stage_robust_sigma)
+from .losses import (MarkerLoss, RobustMarkerLoss, chamfer_distance, foot_lock_loss, joint_accel_loss,  # noqa: F401  (re-exported)
                      robust_weighted_chamfer_distance, soft_weighted_chamfer_distance, weighted_chamfer_distance)
 from .smpl import SmplInference
 from .transforms import compute_root_orient_y, compute_root_orient_z, normalize_rot  # noqa: F401
@@ -56,9 +56,12 @@ def optim_chamfer(
     repeat: int = 0,
     verbose: bool = False,
     iter_fn: Callable = None,
+    foot_contacts: torch.Tensor = None,
 ):
     """Chamfer (pose fitting) stage: L-BFGS over [trans, z_angle, betas, pose_body], lr 0.1.  Mutates
-    trans / betas / pose_body in place and applies the optimised yaw to root_orient in place."""
+    trans / betas / pose_body in place and applies the optimised yaw to root_orient in place.
+    EXTENSION: `foot_contacts` ([F, 2] in [0, 1], optional) are the video's contact labels of the left and right foot for
+    stages.chamfer.losses.foot_lock (without them, or with labels that gate nothing, the key changes nothing)."""
     st = config["stages"]["chamfer"]
     fused_losses = _CHAMFER_FUSED_LOSSES
     if float(st["losses"].get("soft_chamfer", 0.0)) != 0.0 and markers.is_cuda and \
@@ -66,13 +69,13 @@ def optim_chamfer(
         # EXTENSION: the soft-assignment data term has a fused closure (dense backward on the matrix pipe, csrc/dense_bwd.hip);
         # execution.chamfer_soft_fused: False keeps the operator-composed closure, its checker
         fused_losses = _CHAMFER_FUSED_LOSSES | {"soft_chamfer"}
-    if "soft_chamfer" in fused_losses and stage_joint_accel(config, "chamfer") > 0.0:
-        # EXTENSION: the joint-acceleration term has no instantiation of the dense backward (k_bwd_dense): composed closure
+    if "soft_chamfer" in fused_losses and (stage_joint_accel(config, "chamfer") > 0.0 or stage_foot_lock(config, "chamfer") > 0.0):
+        # EXTENSION: the temporal terms have no instantiation of the dense backward (k_bwd_dense): composed closure
         fused_losses = _CHAMFER_FUSED_LOSSES
     if (set(st["losses"]) - fused_losses) or not st["yaw_lock"] or not _robust_fused(config, "chamfer") or \
             not _temporal_fused(config, "chamfer"):
         return _optim_chamfer_general(markers, pose_body, o_pose_body, betas, o_betas, root_orient, trans, marker_labels,
-                                      smpl_inference, config, initial_angle, repeat, verbose, iter_fn)
+                                      smpl_inference, config, initial_angle, repeat, verbose, iter_fn, foot_contacts)
     from .parallel import frame_shard
 
     fs = frame_shard()
@@ -82,7 +85,7 @@ def optim_chamfer(
                                       "(parallel.shard_frames); set execution.chamfer_soft_fused: False or use another mode")
         return _optim_chamfer_frame_sharded(fs, markers, pose_body, o_pose_body, betas, o_betas, root_orient, trans,
                                             smpl_inference, config, iter_fn)
-    prob = ChamferProblem(smpl_inference, markers, o_pose_body, o_betas, root_orient, config)
+    prob = ChamferProblem(smpl_inference, markers, o_pose_body, o_betas, root_orient, config, foot_contacts=foot_contacts)
     z_angle = torch.zeros((root_orient.shape[0], root_orient.shape[1], 1), device=root_orient.device)
     x = prob.pack(trans, z_angle, betas, pose_body)
     point_cb = None
@@ -184,9 +187,10 @@ def _robust_fused(config: Dict, stage: str) -> bool:
 
 
 def _temporal_fused(config: Dict, stage: str) -> bool:
-    """False when the stage's EXTENSION joint-acceleration term (stages.<stage>.losses.joint_accel > 0) is to run on the
-    closure composed from the operators (execution.temporal_fused: False, the fused closures' checker); True otherwise."""
-    return stage_joint_accel(config, stage) == 0.0 or bool((config.get("execution") or {}).get("temporal_fused", True))
+    """False when the stage's EXTENSION temporal terms (stages.<stage>.losses.joint_accel > 0 or foot_lock > 0) are to run on
+    the closure composed from the operators (execution.temporal_fused: False, the fused closures' checker); True otherwise."""
+    return (stage_joint_accel(config, stage) == 0.0 and stage_foot_lock(config, stage) == 0.0) or \
+        bool((config.get("execution") or {}).get("temporal_fused", True))
 
 
 def _refuse_latent_offsets(config: Dict, route: str):
@@ -198,6 +202,9 @@ def _refuse_latent_offsets(config: Dict, route: str):
 def _refuse_sharded_joint_accel(config: Dict, stage: str):
     if stage_joint_accel(config, stage) > 0.0:
         raise NotImplementedError("stages.%s.losses.joint_accel (extension) couples neighbouring frames, across the ranks' "
+                                  "frame blocks too: it is not built for frame-block sharding (parallel.shard_frames)" % stage)
+    if stage_foot_lock(config, stage) > 0.0:
+        raise NotImplementedError("stages.%s.losses.foot_lock (extension) couples neighbouring frames, across the ranks' "
                                   "frame blocks too: it is not built for frame-block sharding (parallel.shard_frames)" % stage)
 
 
@@ -211,11 +218,13 @@ def lockstep_supported(config: Dict, stage: str) -> bool:
         return False
     if stage_joint_accel(config, stage) > 0.0:  # EXTENSION: lock-step batches do not carry the joint-acceleration term
         return False
+    if stage_foot_lock(config, stage) > 0.0:  # EXTENSION: nor the foot-lock term
+        return False
     if stage == "marker" and stage_latent_offsets(config) > 0.0:  # EXTENSION: nor the latent marker offsets
         return False
     if stage == "chamfer":
         return not (set(st["losses"]) - _CHAMFER_FUSED_LOSSES) and bool(st["yaw_lock"])
-    return not (set(st["losses"]) - {"marker", "reg_pose_body", "reg_betas", "joint_accel", "latent_offsets"}) and \
+    return not (set(st["losses"]) - {"marker", "reg_pose_body", "reg_betas", "joint_accel", "latent_offsets", "foot_lock"}) and \
         not st.get("use_sdf")
 
 
@@ -313,11 +322,11 @@ def _solve(prob, x, config, stage: str, lr: float, verbose_tag: str, verbose: bo
 
 
 #: chamfer-stage loss terms the device solver fuses (the only ones the shipped configs enable)
-_CHAMFER_FUSED_LOSSES = {"full_chamfer", "reg_pose_body", "reg_betas", "joint_accel"}
+_CHAMFER_FUSED_LOSSES = {"full_chamfer", "reg_pose_body", "reg_betas", "joint_accel", "foot_lock"}
 
 
 def _optim_chamfer_general(markers, pose_body, o_pose_body, betas, o_betas, root_orient, trans, marker_labels,
-                           smpl_inference, config, initial_angle, repeat, verbose, iter_fn):
+                           smpl_inference, config, initial_angle, repeat, verbose, iter_fn, foot_contacts=None):
     """Chamfer stage with the reference's optional terms (`part_chamfer`, `trans_vel`, `ground`; plus the labelled
     extension `soft_chamfer`, a soft-assignment data term the reference does not have) and / or
     `yaw_lock: False` (reference optimization.py:164-285; none is in a shipped config): the closure is composed from the
@@ -331,7 +340,11 @@ def _optim_chamfer_general(markers, pose_body, o_pose_body, betas, o_betas, root
         raise NotImplementedError("chamfer-stage losses that cannot run in the reference: %s" % sorted(unknown))
     sigma = stage_robust_sigma(config, "chamfer")  # EXTENSION: Geman-McClure data term (0 = the reference's square)
     w_accel = stage_joint_accel(config, "chamfer")  # EXTENSION: joint-acceleration term
+    w_lock = stage_foot_lock(config, "chamfer")  # EXTENSION: foot-lock term, on the video's contact labels
+    contacts = check_foot_contacts(foot_contacts, pose_body.shape[0])
     device = root_orient.device
+    if contacts is not None:
+        contacts = contacts.to(device)
     num_frames = pose_body.shape[0]
     root_fixed = root_orient.detach().clone()
     if st["yaw_lock"]:
@@ -378,6 +391,8 @@ def _optim_chamfer_general(markers, pose_body, o_pose_body, betas, o_betas, root
             loss = loss + F.mse_loss(p_betas, o_betas) * w["reg_betas"]
         if "joint_accel" in w:  # EXTENSION: the fused closures' joint-acceleration term, composed (their checker)
             loss = loss + joint_accel_loss(out["joints"][:, :24]) * w_accel
+        if w_lock > 0.0 and contacts is not None:  # EXTENSION: the fused closures' foot-lock term, composed (their checker)
+            loss = loss + foot_lock_loss(out["joints"][:, :24], contacts) * w_lock
         loss.backward()
         if verbose:
             print("Chamfer", n_eval[0], float(loss))
@@ -421,12 +436,15 @@ def optim_markers(
     verbose: bool = False,
     iter_fn: Callable = None,
     marker_offsets: torch.Tensor = None,
+    foot_contacts: torch.Tensor = None,
 ):
     """Marker (inverse kinematics) stage: L-BFGS over [pose_body, betas, root_orient, trans], lr 1.0, with the
     fixed marker -> vertex placement given as a one-hot [M, V] matrix.  Mutates the four leaves in place.
     EXTENSION: with stages.marker.losses.latent_offsets > 0 the solve also fits one rest-space offset per marker column
     (uuo_problem_t.w_offsets), started from MarkerProblem.offsets_start; `marker_offsets` ([M, 3], optional) receives the
-    fitted offsets in place."""
+    fitted offsets in place.
+    EXTENSION: `foot_contacts` ([F, 2] in [0, 1], optional) are the video's contact labels of the left and right foot for
+    stages.marker.losses.foot_lock (without them, or with labels that gate nothing, the key changes nothing)."""
     one_hot = barycentric_coords_one_hot
     if one_hot.dim() != 2 or one_hot.shape[1] != smpl_inference.device_model.V:
         raise ValueError("barycentric_coords_one_hot must be [M, %d]" % smpl_inference.device_model.V)
@@ -439,7 +457,7 @@ def optim_markers(
     if not _robust_fused(config, "marker") or not _temporal_fused(config, "marker"):
         # EXTENSION: execution.robust_fused / temporal_fused: False -- the composed closure, the fused one's checker
         return _optim_markers_general(markers, pose_body, o_pose_body, betas, o_betas, root_orient, trans, one_hot,
-                                      smpl_inference, config, verbose, iter_fn, initial_angle, repeat)
+                                      smpl_inference, config, verbose, iter_fn, initial_angle, repeat, foot_contacts)
     if not bool(((rows_nz == 1) & (one_hot.sum(dim=1) == 1.0)).all()):
         # barycentric placement (compute_locations.use_barycentric): up to three weighted vertices per marker.  Fused closure
         # (k_bary_fwd + k_bwd_items) when it is that and nothing else; execution.marker_bary_fused: False, more than three
@@ -448,13 +466,14 @@ def optim_markers(
                  bool((config.get("execution") or {}).get("marker_bary_fused", True)))
         if not fused:
             return _optim_markers_general(markers, pose_body, o_pose_body, betas, o_betas, root_orient, trans, one_hot,
-                                          smpl_inference, config, verbose, iter_fn, initial_angle, repeat)
+                                          smpl_inference, config, verbose, iter_fn, initial_angle, repeat, foot_contacts)
         bary = placement_corners(one_hot)
     assign = bary[0] if bary is not None else torch.argmax(one_hot, dim=-1)
     if sharded:
         return _optim_markers_frame_sharded(fs, markers, pose_body, o_pose_body, betas, o_betas, root_orient, trans, assign,
                                             smpl_inference, config, iter_fn)
-    prob = MarkerProblem(smpl_inference, markers, o_pose_body, o_betas, assign, config, bary=None if bary is None else bary[1])
+    prob = MarkerProblem(smpl_inference, markers, o_pose_body, o_betas, assign, config, bary=None if bary is None else bary[1],
+                         foot_contacts=foot_contacts)
     x = prob.pack(pose_body, betas, root_orient, trans)
     if prob.has_offsets:  # EXTENSION: latent marker offsets, every solve from the data-driven start value
         from .parallel import shared_betas_reducer
@@ -485,7 +504,7 @@ def optim_markers(
 
 
 def _optim_markers_general(markers, pose_body, o_pose_body, betas, o_betas, root_orient, trans, coords, smpl_inference,
-                           config, verbose, iter_fn=None, initial_angle=0, repeat=0):
+                           config, verbose, iter_fn=None, initial_angle=0, repeat=0, foot_contacts=None):
     """Marker stage for a general placement matrix [M, V] (reference optimization.py:288-399 as written: virtual
     markers = coords @ vertices).  The fused device solver covers the one-hot placements of the shipped configs; this
     path composes the same closure from the differentiable HIP operators (SmplInference forward / uuo_smpl_backward)
@@ -493,13 +512,17 @@ def _optim_markers_general(markers, pose_body, o_pose_body, betas, o_betas, root
     _refuse_latent_offsets(config, "the closure composed from the operators (more than three non-zeros per placement row, "
                            "execution.robust_fused / temporal_fused / marker_bary_fused: False)")
     st = config["stages"]["marker"]
-    unsupported = set(st["losses"]) - {"marker", "reg_pose_body", "reg_betas", "joint_accel", "latent_offsets"}
+    unsupported = set(st["losses"]) - {"marker", "reg_pose_body", "reg_betas", "joint_accel", "latent_offsets", "foot_lock"}
     if unsupported:
         raise NotImplementedError("marker-stage losses outside the shipped configs: %s" % sorted(unsupported))
     if st.get("use_sdf"):
         raise NotImplementedError("stages.marker.use_sdf is off in every shipped config")
     sigma = stage_robust_sigma(config, "marker")  # EXTENSION: Geman-McClure data term (0 = the reference's square)
     w_accel = stage_joint_accel(config, "marker")  # EXTENSION: joint-acceleration term
+    w_lock = stage_foot_lock(config, "marker")  # EXTENSION: foot-lock term, on the video's contact labels
+    contacts = check_foot_contacts(foot_contacts, pose_body.shape[0])
+    if contacts is not None:
+        contacts = contacts.to(pose_body.device)
     num_frames = pose_body.shape[0]
     leaves = [pose_body, betas, root_orient, trans]
     params = [p.detach().clone().requires_grad_(True) for p in leaves]
@@ -530,6 +553,8 @@ def _optim_markers_general(markers, pose_body, o_pose_body, betas, o_betas, root
             loss = loss + F.mse_loss(p_betas, o_betas) * st["losses"]["reg_betas"]
         if "joint_accel" in st["losses"]:  # EXTENSION: the fused closures' joint-acceleration term, composed (their checker)
             loss = loss + joint_accel_loss(out["joints"][:, :24]) * w_accel
+        if w_lock > 0.0 and contacts is not None:  # EXTENSION: the fused closures' foot-lock term, composed (their checker)
+            loss = loss + foot_lock_loss(out["joints"][:, :24], contacts) * w_lock
         loss.backward()
         if verbose:
             print("Marker", n_eval[0], float(loss))

@@ -113,7 +113,8 @@ class SyntheticSequence:
 def make_sequence(tables: SmplTables, seed: int = 0, num_frames: int = 300, num_markers: int = 50,
                   limb_only: bool = False, yaw_offset_deg: float = 100.0, dropout: float = 0.02,
                   hmr_pose_noise: float = 0.1, hmr_beta_noise: float = 0.5, subject_seed: int = None,
-                  standoff_tilt_deg: float = 0.0, standoff_mm=(9.5, 9.5)) -> SyntheticSequence:
+                  standoff_tilt_deg: float = 0.0, standoff_mm=(9.5, 9.5), planted_feet: bool = False,
+                  stance_frames: int = 20) -> SyntheticSequence:
     """One synthetic sequence: smooth GT motion, unlabeled-but-tracked markers 9.5 mm off the
     surface with 1 mm noise and block dropout, and an HMR stand-in (noisy pose/shape, wrong yaw).  `subject_seed` fixes the
     ground-truth shape independently of `seed`: sequences of ONE subject (the shared-betas extension fits them together).
@@ -121,7 +122,12 @@ def make_sequence(tables: SmplTables, seed: int = 0, num_frames: int = 300, num_
     o_m = 9.5 mm along the outward direction.  A stand-off capture (EXTENSION tests of the latent marker offsets):
     `standoff_tilt_deg` > 0 tilts every direction off the outward one by up to that angle about a random axis, and
     `standoff_mm` = (lo, hi) draws every length uniformly from [lo, hi] mm.  gt["marker_offsets"] holds the o_m [M, 3]
-    (metres, column order)."""
+    (metres, column order).
+    A planted-feet capture (EXTENSION tests of the foot-lock term): with `planted_feet` the pose track is unchanged and the
+    translation is rebuilt so that the stance foot's joint (10 left, 11 right; foot (t // stance_frames) % 2) does not move:
+    trans_t = trans_{t-1} - (j_t[foot] - j_{t-1}[foot]) with j the joints at zero translation.  gt["foot_contacts"] [F, 2] holds
+    the true stance labels; img_smpl.foot_contacts the same eroded by two frames at each end of every stance (a detector that
+    is late and early, never wrong)."""
     F, M = num_frames, num_markers
     s = 7919 * (seed + 1)
     t = np.arange(F, dtype=np.float64) / max(F, 1)
@@ -148,6 +154,23 @@ def make_sequence(tables: SmplTables, seed: int = 0, num_frames: int = 300, num_
     walk = np.clip(walk, -1.0, 1.0)
     trans = walk + np.array([0.0, 0.0, 0.95])[None]
     beta_gt = np.clip(hash_normal((s if subject_seed is None else 7919 * (int(subject_seed) + 1)) + 7, 10), -2.0, 2.0)[None]
+
+    contacts_gt = contacts_seen = None
+    if planted_feet:  # (no hash stream: every other array is made from the rebuilt translation exactly as without the option)
+        stance_frames = int(stance_frames)
+        if stance_frames < 1:
+            raise ValueError("make_sequence: stance_frames must be at least 1")
+        _, j0, _ = lbs_f64(tables, rot, beta_gt, np.zeros((F, 3)))
+        stance = (np.arange(F) // stance_frames) % 2
+        for i in range(1, F):
+            foot = 10 + stance[i]
+            trans[i] = trans[i - 1] - (j0[i, foot] - j0[i - 1, foot])
+        contacts_gt = np.zeros((F, 2))
+        contacts_gt[np.arange(F), stance] = 1.0
+        contacts_seen = np.zeros((F, 2))
+        for a0 in range(0, F, stance_frames):
+            b0 = min(a0 + stance_frames, F)
+            contacts_seen[a0 + 2:max(b0 - 2, a0 + 2), stance[a0]] = 1.0
 
     verts, joints, T_R = lbs_f64(tables, rot, beta_gt, trans)
 
@@ -206,7 +229,7 @@ def make_sequence(tables: SmplTables, seed: int = 0, num_frames: int = 300, num_
         hmr_root_orient=f32(hmr_root[:, None]),
         pose_body=f32(hmr_rot[:, 1:]),
         betas=f32(hmr_betas),
-        foot_contacts=torch.zeros(F, 2),
+        foot_contacts=f32(contacts_seen) if planted_feet else torch.zeros(F, 2),
         camera_bbox=torch.zeros(F, 3),
         center=torch.zeros(F, 2),
         scale=torch.zeros(F, 1),
@@ -220,6 +243,8 @@ def make_sequence(tables: SmplTables, seed: int = 0, num_frames: int = 300, num_
         "marker_vids": pick[perm],
         "marker_offsets": offsets[perm].astype(np.float32),
     }
+    if planted_feet:
+        gt["foot_contacts"] = contacts_gt.astype(np.float32)
     return SyntheticSequence(img_smpl=img, markers=SyntheticMarkers(markers.astype(np.float32), 30.0), gt=gt)
 
 

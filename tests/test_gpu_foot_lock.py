@@ -89,9 +89,10 @@ def _ref_chamfer(smpl64, cfg, markers, o_pose, o_betas, root, x, nn, contacts):
     return float(loss.detach()), torch.cat([t.grad.reshape(-1) for t in leaves]).numpy()
 
 
-def _ref_marker(smpl64, tables, cfg, markers, o_pose, o_betas, x, assign, bary, contacts):
+def _ref_marker(smpl64, tables, cfg, markers, o_pose, o_betas, x, assign, bary, contacts, num_markers=M):
     """Marker stage in float64 autograd: through the float64 SmplInference without the latent offsets, through the float64
     skinning restatement of the offsets' tests (which has the blended rotations the offsets need) with them."""
+    M = num_markers
     from uuo_mocap_amd.engine import MARKER_DISTANCE
 
     F = markers.shape[0]
@@ -134,7 +135,8 @@ def _ref_marker(smpl64, tables, cfg, markers, o_pose, o_betas, x, assign, bary, 
     return float(loss.detach()), torch.cat([t.grad.reshape(-1) for t in leaves]).numpy()
 
 
-def _marker_x(pm, pp, bp, rp, tp, dev, seed):
+def _marker_x(pm, pp, bp, rp, tp, dev, seed, num_markers=M):
+    M = num_markers
     if not pm.has_offsets:
         return pm.pack(pp.to(dev), bp.to(dev), rp.to(dev), tp.to(dev))
     from uuo_mocap_amd.engine import MARKER_DISTANCE

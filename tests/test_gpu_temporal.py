@@ -65,8 +65,8 @@ def _cfg(w_chamfer=0.0, w_marker=0.0, sigma=0.0, name="video_mocap"):
     return cfg
 
 
-def _inputs(tables, F, seed):
-    seq = make_sequence(tables, seed=seed, num_frames=F, num_markers=M)
+def _inputs(tables, F, seed, num_markers=M):
+    seq = make_sequence(tables, seed=seed, num_frames=F, num_markers=num_markers)
     markers = torch.from_numpy(np.nan_to_num(seq.markers.get_points())).float()
     o_pose = seq.img_smpl.pose_body.clone().float()
     o_betas = (seq.img_smpl.betas.sum(0, keepdim=True) / seq.img_smpl.img_mask.sum()).float()
@@ -143,13 +143,13 @@ def _ref_marker(smpl64, cfg, markers, o_pose, o_betas, x, assign, bary=None):
     return float(loss.detach()), torch.cat([t.grad.reshape(-1) for t in leaves]).numpy()
 
 
-def _three_corners(tables, seq, seed):
+def _three_corners(tables, seq, seed, num_markers=M):
     gen = torch.Generator().manual_seed(seed)
     faces = torch.from_numpy(np.asarray(tables.faces).astype(np.int64))
     vids = torch.from_numpy(np.asarray(seq.gt["marker_vids"])).long()
-    i3 = torch.zeros(M, 3, dtype=torch.int64)
-    b3 = torch.zeros(M, 3)
-    for m in range(M):
+    i3 = torch.zeros(num_markers, 3, dtype=torch.int64)
+    b3 = torch.zeros(num_markers, 3)
+    for m in range(num_markers):
         hit = (faces == vids[m]).any(1).nonzero()
         tri = faces[hit[0, 0]] if len(hit) else torch.tensor([int(vids[m]), (int(vids[m]) + 1) % 6890, (int(vids[m]) + 2) % 6890])
         wt = torch.rand(3, generator=gen) + 0.05

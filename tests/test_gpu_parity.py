@@ -672,7 +672,7 @@ def _analytic_objective(kind, n):
     return objective
 
 
-def _run_both_lbfgs(dev, kind, n, lr, max_iter, tolerance_change=1e-9):
+def _run_both_lbfgs(dev, kind, n, lr, max_iter, tolerance_change=1e-9, history_size=100):
     """torch.optim.LBFGS on the CPU and the device driver (debug library's self-test objective, same formulas) from the
     same start: every closure evaluation's loss and point, iteration / evaluation counts, final iterates."""
     import ctypes
@@ -684,7 +684,7 @@ def _run_both_lbfgs(dev, kind, n, lr, max_iter, tolerance_change=1e-9):
     x0 = torch.full((n,), -0.5) if kind == 1 else torch.zeros(n)
     xt = x0.clone().requires_grad_(True)
     opt = torch.optim.LBFGS([xt], max_iter=max_iter, tolerance_grad=1e-7, tolerance_change=tolerance_change, lr=lr,
-                            line_search_fn="strong_wolfe")
+                            history_size=history_size, line_search_fn="strong_wolfe")
     ref = {"loss": [], "x": []}
 
     def closure():
@@ -699,7 +699,7 @@ def _run_both_lbfgs(dev, kind, n, lr, max_iter, tolerance_change=1e-9):
     ref["n_iter"] = int(opt.state[opt._params[0]]["n_iter"])
     ref["x_final"] = xt.detach().numpy().copy()
     xd = x0.clone().to(dev).contiguous()
-    o = _lib.UuoLbfgsOptions(max_iter, 100, lr, 1e-7, tolerance_change, 0, 0)
+    o = _lib.UuoLbfgsOptions(max_iter, history_size, lr, 1e-7, tolerance_change, 0, 0)
     st = _lib.UuoLbfgsStats()
     got = {"loss": [], "x": []}
 
@@ -717,8 +717,12 @@ def _run_both_lbfgs(dev, kind, n, lr, max_iter, tolerance_change=1e-9):
     return ref, got, objective
 
 
-@pytest.mark.parametrize("n,lr,tol_change", [(300, 1.0, 1e-9), (5000, 0.1, 1e-9), (300, 1.0, 1e-6), (64, 0.5, 1e-4)])
-def test_lbfgs_follows_torch_evaluation_by_evaluation_on_a_quadratic(dev, n, lr, tol_change):
+@pytest.mark.parametrize("n,lr,tol_change,history_size",
+                         [(300, 1.0, 1e-9, 100), (5000, 0.1, 1e-9, 100), (300, 1.0, 1e-6, 100), (64, 0.5, 1e-4, 100),
+                          (300, 1.0, 1e-9, 1), (300, 1.0, 1e-9, 2), (300, 1.0, 1e-9, 3)],
+                         ids=["300-1.0-1e-09", "5000-0.1-1e-09", "300-1.0-1e-06", "64-0.5-0.0001",
+                              "300-1.0-1e-09-hist1", "300-1.0-1e-09-hist2", "300-1.0-1e-09-hist3"])
+def test_lbfgs_follows_torch_evaluation_by_evaluation_on_a_quadratic(dev, n, lr, tol_change, history_size):
     """On a well-scaled convex quadratic (condition 4, first step length = lr) every line-search decision has a healthy
     margin, so fp32 round-off cannot flip a branch: the device driver and torch.optim.LBFGS must agree evaluation by
     evaluation -- every trial point and loss, and the same iteration / evaluation counts.  A wrong bracket / zoom branch,
@@ -726,8 +730,11 @@ def test_lbfgs_follows_torch_evaluation_by_evaluation_on_a_quadratic(dev, n, lr,
     tests use the optimiser's value (torch's line search always runs with its own default 1e-9).
     (The ill-scaled quadratic of the next test is NOT suitable for this: its first step 1/|g|_1 is ~200x shorter than the
     curvature scale, the cubic interpolation through two nearly identical slopes has a discriminant below the fp32
-    rounding of the two loss values, and torch itself flips between extrapolation and bisection on a 1-ulp change.)"""
-    ref, got, _ = _run_both_lbfgs(dev, 2, n, lr, max_iter=30, tolerance_change=tol_change)
+    rounding of the two loss values, and torch itself flips between extrapolation and bisection on a 1-ulp change.)
+    history_size 1, 2, 3: the solve takes 7 iterations, so the window is full and slides from the second, third or fourth
+    on (with 100 it only ever grows); torch in fp32 and in fp64 agree evaluation for evaluation there too (7 iterations,
+    8 to 9 evaluations, trial points within 2e-7), so the margin argument above holds."""
+    ref, got, _ = _run_both_lbfgs(dev, 2, n, lr, max_iter=30, tolerance_change=tol_change, history_size=history_size)
     assert got["n_iter"] == ref["n_iter"], (got["n_iter"], ref["n_iter"])
     assert got["n_eval"] == len(ref["loss"]) == len(got["loss"]), (got["n_eval"], len(ref["loss"]))
     scale = ref["loss"][0]

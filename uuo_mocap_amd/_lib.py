@@ -159,6 +159,11 @@ _DEBUG_SIGNATURES = {
     "uuo_debug_index_map": (c_int, [c_int, c_int, c_int, c_void_p]),
     "uuo_debug_problem_index_map": (c_int, [POINTER(UuoProblem), c_int, c_void_p]),
     "uuo_debug_staging_script": (c_int, [c_void_p, c_int, ctypes.c_longlong, c_void_p]),
+    # step-wise replay of the L-BFGS history kernels (tests/test_gpu_lbfgs_history.py)
+    "uuo_debug_lb_replay_create": (c_int, [c_int, c_int, POINTER(c_void_p)]),
+    "uuo_debug_lb_replay_step": (c_int, [c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "uuo_debug_lb_replay_state": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "uuo_debug_lb_replay_destroy": (c_int, [c_void_p]),
 }
 
 # uuo_closure_fn (include/uuo_hip.h): int closure(user, stream, d_x_eval, d_loss, d_grad)

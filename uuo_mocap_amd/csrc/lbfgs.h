@@ -213,6 +213,42 @@ struct LbWs {
 
 int lbws_destroy(LbWs* w);
 int lbws_create(int n, int hist, LbWs** out, bool sync = true);
+
+// How one direction update (n_iter >= 2) is launched: the grids and the arguments of the two history passes and of the
+// coefficient kernel, derived from the vector length, the window (head, count) and the workspace.  lbfgs_run and the debug
+// flavour's replay hook (solver_debug.hip) both build their launches here, so that the hook replays what the driver issues.
+struct LbGeom {
+  int ncb;      // column blocks of the history holding this problem
+  int gcb;      // column blocks per dot-kernel group
+  int nchunks;  // groups = partial sums per Gram entry (<= LB_MAXCHUNK)
+  int nb;       // 256-thread blocks of the element-wise kernels
+};
+inline LbGeom lb_geom(int n) {
+  LbGeom ge;
+  ge.ncb = (n + LB_CW - 1) / LB_CW;
+  ge.gcb = (ge.ncb + LB_MAXCHUNK - 1) / LB_MAXCHUNK;
+  ge.nchunks = (ge.ncb + ge.gcb - 1) / ge.gcb;
+  ge.nb = (n + 255) / 256;
+  return ge;
+}
+inline int lb_cand_slot(int head, int count, int cap) { return (head + count) % cap; }
+inline dim3 lb_dots_grid(const LbGeom& ge) { return dim3(ge.nchunks, LB_DRS); }
+inline dim3 lb_dir_grid(const LbGeom& ge) { return dim3(2 * ge.ncb); }
+inline LbDotsArgs lb_dots_args(const LbWs* w, const LbGeom& ge, int n, int cap, int head, int count, const float* g,
+                               const float* gp, const float* d, float t_prev) {
+  return LbDotsArgs{{0, 0}, n, cap, w->cap, head, count, lb_cand_slot(head, count, cap), w->S, w->Y, g, gp, d, t_prev, ge.ncb,
+                    ge.gcb, w->part};
+}
+inline LbSmallArgs lb_small_args(const LbWs* w, const LbGeom& ge, int cap, int hist, int head, int count, int stop,
+                                 const double* rd_in) {
+  LbSmallArgs sa{{0, 0}, ge.nchunks, cap, hist, lb_cand_slot(head, count, cap), w->part, w->st, stop};
+  sa.rd_in = rd_in;
+  return sa;
+}
+inline LbDirArgs lb_dir_args(const LbWs* w, int n, int cap, const float* g, float* d, const float* x, float t, float* xt,
+                             const UuoIndexMap& map) {
+  return LbDirArgs{{0, 0}, n, cap, w->cap, w->S, w->Y, g, w->st, d, x, t, xt, map};
+}
 int fit_create_impl(uuo_model_t* model, int F, int M, uuo_fit_t** out, bool sync);
 
 // lock-step batches: while a batch steps this problem its launches are recorded (uuo_recorder) and `evaluate` hands control

@@ -187,10 +187,9 @@ int lbfgs_run(LbWs* w, hipStream_t s, Objective& obj, float* d_x, const uuo_lbfg
   const double lr = opt->lr, tol_grad = opt->tolerance_grad, tol_change = opt->tolerance_change;
   const double c1 = 1e-4, c2 = 0.9;
   const size_t stride = (size_t)w->n_cap;
-  const int ncb = (n + LB_CW - 1) / LB_CW;                 // column blocks of the history holding this problem
-  const int gcb = (ncb + LB_MAXCHUNK - 1) / LB_MAXCHUNK;   // column blocks per dot-kernel group
-  const int nchunks = (ncb + gcb - 1) / gcb;               // groups = partial sums per Gram entry (<= LB_MAXCHUNK)
-  const int nb = (n + 255) / 256;
+  const LbGeom ge = lb_geom(n);  // column blocks, dot-kernel groups, element-wise blocks (lbfgs.h)
+  const int nchunks = ge.nchunks;
+  const int nb = ge.nb;
   const int nstat = std::min(64, nb);
   auto vec = [&](int i) { return w->vecs + (size_t)i * stride; };
   // work vectors: 0 direction d, 1 spare iterate buffer, 2.. gradient pool.  Iterates and gradients change hands by
@@ -379,14 +378,13 @@ int lbfgs_run(LbWs* w, hipStream_t s, Objective& obj, float* d_x, const uuo_lbfg
         LbNegArgs na{{0, 0}, n, g, d, xcur, (float)t, xoth, map};
         lb_dispatch(UUO_OP_NEG, s, dim3(nb), uuo_lb_launch_neg, na);
       } else {
-        const int cand = (head + count) % cap;
-        const int nrows = 2 * (count + 1) + 1;
-        LbDotsArgs da{{0, 0}, n, cap, w->cap, head, count, cand, w->S, w->Y, g, vec(ipg), d, (float)t_prev_iter, ncb, gcb, w->part};
+        const int cand = lb_cand_slot(head, count, cap);
+        LbDotsArgs da = lb_dots_args(w, ge, n, cap, head, count, g, vec(ipg), d, (float)t_prev_iter);
         if (sh && sh->rank != 0) {  // the replicated entries are counted once in the joint dot products: on rank 0
           da.skip_lo = sh->off;
           da.skip_hi = sh->off + sh->cnt;
         }
-        lb_dispatch(UUO_OP_DOTS, s, dim3(nchunks, LB_DRS), uuo_lb_launch_dots, da);
+        lb_dispatch(UUO_OP_DOTS, s, lb_dots_grid(ge), uuo_lb_launch_dots, da);
         const double* rd_in = nullptr;
         if (sh) {
           const unsigned long long rseq = ++w->row_seq;
@@ -431,12 +429,11 @@ int lbfgs_run(LbWs* w, hipStream_t s, Objective& obj, float* d_x, const uuo_lbfg
         }
 #endif
         if (!small_done) {
-          LbSmallArgs sa{{0, 0}, nchunks, cap, hist, cand, w->part, w->st, small_stop};
-          sa.rd_in = rd_in;
+          LbSmallArgs sa = lb_small_args(w, ge, cap, hist, head, count, small_stop, rd_in);
           lb_dispatch(UUO_OP_SMALL, s, dim3(1), [](hipStream_t s_, dim3, const LbSmallArgs& a_) { uuo_lb_launch_small(s_, a_); }, sa);
         }
-        LbDirArgs ra{{0, 0}, n, cap, w->cap, w->S, w->Y, g, w->st, d, xcur, (float)t, xoth, map};
-        lb_dispatch(UUO_OP_DIR, s, dim3(2 * ncb), uuo_lb_launch_direction, ra);
+        LbDirArgs ra = lb_dir_args(w, n, cap, g, d, xcur, (float)t, xoth, map);
+        lb_dispatch(UUO_OP_DIR, s, lb_dir_grid(ge), uuo_lb_launch_direction, ra);
       }
       UUO_HIP_CHECK(hipGetLastError());
       prev_loss = loss;

@@ -811,4 +811,158 @@ extern "C" int uuo_debug_small_coeffs(int k, int use_ref, int seed, double* out)
   lbws_destroy(w);
   return 0;
 }
+
+// debug/test hook (not in the public header): step-wise replay of the three kernels that turn (history, gradient) into a
+// direction -- k_lb_dots, k_lb_small_inv, k_lb_direction -- with prescribed inputs: no objective, no line search, no host
+// decision.  Every step uploads a gradient, the previous step length (the stored s is t_prev * d), the next first-trial
+// step length and an iterate, issues what lbfgs_run issues for that iteration (k_lb_neg on the first, the sequence of
+// n_iter >= 2 afterwards; launches built by the same helpers of lbfgs.h, identity index map), mirrors head / count on the
+// host from LbOut.accepted as the driver does, and returns d, the trial point and the scalars of the step
+// (tests/test_gpu_lbfgs_history.py compares them with the float64 two-loop recursion over the same window).
+struct LbReplay {
+  LbWs* w = nullptr;
+  int n = 0, hist = 0, cap = 0;
+  int head = 0, count = 0;  // host mirror of the window, as in lbfgs_run
+  int steps = 0, cur = 0;   // cur: which of the two gradient buffers receives this step's gradient
+};
+// work vectors of the replay: 0 direction, 1 iterate, 2 trial point, 3 / 4 gradients (current and previous, by turns)
+static inline float* lb_replay_vec(const LbReplay* r, int i) { return r->w->vecs + (size_t)i * (size_t)r->w->n_cap; }
+
+extern "C" int uuo_debug_lb_replay_destroy(void* h) {
+  LbReplay* r = (LbReplay*)h;
+  if (!r) return 0;
+  lbws_destroy(r->w);
+  delete r;
+  return 0;
+}
+
+extern "C" int uuo_debug_lb_replay_create(int n, int hist, void** out) {
+  UUO_REQUIRE(out && n >= 1 && hist >= 1 && hist <= LB_MAXH - 4, "uuo_debug_lb_replay_create: bad arguments");
+  LbReplay* r = new LbReplay();
+  int rc = lbws_create(n, hist, &r->w);
+  if (rc) {
+    delete r;
+    return rc;
+  }
+  r->n = n;
+  r->hist = hist;
+  r->cap = hist + 1;
+  uuo_lb_launch_init(nullptr, r->w->st);
+  // the padding of the direction and of both gradients (n .. whole column blocks) holds what a larger problem would
+  // have left there: the history passes load it and must keep it out of the dot products and of the stored pair
+  const int pad = r->w->n_cap - n;
+  if (pad > 0) {
+    const std::vector<float> junk((size_t)pad, 1e30f);
+    const int vecs[3] = {0, 3, 4};
+    for (int v : vecs)
+      if (hipMemcpy(lb_replay_vec(r, v) + n, junk.data(), (size_t)pad * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+        uuo_debug_lb_replay_destroy(r);
+        uuo_set_error("uuo_debug_lb_replay_create: filling the padding failed");
+        return -5;
+      }
+  }
+  if (hipDeviceSynchronize() != hipSuccess) {
+    uuo_debug_lb_replay_destroy(r);
+    uuo_set_error("uuo_debug_lb_replay_create: device synchronisation failed");
+    return -5;
+  }
+  *out = r;
+  return 0;
+}
+
+// h_out[9] = {g.d, accepted, y.s, max|d| (from dmax_bits), head, count, Hdiag (all as the device holds them after the step),
+//             head, count (the host mirror)}
+extern "C" int uuo_debug_lb_replay_step(void* h, const float* h_g, float t_prev, float t, const float* h_x, float* h_d,
+                                        float* h_xt, double* h_out) {
+  LbReplay* r = (LbReplay*)h;
+  UUO_REQUIRE(r && h_g && h_x && h_d && h_xt && h_out, "uuo_debug_lb_replay_step: bad arguments");
+  LbWs* w = r->w;
+  const int n = r->n, cap = r->cap;
+  hipStream_t s = nullptr;
+  float* d = lb_replay_vec(r, 0);
+  float* x = lb_replay_vec(r, 1);
+  float* xt = lb_replay_vec(r, 2);
+  float* g = lb_replay_vec(r, 3 + r->cur);
+  const float* gp = lb_replay_vec(r, 3 + (1 - r->cur));
+  UUO_HIP_CHECK(hipMemcpy(g, h_g, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+  UUO_HIP_CHECK(hipMemcpy(x, h_x, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+  UuoIndexMap map;
+  std::memset(&map, 0, sizeof(map));  // nseg = 0: the identity
+  const LbGeom ge = lb_geom(n);
+  if (r->steps == 0) {
+    LbNegArgs na{{ge.nb, 1}, n, g, d, x, t, xt, map};
+    uuo_lb_launch_neg(s, dim3(ge.nb), na);
+  } else {
+    LbDotsArgs da = lb_dots_args(w, ge, n, cap, r->head, r->count, g, gp, d, t_prev);
+    const dim3 gd = lb_dots_grid(ge);
+    da.h.gx = (int)gd.x;
+    da.h.gy = (int)gd.y;
+    uuo_lb_launch_dots(s, gd, da);
+    LbSmallArgs sa = lb_small_args(w, ge, cap, r->hist, r->head, r->count, 0, nullptr);
+    sa.h.gx = sa.h.gy = 1;
+    uuo_lb_launch_small(s, sa);
+    LbDirArgs ra = lb_dir_args(w, n, cap, g, d, x, t, xt, map);
+    const dim3 gr = lb_dir_grid(ge);
+    ra.h.gx = (int)gr.x;
+    ra.h.gy = 1;
+    uuo_lb_launch_direction(s, gr, ra);
+  }
+  UUO_HIP_CHECK(hipGetLastError());
+  UUO_HIP_CHECK(hipStreamSynchronize(s));
+  UUO_HIP_CHECK(hipMemcpy(h_d, d, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+  UUO_HIP_CHECK(hipMemcpy(h_xt, xt, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+  LbOut o;
+  double Hdiag = 0.0;
+  int hc[2] = {0, 0};
+  unsigned dmax_bits = 0u;
+  UUO_HIP_CHECK(hipMemcpy(&o, (char*)w->st + offsetof(LbDev, out), sizeof(LbOut), hipMemcpyDeviceToHost));
+  UUO_HIP_CHECK(hipMemcpy(&Hdiag, (char*)w->st + offsetof(LbDev, Hdiag), sizeof(double), hipMemcpyDeviceToHost));
+  UUO_HIP_CHECK(hipMemcpy(hc, (char*)w->st + offsetof(LbDev, head), 2 * sizeof(int), hipMemcpyDeviceToHost));
+  UUO_HIP_CHECK(hipMemcpy(&dmax_bits, (char*)w->st + offsetof(LbDev, dmax_bits), sizeof(unsigned), hipMemcpyDeviceToHost));
+  if (r->steps > 0 && o.accepted != 0.0) {  // as lbfgs_run
+    if (r->count == r->hist)
+      r->head = (r->head + 1) % cap;
+    else
+      r->count += 1;
+  }
+  float dmax;
+  std::memcpy(&dmax, &dmax_bits, sizeof(float));
+  h_out[0] = o.gtd_dir;
+  h_out[1] = o.accepted;
+  h_out[2] = o.ys;
+  h_out[3] = (double)dmax;
+  h_out[4] = (double)hc[0];
+  h_out[5] = (double)hc[1];
+  h_out[6] = Hdiag;
+  h_out[7] = (double)r->head;
+  h_out[8] = (double)r->count;
+  r->steps += 1;
+  r->cur = 1 - r->cur;
+  return 0;
+}
+
+// W, SY, YY: the device's three LB_MAXH x LB_MAXH matrices, by slot (any may be null); slot >= 0: that slot's stored s and y,
+// n floats each, gathered from the column-block layout (lb_hist_off)
+extern "C" int uuo_debug_lb_replay_state(void* h, double* W, double* SY, double* YY, int slot, float* s_slot, float* y_slot) {
+  LbReplay* r = (LbReplay*)h;
+  UUO_REQUIRE(r && slot < r->cap && (slot < 0 || (s_slot && y_slot)), "uuo_debug_lb_replay_state: bad arguments");
+  LbWs* w = r->w;
+  const size_t mat = (size_t)LB_MAXH * LB_MAXH * sizeof(double);
+  if (W) UUO_HIP_CHECK(hipMemcpy(W, (char*)w->st + offsetof(LbDev, W), mat, hipMemcpyDeviceToHost));
+  if (SY) UUO_HIP_CHECK(hipMemcpy(SY, (char*)w->st + offsetof(LbDev, SY), mat, hipMemcpyDeviceToHost));
+  if (YY) UUO_HIP_CHECK(hipMemcpy(YY, (char*)w->st + offsetof(LbDev, YY), mat, hipMemcpyDeviceToHost));
+  if (slot >= 0) {
+    const int ncb = lb_geom(r->n).ncb;
+    std::vector<float> tmp((size_t)ncb * LB_CW);
+    const float* src[2] = {w->S, w->Y};
+    float* dst[2] = {s_slot, y_slot};
+    for (int v = 0; v < 2; ++v) {  // one row of LB_CW floats per column block, LB_CBSTRIDE apart
+      UUO_HIP_CHECK(hipMemcpy2D(tmp.data(), LB_CW * sizeof(float), src[v] + lb_hist_off(slot, 0, w->cap),
+                                LB_CBSTRIDE(w->cap) * sizeof(float), LB_CW * sizeof(float), (size_t)ncb,
+                                hipMemcpyDeviceToHost));
+      std::memcpy(dst[v], tmp.data(), (size_t)r->n * sizeof(float));
+    }
+  }
+  return 0;
+}
 #endif  // UUO_DEBUG_HOOKS

@@ -50,6 +50,15 @@ int uuo_model_create(const float* h_v_template, const float* h_shapedirs, const 
                      const int64_t* h_extra_joint_vids, int num_verts, uuo_model_t** out);
 int uuo_model_destroy(uuo_model_t* model);
 int uuo_model_num_verts(const uuo_model_t* model);
+/* EXTENSION (not reference behaviour; the point-to-surface chamfer term, uuo_fit_set_surface, and uuo_ring_closest_points):
+ * the model's triangles, h_faces [NF,3] int32 vertex ids (SmplInference.faces).  Builds every vertex's one-ring -- its incident
+ * faces in ascending face id, a CSR table -- on the host and uploads it with the faces.  A vertex may have no face.  A vertex
+ * with more than UUO_RING_MAX_VALENCE incident faces, or a face naming a vertex outside the model, is refused.  May be called
+ * again (the tables are replaced; synchronises the device).  uuo_ring_table is the host half on its own: h_off [V+1],
+ * h_ring [3 NF] (the first h_off[V] entries are written); no device is touched. */
+#define UUO_RING_MAX_VALENCE 32
+int uuo_model_set_faces(uuo_model_t* model, const int32_t* h_faces, int NF);
+int uuo_ring_table(const int32_t* h_faces, int NF, int V, int32_t* h_off, int32_t* h_ring);
 
 /* ---- SMPL forward (materialising) ---------------------------------------------------------------
  * Replaces SmplInference.forward (src/video_mocap/utils/smpl.py:29-50) = smplx SMPL.forward with
@@ -119,6 +128,15 @@ int uuo_soft_nn_backward(void* stream, int N, int P1, int P2, const float* d_x, 
 int uuo_mesh_closest_points(void* stream, int F, int M, int V, int NF, const float* d_verts,
                             const int32_t* d_faces, const float* d_points, float* d_dist, int32_t* d_face,
                             float* d_closest, float* d_bary);
+
+/* EXTENSION (not reference behaviour): the closest point on the ONE-RING of a given vertex -- the pick of the point-to-surface
+ * chamfer term (uuo_fit_set_surface) on caller-given vertices.  For every query d_points[f,m] and its vertex d_nn_idx[f,m]
+ * (int32; normally uuo_nn_argmin's result): the closest point on the faces incident to that vertex, with the arithmetic and
+ * the conventions of uuo_mesh_closest_points (lowest face id on exact ties, "cramer" coordinates).  A vertex without a face
+ * stands for itself: d_face -1, the closest point is the vertex, d_bary (1, 0, 0) on the corners (v, v, v).  d_verts [F,V,3]
+ * with V the model's vertex count; outputs [F,M,...] as there.  Needs uuo_model_set_faces.  Asynchronous. */
+int uuo_ring_closest_points(void* stream, uuo_model_t* model, int F, int M, const float* d_verts, const float* d_points,
+                            const int32_t* d_nn_idx, float* d_dist, int32_t* d_face, float* d_closest, float* d_bary);
 
 /* ---- stage problems -------------------------------------------------------------------------------
  * One closure evaluation (forward + backward) of the three L-BFGS stages, on flat parameter vectors
@@ -208,6 +226,26 @@ int uuo_fit_set_joint_accel(uuo_fit_t* fit, float w);
  * may be null only with w == 0.  Refused (at evaluation) for the part stage and with w_soft != 0, and inside lock-step batches
  * (uuo_batch_*).  w >= 0, finite. */
 int uuo_fit_set_foot_lock(uuo_fit_t* fit, float w, const float* d_contacts);
+/* EXTENSION (not reference behaviour; MoSh-style fitters score a marker by its distance to the SKIN less its stand-off, the
+ * reference's chamfer term by its distance to the nearest VERTEX): on = 1 replaces the chamfer stage's data term
+ * min_v |x - v|^2 by the point-to-surface term on the one-ring of the nearest vertex v^ the closure's search finds anyway:
+ *   p, b = closest point of x on the faces incident to v^ (ascending face id, lowest id on exact ties; no incident face: v^
+ *          itself), b its barycentric weights at the winning face's corners i_0..2
+ *   s    = (|x - p| - surface_distance)^2,   loss_data = w_data (1 / sum mask) sum mask rho(s)   (rho: robust_sigma)
+ * The face is picked in the search's vertex buffer; p, b and s are then formed on the three corners re-skinned in fp32.
+ * b is held fixed in the gradient (the envelope theorem: exact wherever the term is differentiable):
+ *   d s / d v[i_k] = -2 (|x - p| - surface_distance) / |x - p| b_k (x - p);   |x - p| = 0: no gradient.
+ * Mask and normaliser are the vertex term's; d_nn_idx of uuo_closure_eval still reports v^; works with robust_sigma and the
+ * joint-acceleration and foot-lock terms.  Needs uuo_model_set_faces on the workspace's model.
+ * A setting of the WORKSPACE (off at creation) with the lifetime rules of uuo_fit_set_joint_accel -- uuo_problem_t stays as it
+ * is.  Refused (at evaluation) for the marker and part stages and with w_soft != 0, by uuo_lbfgs_solve_shared, and inside
+ * lock-step batches (uuo_batch_*, whose workspaces cannot carry it).  surface_distance: metres, >= 0, finite.  on = 0: every
+ * result is that of a workspace that never had the term. */
+int uuo_fit_set_surface(uuo_fit_t* fit, int32_t on, float surface_distance);
+/* EXTENSION: the corners and weights the last surface-term evaluation (uuo_fit_set_surface) on `fit` used: d_corners
+ * [F,M,3] int32 vertex ids, d_bary [F,M,3] their weights (either may be NULL); hidden markers carry (v^, v^, v^).  Device to
+ * device on `stream`, ordered behind that evaluation.  Fails if no such evaluation has run on the workspace. */
+int uuo_fit_surface_corners(uuo_fit_t* fit, void* stream, int32_t* d_corners, float* d_bary);
 /* number of parameters of a stage at (F): 211F+10 / 219F+10 / 3F+11; the marker stage with w_offsets != 0: 219F+10+3M */
 int uuo_problem_num_params(const uuo_problem_t* p);
 

@@ -95,6 +95,12 @@ _SIGNATURES = {
     "uuo_model_create": (c_int, [c_void_p] * 7 + [c_int, POINTER(c_void_p)]),
     "uuo_model_destroy": (c_int, [c_void_p]),
     "uuo_model_num_verts": (c_int, [c_void_p]),
+    "uuo_model_set_faces": (c_int, [c_void_p, c_void_p, c_int]),  # EXTENSION: faces + one-ring table (surface chamfer term)
+    "uuo_ring_table": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "uuo_ring_closest_points": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_void_p]),
+    "uuo_fit_set_surface": (c_int, [c_void_p, c_int32, c_float]),  # EXTENSION: point-to-surface chamfer term of the workspace
+    "uuo_fit_surface_corners": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "uuo_smpl_forward": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                                  c_void_p, c_void_p]),
     "uuo_smpl_backward": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,

@@ -8,6 +8,7 @@ semantics for nested dicts: dicts merge recursively, everything else is replaced
 from __future__ import annotations
 
 import copy
+import math
 import os
 from typing import Dict
 
@@ -53,3 +54,27 @@ def load_config(filename: str) -> Dict:
 def packaged_config(name: str = "video_mocap") -> Dict:
     """One of the packaged flag sets: video_mocap | hmr_full | hmr_part | mht_rotation."""
     return load_config(os.path.join(CONFIG_DIR, name + ".yaml"))
+
+
+def stage_surface(config: Dict):
+    """EXTENSION: the point-to-surface data term of the chamfer stage (uuo_problem_t.surface) as (weight, stand-off in metres):
+    stages.chamfer.losses.surface_chamfer and stages.chamfer.surface_distance (absent = 0).  Weight 0 or absent = off.  The term
+    REPLACES the vertex term `full_chamfer`: a config that names both with a non-zero weight is refused, and so are the
+    soft-assignment term `soft_chamfer` beside it, negative or non-finite weights and negative or non-finite stand-offs."""
+    st = config["stages"]["chamfer"]
+    losses = st.get("losses") or {}
+    w = losses.get("surface_chamfer", 0.0)
+    w = 0.0 if w is None else float(w)
+    if not math.isfinite(w) or w < 0.0:
+        raise ValueError("stages.chamfer.losses.surface_chamfer must be 0 (off) or a positive weight (got %r)" % (w,))
+    d0 = st.get("surface_distance", 0.0)
+    d0 = 0.0 if d0 is None else float(d0)
+    if not math.isfinite(d0) or d0 < 0.0:
+        raise ValueError("stages.chamfer.surface_distance must be a finite number of metres >= 0 (got %r)" % (d0,))
+    if w > 0.0 and float(losses.get("full_chamfer", 0.0) or 0.0) != 0.0:
+        raise ValueError("stages.chamfer.losses: surface_chamfer replaces full_chamfer (the point-to-surface term is the stage's "
+                         "data term); name one of them, not both")
+    if w > 0.0 and float(losses.get("soft_chamfer", 0.0) or 0.0) != 0.0:
+        raise NotImplementedError("stages.chamfer: surface_chamfer (point-to-surface term) is not built for the soft-assignment "
+                                  "term soft_chamfer; use one or the other")
+    return w, d0

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "frame_math.h"
+#include "tri_math.h"
 
 #define UUO_STAGE_UPSTREAM 3  // internal: not a fitting stage (uuo_smpl_backward)
 
@@ -430,9 +431,12 @@ __device__ __forceinline__ float gmof_q(float sig2, float s) { return sig2 / (si
 // rest-space position is vp + o_m wherever it enters (the skinned position and the dA outer product), and its d loss / d o =
 // T^T g (dvp, which the blend gradients use too) goes to offs_part[f][mm] for k_finalize_o.  The host launches these with
 // d0 = 0 (the offset carries the stand-off), so the marker branch is the plain square.  Separate instantiations.
+// FASSIGN (EXTENSION, item mode only; uuo_fit_set_surface): the items' vertex ids change with the frame, assign is [F][M]
+// (k_ring_pick chose them in this evaluation).  Separate instantiations: k_bwd_items_f / k_bwd_items_t_f.
 template <bool PART = false, int NWV = BWD_NW, bool DENSE = false, bool ITEMS = false, bool ROBUST = false, bool ACCEL = false,
-          bool OFFS = false>
+          bool OFFS = false, bool FASSIGN = false>
 __device__ __forceinline__ void bwd_body(const BwdArgs& a) {
+  static_assert(!FASSIGN || (ITEMS && !OFFS), "per-frame vertex ids belong to item mode (the surface chamfer closure)");
   static_assert(!OFFS || (!PART && !DENSE && NWV == BWD_NW), "the latent marker offsets are built for the marker stage's "
                 "sparse kernels only");
   static_assert(!ROBUST || (!DENSE && !ITEMS), "the robust data term is formed on the sparse items (k_bary_fwd for item mode)");
@@ -589,7 +593,10 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a) {
       int vi;
       float up0 = 0.f, up1 = 0.f, up2 = 0.f;
       if constexpr (ITEMS) {
-        vi = a.assign[mm];
+        if constexpr (FASSIGN)
+          vi = a.assign[(size_t)f * M + mm];
+        else
+          vi = a.assign[mm];
         const float* pu = a.up_items + ((size_t)f * M + mm) * 3;
         up0 = pu[0]; up1 = pu[1]; up2 = pu[2];
       } else if (a.stage == UUO_STAGE_UPSTREAM) {
@@ -1147,6 +1154,13 @@ __global__ __launch_bounds__(BWD_NW * 64) void k_bwd_dense(BwdArgs a) { bwd_body
 __global__ __launch_bounds__(BWD_NW * 64) void k_bwd_items(BwdArgs a) { bwd_body<false, BWD_NW, false, true>(a); }
 // EXTENSION: the same with the joint-acceleration term (k_bary_fwd / k_bary_fwd_r before it, plain or robust)
 __global__ __launch_bounds__(BWD_NW * 64) void k_bwd_items_t(BwdArgs a) { bwd_body<false, BWD_NW, false, true, false, true>(a); }
+// EXTENSION: the surface chamfer closure's items (uuo_fit_set_surface): vertex ids per frame
+__global__ __launch_bounds__(BWD_NW * 64) void k_bwd_items_f(BwdArgs a) {
+  bwd_body<false, BWD_NW, false, true, false, false, false, true>(a);
+}
+__global__ __launch_bounds__(BWD_NW * 64) void k_bwd_items_t_f(BwdArgs a) {
+  bwd_body<false, BWD_NW, false, true, false, true, false, true>(a);
+}
 // EXTENSION: latent per-marker offsets (uuo_problem_t.w_offsets): the one-hot marker closure -- plain, robust, with the
 // joint-acceleration term, both -- and the item kernels of the three-corner placement (k_bary_fwd_o / _ro before them)
 __global__ __launch_bounds__(BWD_NW * 64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_bwd_sparse_o(BwdArgs a) {
@@ -1324,6 +1338,164 @@ __global__ __launch_bounds__(BWD_NW * 64) void k_bary_fwd_r(BaryFwdArgs a) { bar
 // EXTENSION: with the latent marker offsets (uuo_problem_t.w_offsets)
 __global__ __launch_bounds__(BWD_NW * 64) void k_bary_fwd_o(BaryFwdArgs a) { bary_fwd_body<false, true>(a); }
 __global__ __launch_bounds__(BWD_NW * 64) void k_bary_fwd_ro(BaryFwdArgs a) { bary_fwd_body<true, true>(a); }
+// ----------------------------------------------------------------------------------------------------
+// EXTENSION (not reference behaviour; uuo_fit_set_surface): the chamfer stage's data term as a point-to-surface distance
+// with a stand-off.  k_ring_pick (nn_kernels.hip) has chosen, for every (frame, marker), the face of the nearest vertex's
+// one-ring that lies closest in the search's vertex buffer; this pass is k_bary_fwd with those corners read per frame and the
+// weights formed HERE: the three corners are re-skinned in fp32 (the same gather-LBS), the closest point of the marker on
+// their triangle gives b (closest_on_triangle + tri_bary_cramer, the arithmetic of uuo_mesh_closest_points), p = sum b_k v_k,
+// r = |x - p|, term rho((r - d0)^2).  b is held fixed in the gradient (exact where the term is differentiable: envelope
+// theorem), so corner k's item is b_k d term / d p, as in k_bary_fwd; r = 0 gives no gradient, like the marker stage's term.
+// The search buffer thus decides only WHICH face is used; loss and gradient see fp32 corners.  Items and the frame's loss sum
+// go to k_bwd_items_f / k_bwd_items_t_f; the weights are kept for uuo_fit_surface_corners.
+// ----------------------------------------------------------------------------------------------------
+struct SurfFwdArgs {
+  uuo_gptr<const float> PT, ST, vt, Ww;
+  uuo_gptr<const int> Wi;
+  uuo_gptr<const UuoTree> tree;
+  int V, F, M;
+  UuoPoseSrc src;
+  uuo_gptr<const float> markers, mask;
+  uuo_gptr<const int> corners;   // [F][M][3]
+  float cg, d0;
+  float rs2;                     // robust_sigma^2 (k_surf_fwd_r only)
+  uuo_gptr<float> frames;        // [F][FrameLds]: left for the backward kernel of the same evaluation
+  uuo_gptr<float> up_items;      // [F][3 M][3]
+  uuo_gptr<float> item_loss;     // [F]
+  uuo_gptr<float> bary;          // [F][M][3] out
+};
+template <bool ROBUST>
+__device__ __forceinline__ void surf_fwd_body(const SurfFwdArgs& a) {
+  constexpr int NT = BWD_NW * 64, SLOTS = BWD_NW * 4;
+  __shared__ FrameLds L;
+  __shared__ float sA[UUO_NUM_JOINTS * 12];
+  __shared__ float spf[UUO_KB];
+  __shared__ float sloss[SLOTS];
+  const int f = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int M = a.M;
+  frame_forward(a.src, a.tree, f, L);  // (ends with a barrier)
+  if (tid < UUO_NUM_JOINTS) frame_skin_matrix(L, tid, sA + tid * 12);
+  if (tid < UUO_KB) {
+    float v = 0.f;
+    if (tid < UUO_NUM_POSE_FEATS) {
+      const int j = 1 + tid / 9, e = tid % 9;
+      v = L.R[j][e] - ((e == 0 || e == 4 || e == 8) ? 1.f : 0.f);
+    }
+    spf[tid] = v;
+  }
+  __syncthreads();
+  {  // the frame's state for the backward kernel of this evaluation
+    constexpr int NW = sizeof(FrameLds) / 4;
+    const float* src_l = reinterpret_cast<const float*>(&L);
+    for (int i = tid; i < NW; i += NT) a.frames[(size_t)f * NW + i] = src_l[i];
+  }
+  float tr[3] = {0.f, 0.f, 0.f};
+  if (a.src.trans) {
+    tr[0] = a.src.trans[(size_t)f * 3];
+    tr[1] = a.src.trans[(size_t)f * 3 + 1];
+    tr[2] = a.src.trans[(size_t)f * 3 + 2];
+  }
+  const int gq = lane >> 4, sl = lane & 15;
+  const int slot = wave * 4 + gq;
+  float fk[13];
+#pragma unroll
+  for (int t = 0; t < 13; ++t) fk[t] = spf[sl + 16 * t];
+  const float beta_s = (sl < 10) ? L.beta[sl] : 0.f;
+  auto row_sum = [](float v) {
+    v += dpp_rot<0x128>(v);
+    v += dpp_rot<0x124>(v);
+    v += dpp_rot<0x122>(v);
+    v += dpp_rot<0x121>(v);
+    return v;
+  };
+  float acc_loss = 0.f;
+  const int rounds = (M + SLOTS - 1) / SLOTS;
+  for (int r = 0; r < rounds; ++r) {
+    const int m = slot + SLOTS * r;
+    const bool in = m < M;
+    const int mm = in ? m : 0;
+    const size_t fm = (size_t)f * M + mm;
+    const float wgt = in ? a.mask[fm] : 0.f;
+    float cv[3][3];  // the corners, skinned (every sub-lane of the group holds all three)
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      int vi = a.corners[fm * 3 + k];
+      if ((unsigned)vi >= (unsigned)a.V) vi = 0;
+      const float* pt = a.PT + (size_t)vi * 3 * UUO_KB + sl;
+      float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+#pragma unroll
+      for (int t = 0; t < 13; ++t) {
+        s0 = fmaf(pt[16 * t], fk[t], s0);
+        s1 = fmaf(pt[UUO_KB + 16 * t], fk[t], s1);
+        s2 = fmaf(pt[2 * UUO_KB + 16 * t], fk[t], s2);
+      }
+      const float* ps = a.ST + (size_t)vi * 30 + (sl < 10 ? sl : 0);
+      const float st0 = (sl < 10) ? ps[0] : 0.f, st1 = (sl < 10) ? ps[10] : 0.f, st2 = (sl < 10) ? ps[20] : 0.f;
+      float vp[3];
+      vp[0] = row_sum(s0) + (a.vt[(size_t)vi * 3] + row_sum(st0 * beta_s));
+      vp[1] = row_sum(s1) + (a.vt[(size_t)vi * 3 + 1] + row_sum(st1 * beta_s));
+      vp[2] = row_sum(s2) + (a.vt[(size_t)vi * 3 + 2] + row_sum(st2 * beta_s));
+      const int4 wi = *reinterpret_cast<const int4*>(a.Wi + (size_t)vi * 4);
+      const float4 w4 = *reinterpret_cast<const float4*>(a.Ww + (size_t)vi * 4);
+      const int wj[4] = {wi.x, wi.y, wi.z, wi.w};
+      const float ww[4] = {w4.x, w4.y, w4.z, w4.w};
+      float T[12];
+#pragma unroll
+      for (int e = 0; e < 12; ++e) T[e] = 0.f;
+#pragma unroll
+      for (int n = 0; n < 4; ++n) {
+        const float* pa = sA + wj[n] * 12;
+#pragma unroll
+        for (int e = 0; e < 12; ++e) T[e] = fmaf(ww[n], pa[e], T[e]);
+      }
+      cv[k][0] = fmaf(T[2], vp[2], fmaf(T[1], vp[1], T[0] * vp[0])) + T[3] + tr[0];
+      cv[k][1] = fmaf(T[6], vp[2], fmaf(T[5], vp[1], T[4] * vp[0])) + T[7] + tr[1];
+      cv[k][2] = fmaf(T[10], vp[2], fmaf(T[9], vp[1], T[8] * vp[0])) + T[11] + tr[2];
+    }
+    const float* px = a.markers + fm * 3;
+    const float x0 = px[0], x1 = px[1], x2 = px[2];
+    const TriHit h = closest_on_triangle(x0, x1, x2, cv[0][0], cv[0][1], cv[0][2], cv[1][0], cv[1][1], cv[1][2], cv[2][0], cv[2][1],
+                                         cv[2][2]);
+    float bk[3];
+    tri_bary_cramer(h.cx, h.cy, h.cz, cv[0][0], cv[0][1], cv[0][2], cv[1][0], cv[1][1], cv[1][2], cv[2][0], cv[2][1], cv[2][2], bk);
+    float vm[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      vm[0] = fmaf(bk[k], cv[k][0], vm[0]);
+      vm[1] = fmaf(bk[k], cv[k][1], vm[1]);
+      vm[2] = fmaf(bk[k], cv[k][2], vm[2]);
+    }
+    const float dx = x0 - vm[0], dy = x1 - vm[1], dz = x2 - vm[2];
+    const float rr = sqrtf((dx * dx + dy * dy) + dz * dz);
+    const float e = rr - a.d0;
+    float lw = wgt, gw = wgt;
+    if constexpr (ROBUST) {
+      const float q = gmof_q(a.rs2, e * e);
+      lw = wgt * q;
+      gw = wgt * (q * q);
+    }
+    acc_loss += lw * (e * e);
+    const float sc = (rr > 0.f) ? (-a.cg * gw * e / rr) : 0.f;
+    if (in && sl < 9) {  // sub-lane 3 k + c writes component c of corner k's item
+      const int k = sl / 3, c = sl - 3 * k;
+      const float gc = sc * ((c == 0) ? dx : ((c == 1) ? dy : dz));
+      const float b = (k == 0) ? bk[0] : ((k == 1) ? bk[1] : bk[2]);
+      a.up_items[((size_t)f * 3 * M + (size_t)m * 3 + k) * 3 + c] = b * gc;
+    } else if (in && sl >= 9 && sl < 12) {
+      const int k = sl - 9;
+      a.bary[fm * 3 + k] = (k == 0) ? bk[0] : ((k == 1) ? bk[1] : bk[2]);
+    }
+  }
+  if (sl == 0) sloss[slot] = acc_loss;
+  __syncthreads();
+  if (tid == 0) {
+    float t = 0.f;
+    for (int s = 0; s < SLOTS; ++s) t += sloss[s];
+    a.item_loss[f] = t;
+  }
+}
+__global__ __launch_bounds__(BWD_NW * 64) void k_surf_fwd(SurfFwdArgs a) { surf_fwd_body<false>(a); }
+__global__ __launch_bounds__(BWD_NW * 64) void k_surf_fwd_r(SurfFwdArgs a) { surf_fwd_body<true>(a); }
 // part stage on its cached pose blend: a fraction of the registers and two thirds of the LDS of the general kernel
 // two forms: one wave per frame for <= 16 markers (the candidate search: four items per pass), four waves per frame above
 // that (hmr_full.yaml: 50 markers on the full skeleton would be 13 passes of one wave)
@@ -1491,6 +1663,39 @@ static int validate_problem(const uuo_fit* fit, const uuo_problem_t* p) {
               "closure: w_offsets (latent marker offsets, extension) is built for the marker stage only");
   UUO_REQUIRE(p->w_offsets == 0.f || !uuo_recorder,
               "closure: lock-step batches do not carry the latent marker offsets (w_offsets, extension)");
+  // EXTENSION: the point-to-surface chamfer term of the workspace (uuo_fit_set_surface)
+  UUO_REQUIRE(fit->surface == 0 || p->stage == UUO_STAGE_CHAMFER,
+              "closure: the point-to-surface term (uuo_fit_set_surface, extension) is built for the chamfer stage only");
+  UUO_REQUIRE(fit->surface == 0 || p->w_soft == 0.f,
+              "closure: the point-to-surface term (uuo_fit_set_surface, extension) is not built for the soft-assignment data "
+              "term (w_soft)");
+  UUO_REQUIRE(fit->surface == 0 || !uuo_recorder,
+              "closure: lock-step batches do not carry the point-to-surface term (uuo_fit_set_surface, extension)");
+  UUO_REQUIRE(fit->surface == 0 || (fit->model->ring_off && fit->model->faces),
+              "closure: the point-to-surface term (uuo_fit_set_surface, extension) needs the model's faces (uuo_model_set_faces)");
+  return 0;
+}
+
+extern "C" int uuo_fit_set_surface(uuo_fit_t* fit, int32_t on, float surface_distance) {
+  UUO_REQUIRE(fit, "uuo_fit_set_surface: null fit");
+  UUO_REQUIRE(on == 0 || on == 1, "uuo_fit_set_surface: `on` is 0 (off) or 1");
+  UUO_REQUIRE(on == 0 || (surface_distance >= 0.f && surface_distance <= 3.0e38f),
+              "uuo_fit_set_surface: surface_distance (the stand-off) must be a finite number of metres >= 0");
+  UUO_REQUIRE(on == 0 || !uuo_recorder, "uuo_fit_set_surface: lock-step batches do not carry the point-to-surface term");
+  UUO_REQUIRE(on == 0 || (fit->model->ring_off && fit->model->faces),
+              "uuo_fit_set_surface: the point-to-surface term needs the model's faces (uuo_model_set_faces)");
+  fit->surface = on;
+  fit->surface_distance = on ? surface_distance : 0.f;
+  return 0;
+}
+
+// EXTENSION: corners and weights of the last surface-term evaluation on `fit` (copied on `stream`, behind that evaluation)
+extern "C" int uuo_fit_surface_corners(uuo_fit_t* fit, void* stream, int32_t* d_corners, float* d_bary) {
+  UUO_REQUIRE(fit, "uuo_fit_surface_corners: null fit");
+  UUO_REQUIRE(fit->surf_corners && fit->surf_bary, "uuo_fit_surface_corners: no surface-term evaluation has run on this workspace");
+  const size_t n = (size_t)fit->F * fit->M * 3;
+  if (d_corners) UUO_HIP_CHECK(hipMemcpyAsync(d_corners, fit->surf_corners, n * sizeof(int32_t), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  if (d_bary) UUO_HIP_CHECK(hipMemcpyAsync(d_bary, fit->surf_bary, n * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return 0;
 }
 
@@ -2014,6 +2219,44 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
       hipLaunchKernelGGL(k_bwd_items_t, dim3(F), dim3(BWD_NW * 64), 0, s, a);
     else
       hipLaunchKernelGGL(k_bwd_items, dim3(F), dim3(BWD_NW * 64), 0, s, a);
+  } else if (fit->surface != 0) {
+    // EXTENSION: point-to-surface chamfer term.  The forward above has skinned the vertices and found every marker's nearest
+    // one; k_ring_pick chooses a face of its one-ring in that buffer, k_surf_fwd re-skins the face's corners, forms the
+    // term and its per-corner items, and the sparse backward runs on those items with per-frame vertex ids
+    UUO_REQUIRE(!uuo_recorder, "closure: the surface chamfer closure is not available inside a lock-step batch");
+    UUO_REQUIRE(p->stage == UUO_STAGE_CHAMFER && !soft, "closure: the surface term belongs to the chamfer stage's hard assignment");
+    if (!fit->bary_items) UUO_HIP_CHECK(hipMalloc((void**)&fit->bary_items, ((size_t)F * 3 * M * 3 + F) * sizeof(float)));
+    if (!fit->surf_corners) {
+      UUO_HIP_CHECK(hipMalloc((void**)&fit->surf_corners, (size_t)F * M * 3 * (sizeof(int) + sizeof(float))));
+      fit->surf_bary = reinterpret_cast<float*>(fit->surf_corners + (size_t)F * M * 3);
+    }
+    float* items = fit->bary_items;
+    float* item_loss = fit->bary_items + (size_t)F * 3 * M * 3;
+    rc = uuo_launch_ring_pick(m, s, F, M, fit->verts, p->d_markers, fit->nn, nullptr, fit->mask, fit->surf_corners, nullptr, nullptr,
+                              nullptr, nullptr);
+    if (rc) return rc;
+    SurfFwdArgs b;
+    std::memset(&b, 0, sizeof(b));
+    b.PT = m->PT; b.ST = m->ST; b.vt = m->vt; b.Ww = m->Ww; b.Wi = m->Wi; b.tree = m->tree;
+    b.V = m->V; b.F = F; b.M = M;
+    b.src = src;
+    b.markers = p->d_markers;
+    b.mask = fit->mask;
+    b.corners = fit->surf_corners;
+    b.cg = a.cg;
+    b.d0 = fit->surface_distance;
+    b.rs2 = a.rs2;
+    b.frames = fit->frames;
+    b.up_items = items;
+    b.item_loss = item_loss;
+    b.bary = fit->surf_bary;
+    hipLaunchKernelGGL(robust ? k_surf_fwd_r : k_surf_fwd, dim3(F), dim3(BWD_NW * 64), 0, s, b);
+    a.M = 3 * M;
+    a.assign = fit->surf_corners;
+    a.up_items = items;
+    a.item_loss = item_loss;
+    a.frames = fit->frames;
+    hipLaunchKernelGGL(temporal ? k_bwd_items_t_f : k_bwd_items_f, dim3(F), dim3(BWD_NW * 64), 0, s, a);
   } else if (soft && p->stage == UUO_STAGE_CHAMFER) {
     // EXTENSION: soft-assignment data term of the chamfer stage.  The forward above has skinned the vertices and run the exact
     // search (dmin, the hard assignment); the soft minimum gives EVERY vertex within reach of a marker a gradient, so the

@@ -741,6 +741,7 @@ extern "C" int uuo_fit_destroy(uuo_fit_t* fit) {
   if (fit->soft_sm) (void)hipFree(fit->soft_sm);
   if (fit->bary_items) (void)hipFree(fit->bary_items);
   if (fit->offs_part) (void)hipFree(fit->offs_part);
+  if (fit->surf_corners) (void)hipFree(fit->surf_corners);  // (surf_bary is the same allocation)
   if (fit->dbg_verts) (void)hipFree(fit->dbg_verts);
   if (fit->ev0) (void)hipEventDestroy(fit->ev0);
   if (fit->ev1) (void)hipEventDestroy(fit->ev1);
@@ -796,6 +797,8 @@ static int shared_prepare(uuo_fit_t* fit, hipStream_t s, const uuo_problem_t* p,
   // EXTENSION: the per-evaluation exchange carries the betas' share only, not the latent marker offsets
   UUO_REQUIRE(p->w_offsets == 0.f, "uuo_lbfgs_solve_shared: shared-betas solves do not carry the latent marker offsets (w_offsets, "
               "extension)");
+  UUO_REQUIRE(fit->surface == 0, "uuo_lbfgs_solve_shared: shared-betas solves do not carry the point-to-surface chamfer term "
+              "(uuo_fit_set_surface, extension)");
   const int hist = opt->history_size > 0 ? opt->history_size : 100;
   const int n_params = uuo_problem_num_params(p);
   LbWs* w = (LbWs*)fit->lbws;

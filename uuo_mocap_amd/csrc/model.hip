@@ -230,9 +230,66 @@ extern "C" int uuo_model_create(const float* vt, const float* S, const float* P,
   return 0;
 }
 
+// EXTENSION (surface chamfer term): vertex -> incident faces, ascending face ids per vertex (faces are visited in order).
+// Host only.  A face that names a vertex twice is listed once for it.
+extern "C" int uuo_ring_table(const int32_t* h_faces, int NF, int V, int32_t* h_off, int32_t* h_ring) {
+  UUO_REQUIRE(h_faces && h_off && h_ring, "uuo_ring_table: null argument");
+  UUO_REQUIRE(NF > 0 && V > 0, "uuo_ring_table: sizes must be positive");
+  std::vector<int> count(V, 0);
+  auto listed_before = [&](int t, int k) {  // corner k of face t repeats an earlier corner of that face
+    for (int q = 0; q < k; ++q)
+      if (h_faces[(size_t)t * 3 + q] == h_faces[(size_t)t * 3 + k]) return true;
+    return false;
+  };
+  for (int t = 0; t < NF; ++t)
+    for (int k = 0; k < 3; ++k) {
+      const int v = h_faces[(size_t)t * 3 + k];
+      UUO_REQUIRE(v >= 0 && v < V, "uuo_ring_table: face " + std::to_string(t) + " names a vertex outside 0 .. V-1");
+      if (!listed_before(t, k)) ++count[v];
+    }
+  h_off[0] = 0;
+  for (int v = 0; v < V; ++v) {
+    UUO_REQUIRE(count[v] <= UUO_RING_MAX_VALENCE,
+                "uuo_ring_table: vertex " + std::to_string(v) + " has " + std::to_string(count[v]) +
+                    " incident faces; the one-ring search supports at most " + std::to_string(UUO_RING_MAX_VALENCE));
+    h_off[v + 1] = h_off[v] + count[v];
+  }
+  std::vector<int> fill(h_off, h_off + V);
+  for (int t = 0; t < NF; ++t)
+    for (int k = 0; k < 3; ++k)
+      if (!listed_before(t, k)) h_ring[fill[h_faces[(size_t)t * 3 + k]]++] = t;
+  return 0;
+}
+
+extern "C" int uuo_model_set_faces(uuo_model_t* m, const int32_t* h_faces, int NF) {
+  UUO_REQUIRE(m && h_faces, "uuo_model_set_faces: null argument");
+  UUO_REQUIRE(NF > 0 && NF < (1 << 26), "uuo_model_set_faces: bad face count");
+  std::vector<int> off((size_t)m->V + 1), ring((size_t)NF * 3), faces(h_faces, h_faces + (size_t)NF * 3);
+  int rc = uuo_ring_table(h_faces, NF, m->V, off.data(), ring.data());
+  if (rc) return rc;
+  ring.resize(off[m->V] > 0 ? off[m->V] : 1);
+  int *d_faces = nullptr, *d_off = nullptr, *d_ring = nullptr;
+  rc |= upload(&d_faces, faces);
+  rc |= upload(&d_off, off);
+  rc |= upload(&d_ring, ring);
+  if (rc) {
+    for (void* p : {(void*)d_faces, (void*)d_off, (void*)d_ring})
+      if (p) (void)hipFree(p);
+    return rc;
+  }
+  for (void* p : {(void*)m->faces, (void*)m->ring_off, (void*)m->ring_faces})
+    if (p) (void)hipFree(p);
+  m->faces = d_faces;
+  m->ring_off = d_off;
+  m->ring_faces = d_ring;
+  m->NF = NF;
+  return 0;
+}
+
 extern "C" int uuo_model_destroy(uuo_model_t* m) {
   if (!m) return 0;
-  void* ptrs[] = {m->P3, m->P16, m->vt3, m->PT, m->ST, m->vt, m->Wi, m->Ww, m->tree, m->PB, m->JLoff, m->JLv, m->JLw};
+  void* ptrs[] = {m->P3, m->P16, m->vt3, m->PT, m->ST, m->vt, m->Wi, m->Ww, m->tree, m->PB, m->JLoff, m->JLv, m->JLw,
+                  m->faces, m->ring_off, m->ring_faces};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (auto& kv : m->bwd) {

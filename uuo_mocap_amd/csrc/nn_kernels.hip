@@ -4,6 +4,7 @@
 #include "frame_math.h"
 
 #define UUO_INF __builtin_huge_valf()
+#include "tri_math.h"
 
 // IEEE square root and division, correctly rounded.  HIP's __fsqrt_rn is NOT that: without OCML_BASIC_ROUNDED_OPERATIONS it
 // is __ocml_native_sqrt_f32 (v_sqrt_f32, 1 ulp) -- found in round 3 when the rigidity matrix differed from numpy's in a third
@@ -1395,47 +1396,6 @@ int uuo_launch_soft_chamfer(hipStream_t s, int F, int M, int V, const float* mar
 // markers are broadcast from LDS; faces are merged with a 64-bit min on (d^2 bits << 32 | face), so ties go to the
 // lowest face index independent of the schedule.
 // ----------------------------------------------------------------------------------------------------
-struct TriHit {
-  float cx, cy, cz, d2;
-};
-__device__ __forceinline__ TriHit closest_on_triangle(float px, float py, float pz, float ax, float ay, float az,
-                                                      float bx, float by, float bz, float cx, float cy, float cz) {
-  const float abx = bx - ax, aby = by - ay, abz = bz - az;
-  const float acx = cx - ax, acy = cy - ay, acz = cz - az;
-  const float apx = px - ax, apy = py - ay, apz = pz - az;
-  const float d1 = abx * apx + aby * apy + abz * apz, d2 = acx * apx + acy * apy + acz * apz;
-  const float bpx = px - bx, bpy = py - by, bpz = pz - bz;
-  const float d3 = abx * bpx + aby * bpy + abz * bpz, d4 = acx * bpx + acy * bpy + acz * bpz;
-  const float cpx = px - cx, cpy = py - cy, cpz = pz - cz;
-  const float d5 = abx * cpx + aby * cpy + abz * cpz, d6 = acx * cpx + acy * cpy + acz * cpz;
-  const float vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
-  float v, w;  // closest point = a + v*ab + w*ac
-  if (d1 <= 0.f && d2 <= 0.f) {  // vertex region a
-    v = 0.f; w = 0.f;
-  } else if (d3 >= 0.f && d4 <= d3) {  // vertex region b
-    v = 1.f; w = 0.f;
-  } else if (vc <= 0.f && d1 >= 0.f && d3 <= 0.f) {  // edge ab
-    v = d1 / (d1 - d3); w = 0.f;
-  } else if (d6 >= 0.f && d5 <= d6) {  // vertex region c
-    v = 0.f; w = 1.f;
-  } else if (vb <= 0.f && d2 >= 0.f && d6 <= 0.f) {  // edge ac
-    v = 0.f; w = d2 / (d2 - d6);
-  } else if (va <= 0.f && (d4 - d3) >= 0.f && (d5 - d6) >= 0.f) {  // edge bc
-    w = (d4 - d3) / ((d4 - d3) + (d5 - d6)); v = 1.f - w;
-  } else {  // interior
-    const float denom = 1.f / (va + vb + vc);
-    v = vb * denom; w = vc * denom;
-  }
-  TriHit h;
-  h.cx = ax + abx * v + acx * w;
-  h.cy = ay + aby * v + acy * w;
-  h.cz = az + abz * v + acz * w;
-  const float ex = px - h.cx, ey = py - h.cy, ez = pz - h.cz;
-  h.d2 = ex * ex + ey * ey + ez * ez;
-  if (!(h.d2 == h.d2)) h.d2 = UUO_INF;  // degenerate triangle (0/0): never the winner
-  return h;
-}
-
 #define MESH_MB 16  // query points per block
 __global__ __launch_bounds__(256) void k_mesh_closest(int M, int V, int NF, const float* __restrict__ verts,
                                                        const int32_t* __restrict__ faces,
@@ -1529,6 +1489,107 @@ extern "C" int uuo_mesh_closest_points(void* stream, int F, int M, int V, int NF
                      d_verts, d_faces, d_points, d_dist, d_face, d_closest, d_bary);
   UUO_HIP_CHECK(hipGetLastError());
   return 0;
+}
+
+// ----------------------------------------------------------------------------------------------------
+// EXTENSION (not reference behaviour): closest point on the ONE-RING of the nearest vertex -- the point-to-surface chamfer
+// term's pick (uuo_fit_set_surface) and the operator uuo_ring_closest_points.  Work item = (frame, query): it walks the
+// incident faces of its nearest vertex in ascending face id (uuo_model_set_faces' CSR, at most UUO_RING_MAX_VALENCE of them),
+// gathers each face's corners from `verts` and keeps the first minimum of closest_on_triangle's squared distance (strict '<':
+// the lowest face id on exact ties).  A vertex without a face stands for itself: the triangle (v, v, v), face -1.
+// OP: the operator's outputs (distance, face, closest point, "cramer" coordinates); the closure only needs the corners.
+// ----------------------------------------------------------------------------------------------------
+template <bool OP>
+__global__ __launch_bounds__(256) void k_ring_pick(int count, int M, int V, int NF, const int* __restrict__ faces,
+                                                    const int* __restrict__ ring_off, const int* __restrict__ ring_faces,
+                                                    const float* __restrict__ verts, const float* __restrict__ points,
+                                                    const unsigned long long* __restrict__ keys,
+                                                    const int32_t* __restrict__ nn_idx, const float* __restrict__ mask,
+                                                    int32_t* __restrict__ corners, float* __restrict__ dist,
+                                                    int32_t* __restrict__ face_out, float* __restrict__ closest,
+                                                    float* __restrict__ bary) {
+  const int i = blockIdx.x * 256 + threadIdx.x;  // = f * M + m
+  if (i >= count) return;
+  const int f = i / M;
+  int nn = keys ? (int)(unsigned)(keys[i] & 0xFFFFFFFFull) : nn_idx[i];
+  if ((unsigned)nn >= (unsigned)V) nn = 0;  // never happens for a completed search; keeps the gathers in bounds
+  const float* vf = verts + (size_t)f * V * 3;
+  const float px = points[(size_t)i * 3], py = points[(size_t)i * 3 + 1], pz = points[(size_t)i * 3 + 2];
+  int c0 = nn, c1 = nn, c2 = nn, bestf = -1;
+  float best = UUO_INF;
+  const bool hidden = mask && mask[i] == 0.f;
+  if (!hidden) {
+    const int lo = ring_off[nn];
+    int n = ring_off[nn + 1] - lo;
+    n = n < 0 ? 0 : (n > UUO_RING_MAX_VALENCE ? UUO_RING_MAX_VALENCE : n);
+    for (int k = 0; k < n; ++k) {
+      const int t = ring_faces[lo + k];
+      if ((unsigned)t >= (unsigned)NF) continue;
+      const int i0 = faces[(size_t)t * 3], i1 = faces[(size_t)t * 3 + 1], i2 = faces[(size_t)t * 3 + 2];
+      if ((unsigned)i0 >= (unsigned)V || (unsigned)i1 >= (unsigned)V || (unsigned)i2 >= (unsigned)V) continue;
+      const TriHit h = closest_on_triangle(px, py, pz, vf[i0 * 3], vf[i0 * 3 + 1], vf[i0 * 3 + 2], vf[i1 * 3], vf[i1 * 3 + 1],
+                                           vf[i1 * 3 + 2], vf[i2 * 3], vf[i2 * 3 + 1], vf[i2 * 3 + 2]);
+      if (h.d2 < best) {
+        best = h.d2;
+        bestf = t;
+        c0 = i0; c1 = i1; c2 = i2;
+      }
+    }
+  }
+  if (corners) {
+    corners[(size_t)i * 3] = c0;
+    corners[(size_t)i * 3 + 1] = c1;
+    corners[(size_t)i * 3 + 2] = c2;
+  }
+  if constexpr (OP) {
+    const float ax = vf[c0 * 3], ay = vf[c0 * 3 + 1], az = vf[c0 * 3 + 2];
+    const float bx = vf[c1 * 3], by = vf[c1 * 3 + 1], bz = vf[c1 * 3 + 2];
+    const float cx = vf[c2 * 3], cy = vf[c2 * 3 + 1], cz = vf[c2 * 3 + 2];
+    const TriHit h = closest_on_triangle(px, py, pz, ax, ay, az, bx, by, bz, cx, cy, cz);
+    float b[3];
+    tri_bary_cramer(h.cx, h.cy, h.cz, ax, ay, az, bx, by, bz, cx, cy, cz, b);
+    if (dist) dist[i] = sqrtf(h.d2);
+    if (face_out) face_out[i] = bestf;
+    if (closest) {
+      closest[(size_t)i * 3] = h.cx;
+      closest[(size_t)i * 3 + 1] = h.cy;
+      closest[(size_t)i * 3 + 2] = h.cz;
+    }
+    if (bary) {
+      bary[(size_t)i * 3] = b[0];
+      bary[(size_t)i * 3 + 1] = b[1];
+      bary[(size_t)i * 3 + 2] = b[2];
+    }
+  }
+}
+
+int uuo_launch_ring_pick(const uuo_model* m, hipStream_t s, int F, int M, const float* verts, const float* points,
+                         const unsigned long long* keys, const int32_t* nn_idx, const float* mask, int32_t* corners, float* dist,
+                         int32_t* face, float* closest, float* bary) {
+  UUO_REQUIRE(m && m->ring_off && m->ring_faces && m->faces, "one-ring search: the model has no faces (uuo_model_set_faces)");
+  UUO_REQUIRE((keys != nullptr) != (nn_idx != nullptr), "one-ring search: the nearest vertices come as keys or as ids");
+  UUO_REQUIRE((long long)F * (long long)M <= 2147483647LL / 4, "one-ring search: too many queries");
+  const int count = F * M;
+  if (count <= 0) return 0;
+  const bool op = dist || face || closest || bary;
+  if (op)
+    hipLaunchKernelGGL(k_ring_pick<true>, dim3((count + 255) / 256), dim3(256), 0, s, count, M, m->V, m->NF, m->faces, m->ring_off,
+                       m->ring_faces, verts, points, keys, nn_idx, mask, corners, dist, face, closest, bary);
+  else
+    hipLaunchKernelGGL(k_ring_pick<false>, dim3((count + 255) / 256), dim3(256), 0, s, count, M, m->V, m->NF, m->faces,
+                       m->ring_off, m->ring_faces, verts, points, keys, nn_idx, mask, corners, dist, face, closest, bary);
+  UUO_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int uuo_ring_closest_points(void* stream, uuo_model_t* model, int F, int M, const float* d_verts,
+                                       const float* d_points, const int32_t* d_nn_idx, float* d_dist, int32_t* d_face,
+                                       float* d_closest, float* d_bary) {
+  UUO_REQUIRE(model && d_verts && d_points && d_nn_idx && d_dist && d_face && d_closest && d_bary,
+              "uuo_ring_closest_points: null argument");
+  UUO_REQUIRE(F >= 0 && M >= 0, "uuo_ring_closest_points: negative size");
+  return uuo_launch_ring_pick(model, (hipStream_t)stream, F, M, d_verts, d_points, nullptr, d_nn_idx, nullptr, nullptr, d_dist,
+                              d_face, d_closest, d_bary);
 }
 
 // ----------------------------------------------------------------------------------------------------

@@ -118,6 +118,11 @@ struct uuo_model {
   int* JLoff = nullptr;   // [25] joint j's (vertex, weight) pairs are entries JLoff[j] .. JLoff[j+1] of JLv / JLw (vertices ascending)
   int* JLv = nullptr;
   float* JLw = nullptr;
+  // EXTENSION (uuo_model_set_faces): the triangles and each vertex's one-ring, for the point-to-surface chamfer term
+  int NF = 0;
+  int* faces = nullptr;      // [NF][3]
+  int* ring_off = nullptr;   // [V + 1] CSR offsets: vertex v's incident faces are ring_faces[ring_off[v] .. ring_off[v + 1])
+  int* ring_faces = nullptr; // ascending face ids per vertex, at most UUO_RING_MAX_VALENCE of them
   // scratch of the dense backward, one set per stream (as `fwd`)
   struct BwdScratch {
     std::mutex mu;
@@ -174,6 +179,8 @@ struct uuo_fit {
   float* dbg_verts = nullptr;          // debug flavour, UUO_SKIN_F16_CHECK: the fp32 kernel's vertices and boxes beside k_skin3's (first use)
   float* bary_items = nullptr;         // marker stage on a three-corner placement: [F][3 M][3] corner items + [F] loss sums (first use)
   float* offs_part = nullptr;          // EXTENSION, latent marker offsets: [F][<= 3 M][3] per-item d loss / d o (first use)
+  int* surf_corners = nullptr;         // EXTENSION, surface chamfer term: [F][M][3] corner vertex ids of the last evaluation (k_ring_pick)
+  float* surf_bary = nullptr;          //   and [F][M][3] their weights (k_surf_fwd); allocated together on first use
   int* nn_flags = nullptr;          // [F][8] survivor counts of the pruned nearest-neighbour search (debug / tests)
   unsigned long long* nn = nullptr; // [F][M] packed (dist bits << 32 | idx)
   float* frame_part = nullptr;      // [F][UUO_FP]: loss, dz, pose sq, dbeta[10], gradient statistics
@@ -193,6 +200,8 @@ struct uuo_fit {
   float joint_accel = 0.f;  // EXTENSION: weight of the joint-acceleration term (uuo_fit_set_joint_accel; 0 = off)
   float foot_lock = 0.f;    // EXTENSION: weight of the foot-lock term (uuo_fit_set_foot_lock; 0 = off) and its contact labels
   const float* foot_contacts = nullptr;  // [F][2] on the device, the caller's (read at evaluation)
+  int surface = 0;               // EXTENSION: point-to-surface chamfer term (uuo_fit_set_surface; 0 = off) and its stand-off
+  float surface_distance = 0.f;
 };
 
 // ---- dense backward of the skinning (dense_bwd.hip) ---------------------------------------------------------------------
@@ -248,6 +257,12 @@ int uuo_launch_joints45(const uuo_model* m, hipStream_t s, int F, const float* j
                         float* joints45);
 int uuo_launch_nn(hipStream_t s, int N, int P1, int P2, const float* x, const float* y, const int32_t* ysub,
                   int P2s, unsigned long long* packed);
+// EXTENSION (surface chamfer term): closest point of every query on the one-ring of its nearest vertex (nn_kernels.hip).
+// The nearest vertex comes as packed search keys (`keys`, the closure) or as plain ids (`nn_idx`, the operator); `mask`
+// (optional) zero = hidden query: no ring walk, corners (nn, nn, nn).  Outputs are optional.
+int uuo_launch_ring_pick(const uuo_model* m, hipStream_t s, int F, int M, const float* verts, const float* points,
+                         const unsigned long long* keys, const int32_t* nn_idx, const float* mask, int32_t* corners, float* dist,
+                         int32_t* face, float* closest, float* bary);
 int uuo_launch_nn_unpack(hipStream_t s, int count, const unsigned long long* packed, float* dist, int32_t* idx);
 int uuo_launch_assign(hipStream_t s, int F, int M, int V, const float* verts, const float* markers,
                       const uint8_t* valid, int32_t* idx, unsigned long long* packed);

@@ -20,6 +20,7 @@ from . import _lib
 from ._lib import (EVAL_CALLBACK, UUO_STAGE_CHAMFER, UUO_STAGE_MARKER, UUO_STAGE_PART, UuoLbfgsOptions,
                    UuoLbfgsStats, UuoProblem, UuoReprojectionProblem, check)
 from .body_model import SmplTables
+from .config import stage_surface
 
 MARKER_DISTANCE = 0.0095  # reference utils/settings.py:1
 
@@ -170,6 +171,9 @@ def solve_batch(problems, xs, max_iter: int, lr: float = 1.0, tolerance_grad: fl
     if any(p.foot_lock != 0.0 for p in problems):
         raise NotImplementedError("lock-step batches do not carry the foot-lock term (foot_lock, extension): "
                                   "solve such problems one by one")
+    if any(getattr(p, "surface", False) for p in problems):
+        raise NotImplementedError("lock-step batches do not carry the point-to-surface chamfer term (surface_chamfer, "
+                                  "extension): solve such problems one by one")
     for p, x in zip(problems, xs):
         assert p.stage == p0.stage and p.F == p0.F and p.M == p0.M and p.model is model
         assert x.is_cuda and x.dtype == torch.float32 and x.numel() == p.n and x.is_contiguous()
@@ -225,6 +229,13 @@ class DeviceModel:
         with torch.cuda.device(self.device):
             check(self.lib.uuo_model_create(*[a.ctypes.data for a in arrs], self.V, byref(handle)), "uuo_model_create")
         self.handle = handle
+        # EXTENSION: the triangles and every vertex's one-ring (surface chamfer term, ring_closest_points)
+        self.has_faces = getattr(tables, "faces", None) is not None
+        if self.has_faces:
+            faces = np.ascontiguousarray(tables.faces, np.int32).reshape(-1, 3)
+            with torch.cuda.device(self.device):
+                check(self.lib.uuo_model_set_faces(self.handle, faces.ctypes.data, int(faces.shape[0])), "uuo_model_set_faces")
+            self.faces = torch.from_numpy(faces.astype(np.int64)).to(self.device)  # [NF, 3], for corner look-ups
         self._fits: "OrderedDict" = OrderedDict()   # (slot, F, M) -> _FitHandle, least recently used first
         self._batches: Dict = {}                    # (group, stage) -> _BatchHandle
         self._fits_lock = threading.Lock()
@@ -374,6 +385,25 @@ class DeviceModel:
                                                   _ptr(valid_u8), _ptr(idx), _ptr(ws)), "uuo_assign_mean_argmin")
         return idx
 
+    def ring_closest_points(self, verts, points, nn_idx):
+        """EXTENSION, uuo_ring_closest_points: closest point of points[f,m] on the faces incident to vertex nn_idx[f,m] of the
+        mesh (verts[f], the model's faces) -> (dist [F,M], face [F,M] int32, closest [F,M,3], barycentric [F,M,3])."""
+        verts = _f32(verts, "verts")
+        points = _f32(points, "points")
+        nn_idx = nn_idx.to(device=self.device, dtype=torch.int32).contiguous()
+        if verts.dim() != 3 or verts.shape[1] != self.V or points.dim() != 3 or points.shape[0] != verts.shape[0] or \
+                tuple(nn_idx.shape) != tuple(points.shape[:2]):
+            raise ValueError("ring_closest_points: verts [F,V,3] of the model, points [F,M,3], nn_idx [F,M] expected")
+        F, M = points.shape[0], points.shape[1]
+        dist = torch.empty((F, M), dtype=torch.float32, device=self.device)
+        face = torch.empty((F, M), dtype=torch.int32, device=self.device)
+        closest = torch.empty((F, M, 3), dtype=torch.float32, device=self.device)
+        bary = torch.empty((F, M, 3), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            check(self.lib.uuo_ring_closest_points(current_stream(self.device), self.handle, F, M, _ptr(verts), _ptr(points),
+                                                   _ptr(nn_idx), _ptr(dist), _ptr(face), _ptr(closest), _ptr(bary)),
+                  "uuo_ring_closest_points")
+        return dist, face, closest, bary
 
     def mesh_closest_points(self, verts, faces, points):
         """uuo_mesh_closest_points (see the module-level function; it needs no model tables)."""
@@ -447,6 +477,9 @@ class _StageProblem:
         # (uuo_fit_set_foot_lock); _set_foot_lock decides once, at construction, whether the term has anything to act on
         self.foot_lock = 0.0
         self.foot_contacts = None
+        # EXTENSION: the point-to-surface data term (ChamferProblem) and its stand-off, armed the same way (uuo_fit_set_surface)
+        self.surface = False
+        self.surface_distance = 0.0
 
     def _set_foot_lock(self, w: float, contacts):
         """EXTENSION: keeps a contiguous float32 device copy of the checked contact labels and the weight the workspace is
@@ -459,13 +492,15 @@ class _StageProblem:
             self.foot_lock = float(w)
 
     def _arm(self):
-        """Sets this problem's joint-acceleration and foot-lock weights (0 without the terms) on its workspace.  The workspace
+        """Sets this problem's joint-acceleration and foot-lock weights (0 without the terms) and its surface term on its workspace.  The workspace
         is shared by every problem of the same (F, M) on this thread, so this runs right before each library call that
         evaluates on it."""
         check(self.lib.uuo_fit_set_joint_accel(self.fit, c_float(self.joint_accel)), "uuo_fit_set_joint_accel")
         check(self.lib.uuo_fit_set_foot_lock(self.fit, c_float(self.foot_lock),
                                              self.foot_contacts.data_ptr() if self.foot_lock != 0.0 else None),
               "uuo_fit_set_foot_lock")
+        check(self.lib.uuo_fit_set_surface(self.fit, 1 if self.surface else 0, c_float(self.surface_distance)),
+              "uuo_fit_set_surface")
 
     def _need_workspace(self):
         if self.fit is None:  # created for a lock-step batch only: give it the thread's workspace on first standalone use
@@ -530,6 +565,9 @@ class _StageProblem:
         all ranks take the same decisions and end with bit-identical betas.  x is updated in place."""
         from ._lib import GATHER_FN, UuoShared
 
+        if self.surface:
+            raise NotImplementedError("shared-betas solves do not carry the point-to-surface chamfer term (surface_chamfer, "
+                                      "extension)")
         assert x.is_cuda and x.dtype == torch.float32 and x.numel() == self.n and x.is_contiguous()
         self._need_workspace()
         opt = UuoLbfgsOptions(int(max_iter), int(history_size), float(lr), float(tolerance_grad),
@@ -704,9 +742,11 @@ class ChamferProblem(_StageProblem):
 
     def __init__(self, smpl_inference, markers, o_pose_body, o_betas, root_orient, config, foot_contacts=None):
         losses = config["stages"]["chamfer"]["losses"]
-        unsupported = set(losses) - {"full_chamfer", "reg_pose_body", "reg_betas", "soft_chamfer", "joint_accel", "foot_lock"}
+        unsupported = set(losses) - {"full_chamfer", "reg_pose_body", "reg_betas", "soft_chamfer", "joint_accel", "foot_lock",
+                                     "surface_chamfer"}
         if unsupported:
             raise NotImplementedError("chamfer-stage losses outside the shipped configs: %s" % sorted(unsupported))
+        w_surface, d_surface = stage_surface(config)  # EXTENSION: point-to-surface data term (0 = off)
         w_accel = stage_joint_accel(config, "chamfer")
         if w_accel > 0.0 and float(losses.get("soft_chamfer", 0.0)) != 0.0:
             raise NotImplementedError("stages.chamfer: the fused joint-acceleration term (joint_accel) is not built for the "
@@ -718,10 +758,14 @@ class ChamferProblem(_StageProblem):
         contacts = check_foot_contacts(foot_contacts, None if markers is None else markers.shape[0])
         if not config["stages"]["chamfer"]["yaw_lock"]:
             raise NotImplementedError("stages.chamfer.yaw_lock False is not a shipped configuration")
-        wd, wp, wb = _cfg_weights(losses, "full_chamfer")
+        wd, wp, wb = _cfg_weights(losses, "surface_chamfer" if w_surface > 0.0 else "full_chamfer")
         sigma = stage_robust_sigma(config, "chamfer")
         super().__init__(smpl_inference.device_model, markers, o_pose_body, o_betas, root_orient, wd, wp, wb)
         self.problem.robust_sigma = sigma  # EXTENSION: Geman-McClure data term (0 = off)
+        if w_surface > 0.0:  # EXTENSION: the data term is the point-to-surface distance on the nearest vertex's one-ring
+            if not self.model.has_faces:
+                raise RuntimeError("stages.chamfer.losses.surface_chamfer needs a body model with faces")
+            self.surface, self.surface_distance = True, d_surface
         self.joint_accel = w_accel  # EXTENSION: joint-acceleration term (0 = off)
         self._set_foot_lock(w_lock, contacts)  # EXTENSION: foot-lock term (weight 0 without gated contacts)
         # EXTENSION (not in the reference): soft assignment of every marker to the body's vertices, fused closure with the dense
@@ -732,6 +776,17 @@ class ChamferProblem(_StageProblem):
             self.problem.soft_tau = float(config["stages"]["chamfer"].get("soft_tau", 1e-3))
             if not self.problem.soft_tau > 0.0:
                 raise ValueError("stages.chamfer.soft_tau must be positive")
+
+    def surface_corners(self):
+        """EXTENSION: (corners [F,M,3] int32 vertex ids, weights [F,M,3]) the last evaluation of the surface term on this
+        problem's workspace used (uuo_fit_surface_corners)."""
+        self._need_workspace()
+        corners = torch.empty((self.F, self.M, 3), dtype=torch.int32, device=self.device)
+        bary = torch.empty((self.F, self.M, 3), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            check(self.lib.uuo_fit_surface_corners(self.fit, current_stream(self.device), _ptr(corners), _ptr(bary)),
+                  "uuo_fit_surface_corners")
+        return corners, bary
 
     def pack(self, trans, z_angle, betas, pose_body):
         return torch.cat([_f32(trans, "trans").reshape(-1), _f32(z_angle, "z").reshape(-1),

@@ -133,6 +133,54 @@ def weighted_chamfer_distance(x: torch.Tensor, y: torch.Tensor, x_weights: torch
     return (d * w).sum() / wsum, None
 
 
+class _RingDistance(torch.autograd.Function):
+    """EXTENSION (not in the reference): distance of every x[f, m] to the one-ring of its nearest vertex (uuo_nn_argmin +
+    uuo_ring_closest_points on `model`'s faces).  Backward: the barycentric weights are held fixed (exact where the distance is
+    differentiable), g = grad (x - p) / r: +g to x, -b_k g scattered to the winning face's three corners; r = 0 gives none."""
+
+    @staticmethod
+    def forward(ctx, x, vertices, model):
+        xd, vd = _f32(x, "x"), _f32(vertices, "vertices")
+        _, nn = model.nn_argmin(xd, vd)
+        dist, face, closest, bary = model.ring_closest_points(vd, xd, nn)
+        nn64 = nn.long()
+        corners = torch.where(face[..., None] >= 0, model.faces[face.clamp(min=0).long()], nn64[..., None].expand(-1, -1, 3))
+        ctx.save_for_backward(xd, closest, dist, corners, bary)
+        ctx.v_shape = vd.shape
+        ctx.mark_non_differentiable(nn64, corners, bary)
+        return dist, nn64, corners, bary
+
+    @staticmethod
+    def backward(ctx, grad_dist, _nn, _corners, _bary):
+        x, closest, dist, corners, bary = ctx.saved_tensors
+        safe = torch.where(dist > 0, dist, torch.ones_like(dist))
+        g = torch.where(dist > 0, grad_dist / safe, torch.zeros_like(dist))[..., None] * (x - closest)
+        F_, V_ = ctx.v_shape[0], ctx.v_shape[1]
+        # index_put_ (sort-based, fixed summation order) rather than float atomics: see _Knn1.backward
+        rows = (torch.arange(F_, device=x.device)[:, None, None] * V_ + corners).reshape(-1)
+        gv = torch.zeros((F_ * V_, 3), dtype=x.dtype, device=x.device)
+        gv.index_put_((rows,), (-bary[..., None] * g[:, :, None, :]).reshape(-1, 3), accumulate=True)
+        return g, gv.view(ctx.v_shape), None
+
+
+def surface_chamfer_distance(x: torch.Tensor, vertices: torch.Tensor, x_weights: torch.Tensor, smpl_inference_or_model,
+                             distance: float = 0.0, sigma: float = 0.0):
+    """EXTENSION, not reference behaviour: `weighted_chamfer_distance` with every marker's squared nearest-VERTEX distance
+    replaced by (r - distance)^2, r its distance to the SURFACE on the one-ring of its nearest vertex (the faces incident to
+    it; a vertex without a face stands for itself) and `distance` the marker's stand-off; `sigma` > 0 passes the square through
+    gmof.  Same mask and normalisation.  What the fused chamfer closure computes with uuo_fit_set_surface, composed from the
+    operators.  `smpl_inference_or_model`: a SmplInference or its engine.DeviceModel (the faces come from it)."""
+    model = getattr(smpl_inference_or_model, "device_model", smpl_inference_or_model)
+    if not getattr(model, "has_faces", False):
+        raise RuntimeError("surface_chamfer_distance needs a body model with faces")
+    r = _RingDistance.apply(x, vertices, model)[0]
+    w = x_weights.to(r.dtype) if x_weights.dtype != r.dtype else x_weights
+    wsum = x_weights.sum()
+    if wsum == 0.0:
+        return (x.sum() * 0.0), None
+    return (gmof((r - float(distance)) ** 2, sigma) * w).sum() / wsum, None
+
+
 def MarkerLoss(markers, virtual_markers, marker_weights, marker_distance):
     """[F,M] squared deviation of the marker-to-skin distance from `marker_distance`, masked."""
     gap = torch.norm(markers - virtual_markers, dim=-1) - marker_distance

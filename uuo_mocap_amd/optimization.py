@@ -12,10 +12,12 @@ import torch
 import torch.nn.functional as F
 
 from .device_lbfgs import DeviceLBFGS
+from .config import stage_surface
 from .engine import (MARKER_DISTANCE, ChamferProblem, MarkerProblem, check_foot_contacts, stage_foot_lock, stage_joint_accel,
                      stage_latent_offsets, stage_robust_sigma)
 from .losses import (MarkerLoss, RobustMarkerLoss, chamfer_distance, foot_lock_loss, joint_accel_loss,  # noqa: F401  (re-exported)
-                     robust_weighted_chamfer_distance, soft_weighted_chamfer_distance, weighted_chamfer_distance)
+                     robust_weighted_chamfer_distance, soft_weighted_chamfer_distance, surface_chamfer_distance,
+                     weighted_chamfer_distance)
 from .smpl import SmplInference
 from .transforms import compute_root_orient_y, compute_root_orient_z, normalize_rot  # noqa: F401
 
@@ -72,6 +74,18 @@ def optim_chamfer(
     if "soft_chamfer" in fused_losses and (stage_joint_accel(config, "chamfer") > 0.0 or stage_foot_lock(config, "chamfer") > 0.0):
         # EXTENSION: the temporal terms have no instantiation of the dense backward (k_bwd_dense): composed closure
         fused_losses = _CHAMFER_FUSED_LOSSES
+    w_surface, _ = stage_surface(config)  # EXTENSION: point-to-surface data term (validates the keys)
+    if w_surface > 0.0:
+        from .parallel import frame_shard
+
+        fs = frame_shard()
+        if fs is not None and fs.active:
+            raise NotImplementedError("stages.chamfer.losses.surface_chamfer (point-to-surface term, extension) is not built for "
+                                      "frame-block sharding (parallel.shard_frames)")
+    if w_surface == 0.0 or (markers.is_cuda and bool((config.get("execution") or {}).get("surface_fused", True))):
+        # the term has a fused closure (k_ring_pick + k_surf_fwd + k_bwd_items_f); execution.surface_fused: False keeps the
+        # operator-composed closure, its checker.  (Weight 0 is the key absent.)
+        fused_losses = fused_losses | {"surface_chamfer"}
     if (set(st["losses"]) - fused_losses) or not st["yaw_lock"] or not _robust_fused(config, "chamfer") or \
             not _temporal_fused(config, "chamfer"):
         return _optim_chamfer_general(markers, pose_body, o_pose_body, betas, o_betas, root_orient, trans, marker_labels,
@@ -222,8 +236,10 @@ def lockstep_supported(config: Dict, stage: str) -> bool:
         return False
     if stage == "marker" and stage_latent_offsets(config) > 0.0:  # EXTENSION: nor the latent marker offsets
         return False
+    if stage == "chamfer" and stage_surface(config)[0] > 0.0:  # EXTENSION: nor the point-to-surface chamfer term
+        return False
     if stage == "chamfer":
-        return not (set(st["losses"]) - _CHAMFER_FUSED_LOSSES) and bool(st["yaw_lock"])
+        return not (set(st["losses"]) - _CHAMFER_FUSED_LOSSES - {"surface_chamfer"}) and bool(st["yaw_lock"])
     return not (set(st["losses"]) - {"marker", "reg_pose_body", "reg_betas", "joint_accel", "latent_offsets", "foot_lock"}) and \
         not st.get("use_sdf")
 
@@ -236,6 +252,9 @@ def optim_chamfer_lockstep(markers, hyps, o_pose_body, o_betas, smpl_inference, 
     solver statistics per hypothesis."""
     from .engine import solve_batch
 
+    if stage_surface(config)[0] > 0.0:
+        raise NotImplementedError("stages.chamfer.losses.surface_chamfer (point-to-surface term, extension) is not built for "
+                                  "lock-step batches: solve the hypotheses one by one (optim_chamfer)")
     probs, xs = [], []
     for h in hyps:
         prob = ChamferProblem(smpl_inference, markers, o_pose_body, o_betas, h["root_orient"], config)
@@ -335,9 +354,10 @@ def _optim_chamfer_general(markers, pose_body, o_pose_body, betas, o_betas, root
     refused.  Same in-place semantics as the fused path."""
     st = config["stages"]["chamfer"]
     w = st["losses"]
-    unknown = set(w) - _CHAMFER_FUSED_LOSSES - {"part_chamfer", "trans_vel", "ground", "soft_chamfer"}
+    unknown = set(w) - _CHAMFER_FUSED_LOSSES - {"part_chamfer", "trans_vel", "ground", "soft_chamfer", "surface_chamfer"}
     if unknown:
         raise NotImplementedError("chamfer-stage losses that cannot run in the reference: %s" % sorted(unknown))
+    w_surface, d_surface = stage_surface(config)  # EXTENSION: point-to-surface data term and its stand-off
     sigma = stage_robust_sigma(config, "chamfer")  # EXTENSION: Geman-McClure data term (0 = the reference's square)
     w_accel = stage_joint_accel(config, "chamfer")  # EXTENSION: joint-acceleration term
     w_lock = stage_foot_lock(config, "chamfer")  # EXTENSION: foot-lock term, on the video's contact labels
@@ -372,7 +392,9 @@ def _optim_chamfer_general(markers, pose_body, o_pose_body, betas, o_betas, root
         if "part_chamfer" in w:
             loss = loss + chamfer_distance_by_part(markers, out["vertices"], marker_labels, lbs_weights,
                                                    single_directional=st["single_directional"]) * w["part_chamfer"]
-        if "full_chamfer" in w and sigma > 0.0:  # EXTENSION: the fused closures' robust term, composed (their checker)
+        if w_surface > 0.0:  # EXTENSION: the fused closure's point-to-surface term, composed (its checker); replaces full_chamfer
+            loss = loss + surface_chamfer_distance(markers, out["vertices"], mask, smpl_inference, d_surface, sigma)[0] * w_surface
+        elif "full_chamfer" in w and sigma > 0.0:  # EXTENSION: the fused closures' robust term, composed (their checker)
             loss = loss + robust_weighted_chamfer_distance(markers, out["vertices"], mask, sigma)[0] * w["full_chamfer"]
         elif "full_chamfer" in w:
             loss = loss + weighted_chamfer_distance(x=markers, y=out["vertices"], x_weights=mask,

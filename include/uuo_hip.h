@@ -98,6 +98,17 @@ int uuo_nn_argmin(void* stream, int N, int P1, int P2, const float* d_x, const f
 int uuo_assign_mean_argmin(void* stream, int F, int M, int V, const float* d_verts, const float* d_markers,
                            const uint8_t* d_valid, int32_t* d_idx, void* d_workspace_u64);
 
+/* EXTENSION (not reference behaviour; the reference assumes that a marker column holds one physical marker for the whole
+ * capture): the placement per TRACKLET.  d_seg [F,M] int32 names the tracklet of every entry, -1 = none; ids are 0..S-1, each
+ * id lives in one column and its frames form one run that only -1 entries may interrupt.
+ *   idx[s] = argmin_v (1/n_s) sum_{f : seg[f,col(s)] == s, valid[f]} ||verts[f,v] - markers[f,col(s)]||
+ * with uuo_assign_mean_argmin's arithmetic: fp32, norm sqrt((dx dx + dy dy) + dz dz), the sum sequential in f, one correctly
+ * rounded divide by the count n_s of the frames actually summed, lowest vertex id on ties.  A tracklet with no summed frame
+ * gets -1; entries with ids outside 0..S-1 are ignored.  d_valid [F] uint8, d_idx [S] int32, d_workspace_u64 [S].
+ * Asynchronous: no host read-back (the counts are formed in the kernel). */
+int uuo_assign_segments_argmin(void* stream, int F, int M, int V, int S, const float* d_verts, const float* d_markers,
+                               const int32_t* d_seg, const uint8_t* d_valid, int32_t* d_idx, void* d_workspace_u64);
+
 /* ---- rigidity matrix of the marker segmentation ---------------------------------------------------
  * Replaces the double loop of segment_rigid (src/video_mocap/markers/markers_utils.py:254-259):
  *   d_std[i*M+j] = np.std(np.linalg.norm(points[:, i] - points[:, j], axis=-1))     d_points [F,M,3] float32
@@ -246,6 +257,18 @@ int uuo_fit_set_surface(uuo_fit_t* fit, int32_t on, float surface_distance);
  * [F,M,3] int32 vertex ids, d_bary [F,M,3] their weights (either may be NULL); hidden markers carry (v^, v^, v^).  Device to
  * device on `stream`, ordered behind that evaluation.  Fails if no such evaluation has run on the workspace. */
 int uuo_fit_surface_corners(uuo_fit_t* fit, void* stream, int32_t* d_corners, float* d_bary);
+/* EXTENSION (not reference behaviour; see uuo_assign_segments_argmin): the marker stage's one-hot closure on a PER-FRAME vertex
+ * table.  With d_assign_fm set, item (f, m) of the marker closure takes its vertex from d_assign_fm[f M + m] instead of
+ * uuo_problem_t.d_assign[m]; an entry < 0 is an item of weight 0.  Everything else is unchanged: the data term's definition, its
+ * 1 / (F M) normaliser, marker_distance, the priors, the solver's fused statistics; works with robust_sigma and the
+ * joint-acceleration and foot-lock terms (separate kernel instantiations, the plain ones are unchanged).
+ * A setting of the WORKSPACE (null at creation) with the lifetime rules of uuo_fit_set_joint_accel -- uuo_problem_t stays as it
+ * is (d_assign must still be a valid [M] table; it is not read).  `d_assign_fm` is a device pointer to [F][M] int32 that the
+ * caller keeps alive and may rewrite; it is read at every evaluation, not copied.  NULL = off: every result is that of a
+ * workspace that never had the table.  Refused (at evaluation) for the chamfer and part stages, with n_corners == 3, with
+ * w_offsets != 0 (an offset per column has no meaning once the column changes identity) and with w_soft != 0, by
+ * uuo_lbfgs_solve_shared, and inside lock-step batches (uuo_batch_*). */
+int uuo_fit_set_frame_assign(uuo_fit_t* fit, const int32_t* d_assign_fm);
 /* number of parameters of a stage at (F): 211F+10 / 219F+10 / 3F+11; the marker stage with w_offsets != 0: 219F+10+3M */
 int uuo_problem_num_params(const uuo_problem_t* p);
 

@@ -119,6 +119,10 @@ _SIGNATURES = {
                                         c_void_p, c_void_p, c_void_p]),
     "uuo_fit_create": (c_int, [c_void_p, c_int, c_int, POINTER(c_void_p)]),
     "uuo_fit_destroy": (c_int, [c_void_p]),
+    # EXTENSION: placement per tracklet, and the marker closure's per-frame vertex table of the workspace
+    "uuo_assign_segments_argmin": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p]),
+    "uuo_fit_set_frame_assign": (c_int, [c_void_p, c_void_p]),
     "uuo_fit_set_joint_accel": (c_int, [c_void_p, c_float]),  # EXTENSION: joint-acceleration term of the workspace
     "uuo_fit_set_foot_lock": (c_int, [c_void_p, c_float, c_void_p]),  # EXTENSION: foot-lock term of the workspace, its contacts
     "uuo_problem_num_params": (c_int, [POINTER(UuoProblem)]),

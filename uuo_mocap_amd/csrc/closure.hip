@@ -433,10 +433,14 @@ __device__ __forceinline__ float gmof_q(float sig2, float s) { return sig2 / (si
 // d0 = 0 (the offset carries the stand-off), so the marker branch is the plain square.  Separate instantiations.
 // FASSIGN (EXTENSION, item mode only; uuo_fit_set_surface): the items' vertex ids change with the frame, assign is [F][M]
 // (k_ring_pick chose them in this evaluation).  Separate instantiations: k_bwd_items_f / k_bwd_items_t_f.
+// FASSIGN without ITEMS (EXTENSION, marker stage's one-hot closure only; uuo_fit_set_frame_assign): the column's vertex changes
+// with the frame -- item (f, m) reads assign[f][m], an id < 0 is an item of weight 0 (on vertex 0, like every masked item).
+// Nothing else of the item differs.  Separate instantiations: k_bwd_sparse_f / _r_f / _t_f / _r_t_f.
 template <bool PART = false, int NWV = BWD_NW, bool DENSE = false, bool ITEMS = false, bool ROBUST = false, bool ACCEL = false,
           bool OFFS = false, bool FASSIGN = false>
 __device__ __forceinline__ void bwd_body(const BwdArgs& a) {
-  static_assert(!FASSIGN || (ITEMS && !OFFS), "per-frame vertex ids belong to item mode (the surface chamfer closure)");
+  static_assert(!FASSIGN || (!OFFS && !PART && !DENSE && NWV == BWD_NW), "per-frame vertex ids belong to item mode (the surface "
+                "chamfer closure) and to the marker stage's one-hot closure, without latent offsets");
   static_assert(!OFFS || (!PART && !DENSE && NWV == BWD_NW), "the latent marker offsets are built for the marker stage's "
                 "sparse kernels only");
   static_assert(!ROBUST || (!DENSE && !ITEMS), "the robust data term is formed on the sparse items (k_bary_fwd for item mode)");
@@ -613,7 +617,15 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a) {
         }
       } else if (a.stage == UUO_STAGE_MARKER) {
         wgt *= a.mask[(size_t)f * M + mm];
-        vi = a.assign[mm];
+        if constexpr (FASSIGN) {
+          vi = a.assign[(size_t)f * M + mm];
+          if (vi < 0) {
+            wgt = 0.f;
+            vi = 0;
+          }
+        } else {
+          vi = a.assign[mm];
+        }
       } else {
         const unsigned long long key = a.nn[(size_t)f * M + mm];
         d2 = __uint_as_float((unsigned)(key >> 32));
@@ -1148,6 +1160,19 @@ __global__ __launch_bounds__(BWD_NW * 64) __attribute__((amdgpu_waves_per_eu(3, 
 __global__ __launch_bounds__(BWD_NW * 64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_bwd_sparse_r_t(BwdArgs a) {
   bwd_body<false, BWD_NW, false, false, true, true>(a);
 }
+// EXTENSION: the marker stage's one-hot closure on a per-frame vertex table (uuo_fit_set_frame_assign; no lock-step batch forms)
+__global__ __launch_bounds__(BWD_NW * 64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_bwd_sparse_f(BwdArgs a) {
+  bwd_body<false, BWD_NW, false, false, false, false, false, true>(a);
+}
+__global__ __launch_bounds__(BWD_NW * 64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_bwd_sparse_r_f(BwdArgs a) {
+  bwd_body<false, BWD_NW, false, false, true, false, false, true>(a);
+}
+__global__ __launch_bounds__(BWD_NW * 64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_bwd_sparse_t_f(BwdArgs a) {
+  bwd_body<false, BWD_NW, false, false, false, true, false, true>(a);
+}
+__global__ __launch_bounds__(BWD_NW * 64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_bwd_sparse_r_t_f(BwdArgs a) {
+  bwd_body<false, BWD_NW, false, false, true, true, false, true>(a);
+}
 // the kinematic tail alone, on the sums of a dense backward (dense_bwd.hip)
 __global__ __launch_bounds__(BWD_NW * 64) void k_bwd_dense(BwdArgs a) { bwd_body<false, BWD_NW, true>(a); }
 // the sparse kernel on (vertex, upstream gradient) items (the marker stage on a three-corner placement, k_bary_fwd before it)
@@ -1673,6 +1698,20 @@ static int validate_problem(const uuo_fit* fit, const uuo_problem_t* p) {
               "closure: lock-step batches do not carry the point-to-surface term (uuo_fit_set_surface, extension)");
   UUO_REQUIRE(fit->surface == 0 || (fit->model->ring_off && fit->model->faces),
               "closure: the point-to-surface term (uuo_fit_set_surface, extension) needs the model's faces (uuo_model_set_faces)");
+  // EXTENSION: the per-frame vertex table of the workspace (uuo_fit_set_frame_assign)
+  UUO_REQUIRE(!fit->frame_assign || p->stage == UUO_STAGE_MARKER,
+              "closure: the per-frame vertex table (uuo_fit_set_frame_assign, extension) is built for the marker stage only");
+  UUO_REQUIRE(!fit->frame_assign || p->n_corners != 3,
+              "closure: the per-frame vertex table (uuo_fit_set_frame_assign, extension) is not built for a three-corner placement "
+              "(n_corners = 3)");
+  UUO_REQUIRE(!fit->frame_assign || p->w_offsets == 0.f,
+              "closure: the per-frame vertex table (uuo_fit_set_frame_assign, extension) is not built for the latent marker offsets "
+              "(w_offsets): an offset per column has no meaning once the column changes identity");
+  UUO_REQUIRE(!fit->frame_assign || p->w_soft == 0.f,
+              "closure: the per-frame vertex table (uuo_fit_set_frame_assign, extension) is not built for the soft-assignment data "
+              "term (w_soft)");
+  UUO_REQUIRE(!fit->frame_assign || !uuo_recorder,
+              "closure: lock-step batches do not carry the per-frame vertex table (uuo_fit_set_frame_assign, extension)");
   return 0;
 }
 
@@ -1714,6 +1753,13 @@ extern "C" int uuo_fit_set_foot_lock(uuo_fit_t* fit, float w, const float* d_con
   UUO_REQUIRE(w == 0.f || !uuo_recorder, "uuo_fit_set_foot_lock: lock-step batches do not carry the foot-lock term");
   fit->foot_lock = w;
   fit->foot_contacts = (w == 0.f) ? nullptr : d_contacts;
+  return 0;
+}
+
+extern "C" int uuo_fit_set_frame_assign(uuo_fit_t* fit, const int32_t* d_assign_fm) {
+  UUO_REQUIRE(fit, "uuo_fit_set_frame_assign: null fit");
+  UUO_REQUIRE(!d_assign_fm || !uuo_recorder, "uuo_fit_set_frame_assign: lock-step batches do not carry the per-frame vertex table");
+  fit->frame_assign = d_assign_fm;
   return 0;
 }
 
@@ -2087,7 +2133,12 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
   a.markers = p->d_markers;
   a.mask = fit->mask;
   a.nn = fit->nn;
-  a.assign = p->d_assign;
+  // EXTENSION: with the workspace's per-frame vertex table the marker stage's one-hot closure runs on the *_f instantiations
+  const bool fassign = fit->frame_assign != nullptr;
+  UUO_REQUIRE(!fassign || (p->stage == UUO_STAGE_MARKER && p->n_corners != 3 && !has_offsets(p) && !uuo_recorder),
+              "closure: the per-frame vertex table (uuo_fit_set_frame_assign, extension) belongs to the marker stage's one-hot "
+              "closure outside lock-step batches");
+  a.assign = fassign ? fit->frame_assign : p->d_assign;
   a.subset = p->d_subset;
   a.raw_pose = (p->stage == UUO_STAGE_PART) ? nullptr : d_x + lay.off_pose;
   a.o_pose = p->d_o_pose;
@@ -2303,10 +2354,14 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
         if (rc) return rc;
         a.frames = fit->frames;
       }
-      if (robust)
+      if (fassign)
+        hipLaunchKernelGGL(robust ? k_bwd_sparse_r_t_f : k_bwd_sparse_t_f, dim3(F), dim3(BWD_NW * 64), 0, s, a);
+      else if (robust)
         hipLaunchKernelGGL(k_bwd_sparse_r_t, dim3(F), dim3(BWD_NW * 64), 0, s, a);
       else
         hipLaunchKernelGGL(k_bwd_sparse_t, dim3(F), dim3(BWD_NW * 64), 0, s, a);
+    } else if (fassign) {
+      hipLaunchKernelGGL(robust ? k_bwd_sparse_r_f : k_bwd_sparse_f, dim3(F), dim3(BWD_NW * 64), 0, s, a);
     } else if (robust) {
       if (!uuo_record(UUO_OP_BWD_R, F, 1, a)) hipLaunchKernelGGL(k_bwd_sparse_r, dim3(F), dim3(BWD_NW * 64), 0, s, a);
     } else if (!uuo_record(UUO_OP_BWD, F, 1, a)) {

@@ -799,6 +799,8 @@ static int shared_prepare(uuo_fit_t* fit, hipStream_t s, const uuo_problem_t* p,
               "extension)");
   UUO_REQUIRE(fit->surface == 0, "uuo_lbfgs_solve_shared: shared-betas solves do not carry the point-to-surface chamfer term "
               "(uuo_fit_set_surface, extension)");
+  UUO_REQUIRE(fit->frame_assign == nullptr, "uuo_lbfgs_solve_shared: shared-betas solves do not carry the per-frame vertex table "
+              "(uuo_fit_set_frame_assign, extension)");
   const int hist = opt->history_size > 0 ? opt->history_size : 100;
   const int n_params = uuo_problem_num_params(p);
   LbWs* w = (LbWs*)fit->lbws;

@@ -1095,6 +1095,110 @@ extern "C" int uuo_assign_mean_argmin(void* stream, int F, int M, int V, const f
 }
 
 // ----------------------------------------------------------------------------------------------------
+// EXTENSION (not reference behaviour): marker placement per TRACKLET.  A column of an unlabeled capture may hold several
+// physical markers one after the other; seg[f][m] names the tracklet of every entry (-1: none; each id lives in one column and
+// its frames form one run that only -1 entries interrupt).  idx[s] = argmin_v (1/n_s) sum_{f: seg[f][col(s)] == s, valid[f]}
+// ||v_fv - x_f,col(s)|| with k_assign's arithmetic -- the same norm, the sum sequential in f, one divide by the count n_s of the
+// frames actually summed (counted here: no host read-back), lowest vertex id on ties.  k_assign's loop: thread = vertex,
+// ASSIGN_MG columns in registers, markers and ids of ASSIGN_FC frames staged in LDS, ASSIGN_U vertex loads in flight.  A
+// column's accumulator is flushed when its id changes and at the end: packed key, wave minimum, atomicMin on out[s].  The ids
+// depend on (frame, column) only, so every flush is uniform across the block and the wave shuffles run converged.
+// ----------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void assign_seg_flush(float acc, int n, int sid, int v, int V, unsigned long long* __restrict__ out) {
+  unsigned long long key = ~0ull;
+  if (v < V) key = pack_key(uuo_div_rn(acc, (float)n), (unsigned)v);
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    const unsigned long long o = __shfl_xor(key, off, 64);
+    key = o < key ? o : key;
+  }
+  if ((threadIdx.x & 63) == 0 && key != ~0ull) atomicMin(&out[sid], key);
+}
+
+__global__ __launch_bounds__(256) void k_assign_seg(int F, int M, int V, int S, const float* __restrict__ verts,
+                                                     const float* __restrict__ markers, const int* __restrict__ seg,
+                                                     const unsigned char* __restrict__ valid,
+                                                     unsigned long long* __restrict__ out) {
+  __shared__ float sm[ASSIGN_FC][ASSIGN_MG * 3];
+  __shared__ int ss[ASSIGN_FC][ASSIGN_MG];  // tracklet id of the entry; -1 where it is not summed (none, out of range, invalid frame)
+  __shared__ int sb[ASSIGN_FC][ASSIGN_MG];  // tracklet id of the entry as given (-1: none): an id change ends a run even on an invalid frame
+  const int v = blockIdx.x * 256 + threadIdx.x;
+  const int vc = v < V ? v : V - 1;
+  const int m0 = blockIdx.y * ASSIGN_MG;
+  float acc[ASSIGN_MG];
+  int cnt[ASSIGN_MG], cur[ASSIGN_MG];
+#pragma unroll
+  for (int g = 0; g < ASSIGN_MG; ++g) {
+    acc[g] = 0.f;
+    cnt[g] = 0;
+    cur[g] = -1;
+  }
+  for (int f0 = 0; f0 < F; f0 += ASSIGN_FC) {
+    const int nf = min(ASSIGN_FC, F - f0);
+    __syncthreads();
+    for (int i = threadIdx.x; i < nf * ASSIGN_MG * 3; i += 256) {
+      const int ff = i / (ASSIGN_MG * 3), r = i - ff * (ASSIGN_MG * 3), g = r / 3, c = r - g * 3;
+      sm[ff][r] = (m0 + g < M) ? markers[((size_t)(f0 + ff) * M + m0 + g) * 3 + c] : 0.f;
+    }
+    if (threadIdx.x < nf * ASSIGN_MG) {
+      const int ff = threadIdx.x / ASSIGN_MG, g = threadIdx.x - ff * ASSIGN_MG;
+      int id = (m0 + g < M) ? seg[(size_t)(f0 + ff) * M + m0 + g] : -1;
+      if (id < 0 || id >= S) id = -1;  // (an id past S would index past `out`)
+      sb[ff][g] = id;
+      ss[ff][g] = valid[f0 + ff] ? id : -1;
+    }
+    __syncthreads();
+    for (int q0 = 0; q0 < nf; q0 += ASSIGN_U) {
+      float px[ASSIGN_U], py[ASSIGN_U], pz[ASSIGN_U];
+#pragma unroll
+      for (int u = 0; u < ASSIGN_U; ++u) {
+        const int ff = min(q0 + u, nf - 1);
+        const float* pv = verts + ((size_t)(f0 + ff) * V + vc) * 3;
+        px[u] = pv[0]; py[u] = pv[1]; pz[u] = pv[2];
+      }
+#pragma unroll
+      for (int u = 0; u < ASSIGN_U; ++u) {
+        const int ff = q0 + u;
+        if (ff < nf) {  // uniform across the block, and so is everything that depends on the ids
+#pragma unroll
+          for (int g = 0; g < ASSIGN_MG; ++g) {
+            const int idb = sb[ff][g];
+            if (idb >= 0 && idb != cur[g]) {
+              if (cnt[g] > 0) assign_seg_flush(acc[g], cnt[g], cur[g], v, V, out);
+              acc[g] = 0.f;
+              cnt[g] = 0;
+              cur[g] = idb;
+            }
+            if (ss[ff][g] >= 0) {
+              const float d2 = sqdist(px[u], py[u], pz[u], sm[ff][g * 3], sm[ff][g * 3 + 1], sm[ff][g * 3 + 2]);
+              acc[g] = __fadd_rn(acc[g], uuo_sqrt_rn(d2));
+              cnt[g] += 1;
+            }
+          }
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int g = 0; g < ASSIGN_MG; ++g)
+    if (cnt[g] > 0) assign_seg_flush(acc[g], cnt[g], cur[g], v, V, out);  // uniform across the block
+}
+
+extern "C" int uuo_assign_segments_argmin(void* stream, int F, int M, int V, int S, const float* d_verts, const float* d_markers,
+                                          const int32_t* d_seg, const uint8_t* d_valid, int32_t* d_idx, void* d_ws) {
+  UUO_REQUIRE(F > 0 && M > 0 && V > 0 && S >= 0, "uuo_assign_segments_argmin: F, M, V must be positive and S >= 0");
+  if (S == 0) return 0;
+  UUO_REQUIRE(d_verts && d_markers && d_seg && d_valid && d_idx && d_ws, "uuo_assign_segments_argmin: null argument");
+  hipStream_t s = (hipStream_t)stream;
+  unsigned long long* packed = (unsigned long long*)d_ws;
+  UUO_HIP_CHECK(hipMemsetAsync(packed, 0xFF, (size_t)S * sizeof(unsigned long long), s));
+  hipLaunchKernelGGL(k_assign_seg, dim3((V + 255) / 256, (M + ASSIGN_MG - 1) / ASSIGN_MG), dim3(256), 0, s, F, M, V, S, d_verts,
+                     d_markers, d_seg, d_valid, packed);
+  UUO_HIP_CHECK(hipGetLastError());
+  return uuo_launch_nn_unpack(s, S, packed, nullptr, d_idx);  // (a tracklet without a summed frame keeps ~0: index -1)
+}
+
+// ----------------------------------------------------------------------------------------------------
 // EXTENSION (not reference behaviour; BASELINE's north star names a soft-assignment chamfer): soft-min nearest
 // neighbour.  softmin_i = -tau * log sum_j exp(-d2_ij / tau) = dmin_i - tau * log sum_j exp((dmin_i - d2_ij) / tau),
 // with dmin from the exact K=1 search so that every exponent is <= 0.  Forward: one wave per (cloud, query), lanes

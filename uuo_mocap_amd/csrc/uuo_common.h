@@ -202,6 +202,8 @@ struct uuo_fit {
   const float* foot_contacts = nullptr;  // [F][2] on the device, the caller's (read at evaluation)
   int surface = 0;               // EXTENSION: point-to-surface chamfer term (uuo_fit_set_surface; 0 = off) and its stand-off
   float surface_distance = 0.f;
+  const int32_t* frame_assign = nullptr;  // EXTENSION: [F][M] per-frame vertex table of the marker stage (uuo_fit_set_frame_assign;
+                                          // null = off), the caller's (read at evaluation)
 };
 
 // ---- dense backward of the skinning (dense_bwd.hip) ---------------------------------------------------------------------

@@ -171,6 +171,9 @@ def solve_batch(problems, xs, max_iter: int, lr: float = 1.0, tolerance_grad: fl
     if any(p.foot_lock != 0.0 for p in problems):
         raise NotImplementedError("lock-step batches do not carry the foot-lock term (foot_lock, extension): "
                                   "solve such problems one by one")
+    if any(getattr(p, "frame_assign", None) is not None for p in problems):
+        raise NotImplementedError("lock-step batches do not carry the per-frame vertex table (tracklets, extension): "
+                                  "solve such problems one by one")
     if any(getattr(p, "surface", False) for p in problems):
         raise NotImplementedError("lock-step batches do not carry the point-to-surface chamfer term (surface_chamfer, "
                                   "extension): solve such problems one by one")
@@ -385,6 +388,27 @@ class DeviceModel:
                                                   _ptr(valid_u8), _ptr(idx), _ptr(ws)), "uuo_assign_mean_argmin")
         return idx
 
+    def assign_segments_argmin(self, verts, markers, seg, valid, num_segments: int):
+        """EXTENSION, uuo_assign_segments_argmin: the placement per tracklet.  verts [F,V,3], markers [F,M,3], seg [F,M] int32
+        tracklet ids (-1 = none; each id in one column, its frames one run), valid [F] -> idx [num_segments] int32, -1 for a
+        tracklet without a summed frame.  Asynchronous (no host read-back)."""
+        verts = _f32(verts, "verts")
+        markers = _f32(markers, "markers")
+        F, V, M = verts.shape[0], verts.shape[1], markers.shape[1]
+        S = int(num_segments)
+        seg = seg.to(device=self.device, dtype=torch.int32).contiguous()
+        valid_u8 = valid.to(device=self.device, dtype=torch.uint8).contiguous()
+        if verts.dim() != 3 or markers.dim() != 3 or markers.shape[0] != F or tuple(seg.shape) != (F, M) or \
+                tuple(valid_u8.shape) != (F,) or S < 0:
+            raise ValueError("assign_segments_argmin: verts [F,V,3], markers [F,M,3], seg [F,M], valid [F] expected")
+        idx = torch.empty((S,), dtype=torch.int32, device=self.device)
+        ws = torch.empty((max(S, 1),), dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            check(self.lib.uuo_assign_segments_argmin(current_stream(self.device), F, M, V, S, _ptr(verts), _ptr(markers),
+                                                      _ptr(seg), _ptr(valid_u8), _ptr(idx), _ptr(ws)),
+                  "uuo_assign_segments_argmin")
+        return idx
+
     def ring_closest_points(self, verts, points, nn_idx):
         """EXTENSION, uuo_ring_closest_points: closest point of points[f,m] on the faces incident to vertex nn_idx[f,m] of the
         mesh (verts[f], the model's faces) -> (dist [F,M], face [F,M] int32, closest [F,M,3], barycentric [F,M,3])."""
@@ -480,6 +504,9 @@ class _StageProblem:
         # EXTENSION: the point-to-surface data term (ChamferProblem) and its stand-off, armed the same way (uuo_fit_set_surface)
         self.surface = False
         self.surface_distance = 0.0
+        # EXTENSION: the per-frame vertex table [F, M] int32 of the marker stage's one-hot closure (MarkerProblem), armed the
+        # same way (uuo_fit_set_frame_assign); None = the per-column placement
+        self.frame_assign = None
 
     def _set_foot_lock(self, w: float, contacts):
         """EXTENSION: keeps a contiguous float32 device copy of the checked contact labels and the weight the workspace is
@@ -501,6 +528,8 @@ class _StageProblem:
               "uuo_fit_set_foot_lock")
         check(self.lib.uuo_fit_set_surface(self.fit, 1 if self.surface else 0, c_float(self.surface_distance)),
               "uuo_fit_set_surface")
+        check(self.lib.uuo_fit_set_frame_assign(self.fit, self.frame_assign.data_ptr() if self.frame_assign is not None else None),
+              "uuo_fit_set_frame_assign")
 
     def _need_workspace(self):
         if self.fit is None:  # created for a lock-step batch only: give it the thread's workspace on first standalone use
@@ -568,6 +597,8 @@ class _StageProblem:
         if self.surface:
             raise NotImplementedError("shared-betas solves do not carry the point-to-surface chamfer term (surface_chamfer, "
                                       "extension)")
+        if self.frame_assign is not None:
+            raise NotImplementedError("shared-betas solves do not carry the per-frame vertex table (tracklets, extension)")
         assert x.is_cuda and x.dtype == torch.float32 and x.numel() == self.n and x.is_contiguous()
         self._need_workspace()
         opt = UuoLbfgsOptions(int(max_iter), int(history_size), float(lr), float(tolerance_grad),
@@ -803,9 +834,12 @@ class MarkerProblem(_StageProblem):
 
     stage = UUO_STAGE_MARKER
 
-    def __init__(self, smpl_inference, markers, o_pose_body, o_betas, assign, config, bary=None, foot_contacts=None):
+    def __init__(self, smpl_inference, markers, o_pose_body, o_betas, assign, config, bary=None, foot_contacts=None,
+                 frame_assign=None):
         """`assign` [M] vertex ids (the one-hot placement of the shipped configs), or -- with `bary` [M, 3] -- [M, 3] corner
-        vertex ids of a three-corner (barycentric) placement: virtual marker m = sum_k bary[m, k] v[assign[m, k]]."""
+        vertex ids of a three-corner (barycentric) placement: virtual marker m = sum_k bary[m, k] v[assign[m, k]].
+        EXTENSION: `frame_assign` [F, M] int32, a per-frame vertex table (tracklets: the column's vertex changes with the frame,
+        an entry < 0 is an item of weight 0); `assign` may then be None.  Refused with `bary` and with latent_offsets."""
         st = config["stages"]["marker"]
         unsupported = set(st["losses"]) - {"marker", "reg_pose_body", "reg_betas", "joint_accel", "latent_offsets", "foot_lock"}
         if unsupported:
@@ -818,10 +852,26 @@ class MarkerProblem(_StageProblem):
         w_lock = stage_foot_lock(config, "marker")
         contacts = check_foot_contacts(foot_contacts, None if markers is None else markers.shape[0])
         w_offsets = stage_latent_offsets(config)
+        if frame_assign is not None:
+            if bary is not None:
+                raise NotImplementedError("the per-frame vertex table (tracklets, extension) is not built for a three-corner "
+                                          "placement")
+            if w_offsets > 0.0:
+                raise NotImplementedError("the per-frame vertex table (tracklets, extension) is not built for the latent marker "
+                                          "offsets (stages.marker.losses.latent_offsets): an offset per column has no meaning "
+                                          "once the column changes identity")
+            if tuple(frame_assign.shape) != tuple(markers.shape[:2]):
+                raise ValueError("frame_assign: [F, M] with the markers' F and M expected (got %s)" % (tuple(frame_assign.shape),))
+            if int(frame_assign.max()) >= smpl_inference.device_model.V:
+                raise ValueError("frame_assign: a vertex id is past the model's %d vertices" % smpl_inference.device_model.V)
+            if assign is None:  # (uuo_problem_t.d_assign stays a valid table; the closure does not read it)
+                assign = torch.zeros(int(markers.shape[1]), dtype=torch.int32)
         super().__init__(smpl_inference.device_model, markers, o_pose_body, o_betas, None, wd, wp, wb, assign=assign)
         self.problem.robust_sigma = sigma  # EXTENSION: Geman-McClure data term (0 = off)
         self.joint_accel = w_accel  # EXTENSION: joint-acceleration term (0 = off)
         self._set_foot_lock(w_lock, contacts)  # EXTENSION: foot-lock term (weight 0 without gated contacts)
+        if frame_assign is not None:  # EXTENSION: per-frame vertex table (the *_f kernel instantiations)
+            self.frame_assign = frame_assign.to(device=self.device, dtype=torch.int32).contiguous()
         if w_offsets > 0.0:  # EXTENSION: latent per-marker offsets, 3 M more parameters after trans
             self.problem.w_offsets = w_offsets
             self.n = int(self.lib.uuo_problem_num_params(byref(self.problem)))

@@ -20,8 +20,9 @@ from . import markers_utils, optimization
 from .engine import (set_workspace_group, set_workspace_slot, stage_latent_offsets, worker_pool, worker_streams,
                      workspace_group)
 from .markers_utils import find_best_part_fits, get_aabb, get_aabb_volume, segment_rigid
-from .optimization import (compute_marker_labels_from_coords, compute_nearest_points, get_marker_mask,
-                           optim_chamfer, optim_markers, weighted_chamfer_distance)
+from .optimization import (compute_marker_labels_from_coords, compute_nearest_points, compute_tracklet_placement,
+                           get_marker_mask, optim_chamfer, optim_markers, weighted_chamfer_distance)
+from .tracklets import segment_tracklets, tracklets_config
 from .losses import knn_points_k1
 from .smpl import SmplInference
 from .transforms import compute_root_orient_z, normalize_rot
@@ -169,6 +170,9 @@ def multimodal_video_mocap(
                     node = node.setdefault(kwargs["part"], {})
                 node[iteration] = {k: kwargs[k] for k in recorded if k in kwargs}
 
+    # EXTENSION: stages.compute_locations.tracklets -- the columns change identity: segment once, on the markers that are fitted
+    trk_cfg = tracklets_config(config)
+    tracklets = segment_tracklets(markers, **trk_cfg) if trk_cfg is not None else None
     mark("inputs")
     # ---- marker segmentation
     print("Stage: computing marker segmentation...")
@@ -255,9 +259,32 @@ def multimodal_video_mocap(
     root_orient_angles = torch.arange(0, 2 * np.pi, (2 * np.pi) / config["num_root_orient_angles"]).tolist()
     recompute_labels = bool(config["recompute_marker_labels"]) and run_marker
 
-    def labels_from_placement(coords):
+    def place(pose_p, betas_p, root_p, trans_p, labels, o_pose_p):
+        """The placement of one marker solve as optim_markers' keywords: the reference's one-hot matrix, or -- EXTENSION, with
+        stages.compute_locations.tracklets -- the per-frame vertex table of the tracklets."""
+        if tracklets is not None:
+            table = compute_tracklet_placement(markers, pose_p, betas_p, root_p, trans_p, smpl_inference, img_mask, tracklets)
+            return {"barycentric_coords_one_hot": None, "frame_assign": table}
+        return {"barycentric_coords_one_hot": compute_nearest_points(
+            markers=markers, pose_body=pose_p, betas=betas_p, root_orient=root_p, trans=trans_p,
+            smpl_inference=smpl_inference, marker_labels=labels,
+            granularity=config["stages"]["segment"]["granularity"], img_mask=img_mask, device=device,
+            config=config, o_pose_body=o_pose_p, window_size=1,
+            use_velocity=config["stages"]["compute_locations"]["use_velocity"])}
+
+    def labels_from_placement(coords, labels_before=None):
         """config.recompute_marker_labels (reference :529-539,632-642): the markers' part labels become the dominant
-        joint of the vertex they were placed on, optionally smoothed over the rigid clusters."""
+        joint of the vertex they were placed on, optionally smoothed over the rigid clusters.
+        EXTENSION: from a per-frame vertex table the labels are per entry; entries without a tracklet keep `labels_before`."""
+        if coords.get("frame_assign") is not None:
+            table = coords["frame_assign"].long()
+            joint_of = torch.argmax(smpl_inference.get_lbs_weights(), dim=-1).to(table.device)
+            before = torch.as_tensor(np.asarray(labels_before)).to(table.device).long()
+            labels = torch.where(table >= 0, joint_of[table.clamp(min=0)], before).cpu().numpy()
+            if config["stages"]["segment"]["rigid_filter"]:
+                labels = markers_utils.filter_rigid(markers, labels)
+            return labels
+        coords = coords["barycentric_coords_one_hot"]
         labels = compute_marker_labels_from_coords(smpl_inference, coords, num_frames).detach().cpu().numpy()
         if config["stages"]["segment"]["rigid_filter"]:
             labels = markers_utils.filter_rigid(markers, labels)
@@ -305,6 +332,7 @@ def multimodal_video_mocap(
         pose_f = torch.from_numpy(r["pose_body"]).to(device).requires_grad_(True)
         betas_f = torch.from_numpy(r["betas"][None]).to(device).requires_grad_(True)
         final_np, final_stats = None, []
+        vertex_table = None  # EXTENSION: the per-frame vertex table of the last final marker solve (tracklets)
         # EXTENSION: the latent marker offsets of the last final marker solve (None: the term is off or no such solve ran)
         offsets_f = None
         for stage_i in range(config["stage_repeats"]):
@@ -312,14 +340,10 @@ def multimodal_video_mocap(
             if "progress" in print_options:
                 print("Stage: computing marker placement... [{}/{}]".format(stage_i + 1, config["stage_repeats"]))
             if run_marker:
-                one_hot = compute_nearest_points(
-                    markers=markers, pose_body=pose_f, betas=betas_f, root_orient=root_f, trans=trans_f,
-                    smpl_inference=smpl_inference, marker_labels=labels,
-                    granularity=config["stages"]["segment"]["granularity"], img_mask=img_mask, device=device,
-                    config=config, o_pose_body=pose_stage, window_size=1,
-                    use_velocity=config["stages"]["compute_locations"]["use_velocity"])
+                placement = place(pose_f, betas_f, root_f, trans_f, labels, pose_stage)
+                vertex_table = placement.get("frame_assign")
                 if recompute_labels:
-                    labels = labels_from_placement(one_hot)
+                    labels = labels_from_placement(placement, labels)
                 if "progress" in print_options:
                     print("Stage [marker]: optimizing SMPL parameters... [{}/{}]".format(stage_i + 1,
                                                                                           config["stage_repeats"]))
@@ -328,17 +352,17 @@ def multimodal_video_mocap(
                 offs = (torch.zeros((markers.shape[1], 3), dtype=torch.float32, device=device)
                         if stage_latent_offsets(config) > 0.0 else None)
                 optim_markers(markers=markers, pose_body=pose_f, o_pose_body=pose_stage, betas=betas_f,
-                              o_betas=o_betas, root_orient=root_f, trans=trans_f, barycentric_coords_one_hot=one_hot,
+                              o_betas=o_betas, root_orient=root_f, trans=trans_f,
                               img_mask=img_mask, smpl_inference=smpl_inference, config=config, initial_angle=0,
                               repeat=1, verbose=verbose, iter_fn=save_iter_fn, foot_contacts=o_foot_contacts,
-                              **({} if offs is None else {"marker_offsets": offs}))
+                              **placement, **({} if offs is None else {"marker_offsets": offs}))
                 offsets_f = offs
                 final_stats.append(optimization.last_stats("marker"))
             root_f = normalize_rot(root_f).clone().detach().requires_grad_(True)
             pose_f = normalize_rot(pose_f).clone().detach().requires_grad_(True)
             final_np = _np_dict(trans=trans_f, root_orient=root_f, betas=betas_f[0], pose_body=pose_f)
         return {"trans": trans_f, "root_orient": root_f, "pose_body": pose_f, "betas": betas_f, "np": final_np,
-                "stats": final_stats, "labels": labels, "marker_offsets": offsets_f}
+                "stats": final_stats, "labels": labels, "marker_offsets": offsets_f, "marker_vertices": vertex_table}
 
     def fit_hypothesis(index: int, root_orient_angle: float, stream, marker_labels=marker_labels):
         """One yaw hypothesis (reference multimodal.py:463-574): chamfer L-BFGS -> placement -> marker L-BFGS.
@@ -370,23 +394,18 @@ def multimodal_video_mocap(
             if "progress" in print_options:
                 print("Stage: computing marker placement... [{}/{}]".format(1, config["stage_repeats"]))
             if run_marker:
-                one_hot = compute_nearest_points(
-                    markers=markers, pose_body=pose_angle, betas=betas_angle, root_orient=z_root, trans=trans_angle,
-                    smpl_inference=smpl_inference, marker_labels=marker_labels,
-                    granularity=config["stages"]["segment"]["granularity"], img_mask=img_mask, device=device,
-                    config=config, o_pose_body=o_pose_body, window_size=1,
-                    use_velocity=config["stages"]["compute_locations"]["use_velocity"])
+                placement = place(pose_angle, betas_angle, z_root, trans_angle, marker_labels, o_pose_body)
                 if recompute_labels:
-                    local["marker_labels"] = labels_from_placement(one_hot)
+                    local["marker_labels"] = labels_from_placement(placement, marker_labels)
                 if "progress" in print_options:
                     print("Stage [marker]: optimizing SMPL parameters... [{}/{}]".format(1, config["stage_repeats"]))
                 z_root = z_root.clone().detach().requires_grad_(True)
                 pose_angle = pose_angle.clone().detach().requires_grad_(True)
                 optim_markers(markers=markers, pose_body=pose_angle, o_pose_body=o_pose_body, betas=betas_angle,
                               o_betas=o_betas, root_orient=z_root, trans=trans_angle,
-                              barycentric_coords_one_hot=one_hot, img_mask=img_mask, smpl_inference=smpl_inference,
+                              img_mask=img_mask, smpl_inference=smpl_inference,
                               config=config, initial_angle=root_orient_angle, repeat=0, verbose=verbose,
-                              iter_fn=save_iter_fn, foot_contacts=o_foot_contacts)
+                              iter_fn=save_iter_fn, foot_contacts=o_foot_contacts, **placement)
                 local["marker_stats"] = optimization.last_stats("marker")
             if not run_chamfer and not run_marker:
                 # nothing was optimised: the marker-stage record is the chamfer-stage record (both hold the normalised
@@ -599,6 +618,10 @@ def multimodal_video_mocap(
     mocap_markers.set_points(markers.detach().cpu().numpy())
     output["mocap_markers"] = mocap_markers
     output["markers_labels"] = marker_labels
+    if tracklets is not None:  # EXTENSION: [F, M] int32 vertex of every entry in the last marker solve (-1: none), tracklet ids
+        if fin["marker_vertices"] is not None:
+            output["marker_vertices"] = fin["marker_vertices"].detach().cpu()
+        output["marker_tracklets"] = tracklets.seg.detach().cpu()
     if fin["marker_offsets"] is not None:  # EXTENSION: [M, 3] rest-space offsets (metres) in mocap_markers' column order
         output["marker_offsets"] = fin["marker_offsets"].detach().cpu()
     if save_stages:

@@ -19,6 +19,7 @@ from .losses import (MarkerLoss, RobustMarkerLoss, chamfer_distance, foot_lock_l
                      robust_weighted_chamfer_distance, soft_weighted_chamfer_distance, surface_chamfer_distance,
                      weighted_chamfer_distance)
 from .smpl import SmplInference
+from .tracklets import tracklets_config
 from .transforms import compute_root_orient_y, compute_root_orient_z, normalize_rot  # noqa: F401
 
 #: per-solve statistics of the most recent calls (n_iter, n_eval, losses, device ms) -- bench.py and tests read it
@@ -237,6 +238,8 @@ def lockstep_supported(config: Dict, stage: str) -> bool:
     if stage == "marker" and stage_latent_offsets(config) > 0.0:  # EXTENSION: nor the latent marker offsets
         return False
     if stage == "chamfer" and stage_surface(config)[0] > 0.0:  # EXTENSION: nor the point-to-surface chamfer term
+        return False
+    if stage == "marker" and tracklets_config(config) is not None:  # EXTENSION: nor the per-frame vertex table
         return False
     if stage == "chamfer":
         return not (set(st["losses"]) - _CHAMFER_FUSED_LOSSES - {"surface_chamfer"}) and bool(st["yaw_lock"])
@@ -459,6 +462,7 @@ def optim_markers(
     iter_fn: Callable = None,
     marker_offsets: torch.Tensor = None,
     foot_contacts: torch.Tensor = None,
+    frame_assign: torch.Tensor = None,
 ):
     """Marker (inverse kinematics) stage: L-BFGS over [pose_body, betas, root_orient, trans], lr 1.0, with the
     fixed marker -> vertex placement given as a one-hot [M, V] matrix.  Mutates the four leaves in place.
@@ -466,7 +470,14 @@ def optim_markers(
     (uuo_problem_t.w_offsets), started from MarkerProblem.offsets_start; `marker_offsets` ([M, 3], optional) receives the
     fitted offsets in place.
     EXTENSION: `foot_contacts` ([F, 2] in [0, 1], optional) are the video's contact labels of the left and right foot for
-    stages.marker.losses.foot_lock (without them, or with labels that gate nothing, the key changes nothing)."""
+    stages.marker.losses.foot_lock (without them, or with labels that gate nothing, the key changes nothing).
+    EXTENSION: `frame_assign` ([F, M] int32, optional; compute_tracklet_placement) is a per-frame vertex table for captures whose
+    columns change identity: entry (f, m) is the vertex of marker column m in frame f, an entry < 0 takes no part.  With it
+    `barycentric_coords_one_hot` may be None.  Fused one-hot closure only: refused with latent_offsets, with
+    execution.robust_fused / temporal_fused: False, under frame-block sharding and with shared betas."""
+    if frame_assign is not None:
+        return _optim_markers_frame_assign(markers, pose_body, o_pose_body, betas, o_betas, root_orient, trans, frame_assign,
+                                           smpl_inference, config, initial_angle, repeat, verbose, iter_fn, foot_contacts)
     one_hot = barycentric_coords_one_hot
     if one_hot.dim() != 2 or one_hot.shape[1] != smpl_inference.device_model.V:
         raise ValueError("barycentric_coords_one_hot must be [M, %d]" % smpl_inference.device_model.V)
@@ -520,6 +531,44 @@ def optim_markers(
         trans.copy_(new_trans)
         if marker_offsets is not None and prob.has_offsets:
             marker_offsets.copy_(prob.unpack(x)[4].to(device=marker_offsets.device, dtype=marker_offsets.dtype))
+    LAST_STATS["marker"] = stats
+    _tls_stats.marker = stats
+    return None
+
+
+def _optim_markers_frame_assign(markers, pose_body, o_pose_body, betas, o_betas, root_orient, trans, frame_assign, smpl_inference,
+                                config, initial_angle, repeat, verbose, iter_fn, foot_contacts):
+    """EXTENSION: optim_markers on a per-frame vertex table (uuo_fit_set_frame_assign)."""
+    from .parallel import frame_shard, shared_betas_reducer
+
+    what = "the per-frame vertex table (tracklets, extension)"
+    if not _robust_fused(config, "marker") or not _temporal_fused(config, "marker"):
+        raise NotImplementedError("%s is built for the fused marker closure only, not for the closure composed from the operators "
+                                  "(execution.robust_fused / temporal_fused: False)" % what)
+    _refuse_latent_offsets(config, what + ": an offset per column has no meaning once the column changes identity")
+    fs = frame_shard()
+    if fs is not None and fs.active:
+        raise NotImplementedError("%s is not built for frame-block sharding (parallel.shard_frames)" % what)
+    if shared_betas_reducer() is not None:
+        raise NotImplementedError("%s is not built for shared betas (parallel.shared_betas)" % what)
+    prob = MarkerProblem(smpl_inference, markers, o_pose_body, o_betas, None, config, foot_contacts=foot_contacts,
+                         frame_assign=frame_assign)
+    x = prob.pack(pose_body, betas, root_orient, trans)
+    point_cb = None
+    if iter_fn is not None:
+        def point_cb(i, loss, x_eval):
+            e_pose, e_betas, e_root, e_trans = prob.unpack(x_eval)[:4]
+            iter_fn(stage="marker_" + str(repeat), iteration=i, initial_angle=np.array([initial_angle]),
+                    pose_body=normalize_rot(e_pose).numpy(), betas=e_betas.numpy().copy(), trans=e_trans.numpy().copy(),
+                    root_orient=normalize_rot(e_root).numpy())
+
+    stats = _solve(prob, x, config, "marker", 1.0, "Marker", verbose, point_cb)
+    new_pose, new_betas, new_root, new_trans = prob.unpack(x)[:4]
+    with torch.no_grad():
+        pose_body.copy_(new_pose)
+        betas.copy_(new_betas)
+        root_orient.copy_(new_root)
+        trans.copy_(new_trans)
     LAST_STATS["marker"] = stats
     _tls_stats.marker = stats
     return None
@@ -655,6 +704,29 @@ def compute_nearest_points(
             coords = torch.zeros_like(coords)
             coords.scatter_(1, idx.long()[:, None], 1.0)
     return coords.to(device)
+
+
+def compute_tracklet_placement(markers: torch.Tensor, pose_body: torch.Tensor, betas: torch.Tensor, root_orient: torch.Tensor,
+                               trans: torch.Tensor, smpl_inference: SmplInference, img_mask: torch.Tensor, tracklets):
+    """EXTENSION: the placement of a capture whose columns change identity -> assign_fm [F, M] int32.  The forward of
+    compute_nearest_points (mean betas), then every tracklet of `tracklets` (tracklets.Tracklets of these markers) gets
+    argmin_v of its mean distance over ITS entries in the frames with img_mask == 1 (uuo_assign_segments_argmin: missing
+    entries are not counted, unlike the whole-column mean).  The tracklet's vertex is scattered over its entries; every other
+    entry, and a tracklet without a valid frame, is -1."""
+    if tuple(tracklets.seg.shape) != tuple(markers.shape[:2]):
+        raise ValueError("compute_tracklet_placement: the tracklets belong to markers of another shape")
+    with torch.no_grad():
+        verts = smpl_inference(
+            poses=normalize_rot(pose_body.detach()),
+            betas=torch.repeat_interleave(torch.mean(betas.detach(), dim=0, keepdim=True), dim=0, repeats=betas.shape[0]),
+            root_orient=normalize_rot(root_orient.detach()),
+            trans=trans.detach(),
+        )["vertices"]
+        valid = _valid_frames(img_mask, markers.shape[0])
+        seg = tracklets.seg.to(verts.device)
+        idx = smpl_inference.device_model.assign_segments_argmin(verts, markers, seg, valid, tracklets.count)
+        idx = torch.cat([idx, torch.full((1,), -1, dtype=torch.int32, device=idx.device)])  # seg == -1 reads the last entry
+        return idx[seg.long()].contiguous()
 
 
 def _valid_frames(img_mask: torch.Tensor, num_frames: int) -> torch.Tensor:

@@ -168,7 +168,9 @@ def save_outputs(output_filename: str, result: Dict):
         "mocap_frame_rate": result["mocap_frame_rate"], "mocap_markers": result["mocap_markers"].get_points(),
         "gender": "neutral",
     }
-    np.savez(output_filename, **out)
+    # EXTENSION (stages.compute_locations.tracklets): the final fit's vertex and the tracklet id of every entry, [F, M] int32
+    extra = {k: to_np(result[k]) for k in ("marker_vertices", "marker_tracklets") if k in result}
+    np.savez(output_filename, **out, **extra)
     for stage, st in result.get("stages", {}).items():
         out["trans"] = to_np(st["trans"])
         out["betas"] = to_np(st["betas"])

@@ -114,7 +114,7 @@ def make_sequence(tables: SmplTables, seed: int = 0, num_frames: int = 300, num_
                   limb_only: bool = False, yaw_offset_deg: float = 100.0, dropout: float = 0.02,
                   hmr_pose_noise: float = 0.1, hmr_beta_noise: float = 0.5, subject_seed: int = None,
                   standoff_tilt_deg: float = 0.0, standoff_mm=(9.5, 9.5), planted_feet: bool = False,
-                  stance_frames: int = 20) -> SyntheticSequence:
+                  stance_frames: int = 20, identity_events: int = 0) -> SyntheticSequence:
     """One synthetic sequence: smooth GT motion, unlabeled-but-tracked markers 9.5 mm off the
     surface with 1 mm noise and block dropout, and an HMR stand-in (noisy pose/shape, wrong yaw).  `subject_seed` fixes the
     ground-truth shape independently of `seed`: sequences of ONE subject (the shared-betas extension fits them together).
@@ -127,7 +127,14 @@ def make_sequence(tables: SmplTables, seed: int = 0, num_frames: int = 300, num_
     translation is rebuilt so that the stance foot's joint (10 left, 11 right; foot (t // stance_frames) % 2) does not move:
     trans_t = trans_{t-1} - (j_t[foot] - j_{t-1}[foot]) with j the joints at zero translation.  gt["foot_contacts"] [F, 2] holds
     the true stance labels; img_smpl.foot_contacts the same eroded by two frames at each end of every stance (a detector that
-    is late and early, never wrong)."""
+    is late and early, never wrong).
+    A capture whose columns change identity (EXTENSION tests of the tracklet placement): `identity_events` events, each at a
+    frame t_e in [F/10, 9F/10) and on three columns visible at t_e whose mutual distances there are >= 0.2 m (frame and columns
+    from the event's own hash stream, drawn again until they qualify).  From t_e on the contents of the three columns are
+    rotated cyclically (a takes b's, b takes c's, c takes a's); every second event also blanks the three columns for the five
+    frames before t_e.  gt["marker_vids_fm"] [F, M] holds the true vertex of every entry (-1 where missing), gt["tracklets_fm"]
+    [F, M] the true tracklet ids (a run of consecutive visible frames of one column showing one marker; dense ids ordered by
+    (column, start), -1 where missing).  With 0 events no hash stream is consumed and every other array is unchanged."""
     F, M = num_frames, num_markers
     s = 7919 * (seed + 1)
     t = np.arange(F, dtype=np.float64) / max(F, 1)
@@ -213,6 +220,36 @@ def make_sequence(tables: SmplTables, seed: int = 0, num_frames: int = 300, num_
     drop = hash_uniform(s + 11, nblocks, M) < dropout
     drop_f = np.repeat(drop, 10, axis=0)[:F]
     markers = np.where(drop_f[..., None], 0.0, markers)
+    # identity events (own hash streams; none consumed with 0 events): which physical marker (index into pick[perm]) a column shows
+    identity = np.broadcast_to(np.arange(M)[None, :], (F, M)).copy()
+    identity_events = int(identity_events)
+    if identity_events < 0 or (identity_events > 0 and (M < 3 or F < 10)):
+        raise ValueError("make_sequence: identity_events needs a count >= 0, at least 3 markers and 10 frames")
+    for e in range(identity_events):
+        draws = hash_uniform(s + 1000 + e, 256, 4)
+        for u in draws:
+            fe = int(F // 10 + u[0] * (9 * F // 10 - F // 10))
+            cols = [int(u[1 + i] * M) for i in range(3)]
+            if len(set(cols)) < 3:
+                continue
+            x = markers[fe, cols]
+            if not np.all(np.abs(x).sum(axis=1) != 0.0):
+                continue
+            if min(np.linalg.norm(x[i] - x[j]) for i, j in ((0, 1), (0, 2), (1, 2))) < 0.2:
+                continue
+            break
+        else:
+            raise ValueError("make_sequence: no three columns 0.2 m apart found for identity event %d" % e)
+        src = [cols[1], cols[2], cols[0]]
+        markers[fe:, cols] = markers[fe:, src]
+        identity[fe:, cols] = identity[fe:, src]
+        if e % 2 == 1:
+            markers[max(fe - 5, 0):fe, cols] = 0.0
+    visible = np.abs(markers).sum(axis=-1) != 0.0
+    vids_fm = np.where(visible, pick[perm][identity], -1)
+    from .tracklets import tracklets_from_identity
+
+    tracklets_fm = tracklets_from_identity(torch.from_numpy(np.where(visible, identity, -1))).seg.numpy()
 
     # --- HMR stand-in
     noise_aa = hmr_pose_noise * hash_normal(s + 12, F, NUM_JOINTS, 3)
@@ -242,6 +279,7 @@ def make_sequence(tables: SmplTables, seed: int = 0, num_frames: int = 300, num_
         "verts": verts.astype(np.float32), "joints": joints.astype(np.float32),
         "marker_vids": pick[perm],
         "marker_offsets": offsets[perm].astype(np.float32),
+        "marker_vids_fm": vids_fm.astype(np.int64), "tracklets_fm": tracklets_fm.astype(np.int32),
     }
     if planted_feet:
         gt["foot_contacts"] = contacts_gt.astype(np.float32)

@@ -237,6 +237,26 @@ int uuo_fit_set_joint_accel(uuo_fit_t* fit, float w);
  * may be null only with w == 0.  Refused (at evaluation) for the part stage and with w_soft != 0, and inside lock-step batches
  * (uuo_batch_*).  w >= 0, finite. */
 int uuo_fit_set_foot_lock(uuo_fit_t* fit, float w, const float* d_contacts);
+/* EXTENSION (not reference behaviour; the reference's floor terms -- the chamfer stage's `ground` = mean(relu(-joints_z)) and
+ * the part stage's foot_contact -- act on JOINTS, which sit 5-10 cm above the sole, and run on its operator-composed route): a
+ * floor-contact term on K = k_left + k_right SOLE VERTICES of the chamfer and marker stages.  z is up; the plane lies at
+ * `height`.  d_vids[K] are model vertex ids, the left foot's k_left points first; s(p) is the foot of point p; z[t][p] the world
+ * z of the skinned vertex, translation included; c[F][2] in [0, 1] the contact labels (left, right) of uuo_fit_set_foot_lock:
+ *   pen[t][p] = max(height - z[t][p], 0)                            (always on: nothing goes through the floor)
+ *   flo[t][s] = max(min_{p: s(p) = s} z[t][p] - height, 0)          (the foot's lowest point; the first in list order on ties)
+ *   loss += w_pen sum_t sum_p pen^2 / (F K)  +  w_con sum_t sum_s c[t][s] flo[t][s]^2 / (2 F)
+ *   dL/dz[t][p] = -2 w_pen pen[t][p] / (F K)  +  [p = argmin of its foot] w_con c[t][s] flo[t][s] / F       (x, y: 0)
+ * in m^2.  Both pieces are C^1 at their hinge; the min is piecewise smooth, as the nearest-vertex chamfer is.  Frames are not
+ * coupled: F = 1 is a valid problem.
+ * A setting of the WORKSPACE (off at creation) with the lifetime rules of uuo_fit_set_joint_accel.  `d_vids` and `d_contacts`
+ * are device pointers that the caller keeps alive; they are read at every evaluation, not copied (the ids are read back once,
+ * here, to be checked).  Both weights 0 switches the term off, and the pointers may then be null.  Errors: a negative or
+ * non-finite weight, a non-finite height, K outside 2 .. 16, a foot without points, a vertex id outside [0, V), w_con > 0 with
+ * null contacts.  Works with robust_sigma, the joint-acceleration and foot-lock terms, the latent marker offsets, three-corner
+ * placements and the point-to-surface term.  Refused (at evaluation) for the part stage and with w_soft != 0, and inside
+ * lock-step batches (uuo_batch_*). */
+int uuo_fit_set_floor(uuo_fit_t* fit, float w_pen, float w_con, float height, const int32_t* d_vids, int32_t k_left,
+                      int32_t k_right, const float* d_contacts);
 /* EXTENSION (not reference behaviour; MoSh-style fitters score a marker by its distance to the SKIN less its stand-off, the
  * reference's chamfer term by its distance to the nearest VERTEX): on = 1 replaces the chamfer stage's data term
  * min_v |x - v|^2 by the point-to-surface term on the one-ring of the nearest vertex v^ the closure's search finds anyway:

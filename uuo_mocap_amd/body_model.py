@@ -305,6 +305,32 @@ def synthetic_smpl(seed: int = 0) -> SmplTables:
 # licensed model loader (best effort; mirrors what smplx reads from SMPL_NEUTRAL.pkl)
 # ----------------------------------------------------------------------------------------------
 
+def sole_vertices(tables: SmplTables, per_foot: int = 3) -> np.ndarray:
+    """EXTENSION: the default sole points of the floor-contact term (uuo_fit_set_floor), [2, per_foot] vertex ids (row 0 the
+    left foot).  For foot s: of the vertices whose dominant joint is 10 + s, those within 10 mm of that set's rest-pose minimum
+    along the model's up axis (y); of those, `per_foot` by farthest-point sampling started at the lowest.  Geometric on
+    purpose: the heel and toe picks of smplx (extra_joint_vids[5:11]) are a sensible explicit choice for a real SMPL
+    (unverified here: no licensed model at hand), but on the synthetic tables those ids belong to other joints."""
+    from .synthetic import farthest_point_vertices
+
+    per_foot = int(per_foot)
+    if per_foot < 1:
+        raise ValueError("sole_vertices: per_foot must be at least 1")
+    vt = tables.v_template.astype(np.float64)
+    owner = np.argmax(tables.lbs_weights, axis=1)
+    out = np.zeros((2, per_foot), dtype=np.int64)
+    for s in range(2):
+        cand = np.where(owner == 10 + s)[0]
+        if len(cand) == 0:
+            raise ValueError("sole_vertices: joint %d owns no vertex" % (10 + s))
+        y = vt[cand, 1]
+        band = cand[y <= y.min() + 0.010]
+        if len(band) < per_foot:
+            raise ValueError("sole_vertices: only %d vertices within 10 mm of the sole of joint %d" % (len(band), 10 + s))
+        out[s] = band[farthest_point_vertices(vt[band], per_foot, start=int(np.argmin(vt[band, 1])))]
+    return out
+
+
 class _ChStub:
     """Stands in for chumpy.ch.Ch when unpickling original SMPL files (install.sh:18 needs chumpy)."""
 

@@ -93,6 +93,11 @@ struct BwdArgs {
   uuo_gptr<float> offs_part;   // [F][M][3] out: d loss / d o of every item (T^T g), summed over frames by k_finalize_o
   int offs_k;                  // items per marker: 1 (one-hot) or 3 (item mode on a three-corner placement)
   uuo_gptr<const float> contacts;  // EXTENSION (ACCEL instantiations, lock_w != 0): foot-contact labels [F][2] in [0, 1]
+  // EXTENSION (FLOOR instantiations only): the floor-contact term's sole points (uuo_fit_set_floor), items M .. M + floor_k - 1
+  int floor_k;                        // K sole points (0 = off)
+  uuo_gptr<const int> floor_vids;     // [K] their vertex ids
+  uuo_gptr<const float> floor_up;     // [F][K][3] their upstream gradients, left by k_floor_fwd of this evaluation
+  uuo_gptr<const float> floor_loss;   // [F] the frame's share of the term, already weighted
 };
 
 // EXTENSION: the offsets' share of the finalize (k_finalize_o / k_finalize_to, uuo_problem_t.w_offsets)
@@ -427,6 +432,11 @@ __device__ __forceinline__ float gmof_q(float sig2, float s) { return sig2 / (si
 // dL/dJ[f][foot_s] = 2 lock_w (g[f] v[f] - g[f+1] v[f+1]) (terms outside 1 .. F-1 dropped).  Block f forms g[f] and g[f+1] of
 // both feet beside the window load (parked in s_acc where the feet's dL/dJ and |a|^2 entries land later: no more LDS), takes
 // v from the window's frames f-1 .. f+1, adds dL/dJ to uj and lock_w g[f] |v[f]|^2 to slot 3.  Either coefficient may be 0.
+// FLOOR (EXTENSION, uuo_fit_set_floor; with ACCEL, either of whose coefficients may be 0): the floor-contact term.  k_floor_fwd
+// has skinned the K sole points of every frame, evaluated the term and left d loss / d vertex [F][K][3] and the frame's weighted
+// share of the loss.  The points join the item loop as items M .. M + K - 1 with that upstream gradient given (the fetch and the
+// arithmetic of item mode: weight 1, no residual, no marker offset, no robust weight, no loss of their own); the frame's share
+// joins slot 3.  Separate instantiations (*_fl): sharing the ACCEL ones changed their register allocation.
 // OFFS (EXTENSION, uuo_problem_t.w_offsets > 0): latent per-marker offsets.  Item mm belongs to marker mm / offs_k; its
 // rest-space position is vp + o_m wherever it enters (the skinned position and the dA outer product), and its d loss / d o =
 // T^T g (dvp, which the blend gradients use too) goes to offs_part[f][mm] for k_finalize_o.  The host launches these with
@@ -437,8 +447,10 @@ __device__ __forceinline__ float gmof_q(float sig2, float s) { return sig2 / (si
 // with the frame -- item (f, m) reads assign[f][m], an id < 0 is an item of weight 0 (on vertex 0, like every masked item).
 // Nothing else of the item differs.  Separate instantiations: k_bwd_sparse_f / _r_f / _t_f / _r_t_f.
 template <bool PART = false, int NWV = BWD_NW, bool DENSE = false, bool ITEMS = false, bool ROBUST = false, bool ACCEL = false,
-          bool OFFS = false, bool FASSIGN = false>
+          bool OFFS = false, bool FASSIGN = false, bool FLOOR = false>
 __device__ __forceinline__ void bwd_body(const BwdArgs& a) {
+  static_assert(!FLOOR || (ACCEL && !(FASSIGN && !ITEMS)), "the floor-contact term rides on the temporal instantiations (slot 3 of "
+                "the partials, the frames' FrameLds), outside the per-frame vertex table of the one-hot marker closure");
   static_assert(!FASSIGN || (!OFFS && !PART && !DENSE && NWV == BWD_NW), "per-frame vertex ids belong to item mode (the surface "
                 "chamfer closure) and to the marker stage's one-hot closure, without latent offsets");
   static_assert(!OFFS || (!PART && !DENSE && NWV == BWD_NW), "the latent marker offsets are built for the marker stage's "
@@ -587,6 +599,7 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a) {
       int4 wi;
       float4 ww;
       float o[OFFS ? 3 : 1];  // OFFS: the item's marker offset
+      bool fl;                // FLOOR: a sole point of the floor-contact term (upstream gradient in x0..x2)
     };
     auto fetch16 = [&](int m, Item16& q) {
       // items past M (or masked out) are processed with weight 0 on vertex 0: every contribution is scaled by it
@@ -596,7 +609,15 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a) {
       float d2 = 0.f;
       int vi;
       float up0 = 0.f, up1 = 0.f, up2 = 0.f;
-      if constexpr (ITEMS) {
+      bool fl = false;  // FLOOR: a sole point of the floor-contact term (item M + kf)
+      if constexpr (FLOOR) fl = !in && m < M + a.floor_k;
+      if (FLOOR && fl) {
+        const int kf = m - M;
+        vi = a.floor_vids[kf];
+        const float* pu = a.floor_up + ((size_t)f * a.floor_k + kf) * 3;
+        up0 = pu[0]; up1 = pu[1]; up2 = pu[2];
+        wgt = 1.f;
+      } else if constexpr (ITEMS) {
         if constexpr (FASSIGN)
           vi = a.assign[(size_t)f * M + mm];
         else
@@ -638,7 +659,8 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a) {
       if ((unsigned)vi >= (unsigned)a.V) vi = 0;  // never happens for a completed search; keeps the gather in bounds
       q.wgt = wgt;
       q.d2 = d2;
-      if (ITEMS || a.stage == UUO_STAGE_UPSTREAM) {
+      if constexpr (FLOOR) q.fl = fl;
+      if (ITEMS || a.stage == UUO_STAGE_UPSTREAM || (FLOOR && fl)) {
         q.x0 = up0; q.x1 = up1; q.x2 = up2;
       } else {
         const float* px = a.markers + ((size_t)f * M + mm) * 3;
@@ -668,6 +690,7 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a) {
       if constexpr (OFFS) {
         const float* po = a.offs + (size_t)(mm / a.offs_k) * 3;
         q.o[0] = po[0]; q.o[1] = po[1]; q.o[2] = po[2];
+        if (FLOOR && fl) q.o[0] = q.o[1] = q.o[2] = 0.f;  // a sole point is the vertex itself
       }
     };
     auto row_sum = [](float v) {  // sum over the 16 lanes of the DPP row, left on every lane of the row
@@ -677,7 +700,7 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a) {
       v += dpp_rot<0x121>(v);
       return v;
     };
-    const int rounds = (M + SLOTS - 1) / SLOTS;
+    const int rounds = ((FLOOR ? M + a.floor_k : M) + SLOTS - 1) / SLOTS;
     Item16 cur;
     for (int r = 0; r < rounds; ++r) {
       fetch16(slot + SLOTS * r, cur);
@@ -724,7 +747,7 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a) {
       const float dx = cur.x0 - vx, dy = cur.x1 - vy, dz = cur.x2 - vz;
       float g[3];
       float loss_item;
-      if (ITEMS || a.stage == UUO_STAGE_UPSTREAM) {
+      if (ITEMS || a.stage == UUO_STAGE_UPSTREAM || (FLOOR && cur.fl)) {
         loss_item = 0.f;
         g[0] = wgt * cur.x0; g[1] = wgt * cur.x1; g[2] = wgt * cur.x2;
       } else if (a.stage == UUO_STAGE_MARKER) {
@@ -1107,6 +1130,7 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a) {
         for (int k = 30; k < 36; ++k) sl += s_acc[k];
         share += a.lock_w * sl;
       }
+      if constexpr (FLOOR) share += a.floor_loss[f];  // the floor-contact term's share of this frame (k_floor_fwd)
       BWD_FP_STORE(3, share);
     }
   }
@@ -1203,6 +1227,30 @@ __global__ __launch_bounds__(BWD_NW * 64) __attribute__((amdgpu_waves_per_eu(3, 
 __global__ __launch_bounds__(BWD_NW * 64) void k_bwd_items_o(BwdArgs a) { bwd_body<false, BWD_NW, false, true, false, false, true>(a); }
 __global__ __launch_bounds__(BWD_NW * 64) void k_bwd_items_t_o(BwdArgs a) {
   bwd_body<false, BWD_NW, false, true, false, true, true>(a);
+}
+// EXTENSION: the floor-contact term (uuo_fit_set_floor): the temporal instantiations with the K sole points as further items --
+// one-hot marker / chamfer closure plain and robust, with the latent offsets, and the item kernels (three-corner placement, with
+// offsets, surface chamfer)
+__global__ __launch_bounds__(BWD_NW * 64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_bwd_sparse_t_fl(BwdArgs a) {
+  bwd_body<false, BWD_NW, false, false, false, true, false, false, true>(a);
+}
+__global__ __launch_bounds__(BWD_NW * 64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_bwd_sparse_r_t_fl(BwdArgs a) {
+  bwd_body<false, BWD_NW, false, false, true, true, false, false, true>(a);
+}
+__global__ __launch_bounds__(BWD_NW * 64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_bwd_sparse_t_o_fl(BwdArgs a) {
+  bwd_body<false, BWD_NW, false, false, false, true, true, false, true>(a);
+}
+__global__ __launch_bounds__(BWD_NW * 64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_bwd_sparse_r_t_o_fl(BwdArgs a) {
+  bwd_body<false, BWD_NW, false, false, true, true, true, false, true>(a);
+}
+__global__ __launch_bounds__(BWD_NW * 64) void k_bwd_items_t_fl(BwdArgs a) {
+  bwd_body<false, BWD_NW, false, true, false, true, false, false, true>(a);
+}
+__global__ __launch_bounds__(BWD_NW * 64) void k_bwd_items_t_o_fl(BwdArgs a) {
+  bwd_body<false, BWD_NW, false, true, false, true, true, false, true>(a);
+}
+__global__ __launch_bounds__(BWD_NW * 64) void k_bwd_items_t_f_fl(BwdArgs a) {
+  bwd_body<false, BWD_NW, false, true, false, true, false, true, true>(a);
 }
 
 // ----------------------------------------------------------------------------------------------------
@@ -1363,6 +1411,133 @@ __global__ __launch_bounds__(BWD_NW * 64) void k_bary_fwd_r(BaryFwdArgs a) { bar
 // EXTENSION: with the latent marker offsets (uuo_problem_t.w_offsets)
 __global__ __launch_bounds__(BWD_NW * 64) void k_bary_fwd_o(BaryFwdArgs a) { bary_fwd_body<false, true>(a); }
 __global__ __launch_bounds__(BWD_NW * 64) void k_bary_fwd_ro(BaryFwdArgs a) { bary_fwd_body<true, true>(a); }
+// ----------------------------------------------------------------------------------------------------
+// EXTENSION (not reference behaviour; uuo_fit_set_floor): a floor-contact term on K sole vertices (2 <= K <= 16; the left
+// foot's K_L points first, s(p) the foot of point p), z up, the plane at height h, contact labels c[F][2] in [0, 1]:
+//   pen[t][p] = max(h - z[t][p], 0)                       (always on)
+//   flo[t][s] = max(min_{p of foot s} z[t][p] - h, 0)      (the foot's lowest point; the first in list order on ties)
+//   loss += w_pen sum pen^2 / (F K) + w_con sum c[t][s] flo[t][s]^2 / (2 F)
+//   dL/dz[t][p] = -2 w_pen pen / (F K) + [p = argmin of its foot] w_con c flo / F,   x and y components 0.
+// k_floor_fwd: one wave per frame.  It starts from the frame's FrameLds as k_pose_prep (or the closure's forward) left them,
+// gathers the K vertices four at a time (one per 16-lane group: the arithmetic of the backward kernel's item loop, in its
+// order), evaluates the term on lanes 0 .. K-1 and writes the K upstream gradients and the frame's weighted share of the loss.
+// The backward kernels (ACCEL instantiations of bwd_body) take the points as items M .. M + K - 1.
+// ----------------------------------------------------------------------------------------------------
+#define UUO_FLOOR_MAXK 16
+struct FloorFwdArgs {
+  uuo_gptr<const float> PT, ST, vt, Ww;
+  uuo_gptr<const int> Wi;
+  int V, F, K, KL;               // K points, the first KL of them on the left foot
+  uuo_gptr<const float> frames;  // [F][FrameLds]
+  uuo_gptr<const float> trans;   // [F][3] or null
+  uuo_gptr<const int> vids;      // [K]
+  uuo_gptr<const float> contacts;  // [F][2] or null (ccon == 0)
+  float h, cpen, ccon;           // plane height, w_pen / (F K), w_con / (2 F)
+  uuo_gptr<float> up;            // [F][K][3] out
+  uuo_gptr<float> loss;          // [F] out
+};
+__global__ __launch_bounds__(64) void k_floor_fwd(FloorFwdArgs a) {
+  __shared__ FrameLds L;
+  __shared__ float sA[UUO_NUM_JOINTS * 12];
+  __shared__ float spf[UUO_KB];
+  __shared__ float sz[UUO_FLOOR_MAXK];
+  const int f = blockIdx.x, lane = threadIdx.x;
+  const int K = a.K;
+  {
+    constexpr int NW = sizeof(FrameLds) / 4;
+    float* dst_l = reinterpret_cast<float*>(&L);
+    for (int i = lane; i < NW; i += 64) dst_l[i] = a.frames[(size_t)f * NW + i];
+  }
+  __syncthreads();
+  if (lane < UUO_NUM_JOINTS) frame_skin_matrix(L, lane, sA + lane * 12);
+  for (int i = lane; i < UUO_KB; i += 64) {
+    float v = 0.f;
+    if (i < UUO_NUM_POSE_FEATS) {
+      const int j = 1 + i / 9, e = i % 9;
+      v = L.R[j][e] - ((e == 0 || e == 4 || e == 8) ? 1.f : 0.f);
+    }
+    spf[i] = v;
+  }
+  __syncthreads();
+  const float trz = a.trans ? a.trans[(size_t)f * 3 + 2] : 0.f;
+  const int gq = lane >> 4, sl = lane & 15;
+  float fk[13];
+#pragma unroll
+  for (int t = 0; t < 13; ++t) fk[t] = spf[sl + 16 * t];
+  const float beta_s = (sl < 10) ? L.beta[sl] : 0.f;
+  auto row_sum = [](float v) {
+    v += dpp_rot<0x128>(v);
+    v += dpp_rot<0x124>(v);
+    v += dpp_rot<0x122>(v);
+    v += dpp_rot<0x121>(v);
+    return v;
+  };
+  for (int r = 0; r < (K + 3) / 4; ++r) {
+    const int p = gq + 4 * r;
+    int vi = (p < K) ? a.vids[p] : 0;
+    if ((unsigned)vi >= (unsigned)a.V) vi = 0;  // (uuo_fit_set_floor has checked the ids; keeps the gather in bounds)
+    const float* pt = a.PT + (size_t)vi * 3 * UUO_KB + sl;
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int t = 0; t < 13; ++t) {
+      s0 = fmaf(pt[16 * t], fk[t], s0);
+      s1 = fmaf(pt[UUO_KB + 16 * t], fk[t], s1);
+      s2 = fmaf(pt[2 * UUO_KB + 16 * t], fk[t], s2);
+    }
+    const float* ps = a.ST + (size_t)vi * 30 + (sl < 10 ? sl : 0);
+    const float st0 = (sl < 10) ? ps[0] : 0.f, st1 = (sl < 10) ? ps[10] : 0.f, st2 = (sl < 10) ? ps[20] : 0.f;
+    float vp[3];
+    vp[0] = row_sum(s0) + (a.vt[(size_t)vi * 3] + row_sum(st0 * beta_s));
+    vp[1] = row_sum(s1) + (a.vt[(size_t)vi * 3 + 1] + row_sum(st1 * beta_s));
+    vp[2] = row_sum(s2) + (a.vt[(size_t)vi * 3 + 2] + row_sum(st2 * beta_s));
+    const int4 wi = *reinterpret_cast<const int4*>(a.Wi + (size_t)vi * 4);
+    const float4 w4 = *reinterpret_cast<const float4*>(a.Ww + (size_t)vi * 4);
+    const int wj[4] = {wi.x, wi.y, wi.z, wi.w};
+    const float ww[4] = {w4.x, w4.y, w4.z, w4.w};
+    float T8 = 0.f, T9 = 0.f, T10 = 0.f, T11 = 0.f;  // the z row of the blended transform
+#pragma unroll
+    for (int n = 0; n < 4; ++n) {
+      const float4 r2 = reinterpret_cast<const float4*>(sA + wj[n] * 12)[2];
+      T8 = fmaf(ww[n], r2.x, T8); T9 = fmaf(ww[n], r2.y, T9); T10 = fmaf(ww[n], r2.z, T10); T11 = fmaf(ww[n], r2.w, T11);
+    }
+    const float vz = fmaf(T10, vp[2], fmaf(T9, vp[1], T8 * vp[0])) + T11 + trz;
+    if (p < K && sl == 0) sz[p] = vz;
+  }
+  __syncthreads();
+  const float c0 = (a.ccon != 0.f) ? a.contacts[(size_t)f * 2] : 0.f, c1 = (a.ccon != 0.f) ? a.contacts[(size_t)f * 2 + 1] : 0.f;
+  if (lane < K) {
+    const int p = lane, foot = (p < a.KL) ? 0 : 1;
+    const int lo = foot ? a.KL : 0, hi = foot ? K : a.KL;
+    int am = lo;
+    float zm = sz[lo];
+    for (int q = lo + 1; q < hi; ++q) {
+      const float zq = sz[q];
+      if (zq < zm) {
+        zm = zq;
+        am = q;
+      }
+    }
+    const float pen = fmaxf(a.h - sz[p], 0.f), flo = fmaxf(zm - a.h, 0.f), c = foot ? c1 : c0;
+    float dz = -2.f * a.cpen * pen;
+    if (p == am) dz += 2.f * a.ccon * c * flo;
+    float* pu = a.up + ((size_t)f * K + p) * 3;
+    pu[0] = 0.f;
+    pu[1] = 0.f;
+    pu[2] = dz;
+  }
+  if (lane == 0) {  // the frame's share, in a fixed order
+    float sp = 0.f, zl = sz[0], zr = sz[a.KL];
+    for (int p = 0; p < K; ++p) {
+      const float pen = fmaxf(a.h - sz[p], 0.f);
+      sp += pen * pen;
+      if (p < a.KL) zl = fminf(zl, sz[p]);
+      else zr = fminf(zr, sz[p]);
+    }
+    const float fl0 = fmaxf(zl - a.h, 0.f), fl1 = fmaxf(zr - a.h, 0.f);
+    a.loss[f] = a.cpen * sp + a.ccon * (c0 * (fl0 * fl0) + c1 * (fl1 * fl1));
+  }
+}
+
 // ----------------------------------------------------------------------------------------------------
 // EXTENSION (not reference behaviour; uuo_fit_set_surface): the chamfer stage's data term as a point-to-surface distance
 // with a stand-off.  k_ring_pick (nn_kernels.hip) has chosen, for every (frame, marker), the face of the nearest vertex's
@@ -1681,6 +1856,14 @@ static int validate_problem(const uuo_fit* fit, const uuo_problem_t* p) {
   UUO_REQUIRE(fit->foot_lock == 0.f || p->w_soft == 0.f,
               "closure: the foot-lock term (uuo_fit_set_foot_lock, extension) is not built for the soft-assignment data term "
               "(w_soft)");
+  // EXTENSION: the floor-contact term of the workspace (uuo_fit_set_floor) likewise
+  UUO_REQUIRE(fit->floor_k == 0 || p->stage != UUO_STAGE_PART,
+              "closure: the floor-contact term (uuo_fit_set_floor, extension) is not built for the part stage");
+  UUO_REQUIRE(fit->floor_k == 0 || p->w_soft == 0.f,
+              "closure: the floor-contact term (uuo_fit_set_floor, extension) is not built for the soft-assignment data term "
+              "(w_soft)");
+  UUO_REQUIRE(fit->floor_k == 0 || !uuo_recorder,
+              "closure: lock-step batches do not carry the floor-contact term (uuo_fit_set_floor, extension)");
   // EXTENSION: latent marker offsets
   UUO_REQUIRE(p->w_offsets == 0.f || (p->w_offsets > 0.f && p->w_offsets <= 3.0e38f),
               "closure: w_offsets (latent marker offsets, extension) must be 0 (off) or a positive finite weight");
@@ -1753,6 +1936,42 @@ extern "C" int uuo_fit_set_foot_lock(uuo_fit_t* fit, float w, const float* d_con
   UUO_REQUIRE(w == 0.f || !uuo_recorder, "uuo_fit_set_foot_lock: lock-step batches do not carry the foot-lock term");
   fit->foot_lock = w;
   fit->foot_contacts = (w == 0.f) ? nullptr : d_contacts;
+  return 0;
+}
+
+extern "C" int uuo_fit_set_floor(uuo_fit_t* fit, float w_pen, float w_con, float height, const int32_t* d_vids, int32_t k_left,
+                                 int32_t k_right, const float* d_contacts) {
+  UUO_REQUIRE(fit, "uuo_fit_set_floor: null fit");
+  UUO_REQUIRE((w_pen == 0.f || (w_pen > 0.f && w_pen <= 3.0e38f)) && (w_con == 0.f || (w_con > 0.f && w_con <= 3.0e38f)),
+              "uuo_fit_set_floor: the weights must be 0 (off) or positive finite numbers");
+  if (w_pen == 0.f && w_con == 0.f) {  // off: nothing else is looked at
+    fit->floor_pen = fit->floor_con = fit->floor_height = 0.f;
+    fit->floor_k = fit->floor_kl = 0;
+    fit->floor_vids = nullptr;
+    fit->floor_contacts = nullptr;
+    return 0;
+  }
+  UUO_REQUIRE(height >= -3.0e38f && height <= 3.0e38f, "uuo_fit_set_floor: the plane height must be a finite number of metres");
+  UUO_REQUIRE(k_left >= 1 && k_right >= 1, "uuo_fit_set_floor: every foot needs at least one sole point");
+  UUO_REQUIRE(k_left + (long long)k_right >= 2 && k_left + (long long)k_right <= UUO_FLOOR_MAXK,
+              "uuo_fit_set_floor: 2 .. 16 sole points (k_left + k_right)");
+  UUO_REQUIRE(d_vids, "uuo_fit_set_floor: the sole points' vertex ids [k_left + k_right] on the device are required");
+  UUO_REQUIRE(w_con == 0.f || d_contacts, "uuo_fit_set_floor: a positive contact weight needs the contact labels [F][2] on the device");
+  UUO_REQUIRE(!uuo_recorder, "uuo_fit_set_floor: lock-step batches do not carry the floor-contact term");
+  const int K = k_left + k_right;
+  int32_t h_vids[UUO_FLOOR_MAXK];
+  UUO_HIP_CHECK(hipMemcpy(h_vids, d_vids, (size_t)K * sizeof(int32_t), hipMemcpyDeviceToHost));
+  for (int k = 0; k < K; ++k)
+    UUO_REQUIRE(h_vids[k] >= 0 && h_vids[k] < fit->model->V, "uuo_fit_set_floor: a sole point's vertex id is outside [0, V)");
+  if (!fit->floor_up)  // [F][16][3] upstream gradients + [F] loss shares (k_floor_fwd -> the backward); first use
+    UUO_HIP_CHECK(hipMalloc((void**)&fit->floor_up, ((size_t)fit->F * UUO_FLOOR_MAXK * 3 + fit->F) * sizeof(float)));
+  fit->floor_pen = w_pen;
+  fit->floor_con = w_con;
+  fit->floor_height = height;
+  fit->floor_k = K;
+  fit->floor_kl = k_left;
+  fit->floor_vids = d_vids;
+  fit->floor_contacts = (w_con == 0.f) ? nullptr : d_contacts;
   return 0;
 }
 
@@ -2173,7 +2392,36 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
   UUO_REQUIRE(!lock || !uuo_recorder, "closure: lock-step batches do not carry the foot-lock term");
   a.lock_w = lock ? (float)((double)fit->foot_lock / ((double)(F - 1) * 6.0)) : 0.f;
   a.contacts = lock ? fit->foot_contacts : nullptr;
-  const bool temporal = accel || lock;
+  // EXTENSION: the floor-contact term rides on them too: its K sole points are items M .. M + K - 1 of the backward, with the
+  // upstream gradients k_floor_fwd leaves (launch_floor below, once the frames' FrameLds are there)
+  const bool floor = fit->floor_k != 0;
+  UUO_REQUIRE(!floor || !uuo_recorder, "closure: lock-step batches do not carry the floor-contact term");
+  UUO_REQUIRE(!floor || !fit->frame_assign, "closure: the floor-contact term (uuo_fit_set_floor, extension) is not built for the "
+              "per-frame vertex table (uuo_fit_set_frame_assign)");
+  if (floor) {
+    a.floor_k = fit->floor_k;
+    a.floor_vids = fit->floor_vids;
+    a.floor_up = fit->floor_up;
+    a.floor_loss = fit->floor_up + (size_t)F * UUO_FLOOR_MAXK * 3;
+  }
+  auto launch_floor = [&]() {
+    if (!floor) return;
+    FloorFwdArgs b;
+    std::memset(&b, 0, sizeof(b));
+    b.PT = m->PT; b.ST = m->ST; b.vt = m->vt; b.Ww = m->Ww; b.Wi = m->Wi;
+    b.V = m->V; b.F = F; b.K = fit->floor_k; b.KL = fit->floor_kl;
+    b.frames = fit->frames;
+    b.trans = src.trans;
+    b.vids = fit->floor_vids;
+    b.contacts = fit->floor_contacts;
+    b.h = fit->floor_height;
+    b.cpen = (float)((double)fit->floor_pen / ((double)F * (double)fit->floor_k));
+    b.ccon = (float)((double)fit->floor_con / (2.0 * (double)F));
+    b.up = fit->floor_up;
+    b.loss = fit->floor_up + (size_t)F * UUO_FLOOR_MAXK * 3;
+    hipLaunchKernelGGL(k_floor_fwd, dim3(F), dim3(64), 0, s, b);
+  };
+  const bool temporal = accel || lock || floor;
   a.h.gx = F;
   a.h.gy = 1;
   FinArgs fa;
@@ -2260,11 +2508,14 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
       hipLaunchKernelGGL(k_bary_fwd_r, dim3(F), dim3(BWD_NW * 64), 0, s, b);
     else
       hipLaunchKernelGGL(k_bary_fwd, dim3(F), dim3(BWD_NW * 64), 0, s, b);
+    launch_floor();
     a.M = 3 * M;
     a.up_items = items;
     a.item_loss = item_loss;
     a.frames = fit->frames;
-    if (offs)
+    if (floor)
+      hipLaunchKernelGGL(offs ? k_bwd_items_t_o_fl : k_bwd_items_t_fl, dim3(F), dim3(BWD_NW * 64), 0, s, a);
+    else if (offs)
       hipLaunchKernelGGL(temporal ? k_bwd_items_t_o : k_bwd_items_o, dim3(F), dim3(BWD_NW * 64), 0, s, a);
     else if (temporal)
       hipLaunchKernelGGL(k_bwd_items_t, dim3(F), dim3(BWD_NW * 64), 0, s, a);
@@ -2302,12 +2553,16 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
     b.item_loss = item_loss;
     b.bary = fit->surf_bary;
     hipLaunchKernelGGL(robust ? k_surf_fwd_r : k_surf_fwd, dim3(F), dim3(BWD_NW * 64), 0, s, b);
+    launch_floor();
     a.M = 3 * M;
     a.assign = fit->surf_corners;
     a.up_items = items;
     a.item_loss = item_loss;
     a.frames = fit->frames;
-    hipLaunchKernelGGL(temporal ? k_bwd_items_t_f : k_bwd_items_f, dim3(F), dim3(BWD_NW * 64), 0, s, a);
+    if (floor)
+      hipLaunchKernelGGL(k_bwd_items_t_f_fl, dim3(F), dim3(BWD_NW * 64), 0, s, a);
+    else
+      hipLaunchKernelGGL(temporal ? k_bwd_items_t_f : k_bwd_items_f, dim3(F), dim3(BWD_NW * 64), 0, s, a);
   } else if (soft && p->stage == UUO_STAGE_CHAMFER) {
     // EXTENSION: soft-assignment data term of the chamfer stage.  The forward above has skinned the vertices and run the exact
     // search (dmin, the hard assignment); the soft minimum gives EVERY vertex within reach of a marker a gradient, so the
@@ -2341,7 +2596,11 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
         rc = uuo_launch_pose_prep(m, s, F, src, fit->pfaT, fit->A, nullptr, fit->frames);
         if (rc) return rc;
         a.frames = fit->frames;
-        hipLaunchKernelGGL(robust ? k_bwd_sparse_r_t_o : k_bwd_sparse_t_o, dim3(F), dim3(BWD_NW * 64), 0, s, a);
+        launch_floor();
+        if (floor)
+          hipLaunchKernelGGL(robust ? k_bwd_sparse_r_t_o_fl : k_bwd_sparse_t_o_fl, dim3(F), dim3(BWD_NW * 64), 0, s, a);
+        else
+          hipLaunchKernelGGL(robust ? k_bwd_sparse_r_t_o : k_bwd_sparse_t_o, dim3(F), dim3(BWD_NW * 64), 0, s, a);
       } else {
         hipLaunchKernelGGL(robust ? k_bwd_sparse_r_o : k_bwd_sparse_o, dim3(F), dim3(BWD_NW * 64), 0, s, a);
       }
@@ -2354,7 +2613,10 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
         if (rc) return rc;
         a.frames = fit->frames;
       }
-      if (fassign)
+      launch_floor();
+      if (floor)
+        hipLaunchKernelGGL(robust ? k_bwd_sparse_r_t_fl : k_bwd_sparse_t_fl, dim3(F), dim3(BWD_NW * 64), 0, s, a);
+      else if (fassign)
         hipLaunchKernelGGL(robust ? k_bwd_sparse_r_t_f : k_bwd_sparse_t_f, dim3(F), dim3(BWD_NW * 64), 0, s, a);
       else if (robust)
         hipLaunchKernelGGL(k_bwd_sparse_r_t, dim3(F), dim3(BWD_NW * 64), 0, s, a);

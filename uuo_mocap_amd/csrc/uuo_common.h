@@ -200,6 +200,14 @@ struct uuo_fit {
   float joint_accel = 0.f;  // EXTENSION: weight of the joint-acceleration term (uuo_fit_set_joint_accel; 0 = off)
   float foot_lock = 0.f;    // EXTENSION: weight of the foot-lock term (uuo_fit_set_foot_lock; 0 = off) and its contact labels
   const float* foot_contacts = nullptr;  // [F][2] on the device, the caller's (read at evaluation)
+  // EXTENSION: the floor-contact term (uuo_fit_set_floor; floor_k == 0 = off): weights, plane height, K = floor_k sole points
+  // (the first floor_kl on the left foot), the caller's vertex ids [K] and contact labels [F][2] (read at evaluation), and the
+  // workspace's own [F][16][3] upstream gradients + [F] loss shares (k_floor_fwd -> the backward kernels; first use)
+  float floor_pen = 0.f, floor_con = 0.f, floor_height = 0.f;
+  int floor_k = 0, floor_kl = 0;
+  const int32_t* floor_vids = nullptr;
+  const float* floor_contacts = nullptr;
+  float* floor_up = nullptr;
   int surface = 0;               // EXTENSION: point-to-surface chamfer term (uuo_fit_set_surface; 0 = off) and its stand-off
   float surface_distance = 0.f;
   const int32_t* frame_assign = nullptr;  // EXTENSION: [F][M] per-frame vertex table of the marker stage (uuo_fit_set_frame_assign;

@@ -171,6 +171,9 @@ def solve_batch(problems, xs, max_iter: int, lr: float = 1.0, tolerance_grad: fl
     if any(p.foot_lock != 0.0 for p in problems):
         raise NotImplementedError("lock-step batches do not carry the foot-lock term (foot_lock, extension): "
                                   "solve such problems one by one")
+    if any(getattr(p, "floor_on", False) for p in problems):
+        raise NotImplementedError("lock-step batches do not carry the floor-contact term (floor_penetration / floor_contact, "
+                                  "extension): solve such problems one by one")
     if any(getattr(p, "frame_assign", None) is not None for p in problems):
         raise NotImplementedError("lock-step batches do not carry the per-frame vertex table (tracklets, extension): "
                                   "solve such problems one by one")
@@ -507,6 +510,44 @@ class _StageProblem:
         # EXTENSION: the per-frame vertex table [F, M] int32 of the marker stage's one-hot closure (MarkerProblem), armed the
         # same way (uuo_fit_set_frame_assign); None = the per-column placement
         self.frame_assign = None
+        # EXTENSION: the floor-contact term on sole vertices (ChamferProblem / MarkerProblem), armed the same way
+        # (uuo_fit_set_floor); _set_floor decides once, at construction, which of its two pieces has anything to act on
+        self.floor_pen = 0.0
+        self.floor_con = 0.0
+        self.floor_height = 0.0
+        self.floor_vids = None  # [K] int32 on the device, the left foot's floor_kl points first
+        self.floor_kl = 0
+        self.floor_kr = 0
+        self.floor_contacts = None
+
+    @property
+    def floor_on(self) -> bool:
+        """EXTENSION: True when this problem arms the floor-contact term with a non-zero weight."""
+        return self.floor_pen != 0.0 or self.floor_con != 0.0
+
+    def _set_floor(self, floor: Dict, contacts, smpl_inference):
+        """EXTENSION: `floor` is stage_floor's record.  Keeps the sole points' vertex ids (the configured ones, or
+        body_model.sole_vertices of `smpl_inference.tables`, which is looked at only when the term is on without floor_points) and the contact labels on the device, and the weights the workspace is armed
+        with: floor_penetration as configured (it needs no labels); floor_contact when the labels hold at least one contact,
+        else 0.  With both 0 nothing is armed and the problem runs the plain kernels, bit for bit."""
+        w_pen, w_con = float(floor["w_pen"]), float(floor["w_con"])
+        if contacts is None or not bool(contacts.any()):
+            w_con = 0.0
+        if w_pen == 0.0 and w_con == 0.0:
+            return
+        points = floor["points"]
+        if points is None:
+            from .body_model import sole_vertices
+
+            points = [[int(v) for v in row] for row in sole_vertices(smpl_inference.tables)]
+        vids = [int(v) for v in points[0]] + [int(v) for v in points[1]]
+        if max(vids) >= self.model.V:
+            raise ValueError("floor_points: a vertex id is past the model's %d vertices" % self.model.V)
+        self.floor_vids = torch.tensor(vids, dtype=torch.int32, device=self.device)
+        self.floor_kl, self.floor_kr = len(points[0]), len(points[1])
+        self.floor_pen, self.floor_con, self.floor_height = w_pen, w_con, float(floor["height"])
+        if w_con != 0.0:
+            self.floor_contacts = contacts.to(device=self.device, dtype=torch.float32).contiguous()
 
     def _set_foot_lock(self, w: float, contacts):
         """EXTENSION: keeps a contiguous float32 device copy of the checked contact labels and the weight the workspace is
@@ -530,6 +571,14 @@ class _StageProblem:
               "uuo_fit_set_surface")
         check(self.lib.uuo_fit_set_frame_assign(self.fit, self.frame_assign.data_ptr() if self.frame_assign is not None else None),
               "uuo_fit_set_frame_assign")
+        if self.floor_on:
+            check(self.lib.uuo_fit_set_floor(self.fit, c_float(self.floor_pen), c_float(self.floor_con), c_float(self.floor_height),
+                                             self.floor_vids.data_ptr(), self.floor_kl, self.floor_kr,
+                                             self.floor_contacts.data_ptr() if self.floor_con != 0.0 else None),
+                  "uuo_fit_set_floor")
+        else:
+            check(self.lib.uuo_fit_set_floor(self.fit, c_float(0.0), c_float(0.0), c_float(0.0), None, 0, 0, None),
+                  "uuo_fit_set_floor")
 
     def _need_workspace(self):
         if self.fit is None:  # created for a lock-step batch only: give it the thread's workspace on first standalone use
@@ -748,6 +797,43 @@ def stage_foot_lock(config: Dict, stage: str) -> float:
     return v
 
 
+#: most sole points the floor-contact term takes (uuo_fit_set_floor)
+FLOOR_MAX_POINTS = 16
+
+
+def stage_floor(config: Dict, stage: str) -> Dict:
+    """EXTENSION: the floor-contact term of the chamfer or marker stage (uuo_fit_set_floor) as a config states it --
+    stages.<stage>.losses.floor_penetration and .floor_contact (weights on m^2; absent or 0 = off; negative or non-finite
+    weights are refused), stages.<stage>.floor_height (the plane's z in metres, default 0.0) and stages.<stage>.floor_points
+    (null = body_model.sole_vertices of the model, or [[left vertex ids], [right vertex ids]]: at least one per foot, 2 .. 16 in
+    all; for a real SMPL the heel and toe picks extra_joint_vids[5:11] are a sensible explicit choice).  Returns
+    {"w_pen", "w_con", "height", "points"}.  (The part stage refuses the keys with its other unknown losses.)"""
+    st = config["stages"][stage]
+    losses = st.get("losses") or {}
+    out = {}
+    for key, name in (("w_pen", "floor_penetration"), ("w_con", "floor_contact")):
+        v = losses.get(name, 0.0)
+        v = 0.0 if v is None else float(v)
+        if not math.isfinite(v) or v < 0.0:
+            raise ValueError("stages.%s.losses.%s must be 0 (off) or a positive weight (got %r)" % (stage, name, v))
+        out[key] = v
+    h = st.get("floor_height", 0.0)
+    h = 0.0 if h is None else float(h)
+    if not math.isfinite(h):
+        raise ValueError("stages.%s.floor_height must be a finite number of metres (got %r)" % (stage, h))
+    out["height"] = h
+    pts = st.get("floor_points", None)
+    if pts is not None:
+        ok = isinstance(pts, (list, tuple)) and len(pts) == 2 and all(isinstance(r, (list, tuple)) and len(r) >= 1 for r in pts)
+        ok = ok and all(isinstance(v, int) and not isinstance(v, bool) and v >= 0 for r in pts for v in r)
+        if not ok or not 2 <= len(pts[0]) + len(pts[1]) <= FLOOR_MAX_POINTS:
+            raise ValueError("stages.%s.floor_points must be null or [[left vertex ids], [right vertex ids]] with at least one "
+                             "id >= 0 per foot and 2 .. %d in all (got %r)" % (stage, FLOOR_MAX_POINTS, pts))
+        pts = [list(pts[0]), list(pts[1])]
+    out["points"] = pts
+    return out
+
+
 def check_foot_contacts(foot_contacts, num_frames=None):
     """EXTENSION: the foot-lock term's contact labels as a float32 host tensor [F, 2] (left, right foot; None stays None).
     Shape, finiteness and the range [0, 1] are checked on the host: ValueError before anything touches the device."""
@@ -774,7 +860,7 @@ class ChamferProblem(_StageProblem):
     def __init__(self, smpl_inference, markers, o_pose_body, o_betas, root_orient, config, foot_contacts=None):
         losses = config["stages"]["chamfer"]["losses"]
         unsupported = set(losses) - {"full_chamfer", "reg_pose_body", "reg_betas", "soft_chamfer", "joint_accel", "foot_lock",
-                                     "surface_chamfer"}
+                                     "surface_chamfer", "floor_penetration", "floor_contact"}
         if unsupported:
             raise NotImplementedError("chamfer-stage losses outside the shipped configs: %s" % sorted(unsupported))
         w_surface, d_surface = stage_surface(config)  # EXTENSION: point-to-surface data term (0 = off)
@@ -786,6 +872,11 @@ class ChamferProblem(_StageProblem):
         if w_lock > 0.0 and float(losses.get("soft_chamfer", 0.0)) != 0.0:
             raise NotImplementedError("stages.chamfer: the fused foot-lock term (foot_lock) is not built for the "
                                       "soft-assignment closure; optim_chamfer composes that combination from the operators")
+        floor = stage_floor(config, "chamfer")
+        if (floor["w_pen"] > 0.0 or floor["w_con"] > 0.0) and float(losses.get("soft_chamfer", 0.0)) != 0.0:
+            raise NotImplementedError("stages.chamfer: the fused floor-contact term (floor_penetration / floor_contact) is not "
+                                      "built for the soft-assignment closure; optim_chamfer composes that combination from the "
+                                      "operators")
         contacts = check_foot_contacts(foot_contacts, None if markers is None else markers.shape[0])
         if not config["stages"]["chamfer"]["yaw_lock"]:
             raise NotImplementedError("stages.chamfer.yaw_lock False is not a shipped configuration")
@@ -799,6 +890,7 @@ class ChamferProblem(_StageProblem):
             self.surface, self.surface_distance = True, d_surface
         self.joint_accel = w_accel  # EXTENSION: joint-acceleration term (0 = off)
         self._set_foot_lock(w_lock, contacts)  # EXTENSION: foot-lock term (weight 0 without gated contacts)
+        self._set_floor(floor, contacts, smpl_inference)  # EXTENSION: floor-contact term on sole vertices
         # EXTENSION (not in the reference): soft assignment of every marker to the body's vertices, fused closure with the dense
         # backward on the matrix pipe (csrc/dense_bwd.hip); not available inside lock-step batches
         w_soft = float(losses.get("soft_chamfer", 0.0))
@@ -841,11 +933,16 @@ class MarkerProblem(_StageProblem):
         EXTENSION: `frame_assign` [F, M] int32, a per-frame vertex table (tracklets: the column's vertex changes with the frame,
         an entry < 0 is an item of weight 0); `assign` may then be None.  Refused with `bary` and with latent_offsets."""
         st = config["stages"]["marker"]
-        unsupported = set(st["losses"]) - {"marker", "reg_pose_body", "reg_betas", "joint_accel", "latent_offsets", "foot_lock"}
+        unsupported = set(st["losses"]) - {"marker", "reg_pose_body", "reg_betas", "joint_accel", "latent_offsets", "foot_lock",
+                                           "floor_penetration", "floor_contact"}
         if unsupported:
             raise NotImplementedError("marker-stage losses outside the shipped configs: %s" % sorted(unsupported))
         if st.get("use_sdf"):
             raise NotImplementedError("stages.marker.use_sdf is off in every shipped config")
+        floor = stage_floor(config, "marker")
+        if frame_assign is not None and (floor["w_pen"] > 0.0 or floor["w_con"] > 0.0):
+            raise NotImplementedError("the per-frame vertex table (tracklets, extension) is not built for the floor-contact term "
+                                      "(stages.marker.losses.floor_penetration / floor_contact)")
         wd, wp, wb = _cfg_weights(st["losses"], "marker")
         sigma = stage_robust_sigma(config, "marker")
         w_accel = stage_joint_accel(config, "marker")
@@ -870,6 +967,7 @@ class MarkerProblem(_StageProblem):
         self.problem.robust_sigma = sigma  # EXTENSION: Geman-McClure data term (0 = off)
         self.joint_accel = w_accel  # EXTENSION: joint-acceleration term (0 = off)
         self._set_foot_lock(w_lock, contacts)  # EXTENSION: foot-lock term (weight 0 without gated contacts)
+        self._set_floor(floor, contacts, smpl_inference)  # EXTENSION: floor-contact term on sole vertices
         if frame_assign is not None:  # EXTENSION: per-frame vertex table (the *_f kernel instantiations)
             self.frame_assign = frame_assign.to(device=self.device, dtype=torch.int32).contiguous()
         if w_offsets > 0.0:  # EXTENSION: latent per-marker offsets, 3 M more parameters after trans
@@ -918,13 +1016,16 @@ class MarkerProblem(_StageProblem):
         assert self.has_offsets and x.numel() == self.n
         p = self.problem
         saved = (p.w_pose, p.w_betas, p.robust_sigma, self.joint_accel, self.foot_lock)
+        saved_floor = (self.floor_pen, self.floor_con)
         x0 = x.detach().clone()
         x0[219 * self.F + 10:] = 0.0
         try:
             p.w_pose, p.w_betas, p.robust_sigma, self.joint_accel, self.foot_lock = 0.0, 0.0, 0.0, 0.0, 0.0
+            self.floor_pen, self.floor_con = 0.0, 0.0
             _, grad, _ = self.evaluate(x0, want_nn=False)
         finally:
             p.w_pose, p.w_betas, p.robust_sigma, self.joint_accel, self.foot_lock = saved
+            self.floor_pen, self.floor_con = saved_floor
         g = grad[-3 * self.M:].reshape(self.M, 3).double()
         norm = torch.linalg.norm(g, dim=1, keepdim=True)
         u = torch.where(norm > 0.0, -g / torch.where(norm > 0.0, norm, torch.ones_like(norm)), torch.zeros_like(g))

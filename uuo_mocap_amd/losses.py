@@ -251,3 +251,25 @@ def foot_lock_loss(joints: torch.Tensor, contacts: torch.Tensor) -> torch.Tensor
     v = joints[1:, 10:12] - joints[:-1, 10:12]
     g = contacts[1:] * contacts[:-1]
     return torch.mean(g[..., None] * (v * v))
+
+
+
+def floor_loss(vertices: torch.Tensor, vids, k_left: int, contacts, height: float, w_pen: float, w_con: float) -> torch.Tensor:
+    """EXTENSION (not in the reference): the floor-contact term of the fused chamfer and marker closures (uuo_fit_set_floor),
+    composed -- their checker.  vertices [F, V, 3] (z up), `vids` the K sole points' vertex ids with the left foot's `k_left`
+    first, contacts [F, 2] in [0, 1] (left, right; None = no contact piece), the plane at `height`:
+    w_pen mean(max(h - z, 0)^2) + w_con sum_t sum_s c[t, s] max(min_{p of s} z[t, p] - h, 0)^2 / (2 F).  The foot's lowest point
+    takes the whole gradient of its piece, the first in list order on exact ties."""
+    vids = torch.as_tensor(vids, dtype=torch.long, device=vertices.device)
+    z = vertices[:, vids, 2]
+    k_left = int(k_left)
+    pen = torch.relu(float(height) - z)
+    loss = float(w_pen) * torch.mean(pen * pen)
+    if contacts is not None and float(w_con) != 0.0:
+        contacts = contacts.to(device=z.device, dtype=z.dtype)
+        for s, zs in enumerate((z[:, :k_left], z[:, k_left:])):
+            is_min = zs.detach() == zs.detach().min(dim=1, keepdim=True).values
+            first = is_min & (torch.cumsum(is_min.to(torch.int32), dim=1) == 1)
+            flo = torch.relu(torch.sum(torch.where(first, zs, torch.zeros_like(zs)), dim=1) - float(height))
+            loss = loss + float(w_con) * torch.sum(contacts[:, s] * flo * flo) / (2.0 * z.shape[0])
+    return loss

@@ -5,7 +5,7 @@ and uses the same HIP kernel as the barycentric marker placement (`uuo_mesh_clos
 loops over frames calling igl.signed_distance."""
 from __future__ import annotations
 
-from typing import List
+from typing import Dict, List
 
 import torch
 
@@ -74,6 +74,24 @@ def compute_foot_skate(joints: torch.Tensor, contacts: torch.Tensor, freq: float
         return joints.new_zeros(())
     speed = torch.norm(joints[1:, 10:12] - joints[:-1, 10:12], dim=-1) * float(freq)
     return speed[gate].mean()
+
+
+def compute_floor_error(sole_z: torch.Tensor, k_left: int, contacts: torch.Tensor, height: float = 0.0) -> Dict[str, float]:
+    """Floor errors (not metrics of the reference) of sole heights sole_z [F, K] (world z of the K sole points, the left foot's
+    `k_left` first) against a plane at `height`, with contact labels contacts [F, 2] (left, right), in millimetres for heights
+    in metres: `penetration_mm` the mean of max(h - z, 0) over all (t, p), `max_penetration_mm` its maximum, `float_mm` the mean
+    of max(min_{p of foot s} z - h, 0) over the (t, s) with c = 1 (0.0 when there are none)."""
+    k_left = int(k_left)
+    if sole_z.dim() != 2 or not 0 < k_left < sole_z.shape[1] or tuple(contacts.shape) != (sole_z.shape[0], 2):
+        raise ValueError("compute_floor_error: sole_z [F, K], 0 < k_left < K and contacts [F, 2] expected (got %s, %d and %s)"
+                         % (tuple(sole_z.shape), k_left, tuple(contacts.shape)))
+    z = sole_z.double()
+    pen = torch.relu(float(height) - z)
+    low = torch.stack([z[:, :k_left].min(dim=1).values, z[:, k_left:].min(dim=1).values], dim=1)
+    flo = torch.relu(low - float(height))
+    gate = contacts.to(device=z.device) == 1.0
+    return {"penetration_mm": float(pen.mean()) * 1e3, "max_penetration_mm": float(pen.max()) * 1e3,
+            "float_mm": float(flo[gate].mean()) * 1e3 if bool(gate.any()) else 0.0}
 
 
 def compute_PA_MPJPE(pred_joints: torch.Tensor, gt_joints: torch.Tensor) -> torch.Tensor:

@@ -13,9 +13,9 @@ import torch.nn.functional as F
 
 from .device_lbfgs import DeviceLBFGS
 from .config import stage_surface
-from .engine import (MARKER_DISTANCE, ChamferProblem, MarkerProblem, check_foot_contacts, stage_foot_lock, stage_joint_accel,
-                     stage_latent_offsets, stage_robust_sigma)
-from .losses import (MarkerLoss, RobustMarkerLoss, chamfer_distance, foot_lock_loss, joint_accel_loss,  # noqa: F401  (re-exported)
+from .engine import (MARKER_DISTANCE, ChamferProblem, MarkerProblem, check_foot_contacts, stage_floor, stage_foot_lock,
+                     stage_joint_accel, stage_latent_offsets, stage_robust_sigma)
+from .losses import (MarkerLoss, RobustMarkerLoss, chamfer_distance, floor_loss, foot_lock_loss, joint_accel_loss,  # noqa: F401  (re-exported)
                      robust_weighted_chamfer_distance, soft_weighted_chamfer_distance, surface_chamfer_distance,
                      weighted_chamfer_distance)
 from .smpl import SmplInference
@@ -72,8 +72,10 @@ def optim_chamfer(
         # EXTENSION: the soft-assignment data term has a fused closure (dense backward on the matrix pipe, csrc/dense_bwd.hip);
         # execution.chamfer_soft_fused: False keeps the operator-composed closure, its checker
         fused_losses = _CHAMFER_FUSED_LOSSES | {"soft_chamfer"}
-    if "soft_chamfer" in fused_losses and (stage_joint_accel(config, "chamfer") > 0.0 or stage_foot_lock(config, "chamfer") > 0.0):
-        # EXTENSION: the temporal terms have no instantiation of the dense backward (k_bwd_dense): composed closure
+    if "soft_chamfer" in fused_losses and (stage_joint_accel(config, "chamfer") > 0.0 or stage_foot_lock(config, "chamfer") > 0.0 or
+                                           _floor_on(config, "chamfer")):
+        # EXTENSION: the temporal terms and the floor-contact term have no instantiation of the dense backward (k_bwd_dense):
+        # composed closure
         fused_losses = _CHAMFER_FUSED_LOSSES
     w_surface, _ = stage_surface(config)  # EXTENSION: point-to-surface data term (validates the keys)
     if w_surface > 0.0:
@@ -88,7 +90,7 @@ def optim_chamfer(
         # operator-composed closure, its checker.  (Weight 0 is the key absent.)
         fused_losses = fused_losses | {"surface_chamfer"}
     if (set(st["losses"]) - fused_losses) or not st["yaw_lock"] or not _robust_fused(config, "chamfer") or \
-            not _temporal_fused(config, "chamfer"):
+            not _temporal_fused(config, "chamfer") or not _floor_fused(config, "chamfer"):
         return _optim_chamfer_general(markers, pose_body, o_pose_body, betas, o_betas, root_orient, trans, marker_labels,
                                       smpl_inference, config, initial_angle, repeat, verbose, iter_fn, foot_contacts)
     from .parallel import frame_shard
@@ -208,6 +210,37 @@ def _temporal_fused(config: Dict, stage: str) -> bool:
         bool((config.get("execution") or {}).get("temporal_fused", True))
 
 
+def _floor_on(config: Dict, stage: str) -> bool:
+    """True when the stage's EXTENSION floor-contact term has a non-zero weight (stages.<stage>.losses.floor_penetration /
+    floor_contact; validates the keys)."""
+    fl = stage_floor(config, stage)
+    return fl["w_pen"] > 0.0 or fl["w_con"] > 0.0
+
+
+def _floor_fused(config: Dict, stage: str) -> bool:
+    """False when the stage's EXTENSION floor-contact term is to run on the closure composed from the operators
+    (execution.floor_fused: False, the fused closures' checker); True otherwise."""
+    return not _floor_on(config, stage) or bool((config.get("execution") or {}).get("floor_fused", True))
+
+
+def _composed_floor(config: Dict, stage: str, contacts, smpl_inference):
+    """The floor-contact term of the composed closures: None when off, else a function of the vertices [F, V, 3] -- floor_loss
+    on the configured sole points (body_model.sole_vertices by default), floor_contact only with labels that hold a contact."""
+    fl = stage_floor(config, stage)
+    w_pen, w_con = fl["w_pen"], fl["w_con"]
+    if contacts is None or not bool(contacts.any()):
+        w_con = 0.0
+    if w_pen == 0.0 and w_con == 0.0:
+        return None
+    pts = fl["points"]
+    if pts is None:
+        from .body_model import sole_vertices
+
+        pts = [[int(v) for v in row] for row in sole_vertices(smpl_inference.tables)]
+    vids, k_left = list(pts[0]) + list(pts[1]), len(pts[0])
+    return lambda vertices: floor_loss(vertices, vids, k_left, contacts, fl["height"], w_pen, w_con)
+
+
 def _refuse_latent_offsets(config: Dict, route: str):
     if stage_latent_offsets(config) > 0.0:
         raise NotImplementedError("stages.marker.losses.latent_offsets (latent marker offsets, extension) is built for the fused "
@@ -221,6 +254,9 @@ def _refuse_sharded_joint_accel(config: Dict, stage: str):
     if stage_foot_lock(config, stage) > 0.0:
         raise NotImplementedError("stages.%s.losses.foot_lock (extension) couples neighbouring frames, across the ranks' "
                                   "frame blocks too: it is not built for frame-block sharding (parallel.shard_frames)" % stage)
+    if _floor_on(config, stage):
+        raise NotImplementedError("stages.%s.losses.floor_penetration / floor_contact (extension): the floor-contact term is not "
+                                  "built for frame-block sharding (parallel.shard_frames)" % stage)
 
 
 def lockstep_supported(config: Dict, stage: str) -> bool:
@@ -235,6 +271,8 @@ def lockstep_supported(config: Dict, stage: str) -> bool:
         return False
     if stage_foot_lock(config, stage) > 0.0:  # EXTENSION: nor the foot-lock term
         return False
+    if _floor_on(config, stage) or not _floor_fused(config, stage):  # EXTENSION: nor the floor-contact term
+        return False
     if stage == "marker" and stage_latent_offsets(config) > 0.0:  # EXTENSION: nor the latent marker offsets
         return False
     if stage == "chamfer" and stage_surface(config)[0] > 0.0:  # EXTENSION: nor the point-to-surface chamfer term
@@ -243,8 +281,8 @@ def lockstep_supported(config: Dict, stage: str) -> bool:
         return False
     if stage == "chamfer":
         return not (set(st["losses"]) - _CHAMFER_FUSED_LOSSES - {"surface_chamfer"}) and bool(st["yaw_lock"])
-    return not (set(st["losses"]) - {"marker", "reg_pose_body", "reg_betas", "joint_accel", "latent_offsets", "foot_lock"}) and \
-        not st.get("use_sdf")
+    return not (set(st["losses"]) - {"marker", "reg_pose_body", "reg_betas", "joint_accel", "latent_offsets", "foot_lock",
+                                     "floor_penetration", "floor_contact"}) and not st.get("use_sdf")
 
 
 def optim_chamfer_lockstep(markers, hyps, o_pose_body, o_betas, smpl_inference, config):
@@ -344,7 +382,8 @@ def _solve(prob, x, config, stage: str, lr: float, verbose_tag: str, verbose: bo
 
 
 #: chamfer-stage loss terms the device solver fuses (the only ones the shipped configs enable)
-_CHAMFER_FUSED_LOSSES = {"full_chamfer", "reg_pose_body", "reg_betas", "joint_accel", "foot_lock"}
+_CHAMFER_FUSED_LOSSES = {"full_chamfer", "reg_pose_body", "reg_betas", "joint_accel", "foot_lock", "floor_penetration",
+                         "floor_contact"}
 
 
 def _optim_chamfer_general(markers, pose_body, o_pose_body, betas, o_betas, root_orient, trans, marker_labels,
@@ -368,6 +407,7 @@ def _optim_chamfer_general(markers, pose_body, o_pose_body, betas, o_betas, root
     device = root_orient.device
     if contacts is not None:
         contacts = contacts.to(device)
+    floor_term = _composed_floor(config, "chamfer", contacts, smpl_inference)  # EXTENSION: floor-contact term on sole vertices
     num_frames = pose_body.shape[0]
     root_fixed = root_orient.detach().clone()
     if st["yaw_lock"]:
@@ -418,6 +458,8 @@ def _optim_chamfer_general(markers, pose_body, o_pose_body, betas, o_betas, root
             loss = loss + joint_accel_loss(out["joints"][:, :24]) * w_accel
         if w_lock > 0.0 and contacts is not None:  # EXTENSION: the fused closures' foot-lock term, composed (their checker)
             loss = loss + foot_lock_loss(out["joints"][:, :24], contacts) * w_lock
+        if floor_term is not None:  # EXTENSION: the fused closures' floor-contact term, composed (their checker)
+            loss = loss + floor_term(out["vertices"])
         loss.backward()
         if verbose:
             print("Chamfer", n_eval[0], float(loss))
@@ -487,8 +529,8 @@ def optim_markers(
     fs = frame_shard()
     sharded = fs is not None and fs.active
     bary = None
-    if not _robust_fused(config, "marker") or not _temporal_fused(config, "marker"):
-        # EXTENSION: execution.robust_fused / temporal_fused: False -- the composed closure, the fused one's checker
+    if not _robust_fused(config, "marker") or not _temporal_fused(config, "marker") or not _floor_fused(config, "marker"):
+        # EXTENSION: execution.robust_fused / temporal_fused / floor_fused: False -- the composed closure, the fused one's checker
         return _optim_markers_general(markers, pose_body, o_pose_body, betas, o_betas, root_orient, trans, one_hot,
                                       smpl_inference, config, verbose, iter_fn, initial_angle, repeat, foot_contacts)
     if not bool(((rows_nz == 1) & (one_hot.sum(dim=1) == 1.0)).all()):
@@ -542,6 +584,9 @@ def _optim_markers_frame_assign(markers, pose_body, o_pose_body, betas, o_betas,
     from .parallel import frame_shard, shared_betas_reducer
 
     what = "the per-frame vertex table (tracklets, extension)"
+    if _floor_on(config, "marker"):
+        raise NotImplementedError("%s is not built for the floor-contact term (stages.marker.losses.floor_penetration / "
+                                  "floor_contact)" % what)
     if not _robust_fused(config, "marker") or not _temporal_fused(config, "marker"):
         raise NotImplementedError("%s is built for the fused marker closure only, not for the closure composed from the operators "
                                   "(execution.robust_fused / temporal_fused: False)" % what)
@@ -583,7 +628,8 @@ def _optim_markers_general(markers, pose_body, o_pose_body, betas, o_betas, root
     _refuse_latent_offsets(config, "the closure composed from the operators (more than three non-zeros per placement row, "
                            "execution.robust_fused / temporal_fused / marker_bary_fused: False)")
     st = config["stages"]["marker"]
-    unsupported = set(st["losses"]) - {"marker", "reg_pose_body", "reg_betas", "joint_accel", "latent_offsets", "foot_lock"}
+    unsupported = set(st["losses"]) - {"marker", "reg_pose_body", "reg_betas", "joint_accel", "latent_offsets", "foot_lock",
+                                       "floor_penetration", "floor_contact"}
     if unsupported:
         raise NotImplementedError("marker-stage losses outside the shipped configs: %s" % sorted(unsupported))
     if st.get("use_sdf"):
@@ -594,6 +640,7 @@ def _optim_markers_general(markers, pose_body, o_pose_body, betas, o_betas, root
     contacts = check_foot_contacts(foot_contacts, pose_body.shape[0])
     if contacts is not None:
         contacts = contacts.to(pose_body.device)
+    floor_term = _composed_floor(config, "marker", contacts, smpl_inference)  # EXTENSION: floor-contact term on sole vertices
     num_frames = pose_body.shape[0]
     leaves = [pose_body, betas, root_orient, trans]
     params = [p.detach().clone().requires_grad_(True) for p in leaves]
@@ -626,6 +673,8 @@ def _optim_markers_general(markers, pose_body, o_pose_body, betas, o_betas, root
             loss = loss + joint_accel_loss(out["joints"][:, :24]) * w_accel
         if w_lock > 0.0 and contacts is not None:  # EXTENSION: the fused closures' foot-lock term, composed (their checker)
             loss = loss + foot_lock_loss(out["joints"][:, :24], contacts) * w_lock
+        if floor_term is not None:  # EXTENSION: the fused closures' floor-contact term, composed (their checker)
+            loss = loss + floor_term(out["vertices"])
         loss.backward()
         if verbose:
             print("Marker", n_eval[0], float(loss))

@@ -114,7 +114,7 @@ def make_sequence(tables: SmplTables, seed: int = 0, num_frames: int = 300, num_
                   limb_only: bool = False, yaw_offset_deg: float = 100.0, dropout: float = 0.02,
                   hmr_pose_noise: float = 0.1, hmr_beta_noise: float = 0.5, subject_seed: int = None,
                   standoff_tilt_deg: float = 0.0, standoff_mm=(9.5, 9.5), planted_feet: bool = False,
-                  stance_frames: int = 20, identity_events: int = 0) -> SyntheticSequence:
+                  stance_frames: int = 20, identity_events: int = 0, floor: bool = False) -> SyntheticSequence:
     """One synthetic sequence: smooth GT motion, unlabeled-but-tracked markers 9.5 mm off the
     surface with 1 mm noise and block dropout, and an HMR stand-in (noisy pose/shape, wrong yaw).  `subject_seed` fixes the
     ground-truth shape independently of `seed`: sequences of ONE subject (the shared-betas extension fits them together).
@@ -128,6 +128,12 @@ def make_sequence(tables: SmplTables, seed: int = 0, num_frames: int = 300, num_
     trans_t = trans_{t-1} - (j_t[foot] - j_{t-1}[foot]) with j the joints at zero translation.  gt["foot_contacts"] [F, 2] holds
     the true stance labels; img_smpl.foot_contacts the same eroded by two frames at each end of every stance (a detector that
     is late and early, never wrong).
+    A capture with a floor (EXTENSION tests of the floor-contact term): `floor` (with `planted_feet`; ValueError without) keeps
+    the planted translation in x and y and sets trans_z[t] so that the lowest of the body_model.sole_vertices points, over both
+    feet, lies exactly at z = 0 in every frame (float64).  gt["foot_contacts"][t, s] is then 1 only where foot s is the stance
+    foot AND its lowest sole point is within 5 mm of the floor; img_smpl.foot_contacts is that array eroded by two frames at each
+    end of every run.  gt["sole_vids"] [2, 3] are the points, gt["floor_height"] = 0.0, gt["sole_z"] [F, 6] their float64
+    heights (left foot first).  No hash stream is consumed; without the option every array is what it was.
     A capture whose columns change identity (EXTENSION tests of the tracklet placement): `identity_events` events, each at a
     frame t_e in [F/10, 9F/10) and on three columns visible at t_e whose mutual distances there are >= 0.2 m (frame and columns
     from the event's own hash stream, drawn again until they qualify).  From t_e on the contents of the three columns are
@@ -136,6 +142,8 @@ def make_sequence(tables: SmplTables, seed: int = 0, num_frames: int = 300, num_
     [F, M] the true tracklet ids (a run of consecutive visible frames of one column showing one marker; dense ids ordered by
     (column, start), -1 where missing).  With 0 events no hash stream is consumed and every other array is unchanged."""
     F, M = num_frames, num_markers
+    if floor and not planted_feet:
+        raise ValueError("make_sequence: floor=True needs planted_feet=True (the floor is built under the planted feet)")
     s = 7919 * (seed + 1)
     t = np.arange(F, dtype=np.float64) / max(F, 1)
 
@@ -162,12 +170,12 @@ def make_sequence(tables: SmplTables, seed: int = 0, num_frames: int = 300, num_
     trans = walk + np.array([0.0, 0.0, 0.95])[None]
     beta_gt = np.clip(hash_normal((s if subject_seed is None else 7919 * (int(subject_seed) + 1)) + 7, 10), -2.0, 2.0)[None]
 
-    contacts_gt = contacts_seen = None
+    contacts_gt = contacts_seen = sole = sole_z = None
     if planted_feet:  # (no hash stream: every other array is made from the rebuilt translation exactly as without the option)
         stance_frames = int(stance_frames)
         if stance_frames < 1:
             raise ValueError("make_sequence: stance_frames must be at least 1")
-        _, j0, _ = lbs_f64(tables, rot, beta_gt, np.zeros((F, 3)))
+        v0, j0, _ = lbs_f64(tables, rot, beta_gt, np.zeros((F, 3)))
         stance = (np.arange(F) // stance_frames) % 2
         for i in range(1, F):
             foot = 10 + stance[i]
@@ -178,6 +186,23 @@ def make_sequence(tables: SmplTables, seed: int = 0, num_frames: int = 300, num_
         for a0 in range(0, F, stance_frames):
             b0 = min(a0 + stance_frames, F)
             contacts_seen[a0 + 2:max(b0 - 2, a0 + 2), stance[a0]] = 1.0
+        if floor:  # the lowest sole point of every frame on z = 0; contacts only where the stance foot really is down
+            from .body_model import sole_vertices
+
+            sole = sole_vertices(tables)
+            z0 = v0[:, sole.reshape(-1), 2]
+            trans[:, 2] = -z0.min(axis=1)
+            sole_z = z0 + trans[:, 2:3]
+            k = sole.shape[1]
+            low = np.stack([sole_z[:, :k].min(axis=1), sole_z[:, k:].min(axis=1)], axis=1)
+            contacts_gt = contacts_gt * (low <= 0.005)
+            contacts_seen = np.zeros((F, 2))
+            for sft in range(2):
+                on = np.concatenate([[0.0], contacts_gt[:, sft], [0.0]])
+                starts, ends = np.where(np.diff(on) > 0)[0], np.where(np.diff(on) < 0)[0]
+                for a0, b0 in zip(starts, ends):
+                    contacts_seen[a0 + 2:max(b0 - 2, a0 + 2), sft] = 1.0
+        del v0
 
     verts, joints, T_R = lbs_f64(tables, rot, beta_gt, trans)
 
@@ -283,6 +308,10 @@ def make_sequence(tables: SmplTables, seed: int = 0, num_frames: int = 300, num_
     }
     if planted_feet:
         gt["foot_contacts"] = contacts_gt.astype(np.float32)
+    if floor:
+        gt["sole_vids"] = sole
+        gt["floor_height"] = 0.0
+        gt["sole_z"] = sole_z
     return SyntheticSequence(img_smpl=img, markers=SyntheticMarkers(markers.astype(np.float32), 30.0), gt=gt)
 
 

@@ -257,6 +257,30 @@ int uuo_fit_set_foot_lock(uuo_fit_t* fit, float w, const float* d_contacts);
  * lock-step batches (uuo_batch_*). */
 int uuo_fit_set_floor(uuo_fit_t* fit, float w_pen, float w_con, float height, const int32_t* d_vids, int32_t k_left,
                       int32_t k_right, const float* d_contacts);
+/* EXTENSION (not reference behaviour; SMPLify's interpenetration term is the classic of this kind, the reference has none): a
+ * bone-capsule self-penetration term on the 24 kinematic world joints J = G_j^t of the chamfer and marker stages (the
+ * translation is not read: the term is translation invariant).  Capsule c = (u, v, alpha, beta, r): two joints, two parameters
+ * on the line through them, a radius in metres; a_c = J_u + alpha (J_v - J_u), b_c = J_u + beta (J_v - J_u); alpha == beta is a
+ * sphere, values outside [0, 1] reach past the joints.  Pair k = (i, j): two capsule indices.  For every frame and pair
+ *   (s, t) = closest-point parameters of the segments [a_i, b_i], [a_j, b_j] (Ericson, Real-Time Collision Detection 5.1.9: a
+ *            segment with |b - a|^2 <= 1e-12 is a point, den = A E - b^2 <= 1e-6 A E is parallel and takes s = 0)
+ *   c_i = a_i + s (b_i - a_i),  c_j = a_j + t (b_j - a_j),  delta = c_i - c_j,  d = |delta|,  pen = max(r_i + r_j - d, 0)
+ *   loss += w sum_t sum_k pen^2 / F            (1 / F only: a weight does not depend on the pair list)
+ *   dL/dc_i = -(2 w / F) pen delta / d = -dL/dc_j   (s, t held fixed; d == 0: no gradient, pen^2 still counts)
+ *   gamma_i = alpha_i + s (beta_i - alpha_i):  dL/dJ_{u_i} += (1 - gamma_i) dL/dc_i,  dL/dJ_{v_i} += gamma_i dL/dc_i  (same for j)
+ * in m^2.  Frames are not coupled: F = 1 is a valid problem.  The radii do not follow the shape parameters.
+ * A setting of the WORKSPACE (off at creation) with the lifetime rules of uuo_fit_set_joint_accel.  The three lists are HOST
+ * arrays -- h_cap_joints [C][2], h_cap_geom [C][3] (alpha, beta, radius), h_pairs [P][2] -- checked and COPIED at the call: the
+ * library owns the device copies and a joint -> (pair, end) table it builds from them, in pair order, from which the kernel
+ * sums the joints' gradients without atomics (results are bit-reproducible).  A call with the lists of the previous call
+ * uploads nothing.  w == 0 switches the term off; the pointers may then be null, and every result is that of a workspace that
+ * never had the setting.  Errors (-22): a negative or non-finite w, C outside 1 .. 32, P outside 1 .. 256, a joint id outside
+ * [0, 24) or u == v, a non-finite alpha or beta, a radius <= 0 or non-finite, a pair index outside [0, C) or i == j, null arrays
+ * with w > 0.  Works with robust_sigma, the joint-acceleration, foot-lock and floor-contact terms, the latent marker offsets,
+ * three-corner placements, the point-to-surface term and the per-frame vertex table.  Refused (at evaluation) for the part stage
+ * and with w_soft != 0, and inside lock-step batches (uuo_batch_*). */
+int uuo_fit_set_capsules(uuo_fit_t* fit, float w, int32_t n_caps, const int32_t* h_cap_joints, const float* h_cap_geom,
+                         int32_t n_pairs, const int32_t* h_pairs);
 /* EXTENSION (not reference behaviour; MoSh-style fitters score a marker by its distance to the SKIN less its stand-off, the
  * reference's chamfer term by its distance to the nearest VERTEX): on = 1 replaces the chamfer stage's data term
  * min_v |x - v|^2 by the point-to-surface term on the one-ring of the nearest vertex v^ the closure's search finds anyway:

@@ -1,0 +1,519 @@
+"""EXTENSION: the bone-capsule self-penetration term (stages.{chamfer,marker}.losses.self_penetration) -- config validation and
+routing, the composed route's torch term against a numpy restatement on every branch of the closest-point routine, the envelope
+claim against difference quotients, the capsule builder, the metric, the generator's penetrating capture and the C entry
+point's binding.  No GPU needed (tests/test_gpu_capsules.py holds the fused closures and the fits)."""
+import os
+import re
+import subprocess
+from ctypes import c_float, c_int, c_void_p
+
+import numpy as np
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+BLOCK = {"joints": [[16, 18], [3, 6]], "geom": [[0.0, 1.0, 0.04], [0.1, 0.9, 0.1]], "pairs": [[0, 1]]}
+
+
+def _cfg(name="video_mocap", **stages):
+    """packaged config; per stage a dict whose `capsules` entry goes on the stage, the rest on its losses"""
+    from uuo_mocap_amd.config import packaged_config
+
+    cfg = packaged_config(name)
+    for stage, kv in stages.items():
+        for k, v in kv.items():
+            if k == "capsules":
+                cfg["stages"][stage][k] = v
+            else:
+                cfg["stages"][stage]["losses"][k] = v
+    return cfg
+
+
+# ------------------------------------------------------------------------------------------------ 1. config, refusals, routing
+@pytest.mark.parametrize("stage", ["chamfer", "marker"])
+def test_capsule_keys_are_read_and_validated(stage):
+    from uuo_mocap_amd.engine import stage_capsules
+
+    assert stage_capsules(_cfg(), stage) == {"w": 0.0, "capsules": None}   # absent: off
+    assert stage_capsules(_cfg(**{stage: {"self_penetration": None}}), stage)["w"] == 0.0
+    got = stage_capsules(_cfg(**{stage: {"self_penetration": 2.5, "capsules": BLOCK}}), stage)
+    assert got == {"w": 2.5, "capsules": BLOCK}
+    for bad in (-1.0, float("nan"), float("inf")):
+        with pytest.raises(ValueError, match="self_penetration"):
+            stage_capsules(_cfg(**{stage: {"self_penetration": bad}}), stage)
+
+    def block(**kw):
+        return dict(BLOCK, **kw)
+
+    many_j = [[0, 1]] * 33
+    many_g = [[0.0, 1.0, 0.1]] * 33
+    for bad in ("capsules", [1, 2], {"joints": [[0, 1]]}, block(joints=[[16, 18], [3, 3]]), block(joints=[[16, 18], [3, 24]]),
+                block(joints=[[16, 18], [-1, 3]]), block(joints=[[16, 18]]), block(joints=[[16, 18], [3, 6.0]]),
+                block(geom=[[0.0, 1.0, 0.04], [0.1, 0.9, 0.0]]), block(geom=[[0.0, 1.0, 0.04], [0.1, 0.9, -0.1]]),
+                block(geom=[[0.0, float("nan"), 0.04], [0.1, 0.9, 0.1]]), block(geom=[[0.0, 1.0, float("inf")], [0.1, 0.9, 0.1]]),
+                block(geom=[[0.0, 1.0], [0.1, 0.9]]), block(pairs=[[0, 0]]), block(pairs=[[0, 2]]), block(pairs=[[-1, 1]]),
+                block(pairs=[]), block(pairs=[[0, 1]] * 257), {"joints": many_j, "geom": many_g, "pairs": [[0, 1]]},
+                block(pairs=[[True, 1]])):
+        with pytest.raises(ValueError, match="capsules"):
+            stage_capsules(_cfg(**{stage: {"capsules": bad}}), stage)
+    assert len(stage_capsules(_cfg(**{stage: {"capsules": block(pairs=[[0, 1]] * 256)}}), stage)["capsules"]["pairs"]) == 256
+
+
+def test_stage_problems_refuse_bad_keys_before_touching_the_device():
+    from uuo_mocap_amd.engine import ChamferProblem, MarkerProblem, PartProblem
+
+    with pytest.raises(ValueError, match="self_penetration"):
+        ChamferProblem(None, None, None, None, None, _cfg(chamfer={"self_penetration": -2.0}))
+    with pytest.raises(ValueError, match="self_penetration"):
+        MarkerProblem(None, None, None, None, None, _cfg(marker={"self_penetration": float("nan")}))
+    with pytest.raises(ValueError, match="capsules"):
+        MarkerProblem(None, None, None, None, None, _cfg(marker={"self_penetration": 1.0, "capsules": {"joints": []}}))
+    with pytest.raises(NotImplementedError, match="soft"):
+        ChamferProblem(None, None, None, None, None, _cfg(chamfer={"self_penetration": 1.0, "soft_chamfer": 10.0}))
+    with pytest.raises(NotImplementedError, match="self_penetration"):
+        PartProblem(None, None, None, None, None, None, _cfg(part={"self_penetration": 1.0}))
+
+
+def test_routing_flags():
+    from uuo_mocap_amd.optimization import _capsule_fused, _capsules_on, lockstep_supported
+
+    plain, caps = _cfg(), _cfg("video_mocap_capsules")
+    for stage in ("chamfer", "marker"):
+        assert not _capsules_on(plain, stage) and _capsules_on(caps, stage)
+        assert lockstep_supported(_cfg(**{stage: {"self_penetration": 0.0}}), stage)
+        assert not lockstep_supported(caps, stage)          # lock-step batches do not carry the term
+        assert not lockstep_supported(_cfg(**{stage: {"self_penetration": 1.0}}), stage)
+        assert _capsule_fused(caps, stage)
+        composed = _cfg("video_mocap_capsules")
+        composed["execution"] = {"capsule_fused": False}
+        assert not _capsule_fused(composed, stage)
+        assert _capsule_fused(dict(plain, execution={"capsule_fused": False}), stage)  # nothing to compose without the term
+
+
+def _zeros(*s):
+    return torch.zeros(*s)
+
+
+class _Smpl:
+    class device_model:
+        V = 6890
+
+
+def test_composed_routes_are_taken(monkeypatch):
+    """execution.capsule_fused: False and soft_chamfer + the key go to the closures composed from the operators"""
+    from uuo_mocap_amd import optimization as opt
+
+    F, M = 6, 4
+    markers = _zeros(F, M, 3)
+    one_hot = _zeros(M, 6890)
+    one_hot[:, 0] = 1.0
+    taken = []
+    monkeypatch.setattr(opt, "_optim_chamfer_general", lambda *a, **k: taken.append("chamfer"))
+    monkeypatch.setattr(opt, "_optim_markers_general", lambda *a, **k: taken.append("marker"))
+    cfg = _cfg("video_mocap_capsules")
+    cfg["execution"] = {"capsule_fused": False}
+    args_c = (markers, _zeros(F, 23, 3, 3), _zeros(F, 23, 3, 3), _zeros(1, 10), _zeros(1, 10), _zeros(F, 1, 3, 3), _zeros(F, 3),
+              _zeros(F), torch.zeros(F, M, dtype=torch.long), None)
+    opt.optim_chamfer(*args_c, cfg)
+    opt.optim_markers(markers, _zeros(F, 23, 3, 3), _zeros(F, 23, 3, 3), _zeros(1, 10), _zeros(1, 10), _zeros(F, 1, 3, 3),
+                      _zeros(F, 3), one_hot, _zeros(F), _Smpl, cfg)
+    assert taken == ["chamfer", "marker"]
+    soft = _cfg("video_mocap_capsules", chamfer={"soft_chamfer": 10.0})
+    opt.optim_chamfer(*args_c, soft)   # (markers on the host: the fused soft closure is not in reach either way)
+    assert taken == ["chamfer", "marker", "chamfer"]
+
+
+def test_frame_sharding_refuses_the_term():
+    from uuo_mocap_amd import parallel
+    from uuo_mocap_amd.optimization import optim_chamfer, optim_markers
+
+    F, M = 6, 4
+    markers = _zeros(F, M, 3)
+    one_hot = _zeros(M, 6890)
+    one_hot[:, 0] = 1.0
+    with parallel.shard_frames(joint_with_one_rank=True):
+        with pytest.raises(NotImplementedError, match="self_penetration.*frame-block sharding"):
+            optim_chamfer(markers, _zeros(F, 23, 3, 3), _zeros(F, 23, 3, 3), _zeros(1, 10), _zeros(1, 10), _zeros(F, 1, 3, 3),
+                          _zeros(F, 3), _zeros(F), torch.zeros(F, M, dtype=torch.long), None, _cfg(chamfer={"self_penetration": 1.0}))
+        with pytest.raises(NotImplementedError, match="self_penetration.*frame-block sharding"):
+            optim_markers(markers, _zeros(F, 23, 3, 3), _zeros(F, 23, 3, 3), _zeros(1, 10), _zeros(1, 10), _zeros(F, 1, 3, 3),
+                          _zeros(F, 3), one_hot, _zeros(F), _Smpl, _cfg(marker={"self_penetration": 1.0}))
+
+
+def test_solve_batch_refuses_the_term_up_front():
+    from uuo_mocap_amd.engine import solve_batch
+
+    class _P:
+        model = None
+        joint_accel = 0.0
+        foot_lock = 0.0
+        floor_on = False
+        capsules_on = True
+
+        class problem:
+            w_offsets = 0.0
+
+    with pytest.raises(NotImplementedError, match="self_penetration"):
+        solve_batch([_P()], [None], max_iter=1)
+
+
+def test_shipped_config_differs_from_its_parent_only_by_the_term():
+    from uuo_mocap_amd.engine import stage_capsules
+
+    plain, caps = _cfg(), _cfg("video_mocap_capsules")
+    for stage in ("chamfer", "marker"):
+        c = stage_capsules(caps, stage)
+        assert c["w"] > 0.0 and c["capsules"] is None
+        rest = {k: v for k, v in caps["stages"][stage]["losses"].items() if k != "self_penetration"}
+        assert rest == plain["stages"][stage]["losses"]
+        assert {k: v for k, v in caps["stages"][stage].items() if k not in ("losses", "capsules")} == \
+            {k: v for k, v in plain["stages"][stage].items() if k != "losses"}
+    for k in plain["stages"]:
+        if k not in ("chamfer", "marker"):
+            assert caps["stages"][k] == plain["stages"][k]
+
+
+# ------------------------------------------------------------------------------------------------ 2. the term, branch by branch
+def _clamp(v):
+    return min(max(v, 0.0), 1.0)
+
+
+def _closest_np(a1, b1, a2, b2):
+    """The issue's routine on one pair, plain float64 Python; returns s, t and the name of the branch taken"""
+    d1, d2, r = b1 - a1, b2 - a2, a1 - a2
+    A, E = float(d1 @ d1), float(d2 @ d2)
+    f, c, b = float(d2 @ r), float(d1 @ r), float(d1 @ d2)
+    if A <= 1e-12 and E <= 1e-12:
+        return 0.0, 0.0, "point/point"
+    if A <= 1e-12:
+        return 0.0, _clamp(f / E), "point/segment"
+    if E <= 1e-12:
+        return _clamp(-c / A), 0.0, "segment/point"
+    den = A * E - b * b
+    if den > 1e-6 * A * E:
+        s, tag = _clamp((b * f - c * E) / den), "general"
+        if s in (0.0, 1.0):
+            tag = "general, s clamped"
+    else:
+        s, tag = 0.0, "parallel"
+    t = (b * s + f) / E
+    if t < 0.0:
+        return _clamp(-c / A), 0.0, tag + ", t < 0"
+    if t > 1.0:
+        return _clamp((b - c) / A), 1.0, tag + ", t > 1"
+    return s, t, tag
+
+
+def _term_np(J, cj, cg, pr, w):
+    """loss, d loss / d J [F, 24, 3] and the branches taken: the issue's formulas with explicit loops"""
+    F = J.shape[0]
+    loss, g, tags = 0.0, np.zeros_like(J), []
+    for f in range(F):
+        for (i, j) in pr:
+            ends = []
+            for c in (i, j):
+                u, v = cj[c]
+                ends.append((J[f, u] + cg[c, 0] * (J[f, v] - J[f, u]), J[f, u] + cg[c, 1] * (J[f, v] - J[f, u])))
+            s, t, tag = _closest_np(ends[0][0], ends[0][1], ends[1][0], ends[1][1])
+            delta = (ends[0][0] + s * (ends[0][1] - ends[0][0])) - (ends[1][0] + t * (ends[1][1] - ends[1][0]))
+            d = float(np.sqrt(delta @ delta))
+            pen = max(cg[i, 2] + cg[j, 2] - d, 0.0)
+            loss += w * pen * pen / F
+            tags.append(tag + (", d = 0" if d == 0.0 else "") + (", active" if pen > 0.0 else ""))
+            if d > 0.0 and pen > 0.0:
+                gc = -(2.0 * w / F) * pen * delta / d
+                for c, par, sign in ((i, s, 1.0), (j, t, -1.0)):
+                    gam = cg[c, 0] + par * (cg[c, 1] - cg[c, 0])
+                    g[f, cj[c, 0]] += (1.0 - gam) * sign * gc
+                    g[f, cj[c, 1]] += gam * sign * gc
+    return loss, g, tags
+
+
+# hand-built frames: joints 0, 1 carry capsule 0 (a segment) and capsule 2 (a sphere at its midpoint), joints 2, 3 capsule 1 and
+# capsule 3 likewise; every frame is one geometry of the two lines
+HAND_CJ = np.array([[0, 1], [2, 3], [0, 1], [2, 3]])
+HAND_CG = np.array([[0.0, 1.0, 0.04], [0.0, 1.0, 0.05], [0.5, 0.5, 0.04], [0.5, 0.5, 0.05]])
+HAND_PR = np.array([[0, 1], [2, 1], [0, 3], [2, 3]])   # segment/segment, sphere/segment, segment/sphere, sphere/sphere
+HAND_FRAMES = {
+    "interior / interior crossing": ([-1, 0, 0], [1, 0, 0], [0.1, -1, 0.05], [0.1, 1, 0.05]),
+    "end point / interior (s clamped)": ([0, 0, 0], [1, 0, 0], [1.03, -1, 0.02], [1.03, 1, 0.02]),
+    "interior / end point (t < 0)": ([0, 0, 0], [1, 0, 0], [0.5, 0.05, 0], [0.5, 1, 0]),
+    "interior / end point (t > 1)": ([0, 0, 0], [1, 0, 0], [0.5, -1, 0], [0.5, -0.05, 0]),
+    "end point / end point": ([0, 0, 0], [1, 0, 0], [1.03, 0.03, 0], [2, 1, 0]),
+    "exactly parallel": ([0, 0, 0], [1, 0, 0], [0.2, 0.05, 0], [0.8, 0.05, 0]),
+    "exactly parallel, apart": ([0, 0, 0], [1, 0, 0], [1.5, 0.05, 0], [2.5, 0.05, 0]),
+    "d = 0": ([-1, 0, 0], [1, 0, 0], [0, -1, 0], [0, 1, 0]),
+    "spheres close": ([0, 0, 0], [0.1, 0, 0], [0.05, 0.06, 0], [0.05, 0.06, 0.1]),
+}
+
+
+def _hand_joints():
+    J = np.zeros((len(HAND_FRAMES), 24, 3))
+    J[:, 4:] = 10.0 + np.arange(20)[None, :, None]
+    for f, pts in enumerate(HAND_FRAMES.values()):
+        J[f, :4] = np.array(pts, dtype=np.float64)
+    return J
+
+
+def test_term_and_gradient_match_the_numpy_restatement_on_every_branch():
+    from uuo_mocap_amd.body_model import capsule_closest_params, capsule_pair_depths
+    from uuo_mocap_amd.losses import self_penetration_loss
+
+    J = _hand_joints()
+    w = 3.0
+    loss_np, g_np, tags = _term_np(J, HAND_CJ, HAND_CG, HAND_PR, w)
+    seen = " | ".join(tags)
+    for need in ("general, active", "general, s clamped", "t < 0", "t > 1", "parallel", "point/segment", "segment/point",
+                 "point/point", "d = 0"):
+        assert need in seen, need
+    assert any("d = 0" in t and "active" in t for t in tags) and any("active" not in t for t in tags)
+    Jt = torch.from_numpy(J).requires_grad_(True)
+    loss = self_penetration_loss(Jt, HAND_CJ, HAND_CG, HAND_PR, w)
+    loss.backward()
+    assert loss.dtype == torch.float64
+    np.testing.assert_allclose(float(loss.detach()), loss_np, rtol=1e-13)
+    np.testing.assert_allclose(Jt.grad.numpy(), g_np, rtol=1e-12, atol=1e-15)
+    assert np.isfinite(Jt.grad.numpy()).all()
+    # d = 0: pen^2 counts, no gradient
+    f0 = list(HAND_FRAMES).index("d = 0")
+    l0, g0, _ = _term_np(J[f0:f0 + 1], HAND_CJ, HAND_CG, HAND_PR[:1], w)
+    assert l0 == pytest.approx(w * 0.09 ** 2) and not g0.any()
+    # the vectorised numpy routine (builder, metric, generator) takes the same branches
+    a = J[:, HAND_CJ[:, 0]] + HAND_CG[None, :, 0:1] * (J[:, HAND_CJ[:, 1]] - J[:, HAND_CJ[:, 0]])
+    b = J[:, HAND_CJ[:, 0]] + HAND_CG[None, :, 1:2] * (J[:, HAND_CJ[:, 1]] - J[:, HAND_CJ[:, 0]])
+    s, t = capsule_closest_params(a[:, HAND_PR[:, 0]], b[:, HAND_PR[:, 0]], a[:, HAND_PR[:, 1]], b[:, HAND_PR[:, 1]])
+    for f in range(J.shape[0]):
+        for k, (i, j) in enumerate(HAND_PR):
+            s0, t0, _ = _closest_np(a[f, i], b[f, i], a[f, j], b[f, j])
+            assert (s[f, k], t[f, k]) == (s0, t0), (f, k)
+    pen = capsule_pair_depths(J, HAND_CJ, HAND_CG, HAND_PR)
+    assert w * (pen ** 2).sum() / J.shape[0] == pytest.approx(loss_np, rel=1e-13)
+    # float32 joints: the checker runs in the joints' own precision
+    l32 = self_penetration_loss(torch.from_numpy(J).float(), HAND_CJ, HAND_CG, HAND_PR, w)
+    assert l32.dtype == torch.float32 and float(l32) == pytest.approx(loss_np, rel=1e-5)
+
+
+def test_gradient_is_the_derivative_of_the_re_minimised_term(tables):
+    """The envelope claim: with (s, t) held fixed the gradient equals the derivative of the term whose (s, t) are found again at
+    every point.  Central differences with h = 1e-6 m on float64 joints, away from the kinks: truncation h^2 |f'''| / 6 is below
+    1e-9 (third derivatives of w pen^2 with w = 1 are of order 1 / d^2 <= 1e3 here) and rounding eps |loss| / h below 1e-11, so the
+    two must agree to 1e-8 absolute (gradient entries are of order 1e-2)."""
+    from uuo_mocap_amd.body_model import body_capsules
+    from uuo_mocap_amd.losses import self_penetration_loss
+    from uuo_mocap_amd.synthetic import make_sequence
+
+    cj, cg, pr = body_capsules(tables)
+    cg = cg.astype(np.float64)
+    cg[:, 2] *= 2.0   # doubled radii: the term is active
+    J = make_sequence(tables, seed=3, num_frames=3, num_markers=8).gt["joints"].astype(np.float64)
+    loss, g, tags = _term_np(J, cj, cg, pr, 1.0)
+    assert sum("active" in t for t in tags) >= 9
+    Jt = torch.from_numpy(J).requires_grad_(True)
+    self_penetration_loss(Jt, cj, cg, pr, 1.0).backward()
+    np.testing.assert_allclose(Jt.grad.numpy(), g, rtol=1e-11, atol=1e-15)
+    h = 1e-6
+    idx = np.argsort(-np.abs(g).reshape(-1))[:40]   # the 40 largest entries
+    for flat in idx:
+        e = np.zeros(J.size)
+        e[flat] = h
+        e = e.reshape(J.shape)
+        lp, _, tp = _term_np(J + e, cj, cg, pr, 1.0)
+        lm, _, tm = _term_np(J - e, cj, cg, pr, 1.0)
+        assert tp == tags and tm == tags, "a kink within the step: pick another seed"
+        assert abs((lp - lm) / (2.0 * h) - g.reshape(-1)[flat]) <= 1e-8, flat
+
+
+# ------------------------------------------------------------------------------------------------ 3. the builder
+def test_body_capsules_on_the_synthetic_model(tables, monkeypatch):
+    from uuo_mocap_amd import body_model
+    from uuo_mocap_amd.losses import self_penetration_loss
+
+    cj, cg, pr = body_model.body_capsules(tables)
+    C, P = len(cj), len(pr)
+    assert cj.dtype == np.int32 and cg.dtype == np.float32 and pr.dtype == np.int32
+    assert cj.shape == (C, 2) and cg.shape == (C, 3) and pr.shape == (P, 2)
+    assert 1 <= C <= 32 and 1 <= P <= 256
+    assert (cj >= 0).all() and (cj < 24).all() and (cj[:, 0] != cj[:, 1]).all()
+    assert np.isfinite(cg).all() and (cg[:, 2] > 0).all() and (cg[:, 0] < cg[:, 1]).all()
+    assert (pr[:, 0] < pr[:, 1]).all() and (pr >= 0).all() and (pr < C).all()
+    parents = np.asarray(tables.parents)
+    owner = np.argmax(tables.lbs_weights, axis=1)
+    # one capsule per joint that owns vertices; a leaf's line comes from its parent, any other's goes to a child
+    owners = [j for j in range(24) if (owner == j).any()]
+    assert C == len(owners)
+    for c, j in enumerate(owners):
+        kids = np.where(parents == j)[0]
+        if len(kids) == 0:
+            assert tuple(cj[c]) == (parents[j], j) and cg[c, 0] > 0.5   # the leaf's vertices lie beyond its joint
+        else:
+            assert cj[c, 0] == j and cj[c, 1] in kids
+    J0 = (tables.J_regressor.astype(np.float64) @ tables.v_template.astype(np.float64))[None]
+    # the rule restated on its own for a joint with three children twice (pelvis, spine3), one with a single child (left knee)
+    # and a leaf (left hand): the child with the smallest spread of distances to the LINE (by the cross product here), the 10th /
+    # 90th percentile of the unclamped projections, 0.9 x the median distance to the segment between them
+    vt = tables.v_template.astype(np.float64)
+    for j in (0, 9, 4, 22):
+        c = owners.index(j)
+        O = vt[owner == j]
+        kids = np.where(parents == j)[0]
+        if len(kids):
+            spread = [np.std(np.linalg.norm(np.cross(O - J0[0, j], J0[0, k] - J0[0, j]), axis=1) / np.linalg.norm(J0[0, k] - J0[0, j]))
+                      for k in kids]
+            u, v = j, int(kids[int(np.argmin(spread))])
+        else:
+            u, v = int(parents[j]), j
+        assert tuple(cj[c]) == (u, v), j
+        e = J0[0, v] - J0[0, u]
+        t = (O - J0[0, u]) @ e / (e @ e)
+        lo, hi = np.percentile(t, [10.0, 90.0])
+        near = J0[0, u] + np.clip(t, lo, hi)[:, None] * e
+        r = 0.9 * np.median(np.linalg.norm(O - near, axis=1))
+        np.testing.assert_allclose(cg[c], [lo, hi, r], rtol=1e-6, atol=1e-7, err_msg=str(j))
+    assert np.allclose(body_model.body_capsules(tables, shrink=0.5)[1][:, 2], cg[:, 2] * (0.5 / 0.9), rtol=1e-6)
+    # rest pose: exactly no overlap, with the margin to spare
+    assert float(self_penetration_loss(torch.from_numpy(J0), cj, cg, pr, 1.0)) == 0.0
+    wide = cg.astype(np.float64).copy()
+    wide[:, 2] += 0.0025
+    assert body_model.capsule_pair_depths(J0, cj, wide, pr).max() == 0.0
+    # the exclusion rules: a listed pair shares no joint and has no parent / child relation; every pair left out has one, or is
+    # too close at rest
+    listed = {tuple(p) for p in pr.tolist()}
+    for i in range(C):
+        for j in range(i + 1, C):
+            si, sj = set(cj[i].tolist()), set(cj[j].tolist())
+            adjacent = bool(si & sj) or any(parents[q] in sj for q in si) or any(parents[q] in si for q in sj)
+            if (i, j) in listed:
+                assert not adjacent, (i, j)
+            elif not adjacent:
+                assert body_model.capsule_pair_depths(J0, cj, wide, [(i, j)]).max() > 0.0, (i, j)
+    # a wider margin drops pairs; more pairs than the term takes is an error
+    assert len(body_model.body_capsules(tables, rest_margin=0.2)[2]) < P
+    assert body_model.CAPSULE_PAIRS_MAX == 256 and body_model.CAPSULES_MAX == 32
+    monkeypatch.setattr(body_model, "CAPSULE_PAIRS_MAX", P - 1)
+    with pytest.raises(ValueError, match="pairs"):
+        body_model.body_capsules(tables)
+
+
+# ------------------------------------------------------------------------------------------------ 4. the metric
+def test_self_penetration_metric():
+    from uuo_mocap_amd.metrics import compute_self_penetration
+
+    J = torch.zeros(4, 24, 3)
+    J[:, 1] = torch.tensor([1.0, 0.0, 0.0])
+    J[:, 2, 1] = torch.tensor([0.05, 0.08, 0.2, 0.3])    # capsule 1 runs parallel to capsule 0 at these heights
+    J[:, 3] = J[:, 2] + torch.tensor([1.0, 0.0, 0.0])
+    cj, cg, pr = [[0, 1], [2, 3]], [[0.0, 1.0, 0.05], [0.0, 1.0, 0.05]], [[0, 1]]
+    e = compute_self_penetration(J, cj, cg, pr)
+    assert e["max_depth_mm"] == pytest.approx(50.0, abs=1e-4)
+    assert e["mean_depth_mm"] == pytest.approx((50.0 + 20.0) / 4.0, abs=1e-4)
+    assert e["frames_pct"] == pytest.approx(50.0)
+    e0 = compute_self_penetration(J[2:], cj, cg, pr)
+    assert e0 == {"max_depth_mm": 0.0, "mean_depth_mm": 0.0, "frames_pct": 0.0}
+    with pytest.raises(ValueError, match="joints"):
+        compute_self_penetration(torch.zeros(4, 23, 3), cj, cg, pr)
+
+
+# ------------------------------------------------------------------------------------------------ 5. the generator
+@pytest.fixture(scope="module")
+def sequences(tables):
+    from uuo_mocap_amd.synthetic import make_sequence
+
+    return (make_sequence(tables, seed=0, num_frames=300, num_markers=50),
+            make_sequence(tables, seed=0, num_frames=300, num_markers=50, self_penetration=False),
+            make_sequence(tables, seed=0, num_frames=300, num_markers=50, self_penetration=True))
+
+
+def _same(a, b):
+    if isinstance(a, torch.Tensor):
+        return torch.equal(a, b)
+    if isinstance(a, np.ndarray):
+        return a.dtype == b.dtype and np.array_equal(a, b)
+    return a == b
+
+
+def test_option_off_changes_nothing(sequences):
+    base, off, _ = sequences
+    assert set(base.gt) == set(off.gt) and not {"capsules", "penetration_window", "hmr_overlap"} & set(base.gt)
+    for k in base.gt:
+        assert _same(base.gt[k], off.gt[k]), k
+    for k, v in vars(base.img_smpl).items():
+        assert _same(v, getattr(off.img_smpl, k)), k
+    assert np.array_equal(base.markers.get_points(), off.markers.get_points())
+
+
+def test_penetrating_sequence(tables, sequences):
+    from uuo_mocap_amd.body_model import body_capsules, capsule_pair_depths
+    from uuo_mocap_amd.synthetic import fk_joints_f64, make_sequence, rest_joints_f64
+
+    base, _, seq = sequences
+    cj, cg, pr = seq.gt["capsules"]
+    for a, b in zip((cj, cg, pr), body_capsules(tables)):
+        assert np.array_equal(a, b)
+    t0, t1 = seq.gt["penetration_window"]
+    assert t1 - t0 == 24 and t0 >= 30 and t1 <= 300
+    # every ground-truth array is the default capture's, and the ground truth is free of overlap in the window (and t0 is the
+    # first such start from F / 10 on)
+    for k in base.gt:
+        assert _same(base.gt[k], seq.gt[k]), k
+    free = capsule_pair_depths(seq.gt["joints"].astype(np.float64), cj, cg, pr).max(axis=1) == 0.0
+    assert free[t0:t1].all()
+    assert not any(free[a:a + 24].all() for a in range(30, t0))
+    # the HMR start: only the left shoulder, only in the window; 30 mm of arm / trunk overlap in the untapered frames
+    hb, hs = base.img_smpl.pose_body, seq.img_smpl.pose_body
+    changed = (hb != hs).reshape(300, 23, -1).any(-1)
+    assert changed[t0:t1, 15].all() and not changed[:, :15].any() and not changed[:, 16:].any()
+    assert not changed[:t0].any() and not changed[t1:].any()
+    for k, v in vars(base.img_smpl).items():
+        if k != "pose_body":
+            assert _same(v, getattr(seq.img_smpl, k)), k
+    ov = seq.gt["hmr_overlap"]
+    assert ov.shape == (300,) and np.abs(ov[t0 + 2:t1 - 2] - 0.030).max() <= 1e-3
+    assert (ov[t0:t0 + 2] < 0.030).all() and (ov[t1 - 2:t1] < 0.030).all()          # tapered ends
+    # ... and that is the float32 pose the fit starts from: recomputed from img_smpl, over all pairs at least as deep
+    rot = torch.cat([seq.img_smpl.root_orient, seq.img_smpl.pose_body], dim=1).double().numpy()
+    J = fk_joints_f64(tables, rot, rest_joints_f64(tables, seq.img_smpl.betas.double().numpy().mean(axis=0)))[0]
+    deep = capsule_pair_depths(J, cj, cg, pr).max(axis=1)
+    assert (deep[t0 + 2:t1 - 2] >= 0.030 - 1e-3).all()
+    # the arm's marker columns are blank in the window, and nothing else changed
+    owner = np.argmax(np.asarray(tables.lbs_weights)[np.asarray(seq.gt["marker_vids"])], axis=1)
+    arm = np.isin(owner, [16, 18, 20, 22])
+    assert arm.sum() >= 1
+    m0, m1 = np.asarray(base.markers.get_points()), np.asarray(seq.markers.get_points())
+    assert not m1[t0:t1][:, arm].any()
+    keep = np.ones(m0.shape[:2], dtype=bool)
+    keep[t0:t1, arm] = False
+    assert np.array_equal(m0[keep], m1[keep])
+    with pytest.raises(ValueError, match="window"):
+        make_sequence(tables, seed=0, num_frames=20, num_markers=8, self_penetration=True)
+
+
+# ------------------------------------------------------------------------------------------------ 6. C entry point
+def test_entry_point_is_declared_bound_and_typed_as_in_the_header(tmp_path):
+    from uuo_mocap_amd import _lib
+
+    assert "uuo_fit_set_capsules" in _lib.header_symbols()
+    sig = [c_void_p, c_float, c_int, c_void_p, c_void_p, c_int, c_void_p]
+    assert _lib._SIGNATURES["uuo_fit_set_capsules"] == (c_int, sig)
+    text = re.sub(r"/\*.*?\*/", "", open(_lib.HEADER_PATH).read(), flags=re.S)
+    assert re.search(r"\bint\s+uuo_fit_set_capsules\s*\(\s*uuo_fit_t\s*\*\s*fit\s*,\s*float\s+w\s*,\s*int32_t\s+n_caps\s*,\s*const\s+"
+                     r"int32_t\s*\*\s*h_cap_joints\s*,\s*const\s+float\s*\*\s*h_cap_geom\s*,\s*int32_t\s+n_pairs\s*,\s*const\s+"
+                     r"int32_t\s*\*\s*h_pairs\s*\)\s*;", text)
+    src = tmp_path / "sig.c"
+    src.write_text('#include "uuo_hip.h"\nint (*fp)(uuo_fit_t*, float, int32_t, const int32_t*, const float*, int32_t, const int32_t*) '
+                   '= uuo_fit_set_capsules;\nint main(void) { return 0; }\n')
+    subprocess.check_call(["gcc", "-std=c99", "-Werror", "-c", "-I", os.path.join(ROOT, "include"), str(src), "-o",
+                           str(tmp_path / "sig.o")])
+    assert _lib.ABI_VERSION == 3  # the problem structure and the ABI version did not change
+    lib = _lib.load()             # (dlopen needs no GPU) bound with the declared types
+    assert lib.uuo_fit_set_capsules.argtypes == sig and lib.uuo_fit_set_capsules.restype == c_int
+
+
+def test_note_in_the_header():
+    from uuo_mocap_amd import _lib
+
+    text = open(_lib.HEADER_PATH).read()
+    note = text[text.index("bone-capsule self-penetration term"):text.index("int uuo_fit_set_capsules")]
+    for word in ("translation invariant", "m^2", "Ericson", "1e-12", "1e-6", "HOST", "COPIED", "pair order", "1 .. 32", "1 .. 256",
+                 "F = 1", "part stage", "lock-step", "do not follow"):
+        assert word in note, word

@@ -331,6 +331,109 @@ def sole_vertices(tables: SmplTables, per_foot: int = 3) -> np.ndarray:
     return out
 
 
+def capsule_closest_params(a1: np.ndarray, b1: np.ndarray, a2: np.ndarray, b2: np.ndarray):
+    """EXTENSION: closest-point parameters (s, t) in [0, 1] of the segments [a1, b1] and [a2, b2] (arrays [..., 3], float64),
+    the routine of the self-penetration term (uuo_fit_set_capsules; Ericson, Real-Time Collision Detection 5.1.9) branch for
+    branch: a segment with |b - a|^2 <= 1e-12 is a point, den = A E - b^2 <= 1e-6 A E is parallel and takes s = 0."""
+    a1, b1, a2, b2 = (np.asarray(x, dtype=np.float64) for x in (a1, b1, a2, b2))
+    d1, d2, r = b1 - a1, b2 - a2, a1 - a2
+    A, E = (d1 * d1).sum(-1), (d2 * d2).sum(-1)
+    f, c, b = (d2 * r).sum(-1), (d1 * r).sum(-1), (d1 * d2).sum(-1)
+    dA, dE = A <= 1e-12, E <= 1e-12
+    clamp = lambda v: np.clip(v, 0.0, 1.0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        den = A * E - b * b
+        s = np.where(den > 1e-6 * (A * E), clamp((b * f - c * E) / den), 0.0)
+        t = (b * s + f) / E
+        s = np.where(t < 0.0, clamp(-c / A), np.where(t > 1.0, clamp((b - c) / A), s))
+        t = clamp(t)
+        s = np.where(dE, clamp(-c / A), s)
+        t = np.where(dE, 0.0, t)
+        t = np.where(dA, clamp(f / E), t)
+        s = np.where(dA, 0.0, s)
+        t = np.where(dA & dE, 0.0, t)
+    return s, t
+
+
+def capsule_pair_depths(joints: np.ndarray, cap_joints, cap_geom, pairs) -> np.ndarray:
+    """EXTENSION: overlap depths max(r_i + r_j - d, 0) [F, P] (metres, float64) of the capsule pairs of the self-penetration
+    term on joints [F, >= 24, 3]: capsule c = (u, v, alpha, beta, r) spans a = J_u + alpha (J_v - J_u) .. b = J_u + beta (J_v - J_u),
+    d is the distance of the two segments (capsule_closest_params)."""
+    J = np.asarray(joints, dtype=np.float64)
+    cj = np.asarray(cap_joints, dtype=np.int64).reshape(-1, 2)
+    cg = np.asarray(cap_geom, dtype=np.float64).reshape(-1, 3)
+    pr = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    e = J[:, cj[:, 1]] - J[:, cj[:, 0]]
+    a = J[:, cj[:, 0]] + cg[None, :, 0:1] * e
+    b = J[:, cj[:, 0]] + cg[None, :, 1:2] * e
+    a1, b1, a2, b2 = a[:, pr[:, 0]], b[:, pr[:, 0]], a[:, pr[:, 1]], b[:, pr[:, 1]]
+    s, t = capsule_closest_params(a1, b1, a2, b2)
+    delta = (a1 + s[..., None] * (b1 - a1)) - (a2 + t[..., None] * (b2 - a2))
+    d = np.sqrt((delta * delta).sum(-1))
+    return np.maximum(cg[pr[:, 0], 2] + cg[pr[:, 1], 2] - d, 0.0)
+
+
+#: most capsules and pairs the self-penetration term takes (uuo_fit_set_capsules; UUO_CAPS_MAXC / UUO_CAPS_MAXP of the kernel)
+CAPSULES_MAX, CAPSULE_PAIRS_MAX = 32, 256
+
+
+def body_capsules(tables: SmplTables, shrink: float = 0.9, rest_margin: float = 0.005):
+    """EXTENSION: the default capsule set of the self-penetration term (uuo_fit_set_capsules): (cap_joints [C, 2] int32,
+    cap_geom [C, 3] float32 -- alpha, beta, radius --, pairs [P, 2] int32), from the rest pose at beta = 0 in float64.
+    One capsule per joint j that is the dominant skinning joint of at least one vertex (O_j those vertices).  Its line: a leaf
+    joint uses (parent(j), j); any other (j, k) with k the child for which the standard deviation over O_j of the distance to
+    the line J_j J_k is smallest (lowest k on ties).  alpha, beta are the 10th and 90th percentile (numpy's default
+    interpolation) of the vertices' unclamped projection parameters on that line, the radius `shrink` x the median distance of
+    O_j to the segment [alpha, beta].  Pairs: all i < j, except those whose joint sets share a joint or in which a joint of one
+    is the parent of a joint of the other (neighbouring parts overlap by construction), and those closer than
+    r_i + r_j + rest_margin in the rest pose.  More than 256 pairs is a ValueError.
+    Geometric on purpose, and checked on the synthetic tables only: on a real SMPL the rule is unverified (no licensed model
+    at hand).  The radii do not follow the shape parameters."""
+    vt = tables.v_template.astype(np.float64)
+    J = tables.J_regressor.astype(np.float64) @ vt
+    parents = np.asarray(tables.parents).astype(np.int64)
+    owner = np.argmax(tables.lbs_weights, axis=1)
+    cj, cg = [], []
+    for j in range(NUM_JOINTS):
+        O = vt[owner == j]
+        if len(O) == 0:
+            continue
+        kids = np.where(parents == j)[0]
+        if len(kids) == 0:
+            u, v = int(parents[j]), j
+        else:
+            best = None
+            for k in kids:
+                e = J[k] - J[j]
+                t = ((O - J[j]) @ e) / (e @ e)
+                sd = np.std(np.linalg.norm(O - (J[j] + t[:, None] * e), axis=1))
+                if best is None or sd < best[0]:
+                    best = (sd, int(k))
+            u, v = j, best[1]
+        e = J[v] - J[u]
+        t = ((O - J[u]) @ e) / (e @ e)
+        al, be = np.percentile(t, 10.0), np.percentile(t, 90.0)
+        tc = np.clip(t, al, be)
+        rad = float(shrink) * float(np.median(np.linalg.norm(O - (J[u] + tc[:, None] * e), axis=1)))
+        cj.append((u, v))
+        cg.append((al, be, rad))
+    cj, cg = np.asarray(cj, dtype=np.int64), np.asarray(cg, dtype=np.float64)
+    C = len(cj)
+    cand = []
+    for i in range(C):
+        for j in range(i + 1, C):
+            si, sj = set(cj[i].tolist()), set(cj[j].tolist())
+            if si & sj or any(parents[q] in sj for q in si) or any(parents[q] in si for q in sj):
+                continue
+            cand.append((i, j))
+    if cand:
+        gap = capsule_pair_depths(J[None], cj, np.concatenate([cg[:, :2], cg[:, 2:] + 0.5 * float(rest_margin)], axis=1), cand)[0]
+        cand = [pq for pq, g in zip(cand, gap) if not g > 0.0]  # (r_i + r_j + rest_margin - d > 0: too close at rest)
+    if len(cand) > CAPSULE_PAIRS_MAX:
+        raise ValueError("body_capsules: %d pairs, more than the %d the self-penetration term takes" % (len(cand), CAPSULE_PAIRS_MAX))
+    return cj.astype(np.int32), cg.astype(np.float32), np.asarray(cand, dtype=np.int32).reshape(-1, 2)
+
+
 class _ChStub:
     """Stands in for chumpy.ch.Ch when unpickling original SMPL files (install.sh:18 needs chumpy)."""
 

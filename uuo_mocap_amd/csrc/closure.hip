@@ -98,6 +98,10 @@ struct BwdArgs {
   uuo_gptr<const int> floor_vids;     // [K] their vertex ids
   uuo_gptr<const float> floor_up;     // [F][K][3] their upstream gradients, left by k_floor_fwd of this evaluation
   uuo_gptr<const float> floor_loss;   // [F] the frame's share of the term, already weighted
+  // EXTENSION (ACCEL instantiations, cap_up != null): the self-penetration term (uuo_fit_set_capsules), left by k_capsule_fwd of
+  // this evaluation
+  uuo_gptr<const float> cap_up;       // [F][24][3] upstream gradients on the world joints G_j^t (null = off)
+  uuo_gptr<const float> cap_loss;     // [F] the frame's share of the term, already weighted
 };
 
 // EXTENSION: the offsets' share of the finalize (k_finalize_o / k_finalize_to, uuo_problem_t.w_offsets)
@@ -437,6 +441,11 @@ __device__ __forceinline__ float gmof_q(float sig2, float s) { return sig2 / (si
 // share of the loss.  The points join the item loop as items M .. M + K - 1 with that upstream gradient given (the fetch and the
 // arithmetic of item mode: weight 1, no residual, no marker offset, no robust weight, no loss of their own); the frame's share
 // joins slot 3.  Separate instantiations (*_fl): sharing the ACCEL ones changed their register allocation.
+// block-uniform cap_up != null (EXTENSION, uuo_fit_set_capsules; acc_w and lock_w may both be 0): the bone-capsule
+// self-penetration term.  k_capsule_fwd has evaluated the pairs of every frame on its G^t and left d loss / d G_j^t [F][24][3]
+// and the frame's weighted share of the loss.  The gradient joins uj where the joint-acceleration term's enters (so it reaches
+// sdGt, and through s_acc[ACC_UJ + k] the translation's sum: the term is translation invariant, the 24 entries of a component
+// sum to rounding), the share joins slot 3.  Shared instantiations, by the rule of DESIGN 4o (4s has the resource table).
 // OFFS (EXTENSION, uuo_problem_t.w_offsets > 0): latent per-marker offsets.  Item mm belongs to marker mm / offs_k; its
 // rest-space position is vp + o_m wherever it enters (the skinned position and the dA outer product), and its d loss / d o =
 // T^T g (dvp, which the blend gradients use too) goes to offs_part[f][mm] for k_finalize_o.  The host launches these with
@@ -911,6 +920,7 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a) {
           uj += (2.f * a.lock_w) * (g0 * v0 - g1 * v1);
           s_acc[k] = g0 * (v0 * v0);
         }
+        if (a.cap_up) uj += a.cap_up[(size_t)f * 72 + k];  // the self-penetration term's d loss / d G_j^t (k_capsule_fwd)
         s_acc[ACC_UJ + k] = uj;
         s_acc[ACC_AA + k] = ac[2] * ac[2];
       }
@@ -1131,6 +1141,7 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a) {
         share += a.lock_w * sl;
       }
       if constexpr (FLOOR) share += a.floor_loss[f];  // the floor-contact term's share of this frame (k_floor_fwd)
+      if (a.cap_up) share += a.cap_loss[f];           // the self-penetration term's share of this frame (k_capsule_fwd)
       BWD_FP_STORE(3, share);
     }
   }
@@ -1539,6 +1550,132 @@ __global__ __launch_bounds__(64) void k_floor_fwd(FloorFwdArgs a) {
 }
 
 // ----------------------------------------------------------------------------------------------------
+// EXTENSION (not reference behaviour; uuo_fit_set_capsules): a bone-capsule self-penetration term.  Capsule c = (u, v, alpha,
+// beta, r): end points a = J_u + alpha (J_v - J_u), b = J_u + beta (J_v - J_u) on the line through two world joints J = G_j^t
+// (no translation: the term is translation invariant), radius r.  For every pair k = (i, j) of the list:
+//   (s, t) = closest-point parameters of the segments [a_i, b_i], [a_j, b_j] (Ericson, Real-Time Collision Detection 5.1.9;
+//            capsule_closest below, degenerate when |d|^2 <= 1e-12, parallel when den <= 1e-6 A E)
+//   delta = c_i - c_j,  d = |delta|,  pen = max(r_i + r_j - d, 0),  loss += w pen^2 / F,
+//   dL/dc_i = -(2 w / F) pen delta / d = -dL/dc_j   (s, t held fixed: envelope theorem; d = 0: no gradient, pen^2 still counts)
+//   gamma_i = alpha_i + s (beta_i - alpha_i):  dL/dJ_{u_i} += (1 - gamma_i) dL/dc_i,  dL/dJ_{v_i} += gamma_i dL/dc_i  (same for j).
+// k_capsule_fwd: one wave per frame.  It reads the 24 G^t of the frame's FrameLds (as the closure's forward or k_pose_prep left
+// them), forms the <= 32 capsules' end points in LDS, evaluates the <= 256 pairs (pair k on lane k % 64, up to four per lane) and
+// parks the four end joints' shares of each pair's gradient -- (1 - gamma_i) dL/dc_i, gamma_i dL/dc_i, -(1 - gamma_j) dL/dc_i,
+// -gamma_j dL/dc_i -- in LDS.  The 72 (joint, component) outputs -- lanes 0..63, then lanes 0..7 once more -- are summed over the
+// joint's rows of the host-built CSR table, which lists (pair, end) in pair order and, inside a pair, in the order u_i, v_i, u_j,
+// v_j.  The frame's sum of pen^2: every lane adds its own pairs in order, then a fixed xor butterfly (32, 16, .. 1) adds the
+// lanes.  The table and the geometry are fetched into LDS once, beside G^t: one global round trip.  No atomics: bit-reproducible.
+// ----------------------------------------------------------------------------------------------------
+#define UUO_CAPS_MAXC 32
+#define UUO_CAPS_MAXP 256
+#define UUO_CAPS_TAB_PAIRS (UUO_CAPS_MAXC * 2)                       // cap_tab layout (ints): joints, pairs, CSR offsets, CSR entries
+#define UUO_CAPS_TAB_OFF (UUO_CAPS_TAB_PAIRS + UUO_CAPS_MAXP * 2)
+#define UUO_CAPS_TAB_ENT (UUO_CAPS_TAB_OFF + UUO_NUM_JOINTS + 1)
+#define UUO_CAPS_TAB_INTS (UUO_CAPS_TAB_ENT + UUO_CAPS_MAXP * 4)
+struct CapsFwdArgs {
+  uuo_gptr<const float> frames;  // [F][FrameLds]
+  uuo_gptr<const int> tab;       // the workspace's table (layout above)
+  uuo_gptr<const float> geom;    // [C][3] alpha, beta, radius
+  int C, P;
+  float cl, cg;                  // w / F, 2 w / F
+  uuo_gptr<float> up;            // [F][24][3] out
+  uuo_gptr<float> loss;          // [F] out
+};
+__device__ __forceinline__ float clamp01(float v) { return fminf(fmaxf(v, 0.f), 1.f); }
+// closest-point parameters of the segments p1 + s d1, p2 + t d2 (s, t in [0, 1]); r = p1 - p2
+struct CapsVec { float x, y, z; };
+__device__ __forceinline__ float caps_dot(CapsVec a, CapsVec b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+__device__ __forceinline__ float2 capsule_closest(CapsVec d1, CapsVec d2, CapsVec r) {
+  const float A = caps_dot(d1, d1), E = caps_dot(d2, d2);
+  const float fq = caps_dot(d2, r), cq = caps_dot(d1, r), bq = caps_dot(d1, d2);
+  const bool dA = A <= 1e-12f, dE = E <= 1e-12f;
+  if (dA && dE) return make_float2(0.f, 0.f);
+  if (dA) return make_float2(0.f, clamp01(fq / E));
+  if (dE) return make_float2(clamp01(-cq / A), 0.f);
+  const float den = A * E - bq * bq;
+  float s = (den > 1e-6f * (A * E)) ? clamp01((bq * fq - cq * E) / den) : 0.f;
+  float t = (bq * s + fq) / E;
+  if (t < 0.f) {
+    t = 0.f;
+    s = clamp01(-cq / A);
+  } else if (t > 1.f) {
+    t = 1.f;
+    s = clamp01((bq - cq) / A);
+  }
+  return make_float2(s, t);
+}
+__global__ __launch_bounds__(64) void k_capsule_fwd(CapsFwdArgs a) {
+  __shared__ float sG[UUO_NUM_JOINTS * 3];
+  __shared__ int sTab[UUO_CAPS_TAB_INTS];           // the workspace's table: one coalesced fetch, every lookup below is LDS
+  __shared__ float sGeom[UUO_CAPS_MAXC * 3];
+  __shared__ float sEnd[UUO_CAPS_MAXC][6];          // a, b of every capsule
+  __shared__ float sCon[UUO_CAPS_MAXP * 4][3];      // per (pair, end): that end joint's share of dL/dc, signed
+  const int f = blockIdx.x, lane = threadIdx.x;
+  const int C = min(a.C, UUO_CAPS_MAXC), P = min(a.P, UUO_CAPS_MAXP);  // (uuo_fit_set_capsules has checked them; keeps LDS in bounds)
+  {
+    constexpr int NW = sizeof(FrameLds) / 4, GT = offsetof(FrameLds, Gt) / 4;
+    for (int i = lane; i < UUO_NUM_JOINTS * 3; i += 64) sG[i] = a.frames[(size_t)f * NW + GT + i];
+    for (int i = lane; i < UUO_CAPS_TAB_INTS; i += 64) sTab[i] = a.tab[i];
+    for (int i = lane; i < UUO_CAPS_MAXC * 3; i += 64) sGeom[i] = a.geom[i];
+  }
+  __syncthreads();
+  if (lane < C) {
+    const int u = sTab[lane * 2] % UUO_NUM_JOINTS, v = sTab[lane * 2 + 1] % UUO_NUM_JOINTS;
+    const float al = sGeom[lane * 3], be = sGeom[lane * 3 + 1];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float ju = sG[u * 3 + c], e = sG[v * 3 + c] - ju;
+      sEnd[lane][c] = ju + al * e;
+      sEnd[lane][3 + c] = ju + be * e;
+    }
+  }
+  __syncthreads();
+  float part = 0.f;  // this lane's pen^2, pairs lane, lane + 64, ... in that order
+  for (int k = lane; k < P; k += 64) {
+    const int i = sTab[UUO_CAPS_TAB_PAIRS + k * 2] % UUO_CAPS_MAXC, j = sTab[UUO_CAPS_TAB_PAIRS + k * 2 + 1] % UUO_CAPS_MAXC;
+    const CapsVec p1 = {sEnd[i][0], sEnd[i][1], sEnd[i][2]}, p2 = {sEnd[j][0], sEnd[j][1], sEnd[j][2]};
+    const CapsVec d1 = {sEnd[i][3] - p1.x, sEnd[i][4] - p1.y, sEnd[i][5] - p1.z};
+    const CapsVec d2 = {sEnd[j][3] - p2.x, sEnd[j][4] - p2.y, sEnd[j][5] - p2.z};
+    const CapsVec r = {p1.x - p2.x, p1.y - p2.y, p1.z - p2.z};
+    const float2 st = capsule_closest(d1, d2, r);
+    const float s = st.x, t = st.y;
+    const CapsVec dl = {(p1.x + s * d1.x) - (p2.x + t * d2.x), (p1.y + s * d1.y) - (p2.y + t * d2.y), (p1.z + s * d1.z) - (p2.z + t * d2.z)};
+    const float d = sqrtf(caps_dot(dl, dl));
+    const float pen = fmaxf((sGeom[i * 3 + 2] + sGeom[j * 3 + 2]) - d, 0.f);
+    const float q = (d > 0.f) ? -(a.cg * pen) / d : 0.f;
+    const float g[3] = {q * dl.x, q * dl.y, q * dl.z};  // dL/dc_i = -dL/dc_j
+    const float ai = sGeom[i * 3], aj = sGeom[j * 3];
+    const float gi = ai + s * (sGeom[i * 3 + 1] - ai), gj = aj + t * (sGeom[j * 3 + 1] - aj);
+    const float co[4] = {1.f - gi, gi, 1.f - gj, gj};   // ends u_i, v_i, u_j, v_j
+#pragma unroll
+    for (int end = 0; end < 4; ++end)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) sCon[k * 4 + end][c] = co[end] * ((end & 2) ? -g[c] : g[c]);
+    part += pen * pen;
+  }
+  __syncthreads();
+  for (int o = lane; o < UUO_NUM_JOINTS * 3; o += 64) {
+    const int jj = o / 3, c = o - jj * 3;
+    const int e0 = max(sTab[UUO_CAPS_TAB_OFF + jj], 0), e1 = min(sTab[UUO_CAPS_TAB_OFF + jj + 1], 4 * P);
+    float acc = 0.f;
+    for (int e = e0; e < e1; e += 4) {  // four rows a step: the LDS reads overlap, the adds keep the rows' (= the pairs') order
+      float v[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int ent = (e + u < e1) ? sTab[UUO_CAPS_TAB_ENT + e + u] : -1;
+        v[u] = (ent >= 0) ? sCon[ent % (UUO_CAPS_MAXP * 4)][c] : 0.f;
+      }
+      acc = (((acc + v[0]) + v[1]) + v[2]) + v[3];
+    }
+    a.up[(size_t)f * 72 + o] = acc;
+  }
+  // the frame's share: the lanes' partial sums (each in pair order) through a fixed butterfly, lane l with lane l ^ 32, 16, .. 1
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) part += __shfl_xor(part, m, 64);
+  if (lane == 0) a.loss[f] = a.cl * part;
+}
+
+// ----------------------------------------------------------------------------------------------------
 // EXTENSION (not reference behaviour; uuo_fit_set_surface): the chamfer stage's data term as a point-to-surface distance
 // with a stand-off.  k_ring_pick (nn_kernels.hip) has chosen, for every (frame, marker), the face of the nearest vertex's
 // one-ring that lies closest in the search's vertex buffer; this pass is k_bary_fwd with those corners read per frame and the
@@ -1864,6 +2001,14 @@ static int validate_problem(const uuo_fit* fit, const uuo_problem_t* p) {
               "(w_soft)");
   UUO_REQUIRE(fit->floor_k == 0 || !uuo_recorder,
               "closure: lock-step batches do not carry the floor-contact term (uuo_fit_set_floor, extension)");
+  // EXTENSION: the self-penetration term of the workspace (uuo_fit_set_capsules) likewise
+  UUO_REQUIRE(fit->cap_w == 0.f || p->stage != UUO_STAGE_PART,
+              "closure: the self-penetration term (uuo_fit_set_capsules, extension) is not built for the part stage");
+  UUO_REQUIRE(fit->cap_w == 0.f || p->w_soft == 0.f,
+              "closure: the self-penetration term (uuo_fit_set_capsules, extension) is not built for the soft-assignment data "
+              "term (w_soft)");
+  UUO_REQUIRE(fit->cap_w == 0.f || !uuo_recorder,
+              "closure: lock-step batches do not carry the self-penetration term (uuo_fit_set_capsules, extension)");
   // EXTENSION: latent marker offsets
   UUO_REQUIRE(p->w_offsets == 0.f || (p->w_offsets > 0.f && p->w_offsets <= 3.0e38f),
               "closure: w_offsets (latent marker offsets, extension) must be 0 (off) or a positive finite weight");
@@ -1972,6 +2117,82 @@ extern "C" int uuo_fit_set_floor(uuo_fit_t* fit, float w_pen, float w_con, float
   fit->floor_kl = k_left;
   fit->floor_vids = d_vids;
   fit->floor_contacts = (w_con == 0.f) ? nullptr : d_contacts;
+  return 0;
+}
+
+extern "C" int uuo_fit_set_capsules(uuo_fit_t* fit, float w, int32_t n_caps, const int32_t* h_cap_joints, const float* h_cap_geom,
+                                    int32_t n_pairs, const int32_t* h_pairs) {
+  UUO_REQUIRE(fit, "uuo_fit_set_capsules: null fit");
+  UUO_REQUIRE(w == 0.f || (w > 0.f && w <= 3.0e38f), "uuo_fit_set_capsules: the weight must be 0 (off) or a positive finite number");
+  if (w == 0.f) {  // off: nothing else is looked at (the tables stay for the next call with the same lists)
+    fit->cap_w = 0.f;
+    return 0;
+  }
+  UUO_REQUIRE(n_caps >= 1 && n_caps <= UUO_CAPS_MAXC, "uuo_fit_set_capsules: 1 .. 32 capsules");
+  UUO_REQUIRE(n_pairs >= 1 && n_pairs <= UUO_CAPS_MAXP, "uuo_fit_set_capsules: 1 .. 256 pairs");
+  UUO_REQUIRE(h_cap_joints && h_cap_geom && h_pairs,
+              "uuo_fit_set_capsules: a positive weight needs the capsules' joints [C][2], geometry [C][3] and the pairs [P][2] (host arrays)");
+  UUO_REQUIRE(!uuo_recorder, "uuo_fit_set_capsules: lock-step batches do not carry the self-penetration term");
+  const int C = n_caps, P = n_pairs;
+  for (int c = 0; c < C; ++c) {
+    const int u = h_cap_joints[c * 2], v = h_cap_joints[c * 2 + 1];
+    UUO_REQUIRE(u >= 0 && u < UUO_NUM_JOINTS && v >= 0 && v < UUO_NUM_JOINTS, "uuo_fit_set_capsules: a capsule's joint id is outside [0, 24)");
+    UUO_REQUIRE(u != v, "uuo_fit_set_capsules: a capsule needs two different joints");
+    const float al = h_cap_geom[c * 3], be = h_cap_geom[c * 3 + 1], r = h_cap_geom[c * 3 + 2];
+    UUO_REQUIRE(al >= -3.0e38f && al <= 3.0e38f && be >= -3.0e38f && be <= 3.0e38f,
+                "uuo_fit_set_capsules: a capsule's alpha and beta must be finite");
+    UUO_REQUIRE(r > 0.f && r <= 3.0e38f, "uuo_fit_set_capsules: a capsule's radius must be a positive finite number of metres");
+  }
+  for (int k = 0; k < P; ++k) {
+    const int i = h_pairs[k * 2], j = h_pairs[k * 2 + 1];
+    UUO_REQUIRE(i >= 0 && i < C && j >= 0 && j < C, "uuo_fit_set_capsules: a pair's capsule index is outside [0, C)");
+    UUO_REQUIRE(i != j, "uuo_fit_set_capsules: a pair needs two different capsules");
+  }
+  if (!fit->cap_tab) {  // first use: the tables (ints, then the geometry) and the kernel's outputs
+    UUO_HIP_CHECK(hipMalloc((void**)&fit->cap_tab, UUO_CAPS_TAB_INTS * sizeof(int32_t) + UUO_CAPS_MAXC * 3 * sizeof(float)));
+    fit->cap_geom = reinterpret_cast<float*>(fit->cap_tab + UUO_CAPS_TAB_INTS);
+    fit->cap_c = fit->cap_p = 0;
+    UUO_HIP_CHECK(hipStreamCreateWithFlags(&fit->cap_stream, hipStreamNonBlocking));
+  }
+  if (!fit->cap_up) UUO_HIP_CHECK(hipMalloc((void**)&fit->cap_up, ((size_t)fit->F * 72 + fit->F) * sizeof(float)));
+  const bool same = fit->cap_c == C && fit->cap_p == P &&
+                    std::memcmp(fit->cap_h_joints, h_cap_joints, (size_t)C * 2 * sizeof(int32_t)) == 0 &&
+                    std::memcmp(fit->cap_h_geom, h_cap_geom, (size_t)C * 3 * sizeof(float)) == 0 &&
+                    std::memcmp(fit->cap_h_pairs, h_pairs, (size_t)P * 2 * sizeof(int32_t)) == 0;
+  if (!same) {
+    // the joint -> (pair, end) table, CSR: joint jj's rows list 4 k + end in pair order, inside a pair in the order
+    // u_i (end 0), v_i (1), u_j (2), v_j (3) -- the order in which k_capsule_fwd sums
+    static thread_local int32_t h_tab[UUO_CAPS_TAB_INTS];
+    std::memset(h_tab, 0, sizeof(h_tab));
+    std::memcpy(h_tab, h_cap_joints, (size_t)C * 2 * sizeof(int32_t));
+    std::memcpy(h_tab + UUO_CAPS_TAB_PAIRS, h_pairs, (size_t)P * 2 * sizeof(int32_t));
+    int n = 0;
+    for (int jj = 0; jj < UUO_NUM_JOINTS; ++jj) {
+      h_tab[UUO_CAPS_TAB_OFF + jj] = n;
+      for (int k = 0; k < P; ++k)
+        for (int end = 0; end < 4; ++end)
+          if (h_cap_joints[h_pairs[k * 2 + (end >> 1)] * 2 + (end & 1)] == jj) h_tab[UUO_CAPS_TAB_ENT + n++] = 4 * k + end;
+    }
+    h_tab[UUO_CAPS_TAB_OFF + UUO_NUM_JOINTS] = n;  // = 4 P
+    fit->cap_w = 0.f;
+    fit->cap_c = fit->cap_p = 0;
+    // the only reader of the old tables is the last k_capsule_fwd launched on this workspace: wait for its stream alone (no
+    // device-wide wait: other threads' workspaces keep running; nothing is added to an evaluation), upload on the workspace's
+    // own non-blocking stream, and return once the copies have landed, so that every later launch sees them
+    if (fit->cap_launched) UUO_HIP_CHECK(hipStreamSynchronize(fit->cap_last_stream));
+    fit->cap_launched = false;
+    UUO_HIP_CHECK(hipMemcpyAsync(fit->cap_tab, h_tab, sizeof(h_tab), hipMemcpyHostToDevice, fit->cap_stream));
+    float h_geom[UUO_CAPS_MAXC * 3] = {0.f};  // (the kernel fetches the whole table)
+    std::memcpy(h_geom, h_cap_geom, (size_t)C * 3 * sizeof(float));
+    UUO_HIP_CHECK(hipMemcpyAsync(fit->cap_geom, h_geom, sizeof(h_geom), hipMemcpyHostToDevice, fit->cap_stream));
+    UUO_HIP_CHECK(hipStreamSynchronize(fit->cap_stream));
+    std::memcpy(fit->cap_h_joints, h_cap_joints, (size_t)C * 2 * sizeof(int32_t));
+    std::memcpy(fit->cap_h_geom, h_cap_geom, (size_t)C * 3 * sizeof(float));
+    std::memcpy(fit->cap_h_pairs, h_pairs, (size_t)P * 2 * sizeof(int32_t));
+    fit->cap_c = C;
+    fit->cap_p = P;
+  }
+  fit->cap_w = w;
   return 0;
 }
 
@@ -2421,7 +2642,31 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
     b.loss = fit->floor_up + (size_t)F * UUO_FLOOR_MAXK * 3;
     hipLaunchKernelGGL(k_floor_fwd, dim3(F), dim3(64), 0, s, b);
   };
-  const bool temporal = accel || lock || floor;
+  // EXTENSION: the self-penetration term: k_capsule_fwd (launch_caps below, beside launch_floor) leaves d loss / d G_j^t and the
+  // frames' shares, the temporal instantiations add them to uj and slot 3 (cap_up != null).  Frames are not coupled: any F.
+  const bool caps = fit->cap_w != 0.f;
+  UUO_REQUIRE(!caps || !uuo_recorder, "closure: lock-step batches do not carry the self-penetration term");
+  if (caps) {
+    a.cap_up = fit->cap_up;
+    a.cap_loss = fit->cap_up + (size_t)F * 72;
+  }
+  auto launch_caps = [&]() {
+    if (!caps) return;
+    CapsFwdArgs b;
+    std::memset(&b, 0, sizeof(b));
+    b.frames = fit->frames;
+    b.tab = fit->cap_tab;
+    b.geom = fit->cap_geom;
+    b.C = fit->cap_c; b.P = fit->cap_p;
+    b.cl = (float)((double)fit->cap_w / (double)F);
+    b.cg = (float)(2.0 * (double)fit->cap_w / (double)F);
+    b.up = fit->cap_up;
+    b.loss = fit->cap_up + (size_t)F * 72;
+    hipLaunchKernelGGL(k_capsule_fwd, dim3(F), dim3(64), 0, s, b);
+    fit->cap_launched = true;  // (uuo_fit_set_capsules waits for this stream before it replaces the tables)
+    fit->cap_last_stream = s;
+  };
+  const bool temporal = accel || lock || floor || caps;
   a.h.gx = F;
   a.h.gy = 1;
   FinArgs fa;
@@ -2509,6 +2754,7 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
     else
       hipLaunchKernelGGL(k_bary_fwd, dim3(F), dim3(BWD_NW * 64), 0, s, b);
     launch_floor();
+    launch_caps();
     a.M = 3 * M;
     a.up_items = items;
     a.item_loss = item_loss;
@@ -2554,6 +2800,7 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
     b.bary = fit->surf_bary;
     hipLaunchKernelGGL(robust ? k_surf_fwd_r : k_surf_fwd, dim3(F), dim3(BWD_NW * 64), 0, s, b);
     launch_floor();
+    launch_caps();
     a.M = 3 * M;
     a.assign = fit->surf_corners;
     a.up_items = items;
@@ -2597,6 +2844,7 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
         if (rc) return rc;
         a.frames = fit->frames;
         launch_floor();
+        launch_caps();
         if (floor)
           hipLaunchKernelGGL(robust ? k_bwd_sparse_r_t_o_fl : k_bwd_sparse_t_o_fl, dim3(F), dim3(BWD_NW * 64), 0, s, a);
         else
@@ -2614,6 +2862,7 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
         a.frames = fit->frames;
       }
       launch_floor();
+      launch_caps();
       if (floor)
         hipLaunchKernelGGL(robust ? k_bwd_sparse_r_t_fl : k_bwd_sparse_t_fl, dim3(F), dim3(BWD_NW * 64), 0, s, a);
       else if (fassign)

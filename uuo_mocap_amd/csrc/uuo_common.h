@@ -208,6 +208,23 @@ struct uuo_fit {
   const int32_t* floor_vids = nullptr;
   const float* floor_contacts = nullptr;
   float* floor_up = nullptr;
+  // EXTENSION: the bone-capsule self-penetration term (uuo_fit_set_capsules; cap_w == 0 = off): weight, C capsules, P pairs, the
+  // host copies of the caller's lists (compared at the next call: unchanged lists are not uploaded again), the workspace's own
+  // device tables -- cap_tab: [32][2] joints, [256][2] pairs, [25] CSR offsets of the joint -> (pair, end) table, [1024] its
+  // entries 4 pair + end; cap_geom [32][3] -- and [F][72] upstream joint gradients + [F] loss shares (k_capsule_fwd -> the
+  // backward kernels)
+  float cap_w = 0.f;
+  int cap_c = 0, cap_p = 0;
+  int32_t cap_h_joints[64], cap_h_pairs[512];
+  float cap_h_geom[96];
+  int32_t* cap_tab = nullptr;
+  float* cap_geom = nullptr;
+  float* cap_up = nullptr;
+  // the stream of the last k_capsule_fwd launch on this workspace (the tables' only reader) and a private non-blocking stream
+  // for their upload: new lists wait for that stream alone, not for the device
+  bool cap_launched = false;
+  hipStream_t cap_last_stream = nullptr;
+  hipStream_t cap_stream = nullptr;
   int surface = 0;               // EXTENSION: point-to-surface chamfer term (uuo_fit_set_surface; 0 = off) and its stand-off
   float surface_distance = 0.f;
   const int32_t* frame_assign = nullptr;  // EXTENSION: [F][M] per-frame vertex table of the marker stage (uuo_fit_set_frame_assign;

@@ -19,7 +19,7 @@ import torch
 from . import _lib
 from ._lib import (EVAL_CALLBACK, UUO_STAGE_CHAMFER, UUO_STAGE_MARKER, UUO_STAGE_PART, UuoLbfgsOptions,
                    UuoLbfgsStats, UuoProblem, UuoReprojectionProblem, check)
-from .body_model import SmplTables
+from .body_model import CAPSULE_PAIRS_MAX, CAPSULES_MAX, SmplTables
 from .config import stage_surface
 
 MARKER_DISTANCE = 0.0095  # reference utils/settings.py:1
@@ -174,6 +174,9 @@ def solve_batch(problems, xs, max_iter: int, lr: float = 1.0, tolerance_grad: fl
     if any(getattr(p, "floor_on", False) for p in problems):
         raise NotImplementedError("lock-step batches do not carry the floor-contact term (floor_penetration / floor_contact, "
                                   "extension): solve such problems one by one")
+    if any(getattr(p, "capsules_on", False) for p in problems):
+        raise NotImplementedError("lock-step batches do not carry the self-penetration term (self_penetration, extension): "
+                                  "solve such problems one by one")
     if any(getattr(p, "frame_assign", None) is not None for p in problems):
         raise NotImplementedError("lock-step batches do not carry the per-frame vertex table (tracklets, extension): "
                                   "solve such problems one by one")
@@ -519,6 +522,36 @@ class _StageProblem:
         self.floor_kl = 0
         self.floor_kr = 0
         self.floor_contacts = None
+        # EXTENSION: the bone-capsule self-penetration term (ChamferProblem / MarkerProblem), armed the same way
+        # (uuo_fit_set_capsules): weight and the three HOST lists, which the library checks and copies at the call
+        self.cap_w = 0.0
+        self.cap_joints = None  # [C, 2] int32 numpy
+        self.cap_geom = None    # [C, 3] float32 numpy: alpha, beta, radius
+        self.cap_pairs = None   # [P, 2] int32 numpy
+
+    @property
+    def capsules_on(self) -> bool:
+        """EXTENSION: True when this problem arms the self-penetration term with a non-zero weight."""
+        return self.cap_w != 0.0
+
+    def _set_capsules(self, caps: Dict, smpl_inference):
+        """EXTENSION: `caps` is stage_capsules' record.  Keeps the weight and contiguous host copies of the capsule lists (the
+        configured ones, or body_model.body_capsules of `smpl_inference.tables`, looked at only when the term is on without
+        a `capsules` block).  With weight 0 nothing is armed and the problem runs the plain kernels, bit for bit."""
+        w = float(caps["w"])
+        if w == 0.0:
+            return
+        lists = caps["capsules"]
+        if lists is None:
+            from .body_model import body_capsules
+
+            lists = body_capsules(smpl_inference.tables)
+        else:
+            lists = (lists["joints"], lists["geom"], lists["pairs"])
+        self.cap_joints = np.ascontiguousarray(np.asarray(lists[0], dtype=np.int32).reshape(-1, 2))
+        self.cap_geom = np.ascontiguousarray(np.asarray(lists[1], dtype=np.float32).reshape(-1, 3))
+        self.cap_pairs = np.ascontiguousarray(np.asarray(lists[2], dtype=np.int32).reshape(-1, 2))
+        self.cap_w = w
 
     @property
     def floor_on(self) -> bool:
@@ -579,6 +612,13 @@ class _StageProblem:
         else:
             check(self.lib.uuo_fit_set_floor(self.fit, c_float(0.0), c_float(0.0), c_float(0.0), None, 0, 0, None),
                   "uuo_fit_set_floor")
+        if self.capsules_on:
+            check(self.lib.uuo_fit_set_capsules(self.fit, c_float(self.cap_w), int(self.cap_joints.shape[0]),
+                                                self.cap_joints.ctypes.data, self.cap_geom.ctypes.data,
+                                                int(self.cap_pairs.shape[0]), self.cap_pairs.ctypes.data),
+                  "uuo_fit_set_capsules")
+        else:
+            check(self.lib.uuo_fit_set_capsules(self.fit, c_float(0.0), 0, None, None, 0, None), "uuo_fit_set_capsules")
 
     def _need_workspace(self):
         if self.fit is None:  # created for a lock-step batch only: give it the thread's workspace on first standalone use
@@ -834,6 +874,47 @@ def stage_floor(config: Dict, stage: str) -> Dict:
     return out
 
 
+def stage_capsules(config: Dict, stage: str) -> Dict:
+    """EXTENSION: the bone-capsule self-penetration term of the chamfer or marker stage (uuo_fit_set_capsules) as a config
+    states it -- stages.<stage>.losses.self_penetration (a weight on m^2; absent or 0 = off; negative or non-finite weights are
+    refused) and stages.<stage>.capsules: null (body_model.body_capsules of the model) or {joints: [[u, v], ...] (two
+    different SMPL joints < 24), geom: [[alpha, beta, radius], ...] (finite, radius > 0), pairs: [[i, j], ...] (two different
+    capsule indices)} with 1 .. 32 capsules and 1 .. 256 pairs.  Returns {"w", "capsules"}.  (The part stage refuses the key
+    with its other unknown losses.)"""
+    st = config["stages"][stage]
+    losses = st.get("losses") or {}
+    v = losses.get("self_penetration", 0.0)
+    v = 0.0 if v is None else float(v)
+    if not math.isfinite(v) or v < 0.0:
+        raise ValueError("stages.%s.losses.self_penetration must be 0 (off) or a positive weight (got %r)" % (stage, v))
+    caps = st.get("capsules", None)
+    if caps is not None:
+        def rows(x, n):
+            return isinstance(x, (list, tuple)) and len(x) >= 1 and all(isinstance(r, (list, tuple)) and len(r) == n for r in x)
+
+        def ints(x):
+            return all(isinstance(q, int) and not isinstance(q, bool) for r in x for q in r)
+
+        ok = isinstance(caps, dict) and set(caps) == {"joints", "geom", "pairs"} and rows(caps["joints"], 2) and \
+            rows(caps["geom"], 3) and rows(caps["pairs"], 2) and len(caps["joints"]) == len(caps["geom"]) and \
+            len(caps["joints"]) <= CAPSULES_MAX and len(caps["pairs"]) <= CAPSULE_PAIRS_MAX and ints(caps["joints"]) and \
+            ints(caps["pairs"])
+        if ok:
+            C = len(caps["joints"])
+            ok = all(0 <= u < 24 and 0 <= w < 24 and u != w for u, w in caps["joints"]) and \
+                all(0 <= i < C and 0 <= j < C and i != j for i, j in caps["pairs"]) and \
+                all(isinstance(q, (int, float)) and not isinstance(q, bool) and math.isfinite(q) for r in caps["geom"] for q in r) and \
+                all(r[2] > 0 for r in caps["geom"])
+        if not ok:
+            raise ValueError("stages.%s.capsules must be null or {joints: [[u, v], ...], geom: [[alpha, beta, radius], ...], "
+                             "pairs: [[i, j], ...]} with 1 .. %d capsules on two different joints < 24, finite geometry with "
+                             "radius > 0, and 1 .. %d pairs of two different capsule indices (got %r)"
+                             % (stage, CAPSULES_MAX, CAPSULE_PAIRS_MAX, caps))
+        caps = {"joints": [list(r) for r in caps["joints"]], "geom": [[float(q) for q in r] for r in caps["geom"]],
+                "pairs": [list(r) for r in caps["pairs"]]}
+    return {"w": v, "capsules": caps}
+
+
 def check_foot_contacts(foot_contacts, num_frames=None):
     """EXTENSION: the foot-lock term's contact labels as a float32 host tensor [F, 2] (left, right foot; None stays None).
     Shape, finiteness and the range [0, 1] are checked on the host: ValueError before anything touches the device."""
@@ -860,10 +941,14 @@ class ChamferProblem(_StageProblem):
     def __init__(self, smpl_inference, markers, o_pose_body, o_betas, root_orient, config, foot_contacts=None):
         losses = config["stages"]["chamfer"]["losses"]
         unsupported = set(losses) - {"full_chamfer", "reg_pose_body", "reg_betas", "soft_chamfer", "joint_accel", "foot_lock",
-                                     "surface_chamfer", "floor_penetration", "floor_contact"}
+                                     "surface_chamfer", "floor_penetration", "floor_contact", "self_penetration"}
         if unsupported:
             raise NotImplementedError("chamfer-stage losses outside the shipped configs: %s" % sorted(unsupported))
         w_surface, d_surface = stage_surface(config)  # EXTENSION: point-to-surface data term (0 = off)
+        caps = stage_capsules(config, "chamfer")  # EXTENSION: bone-capsule self-penetration term (0 = off)
+        if caps["w"] > 0.0 and float(losses.get("soft_chamfer", 0.0)) != 0.0:
+            raise NotImplementedError("stages.chamfer: the fused self-penetration term (self_penetration) is not built for the "
+                                      "soft-assignment closure; optim_chamfer composes that combination from the operators")
         w_accel = stage_joint_accel(config, "chamfer")
         if w_accel > 0.0 and float(losses.get("soft_chamfer", 0.0)) != 0.0:
             raise NotImplementedError("stages.chamfer: the fused joint-acceleration term (joint_accel) is not built for the "
@@ -891,6 +976,7 @@ class ChamferProblem(_StageProblem):
         self.joint_accel = w_accel  # EXTENSION: joint-acceleration term (0 = off)
         self._set_foot_lock(w_lock, contacts)  # EXTENSION: foot-lock term (weight 0 without gated contacts)
         self._set_floor(floor, contacts, smpl_inference)  # EXTENSION: floor-contact term on sole vertices
+        self._set_capsules(caps, smpl_inference)  # EXTENSION: bone-capsule self-penetration term
         # EXTENSION (not in the reference): soft assignment of every marker to the body's vertices, fused closure with the dense
         # backward on the matrix pipe (csrc/dense_bwd.hip); not available inside lock-step batches
         w_soft = float(losses.get("soft_chamfer", 0.0))
@@ -934,12 +1020,13 @@ class MarkerProblem(_StageProblem):
         an entry < 0 is an item of weight 0); `assign` may then be None.  Refused with `bary` and with latent_offsets."""
         st = config["stages"]["marker"]
         unsupported = set(st["losses"]) - {"marker", "reg_pose_body", "reg_betas", "joint_accel", "latent_offsets", "foot_lock",
-                                           "floor_penetration", "floor_contact"}
+                                           "floor_penetration", "floor_contact", "self_penetration"}
         if unsupported:
             raise NotImplementedError("marker-stage losses outside the shipped configs: %s" % sorted(unsupported))
         if st.get("use_sdf"):
             raise NotImplementedError("stages.marker.use_sdf is off in every shipped config")
         floor = stage_floor(config, "marker")
+        caps = stage_capsules(config, "marker")  # EXTENSION: bone-capsule self-penetration term (0 = off)
         if frame_assign is not None and (floor["w_pen"] > 0.0 or floor["w_con"] > 0.0):
             raise NotImplementedError("the per-frame vertex table (tracklets, extension) is not built for the floor-contact term "
                                       "(stages.marker.losses.floor_penetration / floor_contact)")
@@ -968,6 +1055,7 @@ class MarkerProblem(_StageProblem):
         self.joint_accel = w_accel  # EXTENSION: joint-acceleration term (0 = off)
         self._set_foot_lock(w_lock, contacts)  # EXTENSION: foot-lock term (weight 0 without gated contacts)
         self._set_floor(floor, contacts, smpl_inference)  # EXTENSION: floor-contact term on sole vertices
+        self._set_capsules(caps, smpl_inference)  # EXTENSION: bone-capsule self-penetration term
         if frame_assign is not None:  # EXTENSION: per-frame vertex table (the *_f kernel instantiations)
             self.frame_assign = frame_assign.to(device=self.device, dtype=torch.int32).contiguous()
         if w_offsets > 0.0:  # EXTENSION: latent per-marker offsets, 3 M more parameters after trans

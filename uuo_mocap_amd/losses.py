@@ -2,6 +2,7 @@
 losses/losses.py:43-51)."""
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -273,3 +274,52 @@ def floor_loss(vertices: torch.Tensor, vids, k_left: int, contacts, height: floa
             flo = torch.relu(torch.sum(torch.where(first, zs, torch.zeros_like(zs)), dim=1) - float(height))
             loss = loss + float(w_con) * torch.sum(contacts[:, s] * flo * flo) / (2.0 * z.shape[0])
     return loss
+
+
+def capsule_closest_params(a1: torch.Tensor, b1: torch.Tensor, a2: torch.Tensor, b2: torch.Tensor):
+    """EXTENSION: closest-point parameters (s, t) in [0, 1] of the segments [a1, b1] and [a2, b2] ([..., 3]) in the tensors' own
+    precision -- the routine of the self-penetration term (uuo_fit_set_capsules; Ericson, Real-Time Collision Detection 5.1.9),
+    branch for branch: a segment with |b - a|^2 <= 1e-12 is a point, den = A E - b^2 <= 1e-6 A E is parallel and takes s = 0."""
+    d1, d2, r = b1 - a1, b2 - a2, a1 - a2
+    A, E = (d1 * d1).sum(-1), (d2 * d2).sum(-1)
+    f, c, b = (d2 * r).sum(-1), (d1 * r).sum(-1), (d1 * d2).sum(-1)
+    dA, dE = A <= 1e-12, E <= 1e-12
+    zero = torch.zeros_like(A)
+    one = torch.ones_like(A)
+    As, Es = torch.where(dA, one, A), torch.where(dE, one, E)  # (the degenerate branches never use the quotient)
+    den = A * E - b * b
+    ok = den > 1e-6 * (A * E)
+    s = torch.where(ok, ((b * f - c * E) / torch.where(ok, den, one)).clamp(0.0, 1.0), zero)
+    t = (b * s + f) / Es
+    s = torch.where(t < 0.0, (-c / As).clamp(0.0, 1.0), torch.where(t > 1.0, ((b - c) / As).clamp(0.0, 1.0), s))
+    t = t.clamp(0.0, 1.0)
+    s = torch.where(dE, (-c / As).clamp(0.0, 1.0), s)
+    t = torch.where(dE, zero, t)
+    t = torch.where(dA, (f / Es).clamp(0.0, 1.0), t)
+    s = torch.where(dA, zero, s)
+    t = torch.where(dA & dE, zero, t)
+    return s, t
+
+
+def self_penetration_loss(joints: torch.Tensor, cap_joints, cap_geom, pairs, w: float) -> torch.Tensor:
+    """EXTENSION (not in the reference): the bone-capsule self-penetration term of the fused chamfer and marker closures
+    (uuo_fit_set_capsules), composed -- their checker.  joints [F, 24, 3] (the kinematic joints; the term is translation
+    invariant), cap_joints [C, 2], cap_geom [C, 3] (alpha, beta, radius), pairs [P, 2]:  w sum_t sum_k max(r_i + r_j - d, 0)^2 / F
+    with d the distance of the pair's segments.  The closest-point parameters are found under no_grad and held fixed (envelope
+    theorem); the distance and the hinge are under autograd.  d = 0 gives no gradient, and pen^2 still counts."""
+    dev = joints.device
+    cj = torch.as_tensor(np.asarray(cap_joints), dtype=torch.long, device=dev).reshape(-1, 2)
+    cg = torch.as_tensor(np.asarray(cap_geom), dtype=joints.dtype, device=dev).reshape(-1, 3)
+    pr = torch.as_tensor(np.asarray(pairs), dtype=torch.long, device=dev).reshape(-1, 2)
+    ju, jv = joints[:, cj[:, 0]], joints[:, cj[:, 1]]
+    a = ju + cg[None, :, 0:1] * (jv - ju)
+    b = ju + cg[None, :, 1:2] * (jv - ju)
+    a1, b1, a2, b2 = a[:, pr[:, 0]], b[:, pr[:, 0]], a[:, pr[:, 1]], b[:, pr[:, 1]]
+    with torch.no_grad():
+        s, t = capsule_closest_params(a1, b1, a2, b2)
+    delta = (a1 + s[..., None] * (b1 - a1)) - (a2 + t[..., None] * (b2 - a2))
+    d2 = (delta * delta).sum(-1)
+    pos = d2 > 0.0
+    d = torch.where(pos, torch.sqrt(torch.where(pos, d2, torch.ones_like(d2))), torch.zeros_like(d2))
+    pen = torch.relu(cg[pr[:, 0], 2] + cg[pr[:, 1], 2] - d)
+    return float(w) * (pen * pen).sum() / joints.shape[0]

@@ -94,6 +94,21 @@ def compute_floor_error(sole_z: torch.Tensor, k_left: int, contacts: torch.Tenso
             "float_mm": float(flo[gate].mean()) * 1e3 if bool(gate.any()) else 0.0}
 
 
+def compute_self_penetration(joints: torch.Tensor, cap_joints, cap_geom, pairs) -> Dict[str, float]:
+    """Self-penetration (not a metric of the reference) of joints [F, >= 24, 3] under the capsule set of the self-penetration
+    term (cap_joints [C, 2], cap_geom [C, 3], pairs [P, 2]; body_model.body_capsules builds the default), float64, in
+    millimetres for joints in metres: `max_depth_mm` the deepest overlap max(r_i + r_j - d, 0) of any pair in any frame,
+    `mean_depth_mm` the mean over frames of the frame's deepest pair, `frames_pct` the share of frames with any overlap."""
+    from .body_model import capsule_pair_depths
+
+    if joints.dim() != 3 or joints.shape[1] < 24 or joints.shape[2] != 3:
+        raise ValueError("compute_self_penetration: joints [F, >= 24, 3] expected (got %s)" % (tuple(joints.shape),))
+    pen = capsule_pair_depths(joints.detach().cpu().double().numpy(), cap_joints, cap_geom, pairs)
+    deepest = pen.max(axis=1)
+    return {"max_depth_mm": float(deepest.max()) * 1e3, "mean_depth_mm": float(deepest.mean()) * 1e3,
+            "frames_pct": 100.0 * float((deepest > 0.0).mean())}
+
+
 def compute_PA_MPJPE(pred_joints: torch.Tensor, gt_joints: torch.Tensor) -> torch.Tensor:
     return compute_MPJPE(compute_similarity_transform(pred_joints, gt_joints), gt_joints)
 

@@ -13,9 +13,10 @@ import torch.nn.functional as F
 
 from .device_lbfgs import DeviceLBFGS
 from .config import stage_surface
-from .engine import (MARKER_DISTANCE, ChamferProblem, MarkerProblem, check_foot_contacts, stage_floor, stage_foot_lock,
+from .engine import (MARKER_DISTANCE, ChamferProblem, MarkerProblem, check_foot_contacts, stage_capsules, stage_floor, stage_foot_lock,
                      stage_joint_accel, stage_latent_offsets, stage_robust_sigma)
 from .losses import (MarkerLoss, RobustMarkerLoss, chamfer_distance, floor_loss, foot_lock_loss, joint_accel_loss,  # noqa: F401  (re-exported)
+                     self_penetration_loss,
                      robust_weighted_chamfer_distance, soft_weighted_chamfer_distance, surface_chamfer_distance,
                      weighted_chamfer_distance)
 from .smpl import SmplInference
@@ -73,9 +74,9 @@ def optim_chamfer(
         # execution.chamfer_soft_fused: False keeps the operator-composed closure, its checker
         fused_losses = _CHAMFER_FUSED_LOSSES | {"soft_chamfer"}
     if "soft_chamfer" in fused_losses and (stage_joint_accel(config, "chamfer") > 0.0 or stage_foot_lock(config, "chamfer") > 0.0 or
-                                           _floor_on(config, "chamfer")):
-        # EXTENSION: the temporal terms and the floor-contact term have no instantiation of the dense backward (k_bwd_dense):
-        # composed closure
+                                           _floor_on(config, "chamfer") or _capsules_on(config, "chamfer")):
+        # EXTENSION: the temporal terms, the floor-contact term and the self-penetration term have no instantiation of the dense
+        # backward (k_bwd_dense): composed closure
         fused_losses = _CHAMFER_FUSED_LOSSES
     w_surface, _ = stage_surface(config)  # EXTENSION: point-to-surface data term (validates the keys)
     if w_surface > 0.0:
@@ -90,7 +91,8 @@ def optim_chamfer(
         # operator-composed closure, its checker.  (Weight 0 is the key absent.)
         fused_losses = fused_losses | {"surface_chamfer"}
     if (set(st["losses"]) - fused_losses) or not st["yaw_lock"] or not _robust_fused(config, "chamfer") or \
-            not _temporal_fused(config, "chamfer") or not _floor_fused(config, "chamfer"):
+            not _temporal_fused(config, "chamfer") or not _floor_fused(config, "chamfer") or \
+            not _capsule_fused(config, "chamfer"):
         return _optim_chamfer_general(markers, pose_body, o_pose_body, betas, o_betas, root_orient, trans, marker_labels,
                                       smpl_inference, config, initial_angle, repeat, verbose, iter_fn, foot_contacts)
     from .parallel import frame_shard
@@ -241,6 +243,34 @@ def _composed_floor(config: Dict, stage: str, contacts, smpl_inference):
     return lambda vertices: floor_loss(vertices, vids, k_left, contacts, fl["height"], w_pen, w_con)
 
 
+def _capsules_on(config: Dict, stage: str) -> bool:
+    """True when the stage's EXTENSION self-penetration term has a non-zero weight (stages.<stage>.losses.self_penetration;
+    validates the keys)."""
+    return stage_capsules(config, stage)["w"] > 0.0
+
+
+def _capsule_fused(config: Dict, stage: str) -> bool:
+    """False when the stage's EXTENSION self-penetration term is to run on the closure composed from the operators
+    (execution.capsule_fused: False, the fused closures' checker); True otherwise."""
+    return not _capsules_on(config, stage) or bool((config.get("execution") or {}).get("capsule_fused", True))
+
+
+def _composed_capsules(config: Dict, stage: str, smpl_inference):
+    """The self-penetration term of the composed closures: None when off, else a function of the joints [F, >= 24, 3] --
+    self_penetration_loss on the configured capsules (body_model.body_capsules by default)."""
+    caps = stage_capsules(config, stage)
+    if caps["w"] == 0.0:
+        return None
+    lists = caps["capsules"]
+    if lists is None:
+        from .body_model import body_capsules
+
+        cj, cg, pr = body_capsules(smpl_inference.tables)
+    else:
+        cj, cg, pr = lists["joints"], lists["geom"], lists["pairs"]
+    return lambda joints: self_penetration_loss(joints[:, :24], cj, cg, pr, caps["w"])
+
+
 def _refuse_latent_offsets(config: Dict, route: str):
     if stage_latent_offsets(config) > 0.0:
         raise NotImplementedError("stages.marker.losses.latent_offsets (latent marker offsets, extension) is built for the fused "
@@ -257,6 +287,9 @@ def _refuse_sharded_joint_accel(config: Dict, stage: str):
     if _floor_on(config, stage):
         raise NotImplementedError("stages.%s.losses.floor_penetration / floor_contact (extension): the floor-contact term is not "
                                   "built for frame-block sharding (parallel.shard_frames)" % stage)
+    if _capsules_on(config, stage):
+        raise NotImplementedError("stages.%s.losses.self_penetration (extension): the self-penetration term is not built for "
+                                  "frame-block sharding (parallel.shard_frames)" % stage)
 
 
 def lockstep_supported(config: Dict, stage: str) -> bool:
@@ -273,6 +306,8 @@ def lockstep_supported(config: Dict, stage: str) -> bool:
         return False
     if _floor_on(config, stage) or not _floor_fused(config, stage):  # EXTENSION: nor the floor-contact term
         return False
+    if _capsules_on(config, stage):  # EXTENSION: nor the self-penetration term
+        return False
     if stage == "marker" and stage_latent_offsets(config) > 0.0:  # EXTENSION: nor the latent marker offsets
         return False
     if stage == "chamfer" and stage_surface(config)[0] > 0.0:  # EXTENSION: nor the point-to-surface chamfer term
@@ -282,7 +317,7 @@ def lockstep_supported(config: Dict, stage: str) -> bool:
     if stage == "chamfer":
         return not (set(st["losses"]) - _CHAMFER_FUSED_LOSSES - {"surface_chamfer"}) and bool(st["yaw_lock"])
     return not (set(st["losses"]) - {"marker", "reg_pose_body", "reg_betas", "joint_accel", "latent_offsets", "foot_lock",
-                                     "floor_penetration", "floor_contact"}) and not st.get("use_sdf")
+                                     "floor_penetration", "floor_contact", "self_penetration"}) and not st.get("use_sdf")
 
 
 def optim_chamfer_lockstep(markers, hyps, o_pose_body, o_betas, smpl_inference, config):
@@ -383,7 +418,7 @@ def _solve(prob, x, config, stage: str, lr: float, verbose_tag: str, verbose: bo
 
 #: chamfer-stage loss terms the device solver fuses (the only ones the shipped configs enable)
 _CHAMFER_FUSED_LOSSES = {"full_chamfer", "reg_pose_body", "reg_betas", "joint_accel", "foot_lock", "floor_penetration",
-                         "floor_contact"}
+                         "floor_contact", "self_penetration"}
 
 
 def _optim_chamfer_general(markers, pose_body, o_pose_body, betas, o_betas, root_orient, trans, marker_labels,
@@ -408,6 +443,7 @@ def _optim_chamfer_general(markers, pose_body, o_pose_body, betas, o_betas, root
     if contacts is not None:
         contacts = contacts.to(device)
     floor_term = _composed_floor(config, "chamfer", contacts, smpl_inference)  # EXTENSION: floor-contact term on sole vertices
+    caps_term = _composed_capsules(config, "chamfer", smpl_inference)  # EXTENSION: bone-capsule self-penetration term
     num_frames = pose_body.shape[0]
     root_fixed = root_orient.detach().clone()
     if st["yaw_lock"]:
@@ -460,6 +496,8 @@ def _optim_chamfer_general(markers, pose_body, o_pose_body, betas, o_betas, root
             loss = loss + foot_lock_loss(out["joints"][:, :24], contacts) * w_lock
         if floor_term is not None:  # EXTENSION: the fused closures' floor-contact term, composed (their checker)
             loss = loss + floor_term(out["vertices"])
+        if caps_term is not None:  # EXTENSION: the fused closures' self-penetration term, composed (their checker)
+            loss = loss + caps_term(out["joints"])
         loss.backward()
         if verbose:
             print("Chamfer", n_eval[0], float(loss))
@@ -529,8 +567,10 @@ def optim_markers(
     fs = frame_shard()
     sharded = fs is not None and fs.active
     bary = None
-    if not _robust_fused(config, "marker") or not _temporal_fused(config, "marker") or not _floor_fused(config, "marker"):
-        # EXTENSION: execution.robust_fused / temporal_fused / floor_fused: False -- the composed closure, the fused one's checker
+    if not _robust_fused(config, "marker") or not _temporal_fused(config, "marker") or not _floor_fused(config, "marker") or \
+            not _capsule_fused(config, "marker"):
+        # EXTENSION: execution.robust_fused / temporal_fused / floor_fused / capsule_fused: False -- the composed closure, the
+        # fused one's checker
         return _optim_markers_general(markers, pose_body, o_pose_body, betas, o_betas, root_orient, trans, one_hot,
                                       smpl_inference, config, verbose, iter_fn, initial_angle, repeat, foot_contacts)
     if not bool(((rows_nz == 1) & (one_hot.sum(dim=1) == 1.0)).all()):
@@ -587,9 +627,9 @@ def _optim_markers_frame_assign(markers, pose_body, o_pose_body, betas, o_betas,
     if _floor_on(config, "marker"):
         raise NotImplementedError("%s is not built for the floor-contact term (stages.marker.losses.floor_penetration / "
                                   "floor_contact)" % what)
-    if not _robust_fused(config, "marker") or not _temporal_fused(config, "marker"):
+    if not _robust_fused(config, "marker") or not _temporal_fused(config, "marker") or not _capsule_fused(config, "marker"):
         raise NotImplementedError("%s is built for the fused marker closure only, not for the closure composed from the operators "
-                                  "(execution.robust_fused / temporal_fused: False)" % what)
+                                  "(execution.robust_fused / temporal_fused / capsule_fused: False)" % what)
     _refuse_latent_offsets(config, what + ": an offset per column has no meaning once the column changes identity")
     fs = frame_shard()
     if fs is not None and fs.active:
@@ -629,7 +669,7 @@ def _optim_markers_general(markers, pose_body, o_pose_body, betas, o_betas, root
                            "execution.robust_fused / temporal_fused / marker_bary_fused: False)")
     st = config["stages"]["marker"]
     unsupported = set(st["losses"]) - {"marker", "reg_pose_body", "reg_betas", "joint_accel", "latent_offsets", "foot_lock",
-                                       "floor_penetration", "floor_contact"}
+                                       "floor_penetration", "floor_contact", "self_penetration"}
     if unsupported:
         raise NotImplementedError("marker-stage losses outside the shipped configs: %s" % sorted(unsupported))
     if st.get("use_sdf"):
@@ -641,6 +681,7 @@ def _optim_markers_general(markers, pose_body, o_pose_body, betas, o_betas, root
     if contacts is not None:
         contacts = contacts.to(pose_body.device)
     floor_term = _composed_floor(config, "marker", contacts, smpl_inference)  # EXTENSION: floor-contact term on sole vertices
+    caps_term = _composed_capsules(config, "marker", smpl_inference)  # EXTENSION: bone-capsule self-penetration term
     num_frames = pose_body.shape[0]
     leaves = [pose_body, betas, root_orient, trans]
     params = [p.detach().clone().requires_grad_(True) for p in leaves]
@@ -675,6 +716,8 @@ def _optim_markers_general(markers, pose_body, o_pose_body, betas, o_betas, root
             loss = loss + foot_lock_loss(out["joints"][:, :24], contacts) * w_lock
         if floor_term is not None:  # EXTENSION: the fused closures' floor-contact term, composed (their checker)
             loss = loss + floor_term(out["vertices"])
+        if caps_term is not None:  # EXTENSION: the fused closures' self-penetration term, composed (their checker)
+            loss = loss + caps_term(out["joints"])
         loss.backward()
         if verbose:
             print("Marker", n_eval[0], float(loss))

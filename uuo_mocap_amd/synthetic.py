@@ -58,6 +58,87 @@ def lbs_f64(tables: SmplTables, rot: np.ndarray, betas: np.ndarray, trans: np.nd
     return verts, G_t + trans[:, None, :], T_R
 
 
+def rest_joints_f64(tables: SmplTables, betas: np.ndarray) -> np.ndarray:
+    """Rest joints [24,3] of the shape `betas` [10], float64."""
+    Jr = tables.J_regressor.astype(np.float64)
+    v = tables.v_template.astype(np.float64) + tables.shapedirs.astype(np.float64) @ np.asarray(betas, dtype=np.float64).reshape(10)
+    return Jr @ v
+
+
+def fk_joints_f64(tables: SmplTables, rot: np.ndarray, rest: np.ndarray):
+    """The kinematic chain of lbs_f64 alone on rest joints `rest` [24,3] (rest_joints_f64): joints [F,24,3] at zero translation
+    and world rotations [F,24,3,3]."""
+    F = rot.shape[0]
+    J = np.broadcast_to(rest[None], (F, NUM_JOINTS, 3))
+    G_R = np.zeros((F, NUM_JOINTS, 3, 3))
+    G_t = np.zeros((F, NUM_JOINTS, 3))
+    G_R[:, 0] = rot[:, 0]
+    G_t[:, 0] = J[:, 0]
+    for j in range(1, NUM_JOINTS):
+        p = tables.parents[j]
+        G_R[:, j] = G_R[:, p] @ rot[:, j]
+        G_t[:, j] = np.einsum("fab,fb->fa", G_R[:, p], J[:, j] - J[:, p]) + G_t[:, p]
+    return G_t, G_R
+
+
+#: the self-penetration capture (make_sequence(self_penetration=True)): window length, depth of the HMR start's overlap, taper
+PENETRATION_WINDOW, PENETRATION_DEPTH, PENETRATION_TAPER = 24, 0.030, 2
+
+
+def _arm_into_torso(tables, hmr_rot, rest, caps, t0):
+    """The HMR stand-in's left shoulder (joint 16) in frames t0 .. t0 + 23, rotated in the world frame about the axis
+    (arm direction) x (direction from the shoulder to the spine line, pelvis -> neck) by the angle at which the deepest overlap of
+    the left arm's capsules (joints 16, 18, 20, 22) with the trunk's (joints 0, 3, 6, 9, 12) -- over the pairs of the default list,
+    on the rest joints `rest` -- is PENETRATION_DEPTH; the angle is the first crossing on a grid of pi / 64, refined by 40 bisections, and tapered
+    (1/3, 2/3) over two frames at each end.  Returns the changed copy of hmr_rot and the indices of the arm / trunk pairs."""
+    from .body_model import capsule_pair_depths
+
+    cj, cg, pr = caps
+    arm = np.isin(cj, [16, 18, 20, 22]).all(axis=1)
+    trunk = np.isin(cj, [0, 3, 6, 9, 12]).all(axis=1)
+    sel = np.array([k for k, (i, j) in enumerate(pr) if (arm[i] and trunk[j]) or (arm[j] and trunk[i])], dtype=np.int64)
+    if len(sel) == 0:
+        raise ValueError("make_sequence: the default capsule list has no arm / trunk pair")
+    out = hmr_rot.copy()
+    n = PENETRATION_WINDOW
+    for i in range(n):
+        f = t0 + i
+        rot_f = hmr_rot[f:f + 1]
+        J, G = fk_joints_f64(tables, rot_f, rest)
+        d_arm = J[0, 18] - J[0, 16]
+        d_arm /= np.linalg.norm(d_arm)
+        e = J[0, 12] - J[0, 0]
+        foot = J[0, 0] + ((J[0, 16] - J[0, 0]) @ e) / (e @ e) * e
+        axis = np.cross(d_arm, foot - J[0, 16])
+        axis /= np.linalg.norm(axis)
+        G13 = G[0, 13]
+
+        def posed(theta):
+            r = rot_f.copy()
+            r[0, 16] = G13.T @ _rodrigues(theta * axis) @ G13 @ rot_f[0, 16]
+            return r
+
+        def depth(theta):
+            return capsule_pair_depths(fk_joints_f64(tables, posed(theta), rest)[0], cj, cg, pr[sel]).max()
+
+        grid = np.linspace(0.0, np.pi, 65)
+        hi = next((th for th in grid[1:] if depth(th) >= PENETRATION_DEPTH), None)
+        if hi is None:
+            raise ValueError("make_sequence: frame %d: no shoulder angle puts the left arm %.0f mm into the trunk"
+                             % (f, 1e3 * PENETRATION_DEPTH))
+        lo = hi - np.pi / 64.0
+        for _ in range(40):
+            mid = 0.5 * (lo + hi)
+            if depth(mid) >= PENETRATION_DEPTH:
+                hi = mid
+            else:
+                lo = mid
+        edge = min(i, n - 1 - i)
+        taper = 1.0 if edge >= PENETRATION_TAPER else (edge + 1.0) / (PENETRATION_TAPER + 1.0)
+        out[f, 16] = posed(taper * hi)[0, 16]
+    return out, sel
+
+
 def farthest_point_vertices(points: np.ndarray, count: int, start: int = 0) -> np.ndarray:
     chosen = [int(start)]
     d = np.linalg.norm(points - points[start], axis=1)
@@ -114,7 +195,8 @@ def make_sequence(tables: SmplTables, seed: int = 0, num_frames: int = 300, num_
                   limb_only: bool = False, yaw_offset_deg: float = 100.0, dropout: float = 0.02,
                   hmr_pose_noise: float = 0.1, hmr_beta_noise: float = 0.5, subject_seed: int = None,
                   standoff_tilt_deg: float = 0.0, standoff_mm=(9.5, 9.5), planted_feet: bool = False,
-                  stance_frames: int = 20, identity_events: int = 0, floor: bool = False) -> SyntheticSequence:
+                  stance_frames: int = 20, identity_events: int = 0, floor: bool = False,
+                  self_penetration: bool = False) -> SyntheticSequence:
     """One synthetic sequence: smooth GT motion, unlabeled-but-tracked markers 9.5 mm off the
     surface with 1 mm noise and block dropout, and an HMR stand-in (noisy pose/shape, wrong yaw).  `subject_seed` fixes the
     ground-truth shape independently of `seed`: sequences of ONE subject (the shared-betas extension fits them together).
@@ -134,6 +216,13 @@ def make_sequence(tables: SmplTables, seed: int = 0, num_frames: int = 300, num_
     foot AND its lowest sole point is within 5 mm of the floor; img_smpl.foot_contacts is that array eroded by two frames at each
     end of every run.  gt["sole_vids"] [2, 3] are the points, gt["floor_height"] = 0.0, gt["sole_z"] [F, 6] their float64
     heights (left foot first).  No hash stream is consumed; without the option every array is what it was.
+    A capture whose video start penetrates itself (EXTENSION tests of the self-penetration term): `self_penetration` picks a
+    window of 24 frames -- the first run starting at or after F / 10 in which the ground truth has zero overlap in every pair of
+    body_model.body_capsules (float64; ValueError if there is none) --, rotates the HMR stand-in's left shoulder there until the
+    arm's capsules sit 30 mm inside the trunk's (_arm_into_torso; the angle tapered over two frames at each end), and blanks
+    (exact zeros) every marker column owned by joints 16, 18, 20, 22 in the window.  gt["capsules"] is the capsule list,
+    gt["penetration_window"] = (first frame, one past the last), gt["hmr_overlap"] [F] the HMR start's deepest arm / trunk overlap
+    per frame (metres, at its mean betas).  No hash stream is consumed; without the option every array is what it was.
     A capture whose columns change identity (EXTENSION tests of the tracklet placement): `identity_events` events, each at a
     frame t_e in [F/10, 9F/10) and on three columns visible at t_e whose mutual distances there are >= 0.2 m (frame and columns
     from the event's own hash stream, drawn again until they qualify).  From t_e on the contents of the three columns are
@@ -284,6 +373,24 @@ def make_sequence(tables: SmplTables, seed: int = 0, num_frames: int = 300, num_
     hmr_betas = beta_gt + hmr_beta_noise * hash_normal(s + 13, F, 10)
     hmr_trans = trans + 0.05 * hash_normal(s + 14, F, 3)
 
+    caps = window = hmr_overlap = None
+    if self_penetration:  # (no hash stream: the HMR pose of the window and the arm's marker columns there change, nothing else)
+        from .body_model import body_capsules, capsule_pair_depths
+
+        caps = body_capsules(tables)
+        free = capsule_pair_depths(joints, *caps).max(axis=1) == 0.0
+        start = -(-F // 10)
+        t0 = next((a0 for a0 in range(start, F - PENETRATION_WINDOW + 1) if free[a0:a0 + PENETRATION_WINDOW].all()), None)
+        if t0 is None:
+            raise ValueError("make_sequence: no window of %d frames from frame %d on in which the ground truth is free of "
+                             "overlap" % (PENETRATION_WINDOW, start))
+        window = (t0, t0 + PENETRATION_WINDOW)
+        rest = rest_joints_f64(tables, hmr_betas.mean(axis=0))  # (the fit starts from the mean of the HMR betas)
+        hmr_rot, sel = _arm_into_torso(tables, hmr_rot, rest, caps, t0)
+        hmr_overlap = capsule_pair_depths(fk_joints_f64(tables, hmr_rot, rest)[0], caps[0], caps[1], caps[2][sel]).max(axis=1)
+        arm_cols = np.isin(owner[pick[perm]], [16, 18, 20, 22])
+        markers[t0:t0 + PENETRATION_WINDOW, arm_cols] = 0.0
+
     f32 = lambda x: torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
     img = SyntheticImgSmpl(
         trans=f32(hmr_trans),
@@ -312,6 +419,10 @@ def make_sequence(tables: SmplTables, seed: int = 0, num_frames: int = 300, num_
         gt["sole_vids"] = sole
         gt["floor_height"] = 0.0
         gt["sole_z"] = sole_z
+    if self_penetration:
+        gt["capsules"] = caps
+        gt["penetration_window"] = window
+        gt["hmr_overlap"] = hmr_overlap
     return SyntheticSequence(img_smpl=img, markers=SyntheticMarkers(markers.astype(np.float32), 30.0), gt=gt)
 
 

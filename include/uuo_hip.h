@@ -281,6 +281,30 @@ int uuo_fit_set_floor(uuo_fit_t* fit, float w_pen, float w_con, float height, co
  * and with w_soft != 0, and inside lock-step batches (uuo_batch_*). */
 int uuo_fit_set_capsules(uuo_fit_t* fit, float w, int32_t n_caps, const int32_t* h_cap_joints, const float* h_cap_geom,
                          int32_t n_pairs, const int32_t* h_pairs);
+/* EXTENSION (not reference behaviour; SMPLify's angle prior on knees and elbows is the classic of this kind, the reference has
+ * none): a joint-angle limit term on the body pose of the chamfer and marker stages, the only term that looks at a joint's own
+ * rotation.  Body joint j = 1 .. 23, R its local rotation as the closure's forward uses it (after the stage's Gram-Schmidt
+ * normalisation), row-major:
+ *   s = 1/2 (R21 - R12, R02 - R20, R10 - R01),  c = 1/2 (R00 + R11 + R22 - 1),  n = |s|,  theta = atan2(n, c),
+ *   omega = kappa s,  kappa = theta / n                       (the axis-angle vector of R)
+ *   n < 1e-4 and c >= 0: kappa = 1, d kappa = 0 (identity);  n < 1e-4 and c < 0: the joint contributes nothing (half turn)
+ *   pen[j][k] = max(omega_k - hi[j][k], 0) + max(lo[j][k] - omega_k, 0)      k = x, y, z;  lo <= hi, -inf / +inf = no bound
+ *   loss += w sum_t sum_j sum_k pen^2 / F                     (1 / F only, as for the capsules)
+ *   dL/d omega_k = (2 w / F) (max(omega_k - hi, 0) - max(lo - omega_k, 0))
+ * in rad^2.  Frames are not coupled: F = 1 is a valid problem.  The root orientation, z, the translation and the shape are not
+ * read.  The gradient reaches the raw 3x3 pose entries through the stage's own Gram-Schmidt backward: third raw rows receive
+ * exact zeros from the term, as from the data term.
+ * A setting of the WORKSPACE (off at creation) with the lifetime rules of uuo_fit_set_joint_accel.  h_lo, h_hi are HOST arrays
+ * [23][3] (row j - 1 is SMPL joint j), checked and COPIED at the call: the library owns the device copy.  A call with the tables
+ * of the previous call uploads nothing; new tables wait for the last evaluation that read the old ones, on its stream alone.
+ * w == 0 switches the term off; the pointers may then be null, and every result is that of a workspace that never had the
+ * setting.  Errors (-22): a negative or non-finite w, a NaN bound, lo > hi, lo = +inf or hi = -inf, null arrays with w > 0; a
+ * refused call changes nothing: the weight and the tables of the last accepted call stay in force.
+ * Sums in a fixed order, no atomics: results are bit-reproducible.  Works with robust_sigma, the joint-acceleration, foot-lock,
+ * floor-contact and self-penetration terms, the latent marker offsets, three-corner placements, the point-to-surface term and
+ * the per-frame vertex table.  Refused (at evaluation) for the part stage and with w_soft != 0, and inside lock-step batches
+ * (uuo_batch_*). */
+int uuo_fit_set_joint_limits(uuo_fit_t* fit, float w, const float* h_lo, const float* h_hi);
 /* EXTENSION (not reference behaviour; MoSh-style fitters score a marker by its distance to the SKIN less its stand-off, the
  * reference's chamfer term by its distance to the nearest VERTEX): on = 1 replaces the chamfer stage's data term
  * min_v |x - v|^2 by the point-to-surface term on the one-ring of the nearest vertex v^ the closure's search finds anyway:

@@ -1,0 +1,523 @@
+"""EXTENSION: the joint-angle limit term on the body pose (stages.{chamfer,marker}.losses.joint_limits) -- config validation and
+routing, the composed route's torch term against a loop-written numpy restatement on every branch of the rotation logarithm, the
+gradient against difference quotients in the raw parameters, the table builder, the metric, the generator's hyperextended
+capture and the C entry point's binding.  No GPU needed (tests/test_gpu_joint_limits.py holds the fused closures and the
+fits)."""
+import math
+import os
+import re
+import subprocess
+from ctypes import c_float, c_int, c_void_p
+
+import numpy as np
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+INF = float("inf")
+
+
+def _table(v):
+    return [[v, v, v] for _ in range(23)]
+
+
+BLOCK = {"lo": _table(-0.2), "hi": _table(0.3)}
+
+
+def _cfg(name="video_mocap", **stages):
+    """packaged config; per stage a dict whose `joint_limits_table` entry goes on the stage as joint_limits, the rest on its
+    losses"""
+    from uuo_mocap_amd.config import packaged_config
+
+    cfg = packaged_config(name)
+    for stage, kv in stages.items():
+        for k, v in kv.items():
+            if k == "joint_limits_table":
+                cfg["stages"][stage]["joint_limits"] = v
+            else:
+                cfg["stages"][stage]["losses"][k] = v
+    return cfg
+
+
+# ------------------------------------------------------------------------------------------------ 1. config, refusals, routing
+@pytest.mark.parametrize("stage", ["chamfer", "marker"])
+def test_limit_keys_are_read_and_validated(stage):
+    from uuo_mocap_amd.engine import stage_joint_limits
+
+    assert stage_joint_limits(_cfg(), stage) == {"w": 0.0, "limits": None}   # absent: off
+    assert stage_joint_limits(_cfg(**{stage: {"joint_limits": None}}), stage)["w"] == 0.0
+    got = stage_joint_limits(_cfg(**{stage: {"joint_limits": 2.5, "joint_limits_table": BLOCK}}), stage)
+    assert got == {"w": 2.5, "limits": BLOCK}
+    for bad in (-1.0, float("nan"), INF):
+        with pytest.raises(ValueError, match="joint_limits"):
+            stage_joint_limits(_cfg(**{stage: {"joint_limits": bad}}), stage)
+
+    def edit(which, j, k, v):
+        b = {"lo": [list(r) for r in BLOCK["lo"]], "hi": [list(r) for r in BLOCK["hi"]]}
+        b[which][j][k] = v
+        return b
+
+    for bad in ("limits", [1, 2], {"lo": _table(0.0)}, {"lo": _table(0.0)[:22], "hi": _table(1.0)[:22]},
+                {"lo": [[0.0, 0.0]] * 23, "hi": _table(1.0)}, edit("lo", 3, 1, float("nan")), edit("hi", 3, 1, float("nan")),
+                edit("lo", 3, 1, 0.4), edit("lo", 3, 1, INF), edit("hi", 3, 1, -INF), edit("lo", 0, 0, True),
+                dict(BLOCK, extra=1)):
+        with pytest.raises(ValueError, match="joint_limits"):
+            stage_joint_limits(_cfg(**{stage: {"joint_limits_table": bad}}), stage)
+    # .inf is accepted (no bound), also straight from YAML text
+    import yaml
+
+    open_ = stage_joint_limits(_cfg(**{stage: {"joint_limits_table": edit("hi", 3, 1, INF)}}), stage)["limits"]
+    assert open_["hi"][3][1] == INF
+    text = yaml.safe_load("{lo: %s, hi: %s}" % (str(_table(0.0)).replace("0.0", "-.inf"), str(_table(0.0)).replace("0.0", ".inf")))
+    got = stage_joint_limits(_cfg(**{stage: {"joint_limits_table": text}}), stage)["limits"]
+    assert got["lo"][22][2] == -INF and got["hi"][0][0] == INF
+
+
+def test_stage_problems_refuse_bad_keys_before_touching_the_device():
+    from uuo_mocap_amd.engine import ChamferProblem, MarkerProblem, PartProblem
+
+    with pytest.raises(ValueError, match="joint_limits"):
+        ChamferProblem(None, None, None, None, None, _cfg(chamfer={"joint_limits": -2.0}))
+    with pytest.raises(ValueError, match="joint_limits"):
+        MarkerProblem(None, None, None, None, None, _cfg(marker={"joint_limits": float("nan")}))
+    with pytest.raises(ValueError, match="joint_limits"):
+        MarkerProblem(None, None, None, None, None, _cfg(marker={"joint_limits": 1.0, "joint_limits_table": {"lo": []}}))
+    with pytest.raises(NotImplementedError, match="soft"):
+        ChamferProblem(None, None, None, None, None, _cfg(chamfer={"joint_limits": 1.0, "soft_chamfer": 10.0}))
+    with pytest.raises(NotImplementedError, match="joint_limits"):
+        PartProblem(None, None, None, None, None, None, _cfg(part={"joint_limits": 1.0}))
+
+
+def test_routing_flags():
+    from uuo_mocap_amd.optimization import _limit_fused, _limits_on, lockstep_supported
+
+    plain, lim = _cfg(), _cfg("video_mocap_limits")
+    for stage in ("chamfer", "marker"):
+        assert not _limits_on(plain, stage) and _limits_on(lim, stage)
+        assert lockstep_supported(_cfg(**{stage: {"joint_limits": 0.0}}), stage)
+        assert not lockstep_supported(lim, stage)          # lock-step batches do not carry the term
+        assert not lockstep_supported(_cfg(**{stage: {"joint_limits": 1.0}}), stage)
+        assert _limit_fused(lim, stage)
+        composed = _cfg("video_mocap_limits")
+        composed["execution"] = {"limit_fused": False}
+        assert not _limit_fused(composed, stage)
+        assert _limit_fused(dict(plain, execution={"limit_fused": False}), stage)  # nothing to compose without the term
+
+
+def _zeros(*s):
+    return torch.zeros(*s)
+
+
+class _Smpl:
+    class device_model:
+        V = 6890
+
+
+def test_composed_routes_are_taken(monkeypatch):
+    """execution.limit_fused: False and soft_chamfer + the key go to the closures composed from the operators"""
+    from uuo_mocap_amd import optimization as opt
+
+    F, M = 6, 4
+    markers = _zeros(F, M, 3)
+    one_hot = _zeros(M, 6890)
+    one_hot[:, 0] = 1.0
+    taken = []
+    monkeypatch.setattr(opt, "_optim_chamfer_general", lambda *a, **k: taken.append("chamfer"))
+    monkeypatch.setattr(opt, "_optim_markers_general", lambda *a, **k: taken.append("marker"))
+    cfg = _cfg("video_mocap_limits")
+    cfg["execution"] = {"limit_fused": False}
+    args_c = (markers, _zeros(F, 23, 3, 3), _zeros(F, 23, 3, 3), _zeros(1, 10), _zeros(1, 10), _zeros(F, 1, 3, 3), _zeros(F, 3),
+              _zeros(F), torch.zeros(F, M, dtype=torch.long), None)
+    opt.optim_chamfer(*args_c, cfg)
+    opt.optim_markers(markers, _zeros(F, 23, 3, 3), _zeros(F, 23, 3, 3), _zeros(1, 10), _zeros(1, 10), _zeros(F, 1, 3, 3),
+                      _zeros(F, 3), one_hot, _zeros(F), _Smpl, cfg)
+    assert taken == ["chamfer", "marker"]
+    soft = _cfg("video_mocap_limits", chamfer={"soft_chamfer": 10.0})
+    opt.optim_chamfer(*args_c, soft)   # (markers on the host: the fused soft closure is not in reach either way)
+    assert taken == ["chamfer", "marker", "chamfer"]
+
+
+def test_frame_sharding_refuses_the_term():
+    from uuo_mocap_amd import parallel
+    from uuo_mocap_amd.optimization import optim_chamfer, optim_markers
+
+    F, M = 6, 4
+    markers = _zeros(F, M, 3)
+    one_hot = _zeros(M, 6890)
+    one_hot[:, 0] = 1.0
+    with parallel.shard_frames(joint_with_one_rank=True):
+        with pytest.raises(NotImplementedError, match="joint_limits.*frame-block sharding"):
+            optim_chamfer(markers, _zeros(F, 23, 3, 3), _zeros(F, 23, 3, 3), _zeros(1, 10), _zeros(1, 10), _zeros(F, 1, 3, 3),
+                          _zeros(F, 3), _zeros(F), torch.zeros(F, M, dtype=torch.long), None, _cfg(chamfer={"joint_limits": 1.0}))
+        with pytest.raises(NotImplementedError, match="joint_limits.*frame-block sharding"):
+            optim_markers(markers, _zeros(F, 23, 3, 3), _zeros(F, 23, 3, 3), _zeros(1, 10), _zeros(1, 10), _zeros(F, 1, 3, 3),
+                          _zeros(F, 3), one_hot, _zeros(F), _Smpl, _cfg(marker={"joint_limits": 1.0}))
+
+
+def test_solve_batch_refuses_the_term_up_front():
+    from uuo_mocap_amd.engine import solve_batch
+
+    class _P:
+        model = None
+        joint_accel = 0.0
+        foot_lock = 0.0
+        floor_on = False
+        capsules_on = False
+        joint_limits_on = True
+
+        class problem:
+            w_offsets = 0.0
+
+    with pytest.raises(NotImplementedError, match="joint_limits"):
+        solve_batch([_P()], [None], max_iter=1)
+
+
+def test_shipped_config_differs_from_its_parent_only_by_the_term():
+    from uuo_mocap_amd.engine import stage_joint_limits
+
+    plain, lim = _cfg(), _cfg("video_mocap_limits")
+    for stage in ("chamfer", "marker"):
+        c = stage_joint_limits(lim, stage)
+        assert c["w"] > 0.0 and c["limits"] is None
+        rest = {k: v for k, v in lim["stages"][stage]["losses"].items() if k != "joint_limits"}
+        assert rest == plain["stages"][stage]["losses"]
+        assert {k: v for k, v in lim["stages"][stage].items() if k not in ("losses", "joint_limits")} == \
+            {k: v for k, v in plain["stages"][stage].items() if k != "losses"}
+    for k in plain["stages"]:
+        if k not in ("chamfer", "marker"):
+            assert lim["stages"][k] == plain["stages"][k]
+    assert {k: v for k, v in lim.items() if k not in ("stages", "name", "parent")} == \
+        {k: v for k, v in plain.items() if k not in ("stages", "name", "parent")}
+
+
+# ------------------------------------------------------------------------------------------------ 2. the term, branch by branch
+def _rodrigues(v):
+    """axis-angle -> rotation, plain float64"""
+    v = np.asarray(v, dtype=np.float64)
+    th = float(np.sqrt(v @ v))
+    if th == 0.0:
+        return np.eye(3)
+    k = v / th
+    K = np.array([[0.0, -k[2], k[1]], [k[2], 0.0, -k[0]], [-k[1], k[0], 0.0]])
+    return np.eye(3) + math.sin(th) * K + (1.0 - math.cos(th)) * (K @ K)
+
+
+def _term_np(R, lo, hi, w):
+    """loss, d loss / d R [F, 23, 3, 3] and one tag per (frame, joint): the issue's formulas with explicit loops"""
+    F = R.shape[0]
+    loss, g, tags = 0.0, np.zeros_like(R), []
+    for f in range(F):
+        for j in range(23):
+            r = R[f, j]
+            s = 0.5 * np.array([r[2, 1] - r[1, 2], r[0, 2] - r[2, 0], r[1, 0] - r[0, 1]])
+            c = 0.5 * (r[0, 0] + r[1, 1] + r[2, 2] - 1.0)
+            n = math.sqrt(s @ s)
+            if n < 1e-4 and c < 0.0:
+                tags.append("half turn")
+                continue
+            if n < 1e-4:
+                theta, kappa, dkn, dkc, tag = 0.0, 1.0, 0.0, 0.0, "identity"
+            else:
+                theta = math.atan2(n, c)
+                kappa = theta / n
+                dkn = c / (n * (n * n + c * c)) - theta / (n * n)
+                dkc = -1.0 / (n * n + c * c)
+                tag = "generic"
+            om = kappa * s
+            gom = np.zeros(3)
+            for k in range(3):
+                up, dn = max(om[k] - hi[j, k], 0.0), max(lo[j, k] - om[k], 0.0)
+                pen = up + dn
+                loss += w * pen * pen / F
+                gom[k] = (2.0 * w / F) * (up - dn)
+                if up > 0.0:
+                    tag += ", beyond hi"
+                if dn > 0.0:
+                    tag += ", beyond lo"
+                if pen == 0.0 and (om[k] == hi[j, k] or om[k] == lo[j, k]):
+                    tag += ", on a bound"
+                if math.isinf(lo[j, k]) or math.isinf(hi[j, k]):
+                    tag += ", open"
+            if "beyond" not in tag:
+                tag += ", inside"
+            tags.append(tag)
+            q = float(s @ gom)
+            ds = kappa * gom + (q * dkn / n) * s if n >= 1e-4 else gom.copy()
+            dc = q * dkc
+            g[f, j, 2, 1] += 0.5 * ds[0]
+            g[f, j, 1, 2] -= 0.5 * ds[0]
+            g[f, j, 0, 2] += 0.5 * ds[1]
+            g[f, j, 2, 0] -= 0.5 * ds[1]
+            g[f, j, 1, 0] += 0.5 * ds[2]
+            g[f, j, 0, 1] -= 0.5 * ds[2]
+            for k in range(3):
+                g[f, j, k, k] += 0.5 * dc
+    return loss, g, tags
+
+
+def _hand_case():
+    """one frame; lo / hi [23, 3]; joint index (row) -> the branch it is built for"""
+    R = np.tile(np.eye(3), (1, 23, 1, 1))
+    lo = np.full((23, 3), -0.4)
+    hi = np.full((23, 3), 0.5)
+    # row 0: the exact identity with lo > 0 (kappa = 1)
+    lo[0] = [0.3, -0.4, -0.4]
+    hi[0] = [0.9, 0.5, 0.5]
+    # row 1: a generic rotation beyond hi;  row 2: beyond lo;  row 3: inside
+    R[0, 1] = _rodrigues([0.9, 0.2, -0.1])
+    R[0, 2] = _rodrigues([0.1, -0.8, 0.3])
+    R[0, 3] = _rodrigues([0.2, -0.1, 0.3])
+    # row 4: exactly on a bound (the bound is the computed component itself: pen = 0)
+    R[0, 4] = _rodrigues([0.45, 0.1, 0.0])
+    # row 5: infinite bounds on a large rotation
+    R[0, 5] = _rodrigues([1.5, -1.0, 0.5])
+    lo[5] = [-INF, -INF, -0.4]
+    hi[5] = [INF, -1.2, INF]
+    # row 6: theta within 1e-5 of pi (skipped), bounds that it would violate grossly
+    R[0, 6] = _rodrigues(np.array([1.0, 0.0, 0.0]) * (math.pi - 5e-6))
+    lo[6] = [-0.1, -0.1, -0.1]
+    hi[6] = [0.1, 0.1, 0.1]
+    # row 7: near the identity but not under the threshold, beyond hi
+    R[0, 7] = _rodrigues([3e-4, 0.0, 0.0])
+    lo[7] = [-1e-4, -0.4, -0.4]
+    hi[7] = [1e-4, 0.5, 0.5]
+    return R, lo, hi
+
+
+def test_term_and_gradient_match_the_numpy_restatement_on_every_branch():
+    from uuo_mocap_amd.body_model import joint_limit_violation, rotation_log
+    from uuo_mocap_amd.losses import joint_limit_loss
+
+    R, lo, hi = _hand_case()
+    om4 = rotation_log(R[0, 4])[0]
+    hi[4, 0] = om4[0]          # exactly on the bound
+    w = 3.0
+    loss_np, g_np, tags = _term_np(R, lo, hi, w)
+    assert tags[0].startswith("identity") and "beyond lo" in tags[0]
+    assert tags[1].startswith("generic") and "beyond hi" in tags[1]
+    assert tags[2].startswith("generic") and "beyond lo" in tags[2]
+    assert tags[3] == "generic, inside"
+    assert "on a bound" in tags[4] and "beyond" not in tags[4]
+    assert "open" in tags[5] and "beyond hi" in tags[5]
+    assert tags[6] == "half turn"
+    assert tags[7].startswith("generic") and "beyond hi" in tags[7]
+    assert all(t == "identity, inside" for t in tags[8:])
+    Rt = torch.from_numpy(R).requires_grad_(True)
+    loss = joint_limit_loss(Rt, lo, hi, w)
+    loss.backward()
+    assert loss.dtype == torch.float64
+    np.testing.assert_allclose(float(loss.detach()), loss_np, rtol=1e-13)
+    np.testing.assert_allclose(Rt.grad.numpy(), g_np, rtol=1e-11, atol=1e-15)
+    assert np.isfinite(Rt.grad.numpy()).all()
+    assert not Rt.grad.numpy()[0, 6].any() and not Rt.grad.numpy()[0, 3].any() and not Rt.grad.numpy()[0, 4].any()
+    # the identity branch: omega = s, so pen = lo exactly and the gradient is the constant map
+    assert g_np[0, 0, 2, 1] == pytest.approx(0.5 * (2.0 * w) * (-0.3)) and g_np[0, 0, 1, 2] == -g_np[0, 0, 2, 1]
+    # the host's numpy routine takes the same branches
+    om, skipped = rotation_log(R)
+    assert skipped[0, 6] and skipped.sum() == 1
+    np.testing.assert_allclose(om[0, 1], [0.9, 0.2, -0.1], atol=1e-14)
+    np.testing.assert_allclose(om[0, 5], [1.5, -1.0, 0.5], atol=1e-14)
+    pen = joint_limit_violation(R, lo, hi)
+    assert w * (pen ** 2).sum() / R.shape[0] == pytest.approx(loss_np, rel=1e-13)
+    assert not pen[0, 6].any()
+    # float32 rotations: the checker runs in the rotations' own precision
+    l32 = joint_limit_loss(torch.from_numpy(R).float(), lo, hi, w)
+    assert l32.dtype == torch.float32 and float(l32) == pytest.approx(loss_np, rel=1e-5)
+
+
+# ------------------------------------------------------------------------------------------------ 3. finite differences
+def _gs64(raw):
+    """the stage's normalisation (Gram-Schmidt on rows 0, 1; row 2 their cross product) on raw [..., 3, 3], float64"""
+    a1, a2 = raw[..., 0, :], raw[..., 1, :]
+    b1 = a1 / np.maximum(np.linalg.norm(a1, axis=-1, keepdims=True), 1e-12)
+    u2 = a2 - (b1 * a2).sum(-1, keepdims=True) * b1
+    b2 = u2 / np.maximum(np.linalg.norm(u2, axis=-1, keepdims=True), 1e-12)
+    return np.stack([b1, b2, np.cross(b1, b2)], axis=-2)
+
+
+def test_gradient_against_central_differences_in_the_raw_parameters():
+    """d term / d raw through the Gram-Schmidt map against central differences with h = 1e-6 in float64.  Truncation
+    h^2 |f'''| / 6: the term is w pen^2 of smooth maps whose third derivatives are of order 10 at theta in [0.3, 1.5] and w = 1,
+    so below 1e-11; rounding eps |loss| / h below 1e-10 at loss of order 1: the two must agree to 1e-8 absolute.  The tags at
+    both displaced points show that no hinge or threshold was crossed."""
+    from uuo_mocap_amd.losses import joint_limit_loss
+    from uuo_mocap_amd.transforms import normalize_rot
+
+    rng = np.random.RandomState(5)
+    F = 2
+    om = rng.uniform(-0.8, 0.8, size=(F, 23, 3))
+    R = np.stack([np.stack([_rodrigues(om[f, j]) for j in range(23)]) for f in range(F)])
+    raw = R * rng.uniform(0.8, 1.25, size=(F, 23, 3, 1)) + 0.05 * rng.standard_normal((F, 23, 3, 3))  # not orthonormal
+    lo, hi = np.full((23, 3), -0.2), np.full((23, 3), 0.2)
+    lo[3], hi[5] = -INF, INF
+    loss, _, tags = _term_np(_gs64(raw), lo, hi, 1.0)
+    assert sum("beyond" in t for t in tags) >= 30 and all(t.startswith("generic") for t in tags)
+    rt = torch.from_numpy(raw).requires_grad_(True)
+    lt = joint_limit_loss(normalize_rot(rt), lo, hi, 1.0)
+    lt.backward()
+    g = rt.grad.numpy()
+    assert float(lt.detach()) == pytest.approx(loss, rel=1e-13)
+    assert not g[:, :, 2].any() and np.abs(g[:, :, :2]).sum() > 0      # third raw rows: exact zeros
+    h = 1e-6
+    idx = np.argsort(-np.abs(g).reshape(-1))[:40]   # the 40 largest entries
+    worst = 0.0
+    for flat in idx:
+        e = np.zeros(raw.size)
+        e[flat] = h
+        e = e.reshape(raw.shape)
+        lp, _, tp = _term_np(_gs64(raw + e), lo, hi, 1.0)
+        lm, _, tm = _term_np(_gs64(raw - e), lo, hi, 1.0)
+        assert tp == tags and tm == tags, "a hinge or a threshold within the step: pick another seed"
+        worst = max(worst, abs((lp - lm) / (2.0 * h) - g.reshape(-1)[flat]))
+    print("OBS joint limits: worst |central difference - gradient| over 40 entries %.2e" % worst)
+    assert worst <= 1e-8
+
+
+# ------------------------------------------------------------------------------------------------ 4. builder and metric
+def test_smpl_joint_limits_builder():
+    from uuo_mocap_amd.body_model import smpl_joint_limits
+
+    lo, hi = smpl_joint_limits()
+    assert lo.dtype == np.float32 and hi.dtype == np.float32 and lo.shape == (23, 3) and hi.shape == (23, 3)
+    finite = np.isfinite(lo) | np.isfinite(hi)
+    assert sorted(zip(*np.nonzero(finite))) == [(3, 0), (4, 0), (17, 1), (18, 1)]     # rows j - 1 of joints 4, 5, 18, 19
+    assert np.isneginf(lo[~finite]).all() and np.isposinf(hi[~finite]).all()
+    f, s = np.float32(2.70), np.float32(0.10)
+    assert (lo[3, 0], hi[3, 0]) == (-s, f) and (lo[4, 0], hi[4, 0]) == (-s, f)        # knees: flexion is +x
+    assert (lo[17, 1], hi[17, 1]) == (-f, s)                                          # left elbow: flexion is -y
+    assert (lo[18, 1], hi[18, 1]) == (-s, f)                                          # right elbow: flexion is +y
+    assert (lo <= hi).all()
+    lo2, hi2 = smpl_joint_limits(flex=2.0, slack=0.0)
+    assert (lo2[3, 0], hi2[3, 0], lo2[17, 1], hi2[17, 1], lo2[18, 1], hi2[18, 1]) == (0.0, 2.0, -2.0, 0.0, 0.0, 2.0)
+    with pytest.raises(ValueError, match="flex"):
+        smpl_joint_limits(flex=-1.0)
+
+
+def test_joint_limit_violation_metric():
+    from uuo_mocap_amd.body_model import smpl_joint_limits
+    from uuo_mocap_amd.metrics import compute_joint_limit_violation
+
+    lo, hi = smpl_joint_limits()
+    R = np.tile(np.eye(3), (4, 23, 1, 1))
+    R[0, 3] = _rodrigues([-0.3, 0.0, 0.0])      # left knee 0.2 rad past -slack
+    R[1, 17] = _rodrigues([0.0, 0.15, 0.4])     # left elbow 0.05 rad past +slack in y (z is free)
+    R[1, 3] = _rodrigues([2.8, 0.0, 0.0])       # and the knee 0.1 rad past flex: the frame's largest
+    R[2, 0] = _rodrigues([1.0, 1.0, 1.0])       # an unlimited joint
+    e = compute_joint_limit_violation(torch.from_numpy(R), lo, hi)
+    assert e["max_deg"] == pytest.approx(math.degrees(0.2), abs=1e-4)
+    assert e["mean_deg"] == pytest.approx(math.degrees(0.2 + 0.1) / 4.0, abs=1e-4)
+    assert e["frames_pct"] == pytest.approx(50.0)
+    assert compute_joint_limit_violation(torch.from_numpy(R[2:]), lo, hi) == {"max_deg": 0.0, "mean_deg": 0.0, "frames_pct": 0.0}
+    with pytest.raises(ValueError, match="rot_body"):
+        compute_joint_limit_violation(torch.zeros(4, 24, 3, 3), lo, hi)
+
+
+# ------------------------------------------------------------------------------------------------ 5. the generator
+@pytest.fixture(scope="module")
+def sequences(tables):
+    from uuo_mocap_amd.synthetic import make_sequence
+
+    return (make_sequence(tables, seed=0, num_frames=300, num_markers=50),
+            make_sequence(tables, seed=0, num_frames=300, num_markers=50, joint_limits=False),
+            make_sequence(tables, seed=0, num_frames=300, num_markers=50, joint_limits=True))
+
+
+def _same(a, b):
+    if isinstance(a, torch.Tensor):
+        return torch.equal(a, b)
+    if isinstance(a, np.ndarray):
+        return a.dtype == b.dtype and np.array_equal(a, b)
+    return a == b
+
+
+def test_option_off_changes_nothing(sequences):
+    base, off, _ = sequences
+    assert set(base.gt) == set(off.gt) and not {"joint_limits", "limit_window", "hmr_violation"} & set(base.gt)
+    for k in base.gt:
+        assert _same(base.gt[k], off.gt[k]), k
+    for k, v in vars(base.img_smpl).items():
+        assert _same(v, getattr(off.img_smpl, k)), k
+    assert np.array_equal(base.markers.get_points(), off.markers.get_points())
+
+
+def test_hyperextended_sequence(tables, sequences):
+    from uuo_mocap_amd.body_model import joint_limit_violation, rotation_log, smpl_joint_limits
+    from uuo_mocap_amd.synthetic import make_sequence
+
+    base, _, seq = sequences
+    lo, hi = seq.gt["joint_limits"]
+    for a, b in zip((lo, hi), smpl_joint_limits()):
+        assert np.array_equal(a, b)
+    t0, t1 = seq.gt["limit_window"]
+    assert (t0, t1) == (30, 54)
+    # the ground truth is inside the limits in every frame; the four limited components move on the allowed side only, and
+    # nothing else of the true pose changed
+    rot = seq.gt["rot"].astype(np.float64)
+    assert joint_limit_violation(rot[:, 1:], lo, hi).max() == 0.0
+    om = rotation_log(rot[:, 1:])[0]
+    om0 = rotation_log(base.gt["rot"].astype(np.float64)[:, 1:])[0]
+    assert om[:, 3, 0].min() >= -1e-6 and om[:, 4, 0].min() >= -1e-6 and om[:, 17, 1].max() <= 1e-6 and om[:, 18, 1].min() >= -1e-6
+    assert om[:, 3, 0].max() > 0.05 and om[:, 17, 1].min() < -0.05
+    same = np.ones((23, 3), dtype=bool)
+    same[[3, 4, 17, 18], [0, 0, 1, 1]] = False
+    assert np.abs(om - om0)[:, same].max() < 1e-6
+    assert joint_limit_violation(base.gt["rot"].astype(np.float64)[:, 1:], lo, hi).max() > 0.0  # (the default motion is not)
+    # the HMR start against the same capture without the window: only joint 4, only in the window; x = -0.5 in the untapered
+    # frames, 1/3 and 2/3 of it at the ends; the other two components of the knee's vector are kept
+    hs = seq.img_smpl.pose_body.double().numpy()
+    omh = rotation_log(hs)[0]
+    assert np.abs(omh[t0 + 2:t1 - 2, 3, 0] + 0.5).max() < 1e-6
+    np.testing.assert_allclose(omh[[t0, t0 + 1, t1 - 2, t1 - 1], 3, 0], [-0.5 / 3, -1.0 / 3, -1.0 / 3, -0.5 / 3], atol=1e-6)
+    noise = rot[:, 1:].transpose(0, 1, 3, 2) @ hs       # the HMR noise factor rot^T hmr: the default capture's outside the knee window
+    noise0 = base.gt["rot"].astype(np.float64)[:, 1:].transpose(0, 1, 3, 2) @ base.img_smpl.pose_body.double().numpy()
+    changed = np.abs(noise - noise0).reshape(300, 23, -1).max(-1) > 1e-5
+    assert changed[t0:t1, 3].all() and not changed[:, :3].any() and not changed[:, 4:].any()
+    assert not changed[:t0].any() and not changed[t1:].any()
+    for k, v in vars(base.img_smpl).items():
+        if k != "pose_body":
+            assert _same(v, getattr(seq.img_smpl, k)), k
+    hv = seq.gt["hmr_violation"]
+    assert hv.shape == (300,) and (hv[t0 + 2:t1 - 2] >= 0.4 - 1e-6).all()
+    np.testing.assert_allclose(hv, joint_limit_violation(hs, lo, hi).reshape(300, -1).max(axis=1), atol=1e-6)
+    # the left leg's marker columns are blank in the window, and no other entry is
+    owner = np.argmax(np.asarray(tables.lbs_weights)[np.asarray(seq.gt["marker_vids"])], axis=1)
+    leg = np.isin(owner, [4, 7, 10])
+    assert leg.sum() >= 1
+    m1 = np.asarray(seq.markers.get_points())
+    assert not m1[t0:t1][:, leg].any()
+    m0 = np.asarray(base.markers.get_points())
+    blank0, blank1 = (m0 == 0.0).all(-1), (m1 == 0.0).all(-1)
+    extra = blank1 & ~blank0
+    assert not extra[:t0].any() and not extra[t1:].any() and not extra[:, ~leg].any()
+    with pytest.raises(ValueError, match="window"):
+        make_sequence(tables, seed=0, num_frames=20, num_markers=8, joint_limits=True)
+
+
+# ------------------------------------------------------------------------------------------------ 6. C entry point
+def test_entry_point_is_declared_bound_and_typed_as_in_the_header(tmp_path):
+    from uuo_mocap_amd import _lib
+
+    assert "uuo_fit_set_joint_limits" in _lib.header_symbols()
+    sig = [c_void_p, c_float, c_void_p, c_void_p]
+    assert _lib._SIGNATURES["uuo_fit_set_joint_limits"] == (c_int, sig)
+    text = re.sub(r"/\*.*?\*/", "", open(_lib.HEADER_PATH).read(), flags=re.S)
+    assert re.search(r"\bint\s+uuo_fit_set_joint_limits\s*\(\s*uuo_fit_t\s*\*\s*fit\s*,\s*float\s+w\s*,\s*const\s+float\s*\*\s*h_lo\s*,"
+                     r"\s*const\s+float\s*\*\s*h_hi\s*\)\s*;", text)
+    src = tmp_path / "sig.c"
+    src.write_text('#include "uuo_hip.h"\nint (*fp)(uuo_fit_t*, float, const float*, const float*) = uuo_fit_set_joint_limits;\n'
+                   'int main(void) { return 0; }\n')
+    subprocess.check_call(["gcc", "-std=c99", "-Werror", "-c", "-I", os.path.join(ROOT, "include"), str(src), "-o",
+                           str(tmp_path / "sig.o")])
+    assert _lib.ABI_VERSION == 3  # the problem structure and the ABI version did not change
+    lib = _lib.load()             # (dlopen needs no GPU) bound with the declared types
+    assert lib.uuo_fit_set_joint_limits.argtypes == sig and lib.uuo_fit_set_joint_limits.restype == c_int
+
+
+def test_note_in_the_header():
+    from uuo_mocap_amd import _lib
+
+    text = open(_lib.HEADER_PATH).read()
+    note = text[text.index("joint-angle limit term"):text.index("int uuo_fit_set_joint_limits")]
+    for word in ("atan2", "1e-4", "half turn", "rad^2", "HOST", "COPIED", "[23][3]", "row j - 1", "F = 1", "NaN", "lo > hi",
+                 "part stage", "lock-step", "Gram-Schmidt", "exact zeros", "uploads nothing"):
+        assert word in note, word

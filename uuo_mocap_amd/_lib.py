@@ -129,6 +129,8 @@ _SIGNATURES = {
     "uuo_fit_set_floor": (c_int, [c_void_p, c_float, c_float, c_float, c_void_p, c_int, c_int, c_void_p]),
     # EXTENSION: self-penetration term of the workspace (w, C, host joints [C][2], host geometry [C][3], P, host pairs [P][2])
     "uuo_fit_set_capsules": (c_int, [c_void_p, c_float, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    # EXTENSION: joint-angle limit term of the workspace (w, host lo [23][3], host hi [23][3])
+    "uuo_fit_set_joint_limits": (c_int, [c_void_p, c_float, c_void_p, c_void_p]),
     "uuo_problem_num_params": (c_int, [POINTER(UuoProblem)]),
     "uuo_closure_eval": (c_int, [c_void_p, c_void_p, POINTER(UuoProblem), c_void_p, c_void_p, c_void_p, c_void_p]),
     "uuo_lbfgs_solve": (c_int, [c_void_p, c_void_p, POINTER(UuoProblem), c_void_p, POINTER(UuoLbfgsOptions),

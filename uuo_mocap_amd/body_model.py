@@ -434,6 +434,55 @@ def body_capsules(tables: SmplTables, shrink: float = 0.9, rest_margin: float = 
     return cj.astype(np.int32), cg.astype(np.float32), np.asarray(cand, dtype=np.int32).reshape(-1, 2)
 
 
+#: the two thresholds of the joint-angle limit term's rotation logarithm (uuo_fit_set_joint_limits): below LIMIT_SMALL_N the axis
+#: is not formed -- c >= 0 is the identity branch (kappa = 1), c < 0 a half turn that contributes nothing
+LIMIT_SMALL_N = 1e-4
+
+
+def rotation_log(R: np.ndarray):
+    """EXTENSION: the axis-angle vector omega [..., 3] (float64) of rotations R [..., 3, 3], the host's routine of the joint-angle
+    limit term (uuo_fit_set_joint_limits), branch for branch: s = 1/2 (R21 - R12, R02 - R20, R10 - R01), c = 1/2 (tr R - 1),
+    n = |s|, theta = atan2(n, c), omega = (theta / n) s; n < 1e-4 and c >= 0 takes omega = s (identity branch), n < 1e-4 and
+    c < 0 is a half turn, which has no axis: omega = 0 there and `skipped` is True.  Returns (omega, skipped [...])."""
+    R = np.asarray(R, dtype=np.float64)
+    s = 0.5 * np.stack([R[..., 2, 1] - R[..., 1, 2], R[..., 0, 2] - R[..., 2, 0], R[..., 1, 0] - R[..., 0, 1]], axis=-1)
+    c = 0.5 * (R[..., 0, 0] + R[..., 1, 1] + R[..., 2, 2] - 1.0)
+    n = np.sqrt((s * s).sum(-1))
+    small = n < LIMIT_SMALL_N
+    kappa = np.where(small, 1.0, np.arctan2(n, c) / np.where(small, 1.0, n))
+    skipped = small & (c < 0.0)
+    return np.where(skipped[..., None], 0.0, kappa[..., None] * s), skipped
+
+
+def joint_limit_violation(rot_body: np.ndarray, lo, hi) -> np.ndarray:
+    """EXTENSION: pen [F, 23, 3] (radians, float64) = max(omega - hi, 0) + max(lo - omega, 0) of the joint-angle limit term on body
+    rotations [F, 23, 3, 3] (rotation_log; half turns contribute nothing)."""
+    om, skipped = rotation_log(rot_body)
+    lo = np.asarray(lo, dtype=np.float64).reshape(23, 3)
+    hi = np.asarray(hi, dtype=np.float64).reshape(23, 3)
+    pen = np.maximum(om - hi, 0.0) + np.maximum(lo - om, 0.0)
+    return np.where(skipped[..., None], 0.0, pen)
+
+
+def smpl_joint_limits(flex: float = 2.70, slack: float = 0.10):
+    """EXTENSION: the default tables of the joint-angle limit term (uuo_fit_set_joint_limits): (lo, hi), float32 [23, 3] in
+    radians on the components of each body joint's axis-angle vector (row j - 1 is SMPL joint j), infinite except SMPLify's
+    four hinge components: knees (joints 4, 5) x in [-slack, flex], left elbow (18) y in [-flex, slack], right elbow (19) y in
+    [-slack, flex].  The signs are those of SMPLify's angle prior; synthetic_smpl uses SMPL's nominal y-up rest joints, so they
+    hold for it too.  flex (about 155 degrees of flexion) and slack (about 6 degrees of hyperextension) are an anatomical choice,
+    a parameter, not a measurement; on a licensed SMPL they are unverified (no licensed model at hand)."""
+    flex, slack = float(flex), float(slack)
+    if not (np.isfinite(flex) and np.isfinite(slack) and flex >= 0.0 and slack >= 0.0):
+        raise ValueError("smpl_joint_limits: flex and slack are non-negative finite angles in radians")
+    lo = np.full((23, 3), -np.inf, dtype=np.float32)
+    hi = np.full((23, 3), np.inf, dtype=np.float32)
+    for j in (4, 5):
+        lo[j - 1, 0], hi[j - 1, 0] = -slack, flex
+    lo[18 - 1, 1], hi[18 - 1, 1] = -flex, slack
+    lo[19 - 1, 1], hi[19 - 1, 1] = -slack, flex
+    return lo, hi
+
+
 class _ChStub:
     """Stands in for chumpy.ch.Ch when unpickling original SMPL files (install.sh:18 needs chumpy)."""
 

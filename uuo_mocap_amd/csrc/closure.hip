@@ -100,8 +100,13 @@ struct BwdArgs {
   uuo_gptr<const float> floor_loss;   // [F] the frame's share of the term, already weighted
   // EXTENSION (ACCEL instantiations, cap_up != null): the self-penetration term (uuo_fit_set_capsules), left by k_capsule_fwd of
   // this evaluation
-  uuo_gptr<const float> cap_up;       // [F][24][3] upstream gradients on the world joints G_j^t (null = off)
-  uuo_gptr<const float> cap_loss;     // [F] the frame's share of the term, already weighted
+  // (one pointer each for this term and the next: k_bwd_items_t_o has no scalar register left for more)
+  uuo_gptr<const float> cap_up;       // [F][24][3] upstream gradients on the world joints G_j^t (null = off), then [F] the
+                                      // frames' shares of the term, already weighted
+  // EXTENSION (ACCEL instantiations, lim_g != null): the joint-angle limit term (uuo_fit_set_joint_limits), left by k_limit_fwd of
+  // this evaluation
+  uuo_gptr<const float> lim_g;        // [F][23][9] gradients on the raw body pose entries, in parameter space (null = off),
+                                      // then [F] the frames' shares of the term, already weighted
 };
 
 // EXTENSION: the offsets' share of the finalize (k_finalize_o / k_finalize_to, uuo_problem_t.w_offsets)
@@ -446,6 +451,12 @@ __device__ __forceinline__ float gmof_q(float sig2, float s) { return sig2 / (si
 // and the frame's weighted share of the loss.  The gradient joins uj where the joint-acceleration term's enters (so it reaches
 // sdGt, and through s_acc[ACC_UJ + k] the translation's sum: the term is translation invariant, the 24 entries of a component
 // sum to rounding), the share joins slot 3.  Shared instantiations, by the rule of DESIGN 4o (4s has the resource table).
+// block-uniform lim_g != null (EXTENSION, uuo_fit_set_joint_limits; acc_w and lock_w may both be 0): the joint-angle limit term
+// on the body pose.  k_limit_fwd has formed every body joint's axis-angle vector from the forward's own local rotation, the
+// hinges, and the gradient in PARAMETER space (through the stage's Gram-Schmidt backward) [F][23][9], and the frame's weighted
+// share of the loss.  The nine values join gout after the pose prior, before the store and the fused statistics -- loaded there,
+// not beside raw_pre: nine more registers live across the sweep do not fit --, the share joins slot 3.  Shared
+// instantiations, by the rule of DESIGN 4o (4t has the resource table).
 // OFFS (EXTENSION, uuo_problem_t.w_offsets > 0): latent per-marker offsets.  Item mm belongs to marker mm / offs_k; its
 // rest-space position is vp + o_m wherever it enters (the skinned position and the dA outer product), and its d loss / d o =
 // T^T g (dvp, which the blend gradients use too) goes to offs_part[f][mm] for k_finalize_o.  The host launches these with
@@ -1032,6 +1043,14 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a) {
           psq = fmaf(diff, diff, psq);
         }
       }
+      if constexpr (ACCEL) {
+        if (a.lim_g) {  // the joint-angle limit term's gradient on this joint's raw entries (k_limit_fwd), loaded here
+          // (a 32-bit offset from the uniform base: F * 207 entries stay far below 2^31)
+          const unsigned row = ((unsigned)f * 23u + (unsigned)(j - 1)) * 9u;
+#pragma unroll
+          for (int e = 0; e < 9; ++e) gout[e] += a.lim_g[row + e];
+        }
+      }
       float* pg = a.g_pose + ((size_t)f * 23 + (j - 1)) * a.gs_pose;
       float sd = 0.f, s1 = 0.f, s2 = 0.f, sm = 0.f;
 #pragma unroll
@@ -1141,7 +1160,8 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a) {
         share += a.lock_w * sl;
       }
       if constexpr (FLOOR) share += a.floor_loss[f];  // the floor-contact term's share of this frame (k_floor_fwd)
-      if (a.cap_up) share += a.cap_loss[f];           // the self-penetration term's share of this frame (k_capsule_fwd)
+      if (a.cap_up) share += a.cap_up[(unsigned)a.F * 72u + (unsigned)f];  // the self-penetration term's share (k_capsule_fwd)
+      if (a.lim_g) share += a.lim_g[(unsigned)a.F * 207u + (unsigned)f];  // the joint-angle limit term's share (k_limit_fwd)
       BWD_FP_STORE(3, share);
     }
   }
@@ -1676,6 +1696,99 @@ __global__ __launch_bounds__(64) void k_capsule_fwd(CapsFwdArgs a) {
 }
 
 // ----------------------------------------------------------------------------------------------------
+// EXTENSION (not reference behaviour; uuo_fit_set_joint_limits): a joint-angle limit term on the body pose.  Body joint
+// j = 1 .. 23, R its local rotation as frame_forward forms it (gs6d_forward of the raw entries when the stage normalises, the raw
+// entries otherwise: the same function on the same inputs, so R is bit for bit the forward's), row-major:
+//   s = 1/2 (R21 - R12, R02 - R20, R10 - R01),  c = 1/2 (R00 + R11 + R22 - 1),  n = |s|,  theta = atan2(n, c),  kappa = theta / n,
+//   omega = kappa s;   n < 1e-4: c >= 0 takes kappa = 1, d kappa = 0 (identity), c < 0 contributes nothing (half turn: no axis)
+//   pen_k = max(omega_k - hi_k, 0) + max(lo_k - omega_k, 0),  loss += w pen_k^2 / F,
+//   g_k = dL/d omega_k = (2 w / F) (max(omega_k - hi_k, 0) - max(lo_k - omega_k, 0)),  q = s . g,
+//   dL/ds = kappa g + q (d kappa / dn) s / n,  dL/dc = q d kappa / dc,
+//   d kappa / dn = c / (n (n^2 + c^2)) - theta / n^2,  d kappa / dc = -1 / (n^2 + c^2),
+//   dL/dR21 += 1/2 dL/ds_x, dL/dR12 -= 1/2 dL/ds_x, ... (cyclic),  dL/dR_kk += 1/2 dL/dc.
+// k_limit_fwd: 32 lanes per frame, two frames per 64-thread block (a frame has 23 joints: a wave per frame would leave 41 lanes
+// idle; F odd leaves the last block's upper half idle).  Lane l < 23 of a half takes joint l + 1: raw entries and the six bounds
+// in one round trip, R, omega, the hinges, dL/dR, and the stage's normalisation backward (gs6d_backward) on its own raw entries:
+// it writes the gradient in PARAMETER space, [F][23][9], third rows exact zeros when the stage normalises.  The frame's 69
+// squares: every lane adds its three in the order x, y, z, then a fixed xor butterfly (16, 8, .. 1) inside the half adds the
+// lanes (lanes 23 .. 31 hold zeros).  No atomics, no LDS: bit-reproducible.
+// ----------------------------------------------------------------------------------------------------
+#define UUO_LIM_FPB 2  // frames per block
+struct LimitFwdArgs {
+  uuo_gptr<const float> body;  // [F][23][9] raw body pose entries (UuoPoseSrc.body)
+  uuo_gptr<const float> tab;   // [2][23][3] lo, hi
+  int F, norm_body;
+  float cl, cg;                // w / F, 2 w / F
+  uuo_gptr<float> g;           // [F][23][9] out
+  uuo_gptr<float> loss;        // [F] out
+};
+__global__ __launch_bounds__(64) void k_limit_fwd(LimitFwdArgs a) {
+  const int half = threadIdx.x >> 5, l = threadIdx.x & 31;
+  const int f = blockIdx.x * UUO_LIM_FPB + half;
+  const bool on = f < a.F && l < 23;
+  float raw[9], lo[3], hi[3];
+#pragma unroll
+  for (int e = 0; e < 9; ++e) raw[e] = on ? a.body[((size_t)f * 23 + l) * 9 + e] : ((e == 0 || e == 4 || e == 8) ? 1.f : 0.f);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    lo[k] = on ? a.tab[l * 3 + k] : -INFINITY;
+    hi[k] = on ? a.tab[69 + l * 3 + k] : INFINITY;
+  }
+  float R[9];
+  if (a.norm_body) {
+    gs6d_forward(raw, R);
+  } else {
+#pragma unroll
+    for (int e = 0; e < 9; ++e) R[e] = raw[e];
+  }
+  const float s[3] = {0.5f * (R[7] - R[5]), 0.5f * (R[2] - R[6]), 0.5f * (R[3] - R[1])};
+  const float c = 0.5f * (((R[0] + R[4]) + R[8]) - 1.f);
+  const float n2 = (s[0] * s[0] + s[1] * s[1]) + s[2] * s[2];
+  const float n = sqrtf(n2);
+  const bool small = n < 1e-4f;
+  const bool skip = small && c < 0.f;
+  const float nn = small ? 1.f : n;  // (keeps the quotients of the unused branch finite)
+  const float theta = atan2f(n, c);
+  const float kappa = small ? 1.f : theta / nn;
+  const float den = small ? 1.f : n2 + c * c;
+  const float dkn = small ? 0.f : (c / (nn * den) - theta / (nn * nn));
+  const float dkc = small ? 0.f : (-1.f / den);
+  float g[3], part = 0.f;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float om = kappa * s[k];
+    const float up = fmaxf(om - hi[k], 0.f), dn = fmaxf(lo[k] - om, 0.f);
+    const float pen = (skip || !on) ? 0.f : up + dn;
+    g[k] = (skip || !on) ? 0.f : a.cg * (up - dn);
+    part += pen * pen;
+  }
+  const float q = (s[0] * g[0] + s[1] * g[1]) + s[2] * g[2];
+  const float qn = q * dkn / nn;
+  const float ds[3] = {0.5f * (kappa * g[0] + qn * s[0]), 0.5f * (kappa * g[1] + qn * s[1]), 0.5f * (kappa * g[2] + qn * s[2])};
+  const float dc = 0.5f * (q * dkc);
+  const float dR[9] = {dc, -ds[2], ds[1], ds[2], dc, -ds[0], -ds[1], ds[0], dc};
+  float out[9];
+  if (a.norm_body) {
+    float da[6];
+    gs6d_backward(raw, dR, da);
+#pragma unroll
+    for (int e = 0; e < 6; ++e) out[e] = da[e];
+    out[6] = out[7] = out[8] = 0.f;
+  } else {
+#pragma unroll
+    for (int e = 0; e < 9; ++e) out[e] = dR[e];
+  }
+  if (on) {
+#pragma unroll
+    for (int e = 0; e < 9; ++e) a.g[((size_t)f * 23 + l) * 9 + e] = out[e];
+  }
+  // the frame's share: the lanes' sums (each x, y, z in order) through a fixed butterfly inside the 32-lane half
+#pragma unroll
+  for (int m = 16; m >= 1; m >>= 1) part += __shfl_xor(part, m, 64);
+  if (l == 0 && f < a.F) a.loss[f] = a.cl * part;
+}
+
+// ----------------------------------------------------------------------------------------------------
 // EXTENSION (not reference behaviour; uuo_fit_set_surface): the chamfer stage's data term as a point-to-surface distance
 // with a stand-off.  k_ring_pick (nn_kernels.hip) has chosen, for every (frame, marker), the face of the nearest vertex's
 // one-ring that lies closest in the search's vertex buffer; this pass is k_bary_fwd with those corners read per frame and the
@@ -2009,6 +2122,14 @@ static int validate_problem(const uuo_fit* fit, const uuo_problem_t* p) {
               "term (w_soft)");
   UUO_REQUIRE(fit->cap_w == 0.f || !uuo_recorder,
               "closure: lock-step batches do not carry the self-penetration term (uuo_fit_set_capsules, extension)");
+  // EXTENSION: the joint-angle limit term of the workspace (uuo_fit_set_joint_limits) likewise
+  UUO_REQUIRE(fit->lim_w == 0.f || p->stage != UUO_STAGE_PART,
+              "closure: the joint-angle limit term (uuo_fit_set_joint_limits, extension) is not built for the part stage");
+  UUO_REQUIRE(fit->lim_w == 0.f || p->w_soft == 0.f,
+              "closure: the joint-angle limit term (uuo_fit_set_joint_limits, extension) is not built for the soft-assignment data "
+              "term (w_soft)");
+  UUO_REQUIRE(fit->lim_w == 0.f || !uuo_recorder,
+              "closure: lock-step batches do not carry the joint-angle limit term (uuo_fit_set_joint_limits, extension)");
   // EXTENSION: latent marker offsets
   UUO_REQUIRE(p->w_offsets == 0.f || (p->w_offsets > 0.f && p->w_offsets <= 3.0e38f),
               "closure: w_offsets (latent marker offsets, extension) must be 0 (off) or a positive finite weight");
@@ -2193,6 +2314,50 @@ extern "C" int uuo_fit_set_capsules(uuo_fit_t* fit, float w, int32_t n_caps, con
     fit->cap_p = P;
   }
   fit->cap_w = w;
+  return 0;
+}
+
+extern "C" int uuo_fit_set_joint_limits(uuo_fit_t* fit, float w, const float* h_lo, const float* h_hi) {
+  UUO_REQUIRE(fit, "uuo_fit_set_joint_limits: null fit");
+  UUO_REQUIRE(w == 0.f || (w > 0.f && w <= 3.0e38f), "uuo_fit_set_joint_limits: the weight must be 0 (off) or a positive finite number");
+  if (w == 0.f) {  // off: nothing else is looked at (the table stays for the next call with the same bounds)
+    fit->lim_w = 0.f;
+    return 0;
+  }
+  UUO_REQUIRE(h_lo && h_hi, "uuo_fit_set_joint_limits: a positive weight needs the bounds lo [23][3] and hi [23][3] (host arrays)");
+  UUO_REQUIRE(!uuo_recorder, "uuo_fit_set_joint_limits: lock-step batches do not carry the joint-angle limit term");
+  for (int i = 0; i < 69; ++i) {
+    const float lo = h_lo[i], hi = h_hi[i];
+    UUO_REQUIRE(lo == lo && hi == hi, "uuo_fit_set_joint_limits: a bound is NaN");
+    UUO_REQUIRE(lo <= 3.0e38f, "uuo_fit_set_joint_limits: a lower bound of +inf admits no angle (-inf = no bound)");
+    UUO_REQUIRE(hi >= -3.0e38f, "uuo_fit_set_joint_limits: an upper bound of -inf admits no angle (+inf = no bound)");
+    UUO_REQUIRE(lo <= hi, "uuo_fit_set_joint_limits: lo > hi");
+  }
+  if (!fit->lim_tab) {  // first use: the table and the upload stream
+    UUO_HIP_CHECK(hipMalloc((void**)&fit->lim_tab, 2 * 69 * sizeof(float)));
+    fit->lim_have = false;
+    UUO_HIP_CHECK(hipStreamCreateWithFlags(&fit->lim_stream, hipStreamNonBlocking));
+  }
+  if (!fit->lim_g) UUO_HIP_CHECK(hipMalloc((void**)&fit->lim_g, ((size_t)fit->F * 207 + fit->F) * sizeof(float)));
+  const bool same = fit->lim_have && std::memcmp(fit->lim_h, h_lo, 69 * sizeof(float)) == 0 &&
+                    std::memcmp(fit->lim_h + 69, h_hi, 69 * sizeof(float)) == 0;
+  if (!same) {
+    fit->lim_w = 0.f;
+    fit->lim_have = false;
+    // the only reader of the old table is the last k_limit_fwd launched on this workspace: wait for its stream alone (no
+    // device-wide wait: other threads' workspaces keep running; nothing is added to an evaluation), upload on the workspace's
+    // own non-blocking stream, and return once the copy has landed, so that every later launch sees it
+    if (fit->lim_launched) UUO_HIP_CHECK(hipStreamSynchronize(fit->lim_last_stream));
+    fit->lim_launched = false;
+    static thread_local float h_tab[2 * 69];
+    std::memcpy(h_tab, h_lo, 69 * sizeof(float));
+    std::memcpy(h_tab + 69, h_hi, 69 * sizeof(float));
+    UUO_HIP_CHECK(hipMemcpyAsync(fit->lim_tab, h_tab, sizeof(h_tab), hipMemcpyHostToDevice, fit->lim_stream));
+    UUO_HIP_CHECK(hipStreamSynchronize(fit->lim_stream));
+    std::memcpy(fit->lim_h, h_tab, sizeof(h_tab));
+    fit->lim_have = true;
+  }
+  fit->lim_w = w;
   return 0;
 }
 
@@ -2646,10 +2811,7 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
   // frames' shares, the temporal instantiations add them to uj and slot 3 (cap_up != null).  Frames are not coupled: any F.
   const bool caps = fit->cap_w != 0.f;
   UUO_REQUIRE(!caps || !uuo_recorder, "closure: lock-step batches do not carry the self-penetration term");
-  if (caps) {
-    a.cap_up = fit->cap_up;
-    a.cap_loss = fit->cap_up + (size_t)F * 72;
-  }
+  if (caps) a.cap_up = fit->cap_up;  // ([F][72] gradients, then the [F] shares)
   auto launch_caps = [&]() {
     if (!caps) return;
     CapsFwdArgs b;
@@ -2666,7 +2828,30 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
     fit->cap_launched = true;  // (uuo_fit_set_capsules waits for this stream before it replaces the tables)
     fit->cap_last_stream = s;
   };
-  const bool temporal = accel || lock || floor || caps;
+  // EXTENSION: the joint-angle limit term: k_limit_fwd (launch_limits below, beside launch_caps) leaves the parameter-space
+  // gradients and the frames' shares, the temporal instantiations add them to gout and slot 3 (lim_g != null).  Any F.
+  const bool limits = fit->lim_w != 0.f;
+  UUO_REQUIRE(!limits || !uuo_recorder, "closure: lock-step batches do not carry the joint-angle limit term");
+  UUO_REQUIRE(!limits || (p->stage != UUO_STAGE_PART && !soft_chamfer),
+              "closure: the joint-angle limit term belongs to the chamfer and marker stages' hard-assignment closures");
+  if (limits) a.lim_g = fit->lim_g;  // ([F][207] gradients, then the [F] shares)
+  auto launch_limits = [&]() {
+    if (!limits) return;
+    LimitFwdArgs b;
+    std::memset(&b, 0, sizeof(b));
+    b.body = src.body;
+    b.tab = fit->lim_tab;
+    b.F = F;
+    b.norm_body = src.norm_body;
+    b.cl = (float)((double)fit->lim_w / (double)F);
+    b.cg = (float)(2.0 * (double)fit->lim_w / (double)F);
+    b.g = fit->lim_g;
+    b.loss = fit->lim_g + (size_t)F * 207;
+    hipLaunchKernelGGL(k_limit_fwd, dim3((F + UUO_LIM_FPB - 1) / UUO_LIM_FPB), dim3(64), 0, s, b);
+    fit->lim_launched = true;  // (uuo_fit_set_joint_limits waits for this stream before it replaces the table)
+    fit->lim_last_stream = s;
+  };
+  const bool temporal = accel || lock || floor || caps || limits;
   a.h.gx = F;
   a.h.gy = 1;
   FinArgs fa;
@@ -2755,6 +2940,7 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
       hipLaunchKernelGGL(k_bary_fwd, dim3(F), dim3(BWD_NW * 64), 0, s, b);
     launch_floor();
     launch_caps();
+    launch_limits();
     a.M = 3 * M;
     a.up_items = items;
     a.item_loss = item_loss;
@@ -2801,6 +2987,7 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
     hipLaunchKernelGGL(robust ? k_surf_fwd_r : k_surf_fwd, dim3(F), dim3(BWD_NW * 64), 0, s, b);
     launch_floor();
     launch_caps();
+    launch_limits();
     a.M = 3 * M;
     a.assign = fit->surf_corners;
     a.up_items = items;
@@ -2845,6 +3032,7 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
         a.frames = fit->frames;
         launch_floor();
         launch_caps();
+        launch_limits();
         if (floor)
           hipLaunchKernelGGL(robust ? k_bwd_sparse_r_t_o_fl : k_bwd_sparse_t_o_fl, dim3(F), dim3(BWD_NW * 64), 0, s, a);
         else
@@ -2863,6 +3051,7 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
       }
       launch_floor();
       launch_caps();
+      launch_limits();
       if (floor)
         hipLaunchKernelGGL(robust ? k_bwd_sparse_r_t_fl : k_bwd_sparse_t_fl, dim3(F), dim3(BWD_NW * 64), 0, s, a);
       else if (fassign)

@@ -225,6 +225,18 @@ struct uuo_fit {
   bool cap_launched = false;
   hipStream_t cap_last_stream = nullptr;
   hipStream_t cap_stream = nullptr;
+  // EXTENSION: the joint-angle limit term on the body pose (uuo_fit_set_joint_limits; lim_w == 0 = off): weight, the host copies
+  // of the caller's tables (compared at the next call: unchanged tables are not uploaded again; lim_have = they are valid), the
+  // workspace's own device table lim_tab [2][23][3] (lo, then hi) and [F][23][9] parameter-space gradients + [F] loss shares
+  // (k_limit_fwd -> the backward kernels); the last reader's stream and the upload stream as for the capsules' lists
+  float lim_w = 0.f;
+  bool lim_have = false;
+  float lim_h[2 * 69];
+  float* lim_tab = nullptr;
+  float* lim_g = nullptr;
+  bool lim_launched = false;
+  hipStream_t lim_last_stream = nullptr;
+  hipStream_t lim_stream = nullptr;
   int surface = 0;               // EXTENSION: point-to-surface chamfer term (uuo_fit_set_surface; 0 = off) and its stand-off
   float surface_distance = 0.f;
   const int32_t* frame_assign = nullptr;  // EXTENSION: [F][M] per-frame vertex table of the marker stage (uuo_fit_set_frame_assign;

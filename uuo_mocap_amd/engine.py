@@ -177,6 +177,9 @@ def solve_batch(problems, xs, max_iter: int, lr: float = 1.0, tolerance_grad: fl
     if any(getattr(p, "capsules_on", False) for p in problems):
         raise NotImplementedError("lock-step batches do not carry the self-penetration term (self_penetration, extension): "
                                   "solve such problems one by one")
+    if any(getattr(p, "joint_limits_on", False) for p in problems):
+        raise NotImplementedError("lock-step batches do not carry the joint-angle limit term (joint_limits, extension): "
+                                  "solve such problems one by one")
     if any(getattr(p, "frame_assign", None) is not None for p in problems):
         raise NotImplementedError("lock-step batches do not carry the per-frame vertex table (tracklets, extension): "
                                   "solve such problems one by one")
@@ -528,6 +531,34 @@ class _StageProblem:
         self.cap_joints = None  # [C, 2] int32 numpy
         self.cap_geom = None    # [C, 3] float32 numpy: alpha, beta, radius
         self.cap_pairs = None   # [P, 2] int32 numpy
+        # EXTENSION: the joint-angle limit term on the body pose (ChamferProblem / MarkerProblem), armed the same way
+        # (uuo_fit_set_joint_limits): weight and the two HOST tables, which the library checks and copies at the call
+        self.lim_w = 0.0
+        self.lim_lo = None  # [23, 3] float32 numpy (row j - 1 is SMPL joint j; -inf = no bound)
+        self.lim_hi = None  # [23, 3] float32 numpy (+inf = no bound)
+
+    @property
+    def joint_limits_on(self) -> bool:
+        """EXTENSION: True when this problem arms the joint-angle limit term with a non-zero weight."""
+        return self.lim_w != 0.0
+
+    def _set_joint_limits(self, lim: Dict):
+        """EXTENSION: `lim` is stage_joint_limits' record.  Keeps the weight and contiguous host copies of the two tables (the
+        configured ones, or body_model.smpl_joint_limits(), looked at only when the term is on without a `joint_limits` block).
+        With weight 0 nothing is armed and the problem runs the plain kernels, bit for bit."""
+        w = float(lim["w"])
+        if w == 0.0:
+            return
+        tabs = lim["limits"]
+        if tabs is None:
+            from .body_model import smpl_joint_limits
+
+            lo, hi = smpl_joint_limits()
+        else:
+            lo, hi = tabs["lo"], tabs["hi"]
+        self.lim_lo = np.ascontiguousarray(np.asarray(lo, dtype=np.float32).reshape(23, 3))
+        self.lim_hi = np.ascontiguousarray(np.asarray(hi, dtype=np.float32).reshape(23, 3))
+        self.lim_w = w
 
     @property
     def capsules_on(self) -> bool:
@@ -619,6 +650,11 @@ class _StageProblem:
                   "uuo_fit_set_capsules")
         else:
             check(self.lib.uuo_fit_set_capsules(self.fit, c_float(0.0), 0, None, None, 0, None), "uuo_fit_set_capsules")
+        if self.joint_limits_on:
+            check(self.lib.uuo_fit_set_joint_limits(self.fit, c_float(self.lim_w), self.lim_lo.ctypes.data, self.lim_hi.ctypes.data),
+                  "uuo_fit_set_joint_limits")
+        else:
+            check(self.lib.uuo_fit_set_joint_limits(self.fit, c_float(0.0), None, None), "uuo_fit_set_joint_limits")
 
     def _need_workspace(self):
         if self.fit is None:  # created for a lock-step batch only: give it the thread's workspace on first standalone use
@@ -915,6 +951,36 @@ def stage_capsules(config: Dict, stage: str) -> Dict:
     return {"w": v, "capsules": caps}
 
 
+def stage_joint_limits(config: Dict, stage: str) -> Dict:
+    """EXTENSION: the joint-angle limit term of the chamfer or marker stage (uuo_fit_set_joint_limits) as a config states it --
+    stages.<stage>.losses.joint_limits (a weight on rad^2; absent or 0 = off; negative or non-finite weights are refused) and
+    stages.<stage>.joint_limits: null (body_model.smpl_joint_limits()) or {lo: [[x, y, z] x 23], hi: [[x, y, z] x 23]} in
+    radians on the components of each body joint's axis-angle vector (row j - 1 is SMPL joint j; -.inf / .inf = no bound;
+    lo <= hi, no NaN, lo < +inf, hi > -inf).  Returns {"w", "limits"}.  (The part stage refuses the key with its other unknown
+    losses.)"""
+    st = config["stages"][stage]
+    losses = st.get("losses") or {}
+    v = losses.get("joint_limits", 0.0)
+    v = 0.0 if v is None else float(v)
+    if not math.isfinite(v) or v < 0.0:
+        raise ValueError("stages.%s.losses.joint_limits must be 0 (off) or a positive weight (got %r)" % (stage, v))
+    lim = st.get("joint_limits", None)
+    if lim is not None:
+        def table(x):
+            return isinstance(x, (list, tuple)) and len(x) == 23 and \
+                all(isinstance(r, (list, tuple)) and len(r) == 3 and
+                    all(isinstance(q, (int, float)) and not isinstance(q, bool) and not math.isnan(q) for q in r) for r in x)
+
+        ok = isinstance(lim, dict) and set(lim) == {"lo", "hi"} and table(lim["lo"]) and table(lim["hi"])
+        if ok:
+            ok = all(a <= b and a < math.inf and b > -math.inf for ra, rb in zip(lim["lo"], lim["hi"]) for a, b in zip(ra, rb))
+        if not ok:
+            raise ValueError("stages.%s.joint_limits must be null or {lo: [[x, y, z] x 23], hi: [[x, y, z] x 23]} in radians with "
+                             "lo <= hi, no NaN, lo < +inf and hi > -inf (-.inf / .inf = no bound; got %r)" % (stage, lim))
+        lim = {"lo": [[float(q) for q in r] for r in lim["lo"]], "hi": [[float(q) for q in r] for r in lim["hi"]]}
+    return {"w": v, "limits": lim}
+
+
 def check_foot_contacts(foot_contacts, num_frames=None):
     """EXTENSION: the foot-lock term's contact labels as a float32 host tensor [F, 2] (left, right foot; None stays None).
     Shape, finiteness and the range [0, 1] are checked on the host: ValueError before anything touches the device."""
@@ -941,13 +1007,18 @@ class ChamferProblem(_StageProblem):
     def __init__(self, smpl_inference, markers, o_pose_body, o_betas, root_orient, config, foot_contacts=None):
         losses = config["stages"]["chamfer"]["losses"]
         unsupported = set(losses) - {"full_chamfer", "reg_pose_body", "reg_betas", "soft_chamfer", "joint_accel", "foot_lock",
-                                     "surface_chamfer", "floor_penetration", "floor_contact", "self_penetration"}
+                                     "surface_chamfer", "floor_penetration", "floor_contact", "self_penetration",
+                                     "joint_limits"}
         if unsupported:
             raise NotImplementedError("chamfer-stage losses outside the shipped configs: %s" % sorted(unsupported))
         w_surface, d_surface = stage_surface(config)  # EXTENSION: point-to-surface data term (0 = off)
         caps = stage_capsules(config, "chamfer")  # EXTENSION: bone-capsule self-penetration term (0 = off)
         if caps["w"] > 0.0 and float(losses.get("soft_chamfer", 0.0)) != 0.0:
             raise NotImplementedError("stages.chamfer: the fused self-penetration term (self_penetration) is not built for the "
+                                      "soft-assignment closure; optim_chamfer composes that combination from the operators")
+        lim = stage_joint_limits(config, "chamfer")  # EXTENSION: joint-angle limit term on the body pose (0 = off)
+        if lim["w"] > 0.0 and float(losses.get("soft_chamfer", 0.0)) != 0.0:
+            raise NotImplementedError("stages.chamfer: the fused joint-angle limit term (joint_limits) is not built for the "
                                       "soft-assignment closure; optim_chamfer composes that combination from the operators")
         w_accel = stage_joint_accel(config, "chamfer")
         if w_accel > 0.0 and float(losses.get("soft_chamfer", 0.0)) != 0.0:
@@ -977,6 +1048,7 @@ class ChamferProblem(_StageProblem):
         self._set_foot_lock(w_lock, contacts)  # EXTENSION: foot-lock term (weight 0 without gated contacts)
         self._set_floor(floor, contacts, smpl_inference)  # EXTENSION: floor-contact term on sole vertices
         self._set_capsules(caps, smpl_inference)  # EXTENSION: bone-capsule self-penetration term
+        self._set_joint_limits(lim)  # EXTENSION: joint-angle limit term on the body pose
         # EXTENSION (not in the reference): soft assignment of every marker to the body's vertices, fused closure with the dense
         # backward on the matrix pipe (csrc/dense_bwd.hip); not available inside lock-step batches
         w_soft = float(losses.get("soft_chamfer", 0.0))
@@ -1020,12 +1092,13 @@ class MarkerProblem(_StageProblem):
         an entry < 0 is an item of weight 0); `assign` may then be None.  Refused with `bary` and with latent_offsets."""
         st = config["stages"]["marker"]
         unsupported = set(st["losses"]) - {"marker", "reg_pose_body", "reg_betas", "joint_accel", "latent_offsets", "foot_lock",
-                                           "floor_penetration", "floor_contact", "self_penetration"}
+                                           "floor_penetration", "floor_contact", "self_penetration", "joint_limits"}
         if unsupported:
             raise NotImplementedError("marker-stage losses outside the shipped configs: %s" % sorted(unsupported))
         if st.get("use_sdf"):
             raise NotImplementedError("stages.marker.use_sdf is off in every shipped config")
         floor = stage_floor(config, "marker")
+        lim = stage_joint_limits(config, "marker")  # EXTENSION: joint-angle limit term on the body pose (0 = off)
         caps = stage_capsules(config, "marker")  # EXTENSION: bone-capsule self-penetration term (0 = off)
         if frame_assign is not None and (floor["w_pen"] > 0.0 or floor["w_con"] > 0.0):
             raise NotImplementedError("the per-frame vertex table (tracklets, extension) is not built for the floor-contact term "
@@ -1056,6 +1129,7 @@ class MarkerProblem(_StageProblem):
         self._set_foot_lock(w_lock, contacts)  # EXTENSION: foot-lock term (weight 0 without gated contacts)
         self._set_floor(floor, contacts, smpl_inference)  # EXTENSION: floor-contact term on sole vertices
         self._set_capsules(caps, smpl_inference)  # EXTENSION: bone-capsule self-penetration term
+        self._set_joint_limits(lim)  # EXTENSION: joint-angle limit term on the body pose
         if frame_assign is not None:  # EXTENSION: per-frame vertex table (the *_f kernel instantiations)
             self.frame_assign = frame_assign.to(device=self.device, dtype=torch.int32).contiguous()
         if w_offsets > 0.0:  # EXTENSION: latent per-marker offsets, 3 M more parameters after trans

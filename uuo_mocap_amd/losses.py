@@ -323,3 +323,30 @@ def self_penetration_loss(joints: torch.Tensor, cap_joints, cap_geom, pairs, w: 
     d = torch.where(pos, torch.sqrt(torch.where(pos, d2, torch.ones_like(d2))), torch.zeros_like(d2))
     pen = torch.relu(cg[pr[:, 0], 2] + cg[pr[:, 1], 2] - d)
     return float(w) * (pen * pen).sum() / joints.shape[0]
+
+
+def joint_limit_loss(rot_body: torch.Tensor, lo, hi, w: float) -> torch.Tensor:
+    """EXTENSION (not in the reference): the joint-angle limit term of the fused chamfer and marker closures
+    (uuo_fit_set_joint_limits), composed -- their checker.  rot_body [F, 23, 3, 3] are the body joints' local rotations after the
+    stage's normalisation, lo / hi [23, 3] bounds in radians on the components of each joint's axis-angle vector (-inf / +inf =
+    no bound):  w sum_t sum_j sum_k (max(omega_k - hi, 0) + max(lo - omega_k, 0))^2 / F  with
+    s = 1/2 (R21 - R12, R02 - R20, R10 - R01), c = 1/2 (tr R - 1), n = |s|, omega = (atan2(n, c) / n) s.  The branches are chosen
+    under no_grad and in the tensors' own precision -- n < 1e-4 and c >= 0: omega = s (identity branch, kappa = 1, d kappa = 0);
+    n < 1e-4 and c < 0: the joint contributes nothing (half turn) --, everything else is under autograd."""
+    dev, dt = rot_body.device, rot_body.dtype
+    lo = torch.as_tensor(np.asarray(lo, dtype=np.float64), dtype=dt, device=dev).reshape(23, 3)
+    hi = torch.as_tensor(np.asarray(hi, dtype=np.float64), dtype=dt, device=dev).reshape(23, 3)
+    R = rot_body
+    s = 0.5 * torch.stack([R[..., 2, 1] - R[..., 1, 2], R[..., 0, 2] - R[..., 2, 0], R[..., 1, 0] - R[..., 0, 1]], dim=-1)
+    c = 0.5 * (R[..., 0, 0] + R[..., 1, 1] + R[..., 2, 2] - 1.0)
+    n2 = (s * s).sum(-1)
+    with torch.no_grad():
+        small = torch.sqrt(n2) < 1e-4
+        skip = small & (c < 0.0)
+    one = torch.ones_like(n2)
+    n = torch.sqrt(torch.where(small, one, n2))  # (the identity and half-turn branches never use the quotient)
+    kappa = torch.where(small, one, torch.atan2(n, torch.where(small, one, c)) / n)
+    om = kappa[..., None] * s
+    pen = torch.relu(om - hi) + torch.relu(lo - om)
+    pen = torch.where(skip[..., None], torch.zeros_like(pen), pen)
+    return float(w) * (pen * pen).sum() / rot_body.shape[0]

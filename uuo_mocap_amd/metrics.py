@@ -7,6 +7,7 @@ from __future__ import annotations
 
 from typing import Dict, List
 
+import numpy as np
 import torch
 
 
@@ -107,6 +108,20 @@ def compute_self_penetration(joints: torch.Tensor, cap_joints, cap_geom, pairs) 
     deepest = pen.max(axis=1)
     return {"max_depth_mm": float(deepest.max()) * 1e3, "mean_depth_mm": float(deepest.mean()) * 1e3,
             "frames_pct": 100.0 * float((deepest > 0.0).mean())}
+
+
+def compute_joint_limit_violation(rot_body: torch.Tensor, lo, hi) -> Dict[str, float]:
+    """Joint-limit violation (not a metric of the reference) of body rotations [F, 23, 3, 3] under the tables of the joint-angle
+    limit term (lo / hi [23, 3], radians; body_model.smpl_joint_limits builds the default), float64, in degrees: `max_deg` the
+    largest pen = max(omega - hi, 0) + max(lo - omega, 0) of any component of any joint in any frame, `mean_deg` the mean over
+    frames of the frame's largest pen, `frames_pct` the share of frames with any violation."""
+    from .body_model import joint_limit_violation
+
+    if rot_body.dim() != 4 or tuple(rot_body.shape[1:]) != (23, 3, 3):
+        raise ValueError("compute_joint_limit_violation: rot_body [F, 23, 3, 3] expected (got %s)" % (tuple(rot_body.shape),))
+    pen = joint_limit_violation(rot_body.detach().cpu().double().numpy(), lo, hi)
+    worst = np.degrees(pen.reshape(pen.shape[0], -1).max(axis=1))
+    return {"max_deg": float(worst.max()), "mean_deg": float(worst.mean()), "frames_pct": 100.0 * float((worst > 0.0).mean())}
 
 
 def compute_PA_MPJPE(pred_joints: torch.Tensor, gt_joints: torch.Tensor) -> torch.Tensor:

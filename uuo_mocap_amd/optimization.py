@@ -14,9 +14,9 @@ import torch.nn.functional as F
 from .device_lbfgs import DeviceLBFGS
 from .config import stage_surface
 from .engine import (MARKER_DISTANCE, ChamferProblem, MarkerProblem, check_foot_contacts, stage_capsules, stage_floor, stage_foot_lock,
-                     stage_joint_accel, stage_latent_offsets, stage_robust_sigma)
+                     stage_joint_accel, stage_joint_limits, stage_latent_offsets, stage_robust_sigma)
 from .losses import (MarkerLoss, RobustMarkerLoss, chamfer_distance, floor_loss, foot_lock_loss, joint_accel_loss,  # noqa: F401  (re-exported)
-                     self_penetration_loss,
+                     self_penetration_loss, joint_limit_loss,
                      robust_weighted_chamfer_distance, soft_weighted_chamfer_distance, surface_chamfer_distance,
                      weighted_chamfer_distance)
 from .smpl import SmplInference
@@ -74,9 +74,10 @@ def optim_chamfer(
         # execution.chamfer_soft_fused: False keeps the operator-composed closure, its checker
         fused_losses = _CHAMFER_FUSED_LOSSES | {"soft_chamfer"}
     if "soft_chamfer" in fused_losses and (stage_joint_accel(config, "chamfer") > 0.0 or stage_foot_lock(config, "chamfer") > 0.0 or
-                                           _floor_on(config, "chamfer") or _capsules_on(config, "chamfer")):
-        # EXTENSION: the temporal terms, the floor-contact term and the self-penetration term have no instantiation of the dense
-        # backward (k_bwd_dense): composed closure
+                                           _floor_on(config, "chamfer") or _capsules_on(config, "chamfer") or
+                                           _limits_on(config, "chamfer")):
+        # EXTENSION: the temporal terms, the floor-contact term, the self-penetration term and the joint-angle limit term have no
+        # instantiation of the dense backward (k_bwd_dense): composed closure
         fused_losses = _CHAMFER_FUSED_LOSSES
     w_surface, _ = stage_surface(config)  # EXTENSION: point-to-surface data term (validates the keys)
     if w_surface > 0.0:
@@ -92,7 +93,7 @@ def optim_chamfer(
         fused_losses = fused_losses | {"surface_chamfer"}
     if (set(st["losses"]) - fused_losses) or not st["yaw_lock"] or not _robust_fused(config, "chamfer") or \
             not _temporal_fused(config, "chamfer") or not _floor_fused(config, "chamfer") or \
-            not _capsule_fused(config, "chamfer"):
+            not _capsule_fused(config, "chamfer") or not _limit_fused(config, "chamfer"):
         return _optim_chamfer_general(markers, pose_body, o_pose_body, betas, o_betas, root_orient, trans, marker_labels,
                                       smpl_inference, config, initial_angle, repeat, verbose, iter_fn, foot_contacts)
     from .parallel import frame_shard
@@ -271,6 +272,33 @@ def _composed_capsules(config: Dict, stage: str, smpl_inference):
     return lambda joints: self_penetration_loss(joints[:, :24], cj, cg, pr, caps["w"])
 
 
+def _limits_on(config: Dict, stage: str) -> bool:
+    """True when the stage's EXTENSION joint-angle limit term has a non-zero weight (stages.<stage>.losses.joint_limits;
+    validates the keys)."""
+    return stage_joint_limits(config, stage)["w"] > 0.0
+
+
+def _limit_fused(config: Dict, stage: str) -> bool:
+    """False when the stage's EXTENSION joint-angle limit term is to run on the closure composed from the operators
+    (execution.limit_fused: False, the fused closures' checker); True otherwise."""
+    return not _limits_on(config, stage) or bool((config.get("execution") or {}).get("limit_fused", True))
+
+
+def _composed_limits(config: Dict, stage: str):
+    """The joint-angle limit term of the composed closures: None when off, else a function of the normalised body rotations
+    [F, 23, 3, 3] -- joint_limit_loss on the configured tables (body_model.smpl_joint_limits() by default)."""
+    lim = stage_joint_limits(config, stage)
+    if lim["w"] == 0.0:
+        return None
+    if lim["limits"] is None:
+        from .body_model import smpl_joint_limits
+
+        lo, hi = smpl_joint_limits()
+    else:
+        lo, hi = lim["limits"]["lo"], lim["limits"]["hi"]
+    return lambda rot_body: joint_limit_loss(rot_body, lo, hi, lim["w"])
+
+
 def _refuse_latent_offsets(config: Dict, route: str):
     if stage_latent_offsets(config) > 0.0:
         raise NotImplementedError("stages.marker.losses.latent_offsets (latent marker offsets, extension) is built for the fused "
@@ -290,6 +318,9 @@ def _refuse_sharded_joint_accel(config: Dict, stage: str):
     if _capsules_on(config, stage):
         raise NotImplementedError("stages.%s.losses.self_penetration (extension): the self-penetration term is not built for "
                                   "frame-block sharding (parallel.shard_frames)" % stage)
+    if _limits_on(config, stage):
+        raise NotImplementedError("stages.%s.losses.joint_limits (extension): the joint-angle limit term is not built for "
+                                  "frame-block sharding (parallel.shard_frames)" % stage)
 
 
 def lockstep_supported(config: Dict, stage: str) -> bool:
@@ -308,6 +339,8 @@ def lockstep_supported(config: Dict, stage: str) -> bool:
         return False
     if _capsules_on(config, stage):  # EXTENSION: nor the self-penetration term
         return False
+    if _limits_on(config, stage):  # EXTENSION: nor the joint-angle limit term
+        return False
     if stage == "marker" and stage_latent_offsets(config) > 0.0:  # EXTENSION: nor the latent marker offsets
         return False
     if stage == "chamfer" and stage_surface(config)[0] > 0.0:  # EXTENSION: nor the point-to-surface chamfer term
@@ -317,7 +350,8 @@ def lockstep_supported(config: Dict, stage: str) -> bool:
     if stage == "chamfer":
         return not (set(st["losses"]) - _CHAMFER_FUSED_LOSSES - {"surface_chamfer"}) and bool(st["yaw_lock"])
     return not (set(st["losses"]) - {"marker", "reg_pose_body", "reg_betas", "joint_accel", "latent_offsets", "foot_lock",
-                                     "floor_penetration", "floor_contact", "self_penetration"}) and not st.get("use_sdf")
+                                     "floor_penetration", "floor_contact", "self_penetration", "joint_limits"}) and \
+        not st.get("use_sdf")
 
 
 def optim_chamfer_lockstep(markers, hyps, o_pose_body, o_betas, smpl_inference, config):
@@ -418,7 +452,7 @@ def _solve(prob, x, config, stage: str, lr: float, verbose_tag: str, verbose: bo
 
 #: chamfer-stage loss terms the device solver fuses (the only ones the shipped configs enable)
 _CHAMFER_FUSED_LOSSES = {"full_chamfer", "reg_pose_body", "reg_betas", "joint_accel", "foot_lock", "floor_penetration",
-                         "floor_contact", "self_penetration"}
+                         "floor_contact", "self_penetration", "joint_limits"}
 
 
 def _optim_chamfer_general(markers, pose_body, o_pose_body, betas, o_betas, root_orient, trans, marker_labels,
@@ -444,6 +478,7 @@ def _optim_chamfer_general(markers, pose_body, o_pose_body, betas, o_betas, root
         contacts = contacts.to(device)
     floor_term = _composed_floor(config, "chamfer", contacts, smpl_inference)  # EXTENSION: floor-contact term on sole vertices
     caps_term = _composed_capsules(config, "chamfer", smpl_inference)  # EXTENSION: bone-capsule self-penetration term
+    lim_term = _composed_limits(config, "chamfer")  # EXTENSION: joint-angle limit term on the body pose
     num_frames = pose_body.shape[0]
     root_fixed = root_orient.detach().clone()
     if st["yaw_lock"]:
@@ -498,6 +533,8 @@ def _optim_chamfer_general(markers, pose_body, o_pose_body, betas, o_betas, root
             loss = loss + floor_term(out["vertices"])
         if caps_term is not None:  # EXTENSION: the fused closures' self-penetration term, composed (their checker)
             loss = loss + caps_term(out["joints"])
+        if lim_term is not None:  # EXTENSION: the fused closures' joint-angle limit term, composed (their checker)
+            loss = loss + lim_term(normalize_rot(p_pose))
         loss.backward()
         if verbose:
             print("Chamfer", n_eval[0], float(loss))
@@ -568,9 +605,9 @@ def optim_markers(
     sharded = fs is not None and fs.active
     bary = None
     if not _robust_fused(config, "marker") or not _temporal_fused(config, "marker") or not _floor_fused(config, "marker") or \
-            not _capsule_fused(config, "marker"):
-        # EXTENSION: execution.robust_fused / temporal_fused / floor_fused / capsule_fused: False -- the composed closure, the
-        # fused one's checker
+            not _capsule_fused(config, "marker") or not _limit_fused(config, "marker"):
+        # EXTENSION: execution.robust_fused / temporal_fused / floor_fused / capsule_fused / limit_fused: False -- the composed
+        # closure, the fused one's checker
         return _optim_markers_general(markers, pose_body, o_pose_body, betas, o_betas, root_orient, trans, one_hot,
                                       smpl_inference, config, verbose, iter_fn, initial_angle, repeat, foot_contacts)
     if not bool(((rows_nz == 1) & (one_hot.sum(dim=1) == 1.0)).all()):
@@ -627,9 +664,10 @@ def _optim_markers_frame_assign(markers, pose_body, o_pose_body, betas, o_betas,
     if _floor_on(config, "marker"):
         raise NotImplementedError("%s is not built for the floor-contact term (stages.marker.losses.floor_penetration / "
                                   "floor_contact)" % what)
-    if not _robust_fused(config, "marker") or not _temporal_fused(config, "marker") or not _capsule_fused(config, "marker"):
+    if not _robust_fused(config, "marker") or not _temporal_fused(config, "marker") or not _capsule_fused(config, "marker") or \
+            not _limit_fused(config, "marker"):
         raise NotImplementedError("%s is built for the fused marker closure only, not for the closure composed from the operators "
-                                  "(execution.robust_fused / temporal_fused / capsule_fused: False)" % what)
+                                  "(execution.robust_fused / temporal_fused / capsule_fused / limit_fused: False)" % what)
     _refuse_latent_offsets(config, what + ": an offset per column has no meaning once the column changes identity")
     fs = frame_shard()
     if fs is not None and fs.active:
@@ -669,7 +707,7 @@ def _optim_markers_general(markers, pose_body, o_pose_body, betas, o_betas, root
                            "execution.robust_fused / temporal_fused / marker_bary_fused: False)")
     st = config["stages"]["marker"]
     unsupported = set(st["losses"]) - {"marker", "reg_pose_body", "reg_betas", "joint_accel", "latent_offsets", "foot_lock",
-                                       "floor_penetration", "floor_contact", "self_penetration"}
+                                       "floor_penetration", "floor_contact", "self_penetration", "joint_limits"}
     if unsupported:
         raise NotImplementedError("marker-stage losses outside the shipped configs: %s" % sorted(unsupported))
     if st.get("use_sdf"):
@@ -682,6 +720,7 @@ def _optim_markers_general(markers, pose_body, o_pose_body, betas, o_betas, root
         contacts = contacts.to(pose_body.device)
     floor_term = _composed_floor(config, "marker", contacts, smpl_inference)  # EXTENSION: floor-contact term on sole vertices
     caps_term = _composed_capsules(config, "marker", smpl_inference)  # EXTENSION: bone-capsule self-penetration term
+    lim_term = _composed_limits(config, "marker")  # EXTENSION: joint-angle limit term on the body pose
     num_frames = pose_body.shape[0]
     leaves = [pose_body, betas, root_orient, trans]
     params = [p.detach().clone().requires_grad_(True) for p in leaves]
@@ -718,6 +757,8 @@ def _optim_markers_general(markers, pose_body, o_pose_body, betas, o_betas, root
             loss = loss + floor_term(out["vertices"])
         if caps_term is not None:  # EXTENSION: the fused closures' self-penetration term, composed (their checker)
             loss = loss + caps_term(out["joints"])
+        if lim_term is not None:  # EXTENSION: the fused closures' joint-angle limit term, composed (their checker)
+            loss = loss + lim_term(normalize_rot(p_pose))
         loss.backward()
         if verbose:
             print("Marker", n_eval[0], float(loss))

@@ -139,6 +139,12 @@ def _arm_into_torso(tables, hmr_rot, rest, caps, t0):
     return out, sel
 
 
+#: the joint-limit capture (make_sequence(joint_limits=True)): the limited (joint, component, allowed direction) of the true motion,
+#: window length, the x component of the HMR start's left knee there (radians), taper
+LIMITED_COMPONENTS = ((4, 0, 1.0), (5, 0, 1.0), (18, 1, -1.0), (19, 1, 1.0))
+LIMIT_WINDOW, LIMIT_KNEE_X, LIMIT_TAPER = 24, -0.5, 2
+
+
 def farthest_point_vertices(points: np.ndarray, count: int, start: int = 0) -> np.ndarray:
     chosen = [int(start)]
     d = np.linalg.norm(points - points[start], axis=1)
@@ -196,7 +202,7 @@ def make_sequence(tables: SmplTables, seed: int = 0, num_frames: int = 300, num_
                   hmr_pose_noise: float = 0.1, hmr_beta_noise: float = 0.5, subject_seed: int = None,
                   standoff_tilt_deg: float = 0.0, standoff_mm=(9.5, 9.5), planted_feet: bool = False,
                   stance_frames: int = 20, identity_events: int = 0, floor: bool = False,
-                  self_penetration: bool = False) -> SyntheticSequence:
+                  self_penetration: bool = False, joint_limits: bool = False) -> SyntheticSequence:
     """One synthetic sequence: smooth GT motion, unlabeled-but-tracked markers 9.5 mm off the
     surface with 1 mm noise and block dropout, and an HMR stand-in (noisy pose/shape, wrong yaw).  `subject_seed` fixes the
     ground-truth shape independently of `seed`: sequences of ONE subject (the shared-betas extension fits them together).
@@ -223,6 +229,15 @@ def make_sequence(tables: SmplTables, seed: int = 0, num_frames: int = 300, num_
     (exact zeros) every marker column owned by joints 16, 18, 20, 22 in the window.  gt["capsules"] is the capsule list,
     gt["penetration_window"] = (first frame, one past the last), gt["hmr_overlap"] [F] the HMR start's deepest arm / trunk overlap
     per frame (metres, at its mean betas).  No hash stream is consumed; without the option every array is what it was.
+    A capture whose video start bends a knee backwards (EXTENSION tests of the joint-angle limit term): with `joint_limits` the
+    ground truth's four limited components (LIMITED_COMPONENTS: knees x, elbows y) become d |A| (1 + sin(2 pi f t + phi)) with
+    A, f, phi the component's own and d the allowed direction, so that the true motion lies inside body_model.smpl_joint_limits()
+    in every frame.  In a window of 24 frames starting at F / 10 (rounded up; ValueError if the sequence is shorter) the x
+    component of the axis-angle vector of the HMR stand-in's left knee (joint 4) is replaced by -0.5 rad, about 29 degrees
+    backwards (tapered 1/3, 2/3 over two frames at each end), and every marker column owned by joints 4, 7 and 10 is blanked
+    (exact zeros): nothing but the prior then holds the shank.  gt["joint_limits"] = (lo, hi) are the default tables,
+    gt["limit_window"] = (first frame, one past the last), gt["hmr_violation"] [F] the HMR start's largest violation per frame
+    (radians).  No hash stream is consumed; without the option every array is what it was.
     A capture whose columns change identity (EXTENSION tests of the tracklet placement): `identity_events` events, each at a
     frame t_e in [F/10, 9F/10) and on three columns visible at t_e whose mutual distances there are >= 0.2 m (frame and columns
     from the event's own hash stream, drawn again until they qualify).  From t_e on the contents of the three columns are
@@ -243,6 +258,9 @@ def make_sequence(tables: SmplTables, seed: int = 0, num_frames: int = 300, num_
     freq = 0.5 + 2.5 * hash_uniform(s + 2, NUM_JOINTS, 3)
     phase = 2.0 * np.pi * hash_uniform(s + 3, NUM_JOINTS, 3)
     aa = amp[None] * np.sin(2.0 * np.pi * freq[None] * t[:, None, None] + phase[None])  # [F,24,3]
+    if joint_limits:  # (no hash stream: the four limited components of the true motion stay on the allowed side)
+        for jj, kk, dd in LIMITED_COMPONENTS:
+            aa[:, jj, kk] = dd * np.abs(amp[jj, kk]) * (1.0 + np.sin(2.0 * np.pi * freq[jj, kk] * t + phase[jj, kk]))
     rot = _rodrigues(aa)
     yaw = 1.0 * np.sin(2.0 * np.pi * 0.5 * t + 2.0 * np.pi * hash_uniform(s + 4))
     up = _rodrigues(np.array([np.pi / 2.0, 0.0, 0.0]))  # SMPL y-up -> mocap z-up
@@ -391,6 +409,26 @@ def make_sequence(tables: SmplTables, seed: int = 0, num_frames: int = 300, num_
         arm_cols = np.isin(owner[pick[perm]], [16, 18, 20, 22])
         markers[t0:t0 + PENETRATION_WINDOW, arm_cols] = 0.0
 
+    limits = limit_window = hmr_violation = None
+    if joint_limits:  # (no hash stream: the HMR knee of the window and the left leg's marker columns there change, nothing else)
+        from .body_model import joint_limit_violation, rotation_log, smpl_joint_limits
+
+        t0 = -(-F // 10)
+        if t0 + LIMIT_WINDOW > F:
+            raise ValueError("make_sequence: joint_limits needs a window of %d frames from frame %d on (F = %d)" % (LIMIT_WINDOW, t0, F))
+        limits = smpl_joint_limits()
+        limit_window = (t0, t0 + LIMIT_WINDOW)
+        hmr_rot = hmr_rot.copy()
+        for i in range(LIMIT_WINDOW):
+            edge = min(i, LIMIT_WINDOW - 1 - i)
+            taper = 1.0 if edge >= LIMIT_TAPER else (edge + 1.0) / (LIMIT_TAPER + 1.0)
+            om = rotation_log(hmr_rot[t0 + i, 4])[0]
+            om[0] = taper * LIMIT_KNEE_X
+            hmr_rot[t0 + i, 4] = _rodrigues(om)
+        hmr_violation = joint_limit_violation(hmr_rot[:, 1:], *limits).reshape(F, -1).max(axis=1)
+        leg_cols = np.isin(owner[pick[perm]], [4, 7, 10])
+        markers[t0:t0 + LIMIT_WINDOW, leg_cols] = 0.0
+
     f32 = lambda x: torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
     img = SyntheticImgSmpl(
         trans=f32(hmr_trans),
@@ -423,6 +461,10 @@ def make_sequence(tables: SmplTables, seed: int = 0, num_frames: int = 300, num_
         gt["capsules"] = caps
         gt["penetration_window"] = window
         gt["hmr_overlap"] = hmr_overlap
+    if joint_limits:
+        gt["joint_limits"] = limits
+        gt["limit_window"] = limit_window
+        gt["hmr_violation"] = hmr_violation
     return SyntheticSequence(img_smpl=img, markers=SyntheticMarkers(markers.astype(np.float32), 30.0), gt=gt)
 
 

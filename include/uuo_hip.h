@@ -449,7 +449,8 @@ int uuo_reprojection_create(const uuo_reprojection_problem_t* p, uuo_reprojectio
 int uuo_reprojection_destroy(uuo_reprojection_t* h);
 int uuo_reprojection_num_params(const uuo_reprojection_problem_t* p); /* 3F + 14 */
 /* One closure evaluation at d_x: loss to d_loss[0], gradient to d_grad[3F+14]; optional outputs: d_kp [F,J,2] the projected
- * key points (+0.5, as the reference's joints_2d), d_nn_idx [F,M] the nearest vertex of every marker.  Asynchronous. */
+ * key points (+0.5, as the reference's joints_2d), d_nn_idx [F,M] the nearest vertex of every marker, -1 for a marker that
+ * has none (NaN coordinates: it adds nothing to the loss or the gradient, the divisor stays F M).  Asynchronous. */
 int uuo_reprojection_eval(uuo_reprojection_t* h, void* stream, const float* d_x, float* d_loss, float* d_grad,
                           float* d_kp, int32_t* d_nn_idx);
 /* uuo_lbfgs_solve for this closure.  The reference returns quantities of the LAST closure evaluation (its `nonlocal`

@@ -201,6 +201,8 @@ __global__ __launch_bounds__(64) void k_reproj_terms(ReprojArgs a) {
       const float gx_ = a.coef_ch * dx, gy_ = a.coef_ch * dy, gz_ = a.coef_ch * dz;
       cbx += (double)gx_; cby += (double)gy_; cbz += (double)gz_;
       cyaw += (double)(gx_ * rz) - (double)(gz_ * rx);  // d . (d Ry / d yaw) W,  (d Ry / d yaw) W = (rz, 0, -rx)
+    } else if (a.nn_idx) {
+      a.nn_idx[(size_t)f * M + m] = -1;  // no vertex: the caller's buffer is not left as it was allocated
     }
   }
   cl = rpj_wave_sum(cl); cyaw = rpj_wave_sum(cyaw); cbx = rpj_wave_sum(cbx); cby = rpj_wave_sum(cby); cbz = rpj_wave_sum(cbz);

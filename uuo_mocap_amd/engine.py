@@ -1276,7 +1276,9 @@ class ReprojectionProblem:
             self.lib.uuo_reprojection_destroy(h)
 
     def evaluate(self, x: torch.Tensor, want_kp: bool = False, want_nn: bool = False):
-        """One closure evaluation: (loss, flat gradient [3F+14], key points [F,J,2] | None, nearest vertex [F,M] | None)."""
+        """One closure evaluation: (loss, flat gradient [3F+14], key points [F,J,2] | None, nearest vertex [F,M] | None).
+        A marker with NaN coordinates has no nearest vertex: its entry is -1 and it adds nothing to the loss or the gradient
+        (the divisor stays F M) -- mask such entries before indexing with them."""
         assert x.is_cuda and x.dtype == torch.float32 and x.numel() == self.n and x.is_contiguous()
         loss = torch.empty((1,), dtype=torch.float32, device=self.device)
         grad = torch.empty((self.n,), dtype=torch.float32, device=self.device)

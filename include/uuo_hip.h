@@ -305,6 +305,25 @@ int uuo_fit_set_capsules(uuo_fit_t* fit, float w, int32_t n_caps, const int32_t*
  * the per-frame vertex table.  Refused (at evaluation) for the part stage and with w_soft != 0, and inside lock-step batches
  * (uuo_batch_*). */
 int uuo_fit_set_joint_limits(uuo_fit_t* fit, float w, const float* h_lo, const float* h_hi);
+/* EXTENSION (not reference behaviour; the reference's author left `weighted_mse_loss(pose_body, o_pose_body, img_mask[...])`
+ * commented out in its chamfer closure): a weight per (frame, body joint) on the pose prior of the chamfer and marker stages,
+ * w[F][23] >= 0 (row j - 1 of a frame is SMPL joint j).  With raw the optimised raw body rotations and o = d_o_pose:
+ *   prior = w_pose / (F 207) sum_t sum_j w[t][j] sum_e (raw[t][j][e] - o[t][j][e])^2
+ *   d prior / d raw[t][j][e] = 2 w_pose / (F 207) w[t][j] (raw - o)
+ * in place of the uniform w_pose / (F 207) sum (raw - o)^2.  The normaliser stays F 207, not sum w: w == 1 everywhere is the
+ * uniform term (to rounding: other kernels form it), and a weight means the same whatever the number of frames it is lowered
+ * on.  Frames are not coupled: F = 1 is a valid problem.  Every entry of a (frame, joint) with w == 0 receives an exact +0 from
+ * the prior; a third raw row that sits on its target receives exact zeros whatever its weight, and uuo_lbfgs_solve decides the
+ * compact packing from the problem's own w_pose and rows, as without the setting.
+ * A setting of the WORKSPACE (null at creation) with the lifetime rules of uuo_fit_set_foot_lock: `d_weights` is a device
+ * pointer to [F][23] floats that the caller keeps alive and may rewrite; it is read at every evaluation, not copied, and not
+ * checked (finite values >= 0 are the caller's duty).  Null switches the setting off, and every result is that of a workspace
+ * that never had it.  With w_pose == 0 there is no prior to weigh and the setting changes nothing.
+ * Sums in a fixed order, no atomics: results are bit-reproducible.  Works with robust_sigma, the joint-acceleration, foot-lock,
+ * floor-contact, self-penetration and joint-angle limit terms, the latent marker offsets, three-corner placements, the
+ * point-to-surface term and the per-frame vertex table.  Refused (at evaluation, -22) for the part stage and with w_soft != 0,
+ * and inside lock-step batches (uuo_batch_*).  uuo_problem_t and uuo_abi_version() are unchanged. */
+int uuo_fit_set_prior_weights(uuo_fit_t* fit, const float* d_weights);
 /* EXTENSION (not reference behaviour; MoSh-style fitters score a marker by its distance to the SKIN less its stand-off, the
  * reference's chamfer term by its distance to the nearest VERTEX): on = 1 replaces the chamfer stage's data term
  * min_v |x - v|^2 by the point-to-surface term on the one-ring of the nearest vertex v^ the closure's search finds anyway:

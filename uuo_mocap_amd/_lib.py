@@ -131,6 +131,8 @@ _SIGNATURES = {
     "uuo_fit_set_capsules": (c_int, [c_void_p, c_float, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     # EXTENSION: joint-angle limit term of the workspace (w, host lo [23][3], host hi [23][3])
     "uuo_fit_set_joint_limits": (c_int, [c_void_p, c_float, c_void_p, c_void_p]),
+    # EXTENSION: per-(frame, joint) weights of the pose prior of the workspace (device [F][23]; null = off)
+    "uuo_fit_set_prior_weights": (c_int, [c_void_p, c_void_p]),
     "uuo_problem_num_params": (c_int, [POINTER(UuoProblem)]),
     "uuo_closure_eval": (c_int, [c_void_p, c_void_p, POINTER(UuoProblem), c_void_p, c_void_p, c_void_p, c_void_p]),
     "uuo_lbfgs_solve": (c_int, [c_void_p, c_void_p, POINTER(UuoProblem), c_void_p, POINTER(UuoLbfgsOptions),
@@ -174,6 +176,7 @@ _DEBUG_SIGNATURES = {
     "uuo_debug_time_small": (c_int, [c_int, c_int, c_int, POINTER(c_float)]),
     "uuo_debug_index_map": (c_int, [c_int, c_int, c_int, c_void_p]),
     "uuo_debug_problem_index_map": (c_int, [POINTER(UuoProblem), c_int, c_void_p]),
+    "uuo_debug_last_solve_n": (c_int, [c_void_p]),  # coordinates of the workspace's last stage solve (which packing it took)
     "uuo_debug_staging_script": (c_int, [c_void_p, c_int, ctypes.c_longlong, c_void_p]),
     # step-wise replay of the L-BFGS history kernels (tests/test_gpu_lbfgs_history.py)
     "uuo_debug_lb_replay_create": (c_int, [c_int, c_int, POINTER(c_void_p)]),

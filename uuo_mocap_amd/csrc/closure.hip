@@ -1789,6 +1789,63 @@ __global__ __launch_bounds__(64) void k_limit_fwd(LimitFwdArgs a) {
 }
 
 // ----------------------------------------------------------------------------------------------------
+// EXTENSION (not reference behaviour; uuo_fit_set_prior_weights): the pose prior of the chamfer and marker stages with a weight
+// per (frame, body joint), w[t][j] >= 0:
+//   loss += c sum_t sum_j w[t][j] sum_e (raw[t][j][e] - o[t][j][e])^2,   c = w_pose / (F 207)   (the normaliser of the uniform
+//   prior, not sum w: w == 1 everywhere is the uniform term),   dL/d raw[t][j][e] = 2 c w[t][j] (raw - o).
+// k_prior_conf delivers the WHOLE prior -- the backward kernels and the finalize then run with a pose coefficient of 0 -- through
+// the buffer of the joint-angle limit term, [F][23][9] gradients in parameter space and [F] shares behind them, which the
+// temporal instantiations add to gout and to slot 3 (lim_g != null): no existing kernel changes.  add == 0: it writes the buffer;
+// add != 0 (the limit term is on, k_limit_fwd of this evaluation ran before it on the same stream): it adds to it.
+// The shape of k_limit_fwd: 32 lanes per frame, two frames per 64-thread block.  Lane l < 23 of a half takes joint l + 1: its
+// nine raw entries, nine targets, its weight (and with add its nine old gradients; lane 0 the old share) in one round trip -- the
+// 23 lanes of a half read 207 consecutive floats of each table.  A weight of 0 stores exact +0 (not 0 * diff), a row on its
+// target 2 c w * 0 = 0: third rows on their targets stay exact zeros, as the compact packing needs.  The frame's share: every lane
+// sums its nine squares in the order e = 0 .. 8 and weighs the sum, then a fixed xor butterfly (16, 8, .. 1) inside the half adds
+// the lanes (lanes 23 .. 31 hold zeros).  No atomics, no LDS: bit-reproducible.
+// ----------------------------------------------------------------------------------------------------
+struct PriorConfArgs {
+  uuo_gptr<const float> body;    // [F][23][9] raw body pose entries (the optimised parameters)
+  uuo_gptr<const float> target;  // [F][23][9] the prior's target (uuo_problem_t.d_o_pose)
+  uuo_gptr<const float> w;       // [F][23] weights
+  int F, add;
+  float cl, cg;                  // w_pose / (F 207), 2 w_pose / (F 207)
+  uuo_gptr<float> g;             // [F][23][9] gradients, then [F] shares: written (add == 0) or added to
+};
+__global__ __launch_bounds__(64) void k_prior_conf(PriorConfArgs a) {
+  const int half = threadIdx.x >> 5, l = threadIdx.x & 31;
+  const int f = blockIdx.x * UUO_LIM_FPB + half;
+  const bool on = f < a.F && l < 23;
+  const size_t row = on ? ((size_t)f * 23 + l) * 9 : 0;
+  float raw[9], tg[9], old[9];
+#pragma unroll
+  for (int e = 0; e < 9; ++e) {
+    raw[e] = on ? a.body[row + e] : 0.f;
+    tg[e] = on ? a.target[row + e] : 0.f;
+    old[e] = (on && a.add) ? a.g[row + e] : 0.f;
+  }
+  const float w = on ? a.w[(size_t)f * 23 + l] : 0.f;
+  const bool head = l == 0 && f < a.F;
+  const float old_share = (head && a.add) ? a.g[(size_t)a.F * 207 + f] : 0.f;
+  const float wc = a.cg * w;
+  float sq = 0.f, out[9];
+#pragma unroll
+  for (int e = 0; e < 9; ++e) {
+    const float diff = raw[e] - tg[e];
+    out[e] = old[e] + ((w == 0.f) ? 0.f : wc * diff);
+    sq = fmaf(diff, diff, sq);
+  }
+  if (on) {
+#pragma unroll
+    for (int e = 0; e < 9; ++e) a.g[row + e] = out[e];
+  }
+  float part = (w == 0.f) ? 0.f : w * sq;
+#pragma unroll
+  for (int m = 16; m >= 1; m >>= 1) part += __shfl_xor(part, m, 64);
+  if (head) a.g[(size_t)a.F * 207 + f] = old_share + a.cl * part;
+}
+
+// ----------------------------------------------------------------------------------------------------
 // EXTENSION (not reference behaviour; uuo_fit_set_surface): the chamfer stage's data term as a point-to-surface distance
 // with a stand-off.  k_ring_pick (nn_kernels.hip) has chosen, for every (frame, marker), the face of the nearest vertex's
 // one-ring that lies closest in the search's vertex buffer; this pass is k_bary_fwd with those corners read per frame and the
@@ -2130,6 +2187,14 @@ static int validate_problem(const uuo_fit* fit, const uuo_problem_t* p) {
               "term (w_soft)");
   UUO_REQUIRE(fit->lim_w == 0.f || !uuo_recorder,
               "closure: lock-step batches do not carry the joint-angle limit term (uuo_fit_set_joint_limits, extension)");
+  // EXTENSION: the pose prior's per-(frame, joint) weights of the workspace (uuo_fit_set_prior_weights) likewise
+  UUO_REQUIRE(!fit->prior_w || p->stage != UUO_STAGE_PART,
+              "closure: the pose prior's weights (uuo_fit_set_prior_weights, extension) are not built for the part stage");
+  UUO_REQUIRE(!fit->prior_w || p->w_soft == 0.f,
+              "closure: the pose prior's weights (uuo_fit_set_prior_weights, extension) are not built for the soft-assignment data "
+              "term (w_soft)");
+  UUO_REQUIRE(!fit->prior_w || !uuo_recorder,
+              "closure: lock-step batches do not carry the pose prior's weights (uuo_fit_set_prior_weights, extension)");
   // EXTENSION: latent marker offsets
   UUO_REQUIRE(p->w_offsets == 0.f || (p->w_offsets > 0.f && p->w_offsets <= 3.0e38f),
               "closure: w_offsets (latent marker offsets, extension) must be 0 (off) or a positive finite weight");
@@ -2358,6 +2423,15 @@ extern "C" int uuo_fit_set_joint_limits(uuo_fit_t* fit, float w, const float* h_
     fit->lim_have = true;
   }
   fit->lim_w = w;
+  return 0;
+}
+
+extern "C" int uuo_fit_set_prior_weights(uuo_fit_t* fit, const float* d_weights) {
+  UUO_REQUIRE(fit, "uuo_fit_set_prior_weights: null fit");
+  UUO_REQUIRE(!d_weights || !uuo_recorder, "uuo_fit_set_prior_weights: lock-step batches do not carry the pose prior's weights");
+  // (the buffer k_prior_conf fills is the joint-angle limit term's: [F][23][9] gradients, then [F] shares)
+  if (d_weights && !fit->lim_g) UUO_HIP_CHECK(hipMalloc((void**)&fit->lim_g, ((size_t)fit->F * 207 + fit->F) * sizeof(float)));
+  fit->prior_w = d_weights;
   return 0;
 }
 
@@ -2851,7 +2925,33 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
     fit->lim_launched = true;  // (uuo_fit_set_joint_limits waits for this stream before it replaces the table)
     fit->lim_last_stream = s;
   };
-  const bool temporal = accel || lock || floor || caps || limits;
+  // EXTENSION: the pose prior's per-(frame, joint) weights: k_prior_conf (launch_prior below, after launch_limits) leaves the whole
+  // weighted prior in the limit term's buffer, which the temporal instantiations add after their own pose prior -- that one runs
+  // with a coefficient of 0 here, and so does the finalize's (its slot-2 sum is then 0).  With w_pose == 0 there is no prior to
+  // weigh: the setting changes nothing.  (uuo_stage_compactable looks at the problem's w_pose, not at these coefficients.)
+  const bool prior = fit->prior_w != nullptr && (p->stage == UUO_STAGE_CHAMFER || p->stage == UUO_STAGE_MARKER) && p->w_pose != 0.f;
+  UUO_REQUIRE(!prior || (!uuo_recorder && !soft_chamfer),
+              "closure: the pose prior's weights belong to the chamfer and marker stages' hard-assignment closures");
+  if (prior) {
+    UUO_REQUIRE(fit->lim_g, "closure: the pose prior's weights were set without their buffer");
+    a.cpose = 0.f;
+    a.lim_g = fit->lim_g;
+  }
+  auto launch_prior = [&]() {
+    if (!prior) return;
+    PriorConfArgs b;
+    std::memset(&b, 0, sizeof(b));
+    b.body = d_x + lay.off_pose;
+    b.target = p->d_o_pose;
+    b.w = fit->prior_w;
+    b.F = F;
+    b.add = limits ? 1 : 0;
+    b.cl = (float)((double)p->w_pose / ((double)F * 207.0));
+    b.cg = (float)(2.0 * (double)p->w_pose / ((double)F * 207.0));
+    b.g = fit->lim_g;
+    hipLaunchKernelGGL(k_prior_conf, dim3((F + UUO_LIM_FPB - 1) / UUO_LIM_FPB), dim3(64), 0, s, b);
+  };
+  const bool temporal = accel || lock || floor || caps || limits || prior;
   a.h.gx = F;
   a.h.gy = 1;
   FinArgs fa;
@@ -2861,7 +2961,7 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
   fa.betas = d_x + lay.off_betas;
   fa.o_betas = p->d_o_betas;
   fa.closs = data_c;
-  fa.cpose = (p->stage == UUO_STAGE_PART) ? 0.0 : (double)p->w_pose / ((double)F * 207.0);
+  fa.cpose = (p->stage == UUO_STAGE_PART || prior) ? 0.0 : (double)p->w_pose / ((double)F * 207.0);  // (prior: k_prior_conf's shares)
   fa.cbetas = (double)p->w_betas / 10.0;
   fa.g_betas = d_grad + gl.off_betas;
   fa.g_z = (p->stage == UUO_STAGE_PART) ? d_grad + gl.off_z : nullptr;
@@ -2941,6 +3041,7 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
     launch_floor();
     launch_caps();
     launch_limits();
+    launch_prior();
     a.M = 3 * M;
     a.up_items = items;
     a.item_loss = item_loss;
@@ -2988,6 +3089,7 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
     launch_floor();
     launch_caps();
     launch_limits();
+    launch_prior();
     a.M = 3 * M;
     a.assign = fit->surf_corners;
     a.up_items = items;
@@ -3033,6 +3135,7 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
         launch_floor();
         launch_caps();
         launch_limits();
+        launch_prior();
         if (floor)
           hipLaunchKernelGGL(robust ? k_bwd_sparse_r_t_o_fl : k_bwd_sparse_t_o_fl, dim3(F), dim3(BWD_NW * 64), 0, s, a);
         else
@@ -3052,6 +3155,7 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
       launch_floor();
       launch_caps();
       launch_limits();
+      launch_prior();
       if (floor)
         hipLaunchKernelGGL(robust ? k_bwd_sparse_r_t_fl : k_bwd_sparse_t_fl, dim3(F), dim3(BWD_NW * 64), 0, s, a);
       else if (fassign)
@@ -3162,6 +3266,10 @@ extern "C" int uuo_debug_index_map(int stage, int F, int compact, int* h_out) {
   return n;
 }
 // the same for a whole problem (stage, F, M, w_offsets: the latent marker offsets' coordinates included)
+// host-only debug hook: the number of solver coordinates of the last stage solve set up on `fit` (stage_objective_init): n_act on
+// the compact packing, the problem's parameter count on the full one; 0 before the first solve
+extern "C" int uuo_debug_last_solve_n(const uuo_fit_t* fit) { return fit ? fit->last_n : -22; }
+
 extern "C" int uuo_debug_problem_index_map(const uuo_problem_t* p, int compact, int* h_out) {
   UUO_REQUIRE(p && p->stage >= 0 && p->stage <= 2 && p->F > 0 && h_out, "uuo_debug_problem_index_map: bad arguments");
   const UuoIndexMap m = uuo_stage_index_map(p, compact != 0 && p->stage != UUO_STAGE_PART);

@@ -186,6 +186,7 @@ inline int stage_objective_init(StageObjective& obj, uuo_fit* fit, hipStream_t s
   obj.map = uuo_stage_index_map(p, compact);
   obj.n_full = uuo_problem_num_params(p);
   obj.n = compact ? obj.map.n_act : obj.n_full;
+  fit->last_n = obj.n;
   return 0;
 }
 

@@ -237,6 +237,13 @@ struct uuo_fit {
   bool lim_launched = false;
   hipStream_t lim_last_stream = nullptr;
   hipStream_t lim_stream = nullptr;
+  // EXTENSION: per-(frame, joint) weights [F][23] on the pose prior of the chamfer and marker stages (uuo_fit_set_prior_weights;
+  // null = off), the caller's device pointer, read at every evaluation and not copied.  k_prior_conf leaves the whole weighted
+  // prior -- gradients and shares -- in lim_g (added there when the joint-angle limit term is on too), and the backward and the
+  // finalize run with a pose coefficient of 0.
+  const float* prior_w = nullptr;
+  int last_n = 0;  // coordinates of the last stage solve set up on this workspace (n_act on the compact packing, else n_full):
+                   // read back by the debug flavour's uuo_debug_last_solve_n, which tests use to see which packing a solve took
   int surface = 0;               // EXTENSION: point-to-surface chamfer term (uuo_fit_set_surface; 0 = off) and its stand-off
   float surface_distance = 0.f;
   const int32_t* frame_assign = nullptr;  // EXTENSION: [F][M] per-frame vertex table of the marker stage (uuo_fit_set_frame_assign;

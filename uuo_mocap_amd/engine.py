@@ -180,6 +180,9 @@ def solve_batch(problems, xs, max_iter: int, lr: float = 1.0, tolerance_grad: fl
     if any(getattr(p, "joint_limits_on", False) for p in problems):
         raise NotImplementedError("lock-step batches do not carry the joint-angle limit term (joint_limits, extension): "
                                   "solve such problems one by one")
+    if any(getattr(p, "prior_conf_on", False) for p in problems):
+        raise NotImplementedError("lock-step batches do not carry the pose prior's weights (prior_confidence, extension): "
+                                  "solve such problems one by one")
     if any(getattr(p, "frame_assign", None) is not None for p in problems):
         raise NotImplementedError("lock-step batches do not carry the per-frame vertex table (tracklets, extension): "
                                   "solve such problems one by one")
@@ -536,6 +539,21 @@ class _StageProblem:
         self.lim_w = 0.0
         self.lim_lo = None  # [23, 3] float32 numpy (row j - 1 is SMPL joint j; -inf = no bound)
         self.lim_hi = None  # [23, 3] float32 numpy (+inf = no bound)
+        # EXTENSION: per-(frame, joint) weights of the pose prior (ChamferProblem / MarkerProblem), armed the same way
+        # (uuo_fit_set_prior_weights): [F, 23] float32 on the device, which the library reads at every evaluation; None = off
+        self.prior_weights = None
+
+    @property
+    def prior_conf_on(self) -> bool:
+        """EXTENSION: True when this problem arms per-(frame, joint) weights of the pose prior."""
+        return self.prior_weights is not None
+
+    def _set_prior_weights(self, weights):
+        """EXTENSION: `weights` is check_prior_weights' host tensor (or None).  None, or a table that is 1 everywhere, arms
+        nothing: the problem runs the plain kernels, bit for bit (as foot-lock labels that gate nothing do)."""
+        if weights is None or bool((weights == 1.0).all()):
+            return
+        self.prior_weights = weights.to(device=self.device, dtype=torch.float32).contiguous()
 
     @property
     def joint_limits_on(self) -> bool:
@@ -655,6 +673,8 @@ class _StageProblem:
                   "uuo_fit_set_joint_limits")
         else:
             check(self.lib.uuo_fit_set_joint_limits(self.fit, c_float(0.0), None, None), "uuo_fit_set_joint_limits")
+        check(self.lib.uuo_fit_set_prior_weights(self.fit, self.prior_weights.data_ptr() if self.prior_conf_on else None),
+              "uuo_fit_set_prior_weights")
 
     def _need_workspace(self):
         if self.fit is None:  # created for a lock-step batch only: give it the thread's workspace on first standalone use
@@ -981,6 +1001,67 @@ def stage_joint_limits(config: Dict, stage: str) -> Dict:
     return {"w": v, "limits": lim}
 
 
+def stage_prior_confidence(config: Dict, stage: str):
+    """EXTENSION: the per-(frame, joint) confidence in the video's pose of the chamfer or marker stage as a config states it --
+    stages.<stage>.prior_confidence: absent or null = off (returns None), else {gap_weight: 0.0, ramp: 0, joint_weights: null}:
+    `gap_weight` in [0, 1], the weight of the pose prior in frames the video did not see; `ramp`, an integer >= 0, the number of
+    unseen frames next to a seen one over which the weight falls from 1 to it; `joint_weights`, null (ones) or 23 finite values
+    >= 0 (entry j - 1 is SMPL joint j).  Every key may be left out; unknown keys, and values outside these ranges, are a
+    ValueError.  Returns {"gap_weight", "ramp", "joint_weights"} (prior_weight_table's `block`).  A block next to a
+    reg_pose_body that is absent or 0 is allowed and changes nothing."""
+    blk = config["stages"][stage].get("prior_confidence", None)
+    if blk is None:
+        return None
+    what = "stages.%s.prior_confidence" % stage
+    if not isinstance(blk, dict) or set(blk) - {"gap_weight", "ramp", "joint_weights"}:
+        raise ValueError("%s must be null or {gap_weight, ramp, joint_weights} (got %r)" % (what, blk))
+    number = lambda q: isinstance(q, (int, float)) and not isinstance(q, bool) and math.isfinite(q)
+    gw = blk.get("gap_weight", 0.0)
+    if not number(gw) or gw < 0.0 or gw > 1.0:
+        raise ValueError("%s.gap_weight must be a number in [0, 1] (got %r)" % (what, gw))
+    ramp = blk.get("ramp", 0)
+    if not isinstance(ramp, int) or isinstance(ramp, bool) or ramp < 0:
+        raise ValueError("%s.ramp must be an integer >= 0 (got %r)" % (what, ramp))
+    jw = blk.get("joint_weights", None)
+    if jw is not None:
+        if not isinstance(jw, (list, tuple)) or len(jw) != 23 or not all(number(q) and q >= 0.0 for q in jw):
+            raise ValueError("%s.joint_weights must be null or 23 finite values >= 0 (got %r)" % (what, jw))
+        jw = [float(q) for q in jw]
+    return {"gap_weight": float(gw), "ramp": int(ramp), "joint_weights": jw}
+
+
+def prior_weight_table(seen, block: Dict) -> torch.Tensor:
+    """EXTENSION: the pose prior's weights [F, 23] float32 (host) from `seen` [F] (mocap frames the video saw; anything
+    non-zero counts) and stage_prior_confidence's record:  omega[t, j] = frame_w[t] * joint_weights[j],  d[t] the distance in
+    frames to the nearest seen frame,  frame_w[t] = 1 where d = 0, else max(gap_weight, 1 - d / (ramp + 1)).  ramp = 0 makes
+    every unseen frame gap_weight; ramp = 2 tapers 2/3, 1/3.  No seen frame at all is a ValueError."""
+    sn = torch.as_tensor(seen).detach().cpu().reshape(-1) != 0
+    F = int(sn.shape[0])
+    idx = torch.nonzero(sn).reshape(-1).to(torch.int64)
+    if idx.numel() == 0:
+        raise ValueError("prior_weight_table: the video saw no frame at all")
+    t = torch.arange(F, dtype=torch.int64)
+    d = (t[:, None] - idx[None, :]).abs().min(dim=1)[0].to(torch.float64)
+    gw, ramp = float(block["gap_weight"]), int(block["ramp"])
+    fw = torch.where(d == 0, torch.ones_like(d), torch.clamp(1.0 - d / (ramp + 1.0), min=gw))
+    jw = block.get("joint_weights")
+    jw = torch.ones(23, dtype=torch.float64) if jw is None else torch.tensor([float(q) for q in jw], dtype=torch.float64)
+    return (fw[:, None] * jw[None, :]).to(torch.float32).contiguous()
+
+
+def check_prior_weights(prior_weights, num_frames=None):
+    """EXTENSION: the pose prior's weights as a float32 host tensor [F, 23] (None stays None).  Shape, finiteness and >= 0 are
+    checked on the host: ValueError before anything touches the device."""
+    if prior_weights is None:
+        return None
+    w = torch.as_tensor(prior_weights).detach().to(device="cpu", dtype=torch.float32)
+    if w.dim() != 2 or w.shape[1] != 23 or (num_frames is not None and w.shape[0] != int(num_frames)):
+        raise ValueError("prior_weights: [F, 23] with the markers' F = %s expected (got %s)" % (num_frames, tuple(w.shape)))
+    if not bool(torch.isfinite(w).all()) or bool((w < 0.0).any()):
+        raise ValueError("prior_weights: finite weights >= 0 expected")
+    return w
+
+
 def check_foot_contacts(foot_contacts, num_frames=None):
     """EXTENSION: the foot-lock term's contact labels as a float32 host tensor [F, 2] (left, right foot; None stays None).
     Shape, finiteness and the range [0, 1] are checked on the host: ValueError before anything touches the device."""
@@ -1004,7 +1085,10 @@ class ChamferProblem(_StageProblem):
 
     stage = UUO_STAGE_CHAMFER
 
-    def __init__(self, smpl_inference, markers, o_pose_body, o_betas, root_orient, config, foot_contacts=None):
+    def __init__(self, smpl_inference, markers, o_pose_body, o_betas, root_orient, config, foot_contacts=None,
+                 prior_weights=None):
+        """EXTENSION: `prior_weights` [F, 23] >= 0 weighs the pose prior per frame and body joint (prior_weight_table builds it
+        from the video's mask and stages.chamfer.prior_confidence); None, or ones everywhere, changes nothing."""
         losses = config["stages"]["chamfer"]["losses"]
         unsupported = set(losses) - {"full_chamfer", "reg_pose_body", "reg_betas", "soft_chamfer", "joint_accel", "foot_lock",
                                      "surface_chamfer", "floor_penetration", "floor_contact", "self_penetration",
@@ -1034,6 +1118,11 @@ class ChamferProblem(_StageProblem):
                                       "built for the soft-assignment closure; optim_chamfer composes that combination from the "
                                       "operators")
         contacts = check_foot_contacts(foot_contacts, None if markers is None else markers.shape[0])
+        stage_prior_confidence(config, "chamfer")  # EXTENSION: the pose prior's weights (validates the block)
+        weights = check_prior_weights(prior_weights, None if markers is None else markers.shape[0])
+        if weights is not None and not bool((weights == 1.0).all()) and float(losses.get("soft_chamfer", 0.0)) != 0.0:
+            raise NotImplementedError("stages.chamfer: the pose prior's weights (prior_confidence) are not built for the "
+                                      "soft-assignment closure")
         if not config["stages"]["chamfer"]["yaw_lock"]:
             raise NotImplementedError("stages.chamfer.yaw_lock False is not a shipped configuration")
         wd, wp, wb = _cfg_weights(losses, "surface_chamfer" if w_surface > 0.0 else "full_chamfer")
@@ -1049,6 +1138,7 @@ class ChamferProblem(_StageProblem):
         self._set_floor(floor, contacts, smpl_inference)  # EXTENSION: floor-contact term on sole vertices
         self._set_capsules(caps, smpl_inference)  # EXTENSION: bone-capsule self-penetration term
         self._set_joint_limits(lim)  # EXTENSION: joint-angle limit term on the body pose
+        self._set_prior_weights(weights)  # EXTENSION: per-(frame, joint) weights of the pose prior
         # EXTENSION (not in the reference): soft assignment of every marker to the body's vertices, fused closure with the dense
         # backward on the matrix pipe (csrc/dense_bwd.hip); not available inside lock-step batches
         w_soft = float(losses.get("soft_chamfer", 0.0))
@@ -1085,11 +1175,13 @@ class MarkerProblem(_StageProblem):
     stage = UUO_STAGE_MARKER
 
     def __init__(self, smpl_inference, markers, o_pose_body, o_betas, assign, config, bary=None, foot_contacts=None,
-                 frame_assign=None):
+                 frame_assign=None, prior_weights=None):
         """`assign` [M] vertex ids (the one-hot placement of the shipped configs), or -- with `bary` [M, 3] -- [M, 3] corner
         vertex ids of a three-corner (barycentric) placement: virtual marker m = sum_k bary[m, k] v[assign[m, k]].
         EXTENSION: `frame_assign` [F, M] int32, a per-frame vertex table (tracklets: the column's vertex changes with the frame,
-        an entry < 0 is an item of weight 0); `assign` may then be None.  Refused with `bary` and with latent_offsets."""
+        an entry < 0 is an item of weight 0); `assign` may then be None.  Refused with `bary` and with latent_offsets.
+        EXTENSION: `prior_weights` [F, 23] >= 0 weighs the pose prior per frame and body joint (prior_weight_table); None, or
+        ones everywhere, changes nothing."""
         st = config["stages"]["marker"]
         unsupported = set(st["losses"]) - {"marker", "reg_pose_body", "reg_betas", "joint_accel", "latent_offsets", "foot_lock",
                                            "floor_penetration", "floor_contact", "self_penetration", "joint_limits"}
@@ -1108,6 +1200,8 @@ class MarkerProblem(_StageProblem):
         w_accel = stage_joint_accel(config, "marker")
         w_lock = stage_foot_lock(config, "marker")
         contacts = check_foot_contacts(foot_contacts, None if markers is None else markers.shape[0])
+        stage_prior_confidence(config, "marker")  # EXTENSION: the pose prior's weights (validates the block)
+        weights = check_prior_weights(prior_weights, None if markers is None else markers.shape[0])
         w_offsets = stage_latent_offsets(config)
         if frame_assign is not None:
             if bary is not None:
@@ -1130,6 +1224,7 @@ class MarkerProblem(_StageProblem):
         self._set_floor(floor, contacts, smpl_inference)  # EXTENSION: floor-contact term on sole vertices
         self._set_capsules(caps, smpl_inference)  # EXTENSION: bone-capsule self-penetration term
         self._set_joint_limits(lim)  # EXTENSION: joint-angle limit term on the body pose
+        self._set_prior_weights(weights)  # EXTENSION: per-(frame, joint) weights of the pose prior
         if frame_assign is not None:  # EXTENSION: per-frame vertex table (the *_f kernel instantiations)
             self.frame_assign = frame_assign.to(device=self.device, dtype=torch.int32).contiguous()
         if w_offsets > 0.0:  # EXTENSION: latent per-marker offsets, 3 M more parameters after trans

@@ -350,3 +350,15 @@ def joint_limit_loss(rot_body: torch.Tensor, lo, hi, w: float) -> torch.Tensor:
     pen = torch.relu(om - hi) + torch.relu(lo - om)
     pen = torch.where(skip[..., None], torch.zeros_like(pen), pen)
     return float(w) * (pen * pen).sum() / rot_body.shape[0]
+
+
+def weighted_pose_prior(pose_body: torch.Tensor, o_pose_body: torch.Tensor, weights: torch.Tensor) -> torch.Tensor:
+    """EXTENSION (the reference's author left it commented out, optimization.py:244): the pose prior of the fused chamfer and
+    marker closures with a weight per (frame, body joint) (uuo_fit_set_prior_weights), composed -- their checker.  pose_body,
+    o_pose_body [F, 23, 3, 3] raw rotations and their target, weights [F, 23] >= 0:
+    sum_t sum_j w[t, j] sum_e (raw - o)^2 / (F 207) -- the mean of the weighted squares, i.e. the reference's
+    weighted_mse_loss(pose_body, o_pose_body, weights[:, :, None, None]); ones give F.mse_loss.  Times reg_pose_body at the
+    caller."""
+    w = weights.to(device=pose_body.device, dtype=pose_body.dtype)
+    d = pose_body - o_pose_body
+    return torch.mean(d * d * w[:, :, None, None])

@@ -124,6 +124,23 @@ def compute_joint_limit_violation(rot_body: torch.Tensor, lo, hi) -> Dict[str, f
     return {"max_deg": float(worst.max()), "mean_deg": float(worst.mean()), "frames_pct": 100.0 * float((worst > 0.0).mean())}
 
 
+def compute_window_vertex_error(pred_vertices: torch.Tensor, gt_vertices: torch.Tensor, window) -> Dict[str, float]:
+    """EXTENSION: the mean vertex error (the tensors' unit) inside and outside the frame window (first frame, one past the
+    last) -- what the pose prior's weights buy where the video lost the person, and what they cost elsewhere.  [F, V, 3] each;
+    `inside` / `outside` are NaN when the window holds no / every frame."""
+    if pred_vertices.dim() != 3 or tuple(pred_vertices.shape) != tuple(gt_vertices.shape):
+        raise ValueError("compute_window_vertex_error: two [F, V, 3] tensors expected")
+    w0, w1 = int(window[0]), int(window[1])
+    F = int(pred_vertices.shape[0])
+    if not 0 <= w0 <= w1 <= F:
+        raise ValueError("compute_window_vertex_error: the window %r does not lie in the %d frames" % (window, F))
+    e = (pred_vertices.detach().cpu().double() - gt_vertices.detach().cpu().double()).norm(dim=-1).mean(dim=1)
+    inside = torch.zeros(F, dtype=torch.bool)
+    inside[w0:w1] = True
+    mean = lambda v: float(v.mean()) if v.numel() else float("nan")
+    return {"inside": mean(e[inside]), "outside": mean(e[~inside]), "all": mean(e)}
+
+
 def compute_PA_MPJPE(pred_joints: torch.Tensor, gt_joints: torch.Tensor) -> torch.Tensor:
     return compute_MPJPE(compute_similarity_transform(pred_joints, gt_joints), gt_joints)
 

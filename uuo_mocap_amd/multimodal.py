@@ -17,8 +17,8 @@ import numpy as np
 import torch
 
 from . import markers_utils, optimization
-from .engine import (set_workspace_group, set_workspace_slot, stage_latent_offsets, worker_pool, worker_streams,
-                     workspace_group)
+from .engine import (prior_weight_table, set_workspace_group, set_workspace_slot, stage_latent_offsets, stage_prior_confidence,
+                     worker_pool, worker_streams, workspace_group)
 from .markers_utils import find_best_part_fits, get_aabb, get_aabb_volume, segment_rigid
 from .optimization import (compute_marker_labels_from_coords, compute_nearest_points, compute_tracklet_placement,
                            get_marker_mask, optim_chamfer, optim_markers, weighted_chamfer_distance)
@@ -45,6 +45,20 @@ def pad(sequence, offset):
     edge = sequence[[0]] if offset > 0 else sequence[[-1]]
     padding = torch.repeat_interleave(edge, repeats=abs(offset), dim=0)
     return torch.cat((sequence, padding), dim=0) if offset < 0 else torch.cat((padding, sequence), dim=0)
+
+
+def seen_mocap_frames(img_mask, video_freq: float, mocap_freq: float, num_marker_frames: int, offset: int) -> torch.Tensor:
+    """EXTENSION: the video's mask [F_video] bool as the mocap frames of the fit see it, [F] bool -- through exactly the steps the
+    HMR track and its foot contacts take in multimodal_video_mocap: resample.resample_seen when the rates differ (a mocap
+    frame counts as seen only where the lerped mask is exactly 1), the truncation to the shorter of the two sequences, then
+    pad(offset)."""
+    seen = torch.as_tensor(img_mask).detach().cpu().reshape(-1) != 0
+    if mocap_freq != video_freq:
+        from .resample import resample_seen
+
+        seen = resample_seen(seen, float(video_freq), float(mocap_freq))
+    seen = seen[:min(int(num_marker_frames), int(seen.shape[0]))]
+    return pad(seen, 0 if offset is None else offset)
 
 
 def _np(t):
@@ -150,6 +164,15 @@ def multimodal_video_mocap(
         o_foot_contacts = pad(o_foot_contacts, offset).detach()
     markers = pad(markers, -offset).detach().contiguous()
     num_frames = trans.shape[0]
+    # EXTENSION: per-(frame, joint) confidence in the video's pose (stages.<stage>.prior_confidence): the weights of the pose
+    # prior of every chamfer and marker solve whose target is the HMR track, from the frames the video saw
+    prior_weights = {"chamfer": None, "marker": None}
+    for stage_name in ("chamfer", "marker"):
+        blk = stage_prior_confidence(config, stage_name)
+        if blk is not None:
+            seen = seen_mocap_frames(img_smpl.img_mask, float(img_smpl.freq), float(mocap_markers.get_frequency()),
+                                     int(mocap_markers.get_points().shape[0]), offset)
+            prior_weights[stage_name] = prior_weight_table(seen, blk)
 
     # ---- save_iterations: every closure evaluation of every stage is recorded through the stages' iter_fn hook, in the
     # reference's nesting iterations[stage][initial_angle | part][iteration][parameter] (multimodal.py:102-142)
@@ -387,7 +410,7 @@ def multimodal_video_mocap(
                               marker_labels=torch.from_numpy(np.asarray(marker_labels)).to(device),
                               img_mask=img_mask, smpl_inference=smpl_inference, initial_angle=root_orient_angle,
                               repeat=0, config=config, verbose=verbose, iter_fn=save_iter_fn,
-                              foot_contacts=o_foot_contacts)
+                              foot_contacts=o_foot_contacts, prior_weights=prior_weights["chamfer"])
                 local["chamfer_stats"] = optimization.last_stats("chamfer")
             local["chamfer"] = _np_dict(trans=trans_angle, root_orient=normalize_rot(z_root), betas=betas_angle[0],
                                         pose_body=normalize_rot(pose_angle))
@@ -405,7 +428,8 @@ def multimodal_video_mocap(
                               o_betas=o_betas, root_orient=z_root, trans=trans_angle,
                               img_mask=img_mask, smpl_inference=smpl_inference,
                               config=config, initial_angle=root_orient_angle, repeat=0, verbose=verbose,
-                              iter_fn=save_iter_fn, foot_contacts=o_foot_contacts, **placement)
+                              iter_fn=save_iter_fn, foot_contacts=o_foot_contacts, prior_weights=prior_weights["marker"],
+                              **placement)
                 local["marker_stats"] = optimization.last_stats("marker")
             if not run_chamfer and not run_marker:
                 # nothing was optimised: the marker-stage record is the chamfer-stage record (both hold the normalised
@@ -478,7 +502,7 @@ def multimodal_video_mocap(
                                   o_betas=o_betas, root_orient=h["root_orient"], trans=h["trans"],
                                   barycentric_coords_one_hot=oh, img_mask=img_mask, smpl_inference=smpl_inference,
                                   config=config, initial_angle=angle, repeat=0, verbose=verbose,
-                                  foot_contacts=o_foot_contacts)
+                                  foot_contacts=o_foot_contacts, prior_weights=prior_weights["marker"])
                     all_stats.append(optimization.last_stats("marker"))
             for local, stt in zip(locals_, all_stats):
                 local["marker_stats"] = stt

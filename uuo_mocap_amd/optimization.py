@@ -13,10 +13,11 @@ import torch.nn.functional as F
 
 from .device_lbfgs import DeviceLBFGS
 from .config import stage_surface
-from .engine import (MARKER_DISTANCE, ChamferProblem, MarkerProblem, check_foot_contacts, stage_capsules, stage_floor, stage_foot_lock,
-                     stage_joint_accel, stage_joint_limits, stage_latent_offsets, stage_robust_sigma)
+from .engine import (MARKER_DISTANCE, ChamferProblem, MarkerProblem, check_foot_contacts, check_prior_weights, stage_capsules, stage_floor,
+                     stage_foot_lock, stage_joint_accel, stage_joint_limits, stage_latent_offsets, stage_prior_confidence,
+                     stage_robust_sigma)
 from .losses import (MarkerLoss, RobustMarkerLoss, chamfer_distance, floor_loss, foot_lock_loss, joint_accel_loss,  # noqa: F401  (re-exported)
-                     self_penetration_loss, joint_limit_loss,
+                     self_penetration_loss, joint_limit_loss, weighted_pose_prior,
                      robust_weighted_chamfer_distance, soft_weighted_chamfer_distance, surface_chamfer_distance,
                      weighted_chamfer_distance)
 from .smpl import SmplInference
@@ -61,12 +62,16 @@ def optim_chamfer(
     verbose: bool = False,
     iter_fn: Callable = None,
     foot_contacts: torch.Tensor = None,
+    prior_weights: torch.Tensor = None,
 ):
     """Chamfer (pose fitting) stage: L-BFGS over [trans, z_angle, betas, pose_body], lr 0.1.  Mutates
     trans / betas / pose_body in place and applies the optimised yaw to root_orient in place.
     EXTENSION: `foot_contacts` ([F, 2] in [0, 1], optional) are the video's contact labels of the left and right foot for
-    stages.chamfer.losses.foot_lock (without them, or with labels that gate nothing, the key changes nothing)."""
+    stages.chamfer.losses.foot_lock (without them, or with labels that gate nothing, the key changes nothing).
+    EXTENSION: `prior_weights` ([F, 23] >= 0, optional; engine.prior_weight_table) weigh reg_pose_body per frame and body joint
+    (None, or ones everywhere, changes nothing; `img_mask` itself is not read)."""
     st = config["stages"]["chamfer"]
+    prior_weights = _armed_prior_weights(config, "chamfer", prior_weights, markers.shape[0])
     fused_losses = _CHAMFER_FUSED_LOSSES
     if float(st["losses"].get("soft_chamfer", 0.0)) != 0.0 and markers.is_cuda and \
             bool((config.get("execution") or {}).get("chamfer_soft_fused", True)):
@@ -75,9 +80,9 @@ def optim_chamfer(
         fused_losses = _CHAMFER_FUSED_LOSSES | {"soft_chamfer"}
     if "soft_chamfer" in fused_losses and (stage_joint_accel(config, "chamfer") > 0.0 or stage_foot_lock(config, "chamfer") > 0.0 or
                                            _floor_on(config, "chamfer") or _capsules_on(config, "chamfer") or
-                                           _limits_on(config, "chamfer")):
-        # EXTENSION: the temporal terms, the floor-contact term, the self-penetration term and the joint-angle limit term have no
-        # instantiation of the dense backward (k_bwd_dense): composed closure
+                                           _limits_on(config, "chamfer") or prior_weights is not None):
+        # EXTENSION: the temporal terms, the floor-contact term, the self-penetration term, the joint-angle limit term and the
+        # pose prior's weights have no instantiation of the dense backward (k_bwd_dense): composed closure
         fused_losses = _CHAMFER_FUSED_LOSSES
     w_surface, _ = stage_surface(config)  # EXTENSION: point-to-surface data term (validates the keys)
     if w_surface > 0.0:
@@ -93,9 +98,11 @@ def optim_chamfer(
         fused_losses = fused_losses | {"surface_chamfer"}
     if (set(st["losses"]) - fused_losses) or not st["yaw_lock"] or not _robust_fused(config, "chamfer") or \
             not _temporal_fused(config, "chamfer") or not _floor_fused(config, "chamfer") or \
-            not _capsule_fused(config, "chamfer") or not _limit_fused(config, "chamfer"):
+            not _capsule_fused(config, "chamfer") or not _limit_fused(config, "chamfer") or \
+            not _prior_conf_fused(config, prior_weights):
         return _optim_chamfer_general(markers, pose_body, o_pose_body, betas, o_betas, root_orient, trans, marker_labels,
-                                      smpl_inference, config, initial_angle, repeat, verbose, iter_fn, foot_contacts)
+                                      smpl_inference, config, initial_angle, repeat, verbose, iter_fn, foot_contacts,
+                                      prior_weights)
     from .parallel import frame_shard
 
     fs = frame_shard()
@@ -103,9 +110,11 @@ def optim_chamfer(
         if "soft_chamfer" in fused_losses:
             raise NotImplementedError("stages.chamfer.losses.soft_chamfer (extension) is not built for frame-block sharding "
                                       "(parallel.shard_frames); set execution.chamfer_soft_fused: False or use another mode")
+        _refuse_sharded_prior_weights(config, "chamfer", prior_weights)
         return _optim_chamfer_frame_sharded(fs, markers, pose_body, o_pose_body, betas, o_betas, root_orient, trans,
                                             smpl_inference, config, iter_fn)
-    prob = ChamferProblem(smpl_inference, markers, o_pose_body, o_betas, root_orient, config, foot_contacts=foot_contacts)
+    prob = ChamferProblem(smpl_inference, markers, o_pose_body, o_betas, root_orient, config, foot_contacts=foot_contacts,
+                          prior_weights=prior_weights)
     z_angle = torch.zeros((root_orient.shape[0], root_orient.shape[1], 1), device=root_orient.device)
     x = prob.pack(trans, z_angle, betas, pose_body)
     point_cb = None
@@ -299,6 +308,34 @@ def _composed_limits(config: Dict, stage: str):
     return lambda rot_body: joint_limit_loss(rot_body, lo, hi, lim["w"])
 
 
+def _prior_conf_on(config: Dict, stage: str) -> bool:
+    """True when the stage's config carries the EXTENSION block stages.<stage>.prior_confidence (validates it)."""
+    return stage_prior_confidence(config, stage) is not None
+
+
+def _armed_prior_weights(config: Dict, stage: str, prior_weights, num_frames):
+    """The stage's EXTENSION weights of the pose prior as the solvers use them: the block is validated, the table checked on the
+    host (shape, finite, >= 0: ValueError before the device is touched); None, or a table of ones, comes back as None -- nothing
+    is armed and every route is the one it was."""
+    stage_prior_confidence(config, stage)
+    w = check_prior_weights(prior_weights, num_frames)
+    if w is None or bool((w == 1.0).all()):
+        return None
+    return w
+
+
+def _prior_conf_fused(config: Dict, prior_weights) -> bool:
+    """False when armed weights of the pose prior are to run on the closure composed from the operators
+    (execution.prior_conf_fused: False, the fused closures' checker); True otherwise."""
+    return prior_weights is None or bool((config.get("execution") or {}).get("prior_conf_fused", True))
+
+
+def _refuse_sharded_prior_weights(config: Dict, stage: str, prior_weights):
+    if prior_weights is not None or _prior_conf_on(config, stage):
+        raise NotImplementedError("stages.%s.prior_confidence (extension): the pose prior's weights are not built for "
+                                  "frame-block sharding (parallel.shard_frames)" % stage)
+
+
 def _refuse_latent_offsets(config: Dict, route: str):
     if stage_latent_offsets(config) > 0.0:
         raise NotImplementedError("stages.marker.losses.latent_offsets (latent marker offsets, extension) is built for the fused "
@@ -340,6 +377,8 @@ def lockstep_supported(config: Dict, stage: str) -> bool:
     if _capsules_on(config, stage):  # EXTENSION: nor the self-penetration term
         return False
     if _limits_on(config, stage):  # EXTENSION: nor the joint-angle limit term
+        return False
+    if _prior_conf_on(config, stage):  # EXTENSION: nor the pose prior's weights
         return False
     if stage == "marker" and stage_latent_offsets(config) > 0.0:  # EXTENSION: nor the latent marker offsets
         return False
@@ -456,7 +495,8 @@ _CHAMFER_FUSED_LOSSES = {"full_chamfer", "reg_pose_body", "reg_betas", "joint_ac
 
 
 def _optim_chamfer_general(markers, pose_body, o_pose_body, betas, o_betas, root_orient, trans, marker_labels,
-                           smpl_inference, config, initial_angle, repeat, verbose, iter_fn, foot_contacts=None):
+                           smpl_inference, config, initial_angle, repeat, verbose, iter_fn, foot_contacts=None,
+                           prior_weights=None):
     """Chamfer stage with the reference's optional terms (`part_chamfer`, `trans_vel`, `ground`; plus the labelled
     extension `soft_chamfer`, a soft-assignment data term the reference does not have) and / or
     `yaw_lock: False` (reference optimization.py:164-285; none is in a shipped config): the closure is composed from the
@@ -479,6 +519,8 @@ def _optim_chamfer_general(markers, pose_body, o_pose_body, betas, o_betas, root
     floor_term = _composed_floor(config, "chamfer", contacts, smpl_inference)  # EXTENSION: floor-contact term on sole vertices
     caps_term = _composed_capsules(config, "chamfer", smpl_inference)  # EXTENSION: bone-capsule self-penetration term
     lim_term = _composed_limits(config, "chamfer")  # EXTENSION: joint-angle limit term on the body pose
+    if prior_weights is not None:  # EXTENSION: the pose prior's weights (checked by the caller)
+        prior_weights = prior_weights.to(pose_body.device)
     num_frames = pose_body.shape[0]
     root_fixed = root_orient.detach().clone()
     if st["yaw_lock"]:
@@ -517,7 +559,10 @@ def _optim_chamfer_general(markers, pose_body, o_pose_body, betas, o_betas, root
             loss = loss + soft_weighted_chamfer_distance(markers, out["vertices"], mask,
                                                          float(st.get("soft_tau", 1e-3)))[0] * w["soft_chamfer"]
         if "reg_pose_body" in w:
-            loss = loss + F.mse_loss(p_pose, o_pose_body) * w["reg_pose_body"]
+            if prior_weights is not None:  # EXTENSION: the fused closures' weighted pose prior, composed (their checker)
+                loss = loss + weighted_pose_prior(p_pose, o_pose_body, prior_weights) * w["reg_pose_body"]
+            else:
+                loss = loss + F.mse_loss(p_pose, o_pose_body) * w["reg_pose_body"]
         if "trans_vel" in w:
             markers_mean = torch.mean(markers, dim=1)
             loss = loss + F.mse_loss(p_trans[1:] - p_trans[:-1], markers_mean[1:] - markers_mean[:-1]) * w["trans_vel"]
@@ -580,6 +625,7 @@ def optim_markers(
     marker_offsets: torch.Tensor = None,
     foot_contacts: torch.Tensor = None,
     frame_assign: torch.Tensor = None,
+    prior_weights: torch.Tensor = None,
 ):
     """Marker (inverse kinematics) stage: L-BFGS over [pose_body, betas, root_orient, trans], lr 1.0, with the
     fixed marker -> vertex placement given as a one-hot [M, V] matrix.  Mutates the four leaves in place.
@@ -591,10 +637,14 @@ def optim_markers(
     EXTENSION: `frame_assign` ([F, M] int32, optional; compute_tracklet_placement) is a per-frame vertex table for captures whose
     columns change identity: entry (f, m) is the vertex of marker column m in frame f, an entry < 0 takes no part.  With it
     `barycentric_coords_one_hot` may be None.  Fused one-hot closure only: refused with latent_offsets, with
-    execution.robust_fused / temporal_fused: False, under frame-block sharding and with shared betas."""
+    execution.robust_fused / temporal_fused: False, under frame-block sharding and with shared betas.
+    EXTENSION: `prior_weights` ([F, 23] >= 0, optional; engine.prior_weight_table) weigh reg_pose_body per frame and body joint
+    (None, or ones everywhere, changes nothing; `img_mask` itself is not read)."""
+    prior_weights = _armed_prior_weights(config, "marker", prior_weights, markers.shape[0])
     if frame_assign is not None:
         return _optim_markers_frame_assign(markers, pose_body, o_pose_body, betas, o_betas, root_orient, trans, frame_assign,
-                                           smpl_inference, config, initial_angle, repeat, verbose, iter_fn, foot_contacts)
+                                           smpl_inference, config, initial_angle, repeat, verbose, iter_fn, foot_contacts,
+                                           prior_weights)
     one_hot = barycentric_coords_one_hot
     if one_hot.dim() != 2 or one_hot.shape[1] != smpl_inference.device_model.V:
         raise ValueError("barycentric_coords_one_hot must be [M, %d]" % smpl_inference.device_model.V)
@@ -605,11 +655,13 @@ def optim_markers(
     sharded = fs is not None and fs.active
     bary = None
     if not _robust_fused(config, "marker") or not _temporal_fused(config, "marker") or not _floor_fused(config, "marker") or \
-            not _capsule_fused(config, "marker") or not _limit_fused(config, "marker"):
-        # EXTENSION: execution.robust_fused / temporal_fused / floor_fused / capsule_fused / limit_fused: False -- the composed
-        # closure, the fused one's checker
+            not _capsule_fused(config, "marker") or not _limit_fused(config, "marker") or \
+            not _prior_conf_fused(config, prior_weights):
+        # EXTENSION: execution.robust_fused / temporal_fused / floor_fused / capsule_fused / limit_fused / prior_conf_fused:
+        # False -- the composed closure, the fused one's checker
         return _optim_markers_general(markers, pose_body, o_pose_body, betas, o_betas, root_orient, trans, one_hot,
-                                      smpl_inference, config, verbose, iter_fn, initial_angle, repeat, foot_contacts)
+                                      smpl_inference, config, verbose, iter_fn, initial_angle, repeat, foot_contacts,
+                                      prior_weights)
     if not bool(((rows_nz == 1) & (one_hot.sum(dim=1) == 1.0)).all()):
         # barycentric placement (compute_locations.use_barycentric): up to three weighted vertices per marker.  Fused closure
         # (k_bary_fwd + k_bwd_items) when it is that and nothing else; execution.marker_bary_fused: False, more than three
@@ -617,15 +669,19 @@ def optim_markers(
         fused = (one_hot.is_cuda and int(rows_nz.max()) <= 3 and not sharded and
                  bool((config.get("execution") or {}).get("marker_bary_fused", True)))
         if not fused:
+            if sharded:
+                _refuse_sharded_prior_weights(config, "marker", prior_weights)
             return _optim_markers_general(markers, pose_body, o_pose_body, betas, o_betas, root_orient, trans, one_hot,
-                                          smpl_inference, config, verbose, iter_fn, initial_angle, repeat, foot_contacts)
+                                          smpl_inference, config, verbose, iter_fn, initial_angle, repeat, foot_contacts,
+                                          prior_weights)
         bary = placement_corners(one_hot)
     assign = bary[0] if bary is not None else torch.argmax(one_hot, dim=-1)
     if sharded:
+        _refuse_sharded_prior_weights(config, "marker", prior_weights)
         return _optim_markers_frame_sharded(fs, markers, pose_body, o_pose_body, betas, o_betas, root_orient, trans, assign,
                                             smpl_inference, config, iter_fn)
     prob = MarkerProblem(smpl_inference, markers, o_pose_body, o_betas, assign, config, bary=None if bary is None else bary[1],
-                         foot_contacts=foot_contacts)
+                         foot_contacts=foot_contacts, prior_weights=prior_weights)
     x = prob.pack(pose_body, betas, root_orient, trans)
     if prob.has_offsets:  # EXTENSION: latent marker offsets, every solve from the data-driven start value
         from .parallel import shared_betas_reducer
@@ -656,7 +712,7 @@ def optim_markers(
 
 
 def _optim_markers_frame_assign(markers, pose_body, o_pose_body, betas, o_betas, root_orient, trans, frame_assign, smpl_inference,
-                                config, initial_angle, repeat, verbose, iter_fn, foot_contacts):
+                                config, initial_angle, repeat, verbose, iter_fn, foot_contacts, prior_weights=None):
     """EXTENSION: optim_markers on a per-frame vertex table (uuo_fit_set_frame_assign)."""
     from .parallel import frame_shard, shared_betas_reducer
 
@@ -665,9 +721,10 @@ def _optim_markers_frame_assign(markers, pose_body, o_pose_body, betas, o_betas,
         raise NotImplementedError("%s is not built for the floor-contact term (stages.marker.losses.floor_penetration / "
                                   "floor_contact)" % what)
     if not _robust_fused(config, "marker") or not _temporal_fused(config, "marker") or not _capsule_fused(config, "marker") or \
-            not _limit_fused(config, "marker"):
+            not _limit_fused(config, "marker") or not _prior_conf_fused(config, prior_weights):
         raise NotImplementedError("%s is built for the fused marker closure only, not for the closure composed from the operators "
-                                  "(execution.robust_fused / temporal_fused / capsule_fused / limit_fused: False)" % what)
+                                  "(execution.robust_fused / temporal_fused / capsule_fused / limit_fused / prior_conf_fused: "
+                                  "False)" % what)
     _refuse_latent_offsets(config, what + ": an offset per column has no meaning once the column changes identity")
     fs = frame_shard()
     if fs is not None and fs.active:
@@ -675,7 +732,7 @@ def _optim_markers_frame_assign(markers, pose_body, o_pose_body, betas, o_betas,
     if shared_betas_reducer() is not None:
         raise NotImplementedError("%s is not built for shared betas (parallel.shared_betas)" % what)
     prob = MarkerProblem(smpl_inference, markers, o_pose_body, o_betas, None, config, foot_contacts=foot_contacts,
-                         frame_assign=frame_assign)
+                         frame_assign=frame_assign, prior_weights=prior_weights)
     x = prob.pack(pose_body, betas, root_orient, trans)
     point_cb = None
     if iter_fn is not None:
@@ -698,7 +755,7 @@ def _optim_markers_frame_assign(markers, pose_body, o_pose_body, betas, o_betas,
 
 
 def _optim_markers_general(markers, pose_body, o_pose_body, betas, o_betas, root_orient, trans, coords, smpl_inference,
-                           config, verbose, iter_fn=None, initial_angle=0, repeat=0, foot_contacts=None):
+                           config, verbose, iter_fn=None, initial_angle=0, repeat=0, foot_contacts=None, prior_weights=None):
     """Marker stage for a general placement matrix [M, V] (reference optimization.py:288-399 as written: virtual
     markers = coords @ vertices).  The fused device solver covers the one-hot placements of the shipped configs; this
     path composes the same closure from the differentiable HIP operators (SmplInference forward / uuo_smpl_backward)
@@ -721,6 +778,8 @@ def _optim_markers_general(markers, pose_body, o_pose_body, betas, o_betas, root
     floor_term = _composed_floor(config, "marker", contacts, smpl_inference)  # EXTENSION: floor-contact term on sole vertices
     caps_term = _composed_capsules(config, "marker", smpl_inference)  # EXTENSION: bone-capsule self-penetration term
     lim_term = _composed_limits(config, "marker")  # EXTENSION: joint-angle limit term on the body pose
+    if prior_weights is not None:  # EXTENSION: the pose prior's weights (checked by the caller)
+        prior_weights = prior_weights.to(pose_body.device)
     num_frames = pose_body.shape[0]
     leaves = [pose_body, betas, root_orient, trans]
     params = [p.detach().clone().requires_grad_(True) for p in leaves]
@@ -746,7 +805,10 @@ def _optim_markers_general(markers, pose_body, o_pose_body, betas, o_betas, root
             loss = loss + torch.mean(MarkerLoss(markers=markers, virtual_markers=virtual, marker_weights=weights,
                                                 marker_distance=MARKER_DISTANCE)) * st["losses"]["marker"]
         if "reg_pose_body" in st["losses"]:
-            loss = loss + F.mse_loss(p_pose, o_pose_body) * st["losses"]["reg_pose_body"]
+            if prior_weights is not None:  # EXTENSION: the fused closures' weighted pose prior, composed (their checker)
+                loss = loss + weighted_pose_prior(p_pose, o_pose_body, prior_weights) * st["losses"]["reg_pose_body"]
+            else:
+                loss = loss + F.mse_loss(p_pose, o_pose_body) * st["losses"]["reg_pose_body"]
         if "reg_betas" in st["losses"]:
             loss = loss + F.mse_loss(p_betas, o_betas) * st["losses"]["reg_betas"]
         if "joint_accel" in st["losses"]:  # EXTENSION: the fused closures' joint-acceleration term, composed (their checker)

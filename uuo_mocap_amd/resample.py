@@ -76,3 +76,17 @@ def resample_hmr(trans: torch.Tensor, root_orient: torch.Tensor, pose_body: torc
 
     out_fc = lerp(foot_contacts) if foot_contacts is not None else None
     return lerp(trans), slerp(root_orient), slerp(pose_body), out_fc
+
+
+def resample_seen(seen: torch.Tensor, src_freq: float, dst_freq: float) -> torch.Tensor:
+    """EXTENSION: the video's mask `seen` [F] bool at `src_freq` on resample_hmr's frames at `dst_freq`: a resampled frame
+    counts as seen only where resample_hmr's lerp of the mask (as 0 / 1) is exactly 1 -- its source frame is seen, and so is the
+    next one unless the frame does not interpolate (the last source frame) or sits exactly on its source frame (alpha = 0).
+    Stated on the booleans, so that no rounding of alpha + (1 - alpha) decides it."""
+    sn = seen.reshape(-1) != 0
+    F = int(sn.shape[0])
+    frame, alpha, interp = resample_plan(F, src_freq, dst_freq)
+    frame, interp = frame.to(sn.device), interp.to(sn.device)
+    nxt = torch.clamp(frame + 1, max=F - 1)
+    on_frame = (alpha.to(dtype=torch.float32) == 0.0).to(sn.device)   # (the fp32 alpha resample_hmr multiplies by)
+    return sn[frame] & (sn[nxt] | ~interp | on_frame)

@@ -143,6 +143,8 @@ def _arm_into_torso(tables, hmr_rot, rest, caps, t0):
 #: window length, the x component of the HMR start's left knee there (radians), taper
 LIMITED_COMPONENTS = ((4, 0, 1.0), (5, 0, 1.0), (18, 1, -1.0), (19, 1, 1.0))
 LIMIT_WINDOW, LIMIT_KNEE_X, LIMIT_TAPER = 24, -0.5, 2
+#: video_dropout: frames for which the video loses the person (three seconds at 30 Hz)
+DROPOUT_WINDOW = 90
 
 
 def farthest_point_vertices(points: np.ndarray, count: int, start: int = 0) -> np.ndarray:
@@ -202,7 +204,8 @@ def make_sequence(tables: SmplTables, seed: int = 0, num_frames: int = 300, num_
                   hmr_pose_noise: float = 0.1, hmr_beta_noise: float = 0.5, subject_seed: int = None,
                   standoff_tilt_deg: float = 0.0, standoff_mm=(9.5, 9.5), planted_feet: bool = False,
                   stance_frames: int = 20, identity_events: int = 0, floor: bool = False,
-                  self_penetration: bool = False, joint_limits: bool = False) -> SyntheticSequence:
+                  self_penetration: bool = False, joint_limits: bool = False,
+                  video_dropout: bool = False) -> SyntheticSequence:
     """One synthetic sequence: smooth GT motion, unlabeled-but-tracked markers 9.5 mm off the
     surface with 1 mm noise and block dropout, and an HMR stand-in (noisy pose/shape, wrong yaw).  `subject_seed` fixes the
     ground-truth shape independently of `seed`: sequences of ONE subject (the shared-betas extension fits them together).
@@ -244,7 +247,14 @@ def make_sequence(tables: SmplTables, seed: int = 0, num_frames: int = 300, num_
     rotated cyclically (a takes b's, b takes c's, c takes a's); every second event also blanks the three columns for the five
     frames before t_e.  gt["marker_vids_fm"] [F, M] holds the true vertex of every entry (-1 where missing), gt["tracklets_fm"]
     [F, M] the true tracklet ids (a run of consecutive visible frames of one column showing one marker; dense ids ordered by
-    (column, start), -1 where missing).  With 0 events no hash stream is consumed and every other array is unchanged."""
+    (column, start), -1 where missing).  With 0 events no hash stream is consumed and every other array is unchanged.
+    A capture whose video loses the person (EXTENSION tests of the pose prior's weights): with `video_dropout` the tracker drops
+    the subject for DROPOUT_WINDOW = 90 frames from frame F / 3 on (rounded up; ValueError unless a seen frame is left on both
+    sides).  img_mask is False there, and the stand-in's pose_body, root_orient, hmr_root_orient, trans and betas in the window
+    are what ingest.fill_gaps makes of its own neighbours (slerp / lerp across the gap), as ingest.ImgSmpl would; foot_contacts
+    are 0 there.  The markers are untouched.  gt["dropout_window"] = (first frame, one past the last), gt["hmr_gap_error"] [F]
+    the mean geodesic distance (radians, over the 23 body joints) of the stand-in's pose -- filled, inside the window -- from
+    the ground truth's.  No hash stream is consumed; without the option every array is what it was."""
     F, M = num_frames, num_markers
     if floor and not planted_feet:
         raise ValueError("make_sequence: floor=True needs planted_feet=True (the floor is built under the planted feet)")
@@ -430,18 +440,38 @@ def make_sequence(tables: SmplTables, seed: int = 0, num_frames: int = 300, num_
         markers[t0:t0 + LIMIT_WINDOW, leg_cols] = 0.0
 
     f32 = lambda x: torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
+    img_mask = torch.ones(F, dtype=torch.bool)
+    tracks = {"trans": f32(hmr_trans), "root_orient": f32(hmr_root[:, None]), "pose_body": f32(hmr_rot[:, 1:]),
+              "betas": f32(hmr_betas)}
+    contacts_img = f32(contacts_seen) if planted_feet else torch.zeros(F, 2)
+    dropout_window = hmr_gap_error = None
+    if video_dropout:  # (no hash stream: the video's tracks and labels inside the window change, nothing else)
+        from .ingest import fill_gaps
+
+        t0 = -(-F // 3)
+        if t0 < 1 or t0 + DROPOUT_WINDOW >= F:
+            raise ValueError("make_sequence: video_dropout needs a window of %d frames from frame %d on with a seen frame on both "
+                             "sides (F = %d)" % (DROPOUT_WINDOW, t0, F))
+        dropout_window = (t0, t0 + DROPOUT_WINDOW)
+        img_mask[t0:t0 + DROPOUT_WINDOW] = False
+        tracks = fill_gaps(tracks, img_mask)
+        contacts_img = contacts_img.clone()
+        contacts_img[t0:t0 + DROPOUT_WINDOW] = 0.0
+        rel = np.einsum("fjab,fjac->fjbc", rot[:, 1:], tracks["pose_body"].numpy().astype(np.float64))
+        cos = np.clip(0.5 * (np.trace(rel, axis1=-2, axis2=-1) - 1.0), -1.0, 1.0)
+        hmr_gap_error = np.arccos(cos).mean(axis=1)
     img = SyntheticImgSmpl(
-        trans=f32(hmr_trans),
-        root_orient=f32(hmr_root[:, None]),
-        hmr_root_orient=f32(hmr_root[:, None]),
-        pose_body=f32(hmr_rot[:, 1:]),
-        betas=f32(hmr_betas),
-        foot_contacts=f32(contacts_seen) if planted_feet else torch.zeros(F, 2),
+        trans=tracks["trans"],
+        root_orient=tracks["root_orient"],
+        hmr_root_orient=tracks["root_orient"].clone(),
+        pose_body=tracks["pose_body"],
+        betas=tracks["betas"],
+        foot_contacts=contacts_img,
         camera_bbox=torch.zeros(F, 3),
         center=torch.zeros(F, 2),
         scale=torch.zeros(F, 1),
         size=torch.zeros(F, 2),
-        img_mask=torch.ones(F, dtype=torch.bool),
+        img_mask=img_mask,
         freq=30.0,
     )
     gt = {
@@ -465,6 +495,9 @@ def make_sequence(tables: SmplTables, seed: int = 0, num_frames: int = 300, num_
         gt["joint_limits"] = limits
         gt["limit_window"] = limit_window
         gt["hmr_violation"] = hmr_violation
+    if video_dropout:
+        gt["dropout_window"] = dropout_window
+        gt["hmr_gap_error"] = hmr_gap_error
     return SyntheticSequence(img_smpl=img, markers=SyntheticMarkers(markers.astype(np.float32), 30.0), gt=gt)
 
 

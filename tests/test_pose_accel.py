@@ -1,0 +1,292 @@
+"""EXTENSION: the pose-acceleration term on the local body rotations (stages.{chamfer,marker}.losses.pose_accel,
+losses.pose_accel_loss; it runs on the closures composed from the operators) -- the float64 restatement against the closed form
+and against difference quotients, its exact zeros, the package's term against the restatement, config parsing and routing, the
+refusals that need no device, and the metric.  No GPU needed (tests/test_gpu_pose_accel.py holds the solves and the fits)."""
+import math
+
+import pytest
+import torch
+
+from pose_accel_ref64 import (gram_schmidt64, pose_accel64, pose_accel_grad64, pose_accel_of_rotations64, random_raw,
+                              stencil64)
+
+from uuo_mocap_amd.metrics import LEAF_JOINT_ROWS as LEAF_ROWS
+
+INF = float("inf")
+U_TABLE = [1.0] * 23
+U_TABLE[3], U_TABLE[9], U_TABLE[17] = 0.0, 0.5, 1.75    # a zero, a value below and one above 1
+
+
+def _cfg(name="video_mocap", **stages):
+    """packaged config; per stage a dict whose `pose_accel_block` entry goes on the stage as `pose_accel`, the rest on its losses"""
+    from uuo_mocap_amd.config import packaged_config
+
+    cfg = packaged_config(name)
+    for stage, kv in stages.items():
+        for k, v in kv.items():
+            if k == "pose_accel_block":
+                cfg["stages"][stage]["pose_accel"] = v
+            else:
+                cfg["stages"][stage]["losses"][k] = v
+    return cfg
+
+
+# ------------------------------------------------------------------------------------------------ 1. the restatement
+@pytest.mark.parametrize("u", [None, U_TABLE])
+@pytest.mark.parametrize("F", [3, 4, 5, 6, 9])
+def test_autograd_gradient_is_the_closed_form_stencil(F, u):
+    """d loss / d R by float64 autograd equals (2 w u / ((F - 2) 207)) (a_s - 2 a_{s-1} + a_{s-2}) frame by frame, and the
+    gradient on the raw entries is that stencil pulled through the Gram-Schmidt normalisation"""
+    raw = random_raw(F, 40 + F).double()
+    R = gram_schmidt64(raw).detach().clone().requires_grad_(True)
+    loss = pose_accel_of_rotations64(R, 3.0, u)
+    (g,) = torch.autograd.grad(loss, [R])
+    closed = stencil64(R, 3.0, u)
+    assert float((g - closed).abs().max()) <= 1e-14 * max(1.0, float(closed.abs().max()))
+    assert float(closed.abs().max()) > 1e-4
+    # through the normalisation: vjp of Gram-Schmidt with the stencil
+    leaf = raw.clone().requires_grad_(True)
+    (via,) = torch.autograd.grad(gram_schmidt64(leaf), [leaf], grad_outputs=closed)
+    _, g_raw = pose_accel_grad64(raw, 3.0, u)
+    assert float((via - g_raw).abs().max()) <= 1e-13 * max(1.0, float(g_raw.abs().max()))
+    assert not g_raw[:, :, 2, :].any()       # third raw rows: exact zeros (Gram-Schmidt does not read them)
+    # not normalising: the stencil itself
+    _, g_plain = pose_accel_grad64(raw, 3.0, u, normalise=False)
+    assert float((g_plain - stencil64(raw, 3.0, u)).abs().max()) <= 1e-13 * float(g_plain.abs().max())
+
+
+@pytest.mark.parametrize("normalise", [True, False])
+@pytest.mark.parametrize("F", [3, 4, 5])
+def test_gradient_against_central_differences(F, normalise):
+    raw = random_raw(F, 70 + F).double()
+    loss, g = pose_accel_grad64(raw, 2.0, U_TABLE, normalise)
+    assert loss > 0.0
+    gen = torch.Generator().manual_seed(5)
+    h = 1e-6
+    for _ in range(40):
+        f, j, r, c = (int(torch.randint(0, n, (1,), generator=gen)) for n in (F, 23, 3, 3))
+        up, dn = raw.clone(), raw.clone()
+        up[f, j, r, c] += h
+        dn[f, j, r, c] -= h
+        fd = (float(pose_accel64(up, 2.0, U_TABLE, normalise)) - float(pose_accel64(dn, 2.0, U_TABLE, normalise))) / (2.0 * h)
+        assert abs(fd - float(g[f, j, r, c])) <= 1e-7 + 1e-6 * abs(fd), (f, j, r, c, fd, float(g[f, j, r, c]))
+
+
+def test_normaliser_is_mse_of_the_second_difference():
+    raw = random_raw(6, 3).double()
+    R = gram_schmidt64(raw)
+    a = R[:-2] - 2.0 * R[1:-1] + R[2:]
+    assert float(pose_accel64(raw, 1.0)) == pytest.approx(float(torch.nn.functional.mse_loss(a, torch.zeros_like(a))), rel=1e-14)
+    # small angles: |R_a - R_b|_F^2 ~ 2 theta^2 -- a joint turning about z by t^2 * 1e-3 rad has a second difference of 2e-3 rad
+    th = 1e-3 * torch.arange(5, dtype=torch.float64) ** 2
+    Rz = torch.eye(3, dtype=torch.float64).repeat(5, 23, 1, 1)
+    Rz[:, 0, 0, 0], Rz[:, 0, 0, 1], Rz[:, 0, 1, 0], Rz[:, 0, 1, 1] = torch.cos(th), -torch.sin(th), torch.sin(th), torch.cos(th)
+    got = float(pose_accel_of_rotations64(Rz, 1.0)) * 3 * 207.0 / 3      # per second difference of the one moving joint
+    assert got == pytest.approx(2.0 * (2e-3) ** 2, rel=1e-3)
+
+
+@pytest.mark.parametrize("F", [1, 2])
+def test_fewer_than_three_frames_give_exactly_zero(F):
+    from uuo_mocap_amd.losses import pose_accel_loss
+
+    raw = random_raw(F, 9).double()
+    loss, g = pose_accel_grad64(raw, 5.0, U_TABLE)
+    assert loss == 0.0 and not g.any()
+    leaf = raw.clone().requires_grad_(True)
+    composed = pose_accel_loss(gram_schmidt64(leaf), 5.0, U_TABLE)
+    assert float(composed.detach()) == 0.0
+    (gc,) = torch.autograd.grad(composed, [leaf])
+    assert not gc.any()
+
+
+def test_zero_joint_weight_gives_exact_zero_rows():
+    raw = random_raw(7, 11).double()
+    u = list(U_TABLE)
+    _, g = pose_accel_grad64(raw, 4.0, u)
+    assert not g[:, 3].any() and bool((g[:, 3] == 0.0).all())
+    live = [j for j in range(23) if u[j] != 0.0]
+    assert bool((g[:, live][:, :, :2].abs().amax(dim=(0, 2, 3)) > 0.0).all())
+    assert not stencil64(gram_schmidt64(raw), 4.0, u)[:, 3].any()
+    # and the weights are linear: the loss is the weighted sum of the per-joint losses
+    per_joint = [float(pose_accel64(raw, 4.0, [1.0 if k == j else 0.0 for k in range(23)])) for j in range(23)]
+    assert float(pose_accel64(raw, 4.0, u)) == pytest.approx(sum(a * b for a, b in zip(u, per_joint)), rel=1e-13)
+
+
+@pytest.mark.parametrize("u", [None, U_TABLE])
+def test_composed_term_is_the_restatement(u):
+    """losses.pose_accel_loss (the checker of the fused term on the operator-composed routes) on normalize_rot of the raw entries"""
+    from uuo_mocap_amd.losses import pose_accel_loss
+    from uuo_mocap_amd.transforms import normalize_rot
+
+    raw = random_raw(8, 21).double()
+    ref, g_ref = pose_accel_grad64(raw, 0.7, u)
+    leaf = raw.clone().requires_grad_(True)
+    loss = pose_accel_loss(normalize_rot(leaf), 0.7, u)
+    (g,) = torch.autograd.grad(loss, [leaf])
+    assert float(loss.detach()) == pytest.approx(ref, rel=1e-12)
+    assert float((g - g_ref).abs().max()) <= 1e-12 * float(g_ref.abs().max())
+
+
+# ------------------------------------------------------------------------------------------------ 2. config, routing, refusals
+@pytest.mark.parametrize("stage", ["chamfer", "marker"])
+def test_stage_pose_accel_parsing(stage):
+    from uuo_mocap_amd.engine import stage_pose_accel
+
+    assert stage_pose_accel(_cfg(), stage) == {"w": 0.0, "joint_weights": None}
+    assert stage_pose_accel(_cfg(**{stage: {"pose_accel": None}}), stage) == {"w": 0.0, "joint_weights": None}
+    assert stage_pose_accel(_cfg(**{stage: {"pose_accel": 2}}), stage) == {"w": 2.0, "joint_weights": None}
+    assert stage_pose_accel(_cfg(**{stage: {"pose_accel": 2.5, "pose_accel_block": None}}), stage)["joint_weights"] is None
+    assert stage_pose_accel(_cfg(**{stage: {"pose_accel": 2.5, "pose_accel_block": {}}}), stage)["joint_weights"] is None
+    got = stage_pose_accel(_cfg(**{stage: {"pose_accel": 2.5, "pose_accel_block": {"joint_weights": U_TABLE}}}), stage)
+    assert got == {"w": 2.5, "joint_weights": U_TABLE}
+    other = "marker" if stage == "chamfer" else "chamfer"
+    assert stage_pose_accel(_cfg(**{stage: {"pose_accel": 2.5}}), other)["w"] == 0.0          # per stage
+    for bad in (-1.0, -1e-30, INF, -INF, float("nan")):
+        with pytest.raises(ValueError, match="pose_accel"):
+            stage_pose_accel(_cfg(**{stage: {"pose_accel": bad}}), stage)
+    bad_blocks = [{"joint_weights": [1.0] * 22}, {"joint_weights": [1.0] * 24}, {"joint_weights": [1.0] * 22 + [-0.5]},
+                  {"joint_weights": [1.0] * 22 + [INF]}, {"joint_weights": [1.0] * 22 + [float("nan")]}, {"joint_weights": 1.0},
+                  {"joint_weights": [1.0] * 22 + [True]}, {"weights": [1.0] * 23}, [1.0] * 23, "on"]
+    for blk in bad_blocks:
+        with pytest.raises(ValueError, match="pose_accel"):
+            stage_pose_accel(_cfg(**{stage: {"pose_accel": 1.0, "pose_accel_block": blk}}), stage)
+
+
+def test_bad_values_and_the_stage_problems_refuse_before_the_device_is_touched():
+    """the fused stage problems have no closure for the term: a non-zero weight is refused, weight 0 is the key absent"""
+    from uuo_mocap_amd.engine import ChamferProblem, MarkerProblem, PartProblem
+
+    with pytest.raises(ValueError, match="pose_accel"):
+        ChamferProblem(None, None, None, None, None, _cfg(chamfer={"pose_accel": -1.0}))
+    with pytest.raises(ValueError, match="pose_accel"):
+        MarkerProblem(None, None, None, None, None, _cfg(marker={"pose_accel": 1.0, "pose_accel_block": {"joint_weights": [1.0]}}))
+    with pytest.raises(NotImplementedError, match="pose_accel.*no fused closure"):
+        ChamferProblem(None, None, None, None, None, _cfg(chamfer={"pose_accel": 1.0}))
+    with pytest.raises(NotImplementedError, match="pose_accel.*no fused closure"):
+        MarkerProblem(None, None, None, None, None, _cfg(marker={"pose_accel": 1.0}))
+    with pytest.raises(NotImplementedError, match="pose_accel"):   # the part stage refuses the key with its other unknown losses
+        PartProblem(None, None, None, None, None, None, _cfg(part={"pose_accel": 1.0}))
+
+
+def test_shipped_config_loads_and_differs_from_its_parent_only_by_the_key():
+    from uuo_mocap_amd.engine import stage_pose_accel
+
+    plain, smooth = _cfg(), _cfg("video_mocap_rotsmooth")
+    for stage in ("chamfer", "marker"):
+        rec = stage_pose_accel(smooth, stage)
+        assert rec["w"] > 0.0 and math.isfinite(rec["w"]) and rec["joint_weights"] is None
+        assert stage_pose_accel(plain, stage)["w"] == 0.0
+        assert {k: v for k, v in smooth["stages"][stage]["losses"].items() if k != "pose_accel"} == plain["stages"][stage]["losses"]
+        assert {k: v for k, v in smooth["stages"][stage].items() if k != "losses"} == \
+            {k: v for k, v in plain["stages"][stage].items() if k != "losses"}
+    for k in plain["stages"]:
+        if k not in ("chamfer", "marker"):
+            assert smooth["stages"][k] == plain["stages"][k]
+    assert {k: v for k, v in smooth.items() if k not in ("stages", "name", "parent")} == \
+        {k: v for k, v in plain.items() if k not in ("stages", "name", "parent")}
+
+
+def test_routing_flags():
+    from uuo_mocap_amd.optimization import _composed_pose_accel, _pose_accel_on, lockstep_supported
+
+    plain, smooth = _cfg(), _cfg("video_mocap_rotsmooth")
+    for stage in ("chamfer", "marker"):
+        assert not _pose_accel_on(plain, stage) and _pose_accel_on(smooth, stage)
+        assert lockstep_supported(plain, stage) and not lockstep_supported(smooth, stage)   # the term runs composed: no lock-step
+        assert lockstep_supported(_cfg(**{stage: {"pose_accel": 0.0}}), stage)
+        assert _composed_pose_accel(plain, stage) is None
+        term = _composed_pose_accel(_cfg(**{stage: {"pose_accel": 0.7, "pose_accel_block": {"joint_weights": U_TABLE}}}), stage)
+        raw = random_raw(5, 2).double()
+        assert float(term(gram_schmidt64(raw))) == pytest.approx(float(pose_accel64(raw, 0.7, U_TABLE)), rel=1e-12)
+
+
+def _zeros(*s):
+    return torch.zeros(*s)
+
+
+class _Smpl:
+    class device_model:
+        V = 6890
+
+
+def _stage_args(F, M):
+    markers = _zeros(F, M, 3)
+    one_hot = _zeros(M, 6890)
+    one_hot[:, 0] = 1.0
+    args_c = (markers, _zeros(F, 23, 3, 3), _zeros(F, 23, 3, 3), _zeros(1, 10), _zeros(1, 10), _zeros(F, 1, 3, 3), _zeros(F, 3),
+              _zeros(F), torch.zeros(F, M, dtype=torch.long), None)
+    args_m = (markers, _zeros(F, 23, 3, 3), _zeros(F, 23, 3, 3), _zeros(1, 10), _zeros(1, 10), _zeros(F, 1, 3, 3),
+              _zeros(F, 3), one_hot, _zeros(F), _Smpl)
+    return args_c, args_m
+
+
+def test_composed_routes_are_taken(monkeypatch):
+    """a non-zero weight goes to the closures composed from the operators; weight 0 stays on the fused route"""
+    from uuo_mocap_amd import optimization as opt
+
+    args_c, args_m = _stage_args(6, 4)
+    taken = []
+    monkeypatch.setattr(opt, "_optim_chamfer_general", lambda *a, **k: taken.append("chamfer"))
+    monkeypatch.setattr(opt, "_optim_markers_general", lambda *a, **k: taken.append("marker"))
+    opt.optim_chamfer(*args_c, _cfg("video_mocap_rotsmooth"))
+    opt.optim_markers(*args_m, _cfg("video_mocap_rotsmooth"))
+    assert taken == ["chamfer", "marker"]
+
+    class _Stop(Exception):
+        pass
+
+    def stop(*a, **k):
+        raise _Stop()
+
+    monkeypatch.setattr(opt, "ChamferProblem", stop)
+    monkeypatch.setattr(opt, "MarkerProblem", stop)
+    zero = _cfg(chamfer={"pose_accel": 0.0}, marker={"pose_accel": 0.0})
+    with pytest.raises(_Stop):
+        opt.optim_chamfer(*args_c, zero)
+    with pytest.raises(_Stop):
+        opt.optim_markers(*args_m, zero)
+    assert len(taken) == 2
+
+
+def test_frame_sharding_refuses_the_term_before_touching_a_device():
+    from uuo_mocap_amd import parallel
+    from uuo_mocap_amd.optimization import optim_chamfer, optim_markers
+
+    args_c, args_m = _stage_args(6, 4)   # host tensors, no body model: anything past the refusal would fail otherwise
+    with parallel.shard_frames(joint_with_one_rank=True):
+        with pytest.raises(NotImplementedError, match="pose_accel.*frame-block sharding"):
+            optim_chamfer(*args_c, _cfg("video_mocap_rotsmooth"))
+        with pytest.raises(NotImplementedError, match="pose_accel.*frame-block sharding"):
+            optim_markers(*args_m, _cfg("video_mocap_rotsmooth"))
+
+
+# ------------------------------------------------------------------------------------------------ 3. the metric
+def test_rotation_accel_error_is_zero_for_identical_tracks():
+    from uuo_mocap_amd.metrics import compute_rotation_accel_error
+
+    R = gram_schmidt64(random_raw(9, 5).double())
+    assert float(compute_rotation_accel_error(R, R.clone(), 30.0)) == 0.0
+    assert float(compute_rotation_accel_error(R, R.clone(), 30.0, joints_ids=LEAF_ROWS)) == 0.0
+    # a track that differs by a constant and by a linear drift has the same second difference
+    t = torch.arange(9, dtype=torch.float64)[:, None, None, None]
+    assert float(compute_rotation_accel_error(R + 0.3 + 0.01 * t, R, 30.0)) < 1e-9
+    for bad in ((R[:2], R[:2]), (R, R[:8]), (R[..., 0], R[..., 0])):
+        with pytest.raises(ValueError, match="F, J, 3, 3"):
+            compute_rotation_accel_error(*bad, 30.0)
+
+
+def test_rotation_accel_error_by_hand():
+    """4 frames, 2 joints, gt all zeros.  Joint 0: c_t I with c = 0, 1, 4, 9 -- both second differences are 2 I, Frobenius norm
+    2 sqrt 3.  Joint 1: entry (0, 0) = 0, 0, 1, 0 -- second differences 1 and -2.  Mean (2 sqrt 3 + 2 sqrt 3 + 1 + 2) / 4, times
+    freq^2 = 4."""
+    from uuo_mocap_amd.metrics import compute_rotation_accel_error
+
+    P = torch.zeros(4, 2, 3, 3, dtype=torch.float64)
+    for t, c in enumerate((0.0, 1.0, 4.0, 9.0)):
+        P[t, 0] = c * torch.eye(3, dtype=torch.float64)
+    P[2, 1, 0, 0] = 1.0
+    G = torch.zeros_like(P)
+    assert float(compute_rotation_accel_error(P, G, 2.0)) == pytest.approx(4.0 * (4.0 * math.sqrt(3.0) + 3.0) / 4.0, rel=1e-14)
+    assert float(compute_rotation_accel_error(P, G, 2.0, joints_ids=[1])) == pytest.approx(4.0 * 1.5, rel=1e-14)
+    assert float(compute_rotation_accel_error(P, G, 2.0, joints_ids=[0])) == pytest.approx(4.0 * 2.0 * math.sqrt(3.0), rel=1e-14)
+    assert float(compute_rotation_accel_error(G, P, 2.0)) == pytest.approx(float(compute_rotation_accel_error(P, G, 2.0)), rel=1e-14)

@@ -1001,6 +1001,33 @@ def stage_joint_limits(config: Dict, stage: str) -> Dict:
     return {"w": v, "limits": lim}
 
 
+def stage_pose_accel(config: Dict, stage: str) -> Dict:
+    """EXTENSION: the pose-acceleration term of the chamfer or marker stage (losses.pose_accel_loss) as a config states it --
+    stages.<stage>.losses.pose_accel (a weight on rad^2 per frame^4: it belongs to the frame rate; absent or 0 = off; negative or
+    non-finite weights are refused) and the optional stages.<stage>.pose_accel: null or {joint_weights: null | [23 floats]},
+    finite values >= 0 (entry j - 1 is SMPL joint j; null = ones).  Returns {"w", "joint_weights"}.  (The part stage refuses the
+    key with its other unknown losses.)"""
+    st = config["stages"][stage]
+    losses = st.get("losses") or {}
+    v = losses.get("pose_accel", 0.0)
+    v = 0.0 if v is None else float(v)
+    if not math.isfinite(v) or v < 0.0:
+        raise ValueError("stages.%s.losses.pose_accel must be 0 (off) or a positive weight (got %r)" % (stage, v))
+    blk = st.get("pose_accel", None)
+    jw = None
+    if blk is not None:
+        what = "stages.%s.pose_accel" % stage
+        if not isinstance(blk, dict) or set(blk) - {"joint_weights"}:
+            raise ValueError("%s must be null or {joint_weights} (got %r)" % (what, blk))
+        jw = blk.get("joint_weights", None)
+        if jw is not None:
+            number = lambda q: isinstance(q, (int, float)) and not isinstance(q, bool) and math.isfinite(q)
+            if not isinstance(jw, (list, tuple)) or len(jw) != 23 or not all(number(q) and q >= 0.0 for q in jw):
+                raise ValueError("%s.joint_weights must be null or 23 finite values >= 0 (got %r)" % (what, jw))
+            jw = [float(q) for q in jw]
+    return {"w": v, "joint_weights": jw}
+
+
 def stage_prior_confidence(config: Dict, stage: str):
     """EXTENSION: the per-(frame, joint) confidence in the video's pose of the chamfer or marker stage as a config states it --
     stages.<stage>.prior_confidence: absent or null = off (returns None), else {gap_weight: 0.0, ramp: 0, joint_weights: null}:
@@ -1092,7 +1119,7 @@ class ChamferProblem(_StageProblem):
         losses = config["stages"]["chamfer"]["losses"]
         unsupported = set(losses) - {"full_chamfer", "reg_pose_body", "reg_betas", "soft_chamfer", "joint_accel", "foot_lock",
                                      "surface_chamfer", "floor_penetration", "floor_contact", "self_penetration",
-                                     "joint_limits"}
+                                     "joint_limits", "pose_accel"}
         if unsupported:
             raise NotImplementedError("chamfer-stage losses outside the shipped configs: %s" % sorted(unsupported))
         w_surface, d_surface = stage_surface(config)  # EXTENSION: point-to-surface data term (0 = off)
@@ -1104,6 +1131,9 @@ class ChamferProblem(_StageProblem):
         if lim["w"] > 0.0 and float(losses.get("soft_chamfer", 0.0)) != 0.0:
             raise NotImplementedError("stages.chamfer: the fused joint-angle limit term (joint_limits) is not built for the "
                                       "soft-assignment closure; optim_chamfer composes that combination from the operators")
+        if stage_pose_accel(config, "chamfer")["w"] > 0.0:  # EXTENSION: pose-acceleration term on the local body rotations
+            raise NotImplementedError("stages.chamfer.losses.pose_accel (extension) has no fused closure: optim_chamfer composes "
+                                      "it from the operators")
         w_accel = stage_joint_accel(config, "chamfer")
         if w_accel > 0.0 and float(losses.get("soft_chamfer", 0.0)) != 0.0:
             raise NotImplementedError("stages.chamfer: the fused joint-acceleration term (joint_accel) is not built for the "
@@ -1184,7 +1214,8 @@ class MarkerProblem(_StageProblem):
         ones everywhere, changes nothing."""
         st = config["stages"]["marker"]
         unsupported = set(st["losses"]) - {"marker", "reg_pose_body", "reg_betas", "joint_accel", "latent_offsets", "foot_lock",
-                                           "floor_penetration", "floor_contact", "self_penetration", "joint_limits"}
+                                           "floor_penetration", "floor_contact", "self_penetration", "joint_limits",
+                                           "pose_accel"}
         if unsupported:
             raise NotImplementedError("marker-stage losses outside the shipped configs: %s" % sorted(unsupported))
         if st.get("use_sdf"):
@@ -1192,6 +1223,9 @@ class MarkerProblem(_StageProblem):
         floor = stage_floor(config, "marker")
         lim = stage_joint_limits(config, "marker")  # EXTENSION: joint-angle limit term on the body pose (0 = off)
         caps = stage_capsules(config, "marker")  # EXTENSION: bone-capsule self-penetration term (0 = off)
+        if stage_pose_accel(config, "marker")["w"] > 0.0:  # EXTENSION: pose-acceleration term on the local body rotations
+            raise NotImplementedError("stages.marker.losses.pose_accel (extension) has no fused closure: optim_markers composes "
+                                      "it from the operators")
         if frame_assign is not None and (floor["w_pen"] > 0.0 or floor["w_con"] > 0.0):
             raise NotImplementedError("the per-frame vertex table (tracklets, extension) is not built for the floor-contact term "
                                       "(stages.marker.losses.floor_penetration / floor_contact)")

@@ -352,6 +352,23 @@ def joint_limit_loss(rot_body: torch.Tensor, lo, hi, w: float) -> torch.Tensor:
     return float(w) * (pen * pen).sum() / rot_body.shape[0]
 
 
+def pose_accel_loss(rot_body: torch.Tensor, w: float, joint_weights=None) -> torch.Tensor:
+    """EXTENSION (the reference's `temporal` loss on the second difference of pose_body, optimization.py:368-375, has a sign error
+    and stops in a debugger): the pose-acceleration term of the chamfer and marker stages' composed closures
+    (stages.<stage>.losses.pose_accel; it has no fused closure).  rot_body [F, 23, 3, 3] are the body joints' local rotations
+    after the stage's normalisation, joint_weights None (ones) or 23 values >= 0 (entry j - 1 is SMPL joint j):
+    w sum_t sum_j u[j] |R_t[j] - 2 R_{t+1}[j] + R_{t+2}[j]|_F^2 / ((F - 2) 207) -- with ones, w times F.mse_loss of the second
+    difference against zero.  F < 3: an exact 0 that still hangs on rot_body."""
+    if rot_body.shape[0] < 3:
+        return rot_body.sum() * 0.0
+    acc = rot_body[:-2] - 2.0 * rot_body[1:-1] + rot_body[2:]
+    sq = (acc * acc).sum(dim=(-1, -2))
+    if joint_weights is not None:
+        u = torch.as_tensor(np.asarray(joint_weights, dtype=np.float64), dtype=rot_body.dtype, device=rot_body.device).reshape(23)
+        sq = sq * u[None, :]
+    return float(w) * sq.sum() / ((rot_body.shape[0] - 2) * 207.0)
+
+
 def weighted_pose_prior(pose_body: torch.Tensor, o_pose_body: torch.Tensor, weights: torch.Tensor) -> torch.Tensor:
     """EXTENSION (the reference's author left it commented out, optimization.py:244): the pose prior of the fused chamfer and
     marker closures with a weight per (frame, body joint) (uuo_fit_set_prior_weights), composed -- their checker.  pose_body,

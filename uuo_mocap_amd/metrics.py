@@ -60,6 +60,28 @@ def compute_accel_error(pred_joints: torch.Tensor, gt_joints: torch.Tensor, freq
     return torch.mean(torch.norm(accel(pred_joints) - accel(gt_joints), dim=-1))
 
 
+#: rows of a [F, 23, 3, 3] table of body rotations that hold the joints without a child: SMPL joints 10, 11 (feet), 15 (head),
+#: 22, 23 (hands) -- row j - 1 is joint j
+LEAF_JOINT_ROWS = (9, 10, 14, 21, 22)
+
+
+def compute_rotation_accel_error(pred_rot: torch.Tensor, gt_rot: torch.Tensor, freq: float, joints_ids=None) -> torch.Tensor:
+    """Rotation-acceleration error (not a metric of the reference): mean over frames 0 .. F-3 and joints of
+    |(P_t - 2 P_{t+1} + P_{t+2}) - (G_t - 2 G_{t+1} + G_{t+2})|_F freq^2, the chordal second difference of the local rotations
+    the pose-acceleration term acts on -- for small angles |R_a - R_b|_F is sqrt(2) times the angle, so the unit is about
+    sqrt(2) rad/s^2 for `freq` in frames per second.  pred_rot, gt_rot [F, J, 3, 3] with F >= 3; `joints_ids` selects ROWS of
+    the second dimension (for body rotations [F, 23, 3, 3] row j - 1 is SMPL joint j), None = all."""
+    if pred_rot.shape != gt_rot.shape or pred_rot.dim() != 4 or tuple(pred_rot.shape[2:]) != (3, 3) or pred_rot.shape[0] < 3:
+        raise ValueError("compute_rotation_accel_error: rotations [F, J, 3, 3] of equal shape with F >= 3 expected (got %s and %s)"
+                         % (tuple(pred_rot.shape), tuple(gt_rot.shape)))
+    if joints_ids is not None:
+        ids = [int(j) for j in joints_ids]
+        pred_rot, gt_rot = pred_rot[:, ids], gt_rot[:, ids]
+    accel = lambda x: x[:-2] - 2.0 * x[1:-1] + x[2:]
+    d = accel(pred_rot) - accel(gt_rot)
+    return torch.mean(torch.sqrt((d * d).sum(dim=(-1, -2)))) * (float(freq) ** 2)
+
+
 def compute_foot_skate(joints: torch.Tensor, contacts: torch.Tensor, freq: float) -> torch.Tensor:
     """Foot skate (not a metric of the reference): mean speed |J_t - J_{t-1}| freq of the feet (joints 10 and 11) over the
     (t, foot) pairs in contact in both frames (c_t c_{t-1} = 1), in m/s for positions in metres and `freq` in frames per

@@ -14,10 +14,10 @@ import torch.nn.functional as F
 from .device_lbfgs import DeviceLBFGS
 from .config import stage_surface
 from .engine import (MARKER_DISTANCE, ChamferProblem, MarkerProblem, check_foot_contacts, check_prior_weights, stage_capsules, stage_floor,
-                     stage_foot_lock, stage_joint_accel, stage_joint_limits, stage_latent_offsets, stage_prior_confidence,
-                     stage_robust_sigma)
+                     stage_foot_lock, stage_joint_accel, stage_joint_limits, stage_latent_offsets, stage_pose_accel,
+                     stage_prior_confidence, stage_robust_sigma)
 from .losses import (MarkerLoss, RobustMarkerLoss, chamfer_distance, floor_loss, foot_lock_loss, joint_accel_loss,  # noqa: F401  (re-exported)
-                     self_penetration_loss, joint_limit_loss, weighted_pose_prior,
+                     self_penetration_loss, joint_limit_loss, pose_accel_loss, weighted_pose_prior,
                      robust_weighted_chamfer_distance, soft_weighted_chamfer_distance, surface_chamfer_distance,
                      weighted_chamfer_distance)
 from .smpl import SmplInference
@@ -96,10 +96,12 @@ def optim_chamfer(
         # the term has a fused closure (k_ring_pick + k_surf_fwd + k_bwd_items_f); execution.surface_fused: False keeps the
         # operator-composed closure, its checker.  (Weight 0 is the key absent.)
         fused_losses = fused_losses | {"surface_chamfer"}
-    if (set(st["losses"]) - fused_losses) or not st["yaw_lock"] or not _robust_fused(config, "chamfer") or \
+    if (set(st["losses"]) - fused_losses - {"pose_accel"}) or not st["yaw_lock"] or not _robust_fused(config, "chamfer") or \
             not _temporal_fused(config, "chamfer") or not _floor_fused(config, "chamfer") or \
             not _capsule_fused(config, "chamfer") or not _limit_fused(config, "chamfer") or \
-            not _prior_conf_fused(config, prior_weights):
+            not _prior_conf_fused(config, prior_weights) or _pose_accel_on(config, "chamfer"):
+        # (EXTENSION: the pose-acceleration term, losses.pose_accel, has no fused closure: it always runs composed)
+        _refuse_sharded_pose_accel(config, "chamfer")
         return _optim_chamfer_general(markers, pose_body, o_pose_body, betas, o_betas, root_orient, trans, marker_labels,
                                       smpl_inference, config, initial_angle, repeat, verbose, iter_fn, foot_contacts,
                                       prior_weights)
@@ -308,6 +310,32 @@ def _composed_limits(config: Dict, stage: str):
     return lambda rot_body: joint_limit_loss(rot_body, lo, hi, lim["w"])
 
 
+def _pose_accel_on(config: Dict, stage: str) -> bool:
+    """True when the stage's EXTENSION pose-acceleration term has a non-zero weight (stages.<stage>.losses.pose_accel; validates
+    the keys)."""
+    return stage_pose_accel(config, stage)["w"] > 0.0
+
+
+def _refuse_sharded_pose_accel(config: Dict, stage: str):
+    if _pose_accel_on(config, stage):
+        from .parallel import frame_shard
+
+        fs = frame_shard()
+        if fs is not None and fs.active:
+            raise NotImplementedError("stages.%s.losses.pose_accel (extension) couples neighbouring frames, across the ranks' "
+                                      "frame blocks too: it is not built for frame-block sharding (parallel.shard_frames)" % stage)
+
+
+def _composed_pose_accel(config: Dict, stage: str):
+    """The pose-acceleration term (EXTENSION; it runs on the closures composed from the operators only): None when off, else a
+    function of the normalised body rotations [F, 23, 3, 3] -- pose_accel_loss with the configured joint weights (ones by
+    default)."""
+    pacc = stage_pose_accel(config, stage)
+    if pacc["w"] == 0.0:
+        return None
+    return lambda rot_body: pose_accel_loss(rot_body, pacc["w"], pacc["joint_weights"])
+
+
 def _prior_conf_on(config: Dict, stage: str) -> bool:
     """True when the stage's config carries the EXTENSION block stages.<stage>.prior_confidence (validates it)."""
     return stage_prior_confidence(config, stage) is not None
@@ -380,6 +408,8 @@ def lockstep_supported(config: Dict, stage: str) -> bool:
         return False
     if _prior_conf_on(config, stage):  # EXTENSION: nor the pose prior's weights
         return False
+    if _pose_accel_on(config, stage):  # EXTENSION: the pose-acceleration term runs composed
+        return False
     if stage == "marker" and stage_latent_offsets(config) > 0.0:  # EXTENSION: nor the latent marker offsets
         return False
     if stage == "chamfer" and stage_surface(config)[0] > 0.0:  # EXTENSION: nor the point-to-surface chamfer term
@@ -387,9 +417,10 @@ def lockstep_supported(config: Dict, stage: str) -> bool:
     if stage == "marker" and tracklets_config(config) is not None:  # EXTENSION: nor the per-frame vertex table
         return False
     if stage == "chamfer":
-        return not (set(st["losses"]) - _CHAMFER_FUSED_LOSSES - {"surface_chamfer"}) and bool(st["yaw_lock"])
+        return not (set(st["losses"]) - _CHAMFER_FUSED_LOSSES - {"surface_chamfer", "pose_accel"}) and bool(st["yaw_lock"])
     return not (set(st["losses"]) - {"marker", "reg_pose_body", "reg_betas", "joint_accel", "latent_offsets", "foot_lock",
-                                     "floor_penetration", "floor_contact", "self_penetration", "joint_limits"}) and \
+                                     "floor_penetration", "floor_contact", "self_penetration", "joint_limits",
+                                     "pose_accel"}) and \
         not st.get("use_sdf")
 
 
@@ -505,7 +536,7 @@ def _optim_chamfer_general(markers, pose_body, o_pose_body, betas, o_betas, root
     refused.  Same in-place semantics as the fused path."""
     st = config["stages"]["chamfer"]
     w = st["losses"]
-    unknown = set(w) - _CHAMFER_FUSED_LOSSES - {"part_chamfer", "trans_vel", "ground", "soft_chamfer", "surface_chamfer"}
+    unknown = set(w) - _CHAMFER_FUSED_LOSSES - {"part_chamfer", "trans_vel", "ground", "soft_chamfer", "surface_chamfer", "pose_accel"}
     if unknown:
         raise NotImplementedError("chamfer-stage losses that cannot run in the reference: %s" % sorted(unknown))
     w_surface, d_surface = stage_surface(config)  # EXTENSION: point-to-surface data term and its stand-off
@@ -519,6 +550,7 @@ def _optim_chamfer_general(markers, pose_body, o_pose_body, betas, o_betas, root
     floor_term = _composed_floor(config, "chamfer", contacts, smpl_inference)  # EXTENSION: floor-contact term on sole vertices
     caps_term = _composed_capsules(config, "chamfer", smpl_inference)  # EXTENSION: bone-capsule self-penetration term
     lim_term = _composed_limits(config, "chamfer")  # EXTENSION: joint-angle limit term on the body pose
+    pacc_term = _composed_pose_accel(config, "chamfer")  # EXTENSION: pose-acceleration term on the local body rotations
     if prior_weights is not None:  # EXTENSION: the pose prior's weights (checked by the caller)
         prior_weights = prior_weights.to(pose_body.device)
     num_frames = pose_body.shape[0]
@@ -580,6 +612,8 @@ def _optim_chamfer_general(markers, pose_body, o_pose_body, betas, o_betas, root
             loss = loss + caps_term(out["joints"])
         if lim_term is not None:  # EXTENSION: the fused closures' joint-angle limit term, composed (their checker)
             loss = loss + lim_term(normalize_rot(p_pose))
+        if pacc_term is not None:  # EXTENSION: the fused closures' pose-acceleration term, composed (their checker)
+            loss = loss + pacc_term(normalize_rot(p_pose))
         loss.backward()
         if verbose:
             print("Chamfer", n_eval[0], float(loss))
@@ -656,9 +690,10 @@ def optim_markers(
     bary = None
     if not _robust_fused(config, "marker") or not _temporal_fused(config, "marker") or not _floor_fused(config, "marker") or \
             not _capsule_fused(config, "marker") or not _limit_fused(config, "marker") or \
-            not _prior_conf_fused(config, prior_weights):
+            not _prior_conf_fused(config, prior_weights) or _pose_accel_on(config, "marker"):
         # EXTENSION: execution.robust_fused / temporal_fused / floor_fused / capsule_fused / limit_fused / prior_conf_fused:
-        # False -- the composed closure, the fused one's checker
+        # False -- the composed closure, the fused one's checker; the pose-acceleration term (pose_accel) always runs on it
+        _refuse_sharded_pose_accel(config, "marker")
         return _optim_markers_general(markers, pose_body, o_pose_body, betas, o_betas, root_orient, trans, one_hot,
                                       smpl_inference, config, verbose, iter_fn, initial_angle, repeat, foot_contacts,
                                       prior_weights)
@@ -721,10 +756,11 @@ def _optim_markers_frame_assign(markers, pose_body, o_pose_body, betas, o_betas,
         raise NotImplementedError("%s is not built for the floor-contact term (stages.marker.losses.floor_penetration / "
                                   "floor_contact)" % what)
     if not _robust_fused(config, "marker") or not _temporal_fused(config, "marker") or not _capsule_fused(config, "marker") or \
-            not _limit_fused(config, "marker") or not _prior_conf_fused(config, prior_weights):
+            not _limit_fused(config, "marker") or not _prior_conf_fused(config, prior_weights) or \
+            _pose_accel_on(config, "marker"):
         raise NotImplementedError("%s is built for the fused marker closure only, not for the closure composed from the operators "
                                   "(execution.robust_fused / temporal_fused / capsule_fused / limit_fused / prior_conf_fused: "
-                                  "False)" % what)
+                                  "False; stages.marker.losses.pose_accel)" % what)
     _refuse_latent_offsets(config, what + ": an offset per column has no meaning once the column changes identity")
     fs = frame_shard()
     if fs is not None and fs.active:
@@ -764,7 +800,8 @@ def _optim_markers_general(markers, pose_body, o_pose_body, betas, o_betas, root
                            "execution.robust_fused / temporal_fused / marker_bary_fused: False)")
     st = config["stages"]["marker"]
     unsupported = set(st["losses"]) - {"marker", "reg_pose_body", "reg_betas", "joint_accel", "latent_offsets", "foot_lock",
-                                       "floor_penetration", "floor_contact", "self_penetration", "joint_limits"}
+                                       "floor_penetration", "floor_contact", "self_penetration", "joint_limits",
+                                       "pose_accel"}
     if unsupported:
         raise NotImplementedError("marker-stage losses outside the shipped configs: %s" % sorted(unsupported))
     if st.get("use_sdf"):
@@ -778,6 +815,7 @@ def _optim_markers_general(markers, pose_body, o_pose_body, betas, o_betas, root
     floor_term = _composed_floor(config, "marker", contacts, smpl_inference)  # EXTENSION: floor-contact term on sole vertices
     caps_term = _composed_capsules(config, "marker", smpl_inference)  # EXTENSION: bone-capsule self-penetration term
     lim_term = _composed_limits(config, "marker")  # EXTENSION: joint-angle limit term on the body pose
+    pacc_term = _composed_pose_accel(config, "marker")  # EXTENSION: pose-acceleration term on the local body rotations
     if prior_weights is not None:  # EXTENSION: the pose prior's weights (checked by the caller)
         prior_weights = prior_weights.to(pose_body.device)
     num_frames = pose_body.shape[0]
@@ -821,6 +859,8 @@ def _optim_markers_general(markers, pose_body, o_pose_body, betas, o_betas, root
             loss = loss + caps_term(out["joints"])
         if lim_term is not None:  # EXTENSION: the fused closures' joint-angle limit term, composed (their checker)
             loss = loss + lim_term(normalize_rot(p_pose))
+        if pacc_term is not None:  # EXTENSION: the fused closures' pose-acceleration term, composed (their checker)
+            loss = loss + pacc_term(normalize_rot(p_pose))
         loss.backward()
         if verbose:
             print("Marker", n_eval[0], float(loss))

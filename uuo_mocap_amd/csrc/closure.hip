@@ -400,7 +400,7 @@ __device__ __forceinline__ float gmof_q(float sig2, float s) { return sig2 / (si
 // PART (with SPARSE): the part stage with its cached pose blend.  The body pose is a constant there, so nothing of the
 // pose-feature path exists - no posedirs gather (2.5 KB per item), no feature gradient, no body-rotation epilogue - and
 // the posed-template vertex is read from the cache k_part_fwd searched: v_posed = C[f][v] + S[v] . beta.
-// NWV = waves per block.  One wave per frame (part stage: <= 16 items, the tail's steps never use more than 60 lanes)
+// NWV = waves per block (BWD_ONE_WAVE: 1, else BWD_NW).  One wave per frame (part stage: <= 16 items, the tail's steps never use more than 60 lanes)
 // leaves the per-block latency about where it is and lets four times as many frames be resident.
 // Fused finalize (round 4): BUILT, MEASURED, NOT THE DEFAULT.  With UUO_FIN_FUSED the block of
 // k_bwd_sparse that finishes last does k_finalize's work (bit-identical sums, tests/test_gpu_parity.py) without any
@@ -466,9 +466,25 @@ __device__ __forceinline__ float gmof_q(float sig2, float s) { return sig2 / (si
 // FASSIGN without ITEMS (EXTENSION, marker stage's one-hot closure only; uuo_fit_set_frame_assign): the column's vertex changes
 // with the frame -- item (f, m) reads assign[f][m], an id < 0 is an item of weight 0 (on vertex 0, like every masked item).
 // Nothing else of the item differs.  Separate instantiations: k_bwd_sparse_f / _r_f / _t_f / _r_t_f.
-template <bool PART = false, int NWV = BWD_NW, bool DENSE = false, bool ITEMS = false, bool ROBUST = false, bool ACCEL = false,
-          bool OFFS = false, bool FASSIGN = false, bool FLOOR = false>
+// FL: the instantiation is one word of these flags; the names used above and below (PART, NWV, DENSE, ...) are its bits, spelt
+// out in the body's first lines.  BWD_KERNELS, after the body, lists every word that exists.
+enum : unsigned {
+  BWD_PART = 1u << 0,
+  BWD_ONE_WAVE = 1u << 1,  // NWV = 1 (with BWD_PART), else BWD_NW
+  BWD_DENSE = 1u << 2,
+  BWD_ITEMS = 1u << 3,
+  BWD_ROBUST = 1u << 4,
+  BWD_ACCEL = 1u << 5,
+  BWD_OFFS = 1u << 6,
+  BWD_FASSIGN = 1u << 7,
+  BWD_FLOOR = 1u << 8,
+};
+template <unsigned FL>
 __device__ __forceinline__ void bwd_body(const BwdArgs& a) {
+  constexpr bool PART = (FL & BWD_PART) != 0, DENSE = (FL & BWD_DENSE) != 0, ITEMS = (FL & BWD_ITEMS) != 0;
+  constexpr bool ROBUST = (FL & BWD_ROBUST) != 0, ACCEL = (FL & BWD_ACCEL) != 0, OFFS = (FL & BWD_OFFS) != 0;
+  constexpr bool FASSIGN = (FL & BWD_FASSIGN) != 0, FLOOR = (FL & BWD_FLOOR) != 0;
+  constexpr int NWV = (FL & BWD_ONE_WAVE) ? 1 : BWD_NW;
   static_assert(!FLOOR || (ACCEL && !(FASSIGN && !ITEMS)), "the floor-contact term rides on the temporal instantiations (slot 3 of "
                 "the partials, the frames' FrameLds), outside the per-frame vertex table of the one-hot marker closure");
   static_assert(!FASSIGN || (!OFFS && !PART && !DENSE && NWV == BWD_NW), "per-frame vertex ids belong to item mode (the surface "
@@ -1193,95 +1209,129 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a) {
 // held to 168 VGPRs = 3 waves per SIMD: k_skin2 keeps 2 x 168 of the 512 registers of every SIMD for the whole of its
 // run, and a backward block of another yaw hypothesis / sequence can only start beside it if it fits in the remaining
 // 176 (at 238 registers it waited for the skinning kernel to drain: +1.7 % fit throughput, same single-stream time).
-__global__ __launch_bounds__(BWD_NW * 64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_bwd_sparse(BwdArgs a) {
-  bwd_body<false>(a);
+#define BWD_WPE3 __attribute__((amdgpu_waves_per_eu(3, 3)))
+#define BWD_NO_ATTR
+#define BWD_NO_OP (-1)
+// Every instantiation of bwd_body, one row each: X(entry point, flag word, threads per block, attribute, UUO_OP_* of its lock-step
+// record or BWD_NO_OP); XB(..., batch twin) where a lock-step batch form exists (blockIdx.z picks the problem).  The entry points,
+// the host's table of them (bwd_kernels) and the batched launch all come from this list; a new term is a flag and its rows.
+#define BWD_KERNELS(X, XB)                                                                                                       \
+  XB(k_bwd_sparse, 0u, BWD_NW * 64, BWD_WPE3, UUO_OP_BWD, k_bwd_sparse_b)                                                         \
+  /* EXTENSION: the same with the Geman-McClure data term (uuo_problem_t.robust_sigma > 0) */                                    \
+  XB(k_bwd_sparse_r, BWD_ROBUST, BWD_NW * 64, BWD_WPE3, UUO_OP_BWD_R, k_bwd_sparse_b_r)                                           \
+  /* EXTENSION: the two with the joint-acceleration smoothness term (uuo_fit_set_joint_accel; no lock-step batch forms) */       \
+  X(k_bwd_sparse_t, BWD_ACCEL, BWD_NW * 64, BWD_WPE3, BWD_NO_OP)                                                                  \
+  X(k_bwd_sparse_r_t, BWD_ROBUST | BWD_ACCEL, BWD_NW * 64, BWD_WPE3, BWD_NO_OP)                                                   \
+  /* EXTENSION: the marker stage's one-hot closure on a per-frame vertex table (uuo_fit_set_frame_assign; no batch forms) */     \
+  X(k_bwd_sparse_f, BWD_FASSIGN, BWD_NW * 64, BWD_WPE3, BWD_NO_OP)                                                                \
+  X(k_bwd_sparse_r_f, BWD_ROBUST | BWD_FASSIGN, BWD_NW * 64, BWD_WPE3, BWD_NO_OP)                                                 \
+  X(k_bwd_sparse_t_f, BWD_ACCEL | BWD_FASSIGN, BWD_NW * 64, BWD_WPE3, BWD_NO_OP)                                                  \
+  X(k_bwd_sparse_r_t_f, BWD_ROBUST | BWD_ACCEL | BWD_FASSIGN, BWD_NW * 64, BWD_WPE3, BWD_NO_OP)                                   \
+  /* the kinematic tail alone, on the sums of a dense backward (dense_bwd.hip) */                                                \
+  X(k_bwd_dense, BWD_DENSE, BWD_NW * 64, BWD_NO_ATTR, BWD_NO_OP)                                                                  \
+  /* the sparse kernel on (vertex, upstream gradient) items (the marker stage on a three-corner placement, k_bary_fwd before it; \
+     EXTENSION: with the joint-acceleration term, k_bary_fwd / k_bary_fwd_r before it, plain or robust) */                        \
+  X(k_bwd_items, BWD_ITEMS, BWD_NW * 64, BWD_NO_ATTR, BWD_NO_OP)                                                                  \
+  X(k_bwd_items_t, BWD_ITEMS | BWD_ACCEL, BWD_NW * 64, BWD_NO_ATTR, BWD_NO_OP)                                                    \
+  /* EXTENSION: the surface chamfer closure's items (uuo_fit_set_surface): vertex ids per frame */                               \
+  X(k_bwd_items_f, BWD_ITEMS | BWD_FASSIGN, BWD_NW * 64, BWD_NO_ATTR, BWD_NO_OP)                                                  \
+  X(k_bwd_items_t_f, BWD_ITEMS | BWD_ACCEL | BWD_FASSIGN, BWD_NW * 64, BWD_NO_ATTR, BWD_NO_OP)                                    \
+  /* EXTENSION: latent per-marker offsets (uuo_problem_t.w_offsets): the one-hot marker closure -- plain, robust, with the       \
+     joint-acceleration term, both -- and the item kernels of the three-corner placement (k_bary_fwd_o / _ro before them) */      \
+  X(k_bwd_sparse_o, BWD_OFFS, BWD_NW * 64, BWD_WPE3, BWD_NO_OP)                                                                   \
+  X(k_bwd_sparse_r_o, BWD_ROBUST | BWD_OFFS, BWD_NW * 64, BWD_WPE3, BWD_NO_OP)                                                    \
+  X(k_bwd_sparse_t_o, BWD_ACCEL | BWD_OFFS, BWD_NW * 64, BWD_WPE3, BWD_NO_OP)                                                     \
+  X(k_bwd_sparse_r_t_o, BWD_ROBUST | BWD_ACCEL | BWD_OFFS, BWD_NW * 64, BWD_WPE3, BWD_NO_OP)                                      \
+  X(k_bwd_items_o, BWD_ITEMS | BWD_OFFS, BWD_NW * 64, BWD_NO_ATTR, BWD_NO_OP)                                                     \
+  X(k_bwd_items_t_o, BWD_ITEMS | BWD_ACCEL | BWD_OFFS, BWD_NW * 64, BWD_NO_ATTR, BWD_NO_OP)                                       \
+  /* EXTENSION: the floor-contact term (uuo_fit_set_floor): the temporal instantiations with the K sole points as further items  \
+     -- one-hot marker / chamfer closure plain and robust, with the latent offsets, and the item kernels (three-corner            \
+     placement, with offsets, surface chamfer) */                                                                                 \
+  X(k_bwd_sparse_t_fl, BWD_ACCEL | BWD_FLOOR, BWD_NW * 64, BWD_WPE3, BWD_NO_OP)                                                   \
+  X(k_bwd_sparse_r_t_fl, BWD_ROBUST | BWD_ACCEL | BWD_FLOOR, BWD_NW * 64, BWD_WPE3, BWD_NO_OP)                                    \
+  X(k_bwd_sparse_t_o_fl, BWD_ACCEL | BWD_OFFS | BWD_FLOOR, BWD_NW * 64, BWD_WPE3, BWD_NO_OP)                                      \
+  X(k_bwd_sparse_r_t_o_fl, BWD_ROBUST | BWD_ACCEL | BWD_OFFS | BWD_FLOOR, BWD_NW * 64, BWD_WPE3, BWD_NO_OP)                       \
+  X(k_bwd_items_t_fl, BWD_ITEMS | BWD_ACCEL | BWD_FLOOR, BWD_NW * 64, BWD_NO_ATTR, BWD_NO_OP)                                     \
+  X(k_bwd_items_t_o_fl, BWD_ITEMS | BWD_ACCEL | BWD_OFFS | BWD_FLOOR, BWD_NW * 64, BWD_NO_ATTR, BWD_NO_OP)                        \
+  X(k_bwd_items_t_f_fl, BWD_ITEMS | BWD_ACCEL | BWD_FASSIGN | BWD_FLOOR, BWD_NW * 64, BWD_NO_ATTR, BWD_NO_OP)                     \
+  /* part stage on its cached pose blend: a fraction of the registers and two thirds of the LDS of the general kernel.  Two      \
+     forms: one wave per frame for <= 16 markers (the candidate search: four items per pass), four waves per frame above that    \
+     (hmr_full.yaml: 50 markers on the full skeleton would be 13 passes of one wave) */                                           \
+  XB(k_bwd_part1, BWD_PART | BWD_ONE_WAVE, 64, BWD_NO_ATTR, UUO_OP_BWD_PART, k_bwd_part1_b)                                       \
+  XB(k_bwd_part, BWD_PART, BWD_NW * 64, BWD_NO_ATTR, UUO_OP_BWD_PART, k_bwd_part_b)                                               \
+  /* EXTENSION: the four part-stage forms with the Geman-McClure data term */                                                    \
+  XB(k_bwd_part1_r, BWD_PART | BWD_ONE_WAVE | BWD_ROBUST, 64, BWD_NO_ATTR, UUO_OP_BWD_PART_R, k_bwd_part1_b_r)                    \
+  XB(k_bwd_part_r, BWD_PART | BWD_ROBUST, BWD_NW * 64, BWD_NO_ATTR, UUO_OP_BWD_PART_R, k_bwd_part_b_r)
+
+#define BWD_ENTRY(name, fl, nt, attr, op) \
+  __global__ __launch_bounds__(nt) attr void name(BwdArgs a) { bwd_body<(fl)>(a); }
+#define BWD_ENTRY_B(name, fl, nt, attr, op, twin)                                          \
+  BWD_ENTRY(name, fl, nt, attr, op)                                                        \
+  __global__ __launch_bounds__(nt) attr void twin(const BwdArgs* __restrict__ batch) {     \
+    UUO_BATCH_PICK(BwdArgs, batch)                                                         \
+    bwd_body<(fl)>(a);                                                                     \
+  }
+BWD_KERNELS(BWD_ENTRY, BWD_ENTRY_B)
+
+// the same list as the host sees it
+struct BwdKernel {
+  unsigned flags;
+  int threads;  // per block
+  int op;       // UUO_OP_* under which a lock-step batch records it, or BWD_NO_OP
+  const char* name;
+  void (*kernel)(BwdArgs);
+  void (*batch)(const BwdArgs*);  // its batch twin, or null
+};
+#define BWD_ROW(name, fl, nt, attr, op) {(fl), (nt), (op), #name, name, nullptr},
+#define BWD_ROW_B(name, fl, nt, attr, op, twin) {(fl), (nt), (op), #name, name, twin},
+static const BwdKernel bwd_kernels[] = {BWD_KERNELS(BWD_ROW, BWD_ROW_B)};
+
+// What decides the instantiation of a backward launch, and the one place that decides it.
+struct BwdFacts {
+  int stage;          // UUO_STAGE_* (UUO_STAGE_UPSTREAM: uuo_smpl_backward)
+  bool part_cached;   // the part stage on its cached pose blend
+  bool one_wave;      // ... with M <= 16
+  bool three_corner;  // the marker stage on a three-corner placement (k_bary_fwd* has formed the items)
+  bool surface;       // uuo_fit_set_surface (k_surf_fwd* has formed the items)
+  bool dense;         // the sums come from the dense backward (dense_bwd.hip): the soft-assignment chamfer closure
+  bool robust, temporal, offs, fassign, floor;
+};
+// the routes in the order in which uuo_closure_eval_impl tries them
+enum BwdRoute { BWD_ROUTE_PART, BWD_ROUTE_THREE_CORNER, BWD_ROUTE_SURFACE, BWD_ROUTE_DENSE, BWD_ROUTE_GENERAL };
+static BwdRoute bwd_route(const BwdFacts& k) {
+  if (k.part_cached) return BWD_ROUTE_PART;
+  if (k.three_corner) return BWD_ROUTE_THREE_CORNER;
+  if (k.surface) return BWD_ROUTE_SURFACE;
+  return k.dense ? BWD_ROUTE_DENSE : BWD_ROUTE_GENERAL;
 }
-__global__ __launch_bounds__(BWD_NW * 64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_bwd_sparse_b(const BwdArgs* __restrict__ batch) {
-  UUO_BATCH_PICK(BwdArgs, batch)
-  bwd_body<false>(a);
+static unsigned bwd_flags(const BwdFacts& k) {
+  const unsigned r = k.robust ? BWD_ROBUST : 0u, t = k.temporal ? BWD_ACCEL : 0u, o = k.offs ? BWD_OFFS : 0u;
+  const unsigned fa = k.fassign ? BWD_FASSIGN : 0u, fl = k.floor ? BWD_FLOOR : 0u;
+  switch (bwd_route(k)) {
+    case BWD_ROUTE_PART: return BWD_PART | (k.one_wave ? BWD_ONE_WAVE : 0u) | r;  // (nothing else reaches the part kernels)
+    case BWD_ROUTE_THREE_CORNER: return BWD_ITEMS | t | o | fl;                   // (robust: k_bary_fwd* carries it)
+    case BWD_ROUTE_SURFACE: return BWD_ITEMS | BWD_FASSIGN | t | fl;              // (robust: k_surf_fwd* carries it)
+    case BWD_ROUTE_DENSE: return BWD_DENSE;
+    default: return r | t | o | fa | fl;
+  }
 }
-// EXTENSION: the same with the Geman-McClure data term (uuo_problem_t.robust_sigma > 0)
-__global__ __launch_bounds__(BWD_NW * 64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_bwd_sparse_r(BwdArgs a) {
-  bwd_body<false, BWD_NW, false, false, true>(a);
-}
-__global__ __launch_bounds__(BWD_NW * 64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_bwd_sparse_b_r(const BwdArgs* __restrict__ batch) {
-  UUO_BATCH_PICK(BwdArgs, batch)
-  bwd_body<false, BWD_NW, false, false, true>(a);
-}
-// EXTENSION: the two with the joint-acceleration smoothness term (uuo_fit_set_joint_accel; no lock-step batch forms)
-__global__ __launch_bounds__(BWD_NW * 64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_bwd_sparse_t(BwdArgs a) {
-  bwd_body<false, BWD_NW, false, false, false, true>(a);
-}
-__global__ __launch_bounds__(BWD_NW * 64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_bwd_sparse_r_t(BwdArgs a) {
-  bwd_body<false, BWD_NW, false, false, true, true>(a);
-}
-// EXTENSION: the marker stage's one-hot closure on a per-frame vertex table (uuo_fit_set_frame_assign; no lock-step batch forms)
-__global__ __launch_bounds__(BWD_NW * 64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_bwd_sparse_f(BwdArgs a) {
-  bwd_body<false, BWD_NW, false, false, false, false, false, true>(a);
-}
-__global__ __launch_bounds__(BWD_NW * 64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_bwd_sparse_r_f(BwdArgs a) {
-  bwd_body<false, BWD_NW, false, false, true, false, false, true>(a);
-}
-__global__ __launch_bounds__(BWD_NW * 64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_bwd_sparse_t_f(BwdArgs a) {
-  bwd_body<false, BWD_NW, false, false, false, true, false, true>(a);
-}
-__global__ __launch_bounds__(BWD_NW * 64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_bwd_sparse_r_t_f(BwdArgs a) {
-  bwd_body<false, BWD_NW, false, false, true, true, false, true>(a);
-}
-// the kinematic tail alone, on the sums of a dense backward (dense_bwd.hip)
-__global__ __launch_bounds__(BWD_NW * 64) void k_bwd_dense(BwdArgs a) { bwd_body<false, BWD_NW, true>(a); }
-// the sparse kernel on (vertex, upstream gradient) items (the marker stage on a three-corner placement, k_bary_fwd before it)
-__global__ __launch_bounds__(BWD_NW * 64) void k_bwd_items(BwdArgs a) { bwd_body<false, BWD_NW, false, true>(a); }
-// EXTENSION: the same with the joint-acceleration term (k_bary_fwd / k_bary_fwd_r before it, plain or robust)
-__global__ __launch_bounds__(BWD_NW * 64) void k_bwd_items_t(BwdArgs a) { bwd_body<false, BWD_NW, false, true, false, true>(a); }
-// EXTENSION: the surface chamfer closure's items (uuo_fit_set_surface): vertex ids per frame
-__global__ __launch_bounds__(BWD_NW * 64) void k_bwd_items_f(BwdArgs a) {
-  bwd_body<false, BWD_NW, false, true, false, false, false, true>(a);
-}
-__global__ __launch_bounds__(BWD_NW * 64) void k_bwd_items_t_f(BwdArgs a) {
-  bwd_body<false, BWD_NW, false, true, false, true, false, true>(a);
-}
-// EXTENSION: latent per-marker offsets (uuo_problem_t.w_offsets): the one-hot marker closure -- plain, robust, with the
-// joint-acceleration term, both -- and the item kernels of the three-corner placement (k_bary_fwd_o / _ro before them)
-__global__ __launch_bounds__(BWD_NW * 64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_bwd_sparse_o(BwdArgs a) {
-  bwd_body<false, BWD_NW, false, false, false, false, true>(a);
-}
-__global__ __launch_bounds__(BWD_NW * 64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_bwd_sparse_r_o(BwdArgs a) {
-  bwd_body<false, BWD_NW, false, false, true, false, true>(a);
-}
-__global__ __launch_bounds__(BWD_NW * 64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_bwd_sparse_t_o(BwdArgs a) {
-  bwd_body<false, BWD_NW, false, false, false, true, true>(a);
-}
-__global__ __launch_bounds__(BWD_NW * 64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_bwd_sparse_r_t_o(BwdArgs a) {
-  bwd_body<false, BWD_NW, false, false, true, true, true>(a);
-}
-__global__ __launch_bounds__(BWD_NW * 64) void k_bwd_items_o(BwdArgs a) { bwd_body<false, BWD_NW, false, true, false, false, true>(a); }
-__global__ __launch_bounds__(BWD_NW * 64) void k_bwd_items_t_o(BwdArgs a) {
-  bwd_body<false, BWD_NW, false, true, false, true, true>(a);
-}
-// EXTENSION: the floor-contact term (uuo_fit_set_floor): the temporal instantiations with the K sole points as further items --
-// one-hot marker / chamfer closure plain and robust, with the latent offsets, and the item kernels (three-corner placement, with
-// offsets, surface chamfer)
-__global__ __launch_bounds__(BWD_NW * 64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_bwd_sparse_t_fl(BwdArgs a) {
-  bwd_body<false, BWD_NW, false, false, false, true, false, false, true>(a);
-}
-__global__ __launch_bounds__(BWD_NW * 64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_bwd_sparse_r_t_fl(BwdArgs a) {
-  bwd_body<false, BWD_NW, false, false, true, true, false, false, true>(a);
-}
-__global__ __launch_bounds__(BWD_NW * 64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_bwd_sparse_t_o_fl(BwdArgs a) {
-  bwd_body<false, BWD_NW, false, false, false, true, true, false, true>(a);
-}
-__global__ __launch_bounds__(BWD_NW * 64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_bwd_sparse_r_t_o_fl(BwdArgs a) {
-  bwd_body<false, BWD_NW, false, false, true, true, true, false, true>(a);
-}
-__global__ __launch_bounds__(BWD_NW * 64) void k_bwd_items_t_fl(BwdArgs a) {
-  bwd_body<false, BWD_NW, false, true, false, true, false, false, true>(a);
-}
-__global__ __launch_bounds__(BWD_NW * 64) void k_bwd_items_t_o_fl(BwdArgs a) {
-  bwd_body<false, BWD_NW, false, true, false, true, true, false, true>(a);
-}
-__global__ __launch_bounds__(BWD_NW * 64) void k_bwd_items_t_f_fl(BwdArgs a) {
-  bwd_body<false, BWD_NW, false, true, false, true, false, true, true>(a);
+// The row of bwd_kernels for these facts, by exact match of the flag word: a combination nobody instantiated is an error, never
+// another kernel.  uuo_closure_eval_impl has refused, with messages of their own, a per-frame vertex table outside the marker
+// stage's plain one-hot closure and a surface term outside the chamfer stage's hard assignment before it gets here; both are
+// refused here as well, so that the mapping does not lean on that.
+static int bwd_select(const BwdFacts& k, const BwdKernel** out) {
+  const bool refused = (k.fassign && (k.stage != UUO_STAGE_MARKER || k.three_corner || k.offs || k.floor)) ||
+                       (bwd_route(k) == BWD_ROUTE_SURFACE && (k.stage != UUO_STAGE_CHAMFER || k.dense));
+  const unsigned fl = bwd_flags(k);
+  *out = nullptr;
+  if (!refused)
+    for (const BwdKernel& row : bwd_kernels)
+      if (row.flags == fl) *out = &row;
+  UUO_REQUIRE(*out, "closure: no backward kernel for stage " + std::to_string(k.stage) + (k.part_cached ? " part_cached" : "") +
+                        (k.one_wave ? " one_wave" : "") + (k.three_corner ? " three_corner" : "") + (k.surface ? " surface" : "") +
+                        (k.dense ? " dense" : "") + (k.robust ? " robust" : "") + (k.temporal ? " temporal" : "") +
+                        (k.offs ? " offs" : "") + (k.fassign ? " fassign" : "") + (k.floor ? " floor" : ""));
+  return 0;
 }
 
 // ----------------------------------------------------------------------------------------------------
@@ -1443,409 +1493,6 @@ __global__ __launch_bounds__(BWD_NW * 64) void k_bary_fwd_r(BaryFwdArgs a) { bar
 __global__ __launch_bounds__(BWD_NW * 64) void k_bary_fwd_o(BaryFwdArgs a) { bary_fwd_body<false, true>(a); }
 __global__ __launch_bounds__(BWD_NW * 64) void k_bary_fwd_ro(BaryFwdArgs a) { bary_fwd_body<true, true>(a); }
 // ----------------------------------------------------------------------------------------------------
-// EXTENSION (not reference behaviour; uuo_fit_set_floor): a floor-contact term on K sole vertices (2 <= K <= 16; the left
-// foot's K_L points first, s(p) the foot of point p), z up, the plane at height h, contact labels c[F][2] in [0, 1]:
-//   pen[t][p] = max(h - z[t][p], 0)                       (always on)
-//   flo[t][s] = max(min_{p of foot s} z[t][p] - h, 0)      (the foot's lowest point; the first in list order on ties)
-//   loss += w_pen sum pen^2 / (F K) + w_con sum c[t][s] flo[t][s]^2 / (2 F)
-//   dL/dz[t][p] = -2 w_pen pen / (F K) + [p = argmin of its foot] w_con c flo / F,   x and y components 0.
-// k_floor_fwd: one wave per frame.  It starts from the frame's FrameLds as k_pose_prep (or the closure's forward) left them,
-// gathers the K vertices four at a time (one per 16-lane group: the arithmetic of the backward kernel's item loop, in its
-// order), evaluates the term on lanes 0 .. K-1 and writes the K upstream gradients and the frame's weighted share of the loss.
-// The backward kernels (ACCEL instantiations of bwd_body) take the points as items M .. M + K - 1.
-// ----------------------------------------------------------------------------------------------------
-#define UUO_FLOOR_MAXK 16
-struct FloorFwdArgs {
-  uuo_gptr<const float> PT, ST, vt, Ww;
-  uuo_gptr<const int> Wi;
-  int V, F, K, KL;               // K points, the first KL of them on the left foot
-  uuo_gptr<const float> frames;  // [F][FrameLds]
-  uuo_gptr<const float> trans;   // [F][3] or null
-  uuo_gptr<const int> vids;      // [K]
-  uuo_gptr<const float> contacts;  // [F][2] or null (ccon == 0)
-  float h, cpen, ccon;           // plane height, w_pen / (F K), w_con / (2 F)
-  uuo_gptr<float> up;            // [F][K][3] out
-  uuo_gptr<float> loss;          // [F] out
-};
-__global__ __launch_bounds__(64) void k_floor_fwd(FloorFwdArgs a) {
-  __shared__ FrameLds L;
-  __shared__ float sA[UUO_NUM_JOINTS * 12];
-  __shared__ float spf[UUO_KB];
-  __shared__ float sz[UUO_FLOOR_MAXK];
-  const int f = blockIdx.x, lane = threadIdx.x;
-  const int K = a.K;
-  {
-    constexpr int NW = sizeof(FrameLds) / 4;
-    float* dst_l = reinterpret_cast<float*>(&L);
-    for (int i = lane; i < NW; i += 64) dst_l[i] = a.frames[(size_t)f * NW + i];
-  }
-  __syncthreads();
-  if (lane < UUO_NUM_JOINTS) frame_skin_matrix(L, lane, sA + lane * 12);
-  for (int i = lane; i < UUO_KB; i += 64) {
-    float v = 0.f;
-    if (i < UUO_NUM_POSE_FEATS) {
-      const int j = 1 + i / 9, e = i % 9;
-      v = L.R[j][e] - ((e == 0 || e == 4 || e == 8) ? 1.f : 0.f);
-    }
-    spf[i] = v;
-  }
-  __syncthreads();
-  const float trz = a.trans ? a.trans[(size_t)f * 3 + 2] : 0.f;
-  const int gq = lane >> 4, sl = lane & 15;
-  float fk[13];
-#pragma unroll
-  for (int t = 0; t < 13; ++t) fk[t] = spf[sl + 16 * t];
-  const float beta_s = (sl < 10) ? L.beta[sl] : 0.f;
-  auto row_sum = [](float v) {
-    v += dpp_rot<0x128>(v);
-    v += dpp_rot<0x124>(v);
-    v += dpp_rot<0x122>(v);
-    v += dpp_rot<0x121>(v);
-    return v;
-  };
-  for (int r = 0; r < (K + 3) / 4; ++r) {
-    const int p = gq + 4 * r;
-    int vi = (p < K) ? a.vids[p] : 0;
-    if ((unsigned)vi >= (unsigned)a.V) vi = 0;  // (uuo_fit_set_floor has checked the ids; keeps the gather in bounds)
-    const float* pt = a.PT + (size_t)vi * 3 * UUO_KB + sl;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int t = 0; t < 13; ++t) {
-      s0 = fmaf(pt[16 * t], fk[t], s0);
-      s1 = fmaf(pt[UUO_KB + 16 * t], fk[t], s1);
-      s2 = fmaf(pt[2 * UUO_KB + 16 * t], fk[t], s2);
-    }
-    const float* ps = a.ST + (size_t)vi * 30 + (sl < 10 ? sl : 0);
-    const float st0 = (sl < 10) ? ps[0] : 0.f, st1 = (sl < 10) ? ps[10] : 0.f, st2 = (sl < 10) ? ps[20] : 0.f;
-    float vp[3];
-    vp[0] = row_sum(s0) + (a.vt[(size_t)vi * 3] + row_sum(st0 * beta_s));
-    vp[1] = row_sum(s1) + (a.vt[(size_t)vi * 3 + 1] + row_sum(st1 * beta_s));
-    vp[2] = row_sum(s2) + (a.vt[(size_t)vi * 3 + 2] + row_sum(st2 * beta_s));
-    const int4 wi = *reinterpret_cast<const int4*>(a.Wi + (size_t)vi * 4);
-    const float4 w4 = *reinterpret_cast<const float4*>(a.Ww + (size_t)vi * 4);
-    const int wj[4] = {wi.x, wi.y, wi.z, wi.w};
-    const float ww[4] = {w4.x, w4.y, w4.z, w4.w};
-    float T8 = 0.f, T9 = 0.f, T10 = 0.f, T11 = 0.f;  // the z row of the blended transform
-#pragma unroll
-    for (int n = 0; n < 4; ++n) {
-      const float4 r2 = reinterpret_cast<const float4*>(sA + wj[n] * 12)[2];
-      T8 = fmaf(ww[n], r2.x, T8); T9 = fmaf(ww[n], r2.y, T9); T10 = fmaf(ww[n], r2.z, T10); T11 = fmaf(ww[n], r2.w, T11);
-    }
-    const float vz = fmaf(T10, vp[2], fmaf(T9, vp[1], T8 * vp[0])) + T11 + trz;
-    if (p < K && sl == 0) sz[p] = vz;
-  }
-  __syncthreads();
-  const float c0 = (a.ccon != 0.f) ? a.contacts[(size_t)f * 2] : 0.f, c1 = (a.ccon != 0.f) ? a.contacts[(size_t)f * 2 + 1] : 0.f;
-  if (lane < K) {
-    const int p = lane, foot = (p < a.KL) ? 0 : 1;
-    const int lo = foot ? a.KL : 0, hi = foot ? K : a.KL;
-    int am = lo;
-    float zm = sz[lo];
-    for (int q = lo + 1; q < hi; ++q) {
-      const float zq = sz[q];
-      if (zq < zm) {
-        zm = zq;
-        am = q;
-      }
-    }
-    const float pen = fmaxf(a.h - sz[p], 0.f), flo = fmaxf(zm - a.h, 0.f), c = foot ? c1 : c0;
-    float dz = -2.f * a.cpen * pen;
-    if (p == am) dz += 2.f * a.ccon * c * flo;
-    float* pu = a.up + ((size_t)f * K + p) * 3;
-    pu[0] = 0.f;
-    pu[1] = 0.f;
-    pu[2] = dz;
-  }
-  if (lane == 0) {  // the frame's share, in a fixed order
-    float sp = 0.f, zl = sz[0], zr = sz[a.KL];
-    for (int p = 0; p < K; ++p) {
-      const float pen = fmaxf(a.h - sz[p], 0.f);
-      sp += pen * pen;
-      if (p < a.KL) zl = fminf(zl, sz[p]);
-      else zr = fminf(zr, sz[p]);
-    }
-    const float fl0 = fmaxf(zl - a.h, 0.f), fl1 = fmaxf(zr - a.h, 0.f);
-    a.loss[f] = a.cpen * sp + a.ccon * (c0 * (fl0 * fl0) + c1 * (fl1 * fl1));
-  }
-}
-
-// ----------------------------------------------------------------------------------------------------
-// EXTENSION (not reference behaviour; uuo_fit_set_capsules): a bone-capsule self-penetration term.  Capsule c = (u, v, alpha,
-// beta, r): end points a = J_u + alpha (J_v - J_u), b = J_u + beta (J_v - J_u) on the line through two world joints J = G_j^t
-// (no translation: the term is translation invariant), radius r.  For every pair k = (i, j) of the list:
-//   (s, t) = closest-point parameters of the segments [a_i, b_i], [a_j, b_j] (Ericson, Real-Time Collision Detection 5.1.9;
-//            capsule_closest below, degenerate when |d|^2 <= 1e-12, parallel when den <= 1e-6 A E)
-//   delta = c_i - c_j,  d = |delta|,  pen = max(r_i + r_j - d, 0),  loss += w pen^2 / F,
-//   dL/dc_i = -(2 w / F) pen delta / d = -dL/dc_j   (s, t held fixed: envelope theorem; d = 0: no gradient, pen^2 still counts)
-//   gamma_i = alpha_i + s (beta_i - alpha_i):  dL/dJ_{u_i} += (1 - gamma_i) dL/dc_i,  dL/dJ_{v_i} += gamma_i dL/dc_i  (same for j).
-// k_capsule_fwd: one wave per frame.  It reads the 24 G^t of the frame's FrameLds (as the closure's forward or k_pose_prep left
-// them), forms the <= 32 capsules' end points in LDS, evaluates the <= 256 pairs (pair k on lane k % 64, up to four per lane) and
-// parks the four end joints' shares of each pair's gradient -- (1 - gamma_i) dL/dc_i, gamma_i dL/dc_i, -(1 - gamma_j) dL/dc_i,
-// -gamma_j dL/dc_i -- in LDS.  The 72 (joint, component) outputs -- lanes 0..63, then lanes 0..7 once more -- are summed over the
-// joint's rows of the host-built CSR table, which lists (pair, end) in pair order and, inside a pair, in the order u_i, v_i, u_j,
-// v_j.  The frame's sum of pen^2: every lane adds its own pairs in order, then a fixed xor butterfly (32, 16, .. 1) adds the
-// lanes.  The table and the geometry are fetched into LDS once, beside G^t: one global round trip.  No atomics: bit-reproducible.
-// ----------------------------------------------------------------------------------------------------
-#define UUO_CAPS_MAXC 32
-#define UUO_CAPS_MAXP 256
-#define UUO_CAPS_TAB_PAIRS (UUO_CAPS_MAXC * 2)                       // cap_tab layout (ints): joints, pairs, CSR offsets, CSR entries
-#define UUO_CAPS_TAB_OFF (UUO_CAPS_TAB_PAIRS + UUO_CAPS_MAXP * 2)
-#define UUO_CAPS_TAB_ENT (UUO_CAPS_TAB_OFF + UUO_NUM_JOINTS + 1)
-#define UUO_CAPS_TAB_INTS (UUO_CAPS_TAB_ENT + UUO_CAPS_MAXP * 4)
-struct CapsFwdArgs {
-  uuo_gptr<const float> frames;  // [F][FrameLds]
-  uuo_gptr<const int> tab;       // the workspace's table (layout above)
-  uuo_gptr<const float> geom;    // [C][3] alpha, beta, radius
-  int C, P;
-  float cl, cg;                  // w / F, 2 w / F
-  uuo_gptr<float> up;            // [F][24][3] out
-  uuo_gptr<float> loss;          // [F] out
-};
-__device__ __forceinline__ float clamp01(float v) { return fminf(fmaxf(v, 0.f), 1.f); }
-// closest-point parameters of the segments p1 + s d1, p2 + t d2 (s, t in [0, 1]); r = p1 - p2
-struct CapsVec { float x, y, z; };
-__device__ __forceinline__ float caps_dot(CapsVec a, CapsVec b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ float2 capsule_closest(CapsVec d1, CapsVec d2, CapsVec r) {
-  const float A = caps_dot(d1, d1), E = caps_dot(d2, d2);
-  const float fq = caps_dot(d2, r), cq = caps_dot(d1, r), bq = caps_dot(d1, d2);
-  const bool dA = A <= 1e-12f, dE = E <= 1e-12f;
-  if (dA && dE) return make_float2(0.f, 0.f);
-  if (dA) return make_float2(0.f, clamp01(fq / E));
-  if (dE) return make_float2(clamp01(-cq / A), 0.f);
-  const float den = A * E - bq * bq;
-  float s = (den > 1e-6f * (A * E)) ? clamp01((bq * fq - cq * E) / den) : 0.f;
-  float t = (bq * s + fq) / E;
-  if (t < 0.f) {
-    t = 0.f;
-    s = clamp01(-cq / A);
-  } else if (t > 1.f) {
-    t = 1.f;
-    s = clamp01((bq - cq) / A);
-  }
-  return make_float2(s, t);
-}
-__global__ __launch_bounds__(64) void k_capsule_fwd(CapsFwdArgs a) {
-  __shared__ float sG[UUO_NUM_JOINTS * 3];
-  __shared__ int sTab[UUO_CAPS_TAB_INTS];           // the workspace's table: one coalesced fetch, every lookup below is LDS
-  __shared__ float sGeom[UUO_CAPS_MAXC * 3];
-  __shared__ float sEnd[UUO_CAPS_MAXC][6];          // a, b of every capsule
-  __shared__ float sCon[UUO_CAPS_MAXP * 4][3];      // per (pair, end): that end joint's share of dL/dc, signed
-  const int f = blockIdx.x, lane = threadIdx.x;
-  const int C = min(a.C, UUO_CAPS_MAXC), P = min(a.P, UUO_CAPS_MAXP);  // (uuo_fit_set_capsules has checked them; keeps LDS in bounds)
-  {
-    constexpr int NW = sizeof(FrameLds) / 4, GT = offsetof(FrameLds, Gt) / 4;
-    for (int i = lane; i < UUO_NUM_JOINTS * 3; i += 64) sG[i] = a.frames[(size_t)f * NW + GT + i];
-    for (int i = lane; i < UUO_CAPS_TAB_INTS; i += 64) sTab[i] = a.tab[i];
-    for (int i = lane; i < UUO_CAPS_MAXC * 3; i += 64) sGeom[i] = a.geom[i];
-  }
-  __syncthreads();
-  if (lane < C) {
-    const int u = sTab[lane * 2] % UUO_NUM_JOINTS, v = sTab[lane * 2 + 1] % UUO_NUM_JOINTS;
-    const float al = sGeom[lane * 3], be = sGeom[lane * 3 + 1];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const float ju = sG[u * 3 + c], e = sG[v * 3 + c] - ju;
-      sEnd[lane][c] = ju + al * e;
-      sEnd[lane][3 + c] = ju + be * e;
-    }
-  }
-  __syncthreads();
-  float part = 0.f;  // this lane's pen^2, pairs lane, lane + 64, ... in that order
-  for (int k = lane; k < P; k += 64) {
-    const int i = sTab[UUO_CAPS_TAB_PAIRS + k * 2] % UUO_CAPS_MAXC, j = sTab[UUO_CAPS_TAB_PAIRS + k * 2 + 1] % UUO_CAPS_MAXC;
-    const CapsVec p1 = {sEnd[i][0], sEnd[i][1], sEnd[i][2]}, p2 = {sEnd[j][0], sEnd[j][1], sEnd[j][2]};
-    const CapsVec d1 = {sEnd[i][3] - p1.x, sEnd[i][4] - p1.y, sEnd[i][5] - p1.z};
-    const CapsVec d2 = {sEnd[j][3] - p2.x, sEnd[j][4] - p2.y, sEnd[j][5] - p2.z};
-    const CapsVec r = {p1.x - p2.x, p1.y - p2.y, p1.z - p2.z};
-    const float2 st = capsule_closest(d1, d2, r);
-    const float s = st.x, t = st.y;
-    const CapsVec dl = {(p1.x + s * d1.x) - (p2.x + t * d2.x), (p1.y + s * d1.y) - (p2.y + t * d2.y), (p1.z + s * d1.z) - (p2.z + t * d2.z)};
-    const float d = sqrtf(caps_dot(dl, dl));
-    const float pen = fmaxf((sGeom[i * 3 + 2] + sGeom[j * 3 + 2]) - d, 0.f);
-    const float q = (d > 0.f) ? -(a.cg * pen) / d : 0.f;
-    const float g[3] = {q * dl.x, q * dl.y, q * dl.z};  // dL/dc_i = -dL/dc_j
-    const float ai = sGeom[i * 3], aj = sGeom[j * 3];
-    const float gi = ai + s * (sGeom[i * 3 + 1] - ai), gj = aj + t * (sGeom[j * 3 + 1] - aj);
-    const float co[4] = {1.f - gi, gi, 1.f - gj, gj};   // ends u_i, v_i, u_j, v_j
-#pragma unroll
-    for (int end = 0; end < 4; ++end)
-#pragma unroll
-      for (int c = 0; c < 3; ++c) sCon[k * 4 + end][c] = co[end] * ((end & 2) ? -g[c] : g[c]);
-    part += pen * pen;
-  }
-  __syncthreads();
-  for (int o = lane; o < UUO_NUM_JOINTS * 3; o += 64) {
-    const int jj = o / 3, c = o - jj * 3;
-    const int e0 = max(sTab[UUO_CAPS_TAB_OFF + jj], 0), e1 = min(sTab[UUO_CAPS_TAB_OFF + jj + 1], 4 * P);
-    float acc = 0.f;
-    for (int e = e0; e < e1; e += 4) {  // four rows a step: the LDS reads overlap, the adds keep the rows' (= the pairs') order
-      float v[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int ent = (e + u < e1) ? sTab[UUO_CAPS_TAB_ENT + e + u] : -1;
-        v[u] = (ent >= 0) ? sCon[ent % (UUO_CAPS_MAXP * 4)][c] : 0.f;
-      }
-      acc = (((acc + v[0]) + v[1]) + v[2]) + v[3];
-    }
-    a.up[(size_t)f * 72 + o] = acc;
-  }
-  // the frame's share: the lanes' partial sums (each in pair order) through a fixed butterfly, lane l with lane l ^ 32, 16, .. 1
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) part += __shfl_xor(part, m, 64);
-  if (lane == 0) a.loss[f] = a.cl * part;
-}
-
-// ----------------------------------------------------------------------------------------------------
-// EXTENSION (not reference behaviour; uuo_fit_set_joint_limits): a joint-angle limit term on the body pose.  Body joint
-// j = 1 .. 23, R its local rotation as frame_forward forms it (gs6d_forward of the raw entries when the stage normalises, the raw
-// entries otherwise: the same function on the same inputs, so R is bit for bit the forward's), row-major:
-//   s = 1/2 (R21 - R12, R02 - R20, R10 - R01),  c = 1/2 (R00 + R11 + R22 - 1),  n = |s|,  theta = atan2(n, c),  kappa = theta / n,
-//   omega = kappa s;   n < 1e-4: c >= 0 takes kappa = 1, d kappa = 0 (identity), c < 0 contributes nothing (half turn: no axis)
-//   pen_k = max(omega_k - hi_k, 0) + max(lo_k - omega_k, 0),  loss += w pen_k^2 / F,
-//   g_k = dL/d omega_k = (2 w / F) (max(omega_k - hi_k, 0) - max(lo_k - omega_k, 0)),  q = s . g,
-//   dL/ds = kappa g + q (d kappa / dn) s / n,  dL/dc = q d kappa / dc,
-//   d kappa / dn = c / (n (n^2 + c^2)) - theta / n^2,  d kappa / dc = -1 / (n^2 + c^2),
-//   dL/dR21 += 1/2 dL/ds_x, dL/dR12 -= 1/2 dL/ds_x, ... (cyclic),  dL/dR_kk += 1/2 dL/dc.
-// k_limit_fwd: 32 lanes per frame, two frames per 64-thread block (a frame has 23 joints: a wave per frame would leave 41 lanes
-// idle; F odd leaves the last block's upper half idle).  Lane l < 23 of a half takes joint l + 1: raw entries and the six bounds
-// in one round trip, R, omega, the hinges, dL/dR, and the stage's normalisation backward (gs6d_backward) on its own raw entries:
-// it writes the gradient in PARAMETER space, [F][23][9], third rows exact zeros when the stage normalises.  The frame's 69
-// squares: every lane adds its three in the order x, y, z, then a fixed xor butterfly (16, 8, .. 1) inside the half adds the
-// lanes (lanes 23 .. 31 hold zeros).  No atomics, no LDS: bit-reproducible.
-// ----------------------------------------------------------------------------------------------------
-#define UUO_LIM_FPB 2  // frames per block
-struct LimitFwdArgs {
-  uuo_gptr<const float> body;  // [F][23][9] raw body pose entries (UuoPoseSrc.body)
-  uuo_gptr<const float> tab;   // [2][23][3] lo, hi
-  int F, norm_body;
-  float cl, cg;                // w / F, 2 w / F
-  uuo_gptr<float> g;           // [F][23][9] out
-  uuo_gptr<float> loss;        // [F] out
-};
-__global__ __launch_bounds__(64) void k_limit_fwd(LimitFwdArgs a) {
-  const int half = threadIdx.x >> 5, l = threadIdx.x & 31;
-  const int f = blockIdx.x * UUO_LIM_FPB + half;
-  const bool on = f < a.F && l < 23;
-  float raw[9], lo[3], hi[3];
-#pragma unroll
-  for (int e = 0; e < 9; ++e) raw[e] = on ? a.body[((size_t)f * 23 + l) * 9 + e] : ((e == 0 || e == 4 || e == 8) ? 1.f : 0.f);
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    lo[k] = on ? a.tab[l * 3 + k] : -INFINITY;
-    hi[k] = on ? a.tab[69 + l * 3 + k] : INFINITY;
-  }
-  float R[9];
-  if (a.norm_body) {
-    gs6d_forward(raw, R);
-  } else {
-#pragma unroll
-    for (int e = 0; e < 9; ++e) R[e] = raw[e];
-  }
-  const float s[3] = {0.5f * (R[7] - R[5]), 0.5f * (R[2] - R[6]), 0.5f * (R[3] - R[1])};
-  const float c = 0.5f * (((R[0] + R[4]) + R[8]) - 1.f);
-  const float n2 = (s[0] * s[0] + s[1] * s[1]) + s[2] * s[2];
-  const float n = sqrtf(n2);
-  const bool small = n < 1e-4f;
-  const bool skip = small && c < 0.f;
-  const float nn = small ? 1.f : n;  // (keeps the quotients of the unused branch finite)
-  const float theta = atan2f(n, c);
-  const float kappa = small ? 1.f : theta / nn;
-  const float den = small ? 1.f : n2 + c * c;
-  const float dkn = small ? 0.f : (c / (nn * den) - theta / (nn * nn));
-  const float dkc = small ? 0.f : (-1.f / den);
-  float g[3], part = 0.f;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const float om = kappa * s[k];
-    const float up = fmaxf(om - hi[k], 0.f), dn = fmaxf(lo[k] - om, 0.f);
-    const float pen = (skip || !on) ? 0.f : up + dn;
-    g[k] = (skip || !on) ? 0.f : a.cg * (up - dn);
-    part += pen * pen;
-  }
-  const float q = (s[0] * g[0] + s[1] * g[1]) + s[2] * g[2];
-  const float qn = q * dkn / nn;
-  const float ds[3] = {0.5f * (kappa * g[0] + qn * s[0]), 0.5f * (kappa * g[1] + qn * s[1]), 0.5f * (kappa * g[2] + qn * s[2])};
-  const float dc = 0.5f * (q * dkc);
-  const float dR[9] = {dc, -ds[2], ds[1], ds[2], dc, -ds[0], -ds[1], ds[0], dc};
-  float out[9];
-  if (a.norm_body) {
-    float da[6];
-    gs6d_backward(raw, dR, da);
-#pragma unroll
-    for (int e = 0; e < 6; ++e) out[e] = da[e];
-    out[6] = out[7] = out[8] = 0.f;
-  } else {
-#pragma unroll
-    for (int e = 0; e < 9; ++e) out[e] = dR[e];
-  }
-  if (on) {
-#pragma unroll
-    for (int e = 0; e < 9; ++e) a.g[((size_t)f * 23 + l) * 9 + e] = out[e];
-  }
-  // the frame's share: the lanes' sums (each x, y, z in order) through a fixed butterfly inside the 32-lane half
-#pragma unroll
-  for (int m = 16; m >= 1; m >>= 1) part += __shfl_xor(part, m, 64);
-  if (l == 0 && f < a.F) a.loss[f] = a.cl * part;
-}
-
-// ----------------------------------------------------------------------------------------------------
-// EXTENSION (not reference behaviour; uuo_fit_set_prior_weights): the pose prior of the chamfer and marker stages with a weight
-// per (frame, body joint), w[t][j] >= 0:
-//   loss += c sum_t sum_j w[t][j] sum_e (raw[t][j][e] - o[t][j][e])^2,   c = w_pose / (F 207)   (the normaliser of the uniform
-//   prior, not sum w: w == 1 everywhere is the uniform term),   dL/d raw[t][j][e] = 2 c w[t][j] (raw - o).
-// k_prior_conf delivers the WHOLE prior -- the backward kernels and the finalize then run with a pose coefficient of 0 -- through
-// the buffer of the joint-angle limit term, [F][23][9] gradients in parameter space and [F] shares behind them, which the
-// temporal instantiations add to gout and to slot 3 (lim_g != null): no existing kernel changes.  add == 0: it writes the buffer;
-// add != 0 (the limit term is on, k_limit_fwd of this evaluation ran before it on the same stream): it adds to it.
-// The shape of k_limit_fwd: 32 lanes per frame, two frames per 64-thread block.  Lane l < 23 of a half takes joint l + 1: its
-// nine raw entries, nine targets, its weight (and with add its nine old gradients; lane 0 the old share) in one round trip -- the
-// 23 lanes of a half read 207 consecutive floats of each table.  A weight of 0 stores exact +0 (not 0 * diff), a row on its
-// target 2 c w * 0 = 0: third rows on their targets stay exact zeros, as the compact packing needs.  The frame's share: every lane
-// sums its nine squares in the order e = 0 .. 8 and weighs the sum, then a fixed xor butterfly (16, 8, .. 1) inside the half adds
-// the lanes (lanes 23 .. 31 hold zeros).  No atomics, no LDS: bit-reproducible.
-// ----------------------------------------------------------------------------------------------------
-struct PriorConfArgs {
-  uuo_gptr<const float> body;    // [F][23][9] raw body pose entries (the optimised parameters)
-  uuo_gptr<const float> target;  // [F][23][9] the prior's target (uuo_problem_t.d_o_pose)
-  uuo_gptr<const float> w;       // [F][23] weights
-  int F, add;
-  float cl, cg;                  // w_pose / (F 207), 2 w_pose / (F 207)
-  uuo_gptr<float> g;             // [F][23][9] gradients, then [F] shares: written (add == 0) or added to
-};
-__global__ __launch_bounds__(64) void k_prior_conf(PriorConfArgs a) {
-  const int half = threadIdx.x >> 5, l = threadIdx.x & 31;
-  const int f = blockIdx.x * UUO_LIM_FPB + half;
-  const bool on = f < a.F && l < 23;
-  const size_t row = on ? ((size_t)f * 23 + l) * 9 : 0;
-  float raw[9], tg[9], old[9];
-#pragma unroll
-  for (int e = 0; e < 9; ++e) {
-    raw[e] = on ? a.body[row + e] : 0.f;
-    tg[e] = on ? a.target[row + e] : 0.f;
-    old[e] = (on && a.add) ? a.g[row + e] : 0.f;
-  }
-  const float w = on ? a.w[(size_t)f * 23 + l] : 0.f;
-  const bool head = l == 0 && f < a.F;
-  const float old_share = (head && a.add) ? a.g[(size_t)a.F * 207 + f] : 0.f;
-  const float wc = a.cg * w;
-  float sq = 0.f, out[9];
-#pragma unroll
-  for (int e = 0; e < 9; ++e) {
-    const float diff = raw[e] - tg[e];
-    out[e] = old[e] + ((w == 0.f) ? 0.f : wc * diff);
-    sq = fmaf(diff, diff, sq);
-  }
-  if (on) {
-#pragma unroll
-    for (int e = 0; e < 9; ++e) a.g[row + e] = out[e];
-  }
-  float part = (w == 0.f) ? 0.f : w * sq;
-#pragma unroll
-  for (int m = 16; m >= 1; m >>= 1) part += __shfl_xor(part, m, 64);
-  if (head) a.g[(size_t)a.F * 207 + f] = old_share + a.cl * part;
-}
-
-// ----------------------------------------------------------------------------------------------------
 // EXTENSION (not reference behaviour; uuo_fit_set_surface): the chamfer stage's data term as a point-to-surface distance
 // with a stand-off.  k_ring_pick (nn_kernels.hip) has chosen, for every (frame, marker), the face of the nearest vertex's
 // one-ring that lies closest in the search's vertex buffer; this pass is k_bary_fwd with those corners read per frame and the
@@ -2003,31 +1650,6 @@ __device__ __forceinline__ void surf_fwd_body(const SurfFwdArgs& a) {
 }
 __global__ __launch_bounds__(BWD_NW * 64) void k_surf_fwd(SurfFwdArgs a) { surf_fwd_body<false>(a); }
 __global__ __launch_bounds__(BWD_NW * 64) void k_surf_fwd_r(SurfFwdArgs a) { surf_fwd_body<true>(a); }
-// part stage on its cached pose blend: a fraction of the registers and two thirds of the LDS of the general kernel
-// two forms: one wave per frame for <= 16 markers (the candidate search: four items per pass), four waves per frame above
-// that (hmr_full.yaml: 50 markers on the full skeleton would be 13 passes of one wave)
-__global__ __launch_bounds__(64) void k_bwd_part1(BwdArgs a) { bwd_body<true, 1>(a); }
-__global__ __launch_bounds__(64) void k_bwd_part1_b(const BwdArgs* __restrict__ batch) {
-  UUO_BATCH_PICK(BwdArgs, batch)
-  bwd_body<true, 1>(a);
-}
-__global__ __launch_bounds__(BWD_NW * 64) void k_bwd_part(BwdArgs a) { bwd_body<true>(a); }
-__global__ __launch_bounds__(BWD_NW * 64) void k_bwd_part_b(const BwdArgs* __restrict__ batch) {
-  UUO_BATCH_PICK(BwdArgs, batch)
-  bwd_body<true>(a);
-}
-// EXTENSION: the four part-stage forms with the Geman-McClure data term
-__global__ __launch_bounds__(64) void k_bwd_part1_r(BwdArgs a) { bwd_body<true, 1, false, false, true>(a); }
-__global__ __launch_bounds__(64) void k_bwd_part1_b_r(const BwdArgs* __restrict__ batch) {
-  UUO_BATCH_PICK(BwdArgs, batch)
-  bwd_body<true, 1, false, false, true>(a);
-}
-__global__ __launch_bounds__(BWD_NW * 64) void k_bwd_part_r(BwdArgs a) { bwd_body<true, BWD_NW, false, false, true>(a); }
-__global__ __launch_bounds__(BWD_NW * 64) void k_bwd_part_b_r(const BwdArgs* __restrict__ batch) {
-  UUO_BATCH_PICK(BwdArgs, batch)
-  bwd_body<true, BWD_NW, false, false, true>(a);
-}
-
 __global__ __launch_bounds__(1024) void k_finalize(FinArgs a) { finalize_body<1024, false>(a); }
 // EXTENSION: with the joint-acceleration term's per-frame shares (after the *_t backward kernels)
 __global__ __launch_bounds__(1024) void k_finalize_t(FinArgs a) { finalize_body<1024, false, true>(a); }
@@ -2041,20 +1663,11 @@ __global__ __launch_bounds__(1024) void k_finalize_b(const FinArgs* __restrict__
 
 // batched launches of this file's kernels (uuo_common.h): 0 = launched, 1 = not one of mine, < 0 = error
 int uuo_batched_launch_closure(int op, hipStream_t s, const void* d_args, int count, int gx, int gy) {
-  if (op == UUO_OP_BWD) {
-    hipLaunchKernelGGL(k_bwd_sparse_b, dim3(gx, gy, count), dim3(BWD_NW * 64), 0, s, (const BwdArgs*)d_args);
-  } else if (op == UUO_OP_BWD_PART) {  // gy of the record = waves per frame (1 or BWD_NW; one value per batch: same M)
-    if (gy == 1)
-      hipLaunchKernelGGL(k_bwd_part1_b, dim3(gx, 1, count), dim3(64), 0, s, (const BwdArgs*)d_args);
-    else
-      hipLaunchKernelGGL(k_bwd_part_b, dim3(gx, 1, count), dim3(BWD_NW * 64), 0, s, (const BwdArgs*)d_args);
-  } else if (op == UUO_OP_BWD_R) {
-    hipLaunchKernelGGL(k_bwd_sparse_b_r, dim3(gx, gy, count), dim3(BWD_NW * 64), 0, s, (const BwdArgs*)d_args);
-  } else if (op == UUO_OP_BWD_PART_R) {
-    if (gy == 1)
-      hipLaunchKernelGGL(k_bwd_part1_b_r, dim3(gx, 1, count), dim3(64), 0, s, (const BwdArgs*)d_args);
-    else
-      hipLaunchKernelGGL(k_bwd_part_b_r, dim3(gx, 1, count), dim3(BWD_NW * 64), 0, s, (const BwdArgs*)d_args);
+  const BwdKernel* bk = nullptr;  // gy of a part-stage record = waves per frame (1 or BWD_NW; one value per batch: same M)
+  for (const BwdKernel& row : bwd_kernels)
+    if (row.batch && row.op == op && (!(row.flags & BWD_PART) || ((row.flags & BWD_ONE_WAVE) != 0) == (gy == 1))) bk = &row;
+  if (bk) {
+    hipLaunchKernelGGL((bk->batch), dim3(gx, (bk->flags & BWD_PART) ? 1 : gy, count), dim3(bk->threads), 0, s, (const BwdArgs*)d_args);
   } else if (op == UUO_OP_FIN) {
     hipLaunchKernelGGL(k_finalize_b, dim3(gx, gy, count), dim3(1024), 0, s, (const FinArgs*)d_args);
   } else {
@@ -2257,181 +1870,6 @@ extern "C" int uuo_fit_set_joint_accel(uuo_fit_t* fit, float w) {
   UUO_REQUIRE(w == 0.f || (w > 0.f && w <= 3.0e38f), "uuo_fit_set_joint_accel: the weight must be 0 (off) or a positive finite number");
   UUO_REQUIRE(w == 0.f || !uuo_recorder, "uuo_fit_set_joint_accel: lock-step batches do not carry the joint-acceleration term");
   fit->joint_accel = w;
-  return 0;
-}
-
-extern "C" int uuo_fit_set_foot_lock(uuo_fit_t* fit, float w, const float* d_contacts) {
-  UUO_REQUIRE(fit, "uuo_fit_set_foot_lock: null fit");
-  UUO_REQUIRE(w == 0.f || (w > 0.f && w <= 3.0e38f), "uuo_fit_set_foot_lock: the weight must be 0 (off) or a positive finite number");
-  UUO_REQUIRE(w == 0.f || d_contacts, "uuo_fit_set_foot_lock: a positive weight needs the contact labels [F][2] on the device");
-  UUO_REQUIRE(w == 0.f || !uuo_recorder, "uuo_fit_set_foot_lock: lock-step batches do not carry the foot-lock term");
-  fit->foot_lock = w;
-  fit->foot_contacts = (w == 0.f) ? nullptr : d_contacts;
-  return 0;
-}
-
-extern "C" int uuo_fit_set_floor(uuo_fit_t* fit, float w_pen, float w_con, float height, const int32_t* d_vids, int32_t k_left,
-                                 int32_t k_right, const float* d_contacts) {
-  UUO_REQUIRE(fit, "uuo_fit_set_floor: null fit");
-  UUO_REQUIRE((w_pen == 0.f || (w_pen > 0.f && w_pen <= 3.0e38f)) && (w_con == 0.f || (w_con > 0.f && w_con <= 3.0e38f)),
-              "uuo_fit_set_floor: the weights must be 0 (off) or positive finite numbers");
-  if (w_pen == 0.f && w_con == 0.f) {  // off: nothing else is looked at
-    fit->floor_pen = fit->floor_con = fit->floor_height = 0.f;
-    fit->floor_k = fit->floor_kl = 0;
-    fit->floor_vids = nullptr;
-    fit->floor_contacts = nullptr;
-    return 0;
-  }
-  UUO_REQUIRE(height >= -3.0e38f && height <= 3.0e38f, "uuo_fit_set_floor: the plane height must be a finite number of metres");
-  UUO_REQUIRE(k_left >= 1 && k_right >= 1, "uuo_fit_set_floor: every foot needs at least one sole point");
-  UUO_REQUIRE(k_left + (long long)k_right >= 2 && k_left + (long long)k_right <= UUO_FLOOR_MAXK,
-              "uuo_fit_set_floor: 2 .. 16 sole points (k_left + k_right)");
-  UUO_REQUIRE(d_vids, "uuo_fit_set_floor: the sole points' vertex ids [k_left + k_right] on the device are required");
-  UUO_REQUIRE(w_con == 0.f || d_contacts, "uuo_fit_set_floor: a positive contact weight needs the contact labels [F][2] on the device");
-  UUO_REQUIRE(!uuo_recorder, "uuo_fit_set_floor: lock-step batches do not carry the floor-contact term");
-  const int K = k_left + k_right;
-  int32_t h_vids[UUO_FLOOR_MAXK];
-  UUO_HIP_CHECK(hipMemcpy(h_vids, d_vids, (size_t)K * sizeof(int32_t), hipMemcpyDeviceToHost));
-  for (int k = 0; k < K; ++k)
-    UUO_REQUIRE(h_vids[k] >= 0 && h_vids[k] < fit->model->V, "uuo_fit_set_floor: a sole point's vertex id is outside [0, V)");
-  if (!fit->floor_up)  // [F][16][3] upstream gradients + [F] loss shares (k_floor_fwd -> the backward); first use
-    UUO_HIP_CHECK(hipMalloc((void**)&fit->floor_up, ((size_t)fit->F * UUO_FLOOR_MAXK * 3 + fit->F) * sizeof(float)));
-  fit->floor_pen = w_pen;
-  fit->floor_con = w_con;
-  fit->floor_height = height;
-  fit->floor_k = K;
-  fit->floor_kl = k_left;
-  fit->floor_vids = d_vids;
-  fit->floor_contacts = (w_con == 0.f) ? nullptr : d_contacts;
-  return 0;
-}
-
-extern "C" int uuo_fit_set_capsules(uuo_fit_t* fit, float w, int32_t n_caps, const int32_t* h_cap_joints, const float* h_cap_geom,
-                                    int32_t n_pairs, const int32_t* h_pairs) {
-  UUO_REQUIRE(fit, "uuo_fit_set_capsules: null fit");
-  UUO_REQUIRE(w == 0.f || (w > 0.f && w <= 3.0e38f), "uuo_fit_set_capsules: the weight must be 0 (off) or a positive finite number");
-  if (w == 0.f) {  // off: nothing else is looked at (the tables stay for the next call with the same lists)
-    fit->cap_w = 0.f;
-    return 0;
-  }
-  UUO_REQUIRE(n_caps >= 1 && n_caps <= UUO_CAPS_MAXC, "uuo_fit_set_capsules: 1 .. 32 capsules");
-  UUO_REQUIRE(n_pairs >= 1 && n_pairs <= UUO_CAPS_MAXP, "uuo_fit_set_capsules: 1 .. 256 pairs");
-  UUO_REQUIRE(h_cap_joints && h_cap_geom && h_pairs,
-              "uuo_fit_set_capsules: a positive weight needs the capsules' joints [C][2], geometry [C][3] and the pairs [P][2] (host arrays)");
-  UUO_REQUIRE(!uuo_recorder, "uuo_fit_set_capsules: lock-step batches do not carry the self-penetration term");
-  const int C = n_caps, P = n_pairs;
-  for (int c = 0; c < C; ++c) {
-    const int u = h_cap_joints[c * 2], v = h_cap_joints[c * 2 + 1];
-    UUO_REQUIRE(u >= 0 && u < UUO_NUM_JOINTS && v >= 0 && v < UUO_NUM_JOINTS, "uuo_fit_set_capsules: a capsule's joint id is outside [0, 24)");
-    UUO_REQUIRE(u != v, "uuo_fit_set_capsules: a capsule needs two different joints");
-    const float al = h_cap_geom[c * 3], be = h_cap_geom[c * 3 + 1], r = h_cap_geom[c * 3 + 2];
-    UUO_REQUIRE(al >= -3.0e38f && al <= 3.0e38f && be >= -3.0e38f && be <= 3.0e38f,
-                "uuo_fit_set_capsules: a capsule's alpha and beta must be finite");
-    UUO_REQUIRE(r > 0.f && r <= 3.0e38f, "uuo_fit_set_capsules: a capsule's radius must be a positive finite number of metres");
-  }
-  for (int k = 0; k < P; ++k) {
-    const int i = h_pairs[k * 2], j = h_pairs[k * 2 + 1];
-    UUO_REQUIRE(i >= 0 && i < C && j >= 0 && j < C, "uuo_fit_set_capsules: a pair's capsule index is outside [0, C)");
-    UUO_REQUIRE(i != j, "uuo_fit_set_capsules: a pair needs two different capsules");
-  }
-  if (!fit->cap_tab) {  // first use: the tables (ints, then the geometry) and the kernel's outputs
-    UUO_HIP_CHECK(hipMalloc((void**)&fit->cap_tab, UUO_CAPS_TAB_INTS * sizeof(int32_t) + UUO_CAPS_MAXC * 3 * sizeof(float)));
-    fit->cap_geom = reinterpret_cast<float*>(fit->cap_tab + UUO_CAPS_TAB_INTS);
-    fit->cap_c = fit->cap_p = 0;
-    UUO_HIP_CHECK(hipStreamCreateWithFlags(&fit->cap_stream, hipStreamNonBlocking));
-  }
-  if (!fit->cap_up) UUO_HIP_CHECK(hipMalloc((void**)&fit->cap_up, ((size_t)fit->F * 72 + fit->F) * sizeof(float)));
-  const bool same = fit->cap_c == C && fit->cap_p == P &&
-                    std::memcmp(fit->cap_h_joints, h_cap_joints, (size_t)C * 2 * sizeof(int32_t)) == 0 &&
-                    std::memcmp(fit->cap_h_geom, h_cap_geom, (size_t)C * 3 * sizeof(float)) == 0 &&
-                    std::memcmp(fit->cap_h_pairs, h_pairs, (size_t)P * 2 * sizeof(int32_t)) == 0;
-  if (!same) {
-    // the joint -> (pair, end) table, CSR: joint jj's rows list 4 k + end in pair order, inside a pair in the order
-    // u_i (end 0), v_i (1), u_j (2), v_j (3) -- the order in which k_capsule_fwd sums
-    static thread_local int32_t h_tab[UUO_CAPS_TAB_INTS];
-    std::memset(h_tab, 0, sizeof(h_tab));
-    std::memcpy(h_tab, h_cap_joints, (size_t)C * 2 * sizeof(int32_t));
-    std::memcpy(h_tab + UUO_CAPS_TAB_PAIRS, h_pairs, (size_t)P * 2 * sizeof(int32_t));
-    int n = 0;
-    for (int jj = 0; jj < UUO_NUM_JOINTS; ++jj) {
-      h_tab[UUO_CAPS_TAB_OFF + jj] = n;
-      for (int k = 0; k < P; ++k)
-        for (int end = 0; end < 4; ++end)
-          if (h_cap_joints[h_pairs[k * 2 + (end >> 1)] * 2 + (end & 1)] == jj) h_tab[UUO_CAPS_TAB_ENT + n++] = 4 * k + end;
-    }
-    h_tab[UUO_CAPS_TAB_OFF + UUO_NUM_JOINTS] = n;  // = 4 P
-    fit->cap_w = 0.f;
-    fit->cap_c = fit->cap_p = 0;
-    // the only reader of the old tables is the last k_capsule_fwd launched on this workspace: wait for its stream alone (no
-    // device-wide wait: other threads' workspaces keep running; nothing is added to an evaluation), upload on the workspace's
-    // own non-blocking stream, and return once the copies have landed, so that every later launch sees them
-    if (fit->cap_launched) UUO_HIP_CHECK(hipStreamSynchronize(fit->cap_last_stream));
-    fit->cap_launched = false;
-    UUO_HIP_CHECK(hipMemcpyAsync(fit->cap_tab, h_tab, sizeof(h_tab), hipMemcpyHostToDevice, fit->cap_stream));
-    float h_geom[UUO_CAPS_MAXC * 3] = {0.f};  // (the kernel fetches the whole table)
-    std::memcpy(h_geom, h_cap_geom, (size_t)C * 3 * sizeof(float));
-    UUO_HIP_CHECK(hipMemcpyAsync(fit->cap_geom, h_geom, sizeof(h_geom), hipMemcpyHostToDevice, fit->cap_stream));
-    UUO_HIP_CHECK(hipStreamSynchronize(fit->cap_stream));
-    std::memcpy(fit->cap_h_joints, h_cap_joints, (size_t)C * 2 * sizeof(int32_t));
-    std::memcpy(fit->cap_h_geom, h_cap_geom, (size_t)C * 3 * sizeof(float));
-    std::memcpy(fit->cap_h_pairs, h_pairs, (size_t)P * 2 * sizeof(int32_t));
-    fit->cap_c = C;
-    fit->cap_p = P;
-  }
-  fit->cap_w = w;
-  return 0;
-}
-
-extern "C" int uuo_fit_set_joint_limits(uuo_fit_t* fit, float w, const float* h_lo, const float* h_hi) {
-  UUO_REQUIRE(fit, "uuo_fit_set_joint_limits: null fit");
-  UUO_REQUIRE(w == 0.f || (w > 0.f && w <= 3.0e38f), "uuo_fit_set_joint_limits: the weight must be 0 (off) or a positive finite number");
-  if (w == 0.f) {  // off: nothing else is looked at (the table stays for the next call with the same bounds)
-    fit->lim_w = 0.f;
-    return 0;
-  }
-  UUO_REQUIRE(h_lo && h_hi, "uuo_fit_set_joint_limits: a positive weight needs the bounds lo [23][3] and hi [23][3] (host arrays)");
-  UUO_REQUIRE(!uuo_recorder, "uuo_fit_set_joint_limits: lock-step batches do not carry the joint-angle limit term");
-  for (int i = 0; i < 69; ++i) {
-    const float lo = h_lo[i], hi = h_hi[i];
-    UUO_REQUIRE(lo == lo && hi == hi, "uuo_fit_set_joint_limits: a bound is NaN");
-    UUO_REQUIRE(lo <= 3.0e38f, "uuo_fit_set_joint_limits: a lower bound of +inf admits no angle (-inf = no bound)");
-    UUO_REQUIRE(hi >= -3.0e38f, "uuo_fit_set_joint_limits: an upper bound of -inf admits no angle (+inf = no bound)");
-    UUO_REQUIRE(lo <= hi, "uuo_fit_set_joint_limits: lo > hi");
-  }
-  if (!fit->lim_tab) {  // first use: the table and the upload stream
-    UUO_HIP_CHECK(hipMalloc((void**)&fit->lim_tab, 2 * 69 * sizeof(float)));
-    fit->lim_have = false;
-    UUO_HIP_CHECK(hipStreamCreateWithFlags(&fit->lim_stream, hipStreamNonBlocking));
-  }
-  if (!fit->lim_g) UUO_HIP_CHECK(hipMalloc((void**)&fit->lim_g, ((size_t)fit->F * 207 + fit->F) * sizeof(float)));
-  const bool same = fit->lim_have && std::memcmp(fit->lim_h, h_lo, 69 * sizeof(float)) == 0 &&
-                    std::memcmp(fit->lim_h + 69, h_hi, 69 * sizeof(float)) == 0;
-  if (!same) {
-    fit->lim_w = 0.f;
-    fit->lim_have = false;
-    // the only reader of the old table is the last k_limit_fwd launched on this workspace: wait for its stream alone (no
-    // device-wide wait: other threads' workspaces keep running; nothing is added to an evaluation), upload on the workspace's
-    // own non-blocking stream, and return once the copy has landed, so that every later launch sees it
-    if (fit->lim_launched) UUO_HIP_CHECK(hipStreamSynchronize(fit->lim_last_stream));
-    fit->lim_launched = false;
-    static thread_local float h_tab[2 * 69];
-    std::memcpy(h_tab, h_lo, 69 * sizeof(float));
-    std::memcpy(h_tab + 69, h_hi, 69 * sizeof(float));
-    UUO_HIP_CHECK(hipMemcpyAsync(fit->lim_tab, h_tab, sizeof(h_tab), hipMemcpyHostToDevice, fit->lim_stream));
-    UUO_HIP_CHECK(hipStreamSynchronize(fit->lim_stream));
-    std::memcpy(fit->lim_h, h_tab, sizeof(h_tab));
-    fit->lim_have = true;
-  }
-  fit->lim_w = w;
-  return 0;
-}
-
-extern "C" int uuo_fit_set_prior_weights(uuo_fit_t* fit, const float* d_weights) {
-  UUO_REQUIRE(fit, "uuo_fit_set_prior_weights: null fit");
-  UUO_REQUIRE(!d_weights || !uuo_recorder, "uuo_fit_set_prior_weights: lock-step batches do not carry the pose prior's weights");
-  // (the buffer k_prior_conf fills is the joint-angle limit term's: [F][23][9] gradients, then [F] shares)
-  if (d_weights && !fit->lim_g) UUO_HIP_CHECK(hipMalloc((void**)&fit->lim_g, ((size_t)fit->F * 207 + fit->F) * sizeof(float)));
-  fit->prior_w = d_weights;
   return 0;
 }
 
@@ -2853,7 +2291,7 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
   a.lock_w = lock ? (float)((double)fit->foot_lock / ((double)(F - 1) * 6.0)) : 0.f;
   a.contacts = lock ? fit->foot_contacts : nullptr;
   // EXTENSION: the floor-contact term rides on them too: its K sole points are items M .. M + K - 1 of the backward, with the
-  // upstream gradients k_floor_fwd leaves (launch_floor below, once the frames' FrameLds are there)
+  // upstream gradients k_floor_fwd leaves (launch_side_terms below, once the frames' FrameLds are there)
   const bool floor = fit->floor_k != 0;
   UUO_REQUIRE(!floor || !uuo_recorder, "closure: lock-step batches do not carry the floor-contact term");
   UUO_REQUIRE(!floor || !fit->frame_assign, "closure: the floor-contact term (uuo_fit_set_floor, extension) is not built for the "
@@ -2864,68 +2302,19 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
     a.floor_up = fit->floor_up;
     a.floor_loss = fit->floor_up + (size_t)F * UUO_FLOOR_MAXK * 3;
   }
-  auto launch_floor = [&]() {
-    if (!floor) return;
-    FloorFwdArgs b;
-    std::memset(&b, 0, sizeof(b));
-    b.PT = m->PT; b.ST = m->ST; b.vt = m->vt; b.Ww = m->Ww; b.Wi = m->Wi;
-    b.V = m->V; b.F = F; b.K = fit->floor_k; b.KL = fit->floor_kl;
-    b.frames = fit->frames;
-    b.trans = src.trans;
-    b.vids = fit->floor_vids;
-    b.contacts = fit->floor_contacts;
-    b.h = fit->floor_height;
-    b.cpen = (float)((double)fit->floor_pen / ((double)F * (double)fit->floor_k));
-    b.ccon = (float)((double)fit->floor_con / (2.0 * (double)F));
-    b.up = fit->floor_up;
-    b.loss = fit->floor_up + (size_t)F * UUO_FLOOR_MAXK * 3;
-    hipLaunchKernelGGL(k_floor_fwd, dim3(F), dim3(64), 0, s, b);
-  };
-  // EXTENSION: the self-penetration term: k_capsule_fwd (launch_caps below, beside launch_floor) leaves d loss / d G_j^t and the
+  // EXTENSION: the self-penetration term: k_capsule_fwd (launch_side_terms below) leaves d loss / d G_j^t and the
   // frames' shares, the temporal instantiations add them to uj and slot 3 (cap_up != null).  Frames are not coupled: any F.
   const bool caps = fit->cap_w != 0.f;
   UUO_REQUIRE(!caps || !uuo_recorder, "closure: lock-step batches do not carry the self-penetration term");
   if (caps) a.cap_up = fit->cap_up;  // ([F][72] gradients, then the [F] shares)
-  auto launch_caps = [&]() {
-    if (!caps) return;
-    CapsFwdArgs b;
-    std::memset(&b, 0, sizeof(b));
-    b.frames = fit->frames;
-    b.tab = fit->cap_tab;
-    b.geom = fit->cap_geom;
-    b.C = fit->cap_c; b.P = fit->cap_p;
-    b.cl = (float)((double)fit->cap_w / (double)F);
-    b.cg = (float)(2.0 * (double)fit->cap_w / (double)F);
-    b.up = fit->cap_up;
-    b.loss = fit->cap_up + (size_t)F * 72;
-    hipLaunchKernelGGL(k_capsule_fwd, dim3(F), dim3(64), 0, s, b);
-    fit->cap_launched = true;  // (uuo_fit_set_capsules waits for this stream before it replaces the tables)
-    fit->cap_last_stream = s;
-  };
-  // EXTENSION: the joint-angle limit term: k_limit_fwd (launch_limits below, beside launch_caps) leaves the parameter-space
+  // EXTENSION: the joint-angle limit term: k_limit_fwd (launch_side_terms below) leaves the parameter-space
   // gradients and the frames' shares, the temporal instantiations add them to gout and slot 3 (lim_g != null).  Any F.
   const bool limits = fit->lim_w != 0.f;
   UUO_REQUIRE(!limits || !uuo_recorder, "closure: lock-step batches do not carry the joint-angle limit term");
   UUO_REQUIRE(!limits || (p->stage != UUO_STAGE_PART && !soft_chamfer),
               "closure: the joint-angle limit term belongs to the chamfer and marker stages' hard-assignment closures");
   if (limits) a.lim_g = fit->lim_g;  // ([F][207] gradients, then the [F] shares)
-  auto launch_limits = [&]() {
-    if (!limits) return;
-    LimitFwdArgs b;
-    std::memset(&b, 0, sizeof(b));
-    b.body = src.body;
-    b.tab = fit->lim_tab;
-    b.F = F;
-    b.norm_body = src.norm_body;
-    b.cl = (float)((double)fit->lim_w / (double)F);
-    b.cg = (float)(2.0 * (double)fit->lim_w / (double)F);
-    b.g = fit->lim_g;
-    b.loss = fit->lim_g + (size_t)F * 207;
-    hipLaunchKernelGGL(k_limit_fwd, dim3((F + UUO_LIM_FPB - 1) / UUO_LIM_FPB), dim3(64), 0, s, b);
-    fit->lim_launched = true;  // (uuo_fit_set_joint_limits waits for this stream before it replaces the table)
-    fit->lim_last_stream = s;
-  };
-  // EXTENSION: the pose prior's per-(frame, joint) weights: k_prior_conf (launch_prior below, after launch_limits) leaves the whole
+  // EXTENSION: the pose prior's per-(frame, joint) weights: k_prior_conf (launch_side_terms below) leaves the whole
   // weighted prior in the limit term's buffer, which the temporal instantiations add after their own pose prior -- that one runs
   // with a coefficient of 0 here, and so does the finalize's (its slot-2 sum is then 0).  With w_pose == 0 there is no prior to
   // weigh: the setting changes nothing.  (uuo_stage_compactable looks at the problem's w_pose, not at these coefficients.)
@@ -2937,19 +2326,9 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
     a.cpose = 0.f;
     a.lim_g = fit->lim_g;
   }
-  auto launch_prior = [&]() {
-    if (!prior) return;
-    PriorConfArgs b;
-    std::memset(&b, 0, sizeof(b));
-    b.body = d_x + lay.off_pose;
-    b.target = p->d_o_pose;
-    b.w = fit->prior_w;
-    b.F = F;
-    b.add = limits ? 1 : 0;
-    b.cl = (float)((double)p->w_pose / ((double)F * 207.0));
-    b.cg = (float)(2.0 * (double)p->w_pose / ((double)F * 207.0));
-    b.g = fit->lim_g;
-    hipLaunchKernelGGL(k_prior_conf, dim3((F + UUO_LIM_FPB - 1) / UUO_LIM_FPB), dim3(64), 0, s, b);
+  // the forward kernels of the four terms above (side_terms.hip), for the routes below to launch once fit->frames is there
+  auto launch_side_terms = [&]() {
+    uuo_launch_side_terms(fit, s, F, src, prior ? d_x + lay.off_pose : nullptr, p->d_o_pose, p->w_pose, UuoSideTerms{floor, caps, limits, prior});
   };
   const bool temporal = accel || lock || floor || caps || limits || prior;
   a.h.gx = F;
@@ -2992,30 +2371,32 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
   }
   bool fin_fused = false;
   const int part_general = UUO_ENV_INT("UUO_PART_GENERAL_BWD", 0);  // debug flavour only: the general kernel, for comparison
-  if (p->stage == UUO_STAGE_PART && p->pose_cache_id != 0 && fit->pose_cache_id == p->pose_cache_id && !part_general) {
+  BwdFacts k;
+  k.stage = p->stage;
+  k.part_cached = p->stage == UUO_STAGE_PART && p->pose_cache_id != 0 && fit->pose_cache_id == p->pose_cache_id && !part_general;
+  k.one_wave = M <= 16;
+  k.three_corner = p->stage == UUO_STAGE_MARKER && p->n_corners == 3;
+  k.surface = fit->surface != 0;
+  k.dense = soft_chamfer;
+  k.robust = robust; k.temporal = temporal; k.offs = offs; k.fassign = fassign; k.floor = floor;
+  // the two item routes' buffer: [F][3 M][3] corner items + [F] loss sums, allocated on the first such evaluation
+  float *items = nullptr, *item_loss = nullptr;
+  auto item_buffer = [&]() -> int {
+    if (!fit->bary_items) UUO_HIP_CHECK(hipMalloc((void**)&fit->bary_items, ((size_t)F * 3 * M * 3 + F) * sizeof(float)));
+    items = fit->bary_items;
+    item_loss = fit->bary_items + (size_t)F * 3 * M * 3;
+    return 0;
+  };
+  const BwdRoute route = bwd_route(k);
+  if (route == BWD_ROUTE_PART) {
     a.C = fit->pose_cache;
     a.pre = soft ? fit->soft_pre : nullptr;
-    const int waves = M <= 16 ? 1 : BWD_NW;
-    if (robust) {
-      if (!uuo_record(UUO_OP_BWD_PART_R, F, waves, a)) {
-        if (waves == 1)
-          hipLaunchKernelGGL(k_bwd_part1_r, dim3(F), dim3(64), 0, s, a);
-        else
-          hipLaunchKernelGGL(k_bwd_part_r, dim3(F), dim3(BWD_NW * 64), 0, s, a);
-      }
-    } else if (!uuo_record(UUO_OP_BWD_PART, F, waves, a)) {
-      if (waves == 1)
-        hipLaunchKernelGGL(k_bwd_part1, dim3(F), dim3(64), 0, s, a);
-      else
-        hipLaunchKernelGGL(k_bwd_part, dim3(F), dim3(BWD_NW * 64), 0, s, a);
-    }
-  } else if (p->stage == UUO_STAGE_MARKER && p->n_corners == 3) {
+  } else if (route == BWD_ROUTE_THREE_CORNER) {
     // three-corner (barycentric) placement: a forward pass over the 3 M corner vertices forms the virtual markers, the loss and
     // d loss / d corner; the sparse backward runs on those items (k_bwd_items)
     UUO_REQUIRE(!uuo_recorder, "closure: the three-corner marker closure is not available inside a lock-step batch");
-    if (!fit->bary_items) UUO_HIP_CHECK(hipMalloc((void**)&fit->bary_items, ((size_t)F * 3 * M * 3 + F) * sizeof(float)));
-    float* items = fit->bary_items;
-    float* item_loss = fit->bary_items + (size_t)F * 3 * M * 3;
+    rc = item_buffer();
+    if (rc) return rc;
     BaryFwdArgs b;
     std::memset(&b, 0, sizeof(b));
     b.PT = m->PT; b.ST = m->ST; b.vt = m->vt; b.Ww = m->Ww; b.Wi = m->Wi; b.tree = m->tree;
@@ -3038,35 +2419,23 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
       hipLaunchKernelGGL(k_bary_fwd_r, dim3(F), dim3(BWD_NW * 64), 0, s, b);
     else
       hipLaunchKernelGGL(k_bary_fwd, dim3(F), dim3(BWD_NW * 64), 0, s, b);
-    launch_floor();
-    launch_caps();
-    launch_limits();
-    launch_prior();
+    launch_side_terms();
     a.M = 3 * M;
     a.up_items = items;
     a.item_loss = item_loss;
     a.frames = fit->frames;
-    if (floor)
-      hipLaunchKernelGGL(offs ? k_bwd_items_t_o_fl : k_bwd_items_t_fl, dim3(F), dim3(BWD_NW * 64), 0, s, a);
-    else if (offs)
-      hipLaunchKernelGGL(temporal ? k_bwd_items_t_o : k_bwd_items_o, dim3(F), dim3(BWD_NW * 64), 0, s, a);
-    else if (temporal)
-      hipLaunchKernelGGL(k_bwd_items_t, dim3(F), dim3(BWD_NW * 64), 0, s, a);
-    else
-      hipLaunchKernelGGL(k_bwd_items, dim3(F), dim3(BWD_NW * 64), 0, s, a);
-  } else if (fit->surface != 0) {
+  } else if (route == BWD_ROUTE_SURFACE) {
     // EXTENSION: point-to-surface chamfer term.  The forward above has skinned the vertices and found every marker's nearest
     // one; k_ring_pick chooses a face of its one-ring in that buffer, k_surf_fwd re-skins the face's corners, forms the
     // term and its per-corner items, and the sparse backward runs on those items with per-frame vertex ids
     UUO_REQUIRE(!uuo_recorder, "closure: the surface chamfer closure is not available inside a lock-step batch");
     UUO_REQUIRE(p->stage == UUO_STAGE_CHAMFER && !soft, "closure: the surface term belongs to the chamfer stage's hard assignment");
-    if (!fit->bary_items) UUO_HIP_CHECK(hipMalloc((void**)&fit->bary_items, ((size_t)F * 3 * M * 3 + F) * sizeof(float)));
+    rc = item_buffer();
+    if (rc) return rc;
     if (!fit->surf_corners) {
       UUO_HIP_CHECK(hipMalloc((void**)&fit->surf_corners, (size_t)F * M * 3 * (sizeof(int) + sizeof(float))));
       fit->surf_bary = reinterpret_cast<float*>(fit->surf_corners + (size_t)F * M * 3);
     }
-    float* items = fit->bary_items;
-    float* item_loss = fit->bary_items + (size_t)F * 3 * M * 3;
     rc = uuo_launch_ring_pick(m, s, F, M, fit->verts, p->d_markers, fit->nn, nullptr, fit->mask, fit->surf_corners, nullptr, nullptr,
                               nullptr, nullptr);
     if (rc) return rc;
@@ -3086,20 +2455,13 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
     b.item_loss = item_loss;
     b.bary = fit->surf_bary;
     hipLaunchKernelGGL(robust ? k_surf_fwd_r : k_surf_fwd, dim3(F), dim3(BWD_NW * 64), 0, s, b);
-    launch_floor();
-    launch_caps();
-    launch_limits();
-    launch_prior();
+    launch_side_terms();
     a.M = 3 * M;
     a.assign = fit->surf_corners;
     a.up_items = items;
     a.item_loss = item_loss;
     a.frames = fit->frames;
-    if (floor)
-      hipLaunchKernelGGL(k_bwd_items_t_f_fl, dim3(F), dim3(BWD_NW * 64), 0, s, a);
-    else
-      hipLaunchKernelGGL(temporal ? k_bwd_items_t_f : k_bwd_items_f, dim3(F), dim3(BWD_NW * 64), 0, s, a);
-  } else if (soft && p->stage == UUO_STAGE_CHAMFER) {
+  } else if (route == BWD_ROUTE_DENSE) {
     // EXTENSION: soft-assignment data term of the chamfer stage.  The forward above has skinned the vertices and run the exact
     // search (dmin, the hard assignment); the soft minimum gives EVERY vertex within reach of a marker a gradient, so the
     // backward is the dense one: both blend contractions on the matrix pipe (dense_bwd.hip), then this kernel's kinematic
@@ -3112,7 +2474,6 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
     if (rc) return rc;
     a.pre = fit->dense->pre;
     a.dpf_part = fit->dense->part;
-    hipLaunchKernelGGL(k_bwd_dense, dim3(F), dim3(BWD_NW * 64), 0, s, a);
   } else {
     UUO_REQUIRE(!soft, "closure: the soft-assignment part closure runs on the cached pose blend only");
     // the general kernel finalizes by itself: its last block to finish sums the per-frame partials and reports (bwd_body)
@@ -3125,53 +2486,25 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
       a.fin_counter = reinterpret_cast<unsigned*>(fit->scalars + 32);
       fin_fused = true;
     }
-    if (offs) {
-      // EXTENSION: latent marker offsets (the marker stage's one-hot closure); with the joint-acceleration term the pose-prep
-      // launch below comes first for the same reason as there
-      if (temporal) {
-        rc = uuo_launch_pose_prep(m, s, F, src, fit->pfaT, fit->A, nullptr, fit->frames);
-        if (rc) return rc;
-        a.frames = fit->frames;
-        launch_floor();
-        launch_caps();
-        launch_limits();
-        launch_prior();
-        if (floor)
-          hipLaunchKernelGGL(robust ? k_bwd_sparse_r_t_o_fl : k_bwd_sparse_t_o_fl, dim3(F), dim3(BWD_NW * 64), 0, s, a);
-        else
-          hipLaunchKernelGGL(robust ? k_bwd_sparse_r_t_o : k_bwd_sparse_t_o, dim3(F), dim3(BWD_NW * 64), 0, s, a);
-      } else {
-        hipLaunchKernelGGL(robust ? k_bwd_sparse_r_o : k_bwd_sparse_o, dim3(F), dim3(BWD_NW * 64), 0, s, a);
-      }
-    } else if (temporal) {
+    if (temporal) {
       // EXTENSION: the block of frame f reads its neighbours' world joints.  The marker stage's closure has no forward of its
       // own (its backward re-runs each frame's kinematic chain): a pose-prep launch leaves every frame's FrameLds first, and the
       // backward blocks start from them
-      if (p->stage == UUO_STAGE_MARKER) {
+      if (p->stage == UUO_STAGE_MARKER) {  // (always, with the latent marker offsets: has_offsets)
         rc = uuo_launch_pose_prep(m, s, F, src, fit->pfaT, fit->A, nullptr, fit->frames);
         if (rc) return rc;
         a.frames = fit->frames;
       }
-      launch_floor();
-      launch_caps();
-      launch_limits();
-      launch_prior();
-      if (floor)
-        hipLaunchKernelGGL(robust ? k_bwd_sparse_r_t_fl : k_bwd_sparse_t_fl, dim3(F), dim3(BWD_NW * 64), 0, s, a);
-      else if (fassign)
-        hipLaunchKernelGGL(robust ? k_bwd_sparse_r_t_f : k_bwd_sparse_t_f, dim3(F), dim3(BWD_NW * 64), 0, s, a);
-      else if (robust)
-        hipLaunchKernelGGL(k_bwd_sparse_r_t, dim3(F), dim3(BWD_NW * 64), 0, s, a);
-      else
-        hipLaunchKernelGGL(k_bwd_sparse_t, dim3(F), dim3(BWD_NW * 64), 0, s, a);
-    } else if (fassign) {
-      hipLaunchKernelGGL(robust ? k_bwd_sparse_r_f : k_bwd_sparse_f, dim3(F), dim3(BWD_NW * 64), 0, s, a);
-    } else if (robust) {
-      if (!uuo_record(UUO_OP_BWD_R, F, 1, a)) hipLaunchKernelGGL(k_bwd_sparse_r, dim3(F), dim3(BWD_NW * 64), 0, s, a);
-    } else if (!uuo_record(UUO_OP_BWD, F, 1, a)) {
-      hipLaunchKernelGGL(k_bwd_sparse, dim3(F), dim3(BWD_NW * 64), 0, s, a);
+      launch_side_terms();
     }
   }
+  // the one backward launch: the instantiation these facts name (recorded instead, inside a lock-step batch, where a batch form
+  // exists; gy of a part-stage record = waves per frame)
+  const BwdKernel* bk = nullptr;
+  rc = bwd_select(k, &bk);
+  if (rc) return rc;
+  if (bk->op == BWD_NO_OP || !uuo_record(bk->op, F, (bk->flags & BWD_PART) ? bk->threads / 64 : 1, a))
+    hipLaunchKernelGGL((bk->kernel), dim3(F), dim3(bk->threads), 0, s, a);
   UUO_HIP_CHECK(hipGetLastError());
   if (!fin_fused) {
     if (offs)
@@ -3263,6 +2596,31 @@ extern "C" int uuo_debug_index_map(int stage, int F, int compact, int* h_out) {
   const UuoIndexMap m = uuo_stage_index_map(&p, compact != 0 && stage != UUO_STAGE_PART);
   const int n = m.nseg ? m.n_act : stage_layout(stage, F).n;
   for (int c = 0; c < n; ++c) h_out[c] = m.full(c);
+  return n;
+}
+// host-only debug hook: the backward kernel that bwd_select names for facts[11] = {stage, part_cached, one_wave, three_corner,
+// surface, soft chamfer, robust, temporal, offs, fassign, floor} (tests/test_bwd_select.py), or, with facts == null, row `row` of
+// the kernel table.  Its entry point's name goes to name_out[64], its flag word to *flags_out; returns the number of rows of the
+// table, or -22 for a refused combination / a row outside the table
+extern "C" int uuo_debug_bwd_select(const int* facts, int row, char* name_out, unsigned* flags_out) {
+  UUO_REQUIRE(name_out && flags_out, "uuo_debug_bwd_select: null argument");
+  const int n = (int)(sizeof(bwd_kernels) / sizeof(bwd_kernels[0]));
+  const BwdKernel* bk = nullptr;
+  if (facts) {
+    BwdFacts k;
+    k.stage = facts[0];
+    k.part_cached = facts[1] != 0; k.one_wave = facts[2] != 0; k.three_corner = facts[3] != 0; k.surface = facts[4] != 0;
+    k.dense = facts[5] != 0; k.robust = facts[6] != 0; k.temporal = facts[7] != 0; k.offs = facts[8] != 0;
+    k.fassign = facts[9] != 0; k.floor = facts[10] != 0;
+    const int rc = bwd_select(k, &bk);
+    if (rc) return rc;
+  } else {
+    UUO_REQUIRE(row >= 0 && row < n, "uuo_debug_bwd_select: no such row");
+    bk = &bwd_kernels[row];
+  }
+  std::strncpy(name_out, bk->name, 63);
+  name_out[63] = 0;
+  *flags_out = bk->flags;
   return n;
 }
 // the same for a whole problem (stage, F, M, w_offsets: the latent marker offsets' coordinates included)
@@ -3370,7 +2728,13 @@ extern "C" int uuo_smpl_backward(uuo_model_t* m, void* stream, int F, const floa
   a.off_pose = a.off_root = a.off_z = a.off_trans = -1;
   a.gs_pose = a.gs_root = 9;
   const int gather = UUO_ENV_INT("UUO_SMPL_BWD_GATHER", 0);  // debug flavour only: every vertex an item of the sparse gather
-  if (d_up_verts && !gather) {
+  BwdFacts k = {};
+  k.stage = UUO_STAGE_UPSTREAM;
+  k.dense = d_up_verts && !gather;
+  const BwdKernel* bk = nullptr;  // (k_bwd_dense or k_bwd_sparse; never recorded: this is no solve)
+  const int rc_k = bwd_select(k, &bk);
+  if (rc_k) return rc_k;
+  if (k.dense) {
     // dense route (dense_bwd.hip): both blend contractions on the matrix pipe, the kinematic tail on their sums.  Scratch per
     // stream, under the entry's mutex across reallocation and launches (as uuo_smpl_forward)
     uuo_model::BwdScratch* scp;
@@ -3413,11 +2777,11 @@ extern "C" int uuo_smpl_backward(uuo_model_t* m, void* stream, int F, const floa
     a.frames = sc.frames;
     a.pre = sc.ws->pre;
     a.dpf_part = sc.ws->part;
-    hipLaunchKernelGGL(k_bwd_dense, dim3(F), dim3(BWD_NW * 64), 0, s, a);
+    hipLaunchKernelGGL((bk->kernel), dim3(F), dim3(bk->threads), 0, s, a);  // (under the scratch entry's mutex)
     UUO_HIP_CHECK(hipGetLastError());
     return 0;
   }
-  hipLaunchKernelGGL(k_bwd_sparse, dim3(F), dim3(BWD_NW * 64), 0, s, a);
+  hipLaunchKernelGGL((bk->kernel), dim3(F), dim3(bk->threads), 0, s, a);
   UUO_HIP_CHECK(hipGetLastError());
   return 0;
 }

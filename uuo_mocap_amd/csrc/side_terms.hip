@@ -1,0 +1,649 @@
+// Forward kernels of the closures' side terms -- floor contact, bone-capsule self-penetration, joint-angle limits, the pose
+// prior's per-(frame, joint) weights -- with the setters that configure them on a fit workspace.  Each kernel leaves upstream
+// gradients and per-frame loss shares for the backward kernels of the same evaluation (closure.hip: the temporal instantiations
+// of bwd_body); they share no device code with it but frame_math.h.  closure.hip reaches them through uuo_launch_side_terms.
+#include <cstring>
+
+#include "frame_math.h"
+
+// ----------------------------------------------------------------------------------------------------
+// EXTENSION (not reference behaviour; uuo_fit_set_floor): a floor-contact term on K sole vertices (2 <= K <= 16; the left
+// foot's K_L points first, s(p) the foot of point p), z up, the plane at height h, contact labels c[F][2] in [0, 1]:
+//   pen[t][p] = max(h - z[t][p], 0)                       (always on)
+//   flo[t][s] = max(min_{p of foot s} z[t][p] - h, 0)      (the foot's lowest point; the first in list order on ties)
+//   loss += w_pen sum pen^2 / (F K) + w_con sum c[t][s] flo[t][s]^2 / (2 F)
+//   dL/dz[t][p] = -2 w_pen pen / (F K) + [p = argmin of its foot] w_con c flo / F,   x and y components 0.
+// k_floor_fwd: one wave per frame.  It starts from the frame's FrameLds as k_pose_prep (or the closure's forward) left them,
+// gathers the K vertices four at a time (one per 16-lane group: the arithmetic of the backward kernel's item loop, in its
+// order), evaluates the term on lanes 0 .. K-1 and writes the K upstream gradients and the frame's weighted share of the loss.
+// The backward kernels (ACCEL instantiations of bwd_body) take the points as items M .. M + K - 1.
+// ----------------------------------------------------------------------------------------------------
+struct FloorFwdArgs {
+  uuo_gptr<const float> PT, ST, vt, Ww;
+  uuo_gptr<const int> Wi;
+  int V, F, K, KL;               // K points, the first KL of them on the left foot
+  uuo_gptr<const float> frames;  // [F][FrameLds]
+  uuo_gptr<const float> trans;   // [F][3] or null
+  uuo_gptr<const int> vids;      // [K]
+  uuo_gptr<const float> contacts;  // [F][2] or null (ccon == 0)
+  float h, cpen, ccon;           // plane height, w_pen / (F K), w_con / (2 F)
+  uuo_gptr<float> up;            // [F][K][3] out
+  uuo_gptr<float> loss;          // [F] out
+};
+__global__ __launch_bounds__(64) void k_floor_fwd(FloorFwdArgs a) {
+  __shared__ FrameLds L;
+  __shared__ float sA[UUO_NUM_JOINTS * 12];
+  __shared__ float spf[UUO_KB];
+  __shared__ float sz[UUO_FLOOR_MAXK];
+  const int f = blockIdx.x, lane = threadIdx.x;
+  const int K = a.K;
+  {
+    constexpr int NW = sizeof(FrameLds) / 4;
+    float* dst_l = reinterpret_cast<float*>(&L);
+    for (int i = lane; i < NW; i += 64) dst_l[i] = a.frames[(size_t)f * NW + i];
+  }
+  __syncthreads();
+  if (lane < UUO_NUM_JOINTS) frame_skin_matrix(L, lane, sA + lane * 12);
+  for (int i = lane; i < UUO_KB; i += 64) {
+    float v = 0.f;
+    if (i < UUO_NUM_POSE_FEATS) {
+      const int j = 1 + i / 9, e = i % 9;
+      v = L.R[j][e] - ((e == 0 || e == 4 || e == 8) ? 1.f : 0.f);
+    }
+    spf[i] = v;
+  }
+  __syncthreads();
+  const float trz = a.trans ? a.trans[(size_t)f * 3 + 2] : 0.f;
+  const int gq = lane >> 4, sl = lane & 15;
+  float fk[13];
+#pragma unroll
+  for (int t = 0; t < 13; ++t) fk[t] = spf[sl + 16 * t];
+  const float beta_s = (sl < 10) ? L.beta[sl] : 0.f;
+  auto row_sum = [](float v) {
+    v += dpp_rot<0x128>(v);
+    v += dpp_rot<0x124>(v);
+    v += dpp_rot<0x122>(v);
+    v += dpp_rot<0x121>(v);
+    return v;
+  };
+  for (int r = 0; r < (K + 3) / 4; ++r) {
+    const int p = gq + 4 * r;
+    int vi = (p < K) ? a.vids[p] : 0;
+    if ((unsigned)vi >= (unsigned)a.V) vi = 0;  // (uuo_fit_set_floor has checked the ids; keeps the gather in bounds)
+    const float* pt = a.PT + (size_t)vi * 3 * UUO_KB + sl;
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int t = 0; t < 13; ++t) {
+      s0 = fmaf(pt[16 * t], fk[t], s0);
+      s1 = fmaf(pt[UUO_KB + 16 * t], fk[t], s1);
+      s2 = fmaf(pt[2 * UUO_KB + 16 * t], fk[t], s2);
+    }
+    const float* ps = a.ST + (size_t)vi * 30 + (sl < 10 ? sl : 0);
+    const float st0 = (sl < 10) ? ps[0] : 0.f, st1 = (sl < 10) ? ps[10] : 0.f, st2 = (sl < 10) ? ps[20] : 0.f;
+    float vp[3];
+    vp[0] = row_sum(s0) + (a.vt[(size_t)vi * 3] + row_sum(st0 * beta_s));
+    vp[1] = row_sum(s1) + (a.vt[(size_t)vi * 3 + 1] + row_sum(st1 * beta_s));
+    vp[2] = row_sum(s2) + (a.vt[(size_t)vi * 3 + 2] + row_sum(st2 * beta_s));
+    const int4 wi = *reinterpret_cast<const int4*>(a.Wi + (size_t)vi * 4);
+    const float4 w4 = *reinterpret_cast<const float4*>(a.Ww + (size_t)vi * 4);
+    const int wj[4] = {wi.x, wi.y, wi.z, wi.w};
+    const float ww[4] = {w4.x, w4.y, w4.z, w4.w};
+    float T8 = 0.f, T9 = 0.f, T10 = 0.f, T11 = 0.f;  // the z row of the blended transform
+#pragma unroll
+    for (int n = 0; n < 4; ++n) {
+      const float4 r2 = reinterpret_cast<const float4*>(sA + wj[n] * 12)[2];
+      T8 = fmaf(ww[n], r2.x, T8); T9 = fmaf(ww[n], r2.y, T9); T10 = fmaf(ww[n], r2.z, T10); T11 = fmaf(ww[n], r2.w, T11);
+    }
+    const float vz = fmaf(T10, vp[2], fmaf(T9, vp[1], T8 * vp[0])) + T11 + trz;
+    if (p < K && sl == 0) sz[p] = vz;
+  }
+  __syncthreads();
+  const float c0 = (a.ccon != 0.f) ? a.contacts[(size_t)f * 2] : 0.f, c1 = (a.ccon != 0.f) ? a.contacts[(size_t)f * 2 + 1] : 0.f;
+  if (lane < K) {
+    const int p = lane, foot = (p < a.KL) ? 0 : 1;
+    const int lo = foot ? a.KL : 0, hi = foot ? K : a.KL;
+    int am = lo;
+    float zm = sz[lo];
+    for (int q = lo + 1; q < hi; ++q) {
+      const float zq = sz[q];
+      if (zq < zm) {
+        zm = zq;
+        am = q;
+      }
+    }
+    const float pen = fmaxf(a.h - sz[p], 0.f), flo = fmaxf(zm - a.h, 0.f), c = foot ? c1 : c0;
+    float dz = -2.f * a.cpen * pen;
+    if (p == am) dz += 2.f * a.ccon * c * flo;
+    float* pu = a.up + ((size_t)f * K + p) * 3;
+    pu[0] = 0.f;
+    pu[1] = 0.f;
+    pu[2] = dz;
+  }
+  if (lane == 0) {  // the frame's share, in a fixed order
+    float sp = 0.f, zl = sz[0], zr = sz[a.KL];
+    for (int p = 0; p < K; ++p) {
+      const float pen = fmaxf(a.h - sz[p], 0.f);
+      sp += pen * pen;
+      if (p < a.KL) zl = fminf(zl, sz[p]);
+      else zr = fminf(zr, sz[p]);
+    }
+    const float fl0 = fmaxf(zl - a.h, 0.f), fl1 = fmaxf(zr - a.h, 0.f);
+    a.loss[f] = a.cpen * sp + a.ccon * (c0 * (fl0 * fl0) + c1 * (fl1 * fl1));
+  }
+}
+
+// ----------------------------------------------------------------------------------------------------
+// EXTENSION (not reference behaviour; uuo_fit_set_capsules): a bone-capsule self-penetration term.  Capsule c = (u, v, alpha,
+// beta, r): end points a = J_u + alpha (J_v - J_u), b = J_u + beta (J_v - J_u) on the line through two world joints J = G_j^t
+// (no translation: the term is translation invariant), radius r.  For every pair k = (i, j) of the list:
+//   (s, t) = closest-point parameters of the segments [a_i, b_i], [a_j, b_j] (Ericson, Real-Time Collision Detection 5.1.9;
+//            capsule_closest below, degenerate when |d|^2 <= 1e-12, parallel when den <= 1e-6 A E)
+//   delta = c_i - c_j,  d = |delta|,  pen = max(r_i + r_j - d, 0),  loss += w pen^2 / F,
+//   dL/dc_i = -(2 w / F) pen delta / d = -dL/dc_j   (s, t held fixed: envelope theorem; d = 0: no gradient, pen^2 still counts)
+//   gamma_i = alpha_i + s (beta_i - alpha_i):  dL/dJ_{u_i} += (1 - gamma_i) dL/dc_i,  dL/dJ_{v_i} += gamma_i dL/dc_i  (same for j).
+// k_capsule_fwd: one wave per frame.  It reads the 24 G^t of the frame's FrameLds (as the closure's forward or k_pose_prep left
+// them), forms the <= 32 capsules' end points in LDS, evaluates the <= 256 pairs (pair k on lane k % 64, up to four per lane) and
+// parks the four end joints' shares of each pair's gradient -- (1 - gamma_i) dL/dc_i, gamma_i dL/dc_i, -(1 - gamma_j) dL/dc_i,
+// -gamma_j dL/dc_i -- in LDS.  The 72 (joint, component) outputs -- lanes 0..63, then lanes 0..7 once more -- are summed over the
+// joint's rows of the host-built CSR table, which lists (pair, end) in pair order and, inside a pair, in the order u_i, v_i, u_j,
+// v_j.  The frame's sum of pen^2: every lane adds its own pairs in order, then a fixed xor butterfly (32, 16, .. 1) adds the
+// lanes.  The table and the geometry are fetched into LDS once, beside G^t: one global round trip.  No atomics: bit-reproducible.
+// ----------------------------------------------------------------------------------------------------
+#define UUO_CAPS_MAXC 32
+#define UUO_CAPS_MAXP 256
+#define UUO_CAPS_TAB_PAIRS (UUO_CAPS_MAXC * 2)                       // cap_tab layout (ints): joints, pairs, CSR offsets, CSR entries
+#define UUO_CAPS_TAB_OFF (UUO_CAPS_TAB_PAIRS + UUO_CAPS_MAXP * 2)
+#define UUO_CAPS_TAB_ENT (UUO_CAPS_TAB_OFF + UUO_NUM_JOINTS + 1)
+#define UUO_CAPS_TAB_INTS (UUO_CAPS_TAB_ENT + UUO_CAPS_MAXP * 4)
+struct CapsFwdArgs {
+  uuo_gptr<const float> frames;  // [F][FrameLds]
+  uuo_gptr<const int> tab;       // the workspace's table (layout above)
+  uuo_gptr<const float> geom;    // [C][3] alpha, beta, radius
+  int C, P;
+  float cl, cg;                  // w / F, 2 w / F
+  uuo_gptr<float> up;            // [F][24][3] out
+  uuo_gptr<float> loss;          // [F] out
+};
+__device__ __forceinline__ float clamp01(float v) { return fminf(fmaxf(v, 0.f), 1.f); }
+// closest-point parameters of the segments p1 + s d1, p2 + t d2 (s, t in [0, 1]); r = p1 - p2
+struct CapsVec { float x, y, z; };
+__device__ __forceinline__ float caps_dot(CapsVec a, CapsVec b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+__device__ __forceinline__ float2 capsule_closest(CapsVec d1, CapsVec d2, CapsVec r) {
+  const float A = caps_dot(d1, d1), E = caps_dot(d2, d2);
+  const float fq = caps_dot(d2, r), cq = caps_dot(d1, r), bq = caps_dot(d1, d2);
+  const bool dA = A <= 1e-12f, dE = E <= 1e-12f;
+  if (dA && dE) return make_float2(0.f, 0.f);
+  if (dA) return make_float2(0.f, clamp01(fq / E));
+  if (dE) return make_float2(clamp01(-cq / A), 0.f);
+  const float den = A * E - bq * bq;
+  float s = (den > 1e-6f * (A * E)) ? clamp01((bq * fq - cq * E) / den) : 0.f;
+  float t = (bq * s + fq) / E;
+  if (t < 0.f) {
+    t = 0.f;
+    s = clamp01(-cq / A);
+  } else if (t > 1.f) {
+    t = 1.f;
+    s = clamp01((bq - cq) / A);
+  }
+  return make_float2(s, t);
+}
+__global__ __launch_bounds__(64) void k_capsule_fwd(CapsFwdArgs a) {
+  __shared__ float sG[UUO_NUM_JOINTS * 3];
+  __shared__ int sTab[UUO_CAPS_TAB_INTS];           // the workspace's table: one coalesced fetch, every lookup below is LDS
+  __shared__ float sGeom[UUO_CAPS_MAXC * 3];
+  __shared__ float sEnd[UUO_CAPS_MAXC][6];          // a, b of every capsule
+  __shared__ float sCon[UUO_CAPS_MAXP * 4][3];      // per (pair, end): that end joint's share of dL/dc, signed
+  const int f = blockIdx.x, lane = threadIdx.x;
+  const int C = min(a.C, UUO_CAPS_MAXC), P = min(a.P, UUO_CAPS_MAXP);  // (uuo_fit_set_capsules has checked them; keeps LDS in bounds)
+  {
+    constexpr int NW = sizeof(FrameLds) / 4, GT = offsetof(FrameLds, Gt) / 4;
+    for (int i = lane; i < UUO_NUM_JOINTS * 3; i += 64) sG[i] = a.frames[(size_t)f * NW + GT + i];
+    for (int i = lane; i < UUO_CAPS_TAB_INTS; i += 64) sTab[i] = a.tab[i];
+    for (int i = lane; i < UUO_CAPS_MAXC * 3; i += 64) sGeom[i] = a.geom[i];
+  }
+  __syncthreads();
+  if (lane < C) {
+    const int u = sTab[lane * 2] % UUO_NUM_JOINTS, v = sTab[lane * 2 + 1] % UUO_NUM_JOINTS;
+    const float al = sGeom[lane * 3], be = sGeom[lane * 3 + 1];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float ju = sG[u * 3 + c], e = sG[v * 3 + c] - ju;
+      sEnd[lane][c] = ju + al * e;
+      sEnd[lane][3 + c] = ju + be * e;
+    }
+  }
+  __syncthreads();
+  float part = 0.f;  // this lane's pen^2, pairs lane, lane + 64, ... in that order
+  for (int k = lane; k < P; k += 64) {
+    const int i = sTab[UUO_CAPS_TAB_PAIRS + k * 2] % UUO_CAPS_MAXC, j = sTab[UUO_CAPS_TAB_PAIRS + k * 2 + 1] % UUO_CAPS_MAXC;
+    const CapsVec p1 = {sEnd[i][0], sEnd[i][1], sEnd[i][2]}, p2 = {sEnd[j][0], sEnd[j][1], sEnd[j][2]};
+    const CapsVec d1 = {sEnd[i][3] - p1.x, sEnd[i][4] - p1.y, sEnd[i][5] - p1.z};
+    const CapsVec d2 = {sEnd[j][3] - p2.x, sEnd[j][4] - p2.y, sEnd[j][5] - p2.z};
+    const CapsVec r = {p1.x - p2.x, p1.y - p2.y, p1.z - p2.z};
+    const float2 st = capsule_closest(d1, d2, r);
+    const float s = st.x, t = st.y;
+    const CapsVec dl = {(p1.x + s * d1.x) - (p2.x + t * d2.x), (p1.y + s * d1.y) - (p2.y + t * d2.y), (p1.z + s * d1.z) - (p2.z + t * d2.z)};
+    const float d = sqrtf(caps_dot(dl, dl));
+    const float pen = fmaxf((sGeom[i * 3 + 2] + sGeom[j * 3 + 2]) - d, 0.f);
+    const float q = (d > 0.f) ? -(a.cg * pen) / d : 0.f;
+    const float g[3] = {q * dl.x, q * dl.y, q * dl.z};  // dL/dc_i = -dL/dc_j
+    const float ai = sGeom[i * 3], aj = sGeom[j * 3];
+    const float gi = ai + s * (sGeom[i * 3 + 1] - ai), gj = aj + t * (sGeom[j * 3 + 1] - aj);
+    const float co[4] = {1.f - gi, gi, 1.f - gj, gj};   // ends u_i, v_i, u_j, v_j
+#pragma unroll
+    for (int end = 0; end < 4; ++end)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) sCon[k * 4 + end][c] = co[end] * ((end & 2) ? -g[c] : g[c]);
+    part += pen * pen;
+  }
+  __syncthreads();
+  for (int o = lane; o < UUO_NUM_JOINTS * 3; o += 64) {
+    const int jj = o / 3, c = o - jj * 3;
+    const int e0 = max(sTab[UUO_CAPS_TAB_OFF + jj], 0), e1 = min(sTab[UUO_CAPS_TAB_OFF + jj + 1], 4 * P);
+    float acc = 0.f;
+    for (int e = e0; e < e1; e += 4) {  // four rows a step: the LDS reads overlap, the adds keep the rows' (= the pairs') order
+      float v[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int ent = (e + u < e1) ? sTab[UUO_CAPS_TAB_ENT + e + u] : -1;
+        v[u] = (ent >= 0) ? sCon[ent % (UUO_CAPS_MAXP * 4)][c] : 0.f;
+      }
+      acc = (((acc + v[0]) + v[1]) + v[2]) + v[3];
+    }
+    a.up[(size_t)f * 72 + o] = acc;
+  }
+  // the frame's share: the lanes' partial sums (each in pair order) through a fixed butterfly, lane l with lane l ^ 32, 16, .. 1
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) part += __shfl_xor(part, m, 64);
+  if (lane == 0) a.loss[f] = a.cl * part;
+}
+
+// ----------------------------------------------------------------------------------------------------
+// EXTENSION (not reference behaviour; uuo_fit_set_joint_limits): a joint-angle limit term on the body pose.  Body joint
+// j = 1 .. 23, R its local rotation as frame_forward forms it (gs6d_forward of the raw entries when the stage normalises, the raw
+// entries otherwise: the same function on the same inputs, so R is bit for bit the forward's), row-major:
+//   s = 1/2 (R21 - R12, R02 - R20, R10 - R01),  c = 1/2 (R00 + R11 + R22 - 1),  n = |s|,  theta = atan2(n, c),  kappa = theta / n,
+//   omega = kappa s;   n < 1e-4: c >= 0 takes kappa = 1, d kappa = 0 (identity), c < 0 contributes nothing (half turn: no axis)
+//   pen_k = max(omega_k - hi_k, 0) + max(lo_k - omega_k, 0),  loss += w pen_k^2 / F,
+//   g_k = dL/d omega_k = (2 w / F) (max(omega_k - hi_k, 0) - max(lo_k - omega_k, 0)),  q = s . g,
+//   dL/ds = kappa g + q (d kappa / dn) s / n,  dL/dc = q d kappa / dc,
+//   d kappa / dn = c / (n (n^2 + c^2)) - theta / n^2,  d kappa / dc = -1 / (n^2 + c^2),
+//   dL/dR21 += 1/2 dL/ds_x, dL/dR12 -= 1/2 dL/ds_x, ... (cyclic),  dL/dR_kk += 1/2 dL/dc.
+// k_limit_fwd: 32 lanes per frame, two frames per 64-thread block (a frame has 23 joints: a wave per frame would leave 41 lanes
+// idle; F odd leaves the last block's upper half idle).  Lane l < 23 of a half takes joint l + 1: raw entries and the six bounds
+// in one round trip, R, omega, the hinges, dL/dR, and the stage's normalisation backward (gs6d_backward) on its own raw entries:
+// it writes the gradient in PARAMETER space, [F][23][9], third rows exact zeros when the stage normalises.  The frame's 69
+// squares: every lane adds its three in the order x, y, z, then a fixed xor butterfly (16, 8, .. 1) inside the half adds the
+// lanes (lanes 23 .. 31 hold zeros).  No atomics, no LDS: bit-reproducible.
+// ----------------------------------------------------------------------------------------------------
+#define UUO_LIM_FPB 2  // frames per block
+struct LimitFwdArgs {
+  uuo_gptr<const float> body;  // [F][23][9] raw body pose entries (UuoPoseSrc.body)
+  uuo_gptr<const float> tab;   // [2][23][3] lo, hi
+  int F, norm_body;
+  float cl, cg;                // w / F, 2 w / F
+  uuo_gptr<float> g;           // [F][23][9] out
+  uuo_gptr<float> loss;        // [F] out
+};
+__global__ __launch_bounds__(64) void k_limit_fwd(LimitFwdArgs a) {
+  const int half = threadIdx.x >> 5, l = threadIdx.x & 31;
+  const int f = blockIdx.x * UUO_LIM_FPB + half;
+  const bool on = f < a.F && l < 23;
+  float raw[9], lo[3], hi[3];
+#pragma unroll
+  for (int e = 0; e < 9; ++e) raw[e] = on ? a.body[((size_t)f * 23 + l) * 9 + e] : ((e == 0 || e == 4 || e == 8) ? 1.f : 0.f);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    lo[k] = on ? a.tab[l * 3 + k] : -INFINITY;
+    hi[k] = on ? a.tab[69 + l * 3 + k] : INFINITY;
+  }
+  float R[9];
+  if (a.norm_body) {
+    gs6d_forward(raw, R);
+  } else {
+#pragma unroll
+    for (int e = 0; e < 9; ++e) R[e] = raw[e];
+  }
+  const float s[3] = {0.5f * (R[7] - R[5]), 0.5f * (R[2] - R[6]), 0.5f * (R[3] - R[1])};
+  const float c = 0.5f * (((R[0] + R[4]) + R[8]) - 1.f);
+  const float n2 = (s[0] * s[0] + s[1] * s[1]) + s[2] * s[2];
+  const float n = sqrtf(n2);
+  const bool small = n < 1e-4f;
+  const bool skip = small && c < 0.f;
+  const float nn = small ? 1.f : n;  // (keeps the quotients of the unused branch finite)
+  const float theta = atan2f(n, c);
+  const float kappa = small ? 1.f : theta / nn;
+  const float den = small ? 1.f : n2 + c * c;
+  const float dkn = small ? 0.f : (c / (nn * den) - theta / (nn * nn));
+  const float dkc = small ? 0.f : (-1.f / den);
+  float g[3], part = 0.f;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float om = kappa * s[k];
+    const float up = fmaxf(om - hi[k], 0.f), dn = fmaxf(lo[k] - om, 0.f);
+    const float pen = (skip || !on) ? 0.f : up + dn;
+    g[k] = (skip || !on) ? 0.f : a.cg * (up - dn);
+    part += pen * pen;
+  }
+  const float q = (s[0] * g[0] + s[1] * g[1]) + s[2] * g[2];
+  const float qn = q * dkn / nn;
+  const float ds[3] = {0.5f * (kappa * g[0] + qn * s[0]), 0.5f * (kappa * g[1] + qn * s[1]), 0.5f * (kappa * g[2] + qn * s[2])};
+  const float dc = 0.5f * (q * dkc);
+  const float dR[9] = {dc, -ds[2], ds[1], ds[2], dc, -ds[0], -ds[1], ds[0], dc};
+  float out[9];
+  if (a.norm_body) {
+    float da[6];
+    gs6d_backward(raw, dR, da);
+#pragma unroll
+    for (int e = 0; e < 6; ++e) out[e] = da[e];
+    out[6] = out[7] = out[8] = 0.f;
+  } else {
+#pragma unroll
+    for (int e = 0; e < 9; ++e) out[e] = dR[e];
+  }
+  if (on) {
+#pragma unroll
+    for (int e = 0; e < 9; ++e) a.g[((size_t)f * 23 + l) * 9 + e] = out[e];
+  }
+  // the frame's share: the lanes' sums (each x, y, z in order) through a fixed butterfly inside the 32-lane half
+#pragma unroll
+  for (int m = 16; m >= 1; m >>= 1) part += __shfl_xor(part, m, 64);
+  if (l == 0 && f < a.F) a.loss[f] = a.cl * part;
+}
+
+// ----------------------------------------------------------------------------------------------------
+// EXTENSION (not reference behaviour; uuo_fit_set_prior_weights): the pose prior of the chamfer and marker stages with a weight
+// per (frame, body joint), w[t][j] >= 0:
+//   loss += c sum_t sum_j w[t][j] sum_e (raw[t][j][e] - o[t][j][e])^2,   c = w_pose / (F 207)   (the normaliser of the uniform
+//   prior, not sum w: w == 1 everywhere is the uniform term),   dL/d raw[t][j][e] = 2 c w[t][j] (raw - o).
+// k_prior_conf delivers the WHOLE prior -- the backward kernels and the finalize then run with a pose coefficient of 0 -- through
+// the buffer of the joint-angle limit term, [F][23][9] gradients in parameter space and [F] shares behind them, which the
+// temporal instantiations add to gout and to slot 3 (lim_g != null): no existing kernel changes.  add == 0: it writes the buffer;
+// add != 0 (the limit term is on, k_limit_fwd of this evaluation ran before it on the same stream): it adds to it.
+// The shape of k_limit_fwd: 32 lanes per frame, two frames per 64-thread block.  Lane l < 23 of a half takes joint l + 1: its
+// nine raw entries, nine targets, its weight (and with add its nine old gradients; lane 0 the old share) in one round trip -- the
+// 23 lanes of a half read 207 consecutive floats of each table.  A weight of 0 stores exact +0 (not 0 * diff), a row on its
+// target 2 c w * 0 = 0: third rows on their targets stay exact zeros, as the compact packing needs.  The frame's share: every lane
+// sums its nine squares in the order e = 0 .. 8 and weighs the sum, then a fixed xor butterfly (16, 8, .. 1) inside the half adds
+// the lanes (lanes 23 .. 31 hold zeros).  No atomics, no LDS: bit-reproducible.
+// ----------------------------------------------------------------------------------------------------
+struct PriorConfArgs {
+  uuo_gptr<const float> body;    // [F][23][9] raw body pose entries (the optimised parameters)
+  uuo_gptr<const float> target;  // [F][23][9] the prior's target (uuo_problem_t.d_o_pose)
+  uuo_gptr<const float> w;       // [F][23] weights
+  int F, add;
+  float cl, cg;                  // w_pose / (F 207), 2 w_pose / (F 207)
+  uuo_gptr<float> g;             // [F][23][9] gradients, then [F] shares: written (add == 0) or added to
+};
+__global__ __launch_bounds__(64) void k_prior_conf(PriorConfArgs a) {
+  const int half = threadIdx.x >> 5, l = threadIdx.x & 31;
+  const int f = blockIdx.x * UUO_LIM_FPB + half;
+  const bool on = f < a.F && l < 23;
+  const size_t row = on ? ((size_t)f * 23 + l) * 9 : 0;
+  float raw[9], tg[9], old[9];
+#pragma unroll
+  for (int e = 0; e < 9; ++e) {
+    raw[e] = on ? a.body[row + e] : 0.f;
+    tg[e] = on ? a.target[row + e] : 0.f;
+    old[e] = (on && a.add) ? a.g[row + e] : 0.f;
+  }
+  const float w = on ? a.w[(size_t)f * 23 + l] : 0.f;
+  const bool head = l == 0 && f < a.F;
+  const float old_share = (head && a.add) ? a.g[(size_t)a.F * 207 + f] : 0.f;
+  const float wc = a.cg * w;
+  float sq = 0.f, out[9];
+#pragma unroll
+  for (int e = 0; e < 9; ++e) {
+    const float diff = raw[e] - tg[e];
+    out[e] = old[e] + ((w == 0.f) ? 0.f : wc * diff);
+    sq = fmaf(diff, diff, sq);
+  }
+  if (on) {
+#pragma unroll
+    for (int e = 0; e < 9; ++e) a.g[row + e] = out[e];
+  }
+  float part = (w == 0.f) ? 0.f : w * sq;
+#pragma unroll
+  for (int m = 16; m >= 1; m >>= 1) part += __shfl_xor(part, m, 64);
+  if (head) a.g[(size_t)a.F * 207 + f] = old_share + a.cl * part;
+}
+
+// The side terms that are on, in this order on stream s, once the frames' FrameLds of this evaluation are there.
+void uuo_launch_side_terms(uuo_fit* fit, hipStream_t s, int F, const UuoPoseSrc& src, const float* d_pose, const float* d_o_pose,
+                           float w_pose, UuoSideTerms on) {
+  const uuo_model* m = fit->model;
+  if (on.floor) {
+    FloorFwdArgs b;
+    std::memset(&b, 0, sizeof(b));
+    b.PT = m->PT; b.ST = m->ST; b.vt = m->vt; b.Ww = m->Ww; b.Wi = m->Wi;
+    b.V = m->V; b.F = F; b.K = fit->floor_k; b.KL = fit->floor_kl;
+    b.frames = fit->frames;
+    b.trans = src.trans;
+    b.vids = fit->floor_vids;
+    b.contacts = fit->floor_contacts;
+    b.h = fit->floor_height;
+    b.cpen = (float)((double)fit->floor_pen / ((double)F * (double)fit->floor_k));
+    b.ccon = (float)((double)fit->floor_con / (2.0 * (double)F));
+    b.up = fit->floor_up;
+    b.loss = fit->floor_up + (size_t)F * UUO_FLOOR_MAXK * 3;
+    hipLaunchKernelGGL(k_floor_fwd, dim3(F), dim3(64), 0, s, b);
+  }
+  if (on.caps) {
+    CapsFwdArgs b;
+    std::memset(&b, 0, sizeof(b));
+    b.frames = fit->frames;
+    b.tab = fit->cap_tab;
+    b.geom = fit->cap_geom;
+    b.C = fit->cap_c; b.P = fit->cap_p;
+    b.cl = (float)((double)fit->cap_w / (double)F);
+    b.cg = (float)(2.0 * (double)fit->cap_w / (double)F);
+    b.up = fit->cap_up;
+    b.loss = fit->cap_up + (size_t)F * 72;
+    hipLaunchKernelGGL(k_capsule_fwd, dim3(F), dim3(64), 0, s, b);
+    fit->cap_launched = true;  // (uuo_fit_set_capsules waits for this stream before it replaces the tables)
+    fit->cap_last_stream = s;
+  }
+  if (on.limits) {
+    LimitFwdArgs b;
+    std::memset(&b, 0, sizeof(b));
+    b.body = src.body;
+    b.tab = fit->lim_tab;
+    b.F = F;
+    b.norm_body = src.norm_body;
+    b.cl = (float)((double)fit->lim_w / (double)F);
+    b.cg = (float)(2.0 * (double)fit->lim_w / (double)F);
+    b.g = fit->lim_g;
+    b.loss = fit->lim_g + (size_t)F * 207;
+    hipLaunchKernelGGL(k_limit_fwd, dim3((F + UUO_LIM_FPB - 1) / UUO_LIM_FPB), dim3(64), 0, s, b);
+    fit->lim_launched = true;  // (uuo_fit_set_joint_limits waits for this stream before it replaces the table)
+    fit->lim_last_stream = s;
+  }
+  if (on.prior) {
+    PriorConfArgs b;
+    std::memset(&b, 0, sizeof(b));
+    b.body = d_pose;
+    b.target = d_o_pose;
+    b.w = fit->prior_w;
+    b.F = F;
+    b.add = on.limits ? 1 : 0;
+    b.cl = (float)((double)w_pose / ((double)F * 207.0));
+    b.cg = (float)(2.0 * (double)w_pose / ((double)F * 207.0));
+    b.g = fit->lim_g;
+    hipLaunchKernelGGL(k_prior_conf, dim3((F + UUO_LIM_FPB - 1) / UUO_LIM_FPB), dim3(64), 0, s, b);
+  }
+}
+
+extern "C" int uuo_fit_set_foot_lock(uuo_fit_t* fit, float w, const float* d_contacts) {
+  UUO_REQUIRE(fit, "uuo_fit_set_foot_lock: null fit");
+  UUO_REQUIRE(w == 0.f || (w > 0.f && w <= 3.0e38f), "uuo_fit_set_foot_lock: the weight must be 0 (off) or a positive finite number");
+  UUO_REQUIRE(w == 0.f || d_contacts, "uuo_fit_set_foot_lock: a positive weight needs the contact labels [F][2] on the device");
+  UUO_REQUIRE(w == 0.f || !uuo_recorder, "uuo_fit_set_foot_lock: lock-step batches do not carry the foot-lock term");
+  fit->foot_lock = w;
+  fit->foot_contacts = (w == 0.f) ? nullptr : d_contacts;
+  return 0;
+}
+
+extern "C" int uuo_fit_set_floor(uuo_fit_t* fit, float w_pen, float w_con, float height, const int32_t* d_vids, int32_t k_left,
+                                 int32_t k_right, const float* d_contacts) {
+  UUO_REQUIRE(fit, "uuo_fit_set_floor: null fit");
+  UUO_REQUIRE((w_pen == 0.f || (w_pen > 0.f && w_pen <= 3.0e38f)) && (w_con == 0.f || (w_con > 0.f && w_con <= 3.0e38f)),
+              "uuo_fit_set_floor: the weights must be 0 (off) or positive finite numbers");
+  if (w_pen == 0.f && w_con == 0.f) {  // off: nothing else is looked at
+    fit->floor_pen = fit->floor_con = fit->floor_height = 0.f;
+    fit->floor_k = fit->floor_kl = 0;
+    fit->floor_vids = nullptr;
+    fit->floor_contacts = nullptr;
+    return 0;
+  }
+  UUO_REQUIRE(height >= -3.0e38f && height <= 3.0e38f, "uuo_fit_set_floor: the plane height must be a finite number of metres");
+  UUO_REQUIRE(k_left >= 1 && k_right >= 1, "uuo_fit_set_floor: every foot needs at least one sole point");
+  UUO_REQUIRE(k_left + (long long)k_right >= 2 && k_left + (long long)k_right <= UUO_FLOOR_MAXK,
+              "uuo_fit_set_floor: 2 .. 16 sole points (k_left + k_right)");
+  UUO_REQUIRE(d_vids, "uuo_fit_set_floor: the sole points' vertex ids [k_left + k_right] on the device are required");
+  UUO_REQUIRE(w_con == 0.f || d_contacts, "uuo_fit_set_floor: a positive contact weight needs the contact labels [F][2] on the device");
+  UUO_REQUIRE(!uuo_recorder, "uuo_fit_set_floor: lock-step batches do not carry the floor-contact term");
+  const int K = k_left + k_right;
+  int32_t h_vids[UUO_FLOOR_MAXK];
+  UUO_HIP_CHECK(hipMemcpy(h_vids, d_vids, (size_t)K * sizeof(int32_t), hipMemcpyDeviceToHost));
+  for (int k = 0; k < K; ++k)
+    UUO_REQUIRE(h_vids[k] >= 0 && h_vids[k] < fit->model->V, "uuo_fit_set_floor: a sole point's vertex id is outside [0, V)");
+  if (!fit->floor_up)  // [F][16][3] upstream gradients + [F] loss shares (k_floor_fwd -> the backward); first use
+    UUO_HIP_CHECK(hipMalloc((void**)&fit->floor_up, ((size_t)fit->F * UUO_FLOOR_MAXK * 3 + fit->F) * sizeof(float)));
+  fit->floor_pen = w_pen;
+  fit->floor_con = w_con;
+  fit->floor_height = height;
+  fit->floor_k = K;
+  fit->floor_kl = k_left;
+  fit->floor_vids = d_vids;
+  fit->floor_contacts = (w_con == 0.f) ? nullptr : d_contacts;
+  return 0;
+}
+
+extern "C" int uuo_fit_set_capsules(uuo_fit_t* fit, float w, int32_t n_caps, const int32_t* h_cap_joints, const float* h_cap_geom,
+                                    int32_t n_pairs, const int32_t* h_pairs) {
+  UUO_REQUIRE(fit, "uuo_fit_set_capsules: null fit");
+  UUO_REQUIRE(w == 0.f || (w > 0.f && w <= 3.0e38f), "uuo_fit_set_capsules: the weight must be 0 (off) or a positive finite number");
+  if (w == 0.f) {  // off: nothing else is looked at (the tables stay for the next call with the same lists)
+    fit->cap_w = 0.f;
+    return 0;
+  }
+  UUO_REQUIRE(n_caps >= 1 && n_caps <= UUO_CAPS_MAXC, "uuo_fit_set_capsules: 1 .. 32 capsules");
+  UUO_REQUIRE(n_pairs >= 1 && n_pairs <= UUO_CAPS_MAXP, "uuo_fit_set_capsules: 1 .. 256 pairs");
+  UUO_REQUIRE(h_cap_joints && h_cap_geom && h_pairs,
+              "uuo_fit_set_capsules: a positive weight needs the capsules' joints [C][2], geometry [C][3] and the pairs [P][2] (host arrays)");
+  UUO_REQUIRE(!uuo_recorder, "uuo_fit_set_capsules: lock-step batches do not carry the self-penetration term");
+  const int C = n_caps, P = n_pairs;
+  for (int c = 0; c < C; ++c) {
+    const int u = h_cap_joints[c * 2], v = h_cap_joints[c * 2 + 1];
+    UUO_REQUIRE(u >= 0 && u < UUO_NUM_JOINTS && v >= 0 && v < UUO_NUM_JOINTS, "uuo_fit_set_capsules: a capsule's joint id is outside [0, 24)");
+    UUO_REQUIRE(u != v, "uuo_fit_set_capsules: a capsule needs two different joints");
+    const float al = h_cap_geom[c * 3], be = h_cap_geom[c * 3 + 1], r = h_cap_geom[c * 3 + 2];
+    UUO_REQUIRE(al >= -3.0e38f && al <= 3.0e38f && be >= -3.0e38f && be <= 3.0e38f,
+                "uuo_fit_set_capsules: a capsule's alpha and beta must be finite");
+    UUO_REQUIRE(r > 0.f && r <= 3.0e38f, "uuo_fit_set_capsules: a capsule's radius must be a positive finite number of metres");
+  }
+  for (int k = 0; k < P; ++k) {
+    const int i = h_pairs[k * 2], j = h_pairs[k * 2 + 1];
+    UUO_REQUIRE(i >= 0 && i < C && j >= 0 && j < C, "uuo_fit_set_capsules: a pair's capsule index is outside [0, C)");
+    UUO_REQUIRE(i != j, "uuo_fit_set_capsules: a pair needs two different capsules");
+  }
+  if (!fit->cap_tab) {  // first use: the tables (ints, then the geometry) and the kernel's outputs
+    UUO_HIP_CHECK(hipMalloc((void**)&fit->cap_tab, UUO_CAPS_TAB_INTS * sizeof(int32_t) + UUO_CAPS_MAXC * 3 * sizeof(float)));
+    fit->cap_geom = reinterpret_cast<float*>(fit->cap_tab + UUO_CAPS_TAB_INTS);
+    fit->cap_c = fit->cap_p = 0;
+    UUO_HIP_CHECK(hipStreamCreateWithFlags(&fit->cap_stream, hipStreamNonBlocking));
+  }
+  if (!fit->cap_up) UUO_HIP_CHECK(hipMalloc((void**)&fit->cap_up, ((size_t)fit->F * 72 + fit->F) * sizeof(float)));
+  const bool same = fit->cap_c == C && fit->cap_p == P &&
+                    std::memcmp(fit->cap_h_joints, h_cap_joints, (size_t)C * 2 * sizeof(int32_t)) == 0 &&
+                    std::memcmp(fit->cap_h_geom, h_cap_geom, (size_t)C * 3 * sizeof(float)) == 0 &&
+                    std::memcmp(fit->cap_h_pairs, h_pairs, (size_t)P * 2 * sizeof(int32_t)) == 0;
+  if (!same) {
+    // the joint -> (pair, end) table, CSR: joint jj's rows list 4 k + end in pair order, inside a pair in the order
+    // u_i (end 0), v_i (1), u_j (2), v_j (3) -- the order in which k_capsule_fwd sums
+    static thread_local int32_t h_tab[UUO_CAPS_TAB_INTS];
+    std::memset(h_tab, 0, sizeof(h_tab));
+    std::memcpy(h_tab, h_cap_joints, (size_t)C * 2 * sizeof(int32_t));
+    std::memcpy(h_tab + UUO_CAPS_TAB_PAIRS, h_pairs, (size_t)P * 2 * sizeof(int32_t));
+    int n = 0;
+    for (int jj = 0; jj < UUO_NUM_JOINTS; ++jj) {
+      h_tab[UUO_CAPS_TAB_OFF + jj] = n;
+      for (int k = 0; k < P; ++k)
+        for (int end = 0; end < 4; ++end)
+          if (h_cap_joints[h_pairs[k * 2 + (end >> 1)] * 2 + (end & 1)] == jj) h_tab[UUO_CAPS_TAB_ENT + n++] = 4 * k + end;
+    }
+    h_tab[UUO_CAPS_TAB_OFF + UUO_NUM_JOINTS] = n;  // = 4 P
+    fit->cap_w = 0.f;
+    fit->cap_c = fit->cap_p = 0;
+    // the only reader of the old tables is the last k_capsule_fwd launched on this workspace: wait for its stream alone (no
+    // device-wide wait: other threads' workspaces keep running; nothing is added to an evaluation), upload on the workspace's
+    // own non-blocking stream, and return once the copies have landed, so that every later launch sees them
+    if (fit->cap_launched) UUO_HIP_CHECK(hipStreamSynchronize(fit->cap_last_stream));
+    fit->cap_launched = false;
+    UUO_HIP_CHECK(hipMemcpyAsync(fit->cap_tab, h_tab, sizeof(h_tab), hipMemcpyHostToDevice, fit->cap_stream));
+    float h_geom[UUO_CAPS_MAXC * 3] = {0.f};  // (the kernel fetches the whole table)
+    std::memcpy(h_geom, h_cap_geom, (size_t)C * 3 * sizeof(float));
+    UUO_HIP_CHECK(hipMemcpyAsync(fit->cap_geom, h_geom, sizeof(h_geom), hipMemcpyHostToDevice, fit->cap_stream));
+    UUO_HIP_CHECK(hipStreamSynchronize(fit->cap_stream));
+    std::memcpy(fit->cap_h_joints, h_cap_joints, (size_t)C * 2 * sizeof(int32_t));
+    std::memcpy(fit->cap_h_geom, h_cap_geom, (size_t)C * 3 * sizeof(float));
+    std::memcpy(fit->cap_h_pairs, h_pairs, (size_t)P * 2 * sizeof(int32_t));
+    fit->cap_c = C;
+    fit->cap_p = P;
+  }
+  fit->cap_w = w;
+  return 0;
+}
+
+extern "C" int uuo_fit_set_joint_limits(uuo_fit_t* fit, float w, const float* h_lo, const float* h_hi) {
+  UUO_REQUIRE(fit, "uuo_fit_set_joint_limits: null fit");
+  UUO_REQUIRE(w == 0.f || (w > 0.f && w <= 3.0e38f), "uuo_fit_set_joint_limits: the weight must be 0 (off) or a positive finite number");
+  if (w == 0.f) {  // off: nothing else is looked at (the table stays for the next call with the same bounds)
+    fit->lim_w = 0.f;
+    return 0;
+  }
+  UUO_REQUIRE(h_lo && h_hi, "uuo_fit_set_joint_limits: a positive weight needs the bounds lo [23][3] and hi [23][3] (host arrays)");
+  UUO_REQUIRE(!uuo_recorder, "uuo_fit_set_joint_limits: lock-step batches do not carry the joint-angle limit term");
+  for (int i = 0; i < 69; ++i) {
+    const float lo = h_lo[i], hi = h_hi[i];
+    UUO_REQUIRE(lo == lo && hi == hi, "uuo_fit_set_joint_limits: a bound is NaN");
+    UUO_REQUIRE(lo <= 3.0e38f, "uuo_fit_set_joint_limits: a lower bound of +inf admits no angle (-inf = no bound)");
+    UUO_REQUIRE(hi >= -3.0e38f, "uuo_fit_set_joint_limits: an upper bound of -inf admits no angle (+inf = no bound)");
+    UUO_REQUIRE(lo <= hi, "uuo_fit_set_joint_limits: lo > hi");
+  }
+  if (!fit->lim_tab) {  // first use: the table and the upload stream
+    UUO_HIP_CHECK(hipMalloc((void**)&fit->lim_tab, 2 * 69 * sizeof(float)));
+    fit->lim_have = false;
+    UUO_HIP_CHECK(hipStreamCreateWithFlags(&fit->lim_stream, hipStreamNonBlocking));
+  }
+  if (!fit->lim_g) UUO_HIP_CHECK(hipMalloc((void**)&fit->lim_g, ((size_t)fit->F * 207 + fit->F) * sizeof(float)));
+  const bool same = fit->lim_have && std::memcmp(fit->lim_h, h_lo, 69 * sizeof(float)) == 0 &&
+                    std::memcmp(fit->lim_h + 69, h_hi, 69 * sizeof(float)) == 0;
+  if (!same) {
+    fit->lim_w = 0.f;
+    fit->lim_have = false;
+    // the only reader of the old table is the last k_limit_fwd launched on this workspace: wait for its stream alone (no
+    // device-wide wait: other threads' workspaces keep running; nothing is added to an evaluation), upload on the workspace's
+    // own non-blocking stream, and return once the copy has landed, so that every later launch sees it
+    if (fit->lim_launched) UUO_HIP_CHECK(hipStreamSynchronize(fit->lim_last_stream));
+    fit->lim_launched = false;
+    static thread_local float h_tab[2 * 69];
+    std::memcpy(h_tab, h_lo, 69 * sizeof(float));
+    std::memcpy(h_tab + 69, h_hi, 69 * sizeof(float));
+    UUO_HIP_CHECK(hipMemcpyAsync(fit->lim_tab, h_tab, sizeof(h_tab), hipMemcpyHostToDevice, fit->lim_stream));
+    UUO_HIP_CHECK(hipStreamSynchronize(fit->lim_stream));
+    std::memcpy(fit->lim_h, h_tab, sizeof(h_tab));
+    fit->lim_have = true;
+  }
+  fit->lim_w = w;
+  return 0;
+}
+
+extern "C" int uuo_fit_set_prior_weights(uuo_fit_t* fit, const float* d_weights) {
+  UUO_REQUIRE(fit, "uuo_fit_set_prior_weights: null fit");
+  UUO_REQUIRE(!d_weights || !uuo_recorder, "uuo_fit_set_prior_weights: lock-step batches do not carry the pose prior's weights");
+  // (the buffer k_prior_conf fills is the joint-angle limit term's: [F][23][9] gradients, then [F] shares)
+  if (d_weights && !fit->lim_g) UUO_HIP_CHECK(hipMalloc((void**)&fit->lim_g, ((size_t)fit->F * 207 + fit->F) * sizeof(float)));
+  fit->prior_w = d_weights;
+  return 0;
+}

@@ -318,6 +318,17 @@ int uuo_launch_bwd(const uuo_fit* fit, hipStream_t s, const uuo_problem_t& p, co
 int uuo_launch_finalize(const uuo_fit* fit, hipStream_t s, const uuo_problem_t& p, const float* x, float* grad,
                         float* loss);
 
+// the closures' side terms (side_terms.hip: k_floor_fwd, k_capsule_fwd, k_limit_fwd, k_prior_conf and their setters).  One call
+// per evaluation launches the forward kernels of the terms that are on, in that order on stream s, once fit->frames holds this
+// evaluation's FrameLds; src is the evaluation's pose source, d_pose / d_o_pose / w_pose the raw body pose, its prior target and
+// the prior's weight (the weighted prior only)
+#define UUO_FLOOR_MAXK 16  // sole points of the floor-contact term: fit->floor_up is [F][UUO_FLOOR_MAXK][3], then [F] loss shares
+struct UuoSideTerms {
+  bool floor, caps, limits, prior;
+};
+void uuo_launch_side_terms(uuo_fit* fit, hipStream_t s, int F, const UuoPoseSrc& src, const float* d_pose, const float* d_o_pose,
+                           float w_pose, UuoSideTerms on);
+
 // closure internals shared with the solver (closure.hip)
 int uuo_validate_problem(const uuo_fit* fit, const uuo_problem_t* p);
 int uuo_ensure_mask(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p);

@@ -76,7 +76,11 @@ def test_stage_problems_refuse_bad_keys_before_touching_the_device():
 
 
 def test_routing_flags():
-    from uuo_mocap_amd.optimization import _capsule_fused, _capsules_on, lockstep_supported
+    from uuo_mocap_amd.optimization import lockstep_supported
+    from uuo_mocap_amd.terms import CAPSULES, StageTerms
+
+    _capsules_on = lambda cfg, stage: StageTerms(cfg, stage).on(CAPSULES)
+    _capsule_fused = lambda cfg, stage: StageTerms(cfg, stage).fused(CAPSULES)
 
     plain, caps = _cfg(), _cfg("video_mocap_capsules")
     for stage in ("chamfer", "marker"):

@@ -71,7 +71,11 @@ def test_stage_problems_refuse_bad_keys_before_touching_the_device():
 
 
 def test_routing_flags():
-    from uuo_mocap_amd.optimization import _floor_fused, _floor_on, lockstep_supported
+    from uuo_mocap_amd.optimization import lockstep_supported
+    from uuo_mocap_amd.terms import FLOOR, StageTerms
+
+    _floor_on = lambda cfg, stage: StageTerms(cfg, stage).on(FLOOR)
+    _floor_fused = lambda cfg, stage: StageTerms(cfg, stage).fused(FLOOR)
 
     plain, floor = _cfg(), _cfg("video_mocap_floor")
     for stage in ("chamfer", "marker"):

@@ -75,7 +75,10 @@ def test_foot_lock_in_the_part_stage_is_refused():
 
 
 def test_routing_flags():
-    from uuo_mocap_amd.optimization import _temporal_fused, lockstep_supported
+    from uuo_mocap_amd.optimization import lockstep_supported
+    from uuo_mocap_amd.terms import FOOT_LOCK, JOINT_ACCEL, StageTerms
+
+    _temporal_fused = lambda cfg, stage: all(StageTerms(cfg, stage).fused(t) for t in (JOINT_ACCEL, FOOT_LOCK))  # one switch for both
 
     plain, contact = _cfg(), _cfg("video_mocap_contact")
     for stage in ("chamfer", "marker"):

@@ -89,7 +89,11 @@ def test_stage_problems_refuse_bad_keys_before_touching_the_device():
 
 
 def test_routing_flags():
-    from uuo_mocap_amd.optimization import _limit_fused, _limits_on, lockstep_supported
+    from uuo_mocap_amd.optimization import lockstep_supported
+    from uuo_mocap_amd.terms import LIMITS, StageTerms
+
+    _limits_on = lambda cfg, stage: StageTerms(cfg, stage).on(LIMITS)
+    _limit_fused = lambda cfg, stage: StageTerms(cfg, stage).fused(LIMITS)
 
     plain, lim = _cfg(), _cfg("video_mocap_limits")
     for stage in ("chamfer", "marker"):

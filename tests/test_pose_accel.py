@@ -187,7 +187,15 @@ def test_shipped_config_loads_and_differs_from_its_parent_only_by_the_key():
 
 
 def test_routing_flags():
-    from uuo_mocap_amd.optimization import _composed_pose_accel, _pose_accel_on, lockstep_supported
+    from uuo_mocap_amd.optimization import lockstep_supported
+    from uuo_mocap_amd.terms import POSE_ACCEL, StageTerms
+
+    _pose_accel_on = lambda cfg, stage: StageTerms(cfg, stage).on(POSE_ACCEL)
+
+    def _composed_pose_accel(cfg, stage):  # the term of the composed closures: None when off, else a function of rot_body
+        pair = POSE_ACCEL.composed(StageTerms(cfg, stage)[POSE_ACCEL], cfg["stages"][stage]["losses"], None, None)
+        assert pair is None or pair[0] == "rot_body"
+        return None if pair is None else pair[1]
 
     plain, smooth = _cfg(), _cfg("video_mocap_rotsmooth")
     for stage in ("chamfer", "marker"):

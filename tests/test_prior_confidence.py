@@ -83,7 +83,11 @@ def test_bad_values_raise_before_the_device_is_touched():
 
 
 def test_routing_flags():
-    from uuo_mocap_amd.optimization import _armed_prior_weights, _prior_conf_fused, _prior_conf_on, lockstep_supported
+    from uuo_mocap_amd.optimization import _stage_terms, lockstep_supported
+    from uuo_mocap_amd.terms import PRIOR, StageTerms
+
+    _prior_conf_on = lambda cfg, stage: StageTerms(cfg, stage).on(PRIOR)
+    _armed_prior_weights = lambda cfg, stage, weights, num_frames: _stage_terms(cfg, stage, weights, num_frames).prior_weights
 
     plain, drop = _cfg(), _cfg("video_mocap_dropout")
     half = torch.full((6, 23), 0.5)
@@ -97,6 +101,7 @@ def test_routing_flags():
         with pytest.raises(ValueError, match="prior_weights"):
             _armed_prior_weights(plain, stage, half, 7)
         composed = dict(drop, execution={"prior_conf_fused": False})
+        _prior_conf_fused = lambda cfg, weights: StageTerms(cfg, stage, weights).fused(PRIOR)
         assert _prior_conf_fused(drop, half) and not _prior_conf_fused(composed, half)
         assert _prior_conf_fused(composed, None)                                           # nothing to compose without weights
 

@@ -66,7 +66,10 @@ def test_reference_temporal_terms_stay_refused():
 
 
 def test_routing_flags():
-    from uuo_mocap_amd.optimization import _temporal_fused, lockstep_supported
+    from uuo_mocap_amd.optimization import lockstep_supported
+    from uuo_mocap_amd.terms import FOOT_LOCK, JOINT_ACCEL, StageTerms
+
+    _temporal_fused = lambda cfg, stage: all(StageTerms(cfg, stage).fused(t) for t in (JOINT_ACCEL, FOOT_LOCK))  # one switch for both
 
     plain, smooth = _cfg(), _cfg("video_mocap_smooth")
     for stage in ("chamfer", "marker"):

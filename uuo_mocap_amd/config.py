@@ -63,10 +63,9 @@ def stage_surface(config: Dict):
     soft-assignment term `soft_chamfer` beside it, negative or non-finite weights and negative or non-finite stand-offs."""
     st = config["stages"]["chamfer"]
     losses = st.get("losses") or {}
-    w = losses.get("surface_chamfer", 0.0)
-    w = 0.0 if w is None else float(w)
-    if not math.isfinite(w) or w < 0.0:
-        raise ValueError("stages.chamfer.losses.surface_chamfer must be 0 (off) or a positive weight (got %r)" % (w,))
+    from .terms import _weight  # (the extension terms' one weight check)
+
+    w = _weight(config, "chamfer", "surface_chamfer")
     d0 = st.get("surface_distance", 0.0)
     d0 = 0.0 if d0 is None else float(d0)
     if not math.isfinite(d0) or d0 < 0.0:

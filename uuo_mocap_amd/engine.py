@@ -7,7 +7,6 @@ from __future__ import annotations
 
 import ctypes
 import itertools
-import math
 import threading
 from collections import OrderedDict
 from ctypes import byref, c_float, c_void_p
@@ -19,8 +18,12 @@ import torch
 from . import _lib
 from ._lib import (EVAL_CALLBACK, UUO_STAGE_CHAMFER, UUO_STAGE_MARKER, UUO_STAGE_PART, UuoLbfgsOptions,
                    UuoLbfgsStats, UuoProblem, UuoReprojectionProblem, check)
-from .body_model import CAPSULE_PAIRS_MAX, CAPSULES_MAX, SmplTables
+from . import terms
+from .body_model import SmplTables
 from .config import stage_surface
+from .terms import (FLOOR_MAX_POINTS, check_foot_contacts, check_prior_weights, prior_weight_table, stage_capsules,  # noqa: F401
+                    stage_floor, stage_foot_lock, stage_joint_accel, stage_joint_limits, stage_latent_offsets, stage_pose_accel,
+                    stage_prior_confidence, stage_robust_sigma)  # (re-exported: the terms' parsers live in terms.py)
 
 MARKER_DISTANCE = 0.0095  # reference utils/settings.py:1
 
@@ -162,33 +165,13 @@ def solve_batch(problems, xs, max_iter: int, lr: float = 1.0, tolerance_grad: fl
     assert len(problems) == len(xs) and len(problems) > 0
     p0 = problems[0]
     model = p0.model
-    if any(p.joint_accel != 0.0 for p in problems):
-        raise NotImplementedError("lock-step batches do not carry the joint-acceleration term (joint_accel, extension): "
-                                  "solve such problems one by one")
-    if any(p.problem.w_offsets != 0.0 for p in problems):
-        raise NotImplementedError("lock-step batches do not carry the latent marker offsets (latent_offsets, extension): "
-                                  "solve such problems one by one")
-    if any(p.foot_lock != 0.0 for p in problems):
-        raise NotImplementedError("lock-step batches do not carry the foot-lock term (foot_lock, extension): "
-                                  "solve such problems one by one")
-    if any(getattr(p, "floor_on", False) for p in problems):
-        raise NotImplementedError("lock-step batches do not carry the floor-contact term (floor_penetration / floor_contact, "
-                                  "extension): solve such problems one by one")
-    if any(getattr(p, "capsules_on", False) for p in problems):
-        raise NotImplementedError("lock-step batches do not carry the self-penetration term (self_penetration, extension): "
-                                  "solve such problems one by one")
-    if any(getattr(p, "joint_limits_on", False) for p in problems):
-        raise NotImplementedError("lock-step batches do not carry the joint-angle limit term (joint_limits, extension): "
-                                  "solve such problems one by one")
-    if any(getattr(p, "prior_conf_on", False) for p in problems):
-        raise NotImplementedError("lock-step batches do not carry the pose prior's weights (prior_confidence, extension): "
-                                  "solve such problems one by one")
+    for term in terms.TERMS:  # EXTENSION: what a lock-step batch does not carry
+        if term.flag is not None and any(term.carried_by(p) for p in problems):
+            raise NotImplementedError(terms.batch_refusal_text(term.name, term.label))
     if any(getattr(p, "frame_assign", None) is not None for p in problems):
-        raise NotImplementedError("lock-step batches do not carry the per-frame vertex table (tracklets, extension): "
-                                  "solve such problems one by one")
+        raise NotImplementedError(terms.batch_refusal_text("the per-frame vertex table", "tracklets"))
     if any(getattr(p, "surface", False) for p in problems):
-        raise NotImplementedError("lock-step batches do not carry the point-to-surface chamfer term (surface_chamfer, "
-                                  "extension): solve such problems one by one")
+        raise NotImplementedError(terms.batch_refusal_text("the point-to-surface chamfer term", "surface_chamfer"))
     for p, x in zip(problems, xs):
         assert p.stage == p0.stage and p.F == p0.F and p.M == p0.M and p.model is model
         assert x.is_cuda and x.dtype == torch.float32 and x.numel() == p.n and x.is_contiguous()
@@ -472,6 +455,9 @@ def mesh_closest_points(verts, faces, points):
 _POSE_CACHE_IDS = itertools.count(1)  # unique per PartProblem (thread-safe: itertools.count.__next__ is atomic in CPython)
 
 
+_ARMED = tuple(t for t in terms.TERMS if t.setter is not None)  # EXTENSION: the terms that are settings of a workspace
+
+
 class _StageProblem:
     """One L-BFGS problem of the fit on a flat device vector in the reference's parameter packing."""
 
@@ -506,175 +492,42 @@ class _StageProblem:
         p.marker_distance = MARKER_DISTANCE
         self.problem = p
         self.n = int(self.lib.uuo_problem_num_params(byref(p)))
-        # EXTENSION: weight of the joint-acceleration term (ChamferProblem / MarkerProblem), a setting of the WORKSPACE in
-        # the library (uuo_fit_set_joint_accel): _arm() puts it there before every call that evaluates on it
-        self.joint_accel = 0.0
-        # EXTENSION: weight and contact labels of the foot-lock term (ChamferProblem / MarkerProblem), armed the same way
-        # (uuo_fit_set_foot_lock); _set_foot_lock decides once, at construction, whether the term has anything to act on
-        self.foot_lock = 0.0
-        self.foot_contacts = None
+        # EXTENSION: the terms' state (terms.TERMS: joint_accel, foot_lock, floor_*, cap_*, lim_*, prior_weights), all off.  They
+        # are settings of the WORKSPACE in the library: _arm() puts them there before every call that evaluates on it
+        for term in terms.TERMS:
+            vars(self).update(term.state)
         # EXTENSION: the point-to-surface data term (ChamferProblem) and its stand-off, armed the same way (uuo_fit_set_surface)
         self.surface = False
         self.surface_distance = 0.0
         # EXTENSION: the per-frame vertex table [F, M] int32 of the marker stage's one-hot closure (MarkerProblem), armed the
         # same way (uuo_fit_set_frame_assign); None = the per-column placement
         self.frame_assign = None
-        # EXTENSION: the floor-contact term on sole vertices (ChamferProblem / MarkerProblem), armed the same way
-        # (uuo_fit_set_floor); _set_floor decides once, at construction, which of its two pieces has anything to act on
-        self.floor_pen = 0.0
-        self.floor_con = 0.0
-        self.floor_height = 0.0
-        self.floor_vids = None  # [K] int32 on the device, the left foot's floor_kl points first
-        self.floor_kl = 0
-        self.floor_kr = 0
-        self.floor_contacts = None
-        # EXTENSION: the bone-capsule self-penetration term (ChamferProblem / MarkerProblem), armed the same way
-        # (uuo_fit_set_capsules): weight and the three HOST lists, which the library checks and copies at the call
-        self.cap_w = 0.0
-        self.cap_joints = None  # [C, 2] int32 numpy
-        self.cap_geom = None    # [C, 3] float32 numpy: alpha, beta, radius
-        self.cap_pairs = None   # [P, 2] int32 numpy
-        # EXTENSION: the joint-angle limit term on the body pose (ChamferProblem / MarkerProblem), armed the same way
-        # (uuo_fit_set_joint_limits): weight and the two HOST tables, which the library checks and copies at the call
-        self.lim_w = 0.0
-        self.lim_lo = None  # [23, 3] float32 numpy (row j - 1 is SMPL joint j; -inf = no bound)
-        self.lim_hi = None  # [23, 3] float32 numpy (+inf = no bound)
-        # EXTENSION: per-(frame, joint) weights of the pose prior (ChamferProblem / MarkerProblem), armed the same way
-        # (uuo_fit_set_prior_weights): [F, 23] float32 on the device, which the library reads at every evaluation; None = off
-        self.prior_weights = None
 
-    @property
-    def prior_conf_on(self) -> bool:
-        """EXTENSION: True when this problem arms per-(frame, joint) weights of the pose prior."""
-        return self.prior_weights is not None
+    # EXTENSION: True when this problem arms the term (terms.Term.flag)
+    floor_on = property(lambda self: self.floor_pen != 0.0 or self.floor_con != 0.0)
+    capsules_on = property(lambda self: self.cap_w != 0.0)
+    joint_limits_on = property(lambda self: self.lim_w != 0.0)
+    prior_conf_on = property(lambda self: self.prior_weights is not None)
 
-    def _set_prior_weights(self, weights):
-        """EXTENSION: `weights` is check_prior_weights' host tensor (or None).  None, or a table that is 1 everywhere, arms
-        nothing: the problem runs the plain kernels, bit for bit (as foot-lock labels that gate nothing do)."""
-        if weights is None or bool((weights == 1.0).all()):
-            return
-        self.prior_weights = weights.to(device=self.device, dtype=torch.float32).contiguous()
-
-    @property
-    def joint_limits_on(self) -> bool:
-        """EXTENSION: True when this problem arms the joint-angle limit term with a non-zero weight."""
-        return self.lim_w != 0.0
-
-    def _set_joint_limits(self, lim: Dict):
-        """EXTENSION: `lim` is stage_joint_limits' record.  Keeps the weight and contiguous host copies of the two tables (the
-        configured ones, or body_model.smpl_joint_limits(), looked at only when the term is on without a `joint_limits` block).
-        With weight 0 nothing is armed and the problem runs the plain kernels, bit for bit."""
-        w = float(lim["w"])
-        if w == 0.0:
-            return
-        tabs = lim["limits"]
-        if tabs is None:
-            from .body_model import smpl_joint_limits
-
-            lo, hi = smpl_joint_limits()
-        else:
-            lo, hi = tabs["lo"], tabs["hi"]
-        self.lim_lo = np.ascontiguousarray(np.asarray(lo, dtype=np.float32).reshape(23, 3))
-        self.lim_hi = np.ascontiguousarray(np.asarray(hi, dtype=np.float32).reshape(23, 3))
-        self.lim_w = w
-
-    @property
-    def capsules_on(self) -> bool:
-        """EXTENSION: True when this problem arms the self-penetration term with a non-zero weight."""
-        return self.cap_w != 0.0
-
-    def _set_capsules(self, caps: Dict, smpl_inference):
-        """EXTENSION: `caps` is stage_capsules' record.  Keeps the weight and contiguous host copies of the capsule lists (the
-        configured ones, or body_model.body_capsules of `smpl_inference.tables`, looked at only when the term is on without
-        a `capsules` block).  With weight 0 nothing is armed and the problem runs the plain kernels, bit for bit."""
-        w = float(caps["w"])
-        if w == 0.0:
-            return
-        lists = caps["capsules"]
-        if lists is None:
-            from .body_model import body_capsules
-
-            lists = body_capsules(smpl_inference.tables)
-        else:
-            lists = (lists["joints"], lists["geom"], lists["pairs"])
-        self.cap_joints = np.ascontiguousarray(np.asarray(lists[0], dtype=np.int32).reshape(-1, 2))
-        self.cap_geom = np.ascontiguousarray(np.asarray(lists[1], dtype=np.float32).reshape(-1, 3))
-        self.cap_pairs = np.ascontiguousarray(np.asarray(lists[2], dtype=np.int32).reshape(-1, 2))
-        self.cap_w = w
-
-    @property
-    def floor_on(self) -> bool:
-        """EXTENSION: True when this problem arms the floor-contact term with a non-zero weight."""
-        return self.floor_pen != 0.0 or self.floor_con != 0.0
-
-    def _set_floor(self, floor: Dict, contacts, smpl_inference):
-        """EXTENSION: `floor` is stage_floor's record.  Keeps the sole points' vertex ids (the configured ones, or
-        body_model.sole_vertices of `smpl_inference.tables`, which is looked at only when the term is on without floor_points) and the contact labels on the device, and the weights the workspace is armed
-        with: floor_penetration as configured (it needs no labels); floor_contact when the labels hold at least one contact,
-        else 0.  With both 0 nothing is armed and the problem runs the plain kernels, bit for bit."""
-        w_pen, w_con = float(floor["w_pen"]), float(floor["w_con"])
-        if contacts is None or not bool(contacts.any()):
-            w_con = 0.0
-        if w_pen == 0.0 and w_con == 0.0:
-            return
-        points = floor["points"]
-        if points is None:
-            from .body_model import sole_vertices
-
-            points = [[int(v) for v in row] for row in sole_vertices(smpl_inference.tables)]
-        vids = [int(v) for v in points[0]] + [int(v) for v in points[1]]
-        if max(vids) >= self.model.V:
-            raise ValueError("floor_points: a vertex id is past the model's %d vertices" % self.model.V)
-        self.floor_vids = torch.tensor(vids, dtype=torch.int32, device=self.device)
-        self.floor_kl, self.floor_kr = len(points[0]), len(points[1])
-        self.floor_pen, self.floor_con, self.floor_height = w_pen, w_con, float(floor["height"])
-        if w_con != 0.0:
-            self.floor_contacts = contacts.to(device=self.device, dtype=torch.float32).contiguous()
-
-    def _set_foot_lock(self, w: float, contacts):
-        """EXTENSION: keeps a contiguous float32 device copy of the checked contact labels and the weight the workspace is
-        armed with: `w` when the labels gate at least one (frame pair, foot), else 0 -- a capture without video contacts (no
-        labels, or none that holds over two consecutive frames) runs the plain kernels, bit for bit."""
-        if contacts is None:
-            return
-        self.foot_contacts = contacts.to(device=self.device, dtype=torch.float32).contiguous()
-        if w > 0.0 and self.F >= 2 and bool((contacts[1:] * contacts[:-1]).any()):
-            self.foot_lock = float(w)
+    def _set_terms(self, stage_terms, contacts, weights, smpl_inference):
+        """EXTENSION: every term's state from its parsed record, the checked contact labels and prior weights (terms.Term.set)."""
+        for term in terms.TERMS:
+            if term.set is not None:
+                term.set(self, stage_terms[term], contacts, weights, smpl_inference)
 
     def _arm(self):
-        """Sets this problem's joint-acceleration and foot-lock weights (0 without the terms) and its surface term on its workspace.  The workspace
-        is shared by every problem of the same (F, M) on this thread, so this runs right before each library call that
-        evaluates on it."""
-        check(self.lib.uuo_fit_set_joint_accel(self.fit, c_float(self.joint_accel)), "uuo_fit_set_joint_accel")
-        check(self.lib.uuo_fit_set_foot_lock(self.fit, c_float(self.foot_lock),
-                                             self.foot_contacts.data_ptr() if self.foot_lock != 0.0 else None),
-              "uuo_fit_set_foot_lock")
+        """Sets this problem's terms (off without them), its surface term and its per-frame table on its workspace: one library
+        call each, in the order they have always had (joint_accel, foot_lock, surface, per-frame table, floor, capsules, joint
+        limits, prior weights).  The workspace is shared by every problem of the same (F, M) on this thread, so this runs right
+        before each library call that evaluates on it."""
+        for term in _ARMED[:2]:
+            term.arm(self)
         check(self.lib.uuo_fit_set_surface(self.fit, 1 if self.surface else 0, c_float(self.surface_distance)),
               "uuo_fit_set_surface")
         check(self.lib.uuo_fit_set_frame_assign(self.fit, self.frame_assign.data_ptr() if self.frame_assign is not None else None),
               "uuo_fit_set_frame_assign")
-        if self.floor_on:
-            check(self.lib.uuo_fit_set_floor(self.fit, c_float(self.floor_pen), c_float(self.floor_con), c_float(self.floor_height),
-                                             self.floor_vids.data_ptr(), self.floor_kl, self.floor_kr,
-                                             self.floor_contacts.data_ptr() if self.floor_con != 0.0 else None),
-                  "uuo_fit_set_floor")
-        else:
-            check(self.lib.uuo_fit_set_floor(self.fit, c_float(0.0), c_float(0.0), c_float(0.0), None, 0, 0, None),
-                  "uuo_fit_set_floor")
-        if self.capsules_on:
-            check(self.lib.uuo_fit_set_capsules(self.fit, c_float(self.cap_w), int(self.cap_joints.shape[0]),
-                                                self.cap_joints.ctypes.data, self.cap_geom.ctypes.data,
-                                                int(self.cap_pairs.shape[0]), self.cap_pairs.ctypes.data),
-                  "uuo_fit_set_capsules")
-        else:
-            check(self.lib.uuo_fit_set_capsules(self.fit, c_float(0.0), 0, None, None, 0, None), "uuo_fit_set_capsules")
-        if self.joint_limits_on:
-            check(self.lib.uuo_fit_set_joint_limits(self.fit, c_float(self.lim_w), self.lim_lo.ctypes.data, self.lim_hi.ctypes.data),
-                  "uuo_fit_set_joint_limits")
-        else:
-            check(self.lib.uuo_fit_set_joint_limits(self.fit, c_float(0.0), None, None), "uuo_fit_set_joint_limits")
-        check(self.lib.uuo_fit_set_prior_weights(self.fit, self.prior_weights.data_ptr() if self.prior_conf_on else None),
-              "uuo_fit_set_prior_weights")
+        for term in _ARMED[2:]:
+            term.arm(self)
 
     def _need_workspace(self):
         if self.fit is None:  # created for a lock-step batch only: give it the thread's workspace on first standalone use
@@ -844,264 +697,6 @@ class _StageProblem:
         return float(ms.value)
 
 
-def stage_robust_sigma(config: Dict, stage: str) -> float:
-    """EXTENSION: stages.<stage>.robust_sigma (metres) of a config -- the Geman-McClure data term of the stage
-    (uuo_problem_t.robust_sigma).  Absent or 0 = off (the reference's square); negative or non-finite values are refused, and so
-    is a robust term together with the soft-assignment term `soft_chamfer`, which has no robust form."""
-    st = config["stages"][stage]
-    v = st.get("robust_sigma", 0.0)
-    v = 0.0 if v is None else float(v)
-    if not math.isfinite(v) or v < 0.0:
-        raise ValueError("stages.%s.robust_sigma must be 0 (off) or a positive number of metres (got %r)" % (stage, v))
-    if v > 0.0 and float((st.get("losses") or {}).get("soft_chamfer", 0.0)) != 0.0:
-        raise NotImplementedError("stages.%s: robust_sigma (Geman-McClure data term) is not built for the soft-assignment "
-                                  "term soft_chamfer; use one or the other" % stage)
-    return v
-
-
-def stage_joint_accel(config: Dict, stage: str) -> float:
-    """EXTENSION: stages.<stage>.losses.joint_accel of a config -- the weight of the joint-acceleration smoothness term of the
-    chamfer or marker stage (uuo_fit_set_joint_accel), in units of m^2 per frame^2 of the sequence the stage is handed.  Absent
-    or 0 = off; negative or non-finite weights are refused.  (The part stage refuses the key with its other unknown losses.)"""
-    v = (config["stages"][stage].get("losses") or {}).get("joint_accel", 0.0)
-    v = 0.0 if v is None else float(v)
-    if not math.isfinite(v) or v < 0.0:
-        raise ValueError("stages.%s.losses.joint_accel must be 0 (off) or a positive weight (got %r)" % (stage, v))
-    return v
-
-
-def stage_latent_offsets(config: Dict) -> float:
-    """EXTENSION: stages.marker.losses.latent_offsets of a config -- the weight w of the latent per-marker offsets of the marker
-    stage (uuo_problem_t.w_offsets): one rest-space offset per marker column, shared by all frames and skinned with the body,
-    with the prior w (1/M) sum_m (|o_m| - MARKER_DISTANCE)^2.  Absent or 0 = off; negative or non-finite weights are refused.
-    (The chamfer and part stages refuse the key with their other unknown losses.)"""
-    v = (config["stages"]["marker"].get("losses") or {}).get("latent_offsets", 0.0)
-    v = 0.0 if v is None else float(v)
-    if not math.isfinite(v) or v < 0.0:
-        raise ValueError("stages.marker.losses.latent_offsets must be 0 (off) or a positive weight (got %r)" % (v,))
-    return v
-
-
-def stage_foot_lock(config: Dict, stage: str) -> float:
-    """EXTENSION: stages.<stage>.losses.foot_lock of a config -- the weight of the contact-gated foot-lock term of the chamfer
-    or marker stage (uuo_fit_set_foot_lock), in units of m^2 per frame^2 of the sequence the stage is handed.  Absent or 0 =
-    off; negative or non-finite weights are refused.  (The part stage refuses the key with its other unknown losses.)"""
-    v = (config["stages"][stage].get("losses") or {}).get("foot_lock", 0.0)
-    v = 0.0 if v is None else float(v)
-    if not math.isfinite(v) or v < 0.0:
-        raise ValueError("stages.%s.losses.foot_lock must be 0 (off) or a positive weight (got %r)" % (stage, v))
-    return v
-
-
-#: most sole points the floor-contact term takes (uuo_fit_set_floor)
-FLOOR_MAX_POINTS = 16
-
-
-def stage_floor(config: Dict, stage: str) -> Dict:
-    """EXTENSION: the floor-contact term of the chamfer or marker stage (uuo_fit_set_floor) as a config states it --
-    stages.<stage>.losses.floor_penetration and .floor_contact (weights on m^2; absent or 0 = off; negative or non-finite
-    weights are refused), stages.<stage>.floor_height (the plane's z in metres, default 0.0) and stages.<stage>.floor_points
-    (null = body_model.sole_vertices of the model, or [[left vertex ids], [right vertex ids]]: at least one per foot, 2 .. 16 in
-    all; for a real SMPL the heel and toe picks extra_joint_vids[5:11] are a sensible explicit choice).  Returns
-    {"w_pen", "w_con", "height", "points"}.  (The part stage refuses the keys with its other unknown losses.)"""
-    st = config["stages"][stage]
-    losses = st.get("losses") or {}
-    out = {}
-    for key, name in (("w_pen", "floor_penetration"), ("w_con", "floor_contact")):
-        v = losses.get(name, 0.0)
-        v = 0.0 if v is None else float(v)
-        if not math.isfinite(v) or v < 0.0:
-            raise ValueError("stages.%s.losses.%s must be 0 (off) or a positive weight (got %r)" % (stage, name, v))
-        out[key] = v
-    h = st.get("floor_height", 0.0)
-    h = 0.0 if h is None else float(h)
-    if not math.isfinite(h):
-        raise ValueError("stages.%s.floor_height must be a finite number of metres (got %r)" % (stage, h))
-    out["height"] = h
-    pts = st.get("floor_points", None)
-    if pts is not None:
-        ok = isinstance(pts, (list, tuple)) and len(pts) == 2 and all(isinstance(r, (list, tuple)) and len(r) >= 1 for r in pts)
-        ok = ok and all(isinstance(v, int) and not isinstance(v, bool) and v >= 0 for r in pts for v in r)
-        if not ok or not 2 <= len(pts[0]) + len(pts[1]) <= FLOOR_MAX_POINTS:
-            raise ValueError("stages.%s.floor_points must be null or [[left vertex ids], [right vertex ids]] with at least one "
-                             "id >= 0 per foot and 2 .. %d in all (got %r)" % (stage, FLOOR_MAX_POINTS, pts))
-        pts = [list(pts[0]), list(pts[1])]
-    out["points"] = pts
-    return out
-
-
-def stage_capsules(config: Dict, stage: str) -> Dict:
-    """EXTENSION: the bone-capsule self-penetration term of the chamfer or marker stage (uuo_fit_set_capsules) as a config
-    states it -- stages.<stage>.losses.self_penetration (a weight on m^2; absent or 0 = off; negative or non-finite weights are
-    refused) and stages.<stage>.capsules: null (body_model.body_capsules of the model) or {joints: [[u, v], ...] (two
-    different SMPL joints < 24), geom: [[alpha, beta, radius], ...] (finite, radius > 0), pairs: [[i, j], ...] (two different
-    capsule indices)} with 1 .. 32 capsules and 1 .. 256 pairs.  Returns {"w", "capsules"}.  (The part stage refuses the key
-    with its other unknown losses.)"""
-    st = config["stages"][stage]
-    losses = st.get("losses") or {}
-    v = losses.get("self_penetration", 0.0)
-    v = 0.0 if v is None else float(v)
-    if not math.isfinite(v) or v < 0.0:
-        raise ValueError("stages.%s.losses.self_penetration must be 0 (off) or a positive weight (got %r)" % (stage, v))
-    caps = st.get("capsules", None)
-    if caps is not None:
-        def rows(x, n):
-            return isinstance(x, (list, tuple)) and len(x) >= 1 and all(isinstance(r, (list, tuple)) and len(r) == n for r in x)
-
-        def ints(x):
-            return all(isinstance(q, int) and not isinstance(q, bool) for r in x for q in r)
-
-        ok = isinstance(caps, dict) and set(caps) == {"joints", "geom", "pairs"} and rows(caps["joints"], 2) and \
-            rows(caps["geom"], 3) and rows(caps["pairs"], 2) and len(caps["joints"]) == len(caps["geom"]) and \
-            len(caps["joints"]) <= CAPSULES_MAX and len(caps["pairs"]) <= CAPSULE_PAIRS_MAX and ints(caps["joints"]) and \
-            ints(caps["pairs"])
-        if ok:
-            C = len(caps["joints"])
-            ok = all(0 <= u < 24 and 0 <= w < 24 and u != w for u, w in caps["joints"]) and \
-                all(0 <= i < C and 0 <= j < C and i != j for i, j in caps["pairs"]) and \
-                all(isinstance(q, (int, float)) and not isinstance(q, bool) and math.isfinite(q) for r in caps["geom"] for q in r) and \
-                all(r[2] > 0 for r in caps["geom"])
-        if not ok:
-            raise ValueError("stages.%s.capsules must be null or {joints: [[u, v], ...], geom: [[alpha, beta, radius], ...], "
-                             "pairs: [[i, j], ...]} with 1 .. %d capsules on two different joints < 24, finite geometry with "
-                             "radius > 0, and 1 .. %d pairs of two different capsule indices (got %r)"
-                             % (stage, CAPSULES_MAX, CAPSULE_PAIRS_MAX, caps))
-        caps = {"joints": [list(r) for r in caps["joints"]], "geom": [[float(q) for q in r] for r in caps["geom"]],
-                "pairs": [list(r) for r in caps["pairs"]]}
-    return {"w": v, "capsules": caps}
-
-
-def stage_joint_limits(config: Dict, stage: str) -> Dict:
-    """EXTENSION: the joint-angle limit term of the chamfer or marker stage (uuo_fit_set_joint_limits) as a config states it --
-    stages.<stage>.losses.joint_limits (a weight on rad^2; absent or 0 = off; negative or non-finite weights are refused) and
-    stages.<stage>.joint_limits: null (body_model.smpl_joint_limits()) or {lo: [[x, y, z] x 23], hi: [[x, y, z] x 23]} in
-    radians on the components of each body joint's axis-angle vector (row j - 1 is SMPL joint j; -.inf / .inf = no bound;
-    lo <= hi, no NaN, lo < +inf, hi > -inf).  Returns {"w", "limits"}.  (The part stage refuses the key with its other unknown
-    losses.)"""
-    st = config["stages"][stage]
-    losses = st.get("losses") or {}
-    v = losses.get("joint_limits", 0.0)
-    v = 0.0 if v is None else float(v)
-    if not math.isfinite(v) or v < 0.0:
-        raise ValueError("stages.%s.losses.joint_limits must be 0 (off) or a positive weight (got %r)" % (stage, v))
-    lim = st.get("joint_limits", None)
-    if lim is not None:
-        def table(x):
-            return isinstance(x, (list, tuple)) and len(x) == 23 and \
-                all(isinstance(r, (list, tuple)) and len(r) == 3 and
-                    all(isinstance(q, (int, float)) and not isinstance(q, bool) and not math.isnan(q) for q in r) for r in x)
-
-        ok = isinstance(lim, dict) and set(lim) == {"lo", "hi"} and table(lim["lo"]) and table(lim["hi"])
-        if ok:
-            ok = all(a <= b and a < math.inf and b > -math.inf for ra, rb in zip(lim["lo"], lim["hi"]) for a, b in zip(ra, rb))
-        if not ok:
-            raise ValueError("stages.%s.joint_limits must be null or {lo: [[x, y, z] x 23], hi: [[x, y, z] x 23]} in radians with "
-                             "lo <= hi, no NaN, lo < +inf and hi > -inf (-.inf / .inf = no bound; got %r)" % (stage, lim))
-        lim = {"lo": [[float(q) for q in r] for r in lim["lo"]], "hi": [[float(q) for q in r] for r in lim["hi"]]}
-    return {"w": v, "limits": lim}
-
-
-def stage_pose_accel(config: Dict, stage: str) -> Dict:
-    """EXTENSION: the pose-acceleration term of the chamfer or marker stage (losses.pose_accel_loss) as a config states it --
-    stages.<stage>.losses.pose_accel (a weight on rad^2 per frame^4: it belongs to the frame rate; absent or 0 = off; negative or
-    non-finite weights are refused) and the optional stages.<stage>.pose_accel: null or {joint_weights: null | [23 floats]},
-    finite values >= 0 (entry j - 1 is SMPL joint j; null = ones).  Returns {"w", "joint_weights"}.  (The part stage refuses the
-    key with its other unknown losses.)"""
-    st = config["stages"][stage]
-    losses = st.get("losses") or {}
-    v = losses.get("pose_accel", 0.0)
-    v = 0.0 if v is None else float(v)
-    if not math.isfinite(v) or v < 0.0:
-        raise ValueError("stages.%s.losses.pose_accel must be 0 (off) or a positive weight (got %r)" % (stage, v))
-    blk = st.get("pose_accel", None)
-    jw = None
-    if blk is not None:
-        what = "stages.%s.pose_accel" % stage
-        if not isinstance(blk, dict) or set(blk) - {"joint_weights"}:
-            raise ValueError("%s must be null or {joint_weights} (got %r)" % (what, blk))
-        jw = blk.get("joint_weights", None)
-        if jw is not None:
-            number = lambda q: isinstance(q, (int, float)) and not isinstance(q, bool) and math.isfinite(q)
-            if not isinstance(jw, (list, tuple)) or len(jw) != 23 or not all(number(q) and q >= 0.0 for q in jw):
-                raise ValueError("%s.joint_weights must be null or 23 finite values >= 0 (got %r)" % (what, jw))
-            jw = [float(q) for q in jw]
-    return {"w": v, "joint_weights": jw}
-
-
-def stage_prior_confidence(config: Dict, stage: str):
-    """EXTENSION: the per-(frame, joint) confidence in the video's pose of the chamfer or marker stage as a config states it --
-    stages.<stage>.prior_confidence: absent or null = off (returns None), else {gap_weight: 0.0, ramp: 0, joint_weights: null}:
-    `gap_weight` in [0, 1], the weight of the pose prior in frames the video did not see; `ramp`, an integer >= 0, the number of
-    unseen frames next to a seen one over which the weight falls from 1 to it; `joint_weights`, null (ones) or 23 finite values
-    >= 0 (entry j - 1 is SMPL joint j).  Every key may be left out; unknown keys, and values outside these ranges, are a
-    ValueError.  Returns {"gap_weight", "ramp", "joint_weights"} (prior_weight_table's `block`).  A block next to a
-    reg_pose_body that is absent or 0 is allowed and changes nothing."""
-    blk = config["stages"][stage].get("prior_confidence", None)
-    if blk is None:
-        return None
-    what = "stages.%s.prior_confidence" % stage
-    if not isinstance(blk, dict) or set(blk) - {"gap_weight", "ramp", "joint_weights"}:
-        raise ValueError("%s must be null or {gap_weight, ramp, joint_weights} (got %r)" % (what, blk))
-    number = lambda q: isinstance(q, (int, float)) and not isinstance(q, bool) and math.isfinite(q)
-    gw = blk.get("gap_weight", 0.0)
-    if not number(gw) or gw < 0.0 or gw > 1.0:
-        raise ValueError("%s.gap_weight must be a number in [0, 1] (got %r)" % (what, gw))
-    ramp = blk.get("ramp", 0)
-    if not isinstance(ramp, int) or isinstance(ramp, bool) or ramp < 0:
-        raise ValueError("%s.ramp must be an integer >= 0 (got %r)" % (what, ramp))
-    jw = blk.get("joint_weights", None)
-    if jw is not None:
-        if not isinstance(jw, (list, tuple)) or len(jw) != 23 or not all(number(q) and q >= 0.0 for q in jw):
-            raise ValueError("%s.joint_weights must be null or 23 finite values >= 0 (got %r)" % (what, jw))
-        jw = [float(q) for q in jw]
-    return {"gap_weight": float(gw), "ramp": int(ramp), "joint_weights": jw}
-
-
-def prior_weight_table(seen, block: Dict) -> torch.Tensor:
-    """EXTENSION: the pose prior's weights [F, 23] float32 (host) from `seen` [F] (mocap frames the video saw; anything
-    non-zero counts) and stage_prior_confidence's record:  omega[t, j] = frame_w[t] * joint_weights[j],  d[t] the distance in
-    frames to the nearest seen frame,  frame_w[t] = 1 where d = 0, else max(gap_weight, 1 - d / (ramp + 1)).  ramp = 0 makes
-    every unseen frame gap_weight; ramp = 2 tapers 2/3, 1/3.  No seen frame at all is a ValueError."""
-    sn = torch.as_tensor(seen).detach().cpu().reshape(-1) != 0
-    F = int(sn.shape[0])
-    idx = torch.nonzero(sn).reshape(-1).to(torch.int64)
-    if idx.numel() == 0:
-        raise ValueError("prior_weight_table: the video saw no frame at all")
-    t = torch.arange(F, dtype=torch.int64)
-    d = (t[:, None] - idx[None, :]).abs().min(dim=1)[0].to(torch.float64)
-    gw, ramp = float(block["gap_weight"]), int(block["ramp"])
-    fw = torch.where(d == 0, torch.ones_like(d), torch.clamp(1.0 - d / (ramp + 1.0), min=gw))
-    jw = block.get("joint_weights")
-    jw = torch.ones(23, dtype=torch.float64) if jw is None else torch.tensor([float(q) for q in jw], dtype=torch.float64)
-    return (fw[:, None] * jw[None, :]).to(torch.float32).contiguous()
-
-
-def check_prior_weights(prior_weights, num_frames=None):
-    """EXTENSION: the pose prior's weights as a float32 host tensor [F, 23] (None stays None).  Shape, finiteness and >= 0 are
-    checked on the host: ValueError before anything touches the device."""
-    if prior_weights is None:
-        return None
-    w = torch.as_tensor(prior_weights).detach().to(device="cpu", dtype=torch.float32)
-    if w.dim() != 2 or w.shape[1] != 23 or (num_frames is not None and w.shape[0] != int(num_frames)):
-        raise ValueError("prior_weights: [F, 23] with the markers' F = %s expected (got %s)" % (num_frames, tuple(w.shape)))
-    if not bool(torch.isfinite(w).all()) or bool((w < 0.0).any()):
-        raise ValueError("prior_weights: finite weights >= 0 expected")
-    return w
-
-
-def check_foot_contacts(foot_contacts, num_frames=None):
-    """EXTENSION: the foot-lock term's contact labels as a float32 host tensor [F, 2] (left, right foot; None stays None).
-    Shape, finiteness and the range [0, 1] are checked on the host: ValueError before anything touches the device."""
-    if foot_contacts is None:
-        return None
-    c = torch.as_tensor(foot_contacts).detach().to(device="cpu", dtype=torch.float32)
-    if c.dim() != 2 or c.shape[1] != 2 or (num_frames is not None and c.shape[0] != int(num_frames)):
-        raise ValueError("foot_contacts: [F, 2] with the markers' F = %s expected (got %s)" % (num_frames, tuple(c.shape)))
-    if not bool(torch.isfinite(c).all()) or bool((c < 0.0).any()) or bool((c > 1.0).any()):
-        raise ValueError("foot_contacts: finite labels in [0, 1] expected")
-    return c
-
-
 def _cfg_weights(losses: Dict, data_key: str):
     return (float(losses.get(data_key, 0.0)), float(losses.get("reg_pose_body", 0.0)),
             float(losses.get("reg_betas", 0.0)))
@@ -1113,67 +708,38 @@ class ChamferProblem(_StageProblem):
     stage = UUO_STAGE_CHAMFER
 
     def __init__(self, smpl_inference, markers, o_pose_body, o_betas, root_orient, config, foot_contacts=None,
-                 prior_weights=None):
+                 prior_weights=None, stage_terms=None):
         """EXTENSION: `prior_weights` [F, 23] >= 0 weighs the pose prior per frame and body joint (prior_weight_table builds it
-        from the video's mask and stages.chamfer.prior_confidence); None, or ones everywhere, changes nothing."""
+        from the video's mask and stages.chamfer.prior_confidence); None, or ones everywhere, changes nothing.  `stage_terms`:
+        the caller's terms.StageTerms of this config and stage, when it has parsed them already."""
         losses = config["stages"]["chamfer"]["losses"]
-        unsupported = set(losses) - {"full_chamfer", "reg_pose_body", "reg_betas", "soft_chamfer", "joint_accel", "foot_lock",
-                                     "surface_chamfer", "floor_penetration", "floor_contact", "self_penetration",
-                                     "joint_limits", "pose_accel"}
+        unsupported = set(losses) - terms.problem_keys("chamfer")
         if unsupported:
             raise NotImplementedError("chamfer-stage losses outside the shipped configs: %s" % sorted(unsupported))
         w_surface, d_surface = stage_surface(config)  # EXTENSION: point-to-surface data term (0 = off)
-        caps = stage_capsules(config, "chamfer")  # EXTENSION: bone-capsule self-penetration term (0 = off)
-        if caps["w"] > 0.0 and float(losses.get("soft_chamfer", 0.0)) != 0.0:
-            raise NotImplementedError("stages.chamfer: the fused self-penetration term (self_penetration) is not built for the "
-                                      "soft-assignment closure; optim_chamfer composes that combination from the operators")
-        lim = stage_joint_limits(config, "chamfer")  # EXTENSION: joint-angle limit term on the body pose (0 = off)
-        if lim["w"] > 0.0 and float(losses.get("soft_chamfer", 0.0)) != 0.0:
-            raise NotImplementedError("stages.chamfer: the fused joint-angle limit term (joint_limits) is not built for the "
-                                      "soft-assignment closure; optim_chamfer composes that combination from the operators")
-        if stage_pose_accel(config, "chamfer")["w"] > 0.0:  # EXTENSION: pose-acceleration term on the local body rotations
-            raise NotImplementedError("stages.chamfer.losses.pose_accel (extension) has no fused closure: optim_chamfer composes "
-                                      "it from the operators")
-        w_accel = stage_joint_accel(config, "chamfer")
-        if w_accel > 0.0 and float(losses.get("soft_chamfer", 0.0)) != 0.0:
-            raise NotImplementedError("stages.chamfer: the fused joint-acceleration term (joint_accel) is not built for the "
-                                      "soft-assignment closure; optim_chamfer composes that combination from the operators")
-        w_lock = stage_foot_lock(config, "chamfer")
-        if w_lock > 0.0 and float(losses.get("soft_chamfer", 0.0)) != 0.0:
-            raise NotImplementedError("stages.chamfer: the fused foot-lock term (foot_lock) is not built for the "
-                                      "soft-assignment closure; optim_chamfer composes that combination from the operators")
-        floor = stage_floor(config, "chamfer")
-        if (floor["w_pen"] > 0.0 or floor["w_con"] > 0.0) and float(losses.get("soft_chamfer", 0.0)) != 0.0:
-            raise NotImplementedError("stages.chamfer: the fused floor-contact term (floor_penetration / floor_contact) is not "
-                                      "built for the soft-assignment closure; optim_chamfer composes that combination from the "
-                                      "operators")
+        stage_terms = stage_terms or terms.StageTerms(config, "chamfer")
+        soft = float(losses.get(terms.SOFT_KEY, 0.0)) != 0.0
+        stage_terms.check_problem(soft)  # EXTENSION: the terms, each 0 = off; the soft-assignment closure carries none of them
         contacts = check_foot_contacts(foot_contacts, None if markers is None else markers.shape[0])
-        stage_prior_confidence(config, "chamfer")  # EXTENSION: the pose prior's weights (validates the block)
+        stage_terms[terms.PRIOR]  # EXTENSION: the pose prior's weights (validates the block)
         weights = check_prior_weights(prior_weights, None if markers is None else markers.shape[0])
-        if weights is not None and not bool((weights == 1.0).all()) and float(losses.get("soft_chamfer", 0.0)) != 0.0:
-            raise NotImplementedError("stages.chamfer: the pose prior's weights (prior_confidence) are not built for the "
-                                      "soft-assignment closure")
+        if terms.armed_weights(weights) is not None and soft:
+            raise NotImplementedError(terms.PRIOR.soft)
         if not config["stages"]["chamfer"]["yaw_lock"]:
             raise NotImplementedError("stages.chamfer.yaw_lock False is not a shipped configuration")
         wd, wp, wb = _cfg_weights(losses, "surface_chamfer" if w_surface > 0.0 else "full_chamfer")
-        sigma = stage_robust_sigma(config, "chamfer")
+        sigma = stage_terms[terms.ROBUST]
         super().__init__(smpl_inference.device_model, markers, o_pose_body, o_betas, root_orient, wd, wp, wb)
         self.problem.robust_sigma = sigma  # EXTENSION: Geman-McClure data term (0 = off)
         if w_surface > 0.0:  # EXTENSION: the data term is the point-to-surface distance on the nearest vertex's one-ring
             if not self.model.has_faces:
                 raise RuntimeError("stages.chamfer.losses.surface_chamfer needs a body model with faces")
             self.surface, self.surface_distance = True, d_surface
-        self.joint_accel = w_accel  # EXTENSION: joint-acceleration term (0 = off)
-        self._set_foot_lock(w_lock, contacts)  # EXTENSION: foot-lock term (weight 0 without gated contacts)
-        self._set_floor(floor, contacts, smpl_inference)  # EXTENSION: floor-contact term on sole vertices
-        self._set_capsules(caps, smpl_inference)  # EXTENSION: bone-capsule self-penetration term
-        self._set_joint_limits(lim)  # EXTENSION: joint-angle limit term on the body pose
-        self._set_prior_weights(weights)  # EXTENSION: per-(frame, joint) weights of the pose prior
+        self._set_terms(stage_terms, contacts, weights, smpl_inference)
         # EXTENSION (not in the reference): soft assignment of every marker to the body's vertices, fused closure with the dense
         # backward on the matrix pipe (csrc/dense_bwd.hip); not available inside lock-step batches
-        w_soft = float(losses.get("soft_chamfer", 0.0))
-        if w_soft != 0.0:
-            self.problem.w_soft = w_soft
+        if soft:
+            self.problem.w_soft = float(losses[terms.SOFT_KEY])
             self.problem.soft_tau = float(config["stages"]["chamfer"].get("soft_tau", 1e-3))
             if not self.problem.soft_tau > 0.0:
                 raise ValueError("stages.chamfer.soft_tau must be positive")
@@ -1205,38 +771,29 @@ class MarkerProblem(_StageProblem):
     stage = UUO_STAGE_MARKER
 
     def __init__(self, smpl_inference, markers, o_pose_body, o_betas, assign, config, bary=None, foot_contacts=None,
-                 frame_assign=None, prior_weights=None):
+                 frame_assign=None, prior_weights=None, stage_terms=None):
         """`assign` [M] vertex ids (the one-hot placement of the shipped configs), or -- with `bary` [M, 3] -- [M, 3] corner
         vertex ids of a three-corner (barycentric) placement: virtual marker m = sum_k bary[m, k] v[assign[m, k]].
         EXTENSION: `frame_assign` [F, M] int32, a per-frame vertex table (tracklets: the column's vertex changes with the frame,
         an entry < 0 is an item of weight 0); `assign` may then be None.  Refused with `bary` and with latent_offsets.
         EXTENSION: `prior_weights` [F, 23] >= 0 weighs the pose prior per frame and body joint (prior_weight_table); None, or
-        ones everywhere, changes nothing."""
+        ones everywhere, changes nothing.  `stage_terms`: as ChamferProblem's."""
         st = config["stages"]["marker"]
-        unsupported = set(st["losses"]) - {"marker", "reg_pose_body", "reg_betas", "joint_accel", "latent_offsets", "foot_lock",
-                                           "floor_penetration", "floor_contact", "self_penetration", "joint_limits",
-                                           "pose_accel"}
+        unsupported = set(st["losses"]) - terms.problem_keys("marker")
         if unsupported:
             raise NotImplementedError("marker-stage losses outside the shipped configs: %s" % sorted(unsupported))
         if st.get("use_sdf"):
             raise NotImplementedError("stages.marker.use_sdf is off in every shipped config")
-        floor = stage_floor(config, "marker")
-        lim = stage_joint_limits(config, "marker")  # EXTENSION: joint-angle limit term on the body pose (0 = off)
-        caps = stage_capsules(config, "marker")  # EXTENSION: bone-capsule self-penetration term (0 = off)
-        if stage_pose_accel(config, "marker")["w"] > 0.0:  # EXTENSION: pose-acceleration term on the local body rotations
-            raise NotImplementedError("stages.marker.losses.pose_accel (extension) has no fused closure: optim_markers composes "
-                                      "it from the operators")
-        if frame_assign is not None and (floor["w_pen"] > 0.0 or floor["w_con"] > 0.0):
-            raise NotImplementedError("the per-frame vertex table (tracklets, extension) is not built for the floor-contact term "
-                                      "(stages.marker.losses.floor_penetration / floor_contact)")
+        stage_terms = stage_terms or terms.StageTerms(config, "marker")
+        stage_terms.check_problem(False)  # EXTENSION: the terms, each 0 = off
+        if frame_assign is not None and stage_terms.on(terms.FLOOR):
+            raise NotImplementedError(terms.FLOOR.frame_table)
         wd, wp, wb = _cfg_weights(st["losses"], "marker")
-        sigma = stage_robust_sigma(config, "marker")
-        w_accel = stage_joint_accel(config, "marker")
-        w_lock = stage_foot_lock(config, "marker")
+        sigma = stage_terms[terms.ROBUST]
         contacts = check_foot_contacts(foot_contacts, None if markers is None else markers.shape[0])
-        stage_prior_confidence(config, "marker")  # EXTENSION: the pose prior's weights (validates the block)
+        stage_terms[terms.PRIOR]  # EXTENSION: the pose prior's weights (validates the block)
         weights = check_prior_weights(prior_weights, None if markers is None else markers.shape[0])
-        w_offsets = stage_latent_offsets(config)
+        w_offsets = stage_terms[terms.LATENT_OFFSETS]
         if frame_assign is not None:
             if bary is not None:
                 raise NotImplementedError("the per-frame vertex table (tracklets, extension) is not built for a three-corner "
@@ -1253,12 +810,7 @@ class MarkerProblem(_StageProblem):
                 assign = torch.zeros(int(markers.shape[1]), dtype=torch.int32)
         super().__init__(smpl_inference.device_model, markers, o_pose_body, o_betas, None, wd, wp, wb, assign=assign)
         self.problem.robust_sigma = sigma  # EXTENSION: Geman-McClure data term (0 = off)
-        self.joint_accel = w_accel  # EXTENSION: joint-acceleration term (0 = off)
-        self._set_foot_lock(w_lock, contacts)  # EXTENSION: foot-lock term (weight 0 without gated contacts)
-        self._set_floor(floor, contacts, smpl_inference)  # EXTENSION: floor-contact term on sole vertices
-        self._set_capsules(caps, smpl_inference)  # EXTENSION: bone-capsule self-penetration term
-        self._set_joint_limits(lim)  # EXTENSION: joint-angle limit term on the body pose
-        self._set_prior_weights(weights)  # EXTENSION: per-(frame, joint) weights of the pose prior
+        self._set_terms(stage_terms, contacts, weights, smpl_inference)
         if frame_assign is not None:  # EXTENSION: per-frame vertex table (the *_f kernel instantiations)
             self.frame_assign = frame_assign.to(device=self.device, dtype=torch.int32).contiguous()
         if w_offsets > 0.0:  # EXTENSION: latent per-marker offsets, 3 M more parameters after trans

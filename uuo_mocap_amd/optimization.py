@@ -13,15 +13,14 @@ import torch.nn.functional as F
 
 from .device_lbfgs import DeviceLBFGS
 from .config import stage_surface
-from .engine import (MARKER_DISTANCE, ChamferProblem, MarkerProblem, check_foot_contacts, check_prior_weights, stage_capsules, stage_floor,
-                     stage_foot_lock, stage_joint_accel, stage_joint_limits, stage_latent_offsets, stage_pose_accel,
-                     stage_prior_confidence, stage_robust_sigma)
+from .engine import MARKER_DISTANCE, ChamferProblem, MarkerProblem
 from .losses import (MarkerLoss, RobustMarkerLoss, chamfer_distance, floor_loss, foot_lock_loss, joint_accel_loss,  # noqa: F401  (re-exported)
                      self_penetration_loss, joint_limit_loss, pose_accel_loss, weighted_pose_prior,
                      robust_weighted_chamfer_distance, soft_weighted_chamfer_distance, surface_chamfer_distance,
                      weighted_chamfer_distance)
 from .smpl import SmplInference
-from .tracklets import tracklets_config
+from .terms import (PRIOR, ROBUST, StageTerms, add_tail, armed_weights, check_foot_contacts, check_prior_weights, composed_keys,
+                    lockstep_supported, stage_route)  # noqa: F401  (lockstep_supported: re-exported)
 from .transforms import compute_root_orient_y, compute_root_orient_z, normalize_rot  # noqa: F401
 
 #: per-solve statistics of the most recent calls (n_iter, n_eval, losses, device ms) -- bench.py and tests read it
@@ -70,53 +69,21 @@ def optim_chamfer(
     stages.chamfer.losses.foot_lock (without them, or with labels that gate nothing, the key changes nothing).
     EXTENSION: `prior_weights` ([F, 23] >= 0, optional; engine.prior_weight_table) weigh reg_pose_body per frame and body joint
     (None, or ones everywhere, changes nothing; `img_mask` itself is not read)."""
-    st = config["stages"]["chamfer"]
-    prior_weights = _armed_prior_weights(config, "chamfer", prior_weights, markers.shape[0])
-    fused_losses = _CHAMFER_FUSED_LOSSES
-    if float(st["losses"].get("soft_chamfer", 0.0)) != 0.0 and markers.is_cuda and \
-            bool((config.get("execution") or {}).get("chamfer_soft_fused", True)):
-        # EXTENSION: the soft-assignment data term has a fused closure (dense backward on the matrix pipe, csrc/dense_bwd.hip);
-        # execution.chamfer_soft_fused: False keeps the operator-composed closure, its checker
-        fused_losses = _CHAMFER_FUSED_LOSSES | {"soft_chamfer"}
-    if "soft_chamfer" in fused_losses and (stage_joint_accel(config, "chamfer") > 0.0 or stage_foot_lock(config, "chamfer") > 0.0 or
-                                           _floor_on(config, "chamfer") or _capsules_on(config, "chamfer") or
-                                           _limits_on(config, "chamfer") or prior_weights is not None):
-        # EXTENSION: the temporal terms, the floor-contact term, the self-penetration term, the joint-angle limit term and the
-        # pose prior's weights have no instantiation of the dense backward (k_bwd_dense): composed closure
-        fused_losses = _CHAMFER_FUSED_LOSSES
-    w_surface, _ = stage_surface(config)  # EXTENSION: point-to-surface data term (validates the keys)
-    if w_surface > 0.0:
-        from .parallel import frame_shard
-
-        fs = frame_shard()
-        if fs is not None and fs.active:
-            raise NotImplementedError("stages.chamfer.losses.surface_chamfer (point-to-surface term, extension) is not built for "
-                                      "frame-block sharding (parallel.shard_frames)")
-    if w_surface == 0.0 or (markers.is_cuda and bool((config.get("execution") or {}).get("surface_fused", True))):
-        # the term has a fused closure (k_ring_pick + k_surf_fwd + k_bwd_items_f); execution.surface_fused: False keeps the
-        # operator-composed closure, its checker.  (Weight 0 is the key absent.)
-        fused_losses = fused_losses | {"surface_chamfer"}
-    if (set(st["losses"]) - fused_losses - {"pose_accel"}) or not st["yaw_lock"] or not _robust_fused(config, "chamfer") or \
-            not _temporal_fused(config, "chamfer") or not _floor_fused(config, "chamfer") or \
-            not _capsule_fused(config, "chamfer") or not _limit_fused(config, "chamfer") or \
-            not _prior_conf_fused(config, prior_weights) or _pose_accel_on(config, "chamfer"):
-        # (EXTENSION: the pose-acceleration term, losses.pose_accel, has no fused closure: it always runs composed)
-        _refuse_sharded_pose_accel(config, "chamfer")
-        return _optim_chamfer_general(markers, pose_body, o_pose_body, betas, o_betas, root_orient, trans, marker_labels,
-                                      smpl_inference, config, initial_angle, repeat, verbose, iter_fn, foot_contacts,
-                                      prior_weights)
     from .parallel import frame_shard
 
+    stage_terms = _stage_terms(config, "chamfer", prior_weights, markers.shape[0])
+    prior_weights = stage_terms.prior_weights
     fs = frame_shard()
-    if fs is not None and fs.active:
-        if "soft_chamfer" in fused_losses:
-            raise NotImplementedError("stages.chamfer.losses.soft_chamfer (extension) is not built for frame-block sharding "
-                                      "(parallel.shard_frames); set execution.chamfer_soft_fused: False or use another mode")
-        _refuse_sharded_prior_weights(config, "chamfer", prior_weights)
+    route = stage_route(stage_terms, on_device=markers.is_cuda, sharded=fs is not None and fs.active)
+    if route == "composed":
+        return _optim_chamfer_general(markers, pose_body, o_pose_body, betas, o_betas, root_orient, trans, marker_labels,
+                                      smpl_inference, config, initial_angle, repeat, verbose, iter_fn, foot_contacts,
+                                      prior_weights, stage_terms=stage_terms)
+    if route == "sharded":
         return _optim_chamfer_frame_sharded(fs, markers, pose_body, o_pose_body, betas, o_betas, root_orient, trans,
-                                            smpl_inference, config, iter_fn)
+                                            smpl_inference, config, iter_fn, stage_terms=stage_terms)
     prob = ChamferProblem(smpl_inference, markers, o_pose_body, o_betas, root_orient, config, foot_contacts=foot_contacts,
-                          prior_weights=prior_weights)
+                          prior_weights=prior_weights, stage_terms=stage_terms)
     z_angle = torch.zeros((root_orient.shape[0], root_orient.shape[1], 1), device=root_orient.device)
     x = prob.pack(trans, z_angle, betas, pose_body)
     point_cb = None
@@ -160,10 +127,10 @@ def _frame_sharded_solve(fs, prob, x, config, stage: str, lr: float, frames_here
 
 
 def _optim_chamfer_frame_sharded(fs, markers, pose_body, o_pose_body, betas, o_betas, root_orient, trans, smpl_inference,
-                                 config, iter_fn):
+                                 config, iter_fn, stage_terms=None):
     """optim_chamfer's fused solve spread over ranks by frame blocks (parallel.shard_frames); same in-place contract, every
     rank ends with the full result."""
-    _refuse_sharded_joint_accel(config, "chamfer")
+    (stage_terms or StageTerms(config, "chamfer")).refuse_sharded()
     if iter_fn is not None:
         raise NotImplementedError("frame sharding: no per-evaluation iter_fn")
     F = int(markers.shape[0])
@@ -188,10 +155,9 @@ def _optim_chamfer_frame_sharded(fs, markers, pose_body, o_pose_body, betas, o_b
 
 
 def _optim_markers_frame_sharded(fs, markers, pose_body, o_pose_body, betas, o_betas, root_orient, trans, assign,
-                                 smpl_inference, config, iter_fn):
+                                 smpl_inference, config, iter_fn, stage_terms=None):
     """optim_markers' fused solve (one-hot placement) spread over ranks by frame blocks; same in-place contract."""
-    _refuse_sharded_joint_accel(config, "marker")
-    _refuse_latent_offsets(config, "frame-block sharding (parallel.shard_frames)")
+    (stage_terms or StageTerms(config, "marker")).refuse_sharded()
     if iter_fn is not None:
         raise NotImplementedError("frame sharding: no per-evaluation iter_fn")
     F = int(markers.shape[0])
@@ -211,217 +177,14 @@ def _optim_markers_frame_sharded(fs, markers, pose_body, o_pose_body, betas, o_b
     return None
 
 
-def _robust_fused(config: Dict, stage: str) -> bool:
-    """False when the stage's EXTENSION Geman-McClure data term (stages.<stage>.robust_sigma > 0) is to run on the closure
-    composed from the operators (execution.robust_fused: False, the fused closures' checker); True otherwise."""
-    return stage_robust_sigma(config, stage) == 0.0 or bool((config.get("execution") or {}).get("robust_fused", True))
-
-
-def _temporal_fused(config: Dict, stage: str) -> bool:
-    """False when the stage's EXTENSION temporal terms (stages.<stage>.losses.joint_accel > 0 or foot_lock > 0) are to run on
-    the closure composed from the operators (execution.temporal_fused: False, the fused closures' checker); True otherwise."""
-    return (stage_joint_accel(config, stage) == 0.0 and stage_foot_lock(config, stage) == 0.0) or \
-        bool((config.get("execution") or {}).get("temporal_fused", True))
-
-
-def _floor_on(config: Dict, stage: str) -> bool:
-    """True when the stage's EXTENSION floor-contact term has a non-zero weight (stages.<stage>.losses.floor_penetration /
-    floor_contact; validates the keys)."""
-    fl = stage_floor(config, stage)
-    return fl["w_pen"] > 0.0 or fl["w_con"] > 0.0
-
-
-def _floor_fused(config: Dict, stage: str) -> bool:
-    """False when the stage's EXTENSION floor-contact term is to run on the closure composed from the operators
-    (execution.floor_fused: False, the fused closures' checker); True otherwise."""
-    return not _floor_on(config, stage) or bool((config.get("execution") or {}).get("floor_fused", True))
-
-
-def _composed_floor(config: Dict, stage: str, contacts, smpl_inference):
-    """The floor-contact term of the composed closures: None when off, else a function of the vertices [F, V, 3] -- floor_loss
-    on the configured sole points (body_model.sole_vertices by default), floor_contact only with labels that hold a contact."""
-    fl = stage_floor(config, stage)
-    w_pen, w_con = fl["w_pen"], fl["w_con"]
-    if contacts is None or not bool(contacts.any()):
-        w_con = 0.0
-    if w_pen == 0.0 and w_con == 0.0:
-        return None
-    pts = fl["points"]
-    if pts is None:
-        from .body_model import sole_vertices
-
-        pts = [[int(v) for v in row] for row in sole_vertices(smpl_inference.tables)]
-    vids, k_left = list(pts[0]) + list(pts[1]), len(pts[0])
-    return lambda vertices: floor_loss(vertices, vids, k_left, contacts, fl["height"], w_pen, w_con)
-
-
-def _capsules_on(config: Dict, stage: str) -> bool:
-    """True when the stage's EXTENSION self-penetration term has a non-zero weight (stages.<stage>.losses.self_penetration;
-    validates the keys)."""
-    return stage_capsules(config, stage)["w"] > 0.0
-
-
-def _capsule_fused(config: Dict, stage: str) -> bool:
-    """False when the stage's EXTENSION self-penetration term is to run on the closure composed from the operators
-    (execution.capsule_fused: False, the fused closures' checker); True otherwise."""
-    return not _capsules_on(config, stage) or bool((config.get("execution") or {}).get("capsule_fused", True))
-
-
-def _composed_capsules(config: Dict, stage: str, smpl_inference):
-    """The self-penetration term of the composed closures: None when off, else a function of the joints [F, >= 24, 3] --
-    self_penetration_loss on the configured capsules (body_model.body_capsules by default)."""
-    caps = stage_capsules(config, stage)
-    if caps["w"] == 0.0:
-        return None
-    lists = caps["capsules"]
-    if lists is None:
-        from .body_model import body_capsules
-
-        cj, cg, pr = body_capsules(smpl_inference.tables)
-    else:
-        cj, cg, pr = lists["joints"], lists["geom"], lists["pairs"]
-    return lambda joints: self_penetration_loss(joints[:, :24], cj, cg, pr, caps["w"])
-
-
-def _limits_on(config: Dict, stage: str) -> bool:
-    """True when the stage's EXTENSION joint-angle limit term has a non-zero weight (stages.<stage>.losses.joint_limits;
-    validates the keys)."""
-    return stage_joint_limits(config, stage)["w"] > 0.0
-
-
-def _limit_fused(config: Dict, stage: str) -> bool:
-    """False when the stage's EXTENSION joint-angle limit term is to run on the closure composed from the operators
-    (execution.limit_fused: False, the fused closures' checker); True otherwise."""
-    return not _limits_on(config, stage) or bool((config.get("execution") or {}).get("limit_fused", True))
-
-
-def _composed_limits(config: Dict, stage: str):
-    """The joint-angle limit term of the composed closures: None when off, else a function of the normalised body rotations
-    [F, 23, 3, 3] -- joint_limit_loss on the configured tables (body_model.smpl_joint_limits() by default)."""
-    lim = stage_joint_limits(config, stage)
-    if lim["w"] == 0.0:
-        return None
-    if lim["limits"] is None:
-        from .body_model import smpl_joint_limits
-
-        lo, hi = smpl_joint_limits()
-    else:
-        lo, hi = lim["limits"]["lo"], lim["limits"]["hi"]
-    return lambda rot_body: joint_limit_loss(rot_body, lo, hi, lim["w"])
-
-
-def _pose_accel_on(config: Dict, stage: str) -> bool:
-    """True when the stage's EXTENSION pose-acceleration term has a non-zero weight (stages.<stage>.losses.pose_accel; validates
-    the keys)."""
-    return stage_pose_accel(config, stage)["w"] > 0.0
-
-
-def _refuse_sharded_pose_accel(config: Dict, stage: str):
-    if _pose_accel_on(config, stage):
-        from .parallel import frame_shard
-
-        fs = frame_shard()
-        if fs is not None and fs.active:
-            raise NotImplementedError("stages.%s.losses.pose_accel (extension) couples neighbouring frames, across the ranks' "
-                                      "frame blocks too: it is not built for frame-block sharding (parallel.shard_frames)" % stage)
-
-
-def _composed_pose_accel(config: Dict, stage: str):
-    """The pose-acceleration term (EXTENSION; it runs on the closures composed from the operators only): None when off, else a
-    function of the normalised body rotations [F, 23, 3, 3] -- pose_accel_loss with the configured joint weights (ones by
-    default)."""
-    pacc = stage_pose_accel(config, stage)
-    if pacc["w"] == 0.0:
-        return None
-    return lambda rot_body: pose_accel_loss(rot_body, pacc["w"], pacc["joint_weights"])
-
-
-def _prior_conf_on(config: Dict, stage: str) -> bool:
-    """True when the stage's config carries the EXTENSION block stages.<stage>.prior_confidence (validates it)."""
-    return stage_prior_confidence(config, stage) is not None
-
-
-def _armed_prior_weights(config: Dict, stage: str, prior_weights, num_frames):
-    """The stage's EXTENSION weights of the pose prior as the solvers use them: the block is validated, the table checked on the
-    host (shape, finite, >= 0: ValueError before the device is touched); None, or a table of ones, comes back as None -- nothing
-    is armed and every route is the one it was."""
-    stage_prior_confidence(config, stage)
-    w = check_prior_weights(prior_weights, num_frames)
-    if w is None or bool((w == 1.0).all()):
-        return None
-    return w
-
-
-def _prior_conf_fused(config: Dict, prior_weights) -> bool:
-    """False when armed weights of the pose prior are to run on the closure composed from the operators
-    (execution.prior_conf_fused: False, the fused closures' checker); True otherwise."""
-    return prior_weights is None or bool((config.get("execution") or {}).get("prior_conf_fused", True))
-
-
-def _refuse_sharded_prior_weights(config: Dict, stage: str, prior_weights):
-    if prior_weights is not None or _prior_conf_on(config, stage):
-        raise NotImplementedError("stages.%s.prior_confidence (extension): the pose prior's weights are not built for "
-                                  "frame-block sharding (parallel.shard_frames)" % stage)
-
-
-def _refuse_latent_offsets(config: Dict, route: str):
-    if stage_latent_offsets(config) > 0.0:
-        raise NotImplementedError("stages.marker.losses.latent_offsets (latent marker offsets, extension) is built for the fused "
-                                  "marker closures only, not for %s" % route)
-
-
-def _refuse_sharded_joint_accel(config: Dict, stage: str):
-    if stage_joint_accel(config, stage) > 0.0:
-        raise NotImplementedError("stages.%s.losses.joint_accel (extension) couples neighbouring frames, across the ranks' "
-                                  "frame blocks too: it is not built for frame-block sharding (parallel.shard_frames)" % stage)
-    if stage_foot_lock(config, stage) > 0.0:
-        raise NotImplementedError("stages.%s.losses.foot_lock (extension) couples neighbouring frames, across the ranks' "
-                                  "frame blocks too: it is not built for frame-block sharding (parallel.shard_frames)" % stage)
-    if _floor_on(config, stage):
-        raise NotImplementedError("stages.%s.losses.floor_penetration / floor_contact (extension): the floor-contact term is not "
-                                  "built for frame-block sharding (parallel.shard_frames)" % stage)
-    if _capsules_on(config, stage):
-        raise NotImplementedError("stages.%s.losses.self_penetration (extension): the self-penetration term is not built for "
-                                  "frame-block sharding (parallel.shard_frames)" % stage)
-    if _limits_on(config, stage):
-        raise NotImplementedError("stages.%s.losses.joint_limits (extension): the joint-angle limit term is not built for "
-                                  "frame-block sharding (parallel.shard_frames)" % stage)
-
-
-def lockstep_supported(config: Dict, stage: str) -> bool:
-    """True when `stage` ("chamfer" / "marker") of this configuration runs on the fused device closure with the L-BFGS
-    driver, i.e. when independent solves of it can be stepped together (engine.solve_batch)."""
-    st = config["stages"][stage]
-    if str(config["optimizer"].get("type", "lbfgs")).lower() != "lbfgs":
-        return False
-    if not _robust_fused(config, stage):
-        return False
-    if stage_joint_accel(config, stage) > 0.0:  # EXTENSION: lock-step batches do not carry the joint-acceleration term
-        return False
-    if stage_foot_lock(config, stage) > 0.0:  # EXTENSION: nor the foot-lock term
-        return False
-    if _floor_on(config, stage) or not _floor_fused(config, stage):  # EXTENSION: nor the floor-contact term
-        return False
-    if _capsules_on(config, stage):  # EXTENSION: nor the self-penetration term
-        return False
-    if _limits_on(config, stage):  # EXTENSION: nor the joint-angle limit term
-        return False
-    if _prior_conf_on(config, stage):  # EXTENSION: nor the pose prior's weights
-        return False
-    if _pose_accel_on(config, stage):  # EXTENSION: the pose-acceleration term runs composed
-        return False
-    if stage == "marker" and stage_latent_offsets(config) > 0.0:  # EXTENSION: nor the latent marker offsets
-        return False
-    if stage == "chamfer" and stage_surface(config)[0] > 0.0:  # EXTENSION: nor the point-to-surface chamfer term
-        return False
-    if stage == "marker" and tracklets_config(config) is not None:  # EXTENSION: nor the per-frame vertex table
-        return False
-    if stage == "chamfer":
-        return not (set(st["losses"]) - _CHAMFER_FUSED_LOSSES - {"surface_chamfer", "pose_accel"}) and bool(st["yaw_lock"])
-    return not (set(st["losses"]) - {"marker", "reg_pose_body", "reg_betas", "joint_accel", "latent_offsets", "foot_lock",
-                                     "floor_penetration", "floor_contact", "self_penetration", "joint_limits",
-                                     "pose_accel"}) and \
-        not st.get("use_sdf")
+def _stage_terms(config: Dict, stage: str, prior_weights, num_frames) -> StageTerms:
+    """The stage's EXTENSION terms for one call, parsed once and handed on (terms.StageTerms), with the weights of the pose prior
+    as the solvers use them: the block is validated, the table checked on the host (shape, finite, >= 0: ValueError before the
+    device is touched); None, or a table of ones, is None -- nothing is armed and every route is the one it was."""
+    stage_terms = StageTerms(config, stage)
+    stage_terms[PRIOR]
+    stage_terms.prior_weights = armed_weights(check_prior_weights(prior_weights, num_frames))
+    return stage_terms
 
 
 def optim_chamfer_lockstep(markers, hyps, o_pose_body, o_betas, smpl_inference, config):
@@ -520,14 +283,9 @@ def _solve(prob, x, config, stage: str, lr: float, verbose_tag: str, verbose: bo
                            lr=float(opt.get("adam_lr", lr / 100.0)), callback=_printer(verbose_tag, verbose))
 
 
-#: chamfer-stage loss terms the device solver fuses (the only ones the shipped configs enable)
-_CHAMFER_FUSED_LOSSES = {"full_chamfer", "reg_pose_body", "reg_betas", "joint_accel", "foot_lock", "floor_penetration",
-                         "floor_contact", "self_penetration", "joint_limits"}
-
-
 def _optim_chamfer_general(markers, pose_body, o_pose_body, betas, o_betas, root_orient, trans, marker_labels,
                            smpl_inference, config, initial_angle, repeat, verbose, iter_fn, foot_contacts=None,
-                           prior_weights=None):
+                           prior_weights=None, stage_terms=None):
     """Chamfer stage with the reference's optional terms (`part_chamfer`, `trans_vel`, `ground`; plus the labelled
     extension `soft_chamfer`, a soft-assignment data term the reference does not have) and / or
     `yaw_lock: False` (reference optimization.py:164-285; none is in a shipped config): the closure is composed from the
@@ -536,21 +294,17 @@ def _optim_chamfer_general(markers, pose_body, o_pose_body, betas, o_betas, root
     refused.  Same in-place semantics as the fused path."""
     st = config["stages"]["chamfer"]
     w = st["losses"]
-    unknown = set(w) - _CHAMFER_FUSED_LOSSES - {"part_chamfer", "trans_vel", "ground", "soft_chamfer", "surface_chamfer", "pose_accel"}
+    unknown = set(w) - composed_keys("chamfer")
     if unknown:
         raise NotImplementedError("chamfer-stage losses that cannot run in the reference: %s" % sorted(unknown))
+    stage_terms = stage_terms or StageTerms(config, "chamfer")
     w_surface, d_surface = stage_surface(config)  # EXTENSION: point-to-surface data term and its stand-off
-    sigma = stage_robust_sigma(config, "chamfer")  # EXTENSION: Geman-McClure data term (0 = the reference's square)
-    w_accel = stage_joint_accel(config, "chamfer")  # EXTENSION: joint-acceleration term
-    w_lock = stage_foot_lock(config, "chamfer")  # EXTENSION: foot-lock term, on the video's contact labels
+    sigma = stage_terms[ROBUST]  # EXTENSION: Geman-McClure data term (0 = the reference's square)
     contacts = check_foot_contacts(foot_contacts, pose_body.shape[0])
     device = root_orient.device
     if contacts is not None:
         contacts = contacts.to(device)
-    floor_term = _composed_floor(config, "chamfer", contacts, smpl_inference)  # EXTENSION: floor-contact term on sole vertices
-    caps_term = _composed_capsules(config, "chamfer", smpl_inference)  # EXTENSION: bone-capsule self-penetration term
-    lim_term = _composed_limits(config, "chamfer")  # EXTENSION: joint-angle limit term on the body pose
-    pacc_term = _composed_pose_accel(config, "chamfer")  # EXTENSION: pose-acceleration term on the local body rotations
+    tail = stage_terms.composed_tail(w, contacts, smpl_inference)  # EXTENSION: the fused closures' terms, composed (their checker)
     if prior_weights is not None:  # EXTENSION: the pose prior's weights (checked by the caller)
         prior_weights = prior_weights.to(pose_body.device)
     num_frames = pose_body.shape[0]
@@ -602,18 +356,7 @@ def _optim_chamfer_general(markers, pose_body, o_pose_body, betas, o_betas, root
             loss = loss + torch.mean(F.relu(-out["joints"][..., 2])) * w["ground"]
         if "reg_betas" in w:
             loss = loss + F.mse_loss(p_betas, o_betas) * w["reg_betas"]
-        if "joint_accel" in w:  # EXTENSION: the fused closures' joint-acceleration term, composed (their checker)
-            loss = loss + joint_accel_loss(out["joints"][:, :24]) * w_accel
-        if w_lock > 0.0 and contacts is not None:  # EXTENSION: the fused closures' foot-lock term, composed (their checker)
-            loss = loss + foot_lock_loss(out["joints"][:, :24], contacts) * w_lock
-        if floor_term is not None:  # EXTENSION: the fused closures' floor-contact term, composed (their checker)
-            loss = loss + floor_term(out["vertices"])
-        if caps_term is not None:  # EXTENSION: the fused closures' self-penetration term, composed (their checker)
-            loss = loss + caps_term(out["joints"])
-        if lim_term is not None:  # EXTENSION: the fused closures' joint-angle limit term, composed (their checker)
-            loss = loss + lim_term(normalize_rot(p_pose))
-        if pacc_term is not None:  # EXTENSION: the fused closures' pose-acceleration term, composed (their checker)
-            loss = loss + pacc_term(normalize_rot(p_pose))
+        loss = add_tail(loss, tail, out, p_pose)
         loss.backward()
         if verbose:
             print("Chamfer", n_eval[0], float(loss))
@@ -674,55 +417,36 @@ def optim_markers(
     execution.robust_fused / temporal_fused: False, under frame-block sharding and with shared betas.
     EXTENSION: `prior_weights` ([F, 23] >= 0, optional; engine.prior_weight_table) weigh reg_pose_body per frame and body joint
     (None, or ones everywhere, changes nothing; `img_mask` itself is not read)."""
-    prior_weights = _armed_prior_weights(config, "marker", prior_weights, markers.shape[0])
-    if frame_assign is not None:
-        return _optim_markers_frame_assign(markers, pose_body, o_pose_body, betas, o_betas, root_orient, trans, frame_assign,
-                                           smpl_inference, config, initial_angle, repeat, verbose, iter_fn, foot_contacts,
-                                           prior_weights)
-    one_hot = barycentric_coords_one_hot
-    if one_hot.dim() != 2 or one_hot.shape[1] != smpl_inference.device_model.V:
-        raise ValueError("barycentric_coords_one_hot must be [M, %d]" % smpl_inference.device_model.V)
-    rows_nz = (one_hot != 0).sum(dim=1)
-    from .parallel import frame_shard
+    from .parallel import frame_shard, shared_betas_reducer
 
+    stage_terms = _stage_terms(config, "marker", prior_weights, markers.shape[0])
+    prior_weights = stage_terms.prior_weights
+    one_hot = barycentric_coords_one_hot
+    if frame_assign is not None:
+        placement = "frame_table"
+    elif one_hot.dim() != 2 or one_hot.shape[1] != smpl_inference.device_model.V:
+        raise ValueError("barycentric_coords_one_hot must be [M, %d]" % smpl_inference.device_model.V)
+    else:  # one-hot, or barycentric (compute_locations.use_barycentric): up to three weighted vertices per marker, or more
+        placement = "one_hot" if is_one_hot_placement(one_hot) else "three" if int((one_hot != 0).sum(dim=1).max()) <= 3 else "more"
     fs = frame_shard()
-    sharded = fs is not None and fs.active
-    bary = None
-    if not _robust_fused(config, "marker") or not _temporal_fused(config, "marker") or not _floor_fused(config, "marker") or \
-            not _capsule_fused(config, "marker") or not _limit_fused(config, "marker") or \
-            not _prior_conf_fused(config, prior_weights) or _pose_accel_on(config, "marker"):
-        # EXTENSION: execution.robust_fused / temporal_fused / floor_fused / capsule_fused / limit_fused / prior_conf_fused:
-        # False -- the composed closure, the fused one's checker; the pose-acceleration term (pose_accel) always runs on it
-        _refuse_sharded_pose_accel(config, "marker")
+    route = stage_route(stage_terms, on_device=frame_assign is None and one_hot.is_cuda, sharded=fs is not None and fs.active,
+                        shared_betas=shared_betas_reducer() is not None, placement=placement)
+    if route == "composed":
         return _optim_markers_general(markers, pose_body, o_pose_body, betas, o_betas, root_orient, trans, one_hot,
                                       smpl_inference, config, verbose, iter_fn, initial_angle, repeat, foot_contacts,
-                                      prior_weights)
-    if not bool(((rows_nz == 1) & (one_hot.sum(dim=1) == 1.0)).all()):
-        # barycentric placement (compute_locations.use_barycentric): up to three weighted vertices per marker.  Fused closure
-        # (k_bary_fwd + k_bwd_items) when it is that and nothing else; execution.marker_bary_fused: False, more than three
-        # non-zeros in a row, or frame-block sharding keep the closure composed from the operators
-        fused = (one_hot.is_cuda and int(rows_nz.max()) <= 3 and not sharded and
-                 bool((config.get("execution") or {}).get("marker_bary_fused", True)))
-        if not fused:
-            if sharded:
-                _refuse_sharded_prior_weights(config, "marker", prior_weights)
-            return _optim_markers_general(markers, pose_body, o_pose_body, betas, o_betas, root_orient, trans, one_hot,
-                                          smpl_inference, config, verbose, iter_fn, initial_angle, repeat, foot_contacts,
-                                          prior_weights)
-        bary = placement_corners(one_hot)
-    assign = bary[0] if bary is not None else torch.argmax(one_hot, dim=-1)
-    if sharded:
-        _refuse_sharded_prior_weights(config, "marker", prior_weights)
+                                      prior_weights, stage_terms=stage_terms)
+    bary = placement_corners(one_hot) if placement == "three" else None
+    assign = bary[0] if bary is not None else torch.argmax(one_hot, dim=-1) if frame_assign is None else None
+    if route == "sharded":
         return _optim_markers_frame_sharded(fs, markers, pose_body, o_pose_body, betas, o_betas, root_orient, trans, assign,
-                                            smpl_inference, config, iter_fn)
+                                            smpl_inference, config, iter_fn, stage_terms=stage_terms)
     prob = MarkerProblem(smpl_inference, markers, o_pose_body, o_betas, assign, config, bary=None if bary is None else bary[1],
-                         foot_contacts=foot_contacts, prior_weights=prior_weights)
+                         foot_contacts=foot_contacts, frame_assign=frame_assign, prior_weights=prior_weights,
+                         stage_terms=stage_terms)
     x = prob.pack(pose_body, betas, root_orient, trans)
     if prob.has_offsets:  # EXTENSION: latent marker offsets, every solve from the data-driven start value
-        from .parallel import shared_betas_reducer
-
         if shared_betas_reducer() is not None:
-            _refuse_latent_offsets(config, "shared betas (parallel.shared_betas)")
+            stage_terms.refuse_latent_offsets("shared betas (parallel.shared_betas)")
         x[219 * prob.F + 10:] = prob.offsets_start(x).reshape(-1)
     point_cb = None
     if iter_fn is not None:
@@ -746,76 +470,27 @@ def optim_markers(
     return None
 
 
-def _optim_markers_frame_assign(markers, pose_body, o_pose_body, betas, o_betas, root_orient, trans, frame_assign, smpl_inference,
-                                config, initial_angle, repeat, verbose, iter_fn, foot_contacts, prior_weights=None):
-    """EXTENSION: optim_markers on a per-frame vertex table (uuo_fit_set_frame_assign)."""
-    from .parallel import frame_shard, shared_betas_reducer
-
-    what = "the per-frame vertex table (tracklets, extension)"
-    if _floor_on(config, "marker"):
-        raise NotImplementedError("%s is not built for the floor-contact term (stages.marker.losses.floor_penetration / "
-                                  "floor_contact)" % what)
-    if not _robust_fused(config, "marker") or not _temporal_fused(config, "marker") or not _capsule_fused(config, "marker") or \
-            not _limit_fused(config, "marker") or not _prior_conf_fused(config, prior_weights) or \
-            _pose_accel_on(config, "marker"):
-        raise NotImplementedError("%s is built for the fused marker closure only, not for the closure composed from the operators "
-                                  "(execution.robust_fused / temporal_fused / capsule_fused / limit_fused / prior_conf_fused: "
-                                  "False; stages.marker.losses.pose_accel)" % what)
-    _refuse_latent_offsets(config, what + ": an offset per column has no meaning once the column changes identity")
-    fs = frame_shard()
-    if fs is not None and fs.active:
-        raise NotImplementedError("%s is not built for frame-block sharding (parallel.shard_frames)" % what)
-    if shared_betas_reducer() is not None:
-        raise NotImplementedError("%s is not built for shared betas (parallel.shared_betas)" % what)
-    prob = MarkerProblem(smpl_inference, markers, o_pose_body, o_betas, None, config, foot_contacts=foot_contacts,
-                         frame_assign=frame_assign, prior_weights=prior_weights)
-    x = prob.pack(pose_body, betas, root_orient, trans)
-    point_cb = None
-    if iter_fn is not None:
-        def point_cb(i, loss, x_eval):
-            e_pose, e_betas, e_root, e_trans = prob.unpack(x_eval)[:4]
-            iter_fn(stage="marker_" + str(repeat), iteration=i, initial_angle=np.array([initial_angle]),
-                    pose_body=normalize_rot(e_pose).numpy(), betas=e_betas.numpy().copy(), trans=e_trans.numpy().copy(),
-                    root_orient=normalize_rot(e_root).numpy())
-
-    stats = _solve(prob, x, config, "marker", 1.0, "Marker", verbose, point_cb)
-    new_pose, new_betas, new_root, new_trans = prob.unpack(x)[:4]
-    with torch.no_grad():
-        pose_body.copy_(new_pose)
-        betas.copy_(new_betas)
-        root_orient.copy_(new_root)
-        trans.copy_(new_trans)
-    LAST_STATS["marker"] = stats
-    _tls_stats.marker = stats
-    return None
-
-
 def _optim_markers_general(markers, pose_body, o_pose_body, betas, o_betas, root_orient, trans, coords, smpl_inference,
-                           config, verbose, iter_fn=None, initial_angle=0, repeat=0, foot_contacts=None, prior_weights=None):
+                           config, verbose, iter_fn=None, initial_angle=0, repeat=0, foot_contacts=None, prior_weights=None,
+                           stage_terms=None):
     """Marker stage for a general placement matrix [M, V] (reference optimization.py:288-399 as written: virtual
     markers = coords @ vertices).  The fused device solver covers the one-hot placements of the shipped configs; this
     path composes the same closure from the differentiable HIP operators (SmplInference forward / uuo_smpl_backward)
     and drives it with torch.optim.LBFGS like the reference.  Mutates the four leaves in place."""
-    _refuse_latent_offsets(config, "the closure composed from the operators (more than three non-zeros per placement row, "
-                           "execution.robust_fused / temporal_fused / marker_bary_fused: False)")
+    stage_terms = stage_terms or StageTerms(config, "marker")
+    stage_terms.refuse_latent_offsets("the closure composed from the operators (more than three non-zeros per placement row, "
+                                      "execution.robust_fused / temporal_fused / marker_bary_fused: False)")
     st = config["stages"]["marker"]
-    unsupported = set(st["losses"]) - {"marker", "reg_pose_body", "reg_betas", "joint_accel", "latent_offsets", "foot_lock",
-                                       "floor_penetration", "floor_contact", "self_penetration", "joint_limits",
-                                       "pose_accel"}
+    unsupported = set(st["losses"]) - composed_keys("marker")
     if unsupported:
         raise NotImplementedError("marker-stage losses outside the shipped configs: %s" % sorted(unsupported))
     if st.get("use_sdf"):
         raise NotImplementedError("stages.marker.use_sdf is off in every shipped config")
-    sigma = stage_robust_sigma(config, "marker")  # EXTENSION: Geman-McClure data term (0 = the reference's square)
-    w_accel = stage_joint_accel(config, "marker")  # EXTENSION: joint-acceleration term
-    w_lock = stage_foot_lock(config, "marker")  # EXTENSION: foot-lock term, on the video's contact labels
+    sigma = stage_terms[ROBUST]  # EXTENSION: Geman-McClure data term (0 = the reference's square)
     contacts = check_foot_contacts(foot_contacts, pose_body.shape[0])
     if contacts is not None:
         contacts = contacts.to(pose_body.device)
-    floor_term = _composed_floor(config, "marker", contacts, smpl_inference)  # EXTENSION: floor-contact term on sole vertices
-    caps_term = _composed_capsules(config, "marker", smpl_inference)  # EXTENSION: bone-capsule self-penetration term
-    lim_term = _composed_limits(config, "marker")  # EXTENSION: joint-angle limit term on the body pose
-    pacc_term = _composed_pose_accel(config, "marker")  # EXTENSION: pose-acceleration term on the local body rotations
+    tail = stage_terms.composed_tail(st["losses"], contacts, smpl_inference)  # EXTENSION: the fused closures' terms, composed
     if prior_weights is not None:  # EXTENSION: the pose prior's weights (checked by the caller)
         prior_weights = prior_weights.to(pose_body.device)
     num_frames = pose_body.shape[0]
@@ -849,18 +524,7 @@ def _optim_markers_general(markers, pose_body, o_pose_body, betas, o_betas, root
                 loss = loss + F.mse_loss(p_pose, o_pose_body) * st["losses"]["reg_pose_body"]
         if "reg_betas" in st["losses"]:
             loss = loss + F.mse_loss(p_betas, o_betas) * st["losses"]["reg_betas"]
-        if "joint_accel" in st["losses"]:  # EXTENSION: the fused closures' joint-acceleration term, composed (their checker)
-            loss = loss + joint_accel_loss(out["joints"][:, :24]) * w_accel
-        if w_lock > 0.0 and contacts is not None:  # EXTENSION: the fused closures' foot-lock term, composed (their checker)
-            loss = loss + foot_lock_loss(out["joints"][:, :24], contacts) * w_lock
-        if floor_term is not None:  # EXTENSION: the fused closures' floor-contact term, composed (their checker)
-            loss = loss + floor_term(out["vertices"])
-        if caps_term is not None:  # EXTENSION: the fused closures' self-penetration term, composed (their checker)
-            loss = loss + caps_term(out["joints"])
-        if lim_term is not None:  # EXTENSION: the fused closures' joint-angle limit term, composed (their checker)
-            loss = loss + lim_term(normalize_rot(p_pose))
-        if pacc_term is not None:  # EXTENSION: the fused closures' pose-acceleration term, composed (their checker)
-            loss = loss + pacc_term(normalize_rot(p_pose))
+        loss = add_tail(loss, tail, out, p_pose)
         loss.backward()
         if verbose:
             print("Marker", n_eval[0], float(loss))

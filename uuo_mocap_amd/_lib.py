@@ -171,6 +171,8 @@ _DEBUG_SIGNATURES = {
                                    POINTER(UuoLbfgsStats), c_void_p, c_void_p]),
     "uuo_debug_fit_buffers": (c_int, [c_void_p, c_void_p, c_void_p]),
     "uuo_debug_nn_flags": (c_int, [c_void_p, c_void_p]),
+    "uuo_debug_nn_cull_geometry": (c_int, [c_int, c_int, c_int, c_void_p]),  # -> {groups, markers per group, LDS bytes, list entries}
+    "uuo_debug_nn_cull": (c_int, [c_void_p, c_int, c_int, c_int] + [c_void_p] * 5),  # the pruned search on the caller's cloud
     "uuo_debug_skin16_check": (c_int, [c_void_p, c_int]),
     "uuo_debug_small_coeffs": (c_int, [c_int, c_int, c_int, c_void_p]),
     "uuo_debug_time_small": (c_int, [c_int, c_int, c_int, POINTER(c_float)]),

@@ -711,39 +711,81 @@ int uuo_launch_nn(hipStream_t s, int N, int P1, int P2, const float* x, const fl
 // with lb > d_ub can neither improve nor tie the key and is dropped without an epsilon.  Survivors go to an LDS list;
 // phase B evaluates their 16 vertices (16 lanes per entry), reduces (dist bits << 32 | vertex) inside the DPP row
 // and merges with a 64-bit LDS atomicMin: the result equals the brute-force first-index minimum bit for bit.
-// A frame is split over several blocks by marker groups so that several waves share each SIMD.  If a block has too
-// many survivors for its LDS list (poor bounds: first call, markers far from the body) it enumerates all pairs.
+// A frame is split over several blocks by marker groups so that several waves share each SIMD.
+//
+// LDS.  k_skin3 is on the chip most of a fit's life, one block per CU, and leaves 53 248 B of a CU's LDS (SK3_LDS_PAD,
+// smpl_kernels.hip); a frame's search blocks run in one round beside it only if five of them fit there.  So the unit boxes
+// stay in global memory (they are L2 hits: k_skin3's epilogue and the frame's other blocks have just touched them), every
+// array is sized by the launch's markers per group and super-box count (dynamic LDS, cull_lds_bytes), and the survivor
+// list holds CULL_CAP pairs: the unit tests run in batches of CULL_CAP, each followed by phase B on what it listed, so
+// the list cannot overflow.  The keys merge through atomicMin, which does not depend on order: batches change no key.
+// A block whose bounds are poor (first call, markers far from the body: more than three quarters of its (marker, super-box)
+// pairs survive) skips the unit tests and enumerates all pairs in one pass.  The threshold is measured on the first call of a
+// 300 x 50 closure (no previous assignment): 101-103 us with it, as with the 3072-entry list this kernel had when its boxes
+// lived in LDS, and 231 us at one half -- super-boxes pass far more often than their units, so enumerating that early
+// evaluates many pairs the unit tests would have dropped.
+// stats[f][group]: the pairs phase B evaluated -- the survivor count, or minus the count of all pairs on the enumerate path.
 // ----------------------------------------------------------------------------------------------------
-#define CULL_CAP 3072
-#define CULL_CAP2 1024  // surviving (marker, super-box) pairs a block lists; more = poor bounds: enumerate everything
+#define CULL_CAP 1024  // (marker, unit) pairs per batch = entries of the survivor list; a multiple of CULL_T
 #define CULL_MG 64
 #define CULL_MAXU 512
 #define CULL_UB 4
 #define CULL_MAXG 8
-#ifndef CULL_SUPER
-#define CULL_SUPER 8  // units per super-box of the two-level box test (0: one level, rounds 1-3)
-#endif
+#define CULL_SUPER 8  // units per super-box of the two-level box test
 #ifndef CULL_T
 #define CULL_T 256  // threads per block (128: 7 us slower alone and 2 % slower fits; 512: no faster)
 #endif
+#define CULL_AB (CULL_CAP / CULL_T)  // unit tests per thread and batch, their box loads issued together
+static_assert(CULL_CAP % CULL_T == 0, "a batch of unit tests is a whole number of block passes");
+static_assert((CULL_MAXU + CULL_SUPER - 1) / CULL_SUPER <= 64 && CULL_MG <= 64, "a (marker, super-box) pair packs into 12 bits");
+// dynamic LDS of a block with `mper` markers per group and `nsup` super-boxes: skey, ssup, smx, sub, slist, slist2
+__host__ __device__ constexpr int cull_lds_bytes(int mper, int nsup) {
+  return 8 * mper + 24 * nsup + 12 * mper + 4 * mper + 4 * CULL_CAP + 2 * ((mper * nsup + 1) & ~1);
+}
+extern __shared__ __align__(8) unsigned char cull_lds[];
+__device__ __forceinline__ float cull_box_lb(float b0, float b1, float b2, float b3, float b4, float b5, float qx, float qy,
+                                             float qz) {
+  const float dx = fmaxf(fmaxf(__fsub_rn(b0, qx), __fsub_rn(qx, b3)), 0.f);
+  const float dy = fmaxf(fmaxf(__fsub_rn(b1, qy), __fsub_rn(qy, b4)), 0.f);
+  const float dz = fmaxf(fmaxf(__fsub_rn(b2, qz), __fsub_rn(qz, b5)), 0.f);
+  return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+}
 __device__ __forceinline__ void nn_cull_body(int M, int V, int nunits, int mper, const float* __restrict__ x,
                                              const float* __restrict__ verts, const float* __restrict__ bbox,
                                              unsigned long long* __restrict__ packed, int* __restrict__ stats) {
   __builtin_amdgcn_s_setprio(1);  // latency-bound kernel: do not queue behind co-resident MFMA waves
-  __shared__ float sbox[CULL_MAXU * 6];
-  __shared__ float smx[CULL_MG * 3];
-  __shared__ float sub[CULL_MG];
-  __shared__ unsigned long long skey[CULL_MG];
-  __shared__ unsigned slist[CULL_CAP];
-  __shared__ unsigned scount, scount2;
+  const int nsup = (nunits + CULL_SUPER - 1) / CULL_SUPER;
+  unsigned long long* skey = (unsigned long long*)cull_lds;  // [mper]
+  float* ssup = (float*)(skey + mper);                       // [nsup][6]
+  float* smx = ssup + nsup * 6;                              // [mper][3]
+  float* sub = smx + mper * 3;                               // [mper]
+  unsigned* slist = (unsigned*)(sub + mper);                 // [CULL_CAP]
+  unsigned short* slist2 = (unsigned short*)(slist + CULL_CAP);  // [mper * nsup]: every (marker, super-box) pair fits
+  __shared__ unsigned scount[2], scount2;
   const int f = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int m0 = blockIdx.y * mper;
   const int mg = min(mper, M - m0);
   if (mg <= 0) return;
   const float* vf = verts + (size_t)f * V * 3;
-  {  // unit bounding boxes of this frame (written by k_skin's epilogue) -> LDS
-    const float* bf = bbox + (size_t)f * nunits * 6;
-    for (int i = tid; i < nunits * 6; i += CULL_T) sbox[i] = bf[i];
+  const float* bf = bbox + (size_t)f * nunits * 6;  // unit bounding boxes of this frame (written by k_skin's epilogue)
+  // ---- phase A, two levels.  A marker needs a unit only if the unit's box can hold a vertex at most d_ub away; 2-3 % of
+  // the 21 550 (marker, unit) pairs of a frame pass that test, and testing them all was most of this kernel's vector work
+  // (as many VALU cycles per launch as k_skin2's whole epilogue, profiles/r2_pmc_sq_summary.json).  The boxes of CULL_SUPER
+  // consecutive units are merged into a super-box first; a marker is tested against the 54 super-boxes, and against the
+  // units of the survivors only.  The lower bound of a super-box is <= that of each of its units (every operation of the
+  // bound is monotone), so exactly the same (marker, unit) pairs survive as with one level: bit-identical result.
+  // Super-boxes straight from the global box table: thread = unit (consecutive 24-byte rows: the table is read once, in whole
+  // lines), min / max over the CULL_SUPER lanes of a super-box.  Both passes' loads are issued first, ahead of the markers'
+  // dependent loads below, so that the first wave's three round trips overlap.
+  static_assert(CULL_MAXU <= 2 * CULL_T && CULL_SUPER == 8, "two passes of one unit per thread, a super-box = 8 lanes");
+  float w[2][6];
+#pragma unroll
+  for (int p = 0; p < 2; ++p) {
+    if (p * CULL_T < nunits) {  // (past the last unit: the last unit again, which changes no min / max)
+      const float2* pb = (const float2*)(bf + min(p * CULL_T + tid, nunits - 1) * 6);  // (24-byte rows: 8-byte aligned)
+      const float2 lo = pb[0], mid = pb[1], hi = pb[2];
+      w[p][0] = lo.x, w[p][1] = lo.y, w[p][2] = mid.x, w[p][3] = mid.y, w[p][4] = hi.x, w[p][5] = hi.y;
+    }
   }
   if (tid < mg) {
     const float* px = x + ((size_t)f * M + m0 + tid) * 3;
@@ -758,142 +800,123 @@ __device__ __forceinline__ void nn_cull_body(int M, int V, int nunits, int mper,
     skey[tid] = key;
     sub[tid] = __uint_as_float((unsigned)(key >> 32));
   }
-  if (tid == 0) scount = 0u;
-  if (tid == 1) scount2 = 0u;
-  __syncthreads();
-#if CULL_SUPER
-  // ---- phase A, two levels (round 4).  A marker needs a unit only if the unit's box can hold a vertex at most d_ub away;
-  // 2-3 % of the 21 550 (marker, unit) pairs of a frame pass that test, and testing them all was most of this kernel's
-  // vector work (as many VALU cycles per launch as k_skin2's whole epilogue, profiles/r2_pmc_sq_summary.json).  The boxes of
-  // CULL_SUPER consecutive units are merged into a super-box first; a marker is tested against the 54 super-boxes, and
-  // against the units of the survivors only.  The lower bound of a super-box is <= that of each of its units (every
-  // operation of the bound is monotone), so exactly the same (marker, unit) pairs survive as before: bit-identical result.
-  constexpr int NSUP_MAX = (CULL_MAXU + CULL_SUPER - 1) / CULL_SUPER;
-  __shared__ float ssup[NSUP_MAX * 6];
-  __shared__ unsigned slist2[CULL_CAP2];
-  const int nsup = (nunits + CULL_SUPER - 1) / CULL_SUPER;
-  for (int sidx = tid; sidx < nsup * 6; sidx += CULL_T) {
-    const int sp = sidx / 6, c = sidx - sp * 6;
-    const int u0 = sp * CULL_SUPER, u1 = min(nunits, u0 + CULL_SUPER);
-    float v = sbox[u0 * 6 + c];
-    for (int u = u0 + 1; u < u1; ++u) v = (c < 3) ? fminf(v, sbox[u * 6 + c]) : fmaxf(v, sbox[u * 6 + c]);
-    ssup[sidx] = v;
+  if (tid == 0) scount[0] = scount[1] = scount2 = 0u;
+  {
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      if (p * CULL_T < nunits) {
+#pragma unroll
+        for (int c = 0; c < 6; ++c) {  // DPP: lane ^ 1, lane ^ 2 (quad_perm), then 7 - lane (row_half_mirror: the other quad)
+          float v = w[p][c];
+          v = (c < 3) ? fminf(v, dpp_rot<0xB1>(v)) : fmaxf(v, dpp_rot<0xB1>(v));
+          v = (c < 3) ? fminf(v, dpp_rot<0x4E>(v)) : fmaxf(v, dpp_rot<0x4E>(v));
+          w[p][c] = (c < 3) ? fminf(v, dpp_rot<0x141>(v)) : fmaxf(v, dpp_rot<0x141>(v));
+        }
+        const int sp = (p * CULL_T + tid) / CULL_SUPER;
+        if ((tid & (CULL_SUPER - 1)) == 0 && sp < nsup) {
+#pragma unroll
+          for (int c = 0; c < 6; ++c) ssup[sp * 6 + c] = w[p][c];
+        }
+      }
+    }
   }
   __syncthreads();
   for (int e = tid; e < nsup * mg; e += CULL_T) {  // (super-box, marker) pairs
     const int sp = e / mg, m = e - sp * mg;
     const float* b = ssup + sp * 6;
-    const float qx = smx[m * 3], qy = smx[m * 3 + 1], qz = smx[m * 3 + 2];
-    const float dx = fmaxf(fmaxf(__fsub_rn(b[0], qx), __fsub_rn(qx, b[3])), 0.f);
-    const float dy = fmaxf(fmaxf(__fsub_rn(b[1], qy), __fsub_rn(qy, b[4])), 0.f);
-    const float dz = fmaxf(fmaxf(__fsub_rn(b[2], qz), __fsub_rn(qz, b[5])), 0.f);
-    const float lb = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-    if (lb <= sub[m]) {
-      const unsigned pos = atomicAdd(&scount2, 1u);
-      if (pos < CULL_CAP2) slist2[pos] = ((unsigned)m << 16) | (unsigned)sp;
-    }
+    const float lb = cull_box_lb(b[0], b[1], b[2], b[3], b[4], b[5], smx[m * 3], smx[m * 3 + 1], smx[m * 3 + 2]);
+    if (lb <= sub[m]) slist2[atomicAdd(&scount2, 1u)] = (unsigned short)((m << 6) | sp);
   }
   __syncthreads();
   const int found2 = (int)scount2;
-  if (found2 > CULL_CAP2 && tid == 0) scount = CULL_CAP + 1u;  // (the overflow path below enumerates all pairs)
-  for (int e = tid; e < min(found2, CULL_CAP2 + 0) * CULL_SUPER && found2 <= CULL_CAP2; e += CULL_T) {  // the units of the surviving super-boxes
-    const unsigned ent = slist2[e / CULL_SUPER];
-    const int m = (int)(ent >> 16), u = (int)(ent & 0xFFFFu) * CULL_SUPER + (e % CULL_SUPER);
-    if (u < nunits) {
-      const float* b = sbox + u * 6;
-      const float qx = smx[m * 3], qy = smx[m * 3 + 1], qz = smx[m * 3 + 2];
-      const float dx = fmaxf(fmaxf(__fsub_rn(b[0], qx), __fsub_rn(qx, b[3])), 0.f);
-      const float dy = fmaxf(fmaxf(__fsub_rn(b[1], qy), __fsub_rn(qy, b[4])), 0.f);
-      const float dz = fmaxf(fmaxf(__fsub_rn(b[2], qz), __fsub_rn(qz, b[5])), 0.f);
-      const float lb = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-      if (lb <= sub[m]) {
-        const unsigned pos = atomicAdd(&scount, 1u);
-        if (pos < CULL_CAP) slist[pos] = ((unsigned)m << 16) | (unsigned)u;
-      }
-    }
-  }
-#else
-  // ---- phase A: thread = unit (box in registers); the marker loop only sets bits of a survivor mask (no branch,
-  // no atomic on the loop path), then one LDS atomicAdd per thread reserves the list slots
-  for (int u = tid; u < nunits; u += CULL_T) {
-    const float* b = sbox + u * 6;
-    const float b0 = b[0], b1 = b[1], b2 = b[2], b3 = b[3], b4 = b[4], b5 = b[5];
-    unsigned long long mask = 0ull;
-#pragma unroll 4
-    for (int m = 0; m < mg; ++m) {
-      const float qx = smx[m * 3], qy = smx[m * 3 + 1], qz = smx[m * 3 + 2];
-      const float dx = fmaxf(fmaxf(__fsub_rn(b0, qx), __fsub_rn(qx, b3)), 0.f);
-      const float dy = fmaxf(fmaxf(__fsub_rn(b1, qy), __fsub_rn(qy, b4)), 0.f);
-      const float dz = fmaxf(fmaxf(__fsub_rn(b2, qz), __fsub_rn(qz, b5)), 0.f);
-      const float lb = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-      mask |= (lb <= sub[m]) ? (1ull << m) : 0ull;
-    }
-    const int cnt = __popcll(mask);
-    if (cnt) {
-      unsigned pos = atomicAdd(&scount, (unsigned)cnt);
-      while (mask) {
-        const int m = __ffsll((long long)mask) - 1;
-        mask &= mask - 1;
-        if (pos < CULL_CAP) slist[pos] = ((unsigned)m << 16) | (unsigned)u;
-        ++pos;
-      }
-    }
-  }
-#endif
-  __syncthreads();
-  const int found = (int)scount;
-  const bool overflow = found > CULL_CAP;  // poor bounds (first call, markers far from the body): enumerate all pairs
-  const int nent = overflow ? nunits * mg : found;
-  // ---- phase B: 16 lanes per (marker, unit) pair, 4 pairs per wave pass, CULL_UB passes in flight
-  // (the vertex gathers are L2 round trips: issue them for several passes before the first is consumed)
-  for (int e0 = wave * 4 * CULL_UB; e0 < nent; e0 += (CULL_T / 64) * 4 * CULL_UB) {
-    unsigned long long key[CULL_UB];
-    int mm[CULL_UB];
-    float vx[CULL_UB], vy[CULL_UB], vz[CULL_UB];
-    int vid[CULL_UB];
+  const bool enumerate = 4 * found2 > 3 * nsup * mg;  // poor bounds: every pair, without the unit tests
+  const int ntest = enumerate ? 0 : found2 * CULL_SUPER;  // the units of the surviving super-boxes
+  int found = 0;
+  for (int base = 0, batch = 0;; base += CULL_CAP, ++batch) {
+    int nent = nunits * mg;
+    if (!enumerate) {
+      // ---- the unit tests of this batch: the boxes are global loads (L2 hits), all of a thread's issued before the first is used
+      float bx[CULL_AB][6];
+      int tm[CULL_AB], tu[CULL_AB];
 #pragma unroll
-    for (int r = 0; r < CULL_UB; ++r) {
-      const int e = e0 + 4 * r + (lane >> 4);
-      mm[r] = 0;
-      vid[r] = -1;
-      vx[r] = vy[r] = vz[r] = 0.f;
-      if (e < nent) {
+      for (int r = 0; r < CULL_AB; ++r) {
+        const int e = base + r * CULL_T + tid;
+        tu[r] = -1;
+        tm[r] = 0;
+#pragma unroll
+        for (int c = 0; c < 6; ++c) bx[r][c] = 0.f;
+        if (e < ntest) {
+          const unsigned ent = slist2[e / CULL_SUPER];
+          const int u = (int)(ent & 63u) * CULL_SUPER + (e % CULL_SUPER);
+          if (u < nunits) {
+            const float2* pb = (const float2*)(bf + u * 6);  // (24-byte rows of a hipMalloc'ed table: 8-byte aligned)
+            const float2 lo = pb[0], mid = pb[1], hi = pb[2];
+            bx[r][0] = lo.x, bx[r][1] = lo.y, bx[r][2] = mid.x, bx[r][3] = mid.y, bx[r][4] = hi.x, bx[r][5] = hi.y;
+            tm[r] = (int)(ent >> 6);
+            tu[r] = u;
+          }
+        }
+      }
+      unsigned* cnt = &scount[batch & 1];
+#pragma unroll
+      for (int r = 0; r < CULL_AB; ++r) {
+        const int m = tm[r];
+        const float lb = cull_box_lb(bx[r][0], bx[r][1], bx[r][2], bx[r][3], bx[r][4], bx[r][5], smx[m * 3], smx[m * 3 + 1],
+                                     smx[m * 3 + 2]);
+        if (tu[r] >= 0 && lb <= sub[m]) slist[atomicAdd(cnt, 1u)] = ((unsigned)m << 16) | (unsigned)tu[r];
+      }
+      __syncthreads();
+      nent = (int)*cnt;
+      found += nent;
+      if (tid == 0) scount[(batch + 1) & 1] = 0u;  // the next batch's counter: nobody reads it before the barrier below
+    }
+    // ---- phase B: 16 lanes per (marker, unit) pair, 4 pairs per wave pass, CULL_UB passes in flight
+    // (the vertex gathers are L2 round trips: issue them for several passes before the first is consumed)
+    for (int e0 = wave * 4 * CULL_UB; e0 < nent; e0 += (CULL_T / 64) * 4 * CULL_UB) {
+      unsigned long long key[CULL_UB];
+      int mm[CULL_UB];
+      float vx[CULL_UB], vy[CULL_UB], vz[CULL_UB];
+      int vid[CULL_UB];
+#pragma unroll
+      for (int r = 0; r < CULL_UB; ++r) {
+        // no branch around the loads (a pair past the end reads the last pair's vertices, a lane past V the last vertex,
+        // and is masked by vid): with branches the compiler waits for each pass's load before it issues the next
+        const int e = e0 + 4 * r + (lane >> 4), ec = min(e, nent - 1);
         int u;
-        if (overflow) {
-          u = e / mg;
-          mm[r] = e - u * mg;
+        if (enumerate) {
+          u = ec / mg;
+          mm[r] = ec - u * mg;
         } else {
-          const unsigned ent = slist[e];
+          const unsigned ent = slist[ec];
           mm[r] = (int)(ent >> 16);
           u = (int)(ent & 0xFFFFu);
         }
         const int vtx = u * 16 + (lane & 15);
-        if (vtx < V) {
-          const float* pv = vf + (size_t)vtx * 3;
-          vx[r] = pv[0];
-          vy[r] = pv[1];
-          vz[r] = pv[2];
-          vid[r] = vtx;
+        const float* pv = vf + (size_t)min(vtx, V - 1) * 3;
+        vx[r] = pv[0];
+        vy[r] = pv[1];
+        vz[r] = pv[2];
+        vid[r] = (e < nent && vtx < V) ? vtx : -1;
+      }
+#pragma unroll
+      for (int r = 0; r < CULL_UB; ++r) {
+        const int m = mm[r];
+        key[r] = (vid[r] >= 0)
+                     ? pack_key(sqdist(smx[m * 3], smx[m * 3 + 1], smx[m * 3 + 2], vx[r], vy[r], vz[r]), (unsigned)vid[r])
+                     : ~0ull;
+#pragma unroll
+        for (int off = 8; off >= 1; off >>= 1) {
+          const unsigned long long o = __shfl_xor(key[r], off, 16);
+          key[r] = o < key[r] ? o : key[r];
         }
+        if ((lane & 15) == 0 && key[r] != ~0ull) atomicMin(&skey[m], key[r]);
       }
     }
-#pragma unroll
-    for (int r = 0; r < CULL_UB; ++r) {
-      const int m = mm[r];
-      key[r] = (vid[r] >= 0)
-                   ? pack_key(sqdist(smx[m * 3], smx[m * 3 + 1], smx[m * 3 + 2], vx[r], vy[r], vz[r]), (unsigned)vid[r])
-                   : ~0ull;
-#pragma unroll
-      for (int off = 8; off >= 1; off >>= 1) {
-        const unsigned long long o = __shfl_xor(key[r], off, 16);
-        key[r] = o < key[r] ? o : key[r];
-      }
-      if ((lane & 15) == 0 && key[r] != ~0ull) atomicMin(&skey[m], key[r]);
-    }
+    __syncthreads();  // the batch's list is consumed (and, after the last batch, the keys are final)
+    if (base + CULL_CAP >= ntest) break;
   }
-  __syncthreads();
   if (tid < mg) packed[(size_t)f * M + m0 + tid] = skey[tid];
-  if (tid == 0 && stats) stats[f * CULL_MAXG + blockIdx.y] = overflow ? -found : found;
+  if (tid == 0 && stats) stats[f * CULL_MAXG + blockIdx.y] = enumerate ? -(nunits * mg) : found;
 }
 
 struct NnCullArgs {
@@ -913,21 +936,46 @@ __global__ __launch_bounds__(CULL_T) void k_nn_cull_b(const NnCullArgs* __restri
   nn_cull_body(a.M, a.V, a.nunits, a.mper, a.x, a.verts, a.bbox, a.packed, a.stats);
 }
 
+// marker groups per frame: enough blocks (>= ~1024) that several waves share a SIMD, at most 64 markers per group
+static void cull_geometry(int F, int M, int nunits, int* G_out, int* mper_out, int* lds_out) {
+  int G = (M + CULL_MG - 1) / CULL_MG;
+  while (G < CULL_MAXG && (long)F * G < 1024 && (M + G) / (G + 1) >= 8) ++G;
+  *G_out = G;
+  *mper_out = (M + G - 1) / G;
+  *lds_out = cull_lds_bytes(*mper_out, (nunits + CULL_SUPER - 1) / CULL_SUPER);
+}
+
 int uuo_launch_nn_cull(hipStream_t s, int F, int M, int V, int nunits, const float* markers, const float* verts,
                        const float* bbox, unsigned long long* packed, int* stats) {
   if (F <= 0 || M <= 0) return 0;
-  UUO_REQUIRE(nunits <= CULL_MAXU, "uuo_launch_nn_cull: too many vertex units for the LDS box table");
-  // marker groups per frame: enough blocks (>= ~1024) that several waves share a SIMD, at most 64 markers per group
-  int G = (M + CULL_MG - 1) / CULL_MG;
-  while (G < CULL_MAXG && (long)F * G < 1024 && (M + G) / (G + 1) >= 8) ++G;
-  const int mper = (M + G - 1) / G;
+  UUO_REQUIRE(nunits >= 1 && nunits <= CULL_MAXU, "uuo_launch_nn_cull: too many vertex units for the box table");
+  int G, mper, lds;
+  cull_geometry(F, M, nunits, &G, &mper, &lds);
   UUO_REQUIRE(mper <= CULL_MG && G <= CULL_MAXG, "uuo_launch_nn_cull: too many markers per frame for the pruned search");
   NnCullArgs a{{F, G}, M, V, nunits, mper, markers, verts, bbox, packed, stats};
   if (uuo_record(UUO_OP_NN_CULL, F, G, a)) return 0;
-  hipLaunchKernelGGL(k_nn_cull, dim3(F, G), dim3(CULL_T), 0, s, a);
+  hipLaunchKernelGGL(k_nn_cull, dim3(F, G), dim3(CULL_T), lds, s, a);
   UUO_HIP_CHECK(hipGetLastError());
   return 0;
 }
+
+#ifdef UUO_DEBUG_HOOKS
+// debug/test hooks (not in the public header).  The launch geometry of the pruned search: out = {groups per frame, markers
+// per group, dynamic LDS bytes of a block, entries of the survivor list}; host only
+extern "C" int uuo_debug_nn_cull_geometry(int F, int M, int nunits, int* out) {
+  UUO_REQUIRE(F > 0 && M > 0 && nunits >= 1 && nunits <= CULL_MAXU && out, "uuo_debug_nn_cull_geometry: bad arguments");
+  cull_geometry(F, M, nunits, &out[0], &out[1], &out[2]);
+  out[3] = CULL_CAP;
+  return 0;
+}
+// the pruned search on the caller's own cloud: d_verts [F][V][3], d_bbox [F][ceil(V / 16)][6] (min xyz, max xyz of each
+// 16-vertex unit), d_keys [F][M] in (previous assignment in the low word) and out, d_stats [F][8]
+extern "C" int uuo_debug_nn_cull(void* stream, int F, int M, int V, const float* d_markers, const float* d_verts,
+                                 const float* d_bbox, unsigned long long* d_keys, int* d_stats) {
+  UUO_REQUIRE(V > 0 && d_markers && d_verts && d_bbox && d_keys, "uuo_debug_nn_cull: bad arguments");
+  return uuo_launch_nn_cull((hipStream_t)stream, F, M, V, (V + 15) / 16, d_markers, d_verts, d_bbox, d_keys, d_stats);
+}
+#endif
 
 // batched launches of this file's kernels (uuo_common.h): 0 = launched, 1 = not one of mine, < 0 = error
 int uuo_batched_launch_nn(int op, hipStream_t s, const void* d_args, int count, int gx, int gy) {
@@ -938,7 +986,9 @@ int uuo_batched_launch_nn(int op, hipStream_t s, const void* d_args, int count, 
   } else if (op == UUO_OP_NN_FEWQ) {
     hipLaunchKernelGGL(k_nn_fewq_b, dim3(gx, gy, count), dim3(256), 0, s, (const NnArgs*)d_args);
   } else if (op == UUO_OP_NN_CULL) {
-    hipLaunchKernelGGL(k_nn_cull_b, dim3(gx, gy, count), dim3(CULL_T), 0, s, (const NnCullArgs*)d_args);
+    // (the records' markers per group and unit counts differ and live in device memory: the LDS of the largest block)
+    hipLaunchKernelGGL(k_nn_cull_b, dim3(gx, gy, count), dim3(CULL_T), cull_lds_bytes(CULL_MG, CULL_MAXU / CULL_SUPER), s,
+                       (const NnCullArgs*)d_args);
   } else if (op == UUO_OP_PART_FWD) {  // gx = frames of the longest problem, gy = markers per frame (one value per batch)
     const dim3 grid(8 * ((gx + 7) / 8) * count);
     const PartFwdArgs* pa = (const PartFwdArgs*)d_args;

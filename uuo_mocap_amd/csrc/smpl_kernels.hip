@@ -795,6 +795,9 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 // passes, k_finalize and k_pose_prep (<= 43 KB) still fit -- with a pad that kept k_bwd_sparse out the fit in flight was 2.4 %
 // slower.  With this pad: 184 009 launches of fits in flight checked against the fp32 kernel, 0 values off
 // (tools/skin16_stress.py, debug flavour).
+// The 163 840 - 110 592 = 53 248 B that a block leaves free on its CU are a budget the pruned search relies on: five k_nn_cull
+// blocks (<= 10 240 B each at the benchmark's shape, nn_kernels.hip) run beside it, a frame's 1 200 blocks in one round.  Keep
+// the two numbers together: a larger pad takes search blocks off the CU.
 #ifndef SK3_WAVES
 #define SK3_WAVES 4
 #endif

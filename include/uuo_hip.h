@@ -324,6 +324,30 @@ int uuo_fit_set_joint_limits(uuo_fit_t* fit, float w, const float* h_lo, const f
  * point-to-surface term and the per-frame vertex table.  Refused (at evaluation, -22) for the part stage and with w_soft != 0,
  * and inside lock-step batches (uuo_batch_*).  uuo_problem_t and uuo_abi_version() are unchanged. */
 int uuo_fit_set_prior_weights(uuo_fit_t* fit, const float* d_weights);
+/* EXTENSION (not reference behaviour; SMPLify's data term is the classic of this kind; the reference projects key points in its
+ * 2D-prior stage only): a 2D key-point reprojection term on the 24 kinematic joints J[t][j] = G_j^t + trans_t of the chamfer
+ * and marker stages.  Frame t carries a pinhole camera in WORLD axes, d_cam[t] = 16 floats: A (3x3, row-major), b (3), fx, fy,
+ * cx, cy; d_targets[t][j] are two image coordinates, d_conf[t][j] >= 0 a confidence:
+ *   p = A J + b,  u = (fx p_x / p_z + cx, fy p_y / p_z + cy),  r = u - y,  s = |r|^2
+ *   valid[t][j] = c > 0 and p finite and p_z >= min_depth
+ *   loss += w / (48 F) sum_valid c rho(s)        rho(s) = s sigma^2 / (sigma^2 + s) (Geman-McClure);  sigma == 0: rho(s) = s
+ *   k = 2 w c rho'(s) / (48 F),   rho' = (sigma^2 / (sigma^2 + s))^2;  sigma == 0: 1
+ *   dL/dp = k (r_x fx / p_z, r_y fy / p_z, -(r_x fx p_x + r_y fy p_y) / p_z^2),   dL/dJ = A^T dL/dp
+ * in the camera's own units (pixels, or units of the image size): the weight belongs to them.  48 F is the size of the target
+ * array.  An invalid pair contributes exact zeros to the loss and to the gradient.  Frames are not coupled: F = 1 is a valid
+ * problem.  The gradient reaches the translation, the shape, the root orientation (z in the chamfer stage) and the body pose.
+ * A setting of the WORKSPACE (off at creation) with the lifetime rules of uuo_fit_set_floor: the three arrays are device
+ * pointers that the caller keeps alive and may rewrite; they are read at every evaluation, not copied and not checked (finite
+ * values and confidences >= 0 are the caller's duty).  w == 0 switches the term off, nothing else is then looked at and the
+ * pointers may be null; every result is that of a workspace that never had the setting.  Errors (-22): a negative or non-finite
+ * w, sigma < 0, non-finite or with a square that is no normal float (outside [1e-18, 1e18]), min_depth <= 0 or non-finite, a
+ * null array with w > 0.  Sums in a fixed order, no atomics: results are bit-reproducible.  Works with robust_sigma, the
+ * joint-acceleration, foot-lock, floor-contact, self-penetration and joint-angle limit terms, the pose prior's weights, the
+ * latent marker offsets, three-corner placements, the point-to-surface term and the per-frame vertex table.  Refused (at
+ * evaluation, -22) for the part stage and with w_soft != 0, and inside lock-step batches (uuo_batch_*).  uuo_problem_t and
+ * uuo_abi_version() are unchanged. */
+int uuo_fit_set_keypoints2d(uuo_fit_t* fit, float w, float sigma, float min_depth, const float* d_cam, const float* d_targets,
+                            const float* d_conf);
 /* EXTENSION (not reference behaviour; MoSh-style fitters score a marker by its distance to the SKIN less its stand-off, the
  * reference's chamfer term by its distance to the nearest VERTEX): on = 1 replaces the chamfer stage's data term
  * min_v |x - v|^2 by the point-to-surface term on the one-ring of the nearest vertex v^ the closure's search finds anyway:

@@ -133,6 +133,9 @@ _SIGNATURES = {
     "uuo_fit_set_joint_limits": (c_int, [c_void_p, c_float, c_void_p, c_void_p]),
     # EXTENSION: per-(frame, joint) weights of the pose prior of the workspace (device [F][23]; null = off)
     "uuo_fit_set_prior_weights": (c_int, [c_void_p, c_void_p]),
+    # EXTENSION: 2D key-point reprojection term of the workspace (w, sigma, min_depth, device cameras [F][16], targets
+    # [F][24][2], confidences [F][24])
+    "uuo_fit_set_keypoints2d": (c_int, [c_void_p, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p]),
     "uuo_problem_num_params": (c_int, [POINTER(UuoProblem)]),
     "uuo_closure_eval": (c_int, [c_void_p, c_void_p, POINTER(UuoProblem), c_void_p, c_void_p, c_void_p, c_void_p]),
     "uuo_lbfgs_solve": (c_int, [c_void_p, c_void_p, POINTER(UuoProblem), c_void_p, POINTER(UuoLbfgsOptions),

@@ -1792,6 +1792,14 @@ static int validate_problem(const uuo_fit* fit, const uuo_problem_t* p) {
               "term (w_soft)");
   UUO_REQUIRE(fit->cap_w == 0.f || !uuo_recorder,
               "closure: lock-step batches do not carry the self-penetration term (uuo_fit_set_capsules, extension)");
+  // EXTENSION: the key-point reprojection term of the workspace (uuo_fit_set_keypoints2d) likewise
+  UUO_REQUIRE(fit->kp_w == 0.f || p->stage != UUO_STAGE_PART,
+              "closure: the key-point reprojection term (uuo_fit_set_keypoints2d, extension) is not built for the part stage");
+  UUO_REQUIRE(fit->kp_w == 0.f || p->w_soft == 0.f,
+              "closure: the key-point reprojection term (uuo_fit_set_keypoints2d, extension) is not built for the soft-assignment "
+              "data term (w_soft)");
+  UUO_REQUIRE(fit->kp_w == 0.f || !uuo_recorder,
+              "closure: lock-step batches do not carry the key-point reprojection term (uuo_fit_set_keypoints2d, extension)");
   // EXTENSION: the joint-angle limit term of the workspace (uuo_fit_set_joint_limits) likewise
   UUO_REQUIRE(fit->lim_w == 0.f || p->stage != UUO_STAGE_PART,
               "closure: the joint-angle limit term (uuo_fit_set_joint_limits, extension) is not built for the part stage");
@@ -2306,7 +2314,13 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
   // frames' shares, the temporal instantiations add them to uj and slot 3 (cap_up != null).  Frames are not coupled: any F.
   const bool caps = fit->cap_w != 0.f;
   UUO_REQUIRE(!caps || !uuo_recorder, "closure: lock-step batches do not carry the self-penetration term");
-  if (caps) a.cap_up = fit->cap_up;  // ([F][72] gradients, then the [F] shares)
+  // EXTENSION: the key-point reprojection term: k_keypoint2d_fwd (launch_side_terms below, after k_capsule_fwd) leaves -- or, with
+  // the capsules on, adds -- its d loss / d G_j^t and the frames' shares in the same buffer.  Frames are not coupled: any F.
+  const bool kp = fit->kp_w != 0.f;
+  UUO_REQUIRE(!kp || !uuo_recorder, "closure: lock-step batches do not carry the key-point reprojection term");
+  UUO_REQUIRE(!kp || (p->stage != UUO_STAGE_PART && !soft_chamfer),
+              "closure: the key-point reprojection term belongs to the chamfer and marker stages' hard-assignment closures");
+  if (caps || kp) a.cap_up = fit->cap_up;  // ([F][72] gradients, then the [F] shares)
   // EXTENSION: the joint-angle limit term: k_limit_fwd (launch_side_terms below) leaves the parameter-space
   // gradients and the frames' shares, the temporal instantiations add them to gout and slot 3 (lim_g != null).  Any F.
   const bool limits = fit->lim_w != 0.f;
@@ -2326,11 +2340,11 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
     a.cpose = 0.f;
     a.lim_g = fit->lim_g;
   }
-  // the forward kernels of the four terms above (side_terms.hip), for the routes below to launch once fit->frames is there
+  // the forward kernels of the five terms above (side_terms.hip), for the routes below to launch once fit->frames is there
   auto launch_side_terms = [&]() {
-    uuo_launch_side_terms(fit, s, F, src, prior ? d_x + lay.off_pose : nullptr, p->d_o_pose, p->w_pose, UuoSideTerms{floor, caps, limits, prior});
+    uuo_launch_side_terms(fit, s, F, src, prior ? d_x + lay.off_pose : nullptr, p->d_o_pose, p->w_pose, UuoSideTerms{floor, caps, limits, prior, kp});
   };
-  const bool temporal = accel || lock || floor || caps || limits || prior;
+  const bool temporal = accel || lock || floor || caps || limits || prior || kp;
   a.h.gx = F;
   a.h.gy = 1;
   FinArgs fa;

@@ -1,7 +1,8 @@
-// Forward kernels of the closures' side terms -- floor contact, bone-capsule self-penetration, joint-angle limits, the pose
-// prior's per-(frame, joint) weights -- with the setters that configure them on a fit workspace.  Each kernel leaves upstream
-// gradients and per-frame loss shares for the backward kernels of the same evaluation (closure.hip: the temporal instantiations
-// of bwd_body); they share no device code with it but frame_math.h.  closure.hip reaches them through uuo_launch_side_terms.
+// Forward kernels of the closures' side terms -- floor contact, bone-capsule self-penetration, 2D key-point reprojection,
+// joint-angle limits, the pose prior's per-(frame, joint) weights -- with the setters that configure them on a fit workspace.
+// Each kernel leaves upstream gradients and per-frame loss shares for the backward kernels of the same evaluation (closure.hip:
+// the temporal instantiations of bwd_body); they share no device code with it but frame_math.h.  closure.hip reaches them
+// through uuo_launch_side_terms.
 #include <cstring>
 
 #include "frame_math.h"
@@ -408,6 +409,85 @@ __global__ __launch_bounds__(64) void k_prior_conf(PriorConfArgs a) {
   if (head) a.g[(size_t)a.F * 207 + f] = old_share + a.cl * part;
 }
 
+// ----------------------------------------------------------------------------------------------------
+// EXTENSION (not reference behaviour; uuo_fit_set_keypoints2d): a 2D key-point reprojection term on the 24 kinematic joints
+// J[t][j] = G_j^t + trans_t.  Frame t carries a pinhole camera in world axes, cam[t] = (A 3x3 row-major, b, fx, fy, cx, cy),
+// targets y[t][j] and confidences c[t][j] >= 0:
+//   p = A J + b,  u = (fx p_x / p_z + cx, fy p_y / p_z + cy),  r = u - y,  s = |r|^2,
+//   valid = c > 0 and p finite and p_z >= min_depth,
+//   loss += w / (48 F) sum_valid c rho(s)       (rho(s) = s q, q = sigma^2 / (sigma^2 + s); sigma = 0: rho(s) = s)
+//   k = 2 w c rho'(s) / (48 F)                  (rho' = q^2; sigma = 0: 1)
+//   dL/dp = k (r_x fx / p_z, r_y fy / p_z, -(r_x fx p_x + r_y fy p_y) / p_z^2),  dL/dJ = A^T dL/dp.
+// An invalid pair contributes exact zeros (selected, not multiplied).
+// k_keypoint2d_fwd delivers dL/dG_j^t and the frames' shares through the buffer of the self-penetration term, [F][24][3] and
+// [F] behind them, which the temporal instantiations add to uj -- from where the translation takes the joints' sum -- and to
+// slot 3 (cap_up != null): no existing kernel changes.  add == 0: it writes the buffer; add != 0 (the capsules are on,
+// k_capsule_fwd of this evaluation ran before it on the same stream): it adds to it.
+// The shape of k_limit_fwd: 32 lanes per frame, two frames per 64-thread block.  Lane l < 24 of a half takes joint l: its G^t
+// of the frame's FrameLds (as the closure's forward or k_pose_prep left them), the frame's translation and camera row (the
+// lanes of a half read the same 19 floats), its target and confidence (and with add its three old gradients; lane 0 the old
+// share) in one round trip.  The frame's share: every lane forms c rho(s), then a fixed xor butterfly (16, 8, .. 1) inside the
+// half adds the lanes (lanes 24 .. 31 and invalid pairs hold zeros).  No atomics, no LDS: bit-reproducible.
+// ----------------------------------------------------------------------------------------------------
+struct Keypoint2dArgs {
+  uuo_gptr<const float> frames;   // [F][FrameLds]
+  uuo_gptr<const float> trans;    // [F][3] or null
+  uuo_gptr<const float> cam;      // [F][16]
+  uuo_gptr<const float> targets;  // [F][24][2]
+  uuo_gptr<const float> conf;     // [F][24]
+  int F, add;
+  float cl, cg;                   // w / (48 F), 2 w / (48 F)
+  float rs2, min_depth;           // sigma^2 (0 = the square)
+  uuo_gptr<float> up;             // [F][24][3] gradients, then [F] shares: written (add == 0) or added to
+};
+__global__ __launch_bounds__(64) void k_keypoint2d_fwd(Keypoint2dArgs a) {
+  constexpr int NW = sizeof(FrameLds) / 4, GT = offsetof(FrameLds, Gt) / 4;
+  const int half = threadIdx.x >> 5, l = threadIdx.x & 31;
+  const int f = blockIdx.x * UUO_LIM_FPB + half;
+  const bool on = f < a.F && l < UUO_NUM_JOINTS;
+  const size_t fr = on ? (size_t)f : 0, row = on ? (size_t)f * UUO_NUM_JOINTS + l : 0;
+  const float* gt = a.frames + fr * NW + GT + (on ? l * 3 : 0);
+  const float gx = gt[0], gy = gt[1], gz = gt[2];
+  const float tx = a.trans ? a.trans[fr * 3] : 0.f, ty = a.trans ? a.trans[fr * 3 + 1] : 0.f, tz = a.trans ? a.trans[fr * 3 + 2] : 0.f;
+  const float* cm = a.cam + fr * 16;
+  const float A0 = cm[0], A1 = cm[1], A2 = cm[2], A3 = cm[3], A4 = cm[4], A5 = cm[5], A6 = cm[6], A7 = cm[7], A8 = cm[8];
+  const float b0 = cm[9], b1 = cm[10], b2 = cm[11], fx = cm[12], fy = cm[13], cx = cm[14], cy = cm[15];
+  const float y0 = a.targets[row * 2], y1 = a.targets[row * 2 + 1];
+  const float c = on ? a.conf[row] : 0.f;
+  const bool head = l == 0 && f < a.F;
+  const float old0 = (on && a.add) ? a.up[row * 3] : 0.f, old1 = (on && a.add) ? a.up[row * 3 + 1] : 0.f,
+              old2 = (on && a.add) ? a.up[row * 3 + 2] : 0.f;
+  const float old_share = (head && a.add) ? a.up[(size_t)a.F * 72 + f] : 0.f;
+  const float jx = gx + tx, jy = gy + ty, jz = gz + tz;
+  const float px = fmaf(A2, jz, fmaf(A1, jy, A0 * jx)) + b0;
+  const float py = fmaf(A5, jz, fmaf(A4, jy, A3 * jx)) + b1;
+  const float pz = fmaf(A8, jz, fmaf(A7, jy, A6 * jx)) + b2;
+  // (false for NaN; the setters' bound: a magnitude in (3.0e38, FLT_MAX] counts as not finite here, where torch.isfinite of the
+  // composed term lets it pass -- no camera puts a joint there)
+  const bool finite = fabsf(px) <= 3.0e38f && fabsf(py) <= 3.0e38f && fabsf(pz) <= 3.0e38f;
+  const bool valid = c > 0.f && finite && pz >= a.min_depth;
+  const float iz = 1.f / (valid ? pz : 1.f);  // (keeps the quotients of the unused branch finite)
+  const float rx = fmaf(fx * px, iz, cx) - y0, ry = fmaf(fy * py, iz, cy) - y1;
+  const float s = rx * rx + ry * ry;
+  const float q = (a.rs2 > 0.f) ? a.rs2 / (a.rs2 + s) : 1.f;
+  const float k = (a.cg * c) * (q * q);
+  const float ax = rx * fx, ay = ry * fy;
+  const float dx = k * (ax * iz), dy = k * (ay * iz), dz = -(k * ((ax * px + ay * py) * (iz * iz)));
+  const float g0 = valid ? fmaf(A6, dz, fmaf(A3, dy, A0 * dx)) : 0.f;
+  const float g1 = valid ? fmaf(A7, dz, fmaf(A4, dy, A1 * dx)) : 0.f;
+  const float g2 = valid ? fmaf(A8, dz, fmaf(A5, dy, A2 * dx)) : 0.f;
+  if (on) {
+    a.up[row * 3] = old0 + g0;
+    a.up[row * 3 + 1] = old1 + g1;
+    a.up[row * 3 + 2] = old2 + g2;
+  }
+  // the frame's share: the lanes' c rho(s) through a fixed butterfly inside the 32-lane half
+  float part = valid ? c * (s * q) : 0.f;
+#pragma unroll
+  for (int m = 16; m >= 1; m >>= 1) part += __shfl_xor(part, m, 64);
+  if (head) a.up[(size_t)a.F * 72 + f] = old_share + a.cl * part;
+}
+
 // The side terms that are on, in this order on stream s, once the frames' FrameLds of this evaluation are there.
 void uuo_launch_side_terms(uuo_fit* fit, hipStream_t s, int F, const UuoPoseSrc& src, const float* d_pose, const float* d_o_pose,
                            float w_pose, UuoSideTerms on) {
@@ -442,6 +522,23 @@ void uuo_launch_side_terms(uuo_fit* fit, hipStream_t s, int F, const UuoPoseSrc&
     hipLaunchKernelGGL(k_capsule_fwd, dim3(F), dim3(64), 0, s, b);
     fit->cap_launched = true;  // (uuo_fit_set_capsules waits for this stream before it replaces the tables)
     fit->cap_last_stream = s;
+  }
+  if (on.kp) {
+    Keypoint2dArgs b;
+    std::memset(&b, 0, sizeof(b));
+    b.frames = fit->frames;
+    b.trans = src.trans;
+    b.cam = fit->kp_cam;
+    b.targets = fit->kp_targets;
+    b.conf = fit->kp_conf;
+    b.F = F;
+    b.add = on.caps ? 1 : 0;
+    b.cl = (float)((double)fit->kp_w / (48.0 * (double)F));
+    b.cg = (float)(2.0 * (double)fit->kp_w / (48.0 * (double)F));
+    b.rs2 = (float)((double)fit->kp_sigma * (double)fit->kp_sigma);
+    b.min_depth = fit->kp_min_depth;
+    b.up = fit->cap_up;
+    hipLaunchKernelGGL(k_keypoint2d_fwd, dim3((F + UUO_LIM_FPB - 1) / UUO_LIM_FPB), dim3(64), 0, s, b);
   }
   if (on.limits) {
     LimitFwdArgs b;
@@ -592,6 +689,34 @@ extern "C" int uuo_fit_set_capsules(uuo_fit_t* fit, float w, int32_t n_caps, con
     fit->cap_p = P;
   }
   fit->cap_w = w;
+  return 0;
+}
+
+extern "C" int uuo_fit_set_keypoints2d(uuo_fit_t* fit, float w, float sigma, float min_depth, const float* d_cam,
+                                       const float* d_targets, const float* d_conf) {
+  UUO_REQUIRE(fit, "uuo_fit_set_keypoints2d: null fit");
+  UUO_REQUIRE(w == 0.f || (w > 0.f && w <= 3.0e38f), "uuo_fit_set_keypoints2d: the weight must be 0 (off) or a positive finite number");
+  if (w == 0.f) {  // off: nothing else is looked at
+    fit->kp_w = fit->kp_sigma = fit->kp_min_depth = 0.f;
+    fit->kp_cam = fit->kp_targets = fit->kp_conf = nullptr;
+    return 0;
+  }
+  // (sigma > 0: sigma^2 has to be a normal fp32 value, as uuo_problem_t.robust_sigma's)
+  UUO_REQUIRE(sigma == 0.f || (sigma >= 1.0e-18f && sigma <= 1.0e18f),
+              "uuo_fit_set_keypoints2d: sigma must be 0 (the square) or a positive finite number in [1e-18, 1e18]");
+  UUO_REQUIRE(min_depth > 0.f && min_depth <= 3.0e38f, "uuo_fit_set_keypoints2d: min_depth must be a positive finite number");
+  UUO_REQUIRE(d_cam && d_targets && d_conf,
+              "uuo_fit_set_keypoints2d: a positive weight needs the cameras [F][16], the targets [F][24][2] and the confidences "
+              "[F][24] on the device");
+  UUO_REQUIRE(!uuo_recorder, "uuo_fit_set_keypoints2d: lock-step batches do not carry the key-point reprojection term");
+  // (the buffer k_keypoint2d_fwd fills is the self-penetration term's: [F][72] gradients, then [F] shares)
+  if (!fit->cap_up) UUO_HIP_CHECK(hipMalloc((void**)&fit->cap_up, ((size_t)fit->F * 72 + fit->F) * sizeof(float)));
+  fit->kp_w = w;
+  fit->kp_sigma = sigma;
+  fit->kp_min_depth = min_depth;
+  fit->kp_cam = d_cam;
+  fit->kp_targets = d_targets;
+  fit->kp_conf = d_conf;
   return 0;
 }
 

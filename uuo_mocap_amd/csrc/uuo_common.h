@@ -242,6 +242,14 @@ struct uuo_fit {
   // prior -- gradients and shares -- in lim_g (added there when the joint-angle limit term is on too), and the backward and the
   // finalize run with a pose coefficient of 0.
   const float* prior_w = nullptr;
+  // EXTENSION: the 2D key-point reprojection term on the 24 kinematic joints (uuo_fit_set_keypoints2d; kp_w == 0 = off): weight,
+  // Geman-McClure sigma (0 = the square), the least depth of a valid pair, and the caller's device arrays -- cameras [F][16],
+  // targets [F][24][2], confidences [F][24] -- read at every evaluation and not copied.  k_keypoint2d_fwd leaves its gradients and
+  // shares in cap_up (added there when the self-penetration term is on too).
+  float kp_w = 0.f, kp_sigma = 0.f, kp_min_depth = 0.f;
+  const float* kp_cam = nullptr;
+  const float* kp_targets = nullptr;
+  const float* kp_conf = nullptr;
   int last_n = 0;  // coordinates of the last stage solve set up on this workspace (n_act on the compact packing, else n_full):
                    // read back by the debug flavour's uuo_debug_last_solve_n, which tests use to see which packing a solve took
   int surface = 0;               // EXTENSION: point-to-surface chamfer term (uuo_fit_set_surface; 0 = off) and its stand-off
@@ -318,13 +326,13 @@ int uuo_launch_bwd(const uuo_fit* fit, hipStream_t s, const uuo_problem_t& p, co
 int uuo_launch_finalize(const uuo_fit* fit, hipStream_t s, const uuo_problem_t& p, const float* x, float* grad,
                         float* loss);
 
-// the closures' side terms (side_terms.hip: k_floor_fwd, k_capsule_fwd, k_limit_fwd, k_prior_conf and their setters).  One call
+// the closures' side terms (side_terms.hip: k_floor_fwd, k_capsule_fwd, k_keypoint2d_fwd, k_limit_fwd, k_prior_conf and their setters).  One call
 // per evaluation launches the forward kernels of the terms that are on, in that order on stream s, once fit->frames holds this
 // evaluation's FrameLds; src is the evaluation's pose source, d_pose / d_o_pose / w_pose the raw body pose, its prior target and
 // the prior's weight (the weighted prior only)
 #define UUO_FLOOR_MAXK 16  // sole points of the floor-contact term: fit->floor_up is [F][UUO_FLOOR_MAXK][3], then [F] loss shares
 struct UuoSideTerms {
-  bool floor, caps, limits, prior;
+  bool floor, caps, limits, prior, kp;
 };
 void uuo_launch_side_terms(uuo_fit* fit, hipStream_t s, int F, const UuoPoseSrc& src, const float* d_pose, const float* d_o_pose,
                            float w_pose, UuoSideTerms on);

@@ -21,9 +21,9 @@ from ._lib import (EVAL_CALLBACK, UUO_STAGE_CHAMFER, UUO_STAGE_MARKER, UUO_STAGE
 from . import terms
 from .body_model import SmplTables
 from .config import stage_surface
-from .terms import (FLOOR_MAX_POINTS, check_foot_contacts, check_prior_weights, prior_weight_table, stage_capsules,  # noqa: F401
-                    stage_floor, stage_foot_lock, stage_joint_accel, stage_joint_limits, stage_latent_offsets, stage_pose_accel,
-                    stage_prior_confidence, stage_robust_sigma)  # (re-exported: the terms' parsers live in terms.py)
+from .terms import (FLOOR_MAX_POINTS, check_foot_contacts, check_keypoints_2d, check_prior_weights,  # noqa: F401
+                    prior_weight_table, stage_capsules, stage_floor, stage_foot_lock, stage_joint_accel, stage_joint_limits,
+                    stage_keypoints_2d, stage_latent_offsets, stage_pose_accel, stage_prior_confidence, stage_robust_sigma)  # (re-exported: the terms' parsers live in terms.py)
 
 MARKER_DISTANCE = 0.0095  # reference utils/settings.py:1
 
@@ -492,7 +492,7 @@ class _StageProblem:
         p.marker_distance = MARKER_DISTANCE
         self.problem = p
         self.n = int(self.lib.uuo_problem_num_params(byref(p)))
-        # EXTENSION: the terms' state (terms.TERMS: joint_accel, foot_lock, floor_*, cap_*, lim_*, prior_weights), all off.  They
+        # EXTENSION: the terms' state (terms.TERMS: joint_accel, foot_lock, floor_*, cap_*, lim_*, prior_weights, kp_*), all off.  They
         # are settings of the WORKSPACE in the library: _arm() puts them there before every call that evaluates on it
         for term in terms.TERMS:
             vars(self).update(term.state)
@@ -508,17 +508,19 @@ class _StageProblem:
     capsules_on = property(lambda self: self.cap_w != 0.0)
     joint_limits_on = property(lambda self: self.lim_w != 0.0)
     prior_conf_on = property(lambda self: self.prior_weights is not None)
+    keypoints_on = property(lambda self: self.kp_w != 0.0)
 
     def _set_terms(self, stage_terms, contacts, weights, smpl_inference):
-        """EXTENSION: every term's state from its parsed record, the checked contact labels and prior weights (terms.Term.set)."""
+        """EXTENSION: every term's state from its parsed record, the checked contact labels and prior weights and the armed
+        key-point record (terms.Term.set)."""
         for term in terms.TERMS:
             if term.set is not None:
-                term.set(self, stage_terms[term], contacts, weights, smpl_inference)
+                term.set(self, stage_terms[term], contacts, weights, stage_terms.keypoints, smpl_inference)
 
     def _arm(self):
         """Sets this problem's terms (off without them), its surface term and its per-frame table on its workspace: one library
         call each, in the order they have always had (joint_accel, foot_lock, surface, per-frame table, floor, capsules, joint
-        limits, prior weights).  The workspace is shared by every problem of the same (F, M) on this thread, so this runs right
+        limits, prior weights, key points).  The workspace is shared by every problem of the same (F, M) on this thread, so this runs right
         before each library call that evaluates on it."""
         for term in _ARMED[:2]:
             term.arm(self)
@@ -708,10 +710,13 @@ class ChamferProblem(_StageProblem):
     stage = UUO_STAGE_CHAMFER
 
     def __init__(self, smpl_inference, markers, o_pose_body, o_betas, root_orient, config, foot_contacts=None,
-                 prior_weights=None, stage_terms=None):
+                 prior_weights=None, stage_terms=None, keypoints_2d=None):
         """EXTENSION: `prior_weights` [F, 23] >= 0 weighs the pose prior per frame and body joint (prior_weight_table builds it
         from the video's mask and stages.chamfer.prior_confidence); None, or ones everywhere, changes nothing.  `stage_terms`:
-        the caller's terms.StageTerms of this config and stage, when it has parsed them already."""
+        the caller's terms.StageTerms of this config and stage, when it has parsed them already.
+        EXTENSION: `keypoints_2d` {"camera" [F, 16], "targets" [F, 24, 2], "confidence" [F, 24]} is the evidence of the
+        key-point reprojection term (terms.check_keypoints_2d; stages.chamfer.losses.keypoints_2d); None -- then what
+        `stage_terms` has armed counts --, weight 0 or no positive confidence changes nothing."""
         losses = config["stages"]["chamfer"]["losses"]
         unsupported = set(losses) - terms.problem_keys("chamfer")
         if unsupported:
@@ -725,6 +730,9 @@ class ChamferProblem(_StageProblem):
         weights = check_prior_weights(prior_weights, None if markers is None else markers.shape[0])
         if terms.armed_weights(weights) is not None and soft:
             raise NotImplementedError(terms.PRIOR.soft)
+        # EXTENSION: the key-point reprojection term's evidence (validates the block and the record)
+        if stage_terms.arm_keypoints(keypoints_2d, None if markers is None else markers.shape[0]) is not None and soft:
+            raise NotImplementedError(terms.KEYPOINTS.soft)
         if not config["stages"]["chamfer"]["yaw_lock"]:
             raise NotImplementedError("stages.chamfer.yaw_lock False is not a shipped configuration")
         wd, wp, wb = _cfg_weights(losses, "surface_chamfer" if w_surface > 0.0 else "full_chamfer")
@@ -771,13 +779,14 @@ class MarkerProblem(_StageProblem):
     stage = UUO_STAGE_MARKER
 
     def __init__(self, smpl_inference, markers, o_pose_body, o_betas, assign, config, bary=None, foot_contacts=None,
-                 frame_assign=None, prior_weights=None, stage_terms=None):
+                 frame_assign=None, prior_weights=None, stage_terms=None, keypoints_2d=None):
         """`assign` [M] vertex ids (the one-hot placement of the shipped configs), or -- with `bary` [M, 3] -- [M, 3] corner
         vertex ids of a three-corner (barycentric) placement: virtual marker m = sum_k bary[m, k] v[assign[m, k]].
         EXTENSION: `frame_assign` [F, M] int32, a per-frame vertex table (tracklets: the column's vertex changes with the frame,
         an entry < 0 is an item of weight 0); `assign` may then be None.  Refused with `bary` and with latent_offsets.
         EXTENSION: `prior_weights` [F, 23] >= 0 weighs the pose prior per frame and body joint (prior_weight_table); None, or
-        ones everywhere, changes nothing.  `stage_terms`: as ChamferProblem's."""
+        ones everywhere, changes nothing.  `stage_terms`, and EXTENSION `keypoints_2d` (stages.marker.losses.keypoints_2d): as
+        ChamferProblem's."""
         st = config["stages"]["marker"]
         unsupported = set(st["losses"]) - terms.problem_keys("marker")
         if unsupported:
@@ -793,6 +802,8 @@ class MarkerProblem(_StageProblem):
         contacts = check_foot_contacts(foot_contacts, None if markers is None else markers.shape[0])
         stage_terms[terms.PRIOR]  # EXTENSION: the pose prior's weights (validates the block)
         weights = check_prior_weights(prior_weights, None if markers is None else markers.shape[0])
+        # EXTENSION: the key-point reprojection term's evidence (validates the block and the record)
+        stage_terms.arm_keypoints(keypoints_2d, None if markers is None else markers.shape[0])
         w_offsets = stage_terms[terms.LATENT_OFFSETS]
         if frame_assign is not None:
             if bary is not None:

@@ -369,6 +369,32 @@ def pose_accel_loss(rot_body: torch.Tensor, w: float, joint_weights=None) -> tor
     return float(w) * sq.sum() / ((rot_body.shape[0] - 2) * 207.0)
 
 
+def keypoints_2d_loss(joints: torch.Tensor, camera: torch.Tensor, targets: torch.Tensor, confidence: torch.Tensor, w: float,
+                      sigma: float = 0.0, min_depth: float = 0.1) -> torch.Tensor:
+    """EXTENSION (not in the reference, whose 2D-prior stage alone projects key points): the 2D key-point reprojection term of
+    the fused chamfer and marker closures (uuo_fit_set_keypoints2d), composed -- their checker.  joints [F, >= 24, 3] (the 24
+    kinematic joints count), camera [F, 16] a pinhole camera per frame in world axes (A 3x3 row-major, b, fx, fy, cx, cy),
+    targets [F, 24, 2], confidence [F, 24] >= 0 (joint weights already multiplied in):
+    p = A J + b,  u = (fx p_x / p_z + cx, fy p_y / p_z + cy),  s = |u - y|^2,
+    w / (48 F) sum over the valid pairs of c gmof(s, sigma);  valid = c > 0 and p finite and p_z >= min_depth.
+    An invalid pair contributes an exact 0 and exact zero gradient rows (it is selected away, not multiplied).  Units: the
+    camera's own, squared."""
+    F = joints.shape[0]
+    J = joints[:, :24]
+    cam = camera.to(device=J.device, dtype=J.dtype)
+    y = targets.to(device=J.device, dtype=J.dtype)
+    c = confidence.to(device=J.device, dtype=J.dtype)
+    A, b, f, c0 = cam[:, :9].reshape(F, 3, 3), cam[:, 9:12], cam[:, 12:14], cam[:, 14:16]
+    p = (A[:, None] * J[:, :, None, :]).sum(-1) + b[:, None]
+    valid = (c > 0) & torch.isfinite(p).all(dim=-1) & (p[..., 2] >= float(min_depth))
+    pz = torch.where(valid, p[..., 2], torch.ones_like(p[..., 2]))
+    pxy = torch.where(valid[..., None], p[..., :2], torch.zeros_like(p[..., :2]))
+    r = f[:, None] * pxy / pz[..., None] + c0[:, None] - y
+    s = (r * r).sum(-1)
+    term = torch.where(valid, c * gmof(s, sigma), torch.zeros_like(s))
+    return float(w) * term.sum() / (48.0 * F)
+
+
 def weighted_pose_prior(pose_body: torch.Tensor, o_pose_body: torch.Tensor, weights: torch.Tensor) -> torch.Tensor:
     """EXTENSION (the reference's author left it commented out, optimization.py:244): the pose prior of the fused chamfer and
     marker closures with a weight per (frame, body joint) (uuo_fit_set_prior_weights), composed -- their checker.  pose_body,

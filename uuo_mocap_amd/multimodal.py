@@ -22,6 +22,7 @@ from .engine import (prior_weight_table, set_workspace_group, set_workspace_slot
 from .markers_utils import find_best_part_fits, get_aabb, get_aabb_volume, segment_rigid
 from .optimization import (compute_marker_labels_from_coords, compute_nearest_points, compute_tracklet_placement,
                            get_marker_mask, optim_chamfer, optim_markers, weighted_chamfer_distance)
+from .terms import check_keypoints_2d, stage_keypoints_2d
 from .tracklets import segment_tracklets, tracklets_config
 from .losses import knn_points_k1
 from .smpl import SmplInference
@@ -93,12 +94,19 @@ def multimodal_video_mocap(
     visualize_fits: bool = False,
     smpl_inference: SmplInference = None,
     execution: Dict = None,
+    keypoints_2d: Dict = None,
 ) -> Dict:
     """See the reference docstring (multimodal.py:49-84) for the meaning of the inputs and output keys.
     `smpl_inference` (extension) lets callers reuse one model/workspace across sequences.  `execution` (extension; how the
     independent solves are scheduled on the device, never what they compute -- markers_utils.EXECUTION_DEFAULTS):
     {"hypothesis_lockstep": False, "hypothesis_threads": 4, "subtree_lockstep": True, "subtree_batch": 256,
-    "subtree_threads": 4}; an `execution` section of `config` sets the same keys, the argument wins."""
+    "subtree_threads": 4}; an `execution` section of `config` sets the same keys, the argument wins.
+    EXTENSION: `keypoints_2d` {"camera" [F, 16], "targets" [F, 24, 2], "confidence" [F, 24]} (terms.check_keypoints_2d) is the
+    2D evidence of stages.{chamfer,marker}.losses.keypoints_2d, one row per VIDEO frame like the tracks of `img_smpl`: a
+    calibrated camera in world axes and a detector's key points with confidences.  It goes to every chamfer and marker solve, the
+    final stage included; it is cut and padded with the video's tracks (padded frames at confidence 0) and refused where the
+    mocap and video frame rates differ.  Without it the record is the winning 2D-prior hypothesis
+    (reprojection.world_keypoints_2d) when stages.reprojection_part ran, else none -- and the keys then change nothing."""
     exe = markers_utils.merge_execution(config, execution)
     if visualize_fits:
         raise NotImplementedError("visualize_fits renders with pyrender, not built")
@@ -128,7 +136,14 @@ def multimodal_video_mocap(
     o_foot_contacts = getattr(img_smpl, "foot_contacts", None)
     if o_foot_contacts is not None:
         o_foot_contacts = o_foot_contacts.clone().detach().to(device)
+    o_keypoints = check_keypoints_2d(keypoints_2d)  # EXTENSION: ValueError before anything is fitted
+    if o_keypoints is not None and int(o_keypoints["camera"].shape[0]) != int(img_smpl.pose_body.shape[0]):
+        raise ValueError("keypoints_2d: one row per video frame expected (%d rows, the video has %d frames)"
+                         % (int(o_keypoints["camera"].shape[0]), int(img_smpl.pose_body.shape[0])))
     if mocap_markers.get_frequency() != img_smpl.freq:
+        if o_keypoints is not None:
+            raise NotImplementedError("keypoints_2d with different mocap / video frame rates: image targets and confidences are "
+                                      "not resampled; pass a record at the mocap frame rate with a video resampled to it")
         # bring the HMR track to the mocap frame rate (reference :145-182); img_mask and the camera stay in video
         # frames there, so the reprojection stage (which pairs them with the resampled track) cannot follow
         if config["find_best_part_fits"] and config["stages"]["reprojection_part"]["num_iters"] > 0:
@@ -163,6 +178,12 @@ def multimodal_video_mocap(
     if o_foot_contacts is not None:
         o_foot_contacts = pad(o_foot_contacts, offset).detach()
     markers = pad(markers, -offset).detach().contiguous()
+    if o_keypoints is not None:  # EXTENSION: cut and padded like the video's tracks; a padded frame weighs nothing
+        o_keypoints = {k: pad(v[:min_frames], offset).clone() for k, v in o_keypoints.items()}
+        if offset > 0:
+            o_keypoints["confidence"][:offset] = 0.0
+        elif offset < 0:
+            o_keypoints["confidence"][offset:] = 0.0
     num_frames = trans.shape[0]
     # EXTENSION: per-(frame, joint) confidence in the video's pose (stages.<stage>.prior_confidence): the weights of the pose
     # prior of every chamfer and marker solve whose target is the HMR track, from the frames the video saw
@@ -252,6 +273,17 @@ def multimodal_video_mocap(
                       "reproject_mask": hyps[best]["reproject_mask"].clone().detach(),
                       "cam_trans": hyps[best]["cam_trans"][0].clone().detach(),
                       "camera_center": hyps[best]["camera_center"].clone().detach()}
+            if o_keypoints is None and any(stage_keypoints_2d(config, k)["w"] > 0.0 for k in ("chamfer", "marker")):
+                # EXTENSION: the winning hypothesis' camera and targets as the record of the chamfer and marker solves; j0, the
+                # rest pelvis joint, once, at the winning hypothesis' mean betas (what the part stage starts from)
+                from .reprojection import world_keypoints_2d
+
+                with torch.no_grad():
+                    eye = torch.eye(3, device=device)
+                    j0 = smpl_inference(poses=eye.expand(1, 23, 3, 3).contiguous(), betas=o_betas[:1],
+                                        root_orient=eye.expand(1, 1, 3, 3).contiguous(),
+                                        trans=torch.zeros(1, 3, device=device))["joints"][0, 0]
+                o_keypoints = {k: v.detach().cpu() for k, v in world_keypoints_2d(camera, j0).items()}
         filter_output = find_best_part_fits(
             markers=markers, pose_body=o_pose_body, betas=o_betas, root_orient=o_root_orient,
             marker_labels=segmented_markers, smpl_inference=smpl_inference, hierarchy=smpl_inference.smpl.parents,
@@ -378,7 +410,7 @@ def multimodal_video_mocap(
                               o_betas=o_betas, root_orient=root_f, trans=trans_f,
                               img_mask=img_mask, smpl_inference=smpl_inference, config=config, initial_angle=0,
                               repeat=1, verbose=verbose, iter_fn=save_iter_fn, foot_contacts=o_foot_contacts,
-                              **placement, **({} if offs is None else {"marker_offsets": offs}))
+                              keypoints_2d=o_keypoints, **placement, **({} if offs is None else {"marker_offsets": offs}))
                 offsets_f = offs
                 final_stats.append(optimization.last_stats("marker"))
             root_f = normalize_rot(root_f).clone().detach().requires_grad_(True)
@@ -410,7 +442,8 @@ def multimodal_video_mocap(
                               marker_labels=torch.from_numpy(np.asarray(marker_labels)).to(device),
                               img_mask=img_mask, smpl_inference=smpl_inference, initial_angle=root_orient_angle,
                               repeat=0, config=config, verbose=verbose, iter_fn=save_iter_fn,
-                              foot_contacts=o_foot_contacts, prior_weights=prior_weights["chamfer"])
+                              foot_contacts=o_foot_contacts, prior_weights=prior_weights["chamfer"],
+                              keypoints_2d=o_keypoints)
                 local["chamfer_stats"] = optimization.last_stats("chamfer")
             local["chamfer"] = _np_dict(trans=trans_angle, root_orient=normalize_rot(z_root), betas=betas_angle[0],
                                         pose_body=normalize_rot(pose_angle))
@@ -429,7 +462,7 @@ def multimodal_video_mocap(
                               img_mask=img_mask, smpl_inference=smpl_inference,
                               config=config, initial_angle=root_orient_angle, repeat=0, verbose=verbose,
                               iter_fn=save_iter_fn, foot_contacts=o_foot_contacts, prior_weights=prior_weights["marker"],
-                              **placement)
+                              keypoints_2d=o_keypoints, **placement)
                 local["marker_stats"] = optimization.last_stats("marker")
             if not run_chamfer and not run_marker:
                 # nothing was optimised: the marker-stage record is the chamfer-stage record (both hold the normalised
@@ -502,7 +535,8 @@ def multimodal_video_mocap(
                                   o_betas=o_betas, root_orient=h["root_orient"], trans=h["trans"],
                                   barycentric_coords_one_hot=oh, img_mask=img_mask, smpl_inference=smpl_inference,
                                   config=config, initial_angle=angle, repeat=0, verbose=verbose,
-                                  foot_contacts=o_foot_contacts, prior_weights=prior_weights["marker"])
+                                  foot_contacts=o_foot_contacts, prior_weights=prior_weights["marker"],
+                                  keypoints_2d=o_keypoints)
                     all_stats.append(optimization.last_stats("marker"))
             for local, stt in zip(locals_, all_stats):
                 local["marker_stats"] = stt

@@ -62,16 +62,21 @@ def optim_chamfer(
     iter_fn: Callable = None,
     foot_contacts: torch.Tensor = None,
     prior_weights: torch.Tensor = None,
+    keypoints_2d: Dict = None,
 ):
     """Chamfer (pose fitting) stage: L-BFGS over [trans, z_angle, betas, pose_body], lr 0.1.  Mutates
     trans / betas / pose_body in place and applies the optimised yaw to root_orient in place.
     EXTENSION: `foot_contacts` ([F, 2] in [0, 1], optional) are the video's contact labels of the left and right foot for
     stages.chamfer.losses.foot_lock (without them, or with labels that gate nothing, the key changes nothing).
     EXTENSION: `prior_weights` ([F, 23] >= 0, optional; engine.prior_weight_table) weigh reg_pose_body per frame and body joint
-    (None, or ones everywhere, changes nothing; `img_mask` itself is not read)."""
+    (None, or ones everywhere, changes nothing; `img_mask` itself is not read).
+    EXTENSION: `keypoints_2d` ({"camera" [F, 16], "targets" [F, 24, 2], "confidence" [F, 24]}, optional;
+    terms.check_keypoints_2d) is the 2D evidence of stages.chamfer.losses.keypoints_2d: a pinhole camera in world axes, image
+    targets and confidences for the 24 kinematic joints (without it, or with confidences that weigh nothing, the key changes
+    nothing)."""
     from .parallel import frame_shard
 
-    stage_terms = _stage_terms(config, "chamfer", prior_weights, markers.shape[0])
+    stage_terms = _stage_terms(config, "chamfer", prior_weights, markers.shape[0], keypoints_2d)
     prior_weights = stage_terms.prior_weights
     fs = frame_shard()
     route = stage_route(stage_terms, on_device=markers.is_cuda, sharded=fs is not None and fs.active)
@@ -177,13 +182,15 @@ def _optim_markers_frame_sharded(fs, markers, pose_body, o_pose_body, betas, o_b
     return None
 
 
-def _stage_terms(config: Dict, stage: str, prior_weights, num_frames) -> StageTerms:
+def _stage_terms(config: Dict, stage: str, prior_weights, num_frames, keypoints_2d=None) -> StageTerms:
     """The stage's EXTENSION terms for one call, parsed once and handed on (terms.StageTerms), with the weights of the pose prior
     as the solvers use them: the block is validated, the table checked on the host (shape, finite, >= 0: ValueError before the
-    device is touched); None, or a table of ones, is None -- nothing is armed and every route is the one it was."""
+    device is touched); None, or a table of ones, is None -- nothing is armed and every route is the one it was.  The key-point
+    reprojection term's record likewise (StageTerms.arm_keypoints): the terminals find what is left of it on `stage_terms`."""
     stage_terms = StageTerms(config, stage)
     stage_terms[PRIOR]
     stage_terms.prior_weights = armed_weights(check_prior_weights(prior_weights, num_frames))
+    stage_terms.arm_keypoints(keypoints_2d, num_frames)
     return stage_terms
 
 
@@ -285,7 +292,7 @@ def _solve(prob, x, config, stage: str, lr: float, verbose_tag: str, verbose: bo
 
 def _optim_chamfer_general(markers, pose_body, o_pose_body, betas, o_betas, root_orient, trans, marker_labels,
                            smpl_inference, config, initial_angle, repeat, verbose, iter_fn, foot_contacts=None,
-                           prior_weights=None, stage_terms=None):
+                           prior_weights=None, stage_terms=None, keypoints_2d=None):
     """Chamfer stage with the reference's optional terms (`part_chamfer`, `trans_vel`, `ground`; plus the labelled
     extension `soft_chamfer`, a soft-assignment data term the reference does not have) and / or
     `yaw_lock: False` (reference optimization.py:164-285; none is in a shipped config): the closure is composed from the
@@ -298,6 +305,7 @@ def _optim_chamfer_general(markers, pose_body, o_pose_body, betas, o_betas, root
     if unknown:
         raise NotImplementedError("chamfer-stage losses that cannot run in the reference: %s" % sorted(unknown))
     stage_terms = stage_terms or StageTerms(config, "chamfer")
+    stage_terms.arm_keypoints(keypoints_2d, pose_body.shape[0])  # EXTENSION: the key-point term's record (None: the caller's)
     w_surface, d_surface = stage_surface(config)  # EXTENSION: point-to-surface data term and its stand-off
     sigma = stage_terms[ROBUST]  # EXTENSION: Geman-McClure data term (0 = the reference's square)
     contacts = check_foot_contacts(foot_contacts, pose_body.shape[0])
@@ -403,6 +411,7 @@ def optim_markers(
     foot_contacts: torch.Tensor = None,
     frame_assign: torch.Tensor = None,
     prior_weights: torch.Tensor = None,
+    keypoints_2d: Dict = None,
 ):
     """Marker (inverse kinematics) stage: L-BFGS over [pose_body, betas, root_orient, trans], lr 1.0, with the
     fixed marker -> vertex placement given as a one-hot [M, V] matrix.  Mutates the four leaves in place.
@@ -416,10 +425,11 @@ def optim_markers(
     `barycentric_coords_one_hot` may be None.  Fused one-hot closure only: refused with latent_offsets, with
     execution.robust_fused / temporal_fused: False, under frame-block sharding and with shared betas.
     EXTENSION: `prior_weights` ([F, 23] >= 0, optional; engine.prior_weight_table) weigh reg_pose_body per frame and body joint
-    (None, or ones everywhere, changes nothing; `img_mask` itself is not read)."""
+    (None, or ones everywhere, changes nothing; `img_mask` itself is not read).
+    EXTENSION: `keypoints_2d` (optional): as optim_chamfer's, for stages.marker.losses.keypoints_2d."""
     from .parallel import frame_shard, shared_betas_reducer
 
-    stage_terms = _stage_terms(config, "marker", prior_weights, markers.shape[0])
+    stage_terms = _stage_terms(config, "marker", prior_weights, markers.shape[0], keypoints_2d)
     prior_weights = stage_terms.prior_weights
     one_hot = barycentric_coords_one_hot
     if frame_assign is not None:
@@ -472,12 +482,13 @@ def optim_markers(
 
 def _optim_markers_general(markers, pose_body, o_pose_body, betas, o_betas, root_orient, trans, coords, smpl_inference,
                            config, verbose, iter_fn=None, initial_angle=0, repeat=0, foot_contacts=None, prior_weights=None,
-                           stage_terms=None):
+                           stage_terms=None, keypoints_2d=None):
     """Marker stage for a general placement matrix [M, V] (reference optimization.py:288-399 as written: virtual
     markers = coords @ vertices).  The fused device solver covers the one-hot placements of the shipped configs; this
     path composes the same closure from the differentiable HIP operators (SmplInference forward / uuo_smpl_backward)
     and drives it with torch.optim.LBFGS like the reference.  Mutates the four leaves in place."""
     stage_terms = stage_terms or StageTerms(config, "marker")
+    stage_terms.arm_keypoints(keypoints_2d, pose_body.shape[0])  # EXTENSION: the key-point term's record (None: the caller's)
     stage_terms.refuse_latent_offsets("the closure composed from the operators (more than three non-zeros per placement row, "
                                       "execution.robust_fused / temporal_fused / marker_bary_fused: False)")
     st = config["stages"]["marker"]

@@ -51,6 +51,30 @@ def convert_mocap_pos_to_hmr_pos(pos):
     return torch.cat((pos[..., [0]], pos[..., [2]] * -1, pos[..., [1]]), dim=-1)
 
 
+def world_keypoints_2d(camera: Dict, j0: torch.Tensor) -> Dict:
+    """EXTENSION: the winning 2D-prior hypothesis as a `keypoints_2d` record of the chamfer and marker stages
+    (terms.check_keypoints_2d): a pinhole camera in WORLD (mocap, z-up) axes with the 24 kinematic joints' targets.  `camera`
+    holds optim_reprojection's joints_2d_gt [F, 45, 2], focal_length [1, 2], camera_center [F, 2], cam_trans [1, 3] or [F, 3] (mocap axes)
+    and reproject_mask [F], as multimodal_video_mocap keeps them; `j0` [3] is the rest pelvis joint of the shape.
+    The part stage's `reproject` term (markers_utils.part_extra_losses) projects the joints of the body turned by C^T about its
+    pelvis, C = [[1, 0, 0], [0, 0, 1], [0, -1, 0]]: C^T (J_w - j0) + j0 with J_w the world joints.  So the record is A = C^T,
+    b = C^T cam_trans + (I - C^T) j0, (fx, fy) = focal_length, (cx, cy) = camera_center + 0.5, targets joints_2d_gt[:, :24],
+    confidence reproject_mask per joint -- in the reference's image-size-1 units.  `j0` is taken ONCE, by the caller (multimodal_video_mocap: at the winning
+    hypothesis' mean betas, which the part stage starts from); it moves by fractions of a millimetre with the fitted shape, which
+    the record does not follow."""
+    gt = camera["joints_2d_gt"]
+    F, dt, dev = gt.shape[0], gt.dtype, gt.device
+    Ct = torch.tensor([[1.0, 0.0, 0.0], [0.0, 0.0, -1.0], [0.0, 1.0, 0.0]], dtype=dt, device=dev)
+    j0 = j0.to(device=dev, dtype=dt).reshape(3)
+    cam_trans = camera["cam_trans"].to(dt).reshape(-1, 3)   # one row, or the same camera once per frame (optim_reprojection)
+    b = cam_trans.expand(F, 3) @ Ct.T + ((torch.eye(3, dtype=dt, device=dev) - Ct) @ j0)[None]
+    focal = camera["focal_length"].to(dt).reshape(1, 2).expand(F, 2)
+    centre = camera["camera_center"].to(dt).reshape(-1, 2).expand(F, 2) + 0.5
+    cam = torch.cat([Ct.reshape(1, 9).expand(F, 9), b, focal, centre], dim=1)
+    conf = camera["reproject_mask"].to(dt).reshape(F, 1).expand(F, 24)
+    return {"camera": cam.contiguous(), "targets": gt[:, :24].contiguous(), "confidence": conf.contiguous()}
+
+
 def apply_matrix_33_to_vector_3(mat, vec):
     return (mat @ vec[..., None])[..., 0]
 

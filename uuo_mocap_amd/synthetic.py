@@ -81,6 +81,10 @@ def fk_joints_f64(tables: SmplTables, rot: np.ndarray, rest: np.ndarray):
     return G_t, G_R
 
 
+#: the elbow capture (make_sequence(elbow_error=True)): window length, the forearm's turn about the camera's depth axis, taper
+ELBOW_WINDOW, ELBOW_ANGLE, ELBOW_TAPER = 24, 0.5, 2
+
+
 #: the self-penetration capture (make_sequence(self_penetration=True)): window length, depth of the HMR start's overlap, taper
 PENETRATION_WINDOW, PENETRATION_DEPTH, PENETRATION_TAPER = 24, 0.030, 2
 
@@ -205,7 +209,7 @@ def make_sequence(tables: SmplTables, seed: int = 0, num_frames: int = 300, num_
                   standoff_tilt_deg: float = 0.0, standoff_mm=(9.5, 9.5), planted_feet: bool = False,
                   stance_frames: int = 20, identity_events: int = 0, floor: bool = False,
                   self_penetration: bool = False, joint_limits: bool = False,
-                  video_dropout: bool = False) -> SyntheticSequence:
+                  video_dropout: bool = False, elbow_error: bool = False) -> SyntheticSequence:
     """One synthetic sequence: smooth GT motion, unlabeled-but-tracked markers 9.5 mm off the
     surface with 1 mm noise and block dropout, and an HMR stand-in (noisy pose/shape, wrong yaw).  `subject_seed` fixes the
     ground-truth shape independently of `seed`: sequences of ONE subject (the shared-betas extension fits them together).
@@ -254,7 +258,14 @@ def make_sequence(tables: SmplTables, seed: int = 0, num_frames: int = 300, num_
     are what ingest.fill_gaps makes of its own neighbours (slerp / lerp across the gap), as ingest.ImgSmpl would; foot_contacts
     are 0 there.  The markers are untouched.  gt["dropout_window"] = (first frame, one past the last), gt["hmr_gap_error"] [F]
     the mean geodesic distance (radians, over the 23 body joints) of the stand-in's pose -- filled, inside the window -- from
-    the ground truth's.  No hash stream is consumed; without the option every array is what it was."""
+    the ground truth's.  No hash stream is consumed; without the option every array is what it was.
+    A capture whose video start has an elbow wrong in the image plane (EXTENSION tests of the 2D key-point term): with
+    `elbow_error`, in a window of ELBOW_WINDOW = 24 frames starting at F / 10 (rounded up; ValueError if the sequence is shorter)
+    the HMR stand-in's left forearm (joint 18, the elbow) is turned by ELBOW_ANGLE = 0.5 rad about the world y axis -- the depth
+    direction of synthetic_camera, so the error lies in its image plane -- (tapered 1/3, 2/3 over two frames at each end), and
+    every marker column owned by joints 16, 18, 20 and 22 is blanked (exact zeros): nothing but the prior then holds the arm.
+    gt["elbow_window"] = (first frame, one past the last).  No hash stream is consumed; without the option every array is what
+    it was."""
     F, M = num_frames, num_markers
     if floor and not planted_feet:
         raise ValueError("make_sequence: floor=True needs planted_feet=True (the floor is built under the planted feet)")
@@ -439,6 +450,22 @@ def make_sequence(tables: SmplTables, seed: int = 0, num_frames: int = 300, num_
         leg_cols = np.isin(owner[pick[perm]], [4, 7, 10])
         markers[t0:t0 + LIMIT_WINDOW, leg_cols] = 0.0
 
+    elbow_window = None
+    if elbow_error:  # (no hash stream: the HMR elbow of the window and the left arm's marker columns there change, nothing else)
+        t0 = -(-F // 10)
+        if t0 + ELBOW_WINDOW > F:
+            raise ValueError("make_sequence: elbow_error needs a window of %d frames from frame %d on (F = %d)" % (ELBOW_WINDOW, t0, F))
+        elbow_window = (t0, t0 + ELBOW_WINDOW)
+        hmr_rot = hmr_rot.copy()
+        world = fk_joints_f64(tables, hmr_rot, rest_joints_f64(tables, hmr_betas.mean(axis=0)))[1][:, 18]
+        for i in range(ELBOW_WINDOW):
+            edge = min(i, ELBOW_WINDOW - 1 - i)
+            taper = 1.0 if edge >= ELBOW_TAPER else (edge + 1.0) / (ELBOW_TAPER + 1.0)
+            axis_local = world[t0 + i].T @ np.array([0.0, 1.0, 0.0])   # a turn about world y, said in the forearm's own frame
+            hmr_rot[t0 + i, 18] = hmr_rot[t0 + i, 18] @ _rodrigues(taper * ELBOW_ANGLE * axis_local)
+        arm_cols = np.isin(owner[pick[perm]], [16, 18, 20, 22])
+        markers[t0:t0 + ELBOW_WINDOW, arm_cols] = 0.0
+
     f32 = lambda x: torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
     img_mask = torch.ones(F, dtype=torch.bool)
     tracks = {"trans": f32(hmr_trans), "root_orient": f32(hmr_root[:, None]), "pose_body": f32(hmr_rot[:, 1:]),
@@ -498,6 +525,8 @@ def make_sequence(tables: SmplTables, seed: int = 0, num_frames: int = 300, num_
     if video_dropout:
         gt["dropout_window"] = dropout_window
         gt["hmr_gap_error"] = hmr_gap_error
+    if elbow_error:
+        gt["elbow_window"] = elbow_window
     return SyntheticSequence(img_smpl=img, markers=SyntheticMarkers(markers.astype(np.float32), 30.0), gt=gt)
 
 
@@ -512,3 +541,33 @@ def synthetic_hmr_camera(num_frames: int, seed: int = 5):
     size = np.tile(np.array([[480.0, 640.0]]), (num_frames, 1))
     scale = 0.35 + 0.1 * u[:, [5]]
     return [torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)) for a in (pred_cam, center, size, scale)]
+
+
+def synthetic_camera(seq: SyntheticSequence, distance: float = 4.0, focal: float = 1000.0, centre=(960.0, 540.0)) -> np.ndarray:
+    """A fixed pinhole camera for a z-up capture, as one row of 16 floats (A 3x3 row-major, b, fx, fy, cx, cy; p = A J + b):
+    it stands `distance` metres in front of the mean ground-truth joint and looks along world +y; image x is world x, image y is
+    world -z.  Pixels."""
+    A = np.array([[1.0, 0.0, 0.0], [0.0, 0.0, -1.0], [0.0, 1.0, 0.0]])
+    mean = np.asarray(seq.gt["joints"], dtype=np.float64)[:, :24].reshape(-1, 3).mean(axis=0)
+    b = np.array([0.0, 0.0, float(distance)]) - A @ mean
+    return np.concatenate([A.reshape(-1), b, [float(focal), float(focal), float(centre[0]), float(centre[1])]])
+
+
+def synthetic_keypoints_2d(seq: SyntheticSequence, camera=None, noise: float = 2.0, seed: int = 0, dropped_frames=()):
+    """EXTENSION: the `keypoints_2d` record of a synthetic capture (terms.check_keypoints_2d) -- the 24 ground-truth kinematic
+    joints projected through one fixed camera (`camera`: 16 floats, default synthetic_camera(seq)), plus Gaussian noise of
+    `noise` units (pixels) per coordinate from the hash stream of `seed`; confidence 1, and 0 in every frame of
+    `dropped_frames` (a detector that lost the person).  Targets made from the ground truth: what a perfect calibration and an
+    unbiased detector would give."""
+    from .body_model import hash_normal
+
+    J = np.asarray(seq.gt["joints"], dtype=np.float64)[:, :24]
+    F = J.shape[0]
+    cam = np.asarray(synthetic_camera(seq) if camera is None else camera, dtype=np.float64).reshape(16)
+    p = J @ cam[:9].reshape(3, 3).T + cam[9:12]
+    u = np.stack([cam[12] * p[..., 0] / p[..., 2] + cam[14], cam[13] * p[..., 1] / p[..., 2] + cam[15]], axis=-1)
+    u = u + float(noise) * hash_normal(104729 * (int(seed) + 1), F, 24, 2)
+    conf = np.ones((F, 24))
+    conf[list(dropped_frames)] = 0.0
+    f32 = lambda x: torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
+    return {"camera": f32(np.tile(cam[None], (F, 1))), "targets": f32(u), "confidence": f32(conf)}

@@ -210,6 +210,79 @@ def stage_prior_confidence(config: Dict, stage: str):
     return {"gap_weight": float(gw), "ramp": int(ramp), "joint_weights": jw}
 
 
+#: joints of the key-point reprojection term: the 24 kinematic joints
+KEYPOINTS_2D_JOINTS = 24
+
+
+def stage_keypoints_2d(config: Dict, stage: str) -> Dict:
+    """EXTENSION: the 2D key-point reprojection term of the chamfer or marker stage (uuo_fit_set_keypoints2d) as a config states
+    it -- stages.<stage>.losses.keypoints_2d (a weight on the camera's own squared units, pixels^2 or image-size-1 units^2;
+    absent or 0 = off; negative or non-finite weights are refused) and the optional stages.<stage>.keypoints_2d: null or
+    {sigma: 0.0, min_depth: 0.1, joint_weights: null}: `sigma` >= 0, the Geman-McClure scale of the residual in the camera's
+    units (0 = the square); `min_depth` > 0, the least camera depth at which a joint counts; `joint_weights`, null (ones) or 24
+    finite values >= 0 that multiply the confidences (entry j is SMPL joint j).  Every key may be left out; unknown keys, and
+    values outside these ranges, are a ValueError.  Returns {"w", "sigma", "min_depth", "joint_weights"}.  The evidence itself --
+    cameras, targets, confidences -- is the `keypoints_2d` record of the call (check_keypoints_2d).  (The part stage refuses
+    the key with its other unknown losses.)"""
+    v = _weight(config, stage, KEYPOINTS.keys[0])
+    blk = config["stages"][stage].get("keypoints_2d", None)
+    sigma, min_depth, jw = 0.0, 0.1, None
+    if blk is not None:
+        what = "stages.%s.keypoints_2d" % stage
+        if not isinstance(blk, dict) or set(blk) - {"sigma", "min_depth", "joint_weights"}:
+            raise ValueError("%s must be null or {sigma, min_depth, joint_weights} (got %r)" % (what, blk))
+        number = lambda q: isinstance(q, (int, float)) and not isinstance(q, bool) and math.isfinite(q)
+        sigma = blk.get("sigma", 0.0)
+        if not number(sigma) or sigma < 0.0 or (sigma != 0.0 and not 1e-18 <= sigma <= 1e18):
+            raise ValueError("%s.sigma must be 0 (the square) or a positive finite number in [1e-18, 1e18] (got %r)" % (what, sigma))
+        min_depth = blk.get("min_depth", 0.1)
+        if not number(min_depth) or not min_depth > 0.0:
+            raise ValueError("%s.min_depth must be a positive finite number (got %r)" % (what, min_depth))
+        jw = blk.get("joint_weights", None)
+        if jw is not None:
+            if not isinstance(jw, (list, tuple)) or len(jw) != KEYPOINTS_2D_JOINTS or not all(number(q) and q >= 0.0 for q in jw):
+                raise ValueError("%s.joint_weights must be null or %d finite values >= 0 (got %r)" % (what, KEYPOINTS_2D_JOINTS, jw))
+            jw = [float(q) for q in jw]
+    return {"w": v, "sigma": float(sigma), "min_depth": float(min_depth), "joint_weights": jw}
+
+
+def check_keypoints_2d(record, num_frames=None):
+    """EXTENSION: the key-point reprojection term's evidence as float32 host tensors (None stays None): a record {"camera"
+    [F, 16] (A 3x3 row-major, b, fx, fy, cx, cy: a pinhole camera per frame in world axes, p = A J + b), "targets" [F, 24, 2],
+    "confidence" [F, 24]}.  The keys, the shapes, finiteness and confidence >= 0 are checked on the host: ValueError before
+    anything touches the device."""
+    if record is None:
+        return None
+    if not isinstance(record, dict) or set(record) != {"camera", "targets", "confidence"}:
+        raise ValueError("keypoints_2d: a record {camera, targets, confidence} expected (got %s)" %
+                         (sorted(record) if isinstance(record, dict) else type(record).__name__))
+    out = {k: torch.as_tensor(v).detach().to(device="cpu", dtype=torch.float32).contiguous() for k, v in record.items()}
+    F = int(out["camera"].shape[0]) if out["camera"].dim() >= 1 else -1
+    want = {"camera": (F, 16), "targets": (F, KEYPOINTS_2D_JOINTS, 2), "confidence": (F, KEYPOINTS_2D_JOINTS)}
+    if F < 1 or (num_frames is not None and F != int(num_frames)) or any(tuple(out[k].shape) != want[k] for k in want):
+        raise ValueError("keypoints_2d: camera [F, 16], targets [F, 24, 2] and confidence [F, 24] with the markers' F = %s "
+                         "expected (got %s)" % (num_frames, {k: tuple(out[k].shape) for k in sorted(out)}))
+    if not all(bool(torch.isfinite(out[k]).all()) for k in out):
+        raise ValueError("keypoints_2d: finite cameras, targets and confidences expected")
+    if bool((out["confidence"] < 0.0).any()):
+        raise ValueError("keypoints_2d: confidences >= 0 expected")
+    return out
+
+
+def armed_keypoints(record, kp: Dict):
+    """check_keypoints_2d's record as the solvers use it, with stage_keypoints_2d's record `kp`: the confidences times the joint
+    weights -- or None when there is no record, the weight is 0 or no confidence * joint weight is positive: nothing is armed,
+    every route and every kernel is the plain one (the foot-lock term's rule for a capture without contacts)."""
+    if record is None or float(kp["w"]) == 0.0:
+        return None
+    conf = record["confidence"]
+    if kp["joint_weights"] is not None:
+        conf = (conf * torch.tensor(kp["joint_weights"], dtype=torch.float32)[None, :]).contiguous()
+    if not bool((conf > 0.0).any()):
+        return None
+    return {"camera": record["camera"], "targets": record["targets"], "confidence": conf}
+
+
 def prior_weight_table(seen, block: Dict) -> torch.Tensor:
     """EXTENSION: the pose prior's weights [F, 23] float32 (host) from `seen` [F] (mocap frames the video saw; anything
     non-zero counts) and stage_prior_confidence's record:  omega[t, j] = frame_w[t] * joint_weights[j],  d[t] the distance in
@@ -301,11 +374,11 @@ def limit_tables(lim: Dict):
 
 
 # ------------------------------------------------------------------------------- a term's state on a stage problem (`set`)
-def _set_joint_accel(p, w, contacts, weights, smpl_inference):
+def _set_joint_accel(p, w, contacts, weights, keypoints, smpl_inference):
     p.joint_accel = w
 
 
-def _set_foot_lock(p, w, contacts, weights, smpl_inference):
+def _set_foot_lock(p, w, contacts, weights, keypoints, smpl_inference):
     """Keeps a contiguous float32 device copy of the checked contact labels and the weight the workspace is armed with: `w` when
     the labels gate at least one (frame pair, foot), else 0 -- a capture without video contacts (no labels, or none that holds
     over two consecutive frames) runs the plain kernels, bit for bit."""
@@ -316,7 +389,7 @@ def _set_foot_lock(p, w, contacts, weights, smpl_inference):
         p.foot_lock = float(w)
 
 
-def _set_floor(p, floor, contacts, weights, smpl_inference):
+def _set_floor(p, floor, contacts, weights, keypoints, smpl_inference):
     """Keeps the sole points' vertex ids and the contact labels on the device, and the weights the workspace is armed with
     (floor_weights).  With both 0 nothing is armed -- the model's tables are not even looked at -- and the problem runs the plain
     kernels, bit for bit."""
@@ -332,7 +405,7 @@ def _set_floor(p, floor, contacts, weights, smpl_inference):
         p.floor_contacts = contacts.to(device=p.device, dtype=torch.float32).contiguous()
 
 
-def _set_capsules(p, caps, contacts, weights, smpl_inference):
+def _set_capsules(p, caps, contacts, weights, keypoints, smpl_inference):
     """Keeps the weight and contiguous HOST copies of the capsule lists, which the library checks and copies at the call.  With
     weight 0 nothing is armed and the problem runs the plain kernels, bit for bit."""
     if float(caps["w"]) == 0.0:
@@ -344,7 +417,7 @@ def _set_capsules(p, caps, contacts, weights, smpl_inference):
     p.cap_w = float(caps["w"])
 
 
-def _set_joint_limits(p, lim, contacts, weights, smpl_inference):
+def _set_joint_limits(p, lim, contacts, weights, keypoints, smpl_inference):
     """Keeps the weight and contiguous HOST copies of the two tables (row j - 1 is SMPL joint j; -inf / +inf = no bound), which
     the library checks and copies at the call.  With weight 0 nothing is armed."""
     if float(lim["w"]) == 0.0:
@@ -355,15 +428,25 @@ def _set_joint_limits(p, lim, contacts, weights, smpl_inference):
     p.lim_w = float(lim["w"])
 
 
-def _set_prior_weights(p, block, contacts, weights, smpl_inference):
+def _set_prior_weights(p, block, contacts, weights, keypoints, smpl_inference):
     """`weights` is check_prior_weights' host tensor (or None); what armed_weights leaves of it goes to the device, where the
     library reads it at every evaluation."""
     if armed_weights(weights) is not None:
         p.prior_weights = weights.to(device=p.device, dtype=torch.float32).contiguous()
 
 
+def _set_keypoints(p, kp, contacts, weights, keypoints, smpl_inference):
+    """`keypoints` is armed_keypoints' record of the call (or None: nothing is armed).  Its three tables go to the device, where
+    the library reads them at every evaluation."""
+    if keypoints is None:
+        return
+    dev = lambda t: t.to(device=p.device, dtype=torch.float32).contiguous()
+    p.kp_cam, p.kp_targets, p.kp_conf = dev(keypoints["camera"]), dev(keypoints["targets"]), dev(keypoints["confidence"])
+    p.kp_w, p.kp_sigma, p.kp_min_depth = float(kp["w"]), float(kp["sigma"]), float(kp["min_depth"])
+
+
 # ---------------------------------------------------------------- a term on the closures composed from the operators (`composed`)
-def _composed_joint_accel(w, losses, contacts, smpl_inference):
+def _composed_joint_accel(w, losses, contacts, smpl_inference, keypoints=None):
     from .losses import joint_accel_loss
 
     if JOINT_ACCEL.keys[0] not in losses:  # (the key's presence, not a positive weight)
@@ -371,7 +454,7 @@ def _composed_joint_accel(w, losses, contacts, smpl_inference):
     return "joints", lambda joints: joint_accel_loss(joints) * w
 
 
-def _composed_foot_lock(w, losses, contacts, smpl_inference):
+def _composed_foot_lock(w, losses, contacts, smpl_inference, keypoints=None):
     from .losses import foot_lock_loss
 
     if not w > 0.0 or contacts is None:  # (whenever labels were passed, whether or not they gate a frame pair)
@@ -379,7 +462,7 @@ def _composed_foot_lock(w, losses, contacts, smpl_inference):
     return "joints", lambda joints: foot_lock_loss(joints, contacts) * w
 
 
-def _composed_floor(floor, losses, contacts, smpl_inference):
+def _composed_floor(floor, losses, contacts, smpl_inference, keypoints=None):
     from .losses import floor_loss
 
     w_pen, w_con = floor_weights(floor, contacts)
@@ -389,7 +472,7 @@ def _composed_floor(floor, losses, contacts, smpl_inference):
     return "vertices", lambda vertices: floor_loss(vertices, vids, k_left, contacts, floor["height"], w_pen, w_con)
 
 
-def _composed_capsules(caps, losses, contacts, smpl_inference):
+def _composed_capsules(caps, losses, contacts, smpl_inference, keypoints=None):
     from .losses import self_penetration_loss
 
     if caps["w"] == 0.0:
@@ -398,7 +481,7 @@ def _composed_capsules(caps, losses, contacts, smpl_inference):
     return "joints", lambda joints: self_penetration_loss(joints, cj, cg, pr, caps["w"])
 
 
-def _composed_limits(lim, losses, contacts, smpl_inference):
+def _composed_limits(lim, losses, contacts, smpl_inference, keypoints=None):
     from .losses import joint_limit_loss
 
     if lim["w"] == 0.0:
@@ -407,12 +490,28 @@ def _composed_limits(lim, losses, contacts, smpl_inference):
     return "rot_body", lambda rot_body: joint_limit_loss(rot_body, lo, hi, lim["w"])
 
 
-def _composed_pose_accel(pacc, losses, contacts, smpl_inference):
+def _composed_pose_accel(pacc, losses, contacts, smpl_inference, keypoints=None):
     from .losses import pose_accel_loss
 
     if pacc["w"] == 0.0:
         return None
     return "rot_body", lambda rot_body: pose_accel_loss(rot_body, pacc["w"], pacc["joint_weights"])
+
+
+def _composed_keypoints(kp, losses, contacts, smpl_inference, keypoints=None):
+    from .losses import keypoints_2d_loss
+
+    if keypoints is None:  # (armed_keypoints: no record, weight 0 or no positive confidence)
+        return None
+    cache = {}
+
+    def term(joints):
+        key = (joints.device, joints.dtype)
+        if key not in cache:
+            cache[key] = [keypoints[k].to(device=joints.device, dtype=joints.dtype) for k in ("camera", "targets", "confidence")]
+        return keypoints_2d_loss(joints, *cache[key], kp["w"], kp["sigma"], kp["min_depth"])
+
+    return "joints", term
 
 
 # ------------------------------------------------------------------------------------------------------------- the table
@@ -435,7 +534,8 @@ class Term:
     fused: bool = True         # False: no fused closure, the term always runs composed
     batch: bool = False        # True: a lock-step batch carries the term (on its fused closure)
     # the term on a stage problem: the attribute (dotted path) that is non-zero when the problem carries it, the attributes it
-    # keeps with their off values, set(problem, record, contacts, weights, smpl_inference) at construction, and the library call
+    # keeps with their off values, set(problem, record, contacts, weights, keypoints, smpl_inference) at construction -- the
+    # checked contact labels, prior weights and armed key-point record of the call -- and the library call
     # that arms a workspace, with its arguments off and on(problem)
     flag: str = None
     state: Dict = dataclasses.field(default_factory=dict)
@@ -451,8 +551,8 @@ class Term:
     frame_table: str = None
     no_closure: str = None
     fused_only: str = None     # ... or of every route but the plain fused closures, whichever it is (%s = the route)
-    # (record, losses, contacts, smpl_inference) -> None | (input, function): the term on the composed closures, a function of
-    # "joints" (joints[:, :24]), "vertices" or "rot_body" (normalize_rot(p_pose))
+    # (record, losses, contacts, smpl_inference, keypoints=None) -> None | (input, function): the term on the composed closures, a
+    # function of "joints" (joints[:, :24]), "vertices" or "rot_body" (normalize_rot(p_pose))
     composed: Callable = None
 
     def __post_init__(self):
@@ -531,6 +631,16 @@ PRIOR = Term(
     sharded="stages.%s.prior_confidence (extension): the pose prior's weights are not built for " + _SHARDING,
     sharded_by_route=True,
     soft="stages.chamfer: the pose prior's weights (prior_confidence) are not built for the soft-assignment closure")
+KEYPOINTS = Term(
+    "the key-point reprojection term", stage_keypoints_2d, lambda r: r["w"] > 0.0, keys=("keypoints_2d",), switch="keypoints_fused",
+    flag="keypoints_on",
+    # the three tables on the device: cameras [F, 16], targets [F, 24, 2], confidences times joint weights [F, 24], float32
+    state={"kp_w": 0.0, "kp_sigma": 0.0, "kp_min_depth": 0.0, "kp_cam": None, "kp_targets": None, "kp_conf": None},
+    set=_set_keypoints, setter="uuo_fit_set_keypoints2d", off_args=(c_float(0.0), c_float(0.0), c_float(0.0), None, None, None),
+    on_args=lambda p: (c_float(p.kp_w), c_float(p.kp_sigma), c_float(p.kp_min_depth), p.kp_cam.data_ptr(), p.kp_targets.data_ptr(),
+                       p.kp_conf.data_ptr()),
+    sharded="stages.%s.losses.keypoints_2d (extension): the key-point reprojection term is not built for " + _SHARDING,
+    soft=_SOFT % "key-point reprojection term (keypoints_2d)", composed=_composed_keypoints)
 POSE_ACCEL = Term(
     "the pose-acceleration term", stage_pose_accel, lambda r: r["w"] > 0.0, keys=("pose_accel",), fused=False,
     sharded=_COUPLES % "pose_accel", sharded_by_route=True,
@@ -539,7 +649,7 @@ POSE_ACCEL = Term(
 
 #: one row per extension term.  The order is that of the library calls in _StageProblem._arm, of the refusals of
 #: engine.solve_batch and of the sharded solves, and of the terms in the composed closures' sum
-TERMS = (ROBUST, JOINT_ACCEL, LATENT_OFFSETS, FOOT_LOCK, FLOOR, CAPSULES, LIMITS, PRIOR, POSE_ACCEL)
+TERMS = (ROBUST, JOINT_ACCEL, LATENT_OFFSETS, FOOT_LOCK, FLOOR, CAPSULES, LIMITS, PRIOR, KEYPOINTS, POSE_ACCEL)
 #: the order in which a stage problem's constructor looks at the terms that can refuse it (that of its refusals, kept)
 PROBLEM_ORDER = (CAPSULES, LIMITS, POSE_ACCEL, JOINT_ACCEL, FOOT_LOCK, FLOOR)
 
@@ -569,10 +679,21 @@ def composed_keys(stage: str) -> set:
 class StageTerms:
     """The terms of one stage of a config: terms[ROW] is the row's parsed record, parsed at the first look and kept (so a
     refusal or a ValueError of a parser surfaces where the record is first needed, as it always has).  `prior_weights` is the
-    armed table of the call (armed_weights), None when there is none."""
+    armed table of the call (armed_weights), None when there is none; `keypoints` the armed key-point record of the call
+    (arm_keypoints), None when there is none."""
 
     def __init__(self, config: Dict, stage: str, prior_weights=None):
         self.config, self.stage, self.prior_weights, self._records = config, stage, prior_weights, {}
+        self.keypoints = None
+
+    def arm_keypoints(self, record, num_frames=None):
+        """The call's `keypoints_2d` record, checked on the host (check_keypoints_2d) and reduced to what acts
+        (armed_keypoints) with the stage's block, which is parsed here whether or not there is a record.  None leaves what an
+        earlier call armed.  Returns self.keypoints."""
+        kp = self[KEYPOINTS]
+        if record is not None:
+            self.keypoints = armed_keypoints(check_keypoints_2d(record, num_frames), kp)
+        return self.keypoints
 
     def __getitem__(self, term: Term):
         if term not in self._records:
@@ -584,7 +705,10 @@ class StageTerms:
         return term.on(self[term])
 
     def active(self, term: Term) -> bool:
-        """True when the term acts in this call: on -- PRIOR: when a table is armed, whatever the config says."""
+        """True when the term acts in this call: on -- PRIOR: when a table is armed, whatever the config says; KEYPOINTS: when a
+        record is armed (which takes the key on)."""
+        if term is KEYPOINTS:
+            return self.keypoints is not None
         return self.prior_weights is not None if term is PRIOR else self.on(term)
 
     def execution(self, switch: str) -> bool:
@@ -599,7 +723,8 @@ class StageTerms:
 
     def composed_tail(self, losses: Dict, contacts, smpl_inference):
         """The terms that the composed closures add after the reference's, as (input, function) pairs in TERMS' order."""
-        pairs = [t.composed(self[t], losses, contacts, smpl_inference) for t in TERMS if t.composed is not None]
+        pairs = [t.composed(self[t], losses, contacts, smpl_inference, keypoints=self.keypoints)
+                 for t in TERMS if t.composed is not None]
         return [p for p in pairs if p is not None]
 
     def refuse_latent_offsets(self, route: str):
@@ -610,7 +735,8 @@ class StageTerms:
         """Frame-block sharding: the refusals of the sharded solve itself (the latent offsets' last), or -- `only` -- those of
         the terms the route refuses on the way (PRIOR on the config block alone too, even without a table)."""
         for t in only or [t for t in TERMS if t.sharded and not t.sharded_by_route]:
-            if self.stage in t.stages and (self.active(t) or self.on(t)):
+            # (KEYPOINTS: only with an armed record -- without one the key changes nothing, a refusal included)
+            if self.stage in t.stages and (self.active(t) or (self.on(t) and t is not KEYPOINTS)):
                 raise NotImplementedError(t.sharded % self.stage)
         if only is None and self.stage == "marker":
             self.refuse_latent_offsets(_SHARDING)

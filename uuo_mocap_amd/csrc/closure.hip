@@ -392,7 +392,9 @@ __device__ unsigned long long g_bwd_stamps[4096 * BWD_NSTAMP];
 // EXTENSION: the Geman-McClure weight of a data item's square s (SMPLify's GMoF): rho(s) = s q, rho'(s) = q^2
 __device__ __forceinline__ float gmof_q(float sig2, float s) { return sig2 / (sig2 + s); }
 
-#define BWD_NW 4  // waves per frame block: one per SIMD, so up to three blocks share a CU at 168 VGPRs.  (6 waves -- 24 item
+#define BWD_NW 4  // waves per frame block: one per SIMD, so up to three blocks share a CU at <= 168 VGPRs -- and two of the plain
+                  // kernel's (<= 160 VGPRs, 24.8 KB of LDS: BWD_WPE3_V160, BwdLdsPhased) a CU that holds a k_skin3 block of
+                  // another chain (191 VGPRs, 108 KB), where one fitted at 168 VGPRs and 42 KB.  (6 waves -- 24 item
                   // slots, 3 rounds for M = 50 instead of 4 -- place 2,2,1,1 waves on the SIMDs and a second block no longer
                   // fits at 3 waves per SIMD: 300 blocks then run in two rounds on 256 CUs, 24.8 -> 38.5 us.  8 waves need
                   // <= 128 VGPRs for two blocks per CU and spill: 43 -> 73 us.)
@@ -478,7 +480,56 @@ enum : unsigned {
   BWD_OFFS = 1u << 6,
   BWD_FASSIGN = 1u << 7,
   BWD_FLOOR = 1u << 8,
+  BWD_WIDE = 1u << 9,  // debug flavour only: the one-array-per-name LDS layout on a general kernel (BWD_WIDE_KERNELS)
 };
+// The float arrays of a general backward block's LDS, by phase.  (The frame, the tree's tables, w_red, red and the ACCEL window live
+// through all of them and stay outside.)
+//   LOOP    sA, spf read and w_dA accumulated by the item loop
+//   REDUCE  w_dA summed over the slots in place (thread i owns column i of every row: the sum lands in row 0, which is sdA from
+//           then on), barrier, the slots' acc_pf registers stored as w_dpf, barrier, w_dpf summed over the slots into sdpf
+//   TAIL    sdA, sdpf read; the kinematic sweep's arrays, the writers' statistics and the shape gradient's 240 products (js)
+// REDUCE's and TAIL's arrays take the bytes that LOOP's leave: sdpf those of spf, sdA row 0 of w_dA, w_dpf its rows 1 .. (13 312
+// of 17 280 B), the tail's arrays those of w_dpf; sA's stay unused after the loop.  20 416 B where one array per name took
+// 38 560, so that a general block holds 24.8 KB and two of them fit beside a k_skin3 block.  The part stage's kernels
+// (w_dpf is one row of scratch there, the whole a fraction of this) and, in the debug flavour, the BWD_WIDE forms of the general
+// ones keep one array per name.
+constexpr int BWD_NA = UUO_NUM_JOINTS * 12;
+struct BwdLdsTail {
+  float sdGR[UUO_NUM_JOINTS][9], sdGt[UUO_NUM_JOINTS][3], sdJ[UUO_NUM_JOINTS][3], sdR[UUO_NUM_JOINTS][9];
+  float spsq[UUO_NUM_JOINTS];
+  float sstat[28][4];  // per writer: g.d, sum|g|, g.g, max|g| (0..22 body joints, 23 root/z, 24..26 transl)
+};
+template <int SLOTS>
+struct BwdLdsPhased {
+  union {
+    struct {  // LOOP
+      float sA[BWD_NA], spf[UUO_KB];
+      float w_dA[SLOTS][BWD_NA];  // private accumulators: one per (wave, 16-lane group)
+    };
+    struct {  // REDUCE, TAIL
+      float sA_unused[BWD_NA], sdpf[UUO_KB];
+      float sdA[BWD_NA];
+      union {
+        float w_dpf[SLOTS][UUO_KB];  // REDUCE
+        struct {                      // TAIL
+          BwdLdsTail t;
+          float js[240];
+        };
+      };
+    };
+  };
+};
+static_assert(offsetof(BwdLdsPhased<BWD_SLOTS>, sdpf) == offsetof(BwdLdsPhased<BWD_SLOTS>, spf) &&
+              offsetof(BwdLdsPhased<BWD_SLOTS>, sdA) == offsetof(BwdLdsPhased<BWD_SLOTS>, w_dA) &&
+              offsetof(BwdLdsPhased<BWD_SLOTS>, w_dpf) == offsetof(BwdLdsPhased<BWD_SLOTS>, w_dA) + sizeof(float) * BWD_NA &&
+              sizeof(BwdLdsPhased<BWD_SLOTS>) == sizeof(float) * (BWD_NA + UUO_KB + BWD_SLOTS * BWD_NA),
+              "REDUCE and TAIL fit into LOOP's bytes: sdA is row 0 of w_dA, w_dpf and the tail's arrays start at row 1");
+// (a name of the phased struct, or the array of its own that the name has in the other instantiations)
+template <bool PHASED, class A, class B>
+__device__ __forceinline__ auto& bwd_lds_pick(A& phased, B& own) {
+  if constexpr (PHASED) return phased;
+  else return own;
+}
 template <unsigned FL>
 __device__ __forceinline__ void bwd_body(const BwdArgs& a) {
   constexpr bool PART = (FL & BWD_PART) != 0, DENSE = (FL & BWD_DENSE) != 0, ITEMS = (FL & BWD_ITEMS) != 0;
@@ -501,18 +552,37 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a) {
   // latency-bound kernel of a solve chain: do not queue behind co-resident MFMA waves.  (Not the one-wave part-stage form:
   // a batch launches tens of thousands of those, and at a raised priority they starve the other group's solver kernels.)
   if constexpr (NWV == BWD_NW) __builtin_amdgcn_s_setprio(2);
+  // the general kernels overlay the phases of their LDS (BwdLdsPhased); PF_LDS: the sparse ones among them -- the kernels under a
+  // register cap (BWD_WPE3, BWD_WPE3_V160) -- read the pose features from spf inside the item loop instead of holding them
+  // (the two at 160 need it; the others lose their spills by it, and with the features in registers the new layout gave
+  // k_bwd_sparse_f 16 B of scratch where it had none)
+  constexpr bool PHASED = !PART && !(FL & BWD_WIDE), PF_LDS = PHASED && !DENSE && !ITEMS;
   __shared__ FrameLds L;
-  __shared__ float sA[UUO_NUM_JOINTS * 12];
-  __shared__ float spf[UUO_KB];
-  __shared__ float w_dA[SLOTS][UUO_NUM_JOINTS * 12];  // private accumulators: one per (wave, 16-lane group)
-  __shared__ float w_dpf[PART ? 1 : SLOTS][PART ? 256 : UUO_KB];  // (the shape-gradient tail borrows 240 entries from row 0)
+  __shared__ BwdLdsPhased<SLOTS> S;  // PHASED; the arrays below otherwise (whichever set an instantiation does not name is not allocated)
+  __shared__ float sA_[UUO_NUM_JOINTS * 12];
+  __shared__ float spf_[UUO_KB];
+  __shared__ float w_dA_[SLOTS][UUO_NUM_JOINTS * 12];
+  __shared__ float w_dpf_[PART ? 1 : SLOTS][PART ? 256 : UUO_KB];  // (the shape-gradient tail borrows 240 entries from row 0)
+  __shared__ float sdA_[UUO_NUM_JOINTS * 12];
+  __shared__ float sdpf_[UUO_KB];
+  __shared__ float sdGR_[UUO_NUM_JOINTS][9], sdGt_[UUO_NUM_JOINTS][3], sdJ_[UUO_NUM_JOINTS][3], sdR_[UUO_NUM_JOINTS][9];
+  __shared__ float spsq_[UUO_NUM_JOINTS];
+  __shared__ float sstat_[28][4];
+  auto& sA = bwd_lds_pick<PHASED>(S.sA, sA_);
+  auto& spf = bwd_lds_pick<PHASED>(S.spf, spf_);
+  auto& w_dA = bwd_lds_pick<PHASED>(S.w_dA, w_dA_);
+  auto& w_dpf = bwd_lds_pick<PHASED>(S.w_dpf, w_dpf_);
+  auto& sdA = bwd_lds_pick<PHASED>(S.sdA, sdA_);
+  auto& sdpf = bwd_lds_pick<PHASED>(S.sdpf, sdpf_);
+  auto& sdGR = bwd_lds_pick<PHASED>(S.t.sdGR, sdGR_);
+  auto& sdGt = bwd_lds_pick<PHASED>(S.t.sdGt, sdGt_);
+  auto& sdJ = bwd_lds_pick<PHASED>(S.t.sdJ, sdJ_);
+  auto& sdR = bwd_lds_pick<PHASED>(S.t.sdR, sdR_);
+  auto& spsq = bwd_lds_pick<PHASED>(S.t.spsq, spsq_);
+  auto& sstat = bwd_lds_pick<PHASED>(S.t.sstat, sstat_);
+  float* const sjs = PHASED ? &S.js[0] : &w_dpf_[0][0];
   __shared__ float w_red[SLOTS][16];
-  __shared__ float sdA[UUO_NUM_JOINTS * 12];
-  __shared__ float sdpf[UUO_KB];
   __shared__ float red[16];
-  __shared__ float sdGR[UUO_NUM_JOINTS][9], sdGt[UUO_NUM_JOINTS][3], sdJ[UUO_NUM_JOINTS][3], sdR[UUO_NUM_JOINTS][9];
-  __shared__ float spsq[UUO_NUM_JOINTS];
-  __shared__ float sstat[28][4];  // per writer: g.d, sum|g|, g.g, max|g| (0..22 body joints, 23 root/z, 24..26 transl)
   __shared__ int s_lvl_n[UUO_MAX_DEPTH], s_lvl_j[UUO_MAX_DEPTH][UUO_LEVEL_W], s_lvl_p[UUO_MAX_DEPTH][UUO_LEVEL_W];
   __shared__ int s_nch[UUO_NUM_JOINTS], s_ch[UUO_NUM_JOINTS][4];
   // ACCEL: [5][75] G^t (72) and trans (3) of frames f-2 .. f+2 (zeros outside the sequence), then [72] dL/dJ_f, [72] |a_f|^2 terms
@@ -573,7 +643,9 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a) {
   for (int i = tid; i < SLOTS * UUO_NUM_JOINTS * 12; i += NT) (&w_dA[0][0])[i] = 0.f;
   // w_dpf is written whole by plain stores at the end of the item loop; w_red's used entries likewise (every slot stores
   // its 14 sums)
-  for (int i = tid; i < 28 * 4; i += NT) (&sstat[0][0])[i] = 0.f;
+  if constexpr (!PHASED) {  // (PHASED: sstat takes bytes of w_dA's; zeroed after the reduction)
+    for (int i = tid; i < 28 * 4; i += NT) (&sstat[0][0])[i] = 0.f;
+  }
   __syncthreads();
 
   if (a.stop == 1) return;
@@ -620,9 +692,9 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a) {
     // that stay inside the DPP row (no v_readlane).  M = 50 -> 4 rounds per block instead of 13 per wave.
     const int gq = lane >> 4, sl = lane & 15;
     const int slot = wave * 4 + gq;  // 0..15
-    float fk[13];
+    float fk[13];  // this sub-lane's pose features (PF_LDS: re-read from spf every round, thirteen registers fewer through the loop)
 #pragma unroll
-    for (int t = 0; t < 13; ++t) fk[t] = PART ? 0.f : spf[sl + 16 * t];
+    for (int t = 0; t < 13; ++t) fk[t] = (PART || PF_LDS) ? 0.f : spf[sl + 16 * t];
     const float beta_s = (sl < 10) ? L.beta[sl] : 0.f;
     float acc_pf[13];
 #pragma unroll
@@ -748,6 +820,12 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a) {
         vp[2] = cur.vt2 + row_sum(cur.st2 * beta_s);
       } else {
         float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+        if constexpr (PF_LDS) {  // (same operands in the same order; the offset passes through an empty asm so that the loads
+          int sl_r = sl;         // are this round's and not hoisted back into thirteen registers)
+          asm volatile("" : "+v"(sl_r));
+#pragma unroll
+          for (int t = 0; t < 13; ++t) fk[t] = spf[sl_r + 16 * t];
+        }
 #pragma unroll
         for (int t = 0; t < 13; ++t) {
           s0 = fmaf(cur.p[0][t], fk[t], s0);
@@ -833,21 +911,20 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a) {
       acc_dt16 += (sl == 0) ? g[0] : ((sl == 1) ? g[1] : g[2]);  // sub-lanes 0..2
       acc_loss16 += loss_item;                                     // sub-lane 0 is the one that is stored
     }
-    if constexpr (!PART) {
+    if constexpr (!PART && !PHASED) {
 #pragma unroll
       for (int t = 0; t < 13; ++t) w_dpf[slot][sl + 16 * t] = acc_pf[t];
     }
     if (sl == 0) w_red[slot][0] = acc_loss16;
     if (sl < 3) w_red[slot][1 + sl] = acc_dt16;
     if (sl < 10) w_red[slot][4 + sl] = acc_db16;
-  }
 
   if (a.stop == 2) return;
   BWD_STAMP(2);
   // ---- block reduction over the accumulation slots (fixed order -> deterministic)
   __syncthreads();
   BWD_STAMP(3);
-  if constexpr (!PART) {
+  if constexpr (!PART && !PHASED) {
     if (tid < UUO_KB) {
       float acc = w_dpf[0][tid];
 #pragma unroll
@@ -855,7 +932,7 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a) {
       sdpf[tid] = acc;
     }
   }
-  for (int i = tid; i < UUO_NUM_JOINTS * 12; i += NT) {
+  for (int i = tid; i < UUO_NUM_JOINTS * 12; i += NT) {  // (PHASED: in place -- sdA is row 0, column i is this thread's alone)
     float acc = w_dA[0][i];
 #pragma unroll
     for (int w = 1; w < SLOTS; ++w) acc += w_dA[w][i];
@@ -867,8 +944,24 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a) {
     for (int w = 1; w < SLOTS; ++w) acc += w_red[w][tid];
     red[tid] = acc;
   }
+  if constexpr (PHASED) {  // rows 1 .. of w_dA are free once every column is summed: the slots' pose-feature sums go through them
+    __syncthreads();
+#pragma unroll
+    for (int t = 0; t < 13; ++t) w_dpf[slot][sl + 16 * t] = acc_pf[t];
+    __syncthreads();
+    if (tid < UUO_KB) {
+      float acc = w_dpf[0][tid];
+#pragma unroll
+      for (int w = 1; w < SLOTS; ++w) acc += w_dpf[w][tid];
+      sdpf[tid] = acc;
+    }
+  }
+  }  // (the item loop's scope: acc_pf lives to here)
   }  // !use_pre
   __syncthreads();
+  if constexpr (PHASED) {  // (the statistics' bytes were w_dpf's until this barrier)
+    for (int i = tid; i < 28 * 4; i += NT) (&sstat[0][0])[i] = 0.f;
+  }
 
   if (a.stop == 3) return;
   BWD_STAMP(4);
@@ -1021,12 +1114,12 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a) {
   // shape gradient of this frame: direct (blend shapes) + joint path (240 threads: one (joint, beta) pair each)
   for (int t = tid; t < 240; t += NT) {
     const int jj = t / 10, l = t - jj * 10;
-    w_dpf[0][t] = fmaf(tree->JS[jj][2][l], sdJ[jj][2], fmaf(tree->JS[jj][1][l], sdJ[jj][1], tree->JS[jj][0][l] * sdJ[jj][0]));
+    sjs[t] = fmaf(tree->JS[jj][2][l], sdJ[jj][2], fmaf(tree->JS[jj][1][l], sdJ[jj][1], tree->JS[jj][0][l] * sdJ[jj][0]));
   }
   __syncthreads();
   if (tid < 10) {
     float acc = red[4 + tid];
-    for (int jj = 0; jj < UUO_NUM_JOINTS; ++jj) acc += w_dpf[0][jj * 10 + tid];
+    for (int jj = 0; jj < UUO_NUM_JOINTS; ++jj) acc += sjs[jj * 10 + tid];
     BWD_FP_STORE(4 + tid, acc);
     if (a.stage == UUO_STAGE_UPSTREAM) a.g_betas_frame[(size_t)f * 10 + tid] = acc;
   }
@@ -1210,15 +1303,20 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a) {
 // run, and a backward block of another yaw hypothesis / sequence can only start beside it if it fits in the remaining
 // 176 (at 238 registers it waited for the skinning kernel to drain: +1.7 % fit throughput, same single-stream time).
 #define BWD_WPE3 __attribute__((amdgpu_waves_per_eu(3, 3)))
+// The plain and the robust sparse kernel -- the fitted stages' backward in the benchmark -- are held to 160: two of their blocks
+// then fit beside a k_skin3 block, 191 + 2 x 160 <= 512 (and twice 24.8 KB of LDS beside its 108 KB, BwdLdsPhased).  The number
+// is given per half of the unified register file on this target: amdgpu_num_vgpr(80) caps the kernel at 160, (160) at nothing.
+// Without spills only because the thirteen pose features are read from LDS inside the item loop (PF_LDS).
+#define BWD_WPE3_V160 __attribute__((amdgpu_waves_per_eu(3, 3), amdgpu_num_vgpr(80)))
 #define BWD_NO_ATTR
 #define BWD_NO_OP (-1)
 // Every instantiation of bwd_body, one row each: X(entry point, flag word, threads per block, attribute, UUO_OP_* of its lock-step
 // record or BWD_NO_OP); XB(..., batch twin) where a lock-step batch form exists (blockIdx.z picks the problem).  The entry points,
 // the host's table of them (bwd_kernels) and the batched launch all come from this list; a new term is a flag and its rows.
 #define BWD_KERNELS(X, XB)                                                                                                       \
-  XB(k_bwd_sparse, 0u, BWD_NW * 64, BWD_WPE3, UUO_OP_BWD, k_bwd_sparse_b)                                                         \
+  XB(k_bwd_sparse, 0u, BWD_NW * 64, BWD_WPE3_V160, UUO_OP_BWD, k_bwd_sparse_b)                                                   \
   /* EXTENSION: the same with the Geman-McClure data term (uuo_problem_t.robust_sigma > 0) */                                    \
-  XB(k_bwd_sparse_r, BWD_ROBUST, BWD_NW * 64, BWD_WPE3, UUO_OP_BWD_R, k_bwd_sparse_b_r)                                           \
+  XB(k_bwd_sparse_r, BWD_ROBUST, BWD_NW * 64, BWD_WPE3_V160, UUO_OP_BWD_R, k_bwd_sparse_b_r)                                     \
   /* EXTENSION: the two with the joint-acceleration smoothness term (uuo_fit_set_joint_accel; no lock-step batch forms) */       \
   X(k_bwd_sparse_t, BWD_ACCEL, BWD_NW * 64, BWD_WPE3, BWD_NO_OP)                                                                  \
   X(k_bwd_sparse_r_t, BWD_ROBUST | BWD_ACCEL, BWD_NW * 64, BWD_WPE3, BWD_NO_OP)                                                   \
@@ -1285,6 +1383,18 @@ struct BwdKernel {
 #define BWD_ROW(name, fl, nt, attr, op) {(fl), (nt), (op), #name, name, nullptr},
 #define BWD_ROW_B(name, fl, nt, attr, op, twin) {(fl), (nt), (op), #name, name, twin},
 static const BwdKernel bwd_kernels[] = {BWD_KERNELS(BWD_ROW, BWD_ROW_B)};
+#ifdef UUO_DEBUG_HOOKS
+// debug flavour only: the plain, robust and temporal sparse kernels on the one-array-per-name LDS layout, the pose features in
+// registers, under the former attribute, to compare the phased layout against (UUO_BWD_WIDE_LDS=1 in uuo_closure_eval_impl; tests/
+// test_gpu_bwd_residency.py).  Not rows of bwd_kernels: nothing selects them by their facts.
+#define BWD_WIDE_KERNELS(X)                                                          \
+  X(k_bwd_sparse_wide, BWD_WIDE, BWD_NW * 64, BWD_WPE3, BWD_NO_OP)                    \
+  X(k_bwd_sparse_r_wide, BWD_WIDE | BWD_ROBUST, BWD_NW * 64, BWD_WPE3, BWD_NO_OP)     \
+  X(k_bwd_sparse_t_wide, BWD_WIDE | BWD_ACCEL, BWD_NW * 64, BWD_WPE3, BWD_NO_OP)      \
+  X(k_bwd_sparse_r_t_wide, BWD_WIDE | BWD_ROBUST | BWD_ACCEL, BWD_NW * 64, BWD_WPE3, BWD_NO_OP)
+BWD_WIDE_KERNELS(BWD_ENTRY)
+static const BwdKernel bwd_wide_kernels[] = {BWD_WIDE_KERNELS(BWD_ROW)};
+#endif
 
 // What decides the instantiation of a backward launch, and the one place that decides it.
 struct BwdFacts {
@@ -2517,6 +2627,16 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
   const BwdKernel* bk = nullptr;
   rc = bwd_select(k, &bk);
   if (rc) return rc;
+#ifdef UUO_DEBUG_HOOKS
+  if (UUO_ENV_INT("UUO_BWD_WIDE_LDS", 0)) {  // debug flavour only: the same instantiation on the former LDS layout, for comparison
+    const BwdKernel* wide = nullptr;
+    for (const BwdKernel& row : bwd_wide_kernels)
+      if (row.flags == (bk->flags | BWD_WIDE)) wide = &row;
+    UUO_REQUIRE(wide && !uuo_recorder, std::string("closure: UUO_BWD_WIDE_LDS has no form of ") + bk->name +
+                                           (uuo_recorder ? " inside a lock-step batch" : ""));
+    bk = wide;
+  }
+#endif
   if (bk->op == BWD_NO_OP || !uuo_record(bk->op, F, (bk->flags & BWD_PART) ? bk->threads / 64 : 1, a))
     hipLaunchKernelGGL((bk->kernel), dim3(F), dim3(bk->threads), 0, s, a);
   UUO_HIP_CHECK(hipGetLastError());

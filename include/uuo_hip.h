@@ -305,6 +305,25 @@ int uuo_fit_set_capsules(uuo_fit_t* fit, float w, int32_t n_caps, const int32_t*
  * the per-frame vertex table.  Refused (at evaluation) for the part stage and with w_soft != 0, and inside lock-step batches
  * (uuo_batch_*). */
 int uuo_fit_set_joint_limits(uuo_fit_t* fit, float w, const float* h_lo, const float* h_hi);
+/* EXTENSION (not reference behaviour): a pose-acceleration term on the LOCAL rotations of the 23 body joints of the chamfer and
+ * marker stages.  R_t[j] is joint j's local rotation in frame t as the forward forms it (the stage's Gram-Schmidt of the raw
+ * entries, or the raw entries themselves where the stage does not normalise), u[23] >= 0 joint weights:
+ *   a_t[j] = R_t[j] - 2 R_{t+1}[j] + R_{t+2}[j]                          t = 0 .. F-3
+ *   loss += w / ((F - 2) 207) sum_t sum_j u[j] |a_t[j]|_F^2
+ *   dL/dR_s[j] = 2 w / ((F - 2) 207) u[j] (a_s - 2 a_{s-1} + a_{s-2})    a_t outside 0 .. F-3 counts as 0
+ * in rad^2 per frame^4: the weight belongs to the frame rate.  The term couples neighbouring frames.  With F < 3 it has no terms:
+ * no kernel runs and every result is that of a workspace without the setting.  The root orientation, z, the translation and the
+ * shape are not read.  The gradient reaches the raw 3x3 pose entries through the stage's own Gram-Schmidt backward: third raw
+ * rows receive exact zeros from the term; a joint of weight 0 receives nothing.
+ * A setting of the WORKSPACE (off at creation) with the lifetime rules of uuo_fit_set_joint_limits.  h_joint_weights is a HOST
+ * array [23] (entry j - 1 is SMPL joint j) or null (ones), checked and COPIED at the call.  A call with the table of the
+ * previous call uploads nothing; a new table waits for the last evaluation that read the old one, on its stream alone.
+ * w == 0 switches the term off and looks at nothing else.  Errors (-22): a negative or non-finite w, a NaN, negative or
+ * non-finite joint weight; a refused call changes nothing.
+ * Sums in a fixed order, no atomics: results are bit-reproducible.  Works with what uuo_fit_set_joint_limits works with, with
+ * that term, the pose prior's weights and the key-point reprojection term.  Refused (at evaluation, -22) for the part stage
+ * and with w_soft != 0, and inside lock-step batches (uuo_batch_*).  uuo_problem_t and uuo_abi_version() are unchanged. */
+int uuo_fit_set_pose_accel(uuo_fit_t* fit, float w, const float* h_joint_weights);
 /* EXTENSION (not reference behaviour; the reference's author left `weighted_mse_loss(pose_body, o_pose_body, img_mask[...])`
  * commented out in its chamfer closure): a weight per (frame, body joint) on the pose prior of the chamfer and marker stages,
  * w[F][23] >= 0 (row j - 1 of a frame is SMPL joint j).  With raw the optimised raw body rotations and o = d_o_pose:

@@ -1,8 +1,9 @@
 """Weight sweep of the pose-acceleration term on the local body rotations: fits the default 300 x 50
 synthetic capture with video_mocap.yaml and with pose_accel weights over decades, and prints per setting the
 rotation-acceleration error over the leaf joints (feet 10, 11, head 15, hands 22, 23) and over all 23 body joints, the
-acceleration error of the joint positions and the mean vertex error.
-python tools/sweep_pose_accel.py [--frames 300 --markers 50 --seed 0 --weights 0:0,1:0.1,10:1]"""
+acceleration error of the joint positions and the mean vertex error.  --fused runs the term on the fused closures
+(execution.pose_accel_fused: True), where the 25-pair sweep is cheap; without it the term runs composed.
+python tools/sweep_pose_accel.py [--frames 300 --markers 50 --seed 0 --weights 0:0,1:0.1,10:1 --fused]"""
 import argparse
 import copy
 import os
@@ -30,6 +31,7 @@ def main():
     ap.add_argument("--markers", type=int, default=50)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--weights", default=DEFAULT, help="chamfer:marker rows, comma separated; 0:0 is video_mocap.yaml")
+    ap.add_argument("--fused", action="store_true", help="execution.pose_accel_fused: True (the fused closures)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     tables = synthetic_smpl(0)
@@ -46,6 +48,8 @@ def main():
     for row in a.weights.split(","):
         wc, wm = (float(v) for v in row.split(":"))
         cfg = packaged_config("video_mocap")
+        if a.fused:
+            cfg["execution"] = dict(cfg.get("execution") or {}, pose_accel_fused=True)
         for stage, w in (("chamfer", wc), ("marker", wm)):
             if w:
                 cfg["stages"][stage]["losses"]["pose_accel"] = w

@@ -131,6 +131,8 @@ _SIGNATURES = {
     "uuo_fit_set_capsules": (c_int, [c_void_p, c_float, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     # EXTENSION: joint-angle limit term of the workspace (w, host lo [23][3], host hi [23][3])
     "uuo_fit_set_joint_limits": (c_int, [c_void_p, c_float, c_void_p, c_void_p]),
+    # EXTENSION: pose-acceleration term of the workspace (w, host joint weights [23] or null = ones)
+    "uuo_fit_set_pose_accel": (c_int, [c_void_p, c_float, c_void_p]),
     # EXTENSION: per-(frame, joint) weights of the pose prior of the workspace (device [F][23]; null = off)
     "uuo_fit_set_prior_weights": (c_int, [c_void_p, c_void_p]),
     # EXTENSION: 2D key-point reprojection term of the workspace (w, sigma, min_depth, device cameras [F][16], targets

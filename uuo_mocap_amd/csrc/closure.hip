@@ -1918,6 +1918,14 @@ static int validate_problem(const uuo_fit* fit, const uuo_problem_t* p) {
               "term (w_soft)");
   UUO_REQUIRE(fit->lim_w == 0.f || !uuo_recorder,
               "closure: lock-step batches do not carry the joint-angle limit term (uuo_fit_set_joint_limits, extension)");
+  // EXTENSION: the pose-acceleration term of the workspace (uuo_fit_set_pose_accel) likewise
+  UUO_REQUIRE(fit->pacc_w == 0.f || p->stage != UUO_STAGE_PART,
+              "closure: the pose-acceleration term (uuo_fit_set_pose_accel, extension) is not built for the part stage");
+  UUO_REQUIRE(fit->pacc_w == 0.f || p->w_soft == 0.f,
+              "closure: the pose-acceleration term (uuo_fit_set_pose_accel, extension) is not built for the soft-assignment data "
+              "term (w_soft)");
+  UUO_REQUIRE(fit->pacc_w == 0.f || !uuo_recorder,
+              "closure: lock-step batches do not carry the pose-acceleration term (uuo_fit_set_pose_accel, extension)");
   // EXTENSION: the pose prior's per-(frame, joint) weights of the workspace (uuo_fit_set_prior_weights) likewise
   UUO_REQUIRE(!fit->prior_w || p->stage != UUO_STAGE_PART,
               "closure: the pose prior's weights (uuo_fit_set_prior_weights, extension) are not built for the part stage");
@@ -2438,6 +2446,17 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
   UUO_REQUIRE(!limits || (p->stage != UUO_STAGE_PART && !soft_chamfer),
               "closure: the joint-angle limit term belongs to the chamfer and marker stages' hard-assignment closures");
   if (limits) a.lim_g = fit->lim_g;  // ([F][207] gradients, then the [F] shares)
+  // EXTENSION: the pose-acceleration term: k_pose_accel (launch_side_terms below, after k_limit_fwd) leaves -- or, with the limit
+  // term on, adds -- its parameter-space gradients and the frames' shares in the same buffer.  With fewer than three frames it has
+  // no terms: no kernel runs, and the evaluation is that of a workspace without the setting.
+  const bool pose_accel = fit->pacc_w != 0.f && F >= 3;
+  UUO_REQUIRE(!pose_accel || !uuo_recorder, "closure: lock-step batches do not carry the pose-acceleration term");
+  UUO_REQUIRE(!pose_accel || (p->stage != UUO_STAGE_PART && !soft_chamfer),
+              "closure: the pose-acceleration term belongs to the chamfer and marker stages' hard-assignment closures");
+  if (pose_accel) {
+    UUO_REQUIRE(fit->lim_g && fit->pacc_tab, "closure: the pose-acceleration term was set without its buffer");
+    a.lim_g = fit->lim_g;
+  }
   // EXTENSION: the pose prior's per-(frame, joint) weights: k_prior_conf (launch_side_terms below) leaves the whole
   // weighted prior in the limit term's buffer, which the temporal instantiations add after their own pose prior -- that one runs
   // with a coefficient of 0 here, and so does the finalize's (its slot-2 sum is then 0).  With w_pose == 0 there is no prior to
@@ -2450,11 +2469,12 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
     a.cpose = 0.f;
     a.lim_g = fit->lim_g;
   }
-  // the forward kernels of the five terms above (side_terms.hip), for the routes below to launch once fit->frames is there
+  // the forward kernels of the six terms above (side_terms.hip), for the routes below to launch once fit->frames is there
   auto launch_side_terms = [&]() {
-    uuo_launch_side_terms(fit, s, F, src, prior ? d_x + lay.off_pose : nullptr, p->d_o_pose, p->w_pose, UuoSideTerms{floor, caps, limits, prior, kp});
+    uuo_launch_side_terms(fit, s, F, src, prior ? d_x + lay.off_pose : nullptr, p->d_o_pose, p->w_pose,
+                          UuoSideTerms{floor, caps, limits, prior, kp, pose_accel});
   };
-  const bool temporal = accel || lock || floor || caps || limits || prior || kp;
+  const bool temporal = accel || lock || floor || caps || limits || prior || kp || pose_accel;
   a.h.gx = F;
   a.h.gy = 1;
   FinArgs fa;

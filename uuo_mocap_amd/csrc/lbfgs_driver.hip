@@ -748,6 +748,8 @@ extern "C" int uuo_fit_destroy(uuo_fit_t* fit) {
   if (fit->lim_tab) (void)hipFree(fit->lim_tab);
   if (fit->lim_g) (void)hipFree(fit->lim_g);
   if (fit->lim_stream) (void)hipStreamDestroy(fit->lim_stream);
+  if (fit->pacc_tab) (void)hipFree(fit->pacc_tab);
+  if (fit->pacc_stream) (void)hipStreamDestroy(fit->pacc_stream);
   if (fit->surf_corners) (void)hipFree(fit->surf_corners);  // (surf_bary is the same allocation)
   if (fit->dbg_verts) (void)hipFree(fit->dbg_verts);
   if (fit->ev0) (void)hipEventDestroy(fit->ev0);

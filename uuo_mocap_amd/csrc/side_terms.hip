@@ -1,5 +1,5 @@
 // Forward kernels of the closures' side terms -- floor contact, bone-capsule self-penetration, 2D key-point reprojection,
-// joint-angle limits, the pose prior's per-(frame, joint) weights -- with the setters that configure them on a fit workspace.
+// joint-angle limits, pose acceleration, the pose prior's per-(frame, joint) weights -- with the setters that configure them on a fit workspace.
 // Each kernel leaves upstream gradients and per-frame loss shares for the backward kernels of the same evaluation (closure.hip:
 // the temporal instantiations of bwd_body); they share no device code with it but frame_math.h.  closure.hip reaches them
 // through uuo_launch_side_terms.
@@ -410,6 +410,94 @@ __global__ __launch_bounds__(64) void k_prior_conf(PriorConfArgs a) {
 }
 
 // ----------------------------------------------------------------------------------------------------
+// EXTENSION (not reference behaviour; uuo_fit_set_pose_accel): the pose-acceleration term on the local body rotations
+// (losses.pose_accel_loss).  Body joint j = 1 .. 23, R_t[j] its local rotation in frame t as k_limit_fwd forms it (gs6d_forward of
+// the raw entries when the stage normalises, the raw entries otherwise), u[23] >= 0 joint weights, F >= 3:
+//   a_t[j] = R_t[j] - 2 R_{t+1}[j] + R_{t+2}[j]                       t = 0 .. F-3
+//   loss += cl sum_t sum_j u[j] |a_t[j]|_F^2                           cl = w / ((F - 2) 207)
+//   dL/dR_s[j] = cg u[j] (a_s - 2 a_{s-1} + a_{s-2})                   cg = 2 w / ((F - 2) 207);  a_t outside 0 .. F-3 is 0
+// k_pose_accel delivers the gradients in PARAMETER space (gs6d_backward on the lane's own raw entries; third rows exact zeros
+// when the stage normalises) and the frames' shares -- frame t holds cl sum_j u[j] |a_t[j]|^2, frames F-2 and F-1 hold 0 --
+// through the buffer of the joint-angle limit term with the protocol of k_prior_conf: add == 0 writes the buffer, add != 0
+// (k_limit_fwd of this evaluation ran before it on the same stream) adds to it; k_prior_conf, when on, runs after it with add.
+// The shape of k_limit_fwd: 32 lanes per frame, two frames per 64-thread block; lane l < 23 of a half takes joint l + 1 of frame
+// s.  It loads the joint's raw entries of the five frames s-2 .. s+2, every index clamped to 0 .. F-1 and every load
+// unconditional (an idle lane loads a clamped row too), forms the five R and the three a_s, a_{s-1}, a_{s-2}, each SELECTED to
+// zero when its t is outside 0 .. F-3.  All loops are unrolled over constants: no private array is indexed dynamically, no
+// scratch.  A lane reads no row of the buffer but its own, and that one only with add; every active lane stores all nine entries
+// at every evaluation.  A joint weight of 0 leaves the lane's old entries as they are (exact +0 without add).  The frame's
+// share: every lane sums the nine squares of a_s in the order e = 0 .. 8 and weighs the sum by u, then a fixed xor butterfly
+// (16, 8, .. 1) inside the half adds the lanes (lanes 23 .. 31 hold zeros).  No atomics, no LDS: bit-reproducible.
+// ----------------------------------------------------------------------------------------------------
+struct PoseAccelArgs {
+  uuo_gptr<const float> body;  // [F][23][9] raw body pose entries (UuoPoseSrc.body)
+  uuo_gptr<const float> u;     // [23] joint weights
+  int F, norm_body, add;
+  float cl, cg;                // w / ((F - 2) 207), 2 w / ((F - 2) 207)
+  uuo_gptr<float> g;           // [F][23][9] gradients, then [F] shares: written (add == 0) or added to
+};
+__global__ __launch_bounds__(64) void k_pose_accel(PoseAccelArgs a) {
+  const int half = threadIdx.x >> 5, l = threadIdx.x & 31;
+  const int f = blockIdx.x * UUO_LIM_FPB + half;
+  const bool on = f < a.F && l < 23;
+  const int s = min(f, a.F - 1), jl = min(l, 22);  // (an idle lane computes on a clamped row and stores nothing)
+  const size_t row = ((size_t)s * 23 + jl) * 9;
+  float raw[5][9], R[5][9], old[9];
+#pragma unroll
+  for (int k = 0; k < 5; ++k) {
+    const size_t rk = ((size_t)min(max(s + k - 2, 0), a.F - 1) * 23 + jl) * 9;
+#pragma unroll
+    for (int e = 0; e < 9; ++e) raw[k][e] = a.body[rk + e];
+  }
+  const float u = a.u[jl];
+#pragma unroll
+  for (int e = 0; e < 9; ++e) old[e] = (on && a.add) ? a.g[row + e] : 0.f;
+  const bool head = l == 0 && f < a.F;
+  const float old_share = (head && a.add) ? a.g[(size_t)a.F * 207 + f] : 0.f;
+#pragma unroll
+  for (int k = 0; k < 5; ++k) {
+    if (a.norm_body) {
+      gs6d_forward(raw[k], R[k]);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 9; ++e) R[k][e] = raw[k][e];
+    }
+  }
+  const bool v0 = f <= a.F - 3, v1 = f >= 1 && f <= a.F - 2, v2 = f >= 2;  // a_s, a_{s-1}, a_{s-2} exist
+  const bool zero = u == 0.f;
+  const float wc = a.cg * u;
+  float dR[9], sq = 0.f;
+#pragma unroll
+  for (int e = 0; e < 9; ++e) {
+    const float a0 = v0 ? (R[2][e] - 2.f * R[3][e]) + R[4][e] : 0.f;
+    const float a1 = v1 ? (R[1][e] - 2.f * R[2][e]) + R[3][e] : 0.f;
+    const float a2 = v2 ? (R[0][e] - 2.f * R[1][e]) + R[2][e] : 0.f;
+    dR[e] = wc * ((a0 - 2.f * a1) + a2);
+    sq = fmaf(a0, a0, sq);
+  }
+  float out[9];
+  if (a.norm_body) {
+    float da[6];
+    gs6d_backward(raw[2], dR, da);
+#pragma unroll
+    for (int e = 0; e < 6; ++e) out[e] = zero ? old[e] : old[e] + da[e];
+    out[6] = old[6]; out[7] = old[7]; out[8] = old[8];
+  } else {
+#pragma unroll
+    for (int e = 0; e < 9; ++e) out[e] = zero ? old[e] : old[e] + dR[e];
+  }
+  if (on) {
+#pragma unroll
+    for (int e = 0; e < 9; ++e) a.g[row + e] = out[e];
+  }
+  // the frame's share: the lanes' weighted sums through a fixed butterfly inside the 32-lane half
+  float part = (on && v0 && !zero) ? u * sq : 0.f;
+#pragma unroll
+  for (int m = 16; m >= 1; m >>= 1) part += __shfl_xor(part, m, 64);
+  if (head) a.g[(size_t)a.F * 207 + f] = old_share + a.cl * part;
+}
+
+// ----------------------------------------------------------------------------------------------------
 // EXTENSION (not reference behaviour; uuo_fit_set_keypoints2d): a 2D key-point reprojection term on the 24 kinematic joints
 // J[t][j] = G_j^t + trans_t.  Frame t carries a pinhole camera in world axes, cam[t] = (A 3x3 row-major, b, fx, fy, cx, cy),
 // targets y[t][j] and confidences c[t][j] >= 0:
@@ -555,6 +643,21 @@ void uuo_launch_side_terms(uuo_fit* fit, hipStream_t s, int F, const UuoPoseSrc&
     fit->lim_launched = true;  // (uuo_fit_set_joint_limits waits for this stream before it replaces the table)
     fit->lim_last_stream = s;
   }
+  if (on.pose_accel) {  // (the caller has seen F >= 3)
+    PoseAccelArgs b;
+    std::memset(&b, 0, sizeof(b));
+    b.body = src.body;
+    b.u = fit->pacc_tab;
+    b.F = F;
+    b.norm_body = src.norm_body;
+    b.add = on.limits ? 1 : 0;
+    b.cl = (float)((double)fit->pacc_w / ((double)(F - 2) * 207.0));
+    b.cg = (float)(2.0 * (double)fit->pacc_w / ((double)(F - 2) * 207.0));
+    b.g = fit->lim_g;
+    hipLaunchKernelGGL(k_pose_accel, dim3((F + UUO_LIM_FPB - 1) / UUO_LIM_FPB), dim3(64), 0, s, b);
+    fit->pacc_launched = true;  // (uuo_fit_set_pose_accel waits for this stream before it replaces the table)
+    fit->pacc_last_stream = s;
+  }
   if (on.prior) {
     PriorConfArgs b;
     std::memset(&b, 0, sizeof(b));
@@ -562,7 +665,7 @@ void uuo_launch_side_terms(uuo_fit* fit, hipStream_t s, int F, const UuoPoseSrc&
     b.target = d_o_pose;
     b.w = fit->prior_w;
     b.F = F;
-    b.add = on.limits ? 1 : 0;
+    b.add = (on.limits || on.pose_accel) ? 1 : 0;
     b.cl = (float)((double)w_pose / ((double)F * 207.0));
     b.cg = (float)(2.0 * (double)w_pose / ((double)F * 207.0));
     b.g = fit->lim_g;
@@ -761,6 +864,44 @@ extern "C" int uuo_fit_set_joint_limits(uuo_fit_t* fit, float w, const float* h_
     fit->lim_have = true;
   }
   fit->lim_w = w;
+  return 0;
+}
+
+extern "C" int uuo_fit_set_pose_accel(uuo_fit_t* fit, float w, const float* h_joint_weights) {
+  UUO_REQUIRE(fit, "uuo_fit_set_pose_accel: null fit");
+  UUO_REQUIRE(w == 0.f || (w > 0.f && w <= 3.0e38f), "uuo_fit_set_pose_accel: the weight must be 0 (off) or a positive finite number");
+  if (w == 0.f) {  // off: nothing else is looked at (the table stays for the next call with the same weights)
+    fit->pacc_w = 0.f;
+    return 0;
+  }
+  UUO_REQUIRE(!uuo_recorder, "uuo_fit_set_pose_accel: lock-step batches do not carry the pose-acceleration term");
+  static thread_local float h_tab[23];
+  for (int i = 0; i < 23; ++i) {
+    const float v = h_joint_weights ? h_joint_weights[i] : 1.f;  // (null = ones)
+    UUO_REQUIRE(v >= 0.f && v <= 3.0e38f, "uuo_fit_set_pose_accel: a joint weight is NaN, negative or not finite");
+    h_tab[i] = v;
+  }
+  if (!fit->pacc_tab) {  // first use: the table and the upload stream
+    UUO_HIP_CHECK(hipMalloc((void**)&fit->pacc_tab, 23 * sizeof(float)));
+    fit->pacc_have = false;
+    UUO_HIP_CHECK(hipStreamCreateWithFlags(&fit->pacc_stream, hipStreamNonBlocking));
+  }
+  // (the buffer k_pose_accel fills is the joint-angle limit term's: [F][23][9] gradients, then [F] shares)
+  if (!fit->lim_g) UUO_HIP_CHECK(hipMalloc((void**)&fit->lim_g, ((size_t)fit->F * 207 + fit->F) * sizeof(float)));
+  const bool same = fit->pacc_have && std::memcmp(fit->pacc_h, h_tab, sizeof(h_tab)) == 0;
+  if (!same) {
+    fit->pacc_w = 0.f;
+    fit->pacc_have = false;
+    // the only reader of the old table is the last k_pose_accel launched on this workspace: wait for its stream alone (no
+    // device-wide wait), upload on the workspace's own non-blocking stream, and return once the copy has landed
+    if (fit->pacc_launched) UUO_HIP_CHECK(hipStreamSynchronize(fit->pacc_last_stream));
+    fit->pacc_launched = false;
+    UUO_HIP_CHECK(hipMemcpyAsync(fit->pacc_tab, h_tab, sizeof(h_tab), hipMemcpyHostToDevice, fit->pacc_stream));
+    UUO_HIP_CHECK(hipStreamSynchronize(fit->pacc_stream));
+    std::memcpy(fit->pacc_h, h_tab, sizeof(h_tab));
+    fit->pacc_have = true;
+  }
+  fit->pacc_w = w;
   return 0;
 }
 

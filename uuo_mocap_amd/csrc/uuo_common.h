@@ -242,6 +242,17 @@ struct uuo_fit {
   // prior -- gradients and shares -- in lim_g (added there when the joint-angle limit term is on too), and the backward and the
   // finalize run with a pose coefficient of 0.
   const float* prior_w = nullptr;
+  // EXTENSION: the pose-acceleration term on the local body rotations (uuo_fit_set_pose_accel; pacc_w == 0 = off): weight, the
+  // host copy of the joint weights (compared at the next call; pacc_have = it is valid), the workspace's own device table
+  // pacc_tab [23]; the last reader's stream and the upload stream as for the limit term's table.  k_pose_accel leaves its
+  // gradients and shares in lim_g (added there when the joint-angle limit term is on too).
+  float pacc_w = 0.f;
+  bool pacc_have = false;
+  float pacc_h[23];
+  float* pacc_tab = nullptr;
+  bool pacc_launched = false;
+  hipStream_t pacc_last_stream = nullptr;
+  hipStream_t pacc_stream = nullptr;
   // EXTENSION: the 2D key-point reprojection term on the 24 kinematic joints (uuo_fit_set_keypoints2d; kp_w == 0 = off): weight,
   // Geman-McClure sigma (0 = the square), the least depth of a valid pair, and the caller's device arrays -- cameras [F][16],
   // targets [F][24][2], confidences [F][24] -- read at every evaluation and not copied.  k_keypoint2d_fwd leaves its gradients and
@@ -326,13 +337,13 @@ int uuo_launch_bwd(const uuo_fit* fit, hipStream_t s, const uuo_problem_t& p, co
 int uuo_launch_finalize(const uuo_fit* fit, hipStream_t s, const uuo_problem_t& p, const float* x, float* grad,
                         float* loss);
 
-// the closures' side terms (side_terms.hip: k_floor_fwd, k_capsule_fwd, k_keypoint2d_fwd, k_limit_fwd, k_prior_conf and their setters).  One call
+// the closures' side terms (side_terms.hip: k_floor_fwd, k_capsule_fwd, k_keypoint2d_fwd, k_limit_fwd, k_pose_accel, k_prior_conf and their setters).  One call
 // per evaluation launches the forward kernels of the terms that are on, in that order on stream s, once fit->frames holds this
 // evaluation's FrameLds; src is the evaluation's pose source, d_pose / d_o_pose / w_pose the raw body pose, its prior target and
 // the prior's weight (the weighted prior only)
 #define UUO_FLOOR_MAXK 16  // sole points of the floor-contact term: fit->floor_up is [F][UUO_FLOOR_MAXK][3], then [F] loss shares
 struct UuoSideTerms {
-  bool floor, caps, limits, prior, kp;
+  bool floor, caps, limits, prior, kp, pose_accel;
 };
 void uuo_launch_side_terms(uuo_fit* fit, hipStream_t s, int F, const UuoPoseSrc& src, const float* d_pose, const float* d_o_pose,
                            float w_pose, UuoSideTerms on);

@@ -492,7 +492,7 @@ class _StageProblem:
         p.marker_distance = MARKER_DISTANCE
         self.problem = p
         self.n = int(self.lib.uuo_problem_num_params(byref(p)))
-        # EXTENSION: the terms' state (terms.TERMS: joint_accel, foot_lock, floor_*, cap_*, lim_*, prior_weights, kp_*), all off.  They
+        # EXTENSION: the terms' state (terms.TERMS: joint_accel, foot_lock, floor_*, cap_*, lim_*, prior_weights, kp_*, pacc_*), all off.  They
         # are settings of the WORKSPACE in the library: _arm() puts them there before every call that evaluates on it
         for term in terms.TERMS:
             vars(self).update(term.state)
@@ -509,6 +509,7 @@ class _StageProblem:
     joint_limits_on = property(lambda self: self.lim_w != 0.0)
     prior_conf_on = property(lambda self: self.prior_weights is not None)
     keypoints_on = property(lambda self: self.kp_w != 0.0)
+    pose_accel_on = property(lambda self: self.pacc_w != 0.0)
 
     def _set_terms(self, stage_terms, contacts, weights, smpl_inference):
         """EXTENSION: every term's state from its parsed record, the checked contact labels and prior weights and the armed
@@ -520,7 +521,7 @@ class _StageProblem:
     def _arm(self):
         """Sets this problem's terms (off without them), its surface term and its per-frame table on its workspace: one library
         call each, in the order they have always had (joint_accel, foot_lock, surface, per-frame table, floor, capsules, joint
-        limits, prior weights, key points).  The workspace is shared by every problem of the same (F, M) on this thread, so this runs right
+        limits, prior weights, key points, pose acceleration).  The workspace is shared by every problem of the same (F, M) on this thread, so this runs right
         before each library call that evaluates on it."""
         for term in _ARMED[:2]:
             term.arm(self)

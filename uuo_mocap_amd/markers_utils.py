@@ -28,7 +28,8 @@ LAST_STATS: Dict[str, list] = {}
 EXECUTION_DEFAULTS = {"subtree_lockstep": True, "subtree_batch": 256, "subtree_threads": 4,
                       "hypothesis_lockstep": False, "hypothesis_threads": 4, "batch_trivial_hypotheses": True,
                       "part_soft_fused": True, "chamfer_soft_fused": True, "marker_bary_fused": True,
-                      "robust_fused": True}
+                      "robust_fused": True,
+                      "pose_accel_fused": False}  # (opt-in: terms.POSE_ACCEL; the one switch that is off when absent)
 
 
 def merge_execution(config: Dict, execution: Dict = None) -> Dict:

@@ -445,6 +445,17 @@ def _set_keypoints(p, kp, contacts, weights, keypoints, smpl_inference):
     p.kp_w, p.kp_sigma, p.kp_min_depth = float(kp["w"]), float(kp["sigma"]), float(kp["min_depth"])
 
 
+def _set_pose_accel(p, pacc, contacts, weights, keypoints, smpl_inference):
+    """Keeps the weight and a contiguous HOST copy of the joint weights (None = ones), which the library checks and copies at the
+    call.  With weight 0 nothing is armed.  (A problem is built with a non-zero weight only under execution.pose_accel_fused:
+    StageTerms.check_problem.)"""
+    if float(pacc["w"]) == 0.0:
+        return
+    if pacc["joint_weights"] is not None:
+        p.pacc_u = np.ascontiguousarray(np.asarray(pacc["joint_weights"], dtype=np.float32).reshape(23))
+    p.pacc_w = float(pacc["w"])
+
+
 # ---------------------------------------------------------------- a term on the closures composed from the operators (`composed`)
 def _composed_joint_accel(w, losses, contacts, smpl_inference, keypoints=None):
     from .losses import joint_accel_loss
@@ -531,7 +542,7 @@ class Term:
     label: str = None          # how the refusals spell the keys
     stages: Tuple[str, ...] = ("chamfer", "marker")
     switch: str = None         # the `execution.*` key that, set False, sends the term to the composed closure (None: one route only)
-    fused: bool = True         # False: no fused closure, the term always runs composed
+    opt_in: bool = False       # True: the switch is False when absent -- the term runs composed unless the config asks for the fused closure
     batch: bool = False        # True: a lock-step batch carries the term (on its fused closure)
     # the term on a stage problem: the attribute (dotted path) that is non-zero when the problem carries it, the attributes it
     # keeps with their off values, set(problem, record, contacts, weights, keypoints, smpl_inference) at construction -- the
@@ -642,9 +653,13 @@ KEYPOINTS = Term(
     sharded="stages.%s.losses.keypoints_2d (extension): the key-point reprojection term is not built for " + _SHARDING,
     soft=_SOFT % "key-point reprojection term (keypoints_2d)", composed=_composed_keypoints)
 POSE_ACCEL = Term(
-    "the pose-acceleration term", stage_pose_accel, lambda r: r["w"] > 0.0, keys=("pose_accel",), fused=False,
-    sharded=_COUPLES % "pose_accel", sharded_by_route=True,
-    no_closure="stages.%s.losses.pose_accel (extension) has no fused closure: %s composes it from the operators",
+    "the pose-acceleration term", stage_pose_accel, lambda r: r["w"] > 0.0, keys=("pose_accel",), switch="pose_accel_fused",
+    opt_in=True, flag="pose_accel_on", state={"pacc_w": 0.0, "pacc_u": None},  # the HOST table: [23] float32 numpy, None = ones
+    set=_set_pose_accel, setter="uuo_fit_set_pose_accel", off_args=(c_float(0.0), None),
+    on_args=lambda p: (c_float(p.pacc_w), p.pacc_u.ctypes.data if p.pacc_u is not None else None),
+    sharded=_COUPLES % "pose_accel", sharded_by_route=True, soft=_SOFT % "pose-acceleration term (pose_accel)",
+    no_closure="stages.%s.losses.pose_accel (extension) has no fused closure without execution.pose_accel_fused: True; %s "
+               "composes it from the operators",
     composed=_composed_pose_accel)
 
 #: one row per extension term.  The order is that of the library calls in _StageProblem._arm, of the refusals of
@@ -711,15 +726,13 @@ class StageTerms:
             return self.keypoints is not None
         return self.prior_weights is not None if term is PRIOR else self.on(term)
 
-    def execution(self, switch: str) -> bool:
-        return bool((self.config.get("execution") or {}).get(switch, True))
+    def execution(self, switch: str, default: bool = True) -> bool:
+        return bool((self.config.get("execution") or {}).get(switch, default))
 
     def fused(self, term: Term) -> bool:
-        """False when the term is to run on the closure composed from the operators: it has no fused closure, or its switch
-        is False (the fused closures' checker).  True when it is not active: nothing to compose without the term."""
-        if not term.fused:
-            return not self.on(term)
-        return term.switch is None or not self.active(term) or self.execution(term.switch)
+        """False when the term is to run on the closure composed from the operators: its switch is False (the fused closures'
+        checker), or absent for a term that is opt-in.  True when it is not active: nothing to compose without the term."""
+        return term.switch is None or not self.active(term) or self.execution(term.switch, not term.opt_in)
 
     def composed_tail(self, losses: Dict, contacts, smpl_inference):
         """The terms that the composed closures add after the reference's, as (input, function) pairs in TERMS' order."""
@@ -745,7 +758,7 @@ class StageTerms:
         """A stage problem's constructor: every term parsed (its ValueError before the device is touched), and refused where
         the fused closure -- with `soft`, the soft-assignment one -- cannot carry it."""
         for t in PROBLEM_ORDER:
-            if self.on(t) and not t.fused:
+            if self.on(t) and t.no_closure and not self.fused(t):  # (opt-in: the problem has the closure only when asked for)
                 raise NotImplementedError(t.no_closure % (self.stage, {"chamfer": "optim_chamfer", "marker": "optim_markers"}[self.stage]))
             if self.on(t) and soft:
                 raise NotImplementedError(t.soft)
@@ -780,7 +793,8 @@ def stage_route(terms: StageTerms, on_device: bool, sharded: bool, shared_betas:
     composed = lambda: any(not terms.fused(t) for t in TERMS if stage in t.stages)
     if stage == "chamfer":
         soft = float(st["losses"].get(SOFT_KEY, 0.0)) != 0.0 and on_device and terms.execution("chamfer_soft_fused")
-        if soft and any(terms.active(t) for t in TERMS if t.soft):
+        # (an opt-in term counts here only on its fused closure: without its switch it is not even parsed at this point, as before)
+        if soft and any(terms.active(t) for t in TERMS if t.soft and (not t.opt_in or terms.execution(t.switch, False))):
             soft = False  # no instantiation of the dense backward (k_bwd_dense) carries these: composed closure, no refusal
         w_surface, _ = stage_surface(config)
         if w_surface > 0.0 and sharded:
@@ -797,7 +811,7 @@ def stage_route(terms: StageTerms, on_device: bool, sharded: bool, shared_betas:
             if soft:
                 raise NotImplementedError("stages.chamfer.losses.soft_chamfer (extension) is not built for " + _SHARDING +
                                           "; set execution.chamfer_soft_fused: False or use another mode")
-            terms.refuse_sharded((PRIOR,))
+            terms.refuse_sharded((PRIOR, POSE_ACCEL))
             return "sharded"
         return "fused"
     if placement == "frame_table":  # fused one-hot closure only
@@ -821,10 +835,10 @@ def stage_route(terms: StageTerms, on_device: bool, sharded: bool, shared_betas:
     # and nothing else; execution.marker_bary_fused: False, more non-zeros in a row, or frame-block sharding keep it composed
     if placement != "one_hot" and not (on_device and placement == "three" and not sharded and terms.execution("marker_bary_fused")):
         if sharded:
-            terms.refuse_sharded((PRIOR,))
+            terms.refuse_sharded((PRIOR, POSE_ACCEL))
         return "composed"
     if sharded:
-        terms.refuse_sharded((PRIOR,))
+        terms.refuse_sharded((PRIOR, POSE_ACCEL))
         return "sharded"
     return "fused"
 

@@ -62,9 +62,9 @@ class _Case:
     """One (F, seed): the inputs, and per stage a maker of problems and the packed evaluation point with body pose `pose`
     (default: the perturbed pose of _inputs)."""
 
-    def __init__(self, smpl, tables, dev, F, seed):
+    def __init__(self, smpl, tables, dev, F, seed, num_markers=M):
         self.F, self.seed, self.smpl, self.dev = F, seed, smpl, dev
-        seq, self.markers, self.o_pose, self.o_betas, self.root, self.trans, self.pert = _inputs(tables, F, seed, num_markers=M)
+        seq, self.markers, self.o_pose, self.o_betas, self.root, self.trans, self.pert = _inputs(tables, F, seed, num_markers=num_markers)
         self.vids = torch.from_numpy(np.asarray(seq.gt["marker_vids"])).to(torch.int32)
         self.contacts = _contacts(F, seed)
         self.svids = _vids(tables, 6)
@@ -234,6 +234,76 @@ def test_the_buffer_shared_with_the_limit_term_and_the_weighted_prior(smpl, smpl
         rows = lambda v: case.raw(stage, v)[:, 3]      # U_TABLE[3] == 0: SMPL joint 4
         assert torch.equal(rows(grad), rows(grad0)), stage
         assert not torch.equal(case.raw(stage, grad)[:, 9], case.raw(stage, grad0)[:, 9]), stage
+
+
+def test_the_add_chains_of_both_shared_buffers_for_every_subset(smpl, smpl64, tables, dev):
+    """The first kernel of an evaluation to reach a shared buffer writes it and the later ones add: lim_g takes k_limit_fwd,
+    k_pose_accel and k_prior_conf, cap_up takes k_capsule_fwd and k_keypoint2d_fwd.  Marker stage, F = 5 (odd: the last 64-thread
+    block has an idle half; the smallest F with an interior frame of k_pose_accel's five-frame stencil), M = 12.  Every one of the
+    8 subsets of {limits, pose acceleration, weighted prior} crossed with the 4 of {capsules, key points} is evaluated on ONE
+    workspace, one after another, in an order in which the last evaluation that wrote a buffer left it with another subset's
+    contents (asserted), and on a fresh thread's workspace that has only ever seen that subset.  Loss and gradient are bitwise
+    equal between the two workspaces and on a repeated evaluation: a kernel that adds where no earlier writer ran picks up the
+    previous subset's contents, one that writes where it should add loses a term -- and the 32 losses are all different."""
+    from keypoints2d_ref64 import evidence
+    from test_gpu_capsules import _block as _cap_block, _joints64, _lists as _cap_lists, _preconditions as _caps_preconditions
+    from test_gpu_joint_limits import W_CAPS_M
+    from uuo_mocap_amd.engine import set_workspace_slot
+
+    F, markers, seed = 5, 12, 5120
+    case = _Case(smpl, tables, dev, F, seed, num_markers=markers)
+    lim_tab, cap_list, wtab = _lim_tables()["full"], _cap_lists(tables)["builder"], _weight_tables(F, seed)["hash"]
+    joints = _joints64(smpl64, tables, F, markers, seed)[1]
+    # every term is active at the evaluated point (host-side, float64)
+    _lim_preconditions(case.pert[3], lim_tab[0], lim_tab[1], 1)
+    _caps_preconditions(joints, cap_list, 1)
+    rec = {k: v.float() for k, v in evidence(joints, seed).items()}
+
+    def problem(limits, pose_accel, prior, caps, kp):
+        cfg = _cfg(W_C if pose_accel else None, W_M if pose_accel else None, U_TABLE, limits=lim_tab if limits else None,
+                   reg=(R_CHAMFER, R_MARKER))
+        for stage in ("chamfer", "marker"):
+            st = cfg["stages"][stage]
+            if caps:
+                st["losses"]["self_penetration"] = W_CAPS_M
+                st["capsules"] = _cap_block(cap_list)
+            if kp:
+                st["losses"]["keypoints_2d"] = 0.02    # test_gpu_keypoints2d's weight, sigma and least depth
+                st["keypoints_2d"] = {"sigma": 8.0, "min_depth": 0.1, "joint_weights": None}
+        p = case.make("marker", cfg, prior_weights=wtab if prior else None, keypoints_2d=rec if kp else None)
+        assert (p.joint_limits_on, p.pose_accel_on, p.prior_conf_on, p.capsules_on, p.keypoints_on) == \
+            (limits, pose_accel, prior, caps, kp)
+        return p
+
+    flags = lambda lim, cap: (bool(lim & 1), bool(lim & 2), bool(lim & 4), bool(cap & 1), bool(cap & 2))
+    lim_order, cap_order = (7, 1, 6, 2, 5, 3, 4, 0), (3, 1, 2, 0)
+    order = [(lim_order[k % 8], cap_order[(k % 8 + k // 8) % 4]) for k in range(32)]
+    assert len(set(order)) == 32
+    x = case.x("marker", problem(*flags(0, 0)))
+    shared, fresh = {}, {}
+    left = [0, 0]    # the subsets whose contents lim_g and cap_up hold
+    for lim, cap in order:
+        assert (lim == 0 or lim != left[0]) and (cap == 0 or cap != left[1]), (lim, cap, left)
+        left = [lim or left[0], cap or left[1]]
+        p = problem(*flags(lim, cap))
+        l1, g1, _ = p.evaluate(x, want_nn=False)
+        l2, g2, _ = p.evaluate(x, want_nn=False)
+        assert l1 == l2 and torch.equal(g1, g2), (lim, cap)
+        shared[lim, cap] = (l1, g1)
+
+    def on_fresh_workspace(k, lim, cap):
+        set_workspace_slot(24 + k)
+        fresh[lim, cap] = problem(*flags(lim, cap)).evaluate(x, want_nn=False)[:2]
+        torch.cuda.synchronize()
+
+    for k, (lim, cap) in enumerate(order):
+        t = threading.Thread(target=on_fresh_workspace, args=(k, lim, cap))
+        t.start()
+        t.join()
+    for key in order:
+        assert key in fresh, key
+        assert fresh[key][0] == shared[key][0] and torch.equal(fresh[key][1], shared[key][1]), key
+    assert len({loss for loss, _ in shared.values()}) == 32
 
 
 # ------------------------------------------------------------------------------------------------ 4. off is off

@@ -184,6 +184,7 @@ _DEBUG_SIGNATURES = {
     "uuo_debug_index_map": (c_int, [c_int, c_int, c_int, c_void_p]),
     "uuo_debug_problem_index_map": (c_int, [POINTER(UuoProblem), c_int, c_void_p]),
     "uuo_debug_bwd_select": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),  # facts -> backward kernel (tests/test_bwd_select.py)
+    "uuo_debug_term_refusal": (c_int, [c_int, c_int]),  # side term x situation -> validation's answer (tests/test_term_refusals.py)
     "uuo_debug_last_solve_n": (c_int, [c_void_p]),  # coordinates of the workspace's last stage solve (which packing it took)
     "uuo_debug_staging_script": (c_int, [c_void_p, c_int, ctypes.c_longlong, c_void_p]),
     # step-wise replay of the L-BFGS history kernels (tests/test_gpu_lbfgs_history.py)

@@ -1852,6 +1852,85 @@ extern "C" int uuo_problem_num_params(const uuo_problem_t* p) {
   return problem_layout(p).n;
 }
 
+// EXTENSION: the side terms of a workspace (side_terms.hip), one row each, in the order of UuoSideTerms: how a refusal names
+// the term, whether it is set, the least F at which it has anything to evaluate, and its flag in UuoSideTerms.  They are built
+// for the chamfer and marker stages' hard-assignment closures outside lock-step batches; side_terms_check refuses the rest.
+struct SideTermRow {
+  const char *subject, *verb, *setter;
+  bool (*set)(const uuo_fit*);
+  int min_frames;
+  bool UuoSideTerms::*on;
+};
+static const SideTermRow side_term_rows[] = {
+    {"the joint-acceleration term", "is", "uuo_fit_set_joint_accel", [](const uuo_fit* f) { return f->joint_accel != 0.f; }, 3, &UuoSideTerms::accel},
+    {"the foot-lock term", "is", "uuo_fit_set_foot_lock", [](const uuo_fit* f) { return f->foot_lock != 0.f; }, 2, &UuoSideTerms::lock},
+    {"the floor-contact term", "is", "uuo_fit_set_floor", [](const uuo_fit* f) { return f->floor_k != 0; }, 1, &UuoSideTerms::floor},
+    {"the self-penetration term", "is", "uuo_fit_set_capsules", [](const uuo_fit* f) { return f->cap_w != 0.f; }, 1, &UuoSideTerms::caps},
+    {"the key-point reprojection term", "is", "uuo_fit_set_keypoints2d", [](const uuo_fit* f) { return f->kp_w != 0.f; }, 1, &UuoSideTerms::kp},
+    {"the joint-angle limit term", "is", "uuo_fit_set_joint_limits", [](const uuo_fit* f) { return f->lim_w != 0.f; }, 1, &UuoSideTerms::limits},
+    {"the pose-acceleration term", "is", "uuo_fit_set_pose_accel", [](const uuo_fit* f) { return f->pacc_w != 0.f; }, 3, &UuoSideTerms::pose_accel},
+    {"the pose prior's weights", "are", "uuo_fit_set_prior_weights", [](const uuo_fit* f) { return f->prior_w != nullptr; }, 1, &UuoSideTerms::prior},
+};
+
+// the terms this evaluation runs: set, and with enough frames; the weighted prior also needs a prior to weigh
+static UuoSideTerms side_terms_on(const uuo_fit* fit, const uuo_problem_t* p) {
+  UuoSideTerms on{};
+  for (const SideTermRow& r : side_term_rows) on.*(r.on) = r.set(fit) && p->F >= r.min_frames;
+  on.prior = on.prior && (p->stage == UUO_STAGE_CHAMFER || p->stage == UUO_STAGE_MARKER) && p->w_pose != 0.f;
+  return on;
+}
+
+// Every refusal of a set side term, for validate_problem and again for each evaluation: a lock-step batch validates its
+// problems before it starts recording, so the evaluation's call is the one that sees uuo_recorder.  The passing path tests eight
+// predicates and builds no string.
+static int side_terms_check(const uuo_fit* fit, const uuo_problem_t* p) {
+  for (const SideTermRow& r : side_term_rows) {
+    if (!r.set(fit)) continue;
+    const char* not_built = p->stage == UUO_STAGE_PART ? "the part stage"
+                            : p->w_soft != 0.f         ? "the soft-assignment data term (w_soft)"
+                                                       : nullptr;
+    if (!not_built && !uuo_recorder) continue;
+    const std::string named = std::string(r.subject) + " (" + r.setter + ", extension)";
+    uuo_set_error(not_built ? "closure: " + named + " " + r.verb + " not built for " + not_built
+                            : "closure: lock-step batches do not carry " + named);
+    return -22;
+  }
+  UUO_REQUIRE(fit->floor_k == 0 || !fit->frame_assign, "closure: the floor-contact term (uuo_fit_set_floor, extension) is not built for the "
+              "per-frame vertex table (uuo_fit_set_frame_assign)");
+  const UuoSideTerms on = side_terms_on(fit, p);
+  UUO_REQUIRE(!on.pose_accel || (fit->lim_g && fit->pacc_tab.dev), "closure: the pose-acceleration term was set without its buffer");
+  UUO_REQUIRE(!on.prior || fit->lim_g, "closure: the pose prior's weights were set without their buffer");
+  return 0;
+}
+
+// Arms the backward's and the finalize's arguments for the terms that are on (a and fa hold the plain closure's values) and
+// returns them, for uuo_launch_side_terms to run their forward kernels once fit->frames is there.  accel and lock run inside
+// the temporal instantiations of the backward; the others reach them as upstream gradients and per-frame loss shares: the
+// floor's K sole points as items M .. M + K - 1, the capsules' and key points' d loss / d G_j^t in cap_up (added to uj and
+// slot 3), the limits', the pose acceleration's and the weighted prior's parameter-space gradients in lim_g (added to gout
+// and slot 3).  The weighted prior replaces the plain one: k_prior_conf leaves the whole of it in lim_g, and the backward's
+// and the finalize's own run with a coefficient of 0 (the finalize's slot-2 sum is then 0; uuo_stage_compactable looks at the
+// problem's w_pose, not at these coefficients).
+static UuoSideTerms arm_side_terms(const uuo_fit* fit, const uuo_problem_t* p, int F, BwdArgs& a, FinArgs& fa) {
+  const UuoSideTerms on = side_terms_on(fit, p);
+  a.acc_w = on.accel ? (float)((double)fit->joint_accel / ((double)(F - 2) * 72.0)) : 0.f;
+  a.lock_w = on.lock ? (float)((double)fit->foot_lock / ((double)(F - 1) * 6.0)) : 0.f;
+  a.contacts = on.lock ? fit->foot_contacts : nullptr;
+  if (on.floor) {
+    a.floor_k = fit->floor_k;
+    a.floor_vids = fit->floor_vids;
+    a.floor_up = fit->floor_up;
+    a.floor_loss = uuo_floor_up_shares(fit);
+  }
+  if (on.caps || on.kp) a.cap_up = fit->cap_up;
+  if (on.limits || on.pose_accel || on.prior) a.lim_g = fit->lim_g;
+  if (on.prior) {
+    a.cpose = 0.f;
+    fa.cpose = 0.0;
+  }
+  return on;
+}
+
 static int validate_problem(const uuo_fit* fit, const uuo_problem_t* p) {
   UUO_REQUIRE(fit && p, "closure: null fit/problem");
   UUO_REQUIRE(p->stage >= 0 && p->stage <= 2, "closure: unknown stage");
@@ -1873,67 +1952,7 @@ static int validate_problem(const uuo_fit* fit, const uuo_problem_t* p) {
                 "whose square is a normal fp32 value");
     UUO_REQUIRE(sg == 0.f || p->w_soft == 0.f, "closure: robust_sigma is not built for the soft-assignment data term (w_soft)");
   }
-  // EXTENSION: the joint-acceleration term of the workspace (uuo_fit_set_joint_accel) is built for the fitted stages' sparse
-  // closures only
-  UUO_REQUIRE(fit->joint_accel == 0.f || p->stage != UUO_STAGE_PART,
-              "closure: the joint-acceleration term (uuo_fit_set_joint_accel, extension) is not built for the part stage");
-  UUO_REQUIRE(fit->joint_accel == 0.f || p->w_soft == 0.f,
-              "closure: the joint-acceleration term (uuo_fit_set_joint_accel, extension) is not built for the soft-assignment "
-              "data term (w_soft)");
-  // EXTENSION: the foot-lock term of the workspace (uuo_fit_set_foot_lock) likewise
-  UUO_REQUIRE(fit->foot_lock == 0.f || p->stage != UUO_STAGE_PART,
-              "closure: the foot-lock term (uuo_fit_set_foot_lock, extension) is not built for the part stage");
-  UUO_REQUIRE(fit->foot_lock == 0.f || p->w_soft == 0.f,
-              "closure: the foot-lock term (uuo_fit_set_foot_lock, extension) is not built for the soft-assignment data term "
-              "(w_soft)");
-  // EXTENSION: the floor-contact term of the workspace (uuo_fit_set_floor) likewise
-  UUO_REQUIRE(fit->floor_k == 0 || p->stage != UUO_STAGE_PART,
-              "closure: the floor-contact term (uuo_fit_set_floor, extension) is not built for the part stage");
-  UUO_REQUIRE(fit->floor_k == 0 || p->w_soft == 0.f,
-              "closure: the floor-contact term (uuo_fit_set_floor, extension) is not built for the soft-assignment data term "
-              "(w_soft)");
-  UUO_REQUIRE(fit->floor_k == 0 || !uuo_recorder,
-              "closure: lock-step batches do not carry the floor-contact term (uuo_fit_set_floor, extension)");
-  // EXTENSION: the self-penetration term of the workspace (uuo_fit_set_capsules) likewise
-  UUO_REQUIRE(fit->cap_w == 0.f || p->stage != UUO_STAGE_PART,
-              "closure: the self-penetration term (uuo_fit_set_capsules, extension) is not built for the part stage");
-  UUO_REQUIRE(fit->cap_w == 0.f || p->w_soft == 0.f,
-              "closure: the self-penetration term (uuo_fit_set_capsules, extension) is not built for the soft-assignment data "
-              "term (w_soft)");
-  UUO_REQUIRE(fit->cap_w == 0.f || !uuo_recorder,
-              "closure: lock-step batches do not carry the self-penetration term (uuo_fit_set_capsules, extension)");
-  // EXTENSION: the key-point reprojection term of the workspace (uuo_fit_set_keypoints2d) likewise
-  UUO_REQUIRE(fit->kp_w == 0.f || p->stage != UUO_STAGE_PART,
-              "closure: the key-point reprojection term (uuo_fit_set_keypoints2d, extension) is not built for the part stage");
-  UUO_REQUIRE(fit->kp_w == 0.f || p->w_soft == 0.f,
-              "closure: the key-point reprojection term (uuo_fit_set_keypoints2d, extension) is not built for the soft-assignment "
-              "data term (w_soft)");
-  UUO_REQUIRE(fit->kp_w == 0.f || !uuo_recorder,
-              "closure: lock-step batches do not carry the key-point reprojection term (uuo_fit_set_keypoints2d, extension)");
-  // EXTENSION: the joint-angle limit term of the workspace (uuo_fit_set_joint_limits) likewise
-  UUO_REQUIRE(fit->lim_w == 0.f || p->stage != UUO_STAGE_PART,
-              "closure: the joint-angle limit term (uuo_fit_set_joint_limits, extension) is not built for the part stage");
-  UUO_REQUIRE(fit->lim_w == 0.f || p->w_soft == 0.f,
-              "closure: the joint-angle limit term (uuo_fit_set_joint_limits, extension) is not built for the soft-assignment data "
-              "term (w_soft)");
-  UUO_REQUIRE(fit->lim_w == 0.f || !uuo_recorder,
-              "closure: lock-step batches do not carry the joint-angle limit term (uuo_fit_set_joint_limits, extension)");
-  // EXTENSION: the pose-acceleration term of the workspace (uuo_fit_set_pose_accel) likewise
-  UUO_REQUIRE(fit->pacc_w == 0.f || p->stage != UUO_STAGE_PART,
-              "closure: the pose-acceleration term (uuo_fit_set_pose_accel, extension) is not built for the part stage");
-  UUO_REQUIRE(fit->pacc_w == 0.f || p->w_soft == 0.f,
-              "closure: the pose-acceleration term (uuo_fit_set_pose_accel, extension) is not built for the soft-assignment data "
-              "term (w_soft)");
-  UUO_REQUIRE(fit->pacc_w == 0.f || !uuo_recorder,
-              "closure: lock-step batches do not carry the pose-acceleration term (uuo_fit_set_pose_accel, extension)");
-  // EXTENSION: the pose prior's per-(frame, joint) weights of the workspace (uuo_fit_set_prior_weights) likewise
-  UUO_REQUIRE(!fit->prior_w || p->stage != UUO_STAGE_PART,
-              "closure: the pose prior's weights (uuo_fit_set_prior_weights, extension) are not built for the part stage");
-  UUO_REQUIRE(!fit->prior_w || p->w_soft == 0.f,
-              "closure: the pose prior's weights (uuo_fit_set_prior_weights, extension) are not built for the soft-assignment data "
-              "term (w_soft)");
-  UUO_REQUIRE(!fit->prior_w || !uuo_recorder,
-              "closure: lock-step batches do not carry the pose prior's weights (uuo_fit_set_prior_weights, extension)");
+  if (const int rc = side_terms_check(fit, p)) return rc;  // EXTENSION: the side terms of the workspace
   // EXTENSION: latent marker offsets
   UUO_REQUIRE(p->w_offsets == 0.f || (p->w_offsets > 0.f && p->w_offsets <= 3.0e38f),
               "closure: w_offsets (latent marker offsets, extension) must be 0 (off) or a positive finite weight");
@@ -1988,14 +2007,6 @@ extern "C" int uuo_fit_surface_corners(uuo_fit_t* fit, void* stream, int32_t* d_
   const size_t n = (size_t)fit->F * fit->M * 3;
   if (d_corners) UUO_HIP_CHECK(hipMemcpyAsync(d_corners, fit->surf_corners, n * sizeof(int32_t), hipMemcpyDeviceToDevice, (hipStream_t)stream));
   if (d_bary) UUO_HIP_CHECK(hipMemcpyAsync(d_bary, fit->surf_bary, n * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-  return 0;
-}
-
-extern "C" int uuo_fit_set_joint_accel(uuo_fit_t* fit, float w) {
-  UUO_REQUIRE(fit, "uuo_fit_set_joint_accel: null fit");
-  UUO_REQUIRE(w == 0.f || (w > 0.f && w <= 3.0e38f), "uuo_fit_set_joint_accel: the weight must be 0 (off) or a positive finite number");
-  UUO_REQUIRE(w == 0.f || !uuo_recorder, "uuo_fit_set_joint_accel: lock-step batches do not carry the joint-acceleration term");
-  fit->joint_accel = w;
   return 0;
 }
 
@@ -2332,7 +2343,8 @@ UuoIndexMap uuo_stage_index_map(const uuo_problem_t* p, bool compact) {
 int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, const float* d_x, float* d_loss,
                           float* d_grad, int32_t* d_nn_idx, const float* d_dir, double* d_stats,
                           const UuoEvalReport* report, bool compact) {
-  int rc = 0;
+  int rc = side_terms_check(fit, p);
+  if (rc) return rc;
   const uuo_model* m = fit->model;
   const int F = p->F, M = p->M;
   const StageLayout lay = problem_layout(p);            // the parameters: always the reference's packing
@@ -2407,74 +2419,6 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
   a.stop = bwd_stop;
   a.dir = d_dir;
   a.off_pose = gl.off_pose; a.off_root = gl.off_root; a.off_z = gl.off_z; a.off_trans = gl.off_trans;
-  // EXTENSION: the joint-acceleration term runs on the *_t instantiations; with fewer than three frames it has no terms
-  const bool accel = fit->joint_accel != 0.f && F >= 3;
-  UUO_REQUIRE(!accel || !uuo_recorder, "closure: lock-step batches do not carry the joint-acceleration term");
-  a.acc_w = accel ? (float)((double)fit->joint_accel / ((double)(F - 2) * 72.0)) : 0.f;
-  // EXTENSION: the foot-lock term rides on the same instantiations (either coefficient may be 0 there); F < 2: no terms
-  const bool lock = fit->foot_lock != 0.f && F >= 2;
-  UUO_REQUIRE(!lock || !uuo_recorder, "closure: lock-step batches do not carry the foot-lock term");
-  a.lock_w = lock ? (float)((double)fit->foot_lock / ((double)(F - 1) * 6.0)) : 0.f;
-  a.contacts = lock ? fit->foot_contacts : nullptr;
-  // EXTENSION: the floor-contact term rides on them too: its K sole points are items M .. M + K - 1 of the backward, with the
-  // upstream gradients k_floor_fwd leaves (launch_side_terms below, once the frames' FrameLds are there)
-  const bool floor = fit->floor_k != 0;
-  UUO_REQUIRE(!floor || !uuo_recorder, "closure: lock-step batches do not carry the floor-contact term");
-  UUO_REQUIRE(!floor || !fit->frame_assign, "closure: the floor-contact term (uuo_fit_set_floor, extension) is not built for the "
-              "per-frame vertex table (uuo_fit_set_frame_assign)");
-  if (floor) {
-    a.floor_k = fit->floor_k;
-    a.floor_vids = fit->floor_vids;
-    a.floor_up = fit->floor_up;
-    a.floor_loss = fit->floor_up + (size_t)F * UUO_FLOOR_MAXK * 3;
-  }
-  // EXTENSION: the self-penetration term: k_capsule_fwd (launch_side_terms below) leaves d loss / d G_j^t and the
-  // frames' shares, the temporal instantiations add them to uj and slot 3 (cap_up != null).  Frames are not coupled: any F.
-  const bool caps = fit->cap_w != 0.f;
-  UUO_REQUIRE(!caps || !uuo_recorder, "closure: lock-step batches do not carry the self-penetration term");
-  // EXTENSION: the key-point reprojection term: k_keypoint2d_fwd (launch_side_terms below, after k_capsule_fwd) leaves -- or, with
-  // the capsules on, adds -- its d loss / d G_j^t and the frames' shares in the same buffer.  Frames are not coupled: any F.
-  const bool kp = fit->kp_w != 0.f;
-  UUO_REQUIRE(!kp || !uuo_recorder, "closure: lock-step batches do not carry the key-point reprojection term");
-  UUO_REQUIRE(!kp || (p->stage != UUO_STAGE_PART && !soft_chamfer),
-              "closure: the key-point reprojection term belongs to the chamfer and marker stages' hard-assignment closures");
-  if (caps || kp) a.cap_up = fit->cap_up;  // ([F][72] gradients, then the [F] shares)
-  // EXTENSION: the joint-angle limit term: k_limit_fwd (launch_side_terms below) leaves the parameter-space
-  // gradients and the frames' shares, the temporal instantiations add them to gout and slot 3 (lim_g != null).  Any F.
-  const bool limits = fit->lim_w != 0.f;
-  UUO_REQUIRE(!limits || !uuo_recorder, "closure: lock-step batches do not carry the joint-angle limit term");
-  UUO_REQUIRE(!limits || (p->stage != UUO_STAGE_PART && !soft_chamfer),
-              "closure: the joint-angle limit term belongs to the chamfer and marker stages' hard-assignment closures");
-  if (limits) a.lim_g = fit->lim_g;  // ([F][207] gradients, then the [F] shares)
-  // EXTENSION: the pose-acceleration term: k_pose_accel (launch_side_terms below, after k_limit_fwd) leaves -- or, with the limit
-  // term on, adds -- its parameter-space gradients and the frames' shares in the same buffer.  With fewer than three frames it has
-  // no terms: no kernel runs, and the evaluation is that of a workspace without the setting.
-  const bool pose_accel = fit->pacc_w != 0.f && F >= 3;
-  UUO_REQUIRE(!pose_accel || !uuo_recorder, "closure: lock-step batches do not carry the pose-acceleration term");
-  UUO_REQUIRE(!pose_accel || (p->stage != UUO_STAGE_PART && !soft_chamfer),
-              "closure: the pose-acceleration term belongs to the chamfer and marker stages' hard-assignment closures");
-  if (pose_accel) {
-    UUO_REQUIRE(fit->lim_g && fit->pacc_tab, "closure: the pose-acceleration term was set without its buffer");
-    a.lim_g = fit->lim_g;
-  }
-  // EXTENSION: the pose prior's per-(frame, joint) weights: k_prior_conf (launch_side_terms below) leaves the whole
-  // weighted prior in the limit term's buffer, which the temporal instantiations add after their own pose prior -- that one runs
-  // with a coefficient of 0 here, and so does the finalize's (its slot-2 sum is then 0).  With w_pose == 0 there is no prior to
-  // weigh: the setting changes nothing.  (uuo_stage_compactable looks at the problem's w_pose, not at these coefficients.)
-  const bool prior = fit->prior_w != nullptr && (p->stage == UUO_STAGE_CHAMFER || p->stage == UUO_STAGE_MARKER) && p->w_pose != 0.f;
-  UUO_REQUIRE(!prior || (!uuo_recorder && !soft_chamfer),
-              "closure: the pose prior's weights belong to the chamfer and marker stages' hard-assignment closures");
-  if (prior) {
-    UUO_REQUIRE(fit->lim_g, "closure: the pose prior's weights were set without their buffer");
-    a.cpose = 0.f;
-    a.lim_g = fit->lim_g;
-  }
-  // the forward kernels of the six terms above (side_terms.hip), for the routes below to launch once fit->frames is there
-  auto launch_side_terms = [&]() {
-    uuo_launch_side_terms(fit, s, F, src, prior ? d_x + lay.off_pose : nullptr, p->d_o_pose, p->w_pose,
-                          UuoSideTerms{floor, caps, limits, prior, kp, pose_accel});
-  };
-  const bool temporal = accel || lock || floor || caps || limits || prior || kp || pose_accel;
   a.h.gx = F;
   a.h.gy = 1;
   FinArgs fa;
@@ -2484,7 +2428,7 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
   fa.betas = d_x + lay.off_betas;
   fa.o_betas = p->d_o_betas;
   fa.closs = data_c;
-  fa.cpose = (p->stage == UUO_STAGE_PART || prior) ? 0.0 : (double)p->w_pose / ((double)F * 207.0);  // (prior: k_prior_conf's shares)
+  fa.cpose = (p->stage == UUO_STAGE_PART) ? 0.0 : (double)p->w_pose / ((double)F * 207.0);
   fa.cbetas = (double)p->w_betas / 10.0;
   fa.g_betas = d_grad + gl.off_betas;
   fa.g_z = (p->stage == UUO_STAGE_PART) ? d_grad + gl.off_z : nullptr;
@@ -2496,6 +2440,12 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
   fa.rep_seq = report ? report->seq : 0ull;
   fa.h.gx = 1;
   fa.h.gy = 1;
+  // EXTENSION: the workspace's side terms; the routes below launch their forward kernels once fit->frames is there
+  const UuoSideTerms terms = arm_side_terms(fit, p, F, a, fa);
+  const bool temporal = terms.any(), floor = terms.floor;
+  auto launch_side_terms = [&]() {
+    uuo_launch_side_terms(fit, s, F, src, terms.prior ? d_x + lay.off_pose : nullptr, p->d_o_pose, p->w_pose, terms);
+  };
   OffsFinArgs oa;
   std::memset(&oa, 0, sizeof(oa));
   if (offs) {
@@ -2776,6 +2726,50 @@ extern "C" int uuo_debug_bwd_select(const int* facts, int row, char* name_out, u
   name_out[63] = 0;
   *flags_out = bk->flags;
   return n;
+}
+// host-only debug hook (tests/test_term_refusals.py): validate_problem on a workspace with side term `term` set (row of
+// side_term_rows; -1: none, -2: all of them) in `situation` 0 none, 1 part stage, 2 soft chamfer, 3 soft part, 4 lock-step
+// recording.  Nothing touches the device: the structs hold dummy pointers that validation only compares with null.
+extern "C" int uuo_debug_term_refusal(int term, int situation) {
+  const int n = (int)(sizeof(side_term_rows) / sizeof(side_term_rows[0]));
+  UUO_REQUIRE(term >= -2 && term < n, "uuo_debug_term_refusal: no such term");
+  UUO_REQUIRE(situation >= 0 && situation <= 4, "uuo_debug_term_refusal: no such situation");
+  static float some[1];
+  static int32_t some_ids[1];
+  uuo_model model;
+  model.V = 1;
+  uuo_fit fit;
+  fit.model = &model;
+  fit.F = 5;
+  fit.M = 4;
+  fit.lim_g = some;
+  fit.pacc_tab.dev = some;
+  const auto set = [&](int t) { return term == -2 || term == t; };
+  if (set(0)) fit.joint_accel = 1.f;
+  if (set(1)) fit.foot_lock = 1.f;
+  if (set(2)) fit.floor_k = 2;
+  if (set(3)) fit.cap_w = 1.f;
+  if (set(4)) fit.kp_w = 1.f;
+  if (set(5)) fit.lim_w = 1.f;
+  if (set(6)) fit.pacc_w = 1.f;
+  if (set(7)) fit.prior_w = some;
+  uuo_problem_t p;
+  std::memset(&p, 0, sizeof(p));
+  const bool part = situation == 1 || situation == 3;
+  p.stage = part ? UUO_STAGE_PART : UUO_STAGE_CHAMFER;
+  p.F = fit.F;
+  p.M = fit.M;
+  p.d_markers = p.d_o_pose = p.d_o_betas = p.d_root = some;
+  p.d_subset = some_ids;  // (read by the part stage alone)
+  p.n_subset = 1;
+  p.pose_cache_id = 1;
+  p.w_pose = 1.f;
+  if (situation == 2 || situation == 3) p.w_soft = p.soft_tau = 1.f;
+  UuoRecorder rec;
+  uuo_recorder = (situation == 4) ? &rec : nullptr;
+  const int rc = validate_problem(&fit, &p);
+  uuo_recorder = nullptr;
+  return rc;
 }
 // the same for a whole problem (stage, F, M, w_offsets: the latent marker offsets' coordinates included)
 // host-only debug hook: the number of solver coordinates of the last stage solve set up on `fit` (stage_objective_init): n_act on

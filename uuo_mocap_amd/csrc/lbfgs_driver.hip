@@ -742,14 +742,10 @@ extern "C" int uuo_fit_destroy(uuo_fit_t* fit) {
   if (fit->bary_items) (void)hipFree(fit->bary_items);
   if (fit->offs_part) (void)hipFree(fit->offs_part);
   if (fit->floor_up) (void)hipFree(fit->floor_up);
-  if (fit->cap_tab) (void)hipFree(fit->cap_tab);  // (cap_geom is the same allocation)
   if (fit->cap_up) (void)hipFree(fit->cap_up);
-  if (fit->cap_stream) (void)hipStreamDestroy(fit->cap_stream);
-  if (fit->lim_tab) (void)hipFree(fit->lim_tab);
   if (fit->lim_g) (void)hipFree(fit->lim_g);
-  if (fit->lim_stream) (void)hipStreamDestroy(fit->lim_stream);
-  if (fit->pacc_tab) (void)hipFree(fit->pacc_tab);
-  if (fit->pacc_stream) (void)hipStreamDestroy(fit->pacc_stream);
+  for (UuoUploadedTable* t : {&fit->cap_tab, &fit->lim_tab, &fit->pacc_tab}) t->destroy();
+  if (fit->upload_stream) (void)hipStreamDestroy(fit->upload_stream);
   if (fit->surf_corners) (void)hipFree(fit->surf_corners);  // (surf_bary is the same allocation)
   if (fit->dbg_verts) (void)hipFree(fit->dbg_verts);
   if (fit->ev0) (void)hipEventDestroy(fit->ev0);

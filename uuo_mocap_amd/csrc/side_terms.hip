@@ -576,10 +576,12 @@ __global__ __launch_bounds__(64) void k_keypoint2d_fwd(Keypoint2dArgs a) {
   if (head) a.up[(size_t)a.F * 72 + f] = old_share + a.cl * part;
 }
 
-// The side terms that are on, in this order on stream s, once the frames' FrameLds of this evaluation are there.
+// The side terms that are on, in this order on stream s, once the frames' FrameLds of this evaluation are there.  cap_up and
+// lim_g are shared: the first kernel of an evaluation to reach a buffer writes it, the later ones add to it.
 void uuo_launch_side_terms(uuo_fit* fit, hipStream_t s, int F, const UuoPoseSrc& src, const float* d_pose, const float* d_o_pose,
                            float w_pose, UuoSideTerms on) {
   const uuo_model* m = fit->model;
+  bool cap_up_written = false, lim_g_written = false;  // in this evaluation
   if (on.floor) {
     FloorFwdArgs b;
     std::memset(&b, 0, sizeof(b));
@@ -593,23 +595,23 @@ void uuo_launch_side_terms(uuo_fit* fit, hipStream_t s, int F, const UuoPoseSrc&
     b.cpen = (float)((double)fit->floor_pen / ((double)F * (double)fit->floor_k));
     b.ccon = (float)((double)fit->floor_con / (2.0 * (double)F));
     b.up = fit->floor_up;
-    b.loss = fit->floor_up + (size_t)F * UUO_FLOOR_MAXK * 3;
+    b.loss = uuo_floor_up_shares(fit);
     hipLaunchKernelGGL(k_floor_fwd, dim3(F), dim3(64), 0, s, b);
   }
   if (on.caps) {
     CapsFwdArgs b;
     std::memset(&b, 0, sizeof(b));
     b.frames = fit->frames;
-    b.tab = fit->cap_tab;
-    b.geom = fit->cap_geom;
+    b.tab = static_cast<const int32_t*>(fit->cap_tab.dev);
+    b.geom = reinterpret_cast<const float*>(static_cast<const int32_t*>(fit->cap_tab.dev) + UUO_CAPS_TAB_INTS);
     b.C = fit->cap_c; b.P = fit->cap_p;
     b.cl = (float)((double)fit->cap_w / (double)F);
     b.cg = (float)(2.0 * (double)fit->cap_w / (double)F);
     b.up = fit->cap_up;
-    b.loss = fit->cap_up + (size_t)F * 72;
+    b.loss = uuo_cap_up_shares(fit);
     hipLaunchKernelGGL(k_capsule_fwd, dim3(F), dim3(64), 0, s, b);
-    fit->cap_launched = true;  // (uuo_fit_set_capsules waits for this stream before it replaces the tables)
-    fit->cap_last_stream = s;
+    fit->cap_tab.note_reader(s);
+    cap_up_written = true;
   }
   if (on.kp) {
     Keypoint2dArgs b;
@@ -620,43 +622,44 @@ void uuo_launch_side_terms(uuo_fit* fit, hipStream_t s, int F, const UuoPoseSrc&
     b.targets = fit->kp_targets;
     b.conf = fit->kp_conf;
     b.F = F;
-    b.add = on.caps ? 1 : 0;
+    b.add = cap_up_written ? 1 : 0;
     b.cl = (float)((double)fit->kp_w / (48.0 * (double)F));
     b.cg = (float)(2.0 * (double)fit->kp_w / (48.0 * (double)F));
     b.rs2 = (float)((double)fit->kp_sigma * (double)fit->kp_sigma);
     b.min_depth = fit->kp_min_depth;
     b.up = fit->cap_up;
     hipLaunchKernelGGL(k_keypoint2d_fwd, dim3((F + UUO_LIM_FPB - 1) / UUO_LIM_FPB), dim3(64), 0, s, b);
+    cap_up_written = true;
   }
   if (on.limits) {
     LimitFwdArgs b;
     std::memset(&b, 0, sizeof(b));
     b.body = src.body;
-    b.tab = fit->lim_tab;
+    b.tab = static_cast<const float*>(fit->lim_tab.dev);
     b.F = F;
     b.norm_body = src.norm_body;
     b.cl = (float)((double)fit->lim_w / (double)F);
     b.cg = (float)(2.0 * (double)fit->lim_w / (double)F);
     b.g = fit->lim_g;
-    b.loss = fit->lim_g + (size_t)F * 207;
+    b.loss = uuo_lim_g_shares(fit);
     hipLaunchKernelGGL(k_limit_fwd, dim3((F + UUO_LIM_FPB - 1) / UUO_LIM_FPB), dim3(64), 0, s, b);
-    fit->lim_launched = true;  // (uuo_fit_set_joint_limits waits for this stream before it replaces the table)
-    fit->lim_last_stream = s;
+    fit->lim_tab.note_reader(s);
+    lim_g_written = true;
   }
   if (on.pose_accel) {  // (the caller has seen F >= 3)
     PoseAccelArgs b;
     std::memset(&b, 0, sizeof(b));
     b.body = src.body;
-    b.u = fit->pacc_tab;
+    b.u = static_cast<const float*>(fit->pacc_tab.dev);
     b.F = F;
     b.norm_body = src.norm_body;
-    b.add = on.limits ? 1 : 0;
+    b.add = lim_g_written ? 1 : 0;
     b.cl = (float)((double)fit->pacc_w / ((double)(F - 2) * 207.0));
     b.cg = (float)(2.0 * (double)fit->pacc_w / ((double)(F - 2) * 207.0));
     b.g = fit->lim_g;
     hipLaunchKernelGGL(k_pose_accel, dim3((F + UUO_LIM_FPB - 1) / UUO_LIM_FPB), dim3(64), 0, s, b);
-    fit->pacc_launched = true;  // (uuo_fit_set_pose_accel waits for this stream before it replaces the table)
-    fit->pacc_last_stream = s;
+    fit->pacc_tab.note_reader(s);
+    lim_g_written = true;
   }
   if (on.prior) {
     PriorConfArgs b;
@@ -665,12 +668,31 @@ void uuo_launch_side_terms(uuo_fit* fit, hipStream_t s, int F, const UuoPoseSrc&
     b.target = d_o_pose;
     b.w = fit->prior_w;
     b.F = F;
-    b.add = (on.limits || on.pose_accel) ? 1 : 0;
+    b.add = lim_g_written ? 1 : 0;
     b.cl = (float)((double)w_pose / ((double)F * 207.0));
     b.cg = (float)(2.0 * (double)w_pose / ((double)F * 207.0));
     b.g = fit->lim_g;
     hipLaunchKernelGGL(k_prior_conf, dim3((F + UUO_LIM_FPB - 1) / UUO_LIM_FPB), dim3(64), 0, s, b);
   }
+}
+
+// the two shared accumulation buffers, allocated by the first setter that needs one: [F][207] (lim_g) or [F][72] (cap_up)
+// gradients, then the [F] loss shares (uuo_lim_g_shares, uuo_cap_up_shares)
+static int ensure_lim_g(uuo_fit* fit) {
+  if (!fit->lim_g) UUO_HIP_CHECK(hipMalloc((void**)&fit->lim_g, ((size_t)fit->F * 207 + fit->F) * sizeof(float)));
+  return 0;
+}
+static int ensure_cap_up(uuo_fit* fit) {
+  if (!fit->cap_up) UUO_HIP_CHECK(hipMalloc((void**)&fit->cap_up, ((size_t)fit->F * 72 + fit->F) * sizeof(float)));
+  return 0;
+}
+
+extern "C" int uuo_fit_set_joint_accel(uuo_fit_t* fit, float w) {
+  UUO_REQUIRE(fit, "uuo_fit_set_joint_accel: null fit");
+  UUO_REQUIRE(w == 0.f || (w > 0.f && w <= 3.0e38f), "uuo_fit_set_joint_accel: the weight must be 0 (off) or a positive finite number");
+  UUO_REQUIRE(w == 0.f || !uuo_recorder, "uuo_fit_set_joint_accel: lock-step batches do not carry the joint-acceleration term");
+  fit->joint_accel = w;
+  return 0;
 }
 
 extern "C" int uuo_fit_set_foot_lock(uuo_fit_t* fit, float w, const float* d_contacts) {
@@ -747,50 +769,43 @@ extern "C" int uuo_fit_set_capsules(uuo_fit_t* fit, float w, int32_t n_caps, con
     UUO_REQUIRE(i >= 0 && i < C && j >= 0 && j < C, "uuo_fit_set_capsules: a pair's capsule index is outside [0, C)");
     UUO_REQUIRE(i != j, "uuo_fit_set_capsules: a pair needs two different capsules");
   }
-  if (!fit->cap_tab) {  // first use: the tables (ints, then the geometry) and the kernel's outputs
-    UUO_HIP_CHECK(hipMalloc((void**)&fit->cap_tab, UUO_CAPS_TAB_INTS * sizeof(int32_t) + UUO_CAPS_MAXC * 3 * sizeof(float)));
-    fit->cap_geom = reinterpret_cast<float*>(fit->cap_tab + UUO_CAPS_TAB_INTS);
-    fit->cap_c = fit->cap_p = 0;
-    UUO_HIP_CHECK(hipStreamCreateWithFlags(&fit->cap_stream, hipStreamNonBlocking));
-  }
-  if (!fit->cap_up) UUO_HIP_CHECK(hipMalloc((void**)&fit->cap_up, ((size_t)fit->F * 72 + fit->F) * sizeof(float)));
-  const bool same = fit->cap_c == C && fit->cap_p == P &&
-                    std::memcmp(fit->cap_h_joints, h_cap_joints, (size_t)C * 2 * sizeof(int32_t)) == 0 &&
-                    std::memcmp(fit->cap_h_geom, h_cap_geom, (size_t)C * 3 * sizeof(float)) == 0 &&
-                    std::memcmp(fit->cap_h_pairs, h_pairs, (size_t)P * 2 * sizeof(int32_t)) == 0;
-  if (!same) {
+  if (const int rc = ensure_cap_up(fit)) return rc;
+  // what the table is built from: the caller's lists (zero-padded, so that equal structs are equal lists)
+  struct {
+    int32_t C, P, joints[UUO_CAPS_MAXC * 2], pairs[UUO_CAPS_MAXP * 2];
+    float geom[UUO_CAPS_MAXC * 3];
+  } key;
+  std::memset(&key, 0, sizeof(key));
+  key.C = C;
+  key.P = P;
+  std::memcpy(key.joints, h_cap_joints, (size_t)C * 2 * sizeof(int32_t));
+  std::memcpy(key.pairs, h_pairs, (size_t)P * 2 * sizeof(int32_t));
+  std::memcpy(key.geom, h_cap_geom, (size_t)C * 3 * sizeof(float));
+  struct Image {  // (the kernel fetches the whole table)
+    int32_t tab[UUO_CAPS_TAB_INTS];
+    float geom[UUO_CAPS_MAXC * 3];
+  };
+  const int rc = fit->cap_tab.replace_if_changed(&fit->upload_stream, &fit->cap_w, &key, sizeof(key), sizeof(Image), [&]() -> const void* {
     // the joint -> (pair, end) table, CSR: joint jj's rows list 4 k + end in pair order, inside a pair in the order
     // u_i (end 0), v_i (1), u_j (2), v_j (3) -- the order in which k_capsule_fwd sums
-    static thread_local int32_t h_tab[UUO_CAPS_TAB_INTS];
-    std::memset(h_tab, 0, sizeof(h_tab));
-    std::memcpy(h_tab, h_cap_joints, (size_t)C * 2 * sizeof(int32_t));
-    std::memcpy(h_tab + UUO_CAPS_TAB_PAIRS, h_pairs, (size_t)P * 2 * sizeof(int32_t));
+    static thread_local Image im;
+    std::memset(&im, 0, sizeof(im));
+    std::memcpy(im.tab, key.joints, sizeof(key.joints));
+    std::memcpy(im.tab + UUO_CAPS_TAB_PAIRS, key.pairs, sizeof(key.pairs));
+    std::memcpy(im.geom, key.geom, sizeof(key.geom));
     int n = 0;
     for (int jj = 0; jj < UUO_NUM_JOINTS; ++jj) {
-      h_tab[UUO_CAPS_TAB_OFF + jj] = n;
+      im.tab[UUO_CAPS_TAB_OFF + jj] = n;
       for (int k = 0; k < P; ++k)
         for (int end = 0; end < 4; ++end)
-          if (h_cap_joints[h_pairs[k * 2 + (end >> 1)] * 2 + (end & 1)] == jj) h_tab[UUO_CAPS_TAB_ENT + n++] = 4 * k + end;
+          if (h_cap_joints[h_pairs[k * 2 + (end >> 1)] * 2 + (end & 1)] == jj) im.tab[UUO_CAPS_TAB_ENT + n++] = 4 * k + end;
     }
-    h_tab[UUO_CAPS_TAB_OFF + UUO_NUM_JOINTS] = n;  // = 4 P
-    fit->cap_w = 0.f;
-    fit->cap_c = fit->cap_p = 0;
-    // the only reader of the old tables is the last k_capsule_fwd launched on this workspace: wait for its stream alone (no
-    // device-wide wait: other threads' workspaces keep running; nothing is added to an evaluation), upload on the workspace's
-    // own non-blocking stream, and return once the copies have landed, so that every later launch sees them
-    if (fit->cap_launched) UUO_HIP_CHECK(hipStreamSynchronize(fit->cap_last_stream));
-    fit->cap_launched = false;
-    UUO_HIP_CHECK(hipMemcpyAsync(fit->cap_tab, h_tab, sizeof(h_tab), hipMemcpyHostToDevice, fit->cap_stream));
-    float h_geom[UUO_CAPS_MAXC * 3] = {0.f};  // (the kernel fetches the whole table)
-    std::memcpy(h_geom, h_cap_geom, (size_t)C * 3 * sizeof(float));
-    UUO_HIP_CHECK(hipMemcpyAsync(fit->cap_geom, h_geom, sizeof(h_geom), hipMemcpyHostToDevice, fit->cap_stream));
-    UUO_HIP_CHECK(hipStreamSynchronize(fit->cap_stream));
-    std::memcpy(fit->cap_h_joints, h_cap_joints, (size_t)C * 2 * sizeof(int32_t));
-    std::memcpy(fit->cap_h_geom, h_cap_geom, (size_t)C * 3 * sizeof(float));
-    std::memcpy(fit->cap_h_pairs, h_pairs, (size_t)P * 2 * sizeof(int32_t));
-    fit->cap_c = C;
-    fit->cap_p = P;
-  }
+    im.tab[UUO_CAPS_TAB_OFF + UUO_NUM_JOINTS] = n;  // = 4 P
+    return &im;
+  });
+  if (rc) return rc;
+  fit->cap_c = C;
+  fit->cap_p = P;
   fit->cap_w = w;
   return 0;
 }
@@ -812,8 +827,7 @@ extern "C" int uuo_fit_set_keypoints2d(uuo_fit_t* fit, float w, float sigma, flo
               "uuo_fit_set_keypoints2d: a positive weight needs the cameras [F][16], the targets [F][24][2] and the confidences "
               "[F][24] on the device");
   UUO_REQUIRE(!uuo_recorder, "uuo_fit_set_keypoints2d: lock-step batches do not carry the key-point reprojection term");
-  // (the buffer k_keypoint2d_fwd fills is the self-penetration term's: [F][72] gradients, then [F] shares)
-  if (!fit->cap_up) UUO_HIP_CHECK(hipMalloc((void**)&fit->cap_up, ((size_t)fit->F * 72 + fit->F) * sizeof(float)));
+  if (const int rc = ensure_cap_up(fit)) return rc;  // (the buffer k_keypoint2d_fwd fills is the self-penetration term's)
   fit->kp_w = w;
   fit->kp_sigma = sigma;
   fit->kp_min_depth = min_depth;
@@ -839,30 +853,11 @@ extern "C" int uuo_fit_set_joint_limits(uuo_fit_t* fit, float w, const float* h_
     UUO_REQUIRE(hi >= -3.0e38f, "uuo_fit_set_joint_limits: an upper bound of -inf admits no angle (+inf = no bound)");
     UUO_REQUIRE(lo <= hi, "uuo_fit_set_joint_limits: lo > hi");
   }
-  if (!fit->lim_tab) {  // first use: the table and the upload stream
-    UUO_HIP_CHECK(hipMalloc((void**)&fit->lim_tab, 2 * 69 * sizeof(float)));
-    fit->lim_have = false;
-    UUO_HIP_CHECK(hipStreamCreateWithFlags(&fit->lim_stream, hipStreamNonBlocking));
-  }
-  if (!fit->lim_g) UUO_HIP_CHECK(hipMalloc((void**)&fit->lim_g, ((size_t)fit->F * 207 + fit->F) * sizeof(float)));
-  const bool same = fit->lim_have && std::memcmp(fit->lim_h, h_lo, 69 * sizeof(float)) == 0 &&
-                    std::memcmp(fit->lim_h + 69, h_hi, 69 * sizeof(float)) == 0;
-  if (!same) {
-    fit->lim_w = 0.f;
-    fit->lim_have = false;
-    // the only reader of the old table is the last k_limit_fwd launched on this workspace: wait for its stream alone (no
-    // device-wide wait: other threads' workspaces keep running; nothing is added to an evaluation), upload on the workspace's
-    // own non-blocking stream, and return once the copy has landed, so that every later launch sees it
-    if (fit->lim_launched) UUO_HIP_CHECK(hipStreamSynchronize(fit->lim_last_stream));
-    fit->lim_launched = false;
-    static thread_local float h_tab[2 * 69];
-    std::memcpy(h_tab, h_lo, 69 * sizeof(float));
-    std::memcpy(h_tab + 69, h_hi, 69 * sizeof(float));
-    UUO_HIP_CHECK(hipMemcpyAsync(fit->lim_tab, h_tab, sizeof(h_tab), hipMemcpyHostToDevice, fit->lim_stream));
-    UUO_HIP_CHECK(hipStreamSynchronize(fit->lim_stream));
-    std::memcpy(fit->lim_h, h_tab, sizeof(h_tab));
-    fit->lim_have = true;
-  }
+  if (const int rc = ensure_lim_g(fit)) return rc;
+  static thread_local float h_tab[2 * 69];
+  std::memcpy(h_tab, h_lo, 69 * sizeof(float));
+  std::memcpy(h_tab + 69, h_hi, 69 * sizeof(float));
+  if (const int rc = fit->lim_tab.replace_if_changed(&fit->upload_stream, &fit->lim_w, h_tab, sizeof(h_tab))) return rc;
   fit->lim_w = w;
   return 0;
 }
@@ -881,26 +876,8 @@ extern "C" int uuo_fit_set_pose_accel(uuo_fit_t* fit, float w, const float* h_jo
     UUO_REQUIRE(v >= 0.f && v <= 3.0e38f, "uuo_fit_set_pose_accel: a joint weight is NaN, negative or not finite");
     h_tab[i] = v;
   }
-  if (!fit->pacc_tab) {  // first use: the table and the upload stream
-    UUO_HIP_CHECK(hipMalloc((void**)&fit->pacc_tab, 23 * sizeof(float)));
-    fit->pacc_have = false;
-    UUO_HIP_CHECK(hipStreamCreateWithFlags(&fit->pacc_stream, hipStreamNonBlocking));
-  }
-  // (the buffer k_pose_accel fills is the joint-angle limit term's: [F][23][9] gradients, then [F] shares)
-  if (!fit->lim_g) UUO_HIP_CHECK(hipMalloc((void**)&fit->lim_g, ((size_t)fit->F * 207 + fit->F) * sizeof(float)));
-  const bool same = fit->pacc_have && std::memcmp(fit->pacc_h, h_tab, sizeof(h_tab)) == 0;
-  if (!same) {
-    fit->pacc_w = 0.f;
-    fit->pacc_have = false;
-    // the only reader of the old table is the last k_pose_accel launched on this workspace: wait for its stream alone (no
-    // device-wide wait), upload on the workspace's own non-blocking stream, and return once the copy has landed
-    if (fit->pacc_launched) UUO_HIP_CHECK(hipStreamSynchronize(fit->pacc_last_stream));
-    fit->pacc_launched = false;
-    UUO_HIP_CHECK(hipMemcpyAsync(fit->pacc_tab, h_tab, sizeof(h_tab), hipMemcpyHostToDevice, fit->pacc_stream));
-    UUO_HIP_CHECK(hipStreamSynchronize(fit->pacc_stream));
-    std::memcpy(fit->pacc_h, h_tab, sizeof(h_tab));
-    fit->pacc_have = true;
-  }
+  if (const int rc = ensure_lim_g(fit)) return rc;  // (the buffer k_pose_accel fills is the joint-angle limit term's)
+  if (const int rc = fit->pacc_tab.replace_if_changed(&fit->upload_stream, &fit->pacc_w, h_tab, sizeof(h_tab))) return rc;
   fit->pacc_w = w;
   return 0;
 }
@@ -908,8 +885,8 @@ extern "C" int uuo_fit_set_pose_accel(uuo_fit_t* fit, float w, const float* h_jo
 extern "C" int uuo_fit_set_prior_weights(uuo_fit_t* fit, const float* d_weights) {
   UUO_REQUIRE(fit, "uuo_fit_set_prior_weights: null fit");
   UUO_REQUIRE(!d_weights || !uuo_recorder, "uuo_fit_set_prior_weights: lock-step batches do not carry the pose prior's weights");
-  // (the buffer k_prior_conf fills is the joint-angle limit term's: [F][23][9] gradients, then [F] shares)
-  if (d_weights && !fit->lim_g) UUO_HIP_CHECK(hipMalloc((void**)&fit->lim_g, ((size_t)fit->F * 207 + fit->F) * sizeof(float)));
+  if (d_weights)  // (the buffer k_prior_conf fills is the joint-angle limit term's)
+    if (const int rc = ensure_lim_g(fit)) return rc;
   fit->prior_w = d_weights;
   return 0;
 }

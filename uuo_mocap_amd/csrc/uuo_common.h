@@ -160,6 +160,54 @@ struct UuoPoseSrc {
   uuo_gptr<const float> trans;  // [F,3] or null
 };
 
+// A small device table that a setter replaces between evaluations and that at most one kernel launch is reading (the
+// capsules', the joint limits' and the pose-acceleration term's tables).  The mirror holds what the table was last built from.
+struct UuoUploadedTable {
+  void* dev = nullptr;   // `bytes` on the device, allocated at the first upload
+  size_t bytes = 0;
+  std::vector<unsigned char> mirror;
+  bool valid = false;     // the device table is the mirror's
+  bool launched = false;  // a reader was launched since the last upload, on last_stream
+  hipStream_t last_stream = nullptr;
+  void note_reader(hipStream_t s) {
+    launched = true;
+    last_stream = s;
+  }
+  // Nothing happens when `key` is the mirror.  Otherwise the term is disarmed (*armed_w = 0: the setter arms it again once this
+  // has returned 0) and build() -- called only now -- gives the new image of image_bytes.  The only reader of the old table is
+  // the last launch noted on this workspace: its stream alone is waited for (no device-wide wait: other threads' workspaces keep
+  // running; nothing is added to an evaluation); the image goes up on the workspace's own non-blocking stream, and the call
+  // returns once the copy has landed, so that every later launch sees it.
+  template <class Build>
+  int replace_if_changed(hipStream_t* upload, float* armed_w, const void* key, size_t key_bytes, size_t image_bytes, Build build) {
+    if (valid && mirror.size() == key_bytes && std::memcmp(mirror.data(), key, key_bytes) == 0) return 0;
+    *armed_w = 0.f;
+    valid = false;
+    if (!dev) {
+      UUO_HIP_CHECK(hipMalloc(&dev, image_bytes));
+      bytes = image_bytes;
+    }
+    if (!*upload) UUO_HIP_CHECK(hipStreamCreateWithFlags(upload, hipStreamNonBlocking));
+    if (launched) UUO_HIP_CHECK(hipStreamSynchronize(last_stream));
+    launched = false;
+    UUO_HIP_CHECK(hipMemcpyAsync(dev, build(), bytes, hipMemcpyHostToDevice, *upload));
+    UUO_HIP_CHECK(hipStreamSynchronize(*upload));
+    const unsigned char* k = static_cast<const unsigned char*>(key);
+    mirror.assign(k, k + key_bytes);
+    valid = true;
+    return 0;
+  }
+  // (a table that is its own key)
+  int replace_if_changed(hipStream_t* upload, float* armed_w, const void* image, size_t n) {
+    return replace_if_changed(upload, armed_w, image, n, n, [image]() { return image; });
+  }
+  void destroy() {
+    if (dev) (void)hipFree(dev);
+    dev = nullptr;
+    valid = false;
+  }
+};
+
 struct uuo_fit {
   uuo_model* model = nullptr;
   int F = 0, M = 0, nFT = 0;
@@ -197,70 +245,44 @@ struct uuo_fit {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   float mask_sum = 0.f;  // host copy of sum(mask) (chamfer normaliser), refreshed by uuo_ensure_mask
   bool shared_pose_cache = false;  // pose_cache belongs to a uuo_batch (not freed with the fit)
-  float joint_accel = 0.f;  // EXTENSION: weight of the joint-acceleration term (uuo_fit_set_joint_accel; 0 = off)
-  float foot_lock = 0.f;    // EXTENSION: weight of the foot-lock term (uuo_fit_set_foot_lock; 0 = off) and its contact labels
-  const float* foot_contacts = nullptr;  // [F][2] on the device, the caller's (read at evaluation)
-  // EXTENSION: the floor-contact term (uuo_fit_set_floor; floor_k == 0 = off): weights, plane height, K = floor_k sole points
-  // (the first floor_kl on the left foot), the caller's vertex ids [K] and contact labels [F][2] (read at evaluation), and the
-  // workspace's own [F][16][3] upstream gradients + [F] loss shares (k_floor_fwd -> the backward kernels; first use)
+  // EXTENSION: the side terms of the fused closures (DESIGN.md "Side terms on the native side"; setters and forward kernels in
+  // side_terms.hip, one row each in closure.hip's side_term_rows).  A weight of 0 / a null pointer / floor_k == 0 is off.  Device
+  // arrays named "the caller's" are read at every evaluation and not copied.
+  float joint_accel = 0.f;  // uuo_fit_set_joint_accel
+  float foot_lock = 0.f;    // uuo_fit_set_foot_lock, and the caller's contact labels [F][2]
+  const float* foot_contacts = nullptr;
+  // uuo_fit_set_floor: weights, plane height, K = floor_k sole points (the first floor_kl on the left foot), the caller's vertex
+  // ids [K] and contact labels [F][2]; floor_up: [F][16][3] upstream gradients + [F] loss shares (k_floor_fwd -> the backward)
   float floor_pen = 0.f, floor_con = 0.f, floor_height = 0.f;
   int floor_k = 0, floor_kl = 0;
   const int32_t* floor_vids = nullptr;
   const float* floor_contacts = nullptr;
   float* floor_up = nullptr;
-  // EXTENSION: the bone-capsule self-penetration term (uuo_fit_set_capsules; cap_w == 0 = off): weight, C capsules, P pairs, the
-  // host copies of the caller's lists (compared at the next call: unchanged lists are not uploaded again), the workspace's own
-  // device tables -- cap_tab: [32][2] joints, [256][2] pairs, [25] CSR offsets of the joint -> (pair, end) table, [1024] its
-  // entries 4 pair + end; cap_geom [32][3] -- and [F][72] upstream joint gradients + [F] loss shares (k_capsule_fwd -> the
-  // backward kernels)
+  // uuo_fit_set_capsules: weight, C capsules, P pairs; cap_tab: [32][2] joints, [256][2] pairs, [25] CSR offsets of the joint ->
+  // (pair, end) table, [1024] its entries 4 pair + end, then the geometry [32][3]; its mirror holds the caller's lists.
+  // cap_up: [F][72] upstream joint gradients + [F] loss shares (k_capsule_fwd, k_keypoint2d_fwd -> the backward)
   float cap_w = 0.f;
   int cap_c = 0, cap_p = 0;
-  int32_t cap_h_joints[64], cap_h_pairs[512];
-  float cap_h_geom[96];
-  int32_t* cap_tab = nullptr;
-  float* cap_geom = nullptr;
+  UuoUploadedTable cap_tab;
   float* cap_up = nullptr;
-  // the stream of the last k_capsule_fwd launch on this workspace (the tables' only reader) and a private non-blocking stream
-  // for their upload: new lists wait for that stream alone, not for the device
-  bool cap_launched = false;
-  hipStream_t cap_last_stream = nullptr;
-  hipStream_t cap_stream = nullptr;
-  // EXTENSION: the joint-angle limit term on the body pose (uuo_fit_set_joint_limits; lim_w == 0 = off): weight, the host copies
-  // of the caller's tables (compared at the next call: unchanged tables are not uploaded again; lim_have = they are valid), the
-  // workspace's own device table lim_tab [2][23][3] (lo, then hi) and [F][23][9] parameter-space gradients + [F] loss shares
-  // (k_limit_fwd -> the backward kernels); the last reader's stream and the upload stream as for the capsules' lists
+  // uuo_fit_set_joint_limits: weight and lim_tab [2][23][3] (lo, then hi).  lim_g: [F][23][9] parameter-space gradients + [F]
+  // loss shares (k_limit_fwd, k_pose_accel, k_prior_conf -> the backward)
   float lim_w = 0.f;
-  bool lim_have = false;
-  float lim_h[2 * 69];
-  float* lim_tab = nullptr;
+  UuoUploadedTable lim_tab;
   float* lim_g = nullptr;
-  bool lim_launched = false;
-  hipStream_t lim_last_stream = nullptr;
-  hipStream_t lim_stream = nullptr;
-  // EXTENSION: per-(frame, joint) weights [F][23] on the pose prior of the chamfer and marker stages (uuo_fit_set_prior_weights;
-  // null = off), the caller's device pointer, read at every evaluation and not copied.  k_prior_conf leaves the whole weighted
-  // prior -- gradients and shares -- in lim_g (added there when the joint-angle limit term is on too), and the backward and the
-  // finalize run with a pose coefficient of 0.
+  // uuo_fit_set_prior_weights: the caller's [F][23] weights on the pose prior of the chamfer and marker stages.  k_prior_conf
+  // leaves the whole weighted prior in lim_g, and the backward and the finalize run with a pose coefficient of 0.
   const float* prior_w = nullptr;
-  // EXTENSION: the pose-acceleration term on the local body rotations (uuo_fit_set_pose_accel; pacc_w == 0 = off): weight, the
-  // host copy of the joint weights (compared at the next call; pacc_have = it is valid), the workspace's own device table
-  // pacc_tab [23]; the last reader's stream and the upload stream as for the limit term's table.  k_pose_accel leaves its
-  // gradients and shares in lim_g (added there when the joint-angle limit term is on too).
+  // uuo_fit_set_pose_accel: weight and pacc_tab [23] joint weights
   float pacc_w = 0.f;
-  bool pacc_have = false;
-  float pacc_h[23];
-  float* pacc_tab = nullptr;
-  bool pacc_launched = false;
-  hipStream_t pacc_last_stream = nullptr;
-  hipStream_t pacc_stream = nullptr;
-  // EXTENSION: the 2D key-point reprojection term on the 24 kinematic joints (uuo_fit_set_keypoints2d; kp_w == 0 = off): weight,
-  // Geman-McClure sigma (0 = the square), the least depth of a valid pair, and the caller's device arrays -- cameras [F][16],
-  // targets [F][24][2], confidences [F][24] -- read at every evaluation and not copied.  k_keypoint2d_fwd leaves its gradients and
-  // shares in cap_up (added there when the self-penetration term is on too).
+  UuoUploadedTable pacc_tab;
+  // uuo_fit_set_keypoints2d: weight, Geman-McClure sigma (0 = the square), the least depth of a valid pair, and the caller's
+  // cameras [F][16], targets [F][24][2], confidences [F][24]
   float kp_w = 0.f, kp_sigma = 0.f, kp_min_depth = 0.f;
   const float* kp_cam = nullptr;
   const float* kp_targets = nullptr;
   const float* kp_conf = nullptr;
+  hipStream_t upload_stream = nullptr;  // the uploaded tables' non-blocking stream (first upload)
   int last_n = 0;  // coordinates of the last stage solve set up on this workspace (n_act on the compact packing, else n_full):
                    // read back by the debug flavour's uuo_debug_last_solve_n, which tests use to see which packing a solve took
   int surface = 0;               // EXTENSION: point-to-surface chamfer term (uuo_fit_set_surface; 0 = off) and its stand-off
@@ -341,12 +363,20 @@ int uuo_launch_finalize(const uuo_fit* fit, hipStream_t s, const uuo_problem_t& 
 // per evaluation launches the forward kernels of the terms that are on, in that order on stream s, once fit->frames holds this
 // evaluation's FrameLds; src is the evaluation's pose source, d_pose / d_o_pose / w_pose the raw body pose, its prior target and
 // the prior's weight (the weighted prior only)
-#define UUO_FLOOR_MAXK 16  // sole points of the floor-contact term: fit->floor_up is [F][UUO_FLOOR_MAXK][3], then [F] loss shares
-struct UuoSideTerms {
-  bool floor, caps, limits, prior, kp, pose_accel;
+#define UUO_FLOOR_MAXK 16  // sole points of the floor-contact term
+struct UuoSideTerms {  // which terms an evaluation runs (accel and lock have no forward kernel: the backward forms them)
+  bool accel, lock, floor, caps, kp, limits, pose_accel, prior;
+  bool any() const {
+    const UuoSideTerms none{};
+    return std::memcmp(this, &none, sizeof(none)) != 0;
+  }
 };
 void uuo_launch_side_terms(uuo_fit* fit, hipStream_t s, int F, const UuoPoseSrc& src, const float* d_pose, const float* d_o_pose,
                            float w_pose, UuoSideTerms on);
+// where the [F] loss shares start behind the gradients of the three accumulation buffers
+inline float* uuo_floor_up_shares(const uuo_fit* fit) { return fit->floor_up + (size_t)fit->F * UUO_FLOOR_MAXK * 3; }
+inline float* uuo_cap_up_shares(const uuo_fit* fit) { return fit->cap_up + (size_t)fit->F * 72; }
+inline float* uuo_lim_g_shares(const uuo_fit* fit) { return fit->lim_g + (size_t)fit->F * 207; }
 
 // closure internals shared with the solver (closure.hip)
 int uuo_validate_problem(const uuo_fit* fit, const uuo_problem_t* p);

@@ -305,6 +305,28 @@ int uuo_fit_set_capsules(uuo_fit_t* fit, float w, int32_t n_caps, const int32_t*
  * the per-frame vertex table.  Refused (at evaluation) for the part stage and with w_soft != 0, and inside lock-step batches
  * (uuo_batch_*). */
 int uuo_fit_set_joint_limits(uuo_fit_t* fit, float w, const float* h_lo, const float* h_hi);
+/* EXTENSION (not reference behaviour; SMPLify's learned pose prior, the max-mixture of Gaussians over the 69 axis-angle
+ * components of the body pose): a mixture pose prior on the chamfer and marker stages.  theta [69] is the concatenation of the
+ * body joints' axis-angle vectors omega_j, j = 1 .. 23, each formed as for uuo_fit_set_joint_limits (same R, same branches: a joint
+ * within 1e-4 of a half turn has omega_j = 0 and receives no gradient).  Component k = 0 .. K-1, 1 <= K <= 16: mean mu_k [69],
+ * A_k [69][69] lower triangular with A_k A_k^T the inverse covariance, offset b_k = -log pi_k + 1/2 log det Sigma_k shifted so
+ * that the least is 0:
+ *   e_k = 1/2 |A_k^T (theta - mu_k)|^2 + b_k,   E = min_k e_k (ties: the lowest k),   loss += w sum_t E(theta_t) / F
+ *   dE/d theta = A_k* (A_k*^T (theta - mu_k*))   for the winner k*; no gradient through the choice.
+ * Frames are not coupled: F = 1 is a valid problem.  The root orientation, z, the translation and the shape are not read.  The
+ * gradient reaches the raw 3x3 pose entries through the stage's own Gram-Schmidt backward: third raw rows receive exact zeros.
+ * A setting of the WORKSPACE (off at creation) with the lifetime and ordering rules of uuo_fit_set_joint_limits.  h_means
+ * [K][69], h_chol [K][69][69] (A_k row-major; what is above the diagonal is not read) and h_offsets [K] are HOST float32 arrays,
+ * checked and COPIED at the call.  A call with the arrays of the previous call uploads nothing; new ones wait for the last
+ * evaluation that read the old table, on its stream alone.  w == 0 switches the term off; K is then not looked at and the
+ * pointers may be null, and every result is that of a workspace that never had the setting.  Errors (-22), each with its own
+ * text: a negative or non-finite w, K outside 1 .. 16, null arrays with w > 0, a non-finite entry, a non-positive diagonal entry
+ * of an A_k, a negative offset; a refused call changes nothing.
+ * Sums in an order fixed by the indices alone, no atomics: results are bit-reproducible, and a frame's result does not depend on
+ * the frames around it.  Works with what uuo_fit_set_joint_limits works with, with that term, the pose-acceleration term, the
+ * pose prior's weights and the key-point reprojection term.  Refused (at evaluation, -22) for the part stage and with
+ * w_soft != 0, and inside lock-step batches (uuo_batch_*).  uuo_problem_t and uuo_abi_version() are unchanged. */
+int uuo_fit_set_pose_gmm(uuo_fit_t* fit, float w, int K, const float* h_means, const float* h_chol, const float* h_offsets);
 /* EXTENSION (not reference behaviour): a pose-acceleration term on the LOCAL rotations of the 23 body joints of the chamfer and
  * marker stages.  R_t[j] is joint j's local rotation in frame t as the forward forms it (the stage's Gram-Schmidt of the raw
  * entries, or the raw entries themselves where the stage does not normalise), u[23] >= 0 joint weights:

@@ -131,6 +131,8 @@ _SIGNATURES = {
     "uuo_fit_set_capsules": (c_int, [c_void_p, c_float, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     # EXTENSION: joint-angle limit term of the workspace (w, host lo [23][3], host hi [23][3])
     "uuo_fit_set_joint_limits": (c_int, [c_void_p, c_float, c_void_p, c_void_p]),
+    # EXTENSION: mixture pose prior of the workspace (w, K, host means [K][69], host factors A_k [K][69][69], host offsets [K])
+    "uuo_fit_set_pose_gmm": (c_int, [c_void_p, c_float, c_int, c_void_p, c_void_p, c_void_p]),
     # EXTENSION: pose-acceleration term of the workspace (w, host joint weights [23] or null = ones)
     "uuo_fit_set_pose_accel": (c_int, [c_void_p, c_float, c_void_p]),
     # EXTENSION: per-(frame, joint) weights of the pose prior of the workspace (device [F][23]; null = off)
@@ -185,6 +187,9 @@ _DEBUG_SIGNATURES = {
     "uuo_debug_problem_index_map": (c_int, [POINTER(UuoProblem), c_int, c_void_p]),
     "uuo_debug_bwd_select": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),  # facts -> backward kernel (tests/test_bwd_select.py)
     "uuo_debug_term_refusal": (c_int, [c_int, c_int]),  # side term x situation -> validation's answer (tests/test_term_refusals.py)
+    "uuo_debug_term_refusal_by_setter": (c_int, [c_char_p, c_int]),  # the same, the row named by its setter (every row)
+    # [F] winning mixture components and [F] lim_g loss shares of the last evaluation (either may be null)
+    "uuo_debug_pose_gmm_state": (c_int, [c_void_p, c_void_p, c_void_p]),
     "uuo_debug_last_solve_n": (c_int, [c_void_p]),  # coordinates of the workspace's last stage solve (which packing it took)
     "uuo_debug_staging_script": (c_int, [c_void_p, c_int, ctypes.c_longlong, c_void_p]),
     # step-wise replay of the L-BFGS history kernels (tests/test_gpu_lbfgs_history.py)

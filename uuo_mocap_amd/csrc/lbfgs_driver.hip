@@ -744,7 +744,8 @@ extern "C" int uuo_fit_destroy(uuo_fit_t* fit) {
   if (fit->floor_up) (void)hipFree(fit->floor_up);
   if (fit->cap_up) (void)hipFree(fit->cap_up);
   if (fit->lim_g) (void)hipFree(fit->lim_g);
-  for (UuoUploadedTable* t : {&fit->cap_tab, &fit->lim_tab, &fit->pacc_tab}) t->destroy();
+  if (fit->gmm_win) (void)hipFree(fit->gmm_win);
+  for (UuoUploadedTable* t : {&fit->cap_tab, &fit->lim_tab, &fit->pacc_tab, &fit->gmm_tab}) t->destroy();
   if (fit->upload_stream) (void)hipStreamDestroy(fit->upload_stream);
   if (fit->surf_corners) (void)hipFree(fit->surf_corners);  // (surf_bary is the same allocation)
   if (fit->dbg_verts) (void)hipFree(fit->dbg_verts);

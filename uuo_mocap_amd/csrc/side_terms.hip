@@ -353,6 +353,244 @@ __global__ __launch_bounds__(64) void k_limit_fwd(LimitFwdArgs a) {
 }
 
 // ----------------------------------------------------------------------------------------------------
+// EXTENSION (not reference behaviour; uuo_fit_set_pose_gmm): SMPLify's max-mixture pose prior on the body pose.  theta [69] is
+// the concatenation of the body joints' axis-angle vectors omega_j, each formed as k_limit_fwd forms it (same R, same branches;
+// a half turn gives omega_j = 0 and receives no gradient).  Component k = 0 .. K-1 (K <= 16): mean mu_k, A_k lower triangular with
+// A_k A_k^T the inverse covariance, offset b_k >= 0:
+//   y_k = A_k^T (theta - mu_k),  e_k = 1/2 |y_k|^2 + b_k,  k* = argmin_k e_k (ties: the lowest k),  loss += (w / F) e_k*,
+//   dL/d theta = (w / F) A_k* y_k*            (no gradient through the choice),
+// then k_limit_fwd's chain per joint (dL/ds, dL/dc -> dL/dR -> gs6d_backward) into PARAMETER space.
+// k_pose_gmm delivers gradients and shares through the buffer of the joint-angle limit term with the protocol of k_prior_conf:
+// add == 0 writes the buffer, add != 0 (k_limit_fwd of this evaluation ran before it on the same stream) adds to it.
+// A block of 512 threads (eight waves) takes UUO_GMM_FPB = 8 frames and reads every table entry of step 1 once for all of them:
+//   0. thread (slot = t / 32, l = t % 32 < 23), t < 256 (four of the eight waves: 32 lanes a frame), forms omega of joint l + 1 of its frame and keeps raw, s,
+//      kappa and the two derivatives in registers for step 4; theta goes to LDS, frame minor.  A slot past F holds theta = 0 and
+//      stores nothing.
+//   1. wave w takes the components k = w, w + 8; lane c holds column c of y_k for the eight frames (lanes 0 .. 4 also columns
+//      64 .. 68): y_k[c] = sum_{r = c .. 68} A_k[r][c] (theta[r] - mu_k[r]), r ascending -- one coalesced row of the packed
+//      triangle per step, used by all eight frames, seven rows fetched at a time.  |y_k|^2: lane c adds y[c]^2 and y[64 + c]^2,
+//      then a fixed xor butterfly (32, 16, .. 1).  The wave keeps the best (e, k, y) per frame in registers (strict <: the
+//      lowest k of the wave stays).
+//   2. the eight waves' bests meet in LDS: the least e, on ties the lowest k; the winner's wave parks its y in LDS.
+//   3. wave w takes frame w: lane r forms row r of A_k* y (lanes 0 .. 4 also rows 64 .. 68), c ascending, seven entries of the
+//      row fetched at a time.
+//   4. thread (slot, l) runs the chain on its joint's three entries and writes or adds its nine gradients; lane 0 of a slot the
+//      frame's share and the winner (gmm_win: F ints that only the checkers read, see uuo_fit_set_pose_gmm).
+// Every sum's order is fixed by (r, c, lane) alone: it depends neither on the grid nor on F nor on the other frames of the block.
+// No atomics, 7 KB of LDS, no scratch: bit-reproducible.
+// ----------------------------------------------------------------------------------------------------
+#define UUO_GMM_FPB 8  // frames per block
+struct PoseGmmArgs {
+  uuo_gptr<const float> body;  // [F][23][9] raw body pose entries (UuoPoseSrc.body)
+  uuo_gptr<const float> tab;   // the workspace's table (uuo_common.h: UUO_GMM_TAB_*)
+  int F, K, norm_body, add;
+  float cw;                    // w / F
+  uuo_gptr<float> g;           // [F][23][9] gradients, then [F] shares: written (add == 0) or added to
+  uuo_gptr<int32_t> win;       // [F] out: the winning component (null: not stored)
+};
+#define UUO_GMM_WAVES 8  // waves per block: one frame each in step 3
+#define UUO_GMM_PF 7     // table entries a lane has in flight (7: 155 VGPRs; 8 takes 164, past the 160 of the kernels beside it)
+__global__ __launch_bounds__(64 * UUO_GMM_WAVES) void k_pose_gmm(PoseGmmArgs a) {
+  constexpr int FPB = UUO_GMM_FPB;
+  __shared__ __attribute__((aligned(16))) float sTh[69][FPB];  // theta, frame minor
+  __shared__ float sY[FPB][72], sG[FPB][72];                   // the winner's y, then (w / F) A y
+  constexpr int NW = UUO_GMM_WAVES, PF = UUO_GMM_PF;
+  static_assert(NW == FPB, "step 3 gives every wave one frame");
+  __shared__ float sBe[NW][FPB], sE[FPB];
+  __shared__ int sBk[NW][FPB], sK[FPB];
+  const int t = threadIdx.x, slot = (t >> 5) & (FPB - 1), l = t & 31;  // (steps 0 and 4 run on t < 256: 32 lanes a frame)
+  const int f = blockIdx.x * FPB + slot;
+  const bool on = t < 32 * FPB && f < a.F && l < 23;
+  const int K = min(max(a.K, 1), UUO_GMM_MAXK);  // (uuo_fit_set_pose_gmm has checked it; keeps the table reads in bounds)
+  const size_t row = on ? ((size_t)f * 23 + l) * 9 : 0;
+  // 0. omega of this thread's joint, as k_limit_fwd
+  float raw[9];
+#pragma unroll
+  for (int e = 0; e < 9; ++e) raw[e] = on ? a.body[row + e] : ((e == 0 || e == 4 || e == 8) ? 1.f : 0.f);
+  float R[9];
+  if (a.norm_body) {
+    gs6d_forward(raw, R);
+  } else {
+#pragma unroll
+    for (int e = 0; e < 9; ++e) R[e] = raw[e];
+  }
+  const float s[3] = {0.5f * (R[7] - R[5]), 0.5f * (R[2] - R[6]), 0.5f * (R[3] - R[1])};
+  const float c = 0.5f * (((R[0] + R[4]) + R[8]) - 1.f);
+  const float n2 = (s[0] * s[0] + s[1] * s[1]) + s[2] * s[2];
+  const float n = sqrtf(n2);
+  const bool small = n < 1e-4f;
+  const bool skip = small && c < 0.f;
+  const float nn = small ? 1.f : n;  // (keeps the quotients of the unused branch finite)
+  const float theta = atan2f(n, c);
+  const float kappa = small ? 1.f : theta / nn;
+  const float den = small ? 1.f : n2 + c * c;
+  const float dkn = small ? 0.f : (c / (nn * den) - theta / (nn * nn));
+  const float dkc = small ? 0.f : (-1.f / den);
+  if (t < 32 * FPB && l < 23) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) sTh[3 * l + k][slot] = (skip || !on) ? 0.f : kappa * s[k];
+  }
+  __syncthreads();
+  // 1. y_k and e_k of this wave's components, for the block's frames
+  const int w = t >> 6, ln = t & 63;
+  const bool tail = ln < 5;           // this lane also holds column (step 3: row) 64 + ln
+  const int c2 = tail ? 64 + ln : 0;
+  float be[FPB], by[FPB], by2[FPB];
+  int bk[FPB];
+#pragma unroll
+  for (int i = 0; i < FPB; ++i) {
+    be[i] = INFINITY;
+    by[i] = by2[i] = 0.f;
+    bk[i] = UUO_GMM_MAXK;
+  }
+  for (int k = w; k < K; k += NW) {
+    const float* A = a.tab + (size_t)k * UUO_GMM_TRI;
+    const float* mu = a.tab + UUO_GMM_TAB_MEANS + k * 69;
+    const float off = a.tab[UUO_GMM_TAB_OFFS + k];
+    float acc[FPB], acc2[FPB];
+#pragma unroll
+    for (int i = 0; i < FPB; ++i) acc[i] = acc2[i] = 0.f;
+    // rows in batches of PF: a batch's entries and means are fetched together (one round trip a batch, not one a row: the
+    // kernel's time is the table's trip from L2), then applied row by row -- the order of every sum stays r ascending
+#pragma unroll 1
+    for (int rb = 0; rb < 69; rb += PF) {
+      float av[PF], mv[PF];
+#pragma unroll
+      for (int u = 0; u < PF; ++u) {
+        const int r = min(rb + u, 68);
+        av[u] = A[r * (r + 1) / 2 + min(ln, r)];
+        mv[u] = mu[r];
+      }
+#pragma unroll
+      for (int u = 0; u < PF; ++u) {
+        const int r = min(rb + u, 68);
+        const bool act = rb + u < 69 && ln <= r;
+        const float4 t0 = *reinterpret_cast<const float4*>(&sTh[r][0]), t1 = *reinterpret_cast<const float4*>(&sTh[r][4]);
+        const float th[FPB] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w};
+#pragma unroll
+        for (int i = 0; i < FPB; ++i) acc[i] = act ? fmaf(av[u], th[i] - mv[u], acc[i]) : acc[i];
+        __builtin_amdgcn_sched_barrier(0);  // (keeps the next rows' LDS reads behind this row: eight more VGPRs a row otherwise)
+      }
+    }
+#pragma unroll
+    for (int r = 64; r < 69; ++r) {  // columns 64 .. 68 on lanes 0 .. 4
+      const bool act = tail && c2 <= r;
+      const float av = A[r * (r + 1) / 2 + (act ? c2 : 0)];
+      const float m = mu[r];
+      const float4 t0 = *reinterpret_cast<const float4*>(&sTh[r][0]), t1 = *reinterpret_cast<const float4*>(&sTh[r][4]);
+      const float th[FPB] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w};
+#pragma unroll
+      for (int i = 0; i < FPB; ++i) acc2[i] = act ? fmaf(av, th[i] - m, acc2[i]) : acc2[i];
+    }
+#pragma unroll
+    for (int i = 0; i < FPB; ++i) {
+      float sq = fmaf(acc2[i], acc2[i], acc[i] * acc[i]);
+#pragma unroll
+      for (int mk = 32; mk >= 1; mk >>= 1) sq += __shfl_xor(sq, mk, 64);
+      const float e = fmaf(0.5f, sq, off);
+      if (e < be[i]) {
+        be[i] = e;
+        bk[i] = k;
+        by[i] = acc[i];
+        by2[i] = acc2[i];
+      }
+    }
+  }
+  // 2. the winner of every frame over the block's eight waves: the least e, on ties the lowest k
+  if (ln == 0) {
+#pragma unroll
+    for (int i = 0; i < FPB; ++i) {
+      sBe[w][i] = be[i];
+      sBk[w][i] = bk[i];
+    }
+  }
+  __syncthreads();
+  if (t < FPB) {
+    float e0 = sBe[0][t];
+    int k0 = sBk[0][t];
+#pragma unroll
+    for (int q = 1; q < NW; ++q) {
+      const float e = sBe[q][t];
+      const int kq = sBk[q][t];
+      if (e < e0 || (e == e0 && kq < k0)) {
+        e0 = e;
+        k0 = kq;
+      }
+    }
+    sE[t] = e0;
+    sK[t] = min(k0, K - 1);  // (k0 = 16 only when no e_k compared at all, a NaN pose: keeps the reads below in bounds)
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < FPB; ++i) {
+    if (w == (sK[i] & (NW - 1))) {  // (component k is wave k % 8's)
+      sY[i][ln] = by[i];
+      if (tail) sY[i][c2] = by2[i];
+    }
+  }
+  __syncthreads();
+  // 3. (w / F) A_k* y: rows ln and 64 + ln of frame w, the row's entries in batches of PF as above
+  {
+    const int i = w;
+    const float* A = a.tab + (size_t)sK[i] * UUO_GMM_TRI;
+    const int base1 = ln * (ln + 1) / 2, base2 = c2 * (c2 + 1) / 2;
+    float g1 = 0.f, g2 = 0.f;
+#pragma unroll 1
+    for (int cb = 0; cb < 69; cb += PF) {
+      float a1[PF], a2[PF];
+#pragma unroll
+      for (int u = 0; u < PF; ++u) {
+        a1[u] = A[base1 + min(cb + u, ln)];
+        a2[u] = A[base2 + min(cb + u, c2)];
+      }
+#pragma unroll
+      for (int u = 0; u < PF; ++u) {
+        const int cc = cb + u;
+        const float y = sY[i][min(cc, 68)];
+        g1 = (cc <= ln) ? fmaf(a1[u], y, g1) : g1;
+        g2 = (tail && cc <= c2) ? fmaf(a2[u], y, g2) : g2;
+      }
+    }
+    sG[i][ln] = a.cw * g1;
+    if (tail) sG[i][c2] = a.cw * g2;
+  }
+  __syncthreads();
+  // 4. k_limit_fwd's chain on this thread's joint
+  float g[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) g[k] = (skip || !on) ? 0.f : sG[slot][3 * min(l, 22) + k];
+  float old[9];
+#pragma unroll
+  for (int e = 0; e < 9; ++e) old[e] = (on && a.add) ? a.g[row + e] : 0.f;
+  const bool head = t < 32 * FPB && l == 0 && f < a.F;
+  const float old_share = (head && a.add) ? a.g[(size_t)a.F * 207 + f] : 0.f;
+  const float q = (s[0] * g[0] + s[1] * g[1]) + s[2] * g[2];
+  const float qn = q * dkn / nn;
+  const float ds[3] = {0.5f * (kappa * g[0] + qn * s[0]), 0.5f * (kappa * g[1] + qn * s[1]), 0.5f * (kappa * g[2] + qn * s[2])};
+  const float dc = 0.5f * (q * dkc);
+  const float dR[9] = {dc, -ds[2], ds[1], ds[2], dc, -ds[0], -ds[1], ds[0], dc};
+  float out[9];
+  if (a.norm_body) {
+    float da[6];
+    gs6d_backward(raw, dR, da);
+#pragma unroll
+    for (int e = 0; e < 6; ++e) out[e] = old[e] + da[e];
+    out[6] = old[6]; out[7] = old[7]; out[8] = old[8];
+  } else {
+#pragma unroll
+    for (int e = 0; e < 9; ++e) out[e] = old[e] + dR[e];
+  }
+  if (on) {
+#pragma unroll
+    for (int e = 0; e < 9; ++e) a.g[row + e] = out[e];
+  }
+  if (head) {
+    a.g[(size_t)a.F * 207 + f] = old_share + a.cw * sE[slot];
+    if (a.win) a.win[f] = sK[slot];
+  }
+}
+
+// ----------------------------------------------------------------------------------------------------
 // EXTENSION (not reference behaviour; uuo_fit_set_prior_weights): the pose prior of the chamfer and marker stages with a weight
 // per (frame, body joint), w[t][j] >= 0:
 //   loss += c sum_t sum_j w[t][j] sum_e (raw[t][j][e] - o[t][j][e])^2,   c = w_pose / (F 207)   (the normaliser of the uniform
@@ -646,6 +884,22 @@ void uuo_launch_side_terms(uuo_fit* fit, hipStream_t s, int F, const UuoPoseSrc&
     fit->lim_tab.note_reader(s);
     lim_g_written = true;
   }
+  if (on.pose_gmm) {
+    PoseGmmArgs b;
+    std::memset(&b, 0, sizeof(b));
+    b.body = src.body;
+    b.tab = static_cast<const float*>(fit->gmm_tab.dev);
+    b.F = F;
+    b.K = fit->gmm_k;
+    b.norm_body = src.norm_body;
+    b.add = lim_g_written ? 1 : 0;
+    b.cw = (float)((double)fit->gmm_w / (double)F);
+    b.g = fit->lim_g;
+    b.win = fit->gmm_win;
+    hipLaunchKernelGGL(k_pose_gmm, dim3((F + UUO_GMM_FPB - 1) / UUO_GMM_FPB), dim3(64 * UUO_GMM_WAVES), 0, s, b);
+    fit->gmm_tab.note_reader(s);
+    lim_g_written = true;
+  }
   if (on.pose_accel) {  // (the caller has seen F >= 3)
     PoseAccelArgs b;
     std::memset(&b, 0, sizeof(b));
@@ -859,6 +1113,68 @@ extern "C" int uuo_fit_set_joint_limits(uuo_fit_t* fit, float w, const float* h_
   std::memcpy(h_tab + 69, h_hi, 69 * sizeof(float));
   if (const int rc = fit->lim_tab.replace_if_changed(&fit->upload_stream, &fit->lim_w, h_tab, sizeof(h_tab))) return rc;
   fit->lim_w = w;
+  return 0;
+}
+
+extern "C" int uuo_fit_set_pose_gmm(uuo_fit_t* fit, float w, int K, const float* h_means, const float* h_chol, const float* h_offsets) {
+  UUO_REQUIRE(fit, "uuo_fit_set_pose_gmm: null fit");
+  UUO_REQUIRE(w == 0.f || (w > 0.f && w <= 3.0e38f), "uuo_fit_set_pose_gmm: the weight must be 0 (off) or a positive finite number");
+  if (w == 0.f) {  // off: nothing else is looked at (the table stays for the next call with the same mixture)
+    fit->gmm_w = 0.f;
+    return 0;
+  }
+  UUO_REQUIRE(K >= 1 && K <= UUO_GMM_MAXK, "uuo_fit_set_pose_gmm: 1 .. 16 components");
+  UUO_REQUIRE(h_means && h_chol && h_offsets,
+              "uuo_fit_set_pose_gmm: a positive weight needs the means [K][69], the factors A_k [K][69][69] and the offsets [K] (host arrays)");
+  UUO_REQUIRE(!uuo_recorder, "uuo_fit_set_pose_gmm: lock-step batches do not carry the pose mixture term");
+  const auto finite = [](float v) { return v >= -3.0e38f && v <= 3.0e38f; };  // (false for NaN)
+  for (int i = 0; i < K * 69; ++i) UUO_REQUIRE(finite(h_means[i]), "uuo_fit_set_pose_gmm: a mean is NaN or not finite");
+  for (int i = 0; i < K * 69 * 69; ++i) UUO_REQUIRE(finite(h_chol[i]), "uuo_fit_set_pose_gmm: an entry of a factor A_k is NaN or not finite");
+  for (int i = 0; i < K; ++i) UUO_REQUIRE(finite(h_offsets[i]), "uuo_fit_set_pose_gmm: an offset is NaN or not finite");
+  for (int k = 0; k < K; ++k)
+    for (int r = 0; r < 69; ++r)
+      UUO_REQUIRE(h_chol[((size_t)k * 69 + r) * 69 + r] > 0.f, "uuo_fit_set_pose_gmm: a diagonal entry of a factor A_k is not positive");
+  for (int i = 0; i < K; ++i) UUO_REQUIRE(h_offsets[i] >= 0.f, "uuo_fit_set_pose_gmm: an offset is negative (they are shifted so that the least is 0)");
+  if (const int rc = ensure_lim_g(fit)) return rc;  // (the buffer k_pose_gmm fills is the joint-angle limit term's)
+  // the winners, F ints and one store a frame: only the checkers read them (uuo_debug_pose_gmm_state), but the tests evaluate
+  // through the product flavour and hand its workspace to the debug flavour's hook, so the product keeps the buffer too
+  if (!fit->gmm_win) UUO_HIP_CHECK(hipMalloc((void**)&fit->gmm_win, (size_t)fit->F * sizeof(int32_t)));
+  // what the table is built from: K and the caller's arrays.  _arm() makes this call before every evaluation and solve with the
+  // arrays of the call before, so that case compares them with the mirror where they lie (three memcmp, 155 KB at K = 8: about
+  // 10 us of host time) and copies nothing
+  const size_t n_mu = (size_t)K * 69, n_a = (size_t)K * 69 * 69;
+  if (fit->gmm_tab.valid && fit->gmm_tab.mirror.size() == (1 + n_mu + n_a + K) * sizeof(float)) {
+    const float* mir = reinterpret_cast<const float*>(fit->gmm_tab.mirror.data());
+    if (mir[0] == (float)K && std::memcmp(mir + 1, h_means, n_mu * sizeof(float)) == 0 &&
+        std::memcmp(mir + 1 + n_mu, h_chol, n_a * sizeof(float)) == 0 &&
+        std::memcmp(mir + 1 + n_mu + n_a, h_offsets, (size_t)K * sizeof(float)) == 0) {
+      fit->gmm_k = K;
+      fit->gmm_w = w;
+      return 0;
+    }
+  }
+  static thread_local std::vector<float> key, image;
+  key.resize(1 + (size_t)K * (69 + 69 * 69 + 1));
+  key[0] = (float)K;
+  std::memcpy(key.data() + 1, h_means, (size_t)K * 69 * sizeof(float));
+  std::memcpy(key.data() + 1 + (size_t)K * 69, h_chol, (size_t)K * 69 * 69 * sizeof(float));
+  std::memcpy(key.data() + 1 + (size_t)K * (69 + 69 * 69), h_offsets, (size_t)K * sizeof(float));
+  const int rc = fit->gmm_tab.replace_if_changed(&fit->upload_stream, &fit->gmm_w, key.data(), key.size() * sizeof(float),
+                                                 (size_t)UUO_GMM_TAB_FLOATS * sizeof(float), [&]() -> const void* {
+    // the lower triangles row-major ((r, c) at r (r + 1) / 2 + c: what is above the diagonal is not read), every array at its
+    // K = 16 place, zeros behind
+    image.assign(UUO_GMM_TAB_FLOATS, 0.f);
+    for (int k = 0; k < K; ++k) {
+      for (int r = 0; r < 69; ++r)
+        for (int c = 0; c <= r; ++c) image[(size_t)k * UUO_GMM_TRI + r * (r + 1) / 2 + c] = h_chol[((size_t)k * 69 + r) * 69 + c];
+      std::memcpy(image.data() + UUO_GMM_TAB_MEANS + k * 69, h_means + k * 69, 69 * sizeof(float));
+      image[UUO_GMM_TAB_OFFS + k] = h_offsets[k];
+    }
+    return image.data();
+  });
+  if (rc) return rc;
+  fit->gmm_k = K;
+  fit->gmm_w = w;
   return 0;
 }
 

@@ -161,7 +161,7 @@ struct UuoPoseSrc {
 };
 
 // A small device table that a setter replaces between evaluations and that at most one kernel launch is reading (the
-// capsules', the joint limits' and the pose-acceleration term's tables).  The mirror holds what the table was last built from.
+// capsules', the joint limits', the pose-acceleration term's and the pose mixture's tables).  The mirror holds what the table was last built from.
 struct UuoUploadedTable {
   void* dev = nullptr;   // `bytes` on the device, allocated at the first upload
   size_t bytes = 0;
@@ -266,7 +266,7 @@ struct uuo_fit {
   UuoUploadedTable cap_tab;
   float* cap_up = nullptr;
   // uuo_fit_set_joint_limits: weight and lim_tab [2][23][3] (lo, then hi).  lim_g: [F][23][9] parameter-space gradients + [F]
-  // loss shares (k_limit_fwd, k_pose_accel, k_prior_conf -> the backward)
+  // loss shares (k_limit_fwd, k_pose_gmm, k_pose_accel, k_prior_conf -> the backward)
   float lim_w = 0.f;
   UuoUploadedTable lim_tab;
   float* lim_g = nullptr;
@@ -282,6 +282,13 @@ struct uuo_fit {
   const float* kp_cam = nullptr;
   const float* kp_targets = nullptr;
   const float* kp_conf = nullptr;
+  // uuo_fit_set_pose_gmm: weight, K components and gmm_tab (UUO_GMM_TAB_FLOATS floats: the packed lower triangles of the A_k,
+  // the means, the offsets, each at its K = 16 place); its mirror holds the caller's arrays
+  float gmm_w = 0.f;
+  int gmm_k = 0;
+  UuoUploadedTable gmm_tab;
+  int32_t* gmm_win = nullptr;  // [F] the winning component of every frame at the last evaluation (k_pose_gmm), for the checkers
+                               // (uuo_debug_pose_gmm_state); allocated by the setter
   hipStream_t upload_stream = nullptr;  // the uploaded tables' non-blocking stream (first upload)
   int last_n = 0;  // coordinates of the last stage solve set up on this workspace (n_act on the compact packing, else n_full):
                    // read back by the debug flavour's uuo_debug_last_solve_n, which tests use to see which packing a solve took
@@ -359,13 +366,18 @@ int uuo_launch_bwd(const uuo_fit* fit, hipStream_t s, const uuo_problem_t& p, co
 int uuo_launch_finalize(const uuo_fit* fit, hipStream_t s, const uuo_problem_t& p, const float* x, float* grad,
                         float* loss);
 
-// the closures' side terms (side_terms.hip: k_floor_fwd, k_capsule_fwd, k_keypoint2d_fwd, k_limit_fwd, k_pose_accel, k_prior_conf and their setters).  One call
+// the closures' side terms (side_terms.hip: k_floor_fwd, k_capsule_fwd, k_keypoint2d_fwd, k_limit_fwd, k_pose_gmm, k_pose_accel, k_prior_conf and their setters).  One call
 // per evaluation launches the forward kernels of the terms that are on, in that order on stream s, once fit->frames holds this
 // evaluation's FrameLds; src is the evaluation's pose source, d_pose / d_o_pose / w_pose the raw body pose, its prior target and
 // the prior's weight (the weighted prior only)
 #define UUO_FLOOR_MAXK 16  // sole points of the floor-contact term
+#define UUO_GMM_MAXK 16    // components of the pose mixture (uuo_fit_set_pose_gmm)
+#define UUO_GMM_TRI 2415   // entries of a 69 x 69 lower triangle, row-major: (r, c) at r (r + 1) / 2 + c
+#define UUO_GMM_TAB_MEANS (UUO_GMM_MAXK * UUO_GMM_TRI)            // gmm_tab layout (floats): triangles, means [16][69], offsets [16]
+#define UUO_GMM_TAB_OFFS (UUO_GMM_TAB_MEANS + UUO_GMM_MAXK * 69)
+#define UUO_GMM_TAB_FLOATS (UUO_GMM_TAB_OFFS + UUO_GMM_MAXK)
 struct UuoSideTerms {  // which terms an evaluation runs (accel and lock have no forward kernel: the backward forms them)
-  bool accel, lock, floor, caps, kp, limits, pose_accel, prior;
+  bool accel, lock, floor, caps, kp, limits, pose_accel, prior, pose_gmm;
   bool any() const {
     const UuoSideTerms none{};
     return std::memcmp(this, &none, sizeof(none)) != 0;

@@ -492,7 +492,7 @@ class _StageProblem:
         p.marker_distance = MARKER_DISTANCE
         self.problem = p
         self.n = int(self.lib.uuo_problem_num_params(byref(p)))
-        # EXTENSION: the terms' state (terms.TERMS: joint_accel, foot_lock, floor_*, cap_*, lim_*, prior_weights, kp_*, pacc_*), all off.  They
+        # EXTENSION: the terms' state (terms.TERMS: joint_accel, foot_lock, floor_*, cap_*, lim_*, gmm_*, prior_weights, kp_*, pacc_*), all off.  They
         # are settings of the WORKSPACE in the library: _arm() puts them there before every call that evaluates on it
         for term in terms.TERMS:
             vars(self).update(term.state)
@@ -510,6 +510,7 @@ class _StageProblem:
     prior_conf_on = property(lambda self: self.prior_weights is not None)
     keypoints_on = property(lambda self: self.kp_w != 0.0)
     pose_accel_on = property(lambda self: self.pacc_w != 0.0)
+    pose_gmm_on = property(lambda self: self.gmm_w != 0.0)
 
     def _set_terms(self, stage_terms, contacts, weights, smpl_inference):
         """EXTENSION: every term's state from its parsed record, the checked contact labels and prior weights and the armed
@@ -521,7 +522,7 @@ class _StageProblem:
     def _arm(self):
         """Sets this problem's terms (off without them), its surface term and its per-frame table on its workspace: one library
         call each, in the order they have always had (joint_accel, foot_lock, surface, per-frame table, floor, capsules, joint
-        limits, prior weights, key points, pose acceleration).  The workspace is shared by every problem of the same (F, M) on this thread, so this runs right
+        limits, pose mixture, prior weights, key points, pose acceleration).  The workspace is shared by every problem of the same (F, M) on this thread, so this runs right
         before each library call that evaluates on it."""
         for term in _ARMED[:2]:
             term.arm(self)
@@ -711,8 +712,10 @@ class ChamferProblem(_StageProblem):
     stage = UUO_STAGE_CHAMFER
 
     def __init__(self, smpl_inference, markers, o_pose_body, o_betas, root_orient, config, foot_contacts=None,
-                 prior_weights=None, stage_terms=None, keypoints_2d=None):
-        """EXTENSION: `prior_weights` [F, 23] >= 0 weighs the pose prior per frame and body joint (prior_weight_table builds it
+                 prior_weights=None, stage_terms=None, keypoints_2d=None, pose_mixture=None):
+        """EXTENSION: `pose_mixture` (a dict {means, covars, weights} or a path; None: stages.chamfer.pose_gmm.path) is the mixture
+        of stages.chamfer.losses.pose_gmm (terms.StageTerms.arm_pose_mixture).
+        EXTENSION: `prior_weights` [F, 23] >= 0 weighs the pose prior per frame and body joint (prior_weight_table builds it
         from the video's mask and stages.chamfer.prior_confidence); None, or ones everywhere, changes nothing.  `stage_terms`:
         the caller's terms.StageTerms of this config and stage, when it has parsed them already.
         EXTENSION: `keypoints_2d` {"camera" [F, 16], "targets" [F, 24, 2], "confidence" [F, 24]} is the evidence of the
@@ -734,6 +737,7 @@ class ChamferProblem(_StageProblem):
         # EXTENSION: the key-point reprojection term's evidence (validates the block and the record)
         if stage_terms.arm_keypoints(keypoints_2d, None if markers is None else markers.shape[0]) is not None and soft:
             raise NotImplementedError(terms.KEYPOINTS.soft)
+        stage_terms.arm_pose_mixture(pose_mixture)  # EXTENSION: the pose mixture (ValueError when the key has none)
         if not config["stages"]["chamfer"]["yaw_lock"]:
             raise NotImplementedError("stages.chamfer.yaw_lock False is not a shipped configuration")
         wd, wp, wb = _cfg_weights(losses, "surface_chamfer" if w_surface > 0.0 else "full_chamfer")
@@ -780,14 +784,14 @@ class MarkerProblem(_StageProblem):
     stage = UUO_STAGE_MARKER
 
     def __init__(self, smpl_inference, markers, o_pose_body, o_betas, assign, config, bary=None, foot_contacts=None,
-                 frame_assign=None, prior_weights=None, stage_terms=None, keypoints_2d=None):
+                 frame_assign=None, prior_weights=None, stage_terms=None, keypoints_2d=None, pose_mixture=None):
         """`assign` [M] vertex ids (the one-hot placement of the shipped configs), or -- with `bary` [M, 3] -- [M, 3] corner
         vertex ids of a three-corner (barycentric) placement: virtual marker m = sum_k bary[m, k] v[assign[m, k]].
         EXTENSION: `frame_assign` [F, M] int32, a per-frame vertex table (tracklets: the column's vertex changes with the frame,
         an entry < 0 is an item of weight 0); `assign` may then be None.  Refused with `bary` and with latent_offsets.
         EXTENSION: `prior_weights` [F, 23] >= 0 weighs the pose prior per frame and body joint (prior_weight_table); None, or
         ones everywhere, changes nothing.  `stage_terms`, and EXTENSION `keypoints_2d` (stages.marker.losses.keypoints_2d): as
-        ChamferProblem's."""
+        ChamferProblem's; EXTENSION `pose_mixture` (stages.marker.losses.pose_gmm) likewise."""
         st = config["stages"]["marker"]
         unsupported = set(st["losses"]) - terms.problem_keys("marker")
         if unsupported:
@@ -805,6 +809,7 @@ class MarkerProblem(_StageProblem):
         weights = check_prior_weights(prior_weights, None if markers is None else markers.shape[0])
         # EXTENSION: the key-point reprojection term's evidence (validates the block and the record)
         stage_terms.arm_keypoints(keypoints_2d, None if markers is None else markers.shape[0])
+        stage_terms.arm_pose_mixture(pose_mixture)  # EXTENSION: the pose mixture (ValueError when the key has none)
         w_offsets = stage_terms[terms.LATENT_OFFSETS]
         if frame_assign is not None:
             if bary is not None:

@@ -352,6 +352,43 @@ def joint_limit_loss(rot_body: torch.Tensor, lo, hi, w: float) -> torch.Tensor:
     return float(w) * (pen * pen).sum() / rot_body.shape[0]
 
 
+def pose_gmm_loss(rot_body: torch.Tensor, means, chol, offsets, w: float, winners_out: list = None) -> torch.Tensor:
+    """EXTENSION (not in the reference; SMPLify's max-mixture pose prior): the mixture pose prior of the fused chamfer and
+    marker closures (uuo_fit_set_pose_gmm), composed -- their checker.  rot_body [F, 23, 3, 3] are the body joints' local
+    rotations after the stage's normalisation; means [K, 69], chol [K, 69, 69] (A_k lower triangular, A_k A_k^T the inverse
+    covariance) and offsets [K] are body_model.prepare_pose_mixture's:
+    w sum_t min_k (1/2 |A_k^T (theta_t - mu_k)|^2 + b_k) / F,  theta the 69 axis-angle components (joint_limit_loss's omega:
+    the same branches; a half turn contributes omega = 0 and receives no gradient).  The branches and the argmin (ties: the
+    lowest k) are chosen under no_grad and in the tensors' own precision; everything else is under autograd, with no gradient
+    through the choice.  `winners_out`, a list, receives the [F] winning components."""
+    dev, dt = rot_body.device, rot_body.dtype
+    mu = torch.as_tensor(np.asarray(means, dtype=np.float64), dtype=dt, device=dev).reshape(-1, 69)
+    A = torch.tril(torch.as_tensor(np.asarray(chol, dtype=np.float64), dtype=dt, device=dev).reshape(-1, 69, 69))
+    b = torch.as_tensor(np.asarray(offsets, dtype=np.float64), dtype=dt, device=dev).reshape(-1)
+    R = rot_body
+    F = R.shape[0]
+    s = 0.5 * torch.stack([R[..., 2, 1] - R[..., 1, 2], R[..., 0, 2] - R[..., 2, 0], R[..., 1, 0] - R[..., 0, 1]], dim=-1)
+    c = 0.5 * (R[..., 0, 0] + R[..., 1, 1] + R[..., 2, 2] - 1.0)
+    n2 = (s * s).sum(-1)
+    with torch.no_grad():
+        small = torch.sqrt(n2) < 1e-4
+        skip = small & (c < 0.0)
+    one = torch.ones_like(n2)
+    n = torch.sqrt(torch.where(small, one, n2))  # (the identity and half-turn branches never use the quotient)
+    kappa = torch.where(small, one, torch.atan2(n, torch.where(small, one, c)) / n)
+    om = torch.where(skip[..., None], torch.zeros_like(s), kappa[..., None] * s)
+    theta = om.reshape(F, 69)
+    y = torch.einsum("krc,fkr->fkc", A, theta[:, None, :] - mu[None])  # A_k^T (theta - mu_k)
+    e = 0.5 * (y * y).sum(-1) + b[None]
+    with torch.no_grad():
+        win = torch.argmin(e, dim=1)  # (the first of equal minima)
+        win = torch.min(torch.where(e == e.gather(1, win[:, None]), torch.arange(e.shape[1], device=dev)[None], e.shape[1]), dim=1)[0]
+        win = win.clamp(max=e.shape[1] - 1)  # (a NaN energy equals nothing)
+    if winners_out is not None:
+        winners_out.append(win.detach().cpu())
+    return float(w) * e.gather(1, win[:, None]).sum() / F
+
+
 def pose_accel_loss(rot_body: torch.Tensor, w: float, joint_weights=None) -> torch.Tensor:
     """EXTENSION (the reference's `temporal` loss on the second difference of pose_body, optimization.py:368-375, has a sign error
     and stops in a debugger): the pose-acceleration term of the chamfer and marker stages' composed closures

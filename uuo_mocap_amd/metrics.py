@@ -146,6 +146,23 @@ def compute_joint_limit_violation(rot_body: torch.Tensor, lo, hi) -> Dict[str, f
     return {"max_deg": float(worst.max()), "mean_deg": float(worst.mean()), "frames_pct": 100.0 * float((worst > 0.0).mean())}
 
 
+def compute_pose_gmm_energy(rot_body: torch.Tensor, mixture: Dict) -> Dict:
+    """EXTENSION: the mixture pose prior's energy (not a metric of the reference) of body rotations [F, 23, 3, 3] under `mixture`
+    {means [K, 69], covars [K, 69, 69], weights [K]} (body_model.load_pose_mixture, synthetic.pose_mixture), float64, in nats:
+    E_t = min_k 1/2 |A_k^T (theta_t - mu_k)|^2 + b_k with the offsets shifted so that the least is 0 (uuo_fit_set_pose_gmm).
+    `mean` and `max` over the frames, `winner` [F] the winning component of every frame (ties: the lowest k)."""
+    from .body_model import check_pose_mixture, pose_log_vector, pose_mixture_factors
+
+    if rot_body.dim() != 4 or tuple(rot_body.shape[1:]) != (23, 3, 3):
+        raise ValueError("compute_pose_gmm_energy: rot_body [F, 23, 3, 3] expected (got %s)" % (tuple(rot_body.shape),))
+    mu, chol, off = pose_mixture_factors(*check_pose_mixture(mixture["means"], mixture["covars"], mixture["weights"],
+                                                             "compute_pose_gmm_energy"))
+    theta = pose_log_vector(rot_body.detach().cpu().double().numpy())
+    y = np.einsum("krc,fkr->fkc", chol, theta[:, None, :] - mu[None])
+    e = 0.5 * (y * y).sum(-1) + off[None]
+    return {"mean": float(e.min(axis=1).mean()), "max": float(e.min(axis=1).max()), "winner": np.argmin(e, axis=1)}
+
+
 def compute_window_vertex_error(pred_vertices: torch.Tensor, gt_vertices: torch.Tensor, window) -> Dict[str, float]:
     """EXTENSION: the mean vertex error (the tensors' unit) inside and outside the frame window (first frame, one past the
     last) -- what the pose prior's weights buy where the video lost the person, and what they cost elsewhere.  [F, V, 3] each;

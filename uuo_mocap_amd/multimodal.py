@@ -95,6 +95,7 @@ def multimodal_video_mocap(
     smpl_inference: SmplInference = None,
     execution: Dict = None,
     keypoints_2d: Dict = None,
+    pose_mixture=None,
 ) -> Dict:
     """See the reference docstring (multimodal.py:49-84) for the meaning of the inputs and output keys.
     `smpl_inference` (extension) lets callers reuse one model/workspace across sequences.  `execution` (extension; how the
@@ -106,7 +107,11 @@ def multimodal_video_mocap(
     calibrated camera in world axes and a detector's key points with confidences.  It goes to every chamfer and marker solve, the
     final stage included; it is cut and padded with the video's tracks (padded frames at confidence 0) and refused where the
     mocap and video frame rates differ.  Without it the record is the winning 2D-prior hypothesis
-    (reprojection.world_keypoints_2d) when stages.reprojection_part ran, else none -- and the keys then change nothing."""
+    (reprojection.world_keypoints_2d) when stages.reprojection_part ran, else none -- and the keys then change nothing.
+    EXTENSION: `pose_mixture` (a dict {means [K, 69], covars [K, 69, 69], weights [K]} or a path to an .npz / SMPLify-style pickle;
+    body_model.load_pose_mixture) is the Gaussian mixture of stages.{chamfer,marker}.losses.pose_gmm.  It goes to every chamfer
+    and marker solve, the final stage included; without it the config's stages.<stage>.pose_gmm.path counts, and a positive weight
+    with neither is a ValueError."""
     exe = markers_utils.merge_execution(config, execution)
     if visualize_fits:
         raise NotImplementedError("visualize_fits renders with pyrender, not built")
@@ -137,6 +142,10 @@ def multimodal_video_mocap(
     if o_foot_contacts is not None:
         o_foot_contacts = o_foot_contacts.clone().detach().to(device)
     o_keypoints = check_keypoints_2d(keypoints_2d)  # EXTENSION: ValueError before anything is fitted
+    if pose_mixture is not None and not isinstance(pose_mixture, dict):  # EXTENSION: a file is read once, and before anything is fitted
+        from .body_model import load_pose_mixture
+
+        pose_mixture = load_pose_mixture(pose_mixture)
     if o_keypoints is not None and int(o_keypoints["camera"].shape[0]) != int(img_smpl.pose_body.shape[0]):
         raise ValueError("keypoints_2d: one row per video frame expected (%d rows, the video has %d frames)"
                          % (int(o_keypoints["camera"].shape[0]), int(img_smpl.pose_body.shape[0])))
@@ -410,7 +419,7 @@ def multimodal_video_mocap(
                               o_betas=o_betas, root_orient=root_f, trans=trans_f,
                               img_mask=img_mask, smpl_inference=smpl_inference, config=config, initial_angle=0,
                               repeat=1, verbose=verbose, iter_fn=save_iter_fn, foot_contacts=o_foot_contacts,
-                              keypoints_2d=o_keypoints, **placement, **({} if offs is None else {"marker_offsets": offs}))
+                              keypoints_2d=o_keypoints, pose_mixture=pose_mixture, **placement, **({} if offs is None else {"marker_offsets": offs}))
                 offsets_f = offs
                 final_stats.append(optimization.last_stats("marker"))
             root_f = normalize_rot(root_f).clone().detach().requires_grad_(True)
@@ -443,7 +452,7 @@ def multimodal_video_mocap(
                               img_mask=img_mask, smpl_inference=smpl_inference, initial_angle=root_orient_angle,
                               repeat=0, config=config, verbose=verbose, iter_fn=save_iter_fn,
                               foot_contacts=o_foot_contacts, prior_weights=prior_weights["chamfer"],
-                              keypoints_2d=o_keypoints)
+                              keypoints_2d=o_keypoints, pose_mixture=pose_mixture)
                 local["chamfer_stats"] = optimization.last_stats("chamfer")
             local["chamfer"] = _np_dict(trans=trans_angle, root_orient=normalize_rot(z_root), betas=betas_angle[0],
                                         pose_body=normalize_rot(pose_angle))
@@ -462,7 +471,7 @@ def multimodal_video_mocap(
                               img_mask=img_mask, smpl_inference=smpl_inference,
                               config=config, initial_angle=root_orient_angle, repeat=0, verbose=verbose,
                               iter_fn=save_iter_fn, foot_contacts=o_foot_contacts, prior_weights=prior_weights["marker"],
-                              keypoints_2d=o_keypoints, **placement)
+                              keypoints_2d=o_keypoints, pose_mixture=pose_mixture, **placement)
                 local["marker_stats"] = optimization.last_stats("marker")
             if not run_chamfer and not run_marker:
                 # nothing was optimised: the marker-stage record is the chamfer-stage record (both hold the normalised
@@ -536,7 +545,7 @@ def multimodal_video_mocap(
                                   barycentric_coords_one_hot=oh, img_mask=img_mask, smpl_inference=smpl_inference,
                                   config=config, initial_angle=angle, repeat=0, verbose=verbose,
                                   foot_contacts=o_foot_contacts, prior_weights=prior_weights["marker"],
-                                  keypoints_2d=o_keypoints)
+                                  keypoints_2d=o_keypoints, pose_mixture=pose_mixture)
                     all_stats.append(optimization.last_stats("marker"))
             for local, stt in zip(locals_, all_stats):
                 local["marker_stats"] = stt

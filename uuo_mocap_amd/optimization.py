@@ -63,6 +63,7 @@ def optim_chamfer(
     foot_contacts: torch.Tensor = None,
     prior_weights: torch.Tensor = None,
     keypoints_2d: Dict = None,
+    pose_mixture=None,
 ):
     """Chamfer (pose fitting) stage: L-BFGS over [trans, z_angle, betas, pose_body], lr 0.1.  Mutates
     trans / betas / pose_body in place and applies the optimised yaw to root_orient in place.
@@ -73,10 +74,13 @@ def optim_chamfer(
     EXTENSION: `keypoints_2d` ({"camera" [F, 16], "targets" [F, 24, 2], "confidence" [F, 24]}, optional;
     terms.check_keypoints_2d) is the 2D evidence of stages.chamfer.losses.keypoints_2d: a pinhole camera in world axes, image
     targets and confidences for the 24 kinematic joints (without it, or with confidences that weigh nothing, the key changes
-    nothing)."""
+    nothing).
+    EXTENSION: `pose_mixture` (a dict {means [K, 69], covars [K, 69, 69], weights [K]} or a path, optional;
+    body_model.load_pose_mixture) is the Gaussian mixture of stages.chamfer.losses.pose_gmm; without it the config's
+    stages.chamfer.pose_gmm.path counts, and a positive weight with neither is a ValueError."""
     from .parallel import frame_shard
 
-    stage_terms = _stage_terms(config, "chamfer", prior_weights, markers.shape[0], keypoints_2d)
+    stage_terms = _stage_terms(config, "chamfer", prior_weights, markers.shape[0], keypoints_2d, pose_mixture)
     prior_weights = stage_terms.prior_weights
     fs = frame_shard()
     route = stage_route(stage_terms, on_device=markers.is_cuda, sharded=fs is not None and fs.active)
@@ -182,7 +186,7 @@ def _optim_markers_frame_sharded(fs, markers, pose_body, o_pose_body, betas, o_b
     return None
 
 
-def _stage_terms(config: Dict, stage: str, prior_weights, num_frames, keypoints_2d=None) -> StageTerms:
+def _stage_terms(config: Dict, stage: str, prior_weights, num_frames, keypoints_2d=None, pose_mixture=None) -> StageTerms:
     """The stage's EXTENSION terms for one call, parsed once and handed on (terms.StageTerms), with the weights of the pose prior
     as the solvers use them: the block is validated, the table checked on the host (shape, finite, >= 0: ValueError before the
     device is touched); None, or a table of ones, is None -- nothing is armed and every route is the one it was.  The key-point
@@ -191,6 +195,7 @@ def _stage_terms(config: Dict, stage: str, prior_weights, num_frames, keypoints_
     stage_terms[PRIOR]
     stage_terms.prior_weights = armed_weights(check_prior_weights(prior_weights, num_frames))
     stage_terms.arm_keypoints(keypoints_2d, num_frames)
+    stage_terms.arm_pose_mixture(pose_mixture)  # (the pose mixture term's likewise: ValueError when the key has no mixture)
     return stage_terms
 
 
@@ -412,6 +417,7 @@ def optim_markers(
     frame_assign: torch.Tensor = None,
     prior_weights: torch.Tensor = None,
     keypoints_2d: Dict = None,
+    pose_mixture=None,
 ):
     """Marker (inverse kinematics) stage: L-BFGS over [pose_body, betas, root_orient, trans], lr 1.0, with the
     fixed marker -> vertex placement given as a one-hot [M, V] matrix.  Mutates the four leaves in place.
@@ -426,10 +432,11 @@ def optim_markers(
     execution.robust_fused / temporal_fused: False, under frame-block sharding and with shared betas.
     EXTENSION: `prior_weights` ([F, 23] >= 0, optional; engine.prior_weight_table) weigh reg_pose_body per frame and body joint
     (None, or ones everywhere, changes nothing; `img_mask` itself is not read).
-    EXTENSION: `keypoints_2d` (optional): as optim_chamfer's, for stages.marker.losses.keypoints_2d."""
+    EXTENSION: `keypoints_2d` (optional): as optim_chamfer's, for stages.marker.losses.keypoints_2d.
+    EXTENSION: `pose_mixture` (optional): as optim_chamfer's, for stages.marker.losses.pose_gmm."""
     from .parallel import frame_shard, shared_betas_reducer
 
-    stage_terms = _stage_terms(config, "marker", prior_weights, markers.shape[0], keypoints_2d)
+    stage_terms = _stage_terms(config, "marker", prior_weights, markers.shape[0], keypoints_2d, pose_mixture)
     prior_weights = stage_terms.prior_weights
     one_hot = barycentric_coords_one_hot
     if frame_assign is not None:

@@ -83,6 +83,7 @@ def fk_joints_f64(tables: SmplTables, rot: np.ndarray, rest: np.ndarray):
 
 #: the elbow capture (make_sequence(elbow_error=True)): window length, the forearm's turn about the camera's depth axis, taper
 ELBOW_WINDOW, ELBOW_ANGLE, ELBOW_TAPER = 24, 0.5, 2
+OUTLIER_WINDOW, OUTLIER_ANGLE, OUTLIER_TAPER = 24, 1.0, 2  # make_sequence(pose_outlier=True): the left hip's twist
 
 
 #: the self-penetration capture (make_sequence(self_penetration=True)): window length, depth of the HMR start's overlap, taper
@@ -203,13 +204,70 @@ class SyntheticSequence:
     gt: dict
 
 
+def _motion_axis_angles(seed: int, F: int):
+    """The ground-truth motion of make_sequence(seed, num_frames=F): the joints' axis-angle vectors [F, 24, 3] (the root's row is
+    zero: make_sequence builds the root's rotation apart) with their amplitudes, frequencies and phases [24, 3]."""
+    s = 7919 * (seed + 1)
+    t = np.arange(F, dtype=np.float64) / max(F, 1)
+    amp = 0.6 * hash_uniform(s + 1, NUM_JOINTS, 3)
+    amp[0] = 0.0
+    amp[[10, 11, 22, 23]] *= 0.3  # feet / hands move less
+    freq = 0.5 + 2.5 * hash_uniform(s + 2, NUM_JOINTS, 3)
+    phase = 2.0 * np.pi * hash_uniform(s + 3, NUM_JOINTS, 3)
+    aa = amp[None] * np.sin(2.0 * np.pi * freq[None] * t[:, None, None] + phase[None])  # [F,24,3]
+    return aa, amp, freq, phase
+
+
+_POSE_MIXTURES = {}
+
+
+def pose_mixture(K: int = 8, seeds=range(100, 132), num_frames: int = 64):
+    """EXTENSION: a deterministic stand-in for a learned pose mixture (no learned one, SMPLify's gmm_08, is at hand):
+    {"means" [K, 69], "covars" [K, 69, 69], "weights" [K]} in float64 from the ground-truth body poses of
+    make_sequence(seed, num_frames=num_frames) at `seeds`, which the tests and the bench do not fit.  numpy only: theta [N, 69]
+    the axis-angle vectors of joints 1 .. 23, k-means with 20 Lloyd iterations from the start centres theta[i N // K] (an empty
+    cluster keeps its centre), then per cluster the mean, the covariance (about the mean, / n) plus 1e-3 rad^2 on the
+    diagonal, and the share of the samples as weight; a cluster left empty takes its centre, the diagonal alone and the weight
+    of one sample.  The motion's components are independent sines: the mixture can show the pull on an outlier, not the value
+    of a learned mixture's correlations."""
+    key = (int(K), tuple(int(q) for q in seeds), int(num_frames))
+    if key in _POSE_MIXTURES:
+        return {k: v.copy() for k, v in _POSE_MIXTURES[key].items()}
+    K = key[0]
+    if not 1 <= K <= 16:
+        raise ValueError("pose_mixture: 1 .. 16 components (got %d)" % K)
+    theta = np.concatenate([_motion_axis_angles(q, key[2])[0][:, 1:].reshape(key[2], 69) for q in key[1]], axis=0)
+    N = theta.shape[0]
+    if N < K:
+        raise ValueError("pose_mixture: %d poses are fewer than the %d components" % (N, K))
+    centres = theta[[(i * N) // K for i in range(K)]].copy()
+    for _ in range(20):
+        label = np.argmin(((theta[:, None, :] - centres[None]) ** 2).sum(-1), axis=1)
+        for k in range(K):
+            if (label == k).any():
+                centres[k] = theta[label == k].mean(axis=0)
+    label = np.argmin(((theta[:, None, :] - centres[None]) ** 2).sum(-1), axis=1)
+    means, covars, weights = centres.copy(), np.zeros((K, 69, 69)), np.zeros(K)
+    for k in range(K):
+        x = theta[label == k]
+        weights[k] = max(len(x), 1) / float(N)
+        if len(x):
+            means[k] = x.mean(axis=0)
+            d = x - means[k][None]
+            covars[k] = d.T @ d / len(x)
+        covars[k] += 1e-3 * np.eye(69)
+    out = {"means": means, "covars": covars, "weights": weights / weights.sum()}
+    _POSE_MIXTURES[key] = {k: v.copy() for k, v in out.items()}
+    return out
+
+
 def make_sequence(tables: SmplTables, seed: int = 0, num_frames: int = 300, num_markers: int = 50,
                   limb_only: bool = False, yaw_offset_deg: float = 100.0, dropout: float = 0.02,
                   hmr_pose_noise: float = 0.1, hmr_beta_noise: float = 0.5, subject_seed: int = None,
                   standoff_tilt_deg: float = 0.0, standoff_mm=(9.5, 9.5), planted_feet: bool = False,
                   stance_frames: int = 20, identity_events: int = 0, floor: bool = False,
                   self_penetration: bool = False, joint_limits: bool = False,
-                  video_dropout: bool = False, elbow_error: bool = False) -> SyntheticSequence:
+                  video_dropout: bool = False, elbow_error: bool = False, pose_outlier: bool = False) -> SyntheticSequence:
     """One synthetic sequence: smooth GT motion, unlabeled-but-tracked markers 9.5 mm off the
     surface with 1 mm noise and block dropout, and an HMR stand-in (noisy pose/shape, wrong yaw).  `subject_seed` fixes the
     ground-truth shape independently of `seed`: sequences of ONE subject (the shared-betas extension fits them together).
@@ -265,7 +323,14 @@ def make_sequence(tables: SmplTables, seed: int = 0, num_frames: int = 300, num_
     direction of synthetic_camera, so the error lies in its image plane -- (tapered 1/3, 2/3 over two frames at each end), and
     every marker column owned by joints 16, 18, 20 and 22 is blanked (exact zeros): nothing but the prior then holds the arm.
     gt["elbow_window"] = (first frame, one past the last).  No hash stream is consumed; without the option every array is what
-    it was."""
+    it was.
+    A capture whose video start twists a hip (EXTENSION tests of the mixture pose prior): with `pose_outlier`, in a window of
+    OUTLIER_WINDOW = 24 frames starting at F / 10 (rounded up; ValueError if the sequence is shorter) the HMR stand-in's left hip
+    (joint 1) is turned by OUTLIER_ANGLE = 1.0 rad about its own y axis -- twist about the thigh, which no hinge limit, capsule or
+    smoothness term prices -- (tapered 1/3, 2/3 over two frames at each end), and every marker column owned by joints 1, 4, 7 and
+    10 is blanked (exact zeros): nothing but the prior then holds the leg.  gt["outlier_window"] = (first frame, one past the
+    last), gt["hmr_outlier_error"] [F] the geodesic distance (radians) of the stand-in's joint 1 from the truth.  No hash stream
+    is consumed; without the option every array is what it was."""
     F, M = num_frames, num_markers
     if floor and not planted_feet:
         raise ValueError("make_sequence: floor=True needs planted_feet=True (the floor is built under the planted feet)")
@@ -273,12 +338,7 @@ def make_sequence(tables: SmplTables, seed: int = 0, num_frames: int = 300, num_
     t = np.arange(F, dtype=np.float64) / max(F, 1)
 
     # --- ground-truth motion
-    amp = 0.6 * hash_uniform(s + 1, NUM_JOINTS, 3)
-    amp[0] = 0.0
-    amp[[10, 11, 22, 23]] *= 0.3  # feet / hands move less
-    freq = 0.5 + 2.5 * hash_uniform(s + 2, NUM_JOINTS, 3)
-    phase = 2.0 * np.pi * hash_uniform(s + 3, NUM_JOINTS, 3)
-    aa = amp[None] * np.sin(2.0 * np.pi * freq[None] * t[:, None, None] + phase[None])  # [F,24,3]
+    aa, amp, freq, phase = _motion_axis_angles(seed, F)
     if joint_limits:  # (no hash stream: the four limited components of the true motion stay on the allowed side)
         for jj, kk, dd in LIMITED_COMPONENTS:
             aa[:, jj, kk] = dd * np.abs(amp[jj, kk]) * (1.0 + np.sin(2.0 * np.pi * freq[jj, kk] * t + phase[jj, kk]))
@@ -466,6 +526,22 @@ def make_sequence(tables: SmplTables, seed: int = 0, num_frames: int = 300, num_
         arm_cols = np.isin(owner[pick[perm]], [16, 18, 20, 22])
         markers[t0:t0 + ELBOW_WINDOW, arm_cols] = 0.0
 
+    outlier_window = hmr_outlier_error = None
+    if pose_outlier:  # (no hash stream: the HMR hip of the window and the left leg's marker columns there change, nothing else)
+        t0 = -(-F // 10)
+        if t0 + OUTLIER_WINDOW > F:
+            raise ValueError("make_sequence: pose_outlier needs a window of %d frames from frame %d on (F = %d)" % (OUTLIER_WINDOW, t0, F))
+        outlier_window = (t0, t0 + OUTLIER_WINDOW)
+        hmr_rot = hmr_rot.copy()
+        for i in range(OUTLIER_WINDOW):
+            edge = min(i, OUTLIER_WINDOW - 1 - i)
+            taper = 1.0 if edge >= OUTLIER_TAPER else (edge + 1.0) / (OUTLIER_TAPER + 1.0)
+            hmr_rot[t0 + i, 1] = hmr_rot[t0 + i, 1] @ _rodrigues(np.array([0.0, taper * OUTLIER_ANGLE, 0.0]))
+        rel = np.einsum("fab,fac->fbc", rot[:, 1], hmr_rot[:, 1])
+        hmr_outlier_error = np.arccos(np.clip(0.5 * (np.trace(rel, axis1=-2, axis2=-1) - 1.0), -1.0, 1.0))
+        leg_cols = np.isin(owner[pick[perm]], [1, 4, 7, 10])
+        markers[t0:t0 + OUTLIER_WINDOW, leg_cols] = 0.0
+
     f32 = lambda x: torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
     img_mask = torch.ones(F, dtype=torch.bool)
     tracks = {"trans": f32(hmr_trans), "root_orient": f32(hmr_root[:, None]), "pose_body": f32(hmr_rot[:, 1:]),
@@ -527,6 +603,9 @@ def make_sequence(tables: SmplTables, seed: int = 0, num_frames: int = 300, num_
         gt["hmr_gap_error"] = hmr_gap_error
     if elbow_error:
         gt["elbow_window"] = elbow_window
+    if pose_outlier:
+        gt["outlier_window"] = outlier_window
+        gt["hmr_outlier_error"] = hmr_outlier_error
     return SyntheticSequence(img_smpl=img, markers=SyntheticMarkers(markers.astype(np.float32), 30.0), gt=gt)
 
 

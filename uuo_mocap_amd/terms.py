@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import dataclasses
 import math
+import os
 from ctypes import c_float
 from typing import Callable, Dict, Tuple
 
@@ -157,6 +158,84 @@ def stage_joint_limits(config: Dict, stage: str) -> Dict:
                              "lo <= hi, no NaN, lo < +inf and hi > -inf (-.inf / .inf = no bound; got %r)" % (stage, lim))
         lim = {"lo": [[float(q) for q in r] for r in lim["lo"]], "hi": [[float(q) for q in r] for r in lim["hi"]]}
     return {"w": v, "limits": lim}
+
+
+def stage_pose_gmm(config: Dict, stage: str) -> Dict:
+    """EXTENSION: the mixture pose prior of the chamfer or marker stage (uuo_fit_set_pose_gmm) as a config states it --
+    stages.<stage>.losses.pose_gmm (a weight on the mixture's negative log-likelihood, in nats; absent or 0 = off; negative or
+    non-finite weights are refused) and the optional stages.<stage>.pose_gmm: null or {path: null | "synthetic" | a file}:
+    where the mixture comes from when the call passes none (`pose_mixture=`) -- an .npz or SMPLify-style pickle with means,
+    covars, weights (body_model.load_pose_mixture), or "synthetic", the stand-in synthetic.pose_mixture().  Returns {"w",
+    "path", "mixture"}; "mixture" is None until the stage's terms resolve it (StageTerms.arm_pose_mixture).  (The part stage
+    refuses the key with its other unknown losses.)"""
+    v = _weight(config, stage, POSE_GMM.keys[0])
+    blk = config["stages"][stage].get("pose_gmm", None)
+    path = None
+    if blk is not None:
+        what = "stages.%s.pose_gmm" % stage
+        if not isinstance(blk, dict) or set(blk) - {"path"}:
+            raise ValueError("%s must be null or {path} (got %r)" % (what, blk))
+        path = blk.get("path", None)
+        if path is not None and (not isinstance(path, str) or not path):
+            raise ValueError("%s.path must be null, \"synthetic\" or a file name (got %r)" % (what, path))
+    return {"w": v, "path": path, "mixture": None}
+
+
+def check_pose_mixture_arg(pose_mixture):
+    """EXTENSION: a call's `pose_mixture` -- None, a path (body_model.load_pose_mixture) or a dict {means [K, 69], covars
+    [K, 69, 69], weights [K]} -- as body_model.prepare_pose_mixture's float32 (means, chol, offsets), or None.  ValueError
+    before anything touches the device."""
+    if pose_mixture is None:
+        return None
+    from .body_model import load_pose_mixture, prepare_pose_mixture
+
+    if isinstance(pose_mixture, (str, bytes)) or hasattr(pose_mixture, "__fspath__"):
+        pose_mixture = load_pose_mixture(pose_mixture)
+    if not isinstance(pose_mixture, dict) or not {"means", "covars", "weights"} <= set(pose_mixture):
+        raise ValueError("pose_mixture: a path or a dict {means, covars, weights} expected (got %s)" %
+                         (sorted(pose_mixture) if isinstance(pose_mixture, dict) else type(pose_mixture).__name__))
+    return prepare_pose_mixture(pose_mixture["means"], pose_mixture["covars"], pose_mixture["weights"])
+
+
+def resolved_mixture(gmm: Dict, stage: str = "<stage>"):
+    """stage_pose_gmm's record with its mixture in place: the call's (arm_pose_mixture), else the config's path.  A positive
+    weight with neither is a ValueError."""
+    if gmm["mixture"] is None and float(gmm["w"]) > 0.0:
+        if gmm["path"] is None:
+            raise ValueError("stages.%s.losses.pose_gmm: a positive weight needs a mixture -- pass pose_mixture= (a dict {means, "
+                             "covars, weights} or a path) to multimodal_video_mocap / optim_chamfer / optim_markers, or name one in "
+                             "the config (stages.%s.pose_gmm: {path: FILE | synthetic})" % (stage, stage))
+        gmm["mixture"] = _mixture_of_path(gmm["path"])
+    return gmm["mixture"]
+
+
+#: the prepared mixtures of the config paths seen so far: every optim_chamfer / optim_markers call parses its config anew, and
+#: reading and factoring a file (an inverse and a Cholesky per component) once per solve would be paid by every fit.  A file is
+#: keyed by its path, size and modification time, so a rewritten file is read again.
+_PATH_MIXTURES = {}
+
+
+def _mixture_of_path(path: str):
+    """The prepared (means, chol, offsets) of stages.<stage>.pose_gmm.path: "synthetic" or a file, read and factored once."""
+    if path == "synthetic":
+        key = ("synthetic",)
+    else:
+        try:
+            st = os.stat(path)
+            key = (os.path.abspath(path), st.st_size, st.st_mtime_ns)
+        except OSError:
+            key = None  # (load_pose_mixture names the file and the fault)
+    if key is None or key not in _PATH_MIXTURES:
+        if path == "synthetic":
+            from .synthetic import pose_mixture
+
+            mixture = check_pose_mixture_arg(pose_mixture())
+        else:
+            mixture = check_pose_mixture_arg(path)
+        if key is None:
+            return mixture
+        _PATH_MIXTURES[key] = mixture
+    return _PATH_MIXTURES[key]
 
 
 def stage_pose_accel(config: Dict, stage: str) -> Dict:
@@ -428,6 +507,15 @@ def _set_joint_limits(p, lim, contacts, weights, keypoints, smpl_inference):
     p.lim_w = float(lim["w"])
 
 
+def _set_pose_gmm(p, gmm, contacts, weights, keypoints, smpl_inference):
+    """Keeps the weight and the three HOST arrays of the prepared mixture (float32: means [K, 69], factors [K, 69, 69],
+    offsets [K]), which the library checks and copies at the call.  With weight 0 nothing is armed."""
+    if float(gmm["w"]) == 0.0:
+        return
+    p.gmm_means, p.gmm_chol, p.gmm_offsets = resolved_mixture(gmm, "chamfer" if p.stage == 0 else "marker")
+    p.gmm_w = float(gmm["w"])
+
+
 def _set_prior_weights(p, block, contacts, weights, keypoints, smpl_inference):
     """`weights` is check_prior_weights' host tensor (or None); what armed_weights leaves of it goes to the device, where the
     library reads it at every evaluation."""
@@ -499,6 +587,15 @@ def _composed_limits(lim, losses, contacts, smpl_inference, keypoints=None):
         return None
     lo, hi = limit_tables(lim)
     return "rot_body", lambda rot_body: joint_limit_loss(rot_body, lo, hi, lim["w"])
+
+
+def _composed_pose_gmm(gmm, losses, contacts, smpl_inference, keypoints=None):
+    from .losses import pose_gmm_loss
+
+    if gmm["w"] == 0.0:
+        return None
+    means, chol, offsets = resolved_mixture(gmm)
+    return "rot_body", lambda rot_body: pose_gmm_loss(rot_body, means, chol, offsets, gmm["w"])
 
 
 def _composed_pose_accel(pacc, losses, contacts, smpl_inference, keypoints=None):
@@ -635,6 +732,16 @@ LIMITS = Term(
     on_args=lambda p: (c_float(p.lim_w), p.lim_lo.ctypes.data, p.lim_hi.ctypes.data),
     sharded="stages.%s.losses.joint_limits (extension): the joint-angle limit term is not built for " + _SHARDING,
     soft=_SOFT % "joint-angle limit term (joint_limits)", composed=_composed_limits)
+POSE_GMM = Term(
+    "the pose mixture term", stage_pose_gmm, lambda r: r["w"] > 0.0, keys=("pose_gmm",), switch="pose_gmm_fused",
+    flag="pose_gmm_on",
+    # the three HOST arrays of the prepared mixture: [K, 69], [K, 69, 69], [K] float32 numpy
+    state={"gmm_w": 0.0, "gmm_means": None, "gmm_chol": None, "gmm_offsets": None},
+    set=_set_pose_gmm, setter="uuo_fit_set_pose_gmm", off_args=(c_float(0.0), 0, None, None, None),
+    on_args=lambda p: (c_float(p.gmm_w), int(p.gmm_means.shape[0]), p.gmm_means.ctypes.data, p.gmm_chol.ctypes.data,
+                       p.gmm_offsets.ctypes.data),
+    sharded="stages.%s.losses.pose_gmm (extension): the pose mixture term is not built for " + _SHARDING,
+    soft=_SOFT % "pose mixture term (pose_gmm)", composed=_composed_pose_gmm)
 PRIOR = Term(
     "the pose prior's weights", stage_prior_confidence, lambda blk: blk is not None, label="prior_confidence",
     switch="prior_conf_fused", flag="prior_conf_on", state={"prior_weights": None},  # [F, 23] float32 on the device
@@ -664,9 +771,9 @@ POSE_ACCEL = Term(
 
 #: one row per extension term.  The order is that of the library calls in _StageProblem._arm, of the refusals of
 #: engine.solve_batch and of the sharded solves, and of the terms in the composed closures' sum
-TERMS = (ROBUST, JOINT_ACCEL, LATENT_OFFSETS, FOOT_LOCK, FLOOR, CAPSULES, LIMITS, PRIOR, KEYPOINTS, POSE_ACCEL)
+TERMS = (ROBUST, JOINT_ACCEL, LATENT_OFFSETS, FOOT_LOCK, FLOOR, CAPSULES, LIMITS, POSE_GMM, PRIOR, KEYPOINTS, POSE_ACCEL)
 #: the order in which a stage problem's constructor looks at the terms that can refuse it (that of its refusals, kept)
-PROBLEM_ORDER = (CAPSULES, LIMITS, POSE_ACCEL, JOINT_ACCEL, FOOT_LOCK, FLOOR)
+PROBLEM_ORDER = (CAPSULES, LIMITS, POSE_ACCEL, JOINT_ACCEL, FOOT_LOCK, FLOOR, POSE_GMM)
 
 #: the reference's own loss keys of the fused closures, the data terms the chamfer stage has beside them (extensions with a
 #: switch of their own: execution.chamfer_soft_fused / surface_fused), and the reference's optional chamfer-stage terms
@@ -709,6 +816,15 @@ class StageTerms:
         if record is not None:
             self.keypoints = armed_keypoints(check_keypoints_2d(record, num_frames), kp)
         return self.keypoints
+
+    def arm_pose_mixture(self, pose_mixture=None):
+        """The call's `pose_mixture` (a dict {means, covars, weights} or a path; None: the config's stages.<stage>.pose_gmm.path,
+        or what an earlier call armed), checked and prepared on the host.  With the key on, a mixture must come from one of the
+        two: ValueError otherwise.  Returns the prepared (means, chol, offsets) or None."""
+        gmm = self[POSE_GMM]
+        if pose_mixture is not None:
+            gmm["mixture"] = check_pose_mixture_arg(pose_mixture)
+        return resolved_mixture(gmm, self.stage) if self.on(POSE_GMM) else None
 
     def __getitem__(self, term: Term):
         if term not in self._records:

@@ -1,10 +1,17 @@
 """EXTENSION: float64 restatement of the 2D key-point reprojection term (losses.keypoints_2d_loss, uuo_fit_set_keypoints2d,
 DESIGN.md section 4y) on joint positions.  The gradient comes from autograd; the closed form of the definition is restated beside
-it in numpy, pair by pair, so that tests can hold the one against the other.  No GPU, no package code."""
+it in numpy, pair by pair, so that tests can hold the one against the other; then what the GPU parity checks of this and of later
+terms share: the config keys, the float32 record and the term's gradient on the leaves of a float64 forward.  No GPU, no package
+code."""
+import copy
+
 import numpy as np
 import torch
 
+from stage_ref64 import _float64
+
 NJ = 24
+MIN_DEPTH = 0.1
 
 
 def gmof64(s, sigma):
@@ -113,3 +120,36 @@ def evidence(J, seed, noise=6.0, zero_every=7, **camera):
     if zero_every:
         conf.reshape(-1)[::zero_every] = 0.0
     return {"camera": cam, "targets": y, "confidence": conf}
+
+
+# ------------------------------------------------------------------------------------------------ for the GPU parity checks
+def _with_key(cfg, w_chamfer, w_marker, sigma=0.0, joint_weights=None, block=True):
+    cfg = copy.deepcopy(cfg)
+    for stage, w in (("chamfer", w_chamfer), ("marker", w_marker)):
+        cfg["stages"][stage]["losses"]["keypoints_2d"] = w
+        if block:
+            cfg["stages"][stage]["keypoints_2d"] = {"sigma": sigma, "min_depth": MIN_DEPTH, "joint_weights": joint_weights}
+    return cfg
+
+
+def _record(J, seed, **kw):
+    """evidence for float64 joints J, rounded to the float32 values the device reads"""
+    return {k: v.float() for k, v in evidence(np.asarray(J, dtype=np.float64), seed, **kw).items()}
+
+
+def _kp_grad(leaves, out, rec, w, sigma, pad=0):
+    """loss and flat gradient (numpy) of the float64 term on the leaves of a float64 forward, zero-padded by `pad` entries; the
+    float64 preconditions of the issue are asserted first: every joint's depth >= 1, no confidence within 1e-4 of 0 but the
+    exact zeros, no depth within 1e-4 of min_depth"""
+    with _float64():
+        cam, y, c = (rec[k].double() for k in ("camera", "targets", "confidence"))
+        J = out["joints"][:, :24]
+        p, _ = project64(J.detach(), cam)
+        assert float(p[..., 2].min()) >= 1.0, "a joint nearer than 1 to the camera: pick another seed"
+        assert float((p[..., 2] - MIN_DEPTH).abs().min()) >= 1e-4 and not bool(((c > 0) & (c < 1e-4)).any()), \
+            "a depth within 1e-4 of min_depth or a confidence within 1e-4 of 0: pick another seed"
+        assert bool((c == 0).any()) and bool((c > 0).any()), "the record needs exact-zero and positive confidences"
+        loss = keypoints2d64(J, cam, y, c, w, sigma, MIN_DEPTH)
+        grads = torch.autograd.grad(loss, leaves, allow_unused=True, retain_graph=True)  # (the capsules' term follows on `out`)
+    g = torch.cat([(torch.zeros_like(t) if gi is None else gi).reshape(-1) for t, gi in zip(leaves, grads)]).numpy()
+    return float(loss.detach()), np.concatenate([g, np.zeros(pad)])

@@ -19,28 +19,15 @@ import os
 
 import numpy as np
 import pytest
-import torch
 
 pytestmark = pytest.mark.gpu
 
+from gpu_support import dev, smpl  # noqa: E402,F401
 from oracle import p3d_ref, stages_ref  # noqa: E402
 from uuo_mocap_amd.config import packaged_config  # noqa: E402
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 CASES = ["e2e_config0", "e2e_config1", "e2e_hmr_part", "e2e_mht_rotation", "e2e_headline_300x50"]
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def smpl(tables, dev):
-    from uuo_mocap_amd.smpl import SmplInference
-
-    return SmplInference(dev, tables=tables)
 
 
 def _load(case):

@@ -1,33 +1,26 @@
 """EXTENSION: the floor-contact term on sole vertices (stages.{chamfer,marker}.losses.floor_penetration / floor_contact,
 uuo_fit_set_floor) on the MI355X -- the fused closures against float64 autograd, the term switched off, the compact packing,
 the operator-composed route, the refusals, and what video_mocap_floor.yaml buys on a capture with a floor."""
-import copy
 import threading
 
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as Fn
 
 pytestmark = pytest.mark.gpu
 
-from oracle import stages_ref  # noqa: E402
-from test_gpu_foot_lock import _lock64, _marker_x  # noqa: E402
-from test_gpu_marker_offsets import _skin64  # noqa: E402  (float64 torch SMPL at picked vertices, with T_R for the offsets)
-from test_gpu_temporal import (_accel64, _d64, _float64, _inputs, _rel_err, _rho, _three_corners, dev, smpl,  # noqa: E402,F401
-                               smpl64)
+from floor_ref64 import _contacts, _planes, _vids  # noqa: E402
+from gpu_support import (W_ACCEL_C, W_ACCEL_M, W_FLOOR_C as W_CHAMFER, W_FLOOR_M as W_MARKER, W_LOCK_C, W_LOCK_M,  # noqa: E402,F401
+                         W_OFFS, _fit_points as _fit, _inputs, _makers_contacts as _makers, _marker_x, _rel_err, _three_corners,
+                         dev, smpl, smpl64)
+from stage_ref64 import _heights64, ref_chamfer64 as _ref_chamfer, ref_marker64 as _ref_marker  # noqa: E402
 from uuo_mocap_amd.body_model import sole_vertices  # noqa: E402
 from uuo_mocap_amd.config import packaged_config  # noqa: E402
-from uuo_mocap_amd.synthetic import SyntheticMarkers, make_sequence  # noqa: E402
+from uuo_mocap_amd.synthetic import make_sequence  # noqa: E402
 
-# weights of the parity checks.  The plane is put through the middle of the sole heights (below), so about half the points
-# penetrate by centimetres: d loss / d z = 2 w pen / (F K) is then of the size of the data term's 2 w_data d / F per frame at
-# these weights, and the check that the term matters (> 1e-2 of the gradient) is met with a wide margin.
-W_CHAMFER, W_MARKER = 100.0, 10.0
-W_ACCEL_C, W_ACCEL_M = 10.0, 1.0   # test_gpu_temporal's
-W_LOCK_C, W_LOCK_M = 100.0, 10.0   # test_gpu_foot_lock's
-W_OFFS = 2.0                       # test_gpu_marker_offsets'
-KINK = 1e-4                        # metres every sole height keeps from the plane, and a foot's two lowest points from each other
+# W_CHAMFER, W_MARKER (100, 10), the weights of the parity checks.  The plane is put through the middle of the sole heights (below),
+# so about half the points penetrate by centimetres: d loss / d z = 2 w pen / (F K) is then of the size of the data term's
+# 2 w_data d / F per frame at these weights, and the check that the term matters (> 1e-2 of the gradient) is met with a wide margin.
 
 
 def _points(tables, K):
@@ -36,10 +29,6 @@ def _points(tables, K):
         return None
     sv = sole_vertices(tables, per_foot=K // 2)
     return [[int(v) for v in sv[0]], [int(v) for v in sv[1]]]
-
-
-def _vids(tables, K):
-    return torch.from_numpy(sole_vertices(tables, per_foot=K // 2).reshape(-1).copy()).long()
 
 
 def _cfg(tables=None, K=6, w_chamfer=0.0, w_marker=0.0, h_chamfer=0.0, h_marker=0.0, sigma=0.0, temporal=False, offs=False,
@@ -64,160 +53,10 @@ def _cfg(tables=None, K=6, w_chamfer=0.0, w_marker=0.0, h_chamfer=0.0, h_marker=
     return cfg
 
 
-def _contacts(F, seed):
-    """Hashed labels in [0, 1] with some exact 0s and 1s"""
-    gen = torch.Generator().manual_seed(2000 + seed)
-    c = torch.rand(F, 2, generator=gen)
-    c[0, 0] = 1.0
-    if F >= 3:
-        c[1, 1] = 0.0
-        c[F - 1, 1] = 1.0
-    if F >= 7:
-        n = max(2, F // 5)
-        c[F // 3:F // 3 + n, 0] = 0.0
-    return c
-
-
-def _floor64(z, k_left, c, h, w_pen, w_con):
-    """The issue's formula, float64 torch, on sole heights z [F, K]; the argmin is the first in list order"""
-    F, K = z.shape
-    pen = torch.relu(h - z)
-    loss = w_pen * (pen * pen).sum() / (F * K)
-    for s, zs in enumerate((z[:, :k_left], z[:, k_left:])):
-        am = torch.from_numpy(np.argmin(zs.detach().numpy(), axis=1))  # numpy: the first occurrence
-        flo = torch.relu(zs.gather(1, am[:, None])[:, 0] - h)
-        loss = loss + w_con * (c[:, s].double() * flo * flo).sum() / (2.0 * F)
-    return loss
-
-
-def _chamfer_forward64(smpl64, x, root, F):
-    leaves = [t.clone().requires_grad_(True) for t in (x[:3 * F].reshape(F, 3), x[3 * F:4 * F].reshape(F, 1, 1),
-                                                      x[4 * F:4 * F + 10].reshape(1, 10), x[4 * F + 10:].reshape(F, 23, 3, 3))]
-    trans, z, betas, pose = leaves
-    z_root = stages_ref.compute_root_orient_z(z) @ root
-    out = stages_ref._smpl_repeat_betas(smpl64, stages_ref.normalize_rot(pose), betas, stages_ref.normalize_rot(z_root), trans)
-    return leaves, out
-
-
-def _marker_forward64(smpl64, x, F):
-    n0 = 219 * F + 10
-    leaves = [t.clone().requires_grad_(True) for t in (x[:207 * F].reshape(F, 23, 3, 3), x[207 * F:207 * F + 10].reshape(1, 10),
-                                                      x[207 * F + 10:216 * F + 10].reshape(F, 1, 3, 3), x[216 * F + 10:n0].reshape(F, 3))]
-    pose, betas, root, trans = leaves
-    out = stages_ref._smpl_repeat_betas(smpl64, stages_ref.normalize_rot(pose), betas, stages_ref.normalize_rot(root), trans)
-    return leaves, out
-
-
-def _plane(z, k_left, c):
-    """The plane of a parity case from the float64 sole heights z [F, K]: the midpoint of the widest gap of the sorted heights
-    between their 30th and 70th percentile.  Asserts (float64, before anything is compared) that every height keeps KINK from
-    the plane and every foot's two lowest points KINK from each other, and that both pieces of the term are active."""
-    s = np.sort(z.reshape(-1))
-    n = len(s)
-    lo, hi = int(np.floor(0.3 * (n - 1))), int(np.ceil(0.7 * (n - 1)))
-    gaps = np.diff(s[lo:hi + 1])
-    i = int(np.argmax(gaps))
-    h = 0.5 * (s[lo + i] + s[lo + i + 1])
-    assert np.abs(z - h).min() >= KINK, "a sole height within 1e-4 m of the plane: pick another seed"
-    for zs in (z[:, :k_left], z[:, k_left:]):
-        if zs.shape[1] >= 2:
-            two = np.sort(zs, axis=1)[:, :2]
-            assert (two[:, 1] - two[:, 0]).min() >= KINK, "a foot's two lowest points within 1e-4 m: pick another seed"
-    low = np.stack([z[:, :k_left].min(axis=1), z[:, k_left:].min(axis=1)], axis=1)
-    assert (z < h).any() and ((low > h) & (c.numpy() > 0)).any(), "the term is not active"
-    return float(h)
-
-
-def _heights64(smpl64, pose, betas, root, trans, vids, z=None):
-    """float64 sole heights [F, K] of the body at (pose, betas, root, trans) -- the marker stage's parameters, or with the yaw
-    angles `z` the chamfer stage's (root = Rz(z) root)"""
-    with _float64(), torch.no_grad():
-        pose, betas, root, trans = _d64(pose, betas, root, trans)
-        if z is not None:
-            root = stages_ref.compute_root_orient_z(z.detach().cpu().double()) @ root
-        out = stages_ref._smpl_repeat_betas(smpl64, stages_ref.normalize_rot(pose), betas, stages_ref.normalize_rot(root), trans)
-        return out["vertices"][:, vids, 2].numpy()
-
-
-def _planes(smpl64, tables, F, M, K, seed):
-    """(chamfer plane, marker plane) of the parity case (F, M, K, seed): host only, so that seeds can be checked without a GPU"""
-    _, _, _, _, root, _, (tp, zp, bp, pp, rp) = _inputs(tables, F, seed, num_markers=M)
-    contacts, vids = _contacts(F, seed), _vids(tables, K)
-    return (_plane(_heights64(smpl64, pp, bp, root, tp, vids, z=zp), K // 2, contacts),
-            _plane(_heights64(smpl64, pp, bp, rp, tp, vids), K // 2, contacts))
-
-
 def _median_plane(smpl64, tables, pose, betas, root, trans, q=50.0):
     """a plane through the default sole points' heights at these parameters, at their q-th percentile (the median: half the
     points penetrate and the other half hover): both pieces of the term are on"""
     return float(np.percentile(_heights64(smpl64, pose, betas, root, trans, _vids(tables, 6)), q))
-
-
-def _ref_chamfer(smpl64, cfg, markers, o_pose, o_betas, root, x, nn, contacts, vids, k_left):
-    F = markers.shape[0]
-    st = cfg["stages"]["chamfer"]
-    w, sigma = st["losses"], float(st.get("robust_sigma", 0.0))
-    with _float64():
-        markers, o_pose, o_betas, root = _d64(markers, o_pose, o_betas, root)
-        leaves, out = _chamfer_forward64(smpl64, x.detach().cpu().double(), root, F)
-        trans, z, betas, pose = leaves
-        vn = torch.gather(out["vertices"], 1, nn.cpu().long()[..., None].expand(-1, -1, 3))
-        mask = stages_ref.get_marker_mask(markers).double()
-        d2 = ((markers - vn) ** 2).sum(-1)
-        loss = (mask * _rho(d2, sigma)).sum() / mask.sum() * w["full_chamfer"] + \
-            Fn.mse_loss(pose, o_pose) * w["reg_pose_body"] + Fn.mse_loss(betas, o_betas) * w["reg_betas"] + \
-            _accel64(out["joints"]) * w.get("joint_accel", 0.0) + _lock64(out["joints"][:, :24], contacts) * w.get("foot_lock", 0.0) + \
-            _floor64(out["vertices"][:, vids, 2], k_left, contacts, float(st["floor_height"]), w.get("floor_penetration", 0.0),
-                     w.get("floor_contact", 0.0))
-        loss.backward()
-    return float(loss.detach()), torch.cat([t.grad.reshape(-1) for t in leaves]).numpy()
-
-
-def _ref_marker(smpl64, tables, cfg, markers, o_pose, o_betas, x, assign, bary, contacts, vids, k_left, M):
-    from uuo_mocap_amd.engine import MARKER_DISTANCE
-
-    F = markers.shape[0]
-    st = cfg["stages"]["marker"]
-    w, sigma = st["losses"], float(st.get("robust_sigma", 0.0))
-    w_offs = float(w.get("latent_offsets", 0.0))
-    n0 = 219 * F + 10
-    with _float64():
-        x = x.detach().cpu().double()
-        markers, o_pose, o_betas = _d64(markers, o_pose, o_betas)
-        a = assign.cpu().long()
-        mask = stages_ref.get_marker_mask(markers).double()
-        if w_offs:
-            leaves = [t.clone().requires_grad_(True) for t in (x[:207 * F].reshape(F, 23, 3, 3), x[207 * F:207 * F + 10].reshape(1, 10),
-                                                              x[207 * F + 10:216 * F + 10].reshape(F, 1, 3, 3), x[216 * F + 10:n0].reshape(F, 3))]
-            pose, betas, root, trans = leaves
-            offs = x[n0:].reshape(M, 3).clone().requires_grad_(True)
-            leaves.append(offs)
-            rot = torch.cat([stages_ref.normalize_rot(root), stages_ref.normalize_rot(pose)], dim=1)
-            a2 = a.reshape(M, -1)
-            K = a2.shape[1]
-            vp, T_R, T_t, joints = _skin64(tables, rot, betas, trans, torch.cat([a2.reshape(-1), vids]))
-            nk = M * K
-            pts = vp[:, :nk].reshape(F, M, K, 3) + offs[None, :, None]
-            vk = torch.einsum("fmkab,fmkb->fmka", T_R[:, :nk].reshape(F, M, K, 3, 3), pts) + T_t[:, :nk].reshape(F, M, K, 3)
-            b = torch.ones(M, 1) if bary is None else bary.cpu().double()
-            vm = (vk * b[None, :, :, None]).sum(2)
-            data = torch.mean(_rho(((markers - vm) ** 2).sum(-1), sigma) * mask)
-            prior = torch.mean((offs.norm(dim=1) - MARKER_DISTANCE) ** 2) * w_offs
-            sole_z = (torch.einsum("fkab,fkb->fka", T_R[:, nk:], vp[:, nk:]) + T_t[:, nk:])[..., 2]  # (no offset on a sole point)
-        else:
-            leaves, out = _marker_forward64(smpl64, x, F)
-            pose, betas, root, trans = leaves
-            v, joints = out["vertices"], out["joints"][:, :24]
-            vm = v[:, a] if bary is None else (v[:, a] * bary.cpu().double()[None, :, :, None]).sum(2)
-            e = torch.norm(markers - vm, dim=-1) - MARKER_DISTANCE
-            data = torch.mean(_rho(e ** 2, sigma) * mask)
-            prior = 0.0
-            sole_z = v[:, vids, 2]
-        loss = data * w["marker"] + Fn.mse_loss(pose, o_pose) * w["reg_pose_body"] + Fn.mse_loss(betas, o_betas) * w["reg_betas"] + \
-            prior + _accel64(joints) * w.get("joint_accel", 0.0) + _lock64(joints, contacts) * w.get("foot_lock", 0.0) + \
-            _floor64(sole_z, k_left, contacts, float(st["floor_height"]), w.get("floor_penetration", 0.0), w.get("floor_contact", 0.0))
-        loss.backward()
-    return float(loss.detach()), torch.cat([t.grad.reshape(-1) for t in leaves]).numpy()
 
 
 # settings toggled off and on: (sigma, joint_accel + foot_lock, latent_offsets)
@@ -301,19 +140,6 @@ def test_floor_closures_match_float64_autograd_300_frames(smpl, smpl64, tables, 
 
 
 # ------------------------------------------------------------------------------------------------ 2. off is off
-def _makers(smpl, dev, md, o_pose, o_betas, root, vids, i3, b3, pert):
-    from uuo_mocap_amd.engine import ChamferProblem, MarkerProblem
-
-    tp, zp, bp, pp, rp = pert
-    a = (md, o_pose.to(dev), o_betas.to(dev))
-    return {
-        "chamfer": (lambda c, fc: ChamferProblem(smpl, *a, root.to(dev), c, foot_contacts=fc),
-                    lambda p: p.pack(tp.to(dev), zp.to(dev), bp.to(dev), pp.to(dev))),
-        "marker": (lambda c, fc: MarkerProblem(smpl, *a, vids.to(dev), c, foot_contacts=fc),
-                   lambda p: p.pack(pp.to(dev), bp.to(dev), rp.to(dev), tp.to(dev))),
-        "marker3": (lambda c, fc: MarkerProblem(smpl, *a, i3.to(dev), c, bary=b3.to(dev), foot_contacts=fc),
-                    lambda p: p.pack(pp.to(dev), bp.to(dev), rp.to(dev), tp.to(dev))),
-    }
 
 
 def test_off_is_off_and_on_is_deterministic(smpl, smpl64, tables, dev):
@@ -532,15 +358,6 @@ def test_library_and_routes_refuse_the_term_where_it_is_not_built(smpl, tables, 
 
 
 # ------------------------------------------------------------------------------------------------ 6. what it buys
-def _fit(seq, points, cfg_name, smpl, dev, iters=None):
-    from uuo_mocap_amd.multimodal import multimodal_video_mocap
-
-    cfg = packaged_config(cfg_name)
-    if iters is not None:
-        for k in ("chamfer", "marker", "part"):
-            cfg["stages"][k]["num_iters"] = iters
-    return multimodal_video_mocap(copy.deepcopy(seq.img_smpl), SyntheticMarkers(points.copy(), 30.0), dev, cfg, offset=0,
-                                  print_options=[], save_stages=False, smpl_inference=smpl)
 
 
 def _quality(out, seq, oracle_smpl):

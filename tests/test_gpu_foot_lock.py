@@ -7,144 +7,20 @@ import threading
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as Fn
 
 pytestmark = pytest.mark.gpu
 
-from oracle import stages_ref  # noqa: E402
-from test_gpu_marker_offsets import _skin64  # noqa: E402  (float64 torch SMPL at picked vertices, with T_R for the offsets)
-from test_gpu_temporal import (_accel64, _d64, _float64, _inputs, _rel_err, _rho, _three_corners, dev, smpl,  # noqa: E402,F401
-                               smpl64)
+from foot_lock_ref64 import _cfg, _contacts  # noqa: E402
+from gpu_support import (W_LOCK_C as W_CHAMFER, W_LOCK_M as W_MARKER, _fit_points as _fit, _inputs,  # noqa: E402,F401
+                         _makers_contacts as _makers, _marker_x, _rel_err, _three_corners, dev, smpl, smpl64)
+from stage_ref64 import ref_chamfer64 as _ref_chamfer, ref_marker64 as _ref_marker  # noqa: E402
 from uuo_mocap_amd.config import packaged_config  # noqa: E402
 from uuo_mocap_amd.synthetic import SyntheticMarkers, make_sequence  # noqa: E402
 
 M = 50
-# weights of the parity checks.  At the inputs below (translation perturbed by 2 cm a frame, so feet that move ~3 cm a frame
-# and data residuals of ~2 cm) the term's gradient on the translation, 2 w g v / (6 (F - 1)), is then of the size of the data
-# term's, 2 w_data d / F: the check that the term matters (> 1e-2 of the gradient) is met with a wide margin.
-W_CHAMFER, W_MARKER = 100.0, 10.0
-W_ACCEL_C, W_ACCEL_M = 10.0, 1.0   # test_gpu_temporal's
-W_OFFS = 2.0                       # test_gpu_marker_offsets'
-
-
-def _cfg(w_chamfer=0.0, w_marker=0.0, sigma=0.0, accel=False, offs=False):
-    cfg = packaged_config("video_mocap")
-    if w_chamfer is not None:
-        cfg["stages"]["chamfer"]["losses"]["foot_lock"] = w_chamfer
-    if w_marker is not None:
-        cfg["stages"]["marker"]["losses"]["foot_lock"] = w_marker
-    if accel:
-        cfg["stages"]["chamfer"]["losses"]["joint_accel"] = W_ACCEL_C
-        cfg["stages"]["marker"]["losses"]["joint_accel"] = W_ACCEL_M
-    if offs:
-        cfg["stages"]["marker"]["losses"]["latent_offsets"] = W_OFFS
-    for k in ("chamfer", "part", "marker"):
-        cfg["stages"][k]["robust_sigma"] = sigma
-    return cfg
-
-
-def _contacts(F, seed):
-    """Random fractional labels in [0, 1] with runs of zeros (from F = 7 on; shorter sequences keep every gate open)."""
-    gen = torch.Generator().manual_seed(1000 + seed)
-    c = torch.rand(F, 2, generator=gen)
-    if F >= 7:
-        n = max(2, F // 5)
-        c[F // 3:F // 3 + n, 0] = 0.0
-        c[F - n - 1:F - 1, 1] = 0.0
-        c[0, 1] = 1.0
-    return c
-
-
-def _lock64(joints, c):
-    """The issue's formula, float64 torch: sum_t sum_s g[t, s] |v[t, s]|^2 / ((F - 1) 6)."""
-    F = joints.shape[0]
-    if F < 2:
-        return joints.sum() * 0.0
-    c = c.double()
-    v = joints[1:, 10:12] - joints[:-1, 10:12]
-    g = c[1:] * c[:-1]
-    return (g[..., None] * v * v).sum() / ((F - 1) * 6.0)
-
-
-def _ref_chamfer(smpl64, cfg, markers, o_pose, o_betas, root, x, nn, contacts):
-    F = markers.shape[0]
-    st = cfg["stages"]["chamfer"]
-    w, sigma = st["losses"], float(st.get("robust_sigma", 0.0))
-    with _float64():
-        x = x.detach().cpu().double()
-        markers, o_pose, o_betas, root = _d64(markers, o_pose, o_betas, root)
-        leaves = [t.clone().requires_grad_(True) for t in (x[:3 * F].reshape(F, 3), x[3 * F:4 * F].reshape(F, 1, 1),
-                                                          x[4 * F:4 * F + 10].reshape(1, 10), x[4 * F + 10:].reshape(F, 23, 3, 3))]
-        trans, z, betas, pose = leaves
-        z_root = stages_ref.compute_root_orient_z(z) @ root
-        out = stages_ref._smpl_repeat_betas(smpl64, stages_ref.normalize_rot(pose), betas, stages_ref.normalize_rot(z_root),
-                                            trans)
-        vn = torch.gather(out["vertices"], 1, nn.cpu().long()[..., None].expand(-1, -1, 3))
-        mask = stages_ref.get_marker_mask(markers).double()
-        d2 = ((markers - vn) ** 2).sum(-1)
-        loss = (mask * _rho(d2, sigma)).sum() / mask.sum() * w["full_chamfer"] + \
-            Fn.mse_loss(pose, o_pose) * w["reg_pose_body"] + Fn.mse_loss(betas, o_betas) * w["reg_betas"] + \
-            _accel64(out["joints"]) * w.get("joint_accel", 0.0) + _lock64(out["joints"][:, :24], contacts) * w["foot_lock"]
-        loss.backward()
-    return float(loss.detach()), torch.cat([t.grad.reshape(-1) for t in leaves]).numpy()
-
-
-def _ref_marker(smpl64, tables, cfg, markers, o_pose, o_betas, x, assign, bary, contacts, num_markers=M):
-    """Marker stage in float64 autograd: through the float64 SmplInference without the latent offsets, through the float64
-    skinning restatement of the offsets' tests (which has the blended rotations the offsets need) with them."""
-    M = num_markers
-    from uuo_mocap_amd.engine import MARKER_DISTANCE
-
-    F = markers.shape[0]
-    st = cfg["stages"]["marker"]
-    w, sigma = st["losses"], float(st.get("robust_sigma", 0.0))
-    w_offs = float(w.get("latent_offsets", 0.0))
-    n0 = 219 * F + 10
-    with _float64():
-        x = x.detach().cpu().double()
-        markers, o_pose, o_betas = _d64(markers, o_pose, o_betas)
-        leaves = [t.clone().requires_grad_(True) for t in (x[:207 * F].reshape(F, 23, 3, 3), x[207 * F:207 * F + 10].reshape(1, 10),
-                                                          x[207 * F + 10:216 * F + 10].reshape(F, 1, 3, 3), x[216 * F + 10:n0].reshape(F, 3))]
-        pose, betas, root, trans = leaves
-        a = assign.cpu().long()
-        mask = stages_ref.get_marker_mask(markers).double()
-        if w_offs:
-            offs = x[n0:].reshape(M, 3).clone().requires_grad_(True)
-            leaves.append(offs)
-            rot = torch.cat([stages_ref.normalize_rot(root), stages_ref.normalize_rot(pose)], dim=1)
-            a2 = a.reshape(M, -1)
-            K = a2.shape[1]
-            vp, T_R, T_t, joints = _skin64(tables, rot, betas, trans, a2.reshape(-1))
-            pts = vp.reshape(F, M, K, 3) + offs[None, :, None]
-            vk = torch.einsum("fmkab,fmkb->fmka", T_R.reshape(F, M, K, 3, 3), pts) + T_t.reshape(F, M, K, 3)
-            b = torch.ones(M, 1) if bary is None else bary.cpu().double()
-            vm = (vk * b[None, :, :, None]).sum(2)
-            data = torch.mean(_rho(((markers - vm) ** 2).sum(-1), sigma) * mask)
-            prior = torch.mean((offs.norm(dim=1) - MARKER_DISTANCE) ** 2) * w_offs
-        else:
-            out = stages_ref._smpl_repeat_betas(smpl64, stages_ref.normalize_rot(pose), betas, stages_ref.normalize_rot(root),
-                                                trans)
-            v, joints = out["vertices"], out["joints"][:, :24]
-            vm = v[:, a] if bary is None else (v[:, a] * bary.cpu().double()[None, :, :, None]).sum(2)
-            e = torch.norm(markers - vm, dim=-1) - MARKER_DISTANCE
-            data = torch.mean(_rho(e ** 2, sigma) * mask)
-            prior = 0.0
-        loss = data * w["marker"] + Fn.mse_loss(pose, o_pose) * w["reg_pose_body"] + Fn.mse_loss(betas, o_betas) * w["reg_betas"] + \
-            prior + _accel64(joints) * w.get("joint_accel", 0.0) + _lock64(joints, contacts) * w["foot_lock"]
-        loss.backward()
-    return float(loss.detach()), torch.cat([t.grad.reshape(-1) for t in leaves]).numpy()
-
-
-def _marker_x(pm, pp, bp, rp, tp, dev, seed, num_markers=M):
-    M = num_markers
-    if not pm.has_offsets:
-        return pm.pack(pp.to(dev), bp.to(dev), rp.to(dev), tp.to(dev))
-    from uuo_mocap_amd.engine import MARKER_DISTANCE
-
-    gen = torch.Generator().manual_seed(seed + 7)
-    d = torch.randn(M, 3, generator=gen)
-    offs = (MARKER_DISTANCE * (1.0 + 0.3 * torch.randn(M, 1, generator=gen))) * d / d.norm(dim=1, keepdim=True)
-    return pm.pack(pp.to(dev), bp.to(dev), rp.to(dev), tp.to(dev), offs.to(dev))
+# W_CHAMFER, W_MARKER (100, 10), the weights of the parity checks.  At the inputs below (translation perturbed by 2 cm a frame, so
+# feet that move ~3 cm a frame and data residuals of ~2 cm) the term's gradient on the translation, 2 w g v / (6 (F - 1)), is then
+# of the size of the data term's, 2 w_data d / F: the check that the term matters (> 1e-2 of the gradient) is met with a wide margin.
 
 
 # ------------------------------------------------------------------------------------------------ 6. closure parity
@@ -204,19 +80,6 @@ def test_foot_lock_closures_match_float64_autograd(smpl, smpl64, tables, dev, F)
 
 
 # ------------------------------------------------------------------------------------------------ 7. off is off
-def _makers(smpl, dev, md, o_pose, o_betas, root, vids, i3, b3, pert):
-    from uuo_mocap_amd.engine import ChamferProblem, MarkerProblem
-
-    tp, zp, bp, pp, rp = pert
-    a = (md, o_pose.to(dev), o_betas.to(dev))
-    return {
-        "chamfer": (lambda c, fc: ChamferProblem(smpl, *a, root.to(dev), c, foot_contacts=fc),
-                    lambda p: p.pack(tp.to(dev), zp.to(dev), bp.to(dev), pp.to(dev))),
-        "marker": (lambda c, fc: MarkerProblem(smpl, *a, vids.to(dev), c, foot_contacts=fc),
-                   lambda p: p.pack(pp.to(dev), bp.to(dev), rp.to(dev), tp.to(dev))),
-        "marker3": (lambda c, fc: MarkerProblem(smpl, *a, i3.to(dev), c, bary=b3.to(dev), foot_contacts=fc),
-                    lambda p: p.pack(pp.to(dev), bp.to(dev), rp.to(dev), tp.to(dev))),
-    }
 
 
 def test_off_is_off_and_on_is_deterministic(smpl, tables, dev):
@@ -426,15 +289,6 @@ def test_lockstep_hypotheses_with_the_term_match_the_threaded_route(smpl, tables
 
 
 # ------------------------------------------------------------------------------------------------ 11. what it buys
-def _fit(seq, points, cfg_name, smpl, dev, iters=None):
-    from uuo_mocap_amd.multimodal import multimodal_video_mocap
-
-    cfg = packaged_config(cfg_name)
-    if iters is not None:
-        for k in ("chamfer", "marker", "part"):
-            cfg["stages"][k]["num_iters"] = iters
-    return multimodal_video_mocap(copy.deepcopy(seq.img_smpl), SyntheticMarkers(points.copy(), 30.0), dev, cfg, offset=0,
-                                  print_options=[], save_stages=False, smpl_inference=smpl)
 
 
 def _quality(out, seq, oracle_smpl):

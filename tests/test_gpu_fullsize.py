@@ -18,28 +18,12 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+from gpu_support import _rel_err, dev, smpl  # noqa: E402,F401
 from oracle import p3d_ref, stages_ref  # noqa: E402
 from uuo_mocap_amd.config import packaged_config  # noqa: E402
 from uuo_mocap_amd.synthetic import make_sequence  # noqa: E402
 
 SIZES = [(300, 50, 0), (30, 41, 11)]  # (frames, markers, sequence seed): BASELINE configs[1] size and configs[0]
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def smpl(tables, dev):
-    from uuo_mocap_amd.smpl import SmplInference
-
-    return SmplInference(dev, tables=tables)
-
-
-def _rel_err(a, b):
-    return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-30))
 
 
 def _inputs(tables, F, M, seed):

@@ -12,25 +12,24 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-from keypoints2d_ref64 import evidence, keypoints2d64, project64  # noqa: E402
-from test_gpu_capsules import _caps_grad, _lists as _cap_lists, _preconditions as _caps_preconditions, _joints64  # noqa: E402
-from test_gpu_floor import _chamfer_forward64, _contacts, _marker_forward64, _planes, _ref_chamfer, _ref_marker, _vids  # noqa: E402
-from test_gpu_foot_lock import _marker_x  # noqa: E402
-from test_gpu_joint_limits import W_CAPS_C, W_CAPS_M, _lim_grad, _preconditions as _lim_preconditions, _tables as _lim_tables  # noqa: E402
-from test_gpu_prior_confidence import W_LIM_C, W_LIM_M, _prior64, _weight_tables, _without  # noqa: E402
-from test_gpu_prior_confidence import _cfg as _prior_cfg  # noqa: E402
-from test_gpu_temporal import _float64, _inputs, _rel_err, _three_corners, dev, smpl, smpl64  # noqa: E402,F401
+from capsules_ref64 import _caps_grad, _lists as _cap_lists, _preconditions as _caps_preconditions, _joints64  # noqa: E402
+from floor_ref64 import _contacts, _planes, _vids  # noqa: E402
+from gpu_support import (W_CAPS_C, W_CAPS_M, W_KP_C, W_KP_M, W_LIM_C, W_LIM_M, _inputs, _marker_x, _rel_err,  # noqa: E402,F401
+                         _three_corners, dev, smpl, smpl64)
+from joint_limits_ref64 import _lim_grad, _preconditions as _lim_preconditions, _tables as _lim_tables  # noqa: E402
+from keypoints2d_ref64 import _kp_grad, _record, _with_key  # noqa: E402
+from prior_confidence_ref64 import _cfg as _prior_cfg, _prior64, _weight_tables, _without  # noqa: E402
+from stage_ref64 import (_chamfer_forward64, _float64, _marker_forward64, ref_chamfer64 as _ref_chamfer,  # noqa: E402
+                         ref_marker64 as _ref_marker)
 from uuo_mocap_amd.config import packaged_config  # noqa: E402
 
-# weights of the parity checks, in pixels^-2: with targets 6 px of uniform noise off the projection, focal length 500 and four
+# W_KP_C, W_KP_M (0.05, 0.02), the weights of the parity checks, in pixels^-2: with targets 6 px of uniform noise off the projection, focal length 500 and four
 # metres of depth a joint's gradient is 2 w c r f / (48 F p_z) ~ w 15 / F per component, a quarter of that under the Geman-McClure
 # weights at sigma = 8 px.  The other terms at their parity weights (joint_accel 10, foot_lock 100, the capsules 100, the floor
 # 100) bring the chamfer closure's float64 gradient to a norm of 10 and more, so 0.05 / 0.02 it is: the term's share of the
 # float64 gradient is then past the 2e-2 that the precondition asks for in every case; asserted per case, before the comparison.
-W_KP_C, W_KP_M = 0.05, 0.02
 R_CHAMFER, R_MARKER = 1.0, 0.1   # video_mocap.yaml's reg_pose_body
 SIGMA_KP = 8.0                   # pixels: of the residuals' own size, so that the Geman-McClure weights are far from 0 and 1
-MIN_DEPTH = 0.1
 SHAPES = [(F, M) for F in (1, 2, 7, 33) for M in (10, 11)]
 # seeds of the parity cases, chosen on the host: the first of 600 + 37 F + M + 1000 n (n = 0, 1, ...) that meets _check_seed
 # and puts every joint at a depth >= 1 (n > 0: a foot's two lowest sole points within 1e-4 m at F = 7; at F = 33 a component of
@@ -62,37 +61,6 @@ def _check_seed(smpl64, tables, F, M, seed):
     for J in _joints64(smpl64, tables, F, M, seed):
         _caps_preconditions(J, _cap_lists(tables)["builder"], 1)
     return _planes(smpl64, tables, F, M, 6, seed)
-
-
-def _with_key(cfg, w_chamfer, w_marker, sigma=0.0, joint_weights=None, block=True):
-    cfg = copy.deepcopy(cfg)
-    for stage, w in (("chamfer", w_chamfer), ("marker", w_marker)):
-        cfg["stages"][stage]["losses"]["keypoints_2d"] = w
-        if block:
-            cfg["stages"][stage]["keypoints_2d"] = {"sigma": sigma, "min_depth": MIN_DEPTH, "joint_weights": joint_weights}
-    return cfg
-
-
-def _record(J, seed, **kw):
-    """keypoints2d_ref64.evidence for float64 joints J, rounded to the float32 values the device reads"""
-    return {k: v.float() for k, v in evidence(np.asarray(J, dtype=np.float64), seed, **kw).items()}
-
-
-def _kp_grad(leaves, out, rec, w, sigma, pad=0):
-    """loss and flat gradient (numpy) of the float64 term on the leaves of a float64 forward, zero-padded by `pad` entries; the
-    float64 preconditions of the issue are asserted first: every joint's depth >= 1, no confidence within 1e-4 of 0 but the
-    exact zeros, no depth within 1e-4 of min_depth"""
-    with _float64():
-        cam, y, c = (rec[k].double() for k in ("camera", "targets", "confidence"))
-        J = out["joints"][:, :24]
-        p, _ = project64(J.detach(), cam)
-        assert float(p[..., 2].min()) >= 1.0, "a joint nearer than 1 to the camera: pick another seed"
-        assert float((p[..., 2] - MIN_DEPTH).abs().min()) >= 1e-4 and not bool(((c > 0) & (c < 1e-4)).any())
-        assert bool((c == 0).any()) and bool((c > 0).any())
-        loss = keypoints2d64(J, cam, y, c, w, sigma, MIN_DEPTH)
-        grads = torch.autograd.grad(loss, leaves, allow_unused=True, retain_graph=True)  # (the capsules' term follows on `out`)
-    g = torch.cat([(torch.zeros_like(t) if gi is None else gi).reshape(-1) for t, gi in zip(leaves, grads)]).numpy()
-    return float(loss.detach()), np.concatenate([g, np.zeros(pad)])
 
 
 def _compare(tag, loss, grad, l_rest, g_rest, l_kp, g_kp):

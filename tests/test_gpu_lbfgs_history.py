@@ -13,23 +13,17 @@ import sys
 
 import numpy as np
 import pytest
-import torch
 
 pytestmark = pytest.mark.gpu
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import lbfgs_replay as lr  # noqa: E402
 
+from gpu_support import dev  # noqa: E402,F401
 from uuo_mocap_amd import _lib  # noqa: E402
 
 LB_MAXH = 104  # csrc/lbfgs.h
 HALF_ULP32 = 2.0 ** -24
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return torch.device("cuda:0")
 
 
 def _ptr(a):

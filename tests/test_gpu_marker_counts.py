@@ -9,6 +9,7 @@ Bars (the suite's, no new ones): loss rtol 2e-5; gradient < 2e-4 relative as a w
 (_check_grad); searches, boxes and route comparisons bit for bit.  Observed errors are recorded with record_property."""
 import copy
 import ctypes
+import functools
 import os
 import subprocess
 import sys
@@ -20,14 +21,21 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from oracle import p3d_ref, stages_ref  # noqa: E402
-from test_gpu_foot_lock import _cfg as _marker_cfg  # noqa: E402
-from test_gpu_foot_lock import _contacts, _marker_x, _ref_marker  # noqa: E402
-from test_gpu_model_range import _check_grad, _float64, _ref_chamfer, _ref_part  # noqa: E402
-from test_gpu_temporal import _inputs, _three_corners, dev, smpl, smpl64  # noqa: E402,F401
+from foot_lock_ref64 import _cfg as _marker_cfg, _contacts  # noqa: E402
+from gpu_support import _check_grad, _inputs, _marker_x, _three_corners, dev, smpl, smpl64  # noqa: E402,F401
+from stage_ref64 import _float64, ref_chamfer64, ref_marker64, ref_part64 as _ref_part  # noqa: E402
 from uuo_mocap_amd.config import packaged_config  # noqa: E402
 from uuo_mocap_amd.synthetic import SyntheticMarkers, make_sequence  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# the stage references as this file calls them: the chamfer stage's without rho and with the float64 vertices (as
+# test_gpu_model_range.py has it), the marker stage's with foot contacts and the marker count of the case
+_ref_chamfer = functools.partial(ref_chamfer64, sigma=0.0, with_vertices=True)
+
+
+def _ref_marker(smpl64, tables, cfg, markers, o_pose, o_betas, x, assign, bary, contacts, num_markers):
+    return ref_marker64(smpl64, tables, cfg, markers, o_pose, o_betas, x, assign, bary, contacts, num_markers=num_markers)
+
 V, NUNITS = 6890, 431
 STEP = 1e-3  # between the two evaluations of a case: 1 mm on every translation, 1 mrad on every rotation (a line-search step)
 

@@ -1,7 +1,6 @@
 """EXTENSION: latent per-marker offsets in the fused marker stage (stages.marker.losses.latent_offsets, uuo_problem_t.w_offsets)
 on the MI355X -- the closures against float64 autograd, the start value, the term switched off, the compact packing,
 determinism, recovery of the generator's offsets and the fit quality of video_mocap_offsets.yaml."""
-import contextlib
 import copy
 import ctypes
 import os
@@ -14,41 +13,16 @@ import torch.nn.functional as Fn
 
 pytestmark = pytest.mark.gpu
 
+from gpu_support import W_ACCEL_M as W_ACCEL, W_OFFS, _rel_err, _three_corners, _vertex_error, dev, smpl  # noqa: E402,F401
 from oracle import stages_ref  # noqa: E402
+from stage_ref64 import _float64, _skin64  # noqa: E402
 from uuo_mocap_amd.config import packaged_config  # noqa: E402
 from uuo_mocap_amd.engine import MARKER_DISTANCE  # noqa: E402
 from uuo_mocap_amd.synthetic import SyntheticMarkers, make_sequence  # noqa: E402
 
 M = 50
-W_OFFS, W_ACCEL = 2.0, 1.0  # weights of the parity checks: both terms then matter at the inputs below
+# W_OFFS, W_ACCEL (2, 1), the weights of the parity checks: both terms then matter at the inputs below
 STANDOFF = dict(standoff_tilt_deg=30.0, standoff_mm=(8.0, 14.0))
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def smpl(tables, dev):
-    from uuo_mocap_amd.smpl import SmplInference
-
-    return SmplInference(dev, tables=tables)
-
-
-@contextlib.contextmanager
-def _float64():
-    old = torch.get_default_dtype()
-    torch.set_default_dtype(torch.float64)
-    try:
-        yield
-    finally:
-        torch.set_default_dtype(old)
-
-
-def _rel_err(a, b):
-    return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-30))
 
 
 def _cfg(w_offs=W_OFFS, sigma=0.0, accel=0.0):
@@ -76,46 +50,6 @@ def _inputs(tables, F, seed):
     pert = (o_pose + 0.05 * r(F, 23, 3, 3), o_betas + 0.3 * r(1, 10), root + 0.05 * r(F, 1, 3, 3), trans + 0.02 * r(F, 3),
             offs)
     return seq, markers, o_pose, o_betas, root, trans, pert
-
-
-def _three_corners(tables, seq, seed):
-    gen = torch.Generator().manual_seed(seed)
-    faces = torch.from_numpy(np.asarray(tables.faces).astype(np.int64))
-    vids = torch.from_numpy(np.asarray(seq.gt["marker_vids"])).long()
-    i3 = torch.zeros(M, 3, dtype=torch.int64)
-    b3 = torch.zeros(M, 3)
-    for m in range(M):
-        hit = (faces == vids[m]).any(1).nonzero()
-        tri = faces[hit[0, 0]] if len(hit) else torch.tensor([int(vids[m]), (int(vids[m]) + 1) % 6890, (int(vids[m]) + 2) % 6890])
-        wt = torch.rand(3, generator=gen) + 0.05
-        i3[m], b3[m] = torch.sort(tri)[0], wt / wt.sum()
-    return i3.to(torch.int32), b3
-
-
-def _skin64(tables, rot, betas, trans, vids):
-    """float64 torch SMPL at the vertices `vids` [K] (synthetic.lbs_f64's arithmetic, differentiable): v_posed [F,K,3],
-    T_R [F,K,3,3], T_t [F,K,3] (translation included) and the 24 world joints [F,24,3]."""
-    F = rot.shape[0]
-    vt = torch.from_numpy(tables.v_template).double()
-    S = torch.from_numpy(tables.shapedirs).double()
-    P = torch.from_numpy(tables.posedirs).double()
-    Jr = torch.from_numpy(tables.J_regressor).double()
-    W = torch.from_numpy(tables.lbs_weights).double()
-    v_shaped = vt[None] + torch.einsum("bl,mkl->bmk", betas.expand(F, 10), S)
-    J = torch.einsum("bik,ji->bjk", v_shaped, Jr)
-    pf = (rot[:, 1:] - torch.eye(3, dtype=torch.float64)).reshape(F, -1)
-    Pk = P.reshape(207, -1, 3)[:, vids]
-    v_posed = v_shaped[:, vids] + torch.einsum("fp,pkc->fkc", pf, Pk)
-    GR, Gt = [rot[:, 0]], [J[:, 0]]
-    for j in range(1, 24):
-        p = int(tables.parents[j])
-        GR.append(GR[p] @ rot[:, j])
-        Gt.append(torch.einsum("fab,fb->fa", GR[p], J[:, j] - J[:, p]) + Gt[p])
-    GR, Gt = torch.stack(GR, 1), torch.stack(Gt, 1)
-    At = Gt - torch.einsum("fjab,fjb->fja", GR, J)
-    T_R = torch.einsum("kj,fjab->fkab", W[vids], GR)
-    T_t = torch.einsum("kj,fja->fka", W[vids], At) + trans[:, None]
-    return v_posed, T_R, T_t, Gt + trans[:, None]
 
 
 def _ref(tables, cfg, markers, o_pose, o_betas, x, assign, bary=None):
@@ -374,12 +308,6 @@ def _fit(seq, points, cfg, smpl, dev):
 
     return multimodal_video_mocap(copy.deepcopy(seq.img_smpl), SyntheticMarkers(points.copy(), 30.0), dev, cfg, offset=0,
                                   print_options=[], save_stages=False, smpl_inference=smpl)
-
-
-def _vertex_error(out, seq, oracle_smpl):
-    r = oracle_smpl(out["pose_body"].cpu().float(), out["betas"].cpu().float(), out["root_orient"].cpu().float(),
-                    out["trans"].cpu().float())
-    return float((r["vertices"] - torch.from_numpy(seq.gt["verts"])).norm(dim=-1).mean())
 
 
 def test_offsets_recovery(smpl, tables, dev, record_property):

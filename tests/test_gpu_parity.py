@@ -10,22 +10,10 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+from gpu_support import _rel_err, dev, smpl  # noqa: E402,F401
 from oracle import p3d_ref, stages_ref  # noqa: E402
 from uuo_mocap_amd.config import packaged_config  # noqa: E402
 from uuo_mocap_amd.synthetic import SyntheticImgSmpl, SyntheticMarkers, make_sequence  # noqa: E402
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def smpl(tables, dev):
-    from uuo_mocap_amd.smpl import SmplInference
-
-    return SmplInference(dev, tables=tables)
 
 
 def _t(x, dev=None):
@@ -179,8 +167,6 @@ def test_compute_nearest_points_golden(smpl, golden, dev):
 
 
 # ------------------------------------------------------------------------------------------------ closures
-def _rel_err(a, b):
-    return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-30))
 
 
 def test_chamfer_closure_matches_oracle_and_golden(smpl, oracle_smpl, golden, dev):
@@ -2171,6 +2157,4 @@ def test_reprojection_stage_matches_reference(smpl, golden, dev):
             # tests/test_gpu_fullsize.py::test_dense_smpl_backward_at_baseline_size)
             if abs(ops["output_angle"] - out["output_angle"]) > 0.1:
                 assert ops["solver"]["final_loss"] <= 1.5 * out["solver"]["final_loss"]
-
-
 

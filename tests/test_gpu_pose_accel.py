@@ -3,7 +3,6 @@ losses.pose_accel_loss) on the MI355X.  The term has no fused closure: optim_cha
 composed from the HIP operators.  Checked here: the composed solves' first loss against the plain composed closure plus the
 float64 term, that they decrease and smooth the pose, the refusals on a device, and video_mocap_rotsmooth.yaml on the default
 capture."""
-import copy
 
 import numpy as np
 import pytest
@@ -12,10 +11,10 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from pose_accel_ref64 import pose_accel64  # noqa: E402
-from test_gpu_temporal import _inputs, dev, smpl  # noqa: E402,F401
+from gpu_support import _fit, _inputs, dev, smpl  # noqa: E402,F401
 from uuo_mocap_amd.config import packaged_config  # noqa: E402
 from uuo_mocap_amd.metrics import LEAF_JOINT_ROWS  # noqa: E402
-from uuo_mocap_amd.synthetic import SyntheticMarkers, make_sequence  # noqa: E402
+from uuo_mocap_amd.synthetic import make_sequence  # noqa: E402
 
 U_TABLE = [1.0] * 23
 U_TABLE[3], U_TABLE[9], U_TABLE[17] = 0.0, 0.5, 1.75
@@ -101,13 +100,6 @@ def test_stage_problems_and_routes_refuse_the_term_where_it_is_not_built(smpl, t
             optim_chamfer(md, pose_body=pose, o_pose_body=o_pose.to(dev), betas=betas, o_betas=o_betas.to(dev), root_orient=rt,
                           trans=tr, img_mask=torch.ones(F, device=dev), marker_labels=torch.zeros(F, Mk, dtype=torch.long, device=dev),
                           smpl_inference=smpl, config=on)
-
-
-def _fit(seq, cfg_name, smpl, dev):
-    from uuo_mocap_amd.multimodal import multimodal_video_mocap
-
-    return multimodal_video_mocap(copy.deepcopy(seq.img_smpl), SyntheticMarkers(np.asarray(seq.markers.get_points()).copy(), 30.0),
-                                  dev, packaged_config(cfg_name), offset=0, print_options=[], save_stages=False, smpl_inference=smpl)
 
 
 def test_rotsmooth_config(smpl, oracle_smpl, tables, dev, record_property):

@@ -14,25 +14,24 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from pose_accel_ref64 import pose_accel_grad64, random_raw  # noqa: E402
-from test_gpu_floor import _chamfer_forward64, _contacts, _ref_chamfer, _ref_marker, _vids  # noqa: E402
-from test_gpu_joint_limits import _block as _lim_block, _lim_grad, _preconditions as _lim_preconditions, _tables as _lim_tables  # noqa: E402
-from test_gpu_prior_confidence import R_CHAMFER, R_MARKER, W_LIM_C, W_LIM_M, _prior64, _weight_tables  # noqa: E402
-from test_gpu_floor import _marker_forward64  # noqa: E402
-from test_gpu_temporal import _float64, _inputs, _rel_err, dev, smpl, smpl64  # noqa: E402,F401
+from floor_ref64 import _contacts, _vids  # noqa: E402
+from gpu_support import (R_CHAMFER, R_MARKER, U_TABLE, W_LIM_C, W_LIM_M, W_PACC_C as W_C, W_PACC_M as W_M, _inputs,  # noqa: E402,F401
+                         _rel_err, dev, smpl, smpl64)
+from joint_limits_ref64 import _block as _lim_block, _lim_grad, _preconditions as _lim_preconditions, _tables as _lim_tables  # noqa: E402
+from prior_confidence_ref64 import _prior64, _weight_tables  # noqa: E402
+from stage_ref64 import (_chamfer_forward64, _float64, _marker_forward64, ref_chamfer64 as _ref_chamfer,  # noqa: E402
+                         ref_marker64 as _ref_marker)
 from uuo_mocap_amd.config import packaged_config  # noqa: E402
 from uuo_mocap_amd.metrics import LEAF_JOINT_ROWS  # noqa: E402
 from uuo_mocap_amd.synthetic import SyntheticMarkers, make_sequence  # noqa: E402
 
 M = 11
-W_C, W_M = 1000.0, 1000.0         # video_mocap_rotsmooth.yaml's
-U_TABLE = [1.0] * 23
-U_TABLE[3], U_TABLE[9], U_TABLE[17] = 0.0, 0.5, 1.75    # tests/test_pose_accel.py's: a zero, a value below and one above 1
 
 
 def _cfg(w_chamfer=None, w_marker=None, u=None, fused=True, limits=None, reg=None):
     """video_mocap.yaml with the term's key (None = absent) and joint weights, execution.pose_accel_fused, the joint-angle limit
-    term on a table `limits`, and reg_pose_body `reg` = (chamfer, marker).  (floor_height: the float64 restatements of
-    test_gpu_floor read it.)"""
+    term on a table `limits`, and reg_pose_body `reg` = (chamfer, marker).  (floor_height: the stage reference
+    reads it.)"""
     cfg = packaged_config("video_mocap")
     if fused:
         cfg["execution"] = dict(cfg.get("execution") or {}, pose_accel_fused=True)
@@ -97,7 +96,7 @@ class _Case:
         return loss, out
 
     def rest64(self, stage, smpl64, tables, cfg, x, nn=None):
-        """float64 loss and gradient of the closure of `cfg` without the extension terms of this file (test_gpu_floor's)"""
+        """float64 loss and gradient of the closure of `cfg` without the extension terms of this file (the stage reference)"""
         if stage == "chamfer":
             return _ref_chamfer(smpl64, cfg, self.markers, self.o_pose, self.o_betas, self.root, x, nn, self.contacts, self.svids, 3)
         return _ref_marker(smpl64, tables, cfg, self.markers, self.o_pose, self.o_betas, x, self.vids, None, self.contacts,
@@ -246,8 +245,8 @@ def test_the_add_chains_of_both_shared_buffers_for_every_subset(smpl, smpl64, ta
     equal between the two workspaces and on a repeated evaluation: a kernel that adds where no earlier writer ran picks up the
     previous subset's contents, one that writes where it should add loses a term -- and the 32 losses are all different."""
     from keypoints2d_ref64 import evidence
-    from test_gpu_capsules import _block as _cap_block, _joints64, _lists as _cap_lists, _preconditions as _caps_preconditions
-    from test_gpu_joint_limits import W_CAPS_M
+    from capsules_ref64 import _block as _cap_block, _joints64, _lists as _cap_lists, _preconditions as _caps_preconditions
+    from gpu_support import W_CAPS_M
     from uuo_mocap_amd.engine import set_workspace_slot
 
     F, markers, seed = 5, 12, 5120

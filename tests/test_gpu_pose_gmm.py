@@ -1,5 +1,5 @@
 """EXTENSION: the mixture pose prior on the body pose (stages.{chamfer,marker}.losses.pose_gmm, uuo_fit_set_pose_gmm, k_pose_gmm) on
-the MI355X -- the fused closures against float64 (test_gpu_floor's restatement of the closure plus the loop-written float64 term
+the MI355X -- the fused closures against float64 (stage_ref64's restatement of the closure plus the loop-written float64 term
 of tests/pose_gmm_ref64.py), the term alone beside the composed fp32 term's own error, the winners, the buffer it shares with
 the joint-angle limits, the pose acceleration and the weighted prior, hand-built poses, the invariances (off is off, two
 evaluations, four in flight, a frame alone and inside a longer sequence, a second mixture and back), fused against composed
@@ -17,15 +17,16 @@ pytestmark = pytest.mark.gpu
 
 from oracle import stages_ref  # noqa: E402
 from pose_gmm_ref64 import energies_np, find_case, gs64, make_mixture, raw_from_theta, rodrigues, term_np  # noqa: E402
-from test_gpu_capsules import _caps_grad, _lists as _cap_lists  # noqa: E402
-from test_gpu_floor import _chamfer_forward64, _contacts, _heights64, _marker_forward64, _plane, _ref_chamfer, _ref_marker, _vids  # noqa: E402
-from test_gpu_foot_lock import _marker_x  # noqa: E402
-from test_gpu_joint_limits import W_CAPS_C, W_CAPS_M, _cfg as _lim_cfg, _lim_grad, _tables as _lim_tables  # noqa: E402
-from test_gpu_keypoints2d import MIN_DEPTH, W_KP_C, W_KP_M, _kp_grad, _record, _with_key  # noqa: E402
-from test_gpu_pose_accel_fused import U_TABLE, W_C as W_PACC_C, W_M as W_PACC_M  # noqa: E402
-from test_gpu_prior_confidence import R_CHAMFER, R_MARKER, W_LIM_C, W_LIM_M, _prior64, _weight_tables, _without  # noqa: E402
-from test_gpu_temporal import _float64, _inputs, _rel_err, _three_corners, dev, smpl, smpl64  # noqa: E402,F401
+from capsules_ref64 import _caps_grad, _lists as _cap_lists  # noqa: E402
+from floor_ref64 import _contacts, _plane, _vids  # noqa: E402
+from gpu_support import (R_CHAMFER, R_MARKER, U_TABLE, W_CAPS_C, W_CAPS_M, W_KP_C, W_KP_M, W_LIM_C, W_LIM_M,  # noqa: E402,F401
+                         W_PACC_C, W_PACC_M, _inputs, _marker_x, _rel_err, _three_corners, dev, smpl, smpl64)
+from joint_limits_ref64 import _cfg as _lim_cfg, _lim_grad, _tables as _lim_tables  # noqa: E402
+from keypoints2d_ref64 import _kp_grad, _record, _with_key  # noqa: E402
 from pose_accel_ref64 import pose_accel_grad64  # noqa: E402
+from prior_confidence_ref64 import _prior64, _weight_tables, _without  # noqa: E402
+from stage_ref64 import (_chamfer_forward64, _float64, _heights64, _marker_forward64, ref_chamfer64 as _ref_chamfer,  # noqa: E402
+                         ref_marker64 as _ref_marker)
 from uuo_mocap_amd.body_model import pose_log_vector, prepare_pose_mixture  # noqa: E402
 from uuo_mocap_amd.config import packaged_config  # noqa: E402
 from uuo_mocap_amd.synthetic import SyntheticMarkers, make_sequence  # noqa: E402
@@ -46,7 +47,7 @@ def _set_gmm(cfg, w_chamfer, w_marker):
     for stage, w in (("chamfer", w_chamfer), ("marker", w_marker)):
         if w is not None:
             cfg["stages"][stage]["losses"]["pose_gmm"] = w
-        cfg["stages"][stage].setdefault("floor_height", 0.0)   # (test_gpu_floor's restatements read it)
+        cfg["stages"][stage].setdefault("floor_height", 0.0)   # (the stage reference reads it)
     return cfg
 
 

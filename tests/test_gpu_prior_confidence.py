@@ -13,81 +13,25 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-from test_gpu_capsules import _caps_grad, _lists as _cap_lists  # noqa: E402
-from test_gpu_floor import _chamfer_forward64, _contacts, _marker_forward64, _ref_chamfer, _ref_marker, _vids  # noqa: E402
-from test_gpu_foot_lock import _marker_x  # noqa: E402
-from test_gpu_joint_limits import (SETTINGS, SHAPES, W_CAPS_C, W_CAPS_M, _check_seed, _lim_grad, _seed,  # noqa: E402
-                                   _cfg as _lim_cfg)
-from test_gpu_temporal import _float64, _inputs, _rel_err, _three_corners, dev, smpl, smpl64  # noqa: E402,F401
-from uuo_mocap_amd.body_model import hash_uniform, smpl_joint_limits  # noqa: E402
+from capsules_ref64 import _caps_grad, _lists as _cap_lists  # noqa: E402
+from floor_ref64 import _contacts, _vids  # noqa: E402
+from gpu_support import (R_CHAMFER, R_MARKER, W_CAPS_C, W_CAPS_M, W_LIM_C, W_LIM_M, _fit, _inputs, _marker_x,  # noqa: E402,F401
+                         _rel_err, _three_corners, dev, smpl, smpl64)
+from joint_limits_ref64 import SETTINGS, SHAPES, _check_seed, _lim_grad, _seed  # noqa: E402
+from prior_confidence_ref64 import _cfg, _prior64, _weight_tables, _without  # noqa: E402
+from stage_ref64 import (_chamfer_forward64, _float64, _marker_forward64, ref_chamfer64 as _ref_chamfer,  # noqa: E402
+                         ref_marker64 as _ref_marker)
+from uuo_mocap_amd.body_model import smpl_joint_limits  # noqa: E402
 from uuo_mocap_amd.config import packaged_config  # noqa: E402
-from uuo_mocap_amd.synthetic import SyntheticMarkers, make_sequence  # noqa: E402
+from uuo_mocap_amd.synthetic import make_sequence  # noqa: E402
 
-# weights of the parity checks.  The evaluated pose is the target + 0.05 randn per entry (_inputs), so the uniform prior's gradient
-# is 2 R 0.05 / (207 F) per entry, and the tables below change a third to a half of it: |weighted - uniform| ~ R 4e-3 / sqrt(F)
+# R_CHAMFER, R_MARKER (600, 60), the weights of the parity checks.  The evaluated pose is the target + 0.05 randn per entry
+# (_inputs), so the uniform prior's gradient is 2 R 0.05 / (207 F) per entry, and the tables below change a third to a half of it: |weighted - uniform| ~ R 4e-3 / sqrt(F)
 # over the pose entries.  The rest of the closure's float64 gradient at these points (data term, shape prior, and with the
 # settings on the limit term at its weight of 10, the floor and the capsules) has a norm of up to 10 on the chamfer and 3 on the
 # marker closures, measured in float64 on the host over every case below; with video_mocap.yaml's 1.0 / 0.1 the weights would
 # move the whole gradient by 1e-4 or less.  The precondition asks for 2e-2, so the parity checks raise reg_pose_body, as the
 # issue provides for: 600 / 60 give 3.9e-2 or more on the chamfer and one-hot closures of every case (float64, host).
-R_CHAMFER, R_MARKER = 600.0, 60.0
-W_LIM_C, W_LIM_M = 10.0, 1.0   # test_gpu_joint_limits'
-
-
-# ------------------------------------------------------------------------------------------------ tables and configs
-def _weight_tables(F, seed):
-    """name -> [F, 23] float32: a run of frames at 0 (all frames at F = 1); hash-uniform values in [0, 2] with exact zeros (every
-    fifth entry); per-joint only (one row for all frames, a zero and values above 1 in it)"""
-    run = torch.ones(F, 23)
-    a = F // 3
-    run[a:a + max(1, F // 2)] = 0.0
-    u = torch.from_numpy(2.0 * hash_uniform(900 + seed, F, 23)).float()
-    u.reshape(-1)[::5] = 0.0
-    jw = torch.from_numpy(2.0 * hash_uniform(901 + seed, 23)).float()
-    jw[3] = 0.0
-    jw[17] = 1.75
-    return {"zero run": run, "hash": u, "per joint": jw[None].repeat(F, 1).contiguous()}
-
-
-def _cfg(limits=False, sigma=0.0, temporal=False, floor=None, caps=None, offs=False, r_chamfer=R_CHAMFER, r_marker=R_MARKER,
-         block=False):
-    """test_gpu_joint_limits' config (video_mocap.yaml with the other settings of the parity checks; `limits` switches the
-    joint-angle limit term on with the builder's table) at the parity checks' reg_pose_body; `block` adds the stage blocks"""
-    cfg = _lim_cfg(smpl_joint_limits() if limits else None, W_LIM_C if limits else 0.0, W_LIM_M if limits else 0.0, sigma=sigma,
-                   temporal=temporal, floor=floor, caps=caps, offs=offs, keys=limits)
-    cfg["stages"]["chamfer"]["losses"]["reg_pose_body"] = r_chamfer
-    cfg["stages"]["marker"]["losses"]["reg_pose_body"] = r_marker
-    if block:
-        for stage in ("chamfer", "marker"):
-            cfg["stages"][stage]["prior_confidence"] = {"gap_weight": 0.0, "ramp": 0, "joint_weights": None}
-    return cfg
-
-
-def _without(cfg, limits=True, prior=True):
-    """the config with the joint-angle limit term and / or the pose prior taken out (what the float64 restatements of the other
-    test files cover: they know neither the limit term nor a weighted prior)"""
-    c = copy.deepcopy(cfg)
-    for stage in ("chamfer", "marker"):
-        if limits and "joint_limits" in c["stages"][stage]["losses"]:
-            c["stages"][stage]["losses"]["joint_limits"] = 0.0
-        if prior:
-            c["stages"][stage]["losses"]["reg_pose_body"] = 0.0
-    return c
-
-
-def _prior64(x, pose_slice, o_pose, w, reg, n):
-    """loss and flat gradient [n] (numpy) of the issue's term in float64 autograd on the raw pose entries of x: reg / (F 207)
-    sum_t sum_j w[t, j] sum_e (raw - o)^2 (w None: the uniform prior)"""
-    with _float64():
-        F = o_pose.shape[0]
-        leaf = x.detach().cpu().double()[pose_slice].reshape(F, 23, 3, 3).clone().requires_grad_(True)
-        d = leaf - o_pose.detach().cpu().double()
-        ww = torch.ones(F, 23) if w is None else w.detach().cpu().double()
-        loss = float(reg) / (F * 207.0) * (ww[:, :, None, None] * d * d).sum()
-        (g,) = torch.autograd.grad(loss, [leaf])
-    out = np.zeros(n)
-    out[pose_slice] = g.reshape(-1).numpy()
-    return float(loss.detach()), out
 
 
 def _compare(tag, loss, grad, l_rest, g_rest, x, pose_slice, o_pose, w, reg):
@@ -502,11 +446,6 @@ def test_library_and_routes_refuse_the_weights_where_they_are_not_built(smpl, ta
 
 
 # ------------------------------------------------------------------------------------------------ 7. the shipped config
-def _fit(seq, cfg_name, smpl, dev):
-    from uuo_mocap_amd.multimodal import multimodal_video_mocap
-
-    return multimodal_video_mocap(copy.deepcopy(seq.img_smpl), SyntheticMarkers(np.asarray(seq.markers.get_points()).copy(), 30.0),
-                                  dev, packaged_config(cfg_name), offset=0, print_options=[], save_stages=False, smpl_inference=smpl)
 
 
 def test_dropout_config(smpl, oracle_smpl, tables, dev, record_property):

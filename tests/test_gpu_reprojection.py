@@ -20,7 +20,7 @@ pytestmark = pytest.mark.gpu
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import reprojection_ref64 as rr  # noqa: E402
-from test_gpu_temporal import dev, smpl  # noqa: E402,F401
+from gpu_support import dev, smpl  # noqa: E402,F401
 
 from oracle import stages_ref  # noqa: E402
 from uuo_mocap_amd.config import packaged_config  # noqa: E402

@@ -1,59 +1,33 @@
 """EXTENSION: Geman-McClure (GMoF) data terms on the fused closures (uuo_problem_t.robust_sigma) on the MI355X -- every stage
 closure against float64 autograd through the oracle's SMPL, the sigma limits, lock-step batches, the operator-composed route
 and a fit on a capture with ghost markers."""
-import contextlib
 import copy
 
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as Fn
 
 pytestmark = pytest.mark.gpu
 
-from oracle import stages_ref  # noqa: E402
+from gpu_support import _rel_err, _three_corners, dev, smpl, smpl64  # noqa: E402,F401
+from stage_ref64 import ref_chamfer64, ref_marker64, ref_part64  # noqa: E402
 from uuo_mocap_amd.config import packaged_config  # noqa: E402
 from uuo_mocap_amd.synthetic import SyntheticMarkers, make_sequence  # noqa: E402
 
 M = 50
 
 
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return torch.device("cuda:0")
+# the stage references at the sigma of the call (this file passes it next to the config)
+def _ref_chamfer(smpl64, cfg, sigma, *args):
+    return ref_chamfer64(smpl64, cfg, *args, sigma=sigma)
 
 
-@pytest.fixture(scope="module")
-def smpl(tables, dev):
-    from uuo_mocap_amd.smpl import SmplInference
-
-    return SmplInference(dev, tables=tables)
+def _ref_marker(smpl64, cfg, sigma, *args):
+    return ref_marker64(smpl64, None, cfg, *args, sigma=sigma)
 
 
-@pytest.fixture(scope="module")
-def smpl64(tables):
-    from oracle.smpl_ref import SmplInferenceRef
-
-    return SmplInferenceRef(tables).double()
-
-
-@contextlib.contextmanager
-def _float64():
-    old = torch.get_default_dtype()
-    torch.set_default_dtype(torch.float64)
-    try:
-        yield
-    finally:
-        torch.set_default_dtype(old)
-
-
-def _rel_err(a, b):
-    return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-30))
-
-
-def _rho(s, sigma):
-    return s * (sigma * sigma / (sigma * sigma + s)) if sigma else s
+def _ref_part(smpl64, cfg, sigma, *args):
+    return ref_part64(smpl64, cfg, *args, sigma=sigma)
 
 
 def _ghosts(markers, frac, seed, columns=()):
@@ -91,87 +65,6 @@ def _cfg(sigma, name="video_mocap"):
     for k in ("chamfer", "part", "marker"):
         cfg["stages"][k]["robust_sigma"] = sigma
     return cfg
-
-
-def _d64(*ts):
-    return [t.detach().cpu().double() for t in ts]
-
-
-def _ref_chamfer(smpl64, cfg, sigma, markers, o_pose, o_betas, root, x, nn):
-    F = markers.shape[0]
-    w = cfg["stages"]["chamfer"]["losses"]
-    with _float64():
-        x = x.detach().cpu().double()
-        markers, o_pose, o_betas, root = _d64(markers, o_pose, o_betas, root)
-        leaves = [t.clone().requires_grad_(True) for t in (x[:3 * F].reshape(F, 3), x[3 * F:4 * F].reshape(F, 1, 1),
-                                                          x[4 * F:4 * F + 10].reshape(1, 10), x[4 * F + 10:].reshape(F, 23, 3, 3))]
-        trans, z, betas, pose = leaves
-        z_root = stages_ref.compute_root_orient_z(z) @ root
-        v = stages_ref._smpl_repeat_betas(smpl64, stages_ref.normalize_rot(pose), betas, stages_ref.normalize_rot(z_root),
-                                          trans)["vertices"]
-        vn = torch.gather(v, 1, nn.cpu().long()[..., None].expand(-1, -1, 3))
-        mask = stages_ref.get_marker_mask(markers).double()
-        d2 = ((markers - vn) ** 2).sum(-1)
-        loss = (mask * _rho(d2, sigma)).sum() / mask.sum() * w["full_chamfer"] + \
-            Fn.mse_loss(pose, o_pose) * w["reg_pose_body"] + Fn.mse_loss(betas, o_betas) * w["reg_betas"]
-        loss.backward()
-    return float(loss.detach()), torch.cat([t.grad.reshape(-1) for t in leaves]).numpy()
-
-
-def _ref_marker(smpl64, cfg, sigma, markers, o_pose, o_betas, x, assign, bary=None):
-    F = markers.shape[0]
-    w = cfg["stages"]["marker"]["losses"]
-    from uuo_mocap_amd.engine import MARKER_DISTANCE
-
-    with _float64():
-        x = x.detach().cpu().double()
-        markers, o_pose, o_betas = _d64(markers, o_pose, o_betas)
-        leaves = [t.clone().requires_grad_(True) for t in (x[:207 * F].reshape(F, 23, 3, 3), x[207 * F:207 * F + 10].reshape(1, 10),
-                                                          x[207 * F + 10:216 * F + 10].reshape(F, 1, 3, 3), x[216 * F + 10:].reshape(F, 3))]
-        pose, betas, root, trans = leaves
-        v = stages_ref._smpl_repeat_betas(smpl64, stages_ref.normalize_rot(pose), betas, stages_ref.normalize_rot(root),
-                                          trans)["vertices"]
-        a = assign.cpu().long()
-        vm = v[:, a] if bary is None else (v[:, a] * bary.cpu().double()[None, :, :, None]).sum(2)
-        e = torch.norm(markers - vm, dim=-1) - MARKER_DISTANCE
-        mask = stages_ref.get_marker_mask(markers).double()
-        loss = torch.mean(_rho(e ** 2, sigma) * mask) * w["marker"] + Fn.mse_loss(pose, o_pose) * w["reg_pose_body"] + \
-            Fn.mse_loss(betas, o_betas) * w["reg_betas"]
-        loss.backward()
-    return float(loss.detach()), torch.cat([t.grad.reshape(-1) for t in leaves]).numpy()
-
-
-def _ref_part(smpl64, cfg, sigma, markers, pose_body, o_betas, root, x, vidx, nn):
-    F, M_ = markers.shape[:2]
-    w = cfg["stages"]["part"]["losses"]
-    with _float64():
-        x = x.detach().cpu().double()
-        markers, pose_body, o_betas, root = _d64(markers, pose_body, o_betas, root)
-        leaves = [t.clone().requires_grad_(True) for t in (x[:1].reshape(1, 1, 1), x[1:3 * F + 1].reshape(F, 3),
-                                                          x[3 * F + 1:].reshape(1, 10))]
-        z, trans, betas = leaves
-        z_root = stages_ref.compute_root_orient_z(torch.repeat_interleave(z, repeats=F, dim=0)) @ root
-        v = stages_ref._smpl_repeat_betas(smpl64, pose_body, betas, z_root, trans)["vertices"]
-        vsel = vidx.cpu().long()[nn.cpu().long()]                     # candidate position -> vertex id, [F, M]
-        vn = torch.gather(v, 1, vsel[..., None].expand(-1, -1, 3))
-        d2 = ((markers - vn) ** 2).sum(-1)
-        loss = _rho(d2, sigma).sum() / float(F * M_) * w["chamfer"] + Fn.mse_loss(betas, o_betas) * w["reg_betas"]
-        loss.backward()
-    return float(loss.detach()), torch.cat([t.grad.reshape(-1) for t in leaves]).numpy()
-
-
-def _three_corners(tables, seq, seed):
-    gen = torch.Generator().manual_seed(seed)
-    faces = torch.from_numpy(np.asarray(tables.faces).astype(np.int64))
-    vids = torch.from_numpy(np.asarray(seq.gt["marker_vids"])).long()
-    i3 = torch.zeros(M, 3, dtype=torch.int64)
-    b3 = torch.zeros(M, 3)
-    for m in range(M):
-        hit = (faces == vids[m]).any(1).nonzero()
-        tri = faces[hit[0, 0]] if len(hit) else torch.tensor([int(vids[m]), (int(vids[m]) + 1) % 6890, (int(vids[m]) + 2) % 6890])
-        wt = torch.rand(3, generator=gen) + 0.05
-        i3[m], b3[m] = torch.sort(tri)[0], wt / wt.sum()
-    return i3.to(torch.int32), b3
 
 
 def _leg_vertices(smpl, dev):

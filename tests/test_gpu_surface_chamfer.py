@@ -15,8 +15,9 @@ import torch.nn.functional as Fn
 pytestmark = pytest.mark.gpu
 
 from oracle import stages_ref  # noqa: E402
-from test_gpu_foot_lock import _contacts, _lock64  # noqa: E402
-from test_gpu_temporal import _accel64, _d64, _float64, _inputs, _rel_err, _rho, dev, smpl, smpl64  # noqa: E402,F401
+from foot_lock_ref64 import _contacts  # noqa: E402
+from gpu_support import _inputs, _rel_err, dev, smpl, smpl64  # noqa: E402,F401
+from stage_ref64 import _accel64, _d64, _float64, _lock64, _rho  # noqa: E402
 from uuo_mocap_amd.config import packaged_config  # noqa: E402
 from uuo_mocap_amd.synthetic import SyntheticMarkers, make_sequence  # noqa: E402
 

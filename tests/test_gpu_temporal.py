@@ -1,57 +1,27 @@
 """EXTENSION: the joint-acceleration smoothness term (stages.{chamfer,marker}.losses.joint_accel, uuo_fit_set_joint_accel) on
 the MI355X -- the fused closures against float64 autograd through the oracle's SMPL, the compact packing, the term switched
 off, the operator-composed route, the routing rules and a fit through a stretch of frames without markers."""
-import contextlib
 import copy
 import threading
 
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as Fn
 
 pytestmark = pytest.mark.gpu
 
-from oracle import stages_ref  # noqa: E402
+from gpu_support import (W_ACCEL_C as W_CHAMFER, W_ACCEL_M as W_MARKER, _fit_points as _fit, _inputs, _rel_err,  # noqa: E402,F401
+                         _three_corners, dev, smpl, smpl64)
+from stage_ref64 import ref_chamfer64 as _ref_chamfer, ref_marker64  # noqa: E402
 from uuo_mocap_amd.config import packaged_config  # noqa: E402
 from uuo_mocap_amd.synthetic import SyntheticMarkers, make_sequence  # noqa: E402
 
 M = 50
-W_CHAMFER, W_MARKER = 10.0, 1.0  # weights of the parity checks: the term is then of the data term's size at the inputs below
+# W_CHAMFER, W_MARKER (10, 1), the weights of the parity checks: the term is then of the data term's size at the inputs below
 
 
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def smpl(tables, dev):
-    from uuo_mocap_amd.smpl import SmplInference
-
-    return SmplInference(dev, tables=tables)
-
-
-@pytest.fixture(scope="module")
-def smpl64(tables):
-    from oracle.smpl_ref import SmplInferenceRef
-
-    return SmplInferenceRef(tables).double()
-
-
-@contextlib.contextmanager
-def _float64():
-    old = torch.get_default_dtype()
-    torch.set_default_dtype(torch.float64)
-    try:
-        yield
-    finally:
-        torch.set_default_dtype(old)
-
-
-def _rel_err(a, b):
-    return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-30))
+def _ref_marker(smpl64, cfg, *args):   # (no latent offsets in this file: the reference needs no model tables)
+    return ref_marker64(smpl64, None, cfg, *args)
 
 
 def _cfg(w_chamfer=0.0, w_marker=0.0, sigma=0.0, name="video_mocap"):
@@ -63,98 +33,6 @@ def _cfg(w_chamfer=0.0, w_marker=0.0, sigma=0.0, name="video_mocap"):
     for k in ("chamfer", "part", "marker"):
         cfg["stages"][k]["robust_sigma"] = sigma
     return cfg
-
-
-def _inputs(tables, F, seed, num_markers=M):
-    seq = make_sequence(tables, seed=seed, num_frames=F, num_markers=num_markers)
-    markers = torch.from_numpy(np.nan_to_num(seq.markers.get_points())).float()
-    o_pose = seq.img_smpl.pose_body.clone().float()
-    o_betas = (seq.img_smpl.betas.sum(0, keepdim=True) / seq.img_smpl.img_mask.sum()).float()
-    root = seq.img_smpl.root_orient.clone().float()
-    trans = torch.median(markers, dim=1)[0].clone()
-    gen = torch.Generator().manual_seed(seed + 2)
-    r = lambda *s: torch.randn(*s, generator=gen)
-    pert = (trans + 0.02 * r(F, 3), 0.3 * r(F, 1, 1), o_betas + 0.3 * r(1, 10), o_pose + 0.05 * r(F, 23, 3, 3),
-            root + 0.05 * r(F, 1, 3, 3))
-    return seq, markers, o_pose, o_betas, root, trans, pert
-
-
-def _d64(*ts):
-    return [t.detach().cpu().double() for t in ts]
-
-
-def _accel64(joints):
-    F = joints.shape[0]
-    if F < 3:
-        return joints.sum() * 0.0
-    a = joints[:-2, :24] - 2.0 * joints[1:-1, :24] + joints[2:, :24]
-    return Fn.mse_loss(a, torch.zeros_like(a))
-
-
-def _rho(s, sigma):
-    return s * (sigma * sigma / (sigma * sigma + s)) if sigma else s
-
-
-def _ref_chamfer(smpl64, cfg, markers, o_pose, o_betas, root, x, nn):
-    F = markers.shape[0]
-    st = cfg["stages"]["chamfer"]
-    w, sigma = st["losses"], float(st.get("robust_sigma", 0.0))
-    with _float64():
-        x = x.detach().cpu().double()
-        markers, o_pose, o_betas, root = _d64(markers, o_pose, o_betas, root)
-        leaves = [t.clone().requires_grad_(True) for t in (x[:3 * F].reshape(F, 3), x[3 * F:4 * F].reshape(F, 1, 1),
-                                                          x[4 * F:4 * F + 10].reshape(1, 10), x[4 * F + 10:].reshape(F, 23, 3, 3))]
-        trans, z, betas, pose = leaves
-        z_root = stages_ref.compute_root_orient_z(z) @ root
-        out = stages_ref._smpl_repeat_betas(smpl64, stages_ref.normalize_rot(pose), betas, stages_ref.normalize_rot(z_root),
-                                            trans)
-        vn = torch.gather(out["vertices"], 1, nn.cpu().long()[..., None].expand(-1, -1, 3))
-        mask = stages_ref.get_marker_mask(markers).double()
-        d2 = ((markers - vn) ** 2).sum(-1)
-        loss = (mask * _rho(d2, sigma)).sum() / mask.sum() * w["full_chamfer"] + \
-            Fn.mse_loss(pose, o_pose) * w["reg_pose_body"] + Fn.mse_loss(betas, o_betas) * w["reg_betas"] + \
-            _accel64(out["joints"]) * w.get("joint_accel", 0.0)
-        loss.backward()
-    return float(loss.detach()), torch.cat([t.grad.reshape(-1) for t in leaves]).numpy()
-
-
-def _ref_marker(smpl64, cfg, markers, o_pose, o_betas, x, assign, bary=None):
-    F = markers.shape[0]
-    st = cfg["stages"]["marker"]
-    w, sigma = st["losses"], float(st.get("robust_sigma", 0.0))
-    from uuo_mocap_amd.engine import MARKER_DISTANCE
-
-    with _float64():
-        x = x.detach().cpu().double()
-        markers, o_pose, o_betas = _d64(markers, o_pose, o_betas)
-        leaves = [t.clone().requires_grad_(True) for t in (x[:207 * F].reshape(F, 23, 3, 3), x[207 * F:207 * F + 10].reshape(1, 10),
-                                                          x[207 * F + 10:216 * F + 10].reshape(F, 1, 3, 3), x[216 * F + 10:].reshape(F, 3))]
-        pose, betas, root, trans = leaves
-        out = stages_ref._smpl_repeat_betas(smpl64, stages_ref.normalize_rot(pose), betas, stages_ref.normalize_rot(root),
-                                            trans)
-        v = out["vertices"]
-        a = assign.cpu().long()
-        vm = v[:, a] if bary is None else (v[:, a] * bary.cpu().double()[None, :, :, None]).sum(2)
-        e = torch.norm(markers - vm, dim=-1) - MARKER_DISTANCE
-        mask = stages_ref.get_marker_mask(markers).double()
-        loss = torch.mean(_rho(e ** 2, sigma) * mask) * w["marker"] + Fn.mse_loss(pose, o_pose) * w["reg_pose_body"] + \
-            Fn.mse_loss(betas, o_betas) * w["reg_betas"] + _accel64(out["joints"]) * w.get("joint_accel", 0.0)
-        loss.backward()
-    return float(loss.detach()), torch.cat([t.grad.reshape(-1) for t in leaves]).numpy()
-
-
-def _three_corners(tables, seq, seed, num_markers=M):
-    gen = torch.Generator().manual_seed(seed)
-    faces = torch.from_numpy(np.asarray(tables.faces).astype(np.int64))
-    vids = torch.from_numpy(np.asarray(seq.gt["marker_vids"])).long()
-    i3 = torch.zeros(num_markers, 3, dtype=torch.int64)
-    b3 = torch.zeros(num_markers, 3)
-    for m in range(num_markers):
-        hit = (faces == vids[m]).any(1).nonzero()
-        tri = faces[hit[0, 0]] if len(hit) else torch.tensor([int(vids[m]), (int(vids[m]) + 1) % 6890, (int(vids[m]) + 2) % 6890])
-        wt = torch.rand(3, generator=gen) + 0.05
-        i3[m], b3[m] = torch.sort(tri)[0], wt / wt.sum()
-    return i3.to(torch.int32), b3
 
 
 # ------------------------------------------------------------------------------------------------ 1. closure parity
@@ -396,14 +274,6 @@ def test_library_refuses_the_term_for_the_part_stage(smpl, tables, dev):
 
 # ------------------------------------------------------------------------------------------------ 6. gap fill
 GAP0, GAP_LEN = 144, 12
-
-
-def _fit(seq, points, cfg_name, smpl, dev):
-    from uuo_mocap_amd.multimodal import multimodal_video_mocap
-
-    return multimodal_video_mocap(copy.deepcopy(seq.img_smpl), SyntheticMarkers(points.copy(), 30.0), dev,
-                                  packaged_config(cfg_name), offset=0, print_options=[], save_stages=False,
-                                  smpl_inference=smpl)
 
 
 def _errors(out, seq, oracle_smpl):

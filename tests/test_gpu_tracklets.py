@@ -13,13 +13,13 @@ import torch.nn.functional as Fn
 pytestmark = pytest.mark.gpu
 
 from oracle import stages_ref  # noqa: E402
-from test_gpu_foot_lock import _contacts, _lock64  # noqa: E402
-from test_gpu_temporal import _accel64, _d64, _float64, _inputs, _rel_err, _rho, dev, smpl, smpl64  # noqa: E402,F401
+from foot_lock_ref64 import _contacts  # noqa: E402
+from gpu_support import (W_ACCEL_M as W_ACCEL, W_LOCK_M as W_LOCK, _fit, _inputs, _rel_err, _vertex_error, dev,  # noqa: E402,F401
+                         smpl, smpl64)
+from stage_ref64 import _accel64, _d64, _float64, _lock64, _rho  # noqa: E402
 from uuo_mocap_amd.config import packaged_config  # noqa: E402
-from uuo_mocap_amd.synthetic import SyntheticMarkers, make_sequence  # noqa: E402
+from uuo_mocap_amd.synthetic import make_sequence  # noqa: E402
 from uuo_mocap_amd.tracklets import Tracklets, segment_tracklets, tracklets_config  # noqa: E402
-
-W_ACCEL, W_LOCK = 1.0, 10.0   # the marker-stage weights of test_gpu_temporal's and test_gpu_foot_lock's parity checks
 
 
 # ------------------------------------------------------------------------------------------------ 1. the placement kernel
@@ -347,20 +347,6 @@ def test_placement_on_the_true_body(smpl, tables, dev, capture, record_property)
     record_property("tracklet_worst_m", worst)
     record_property("column_mean_m", float(col_events.mean()))
     assert worst <= 0.025
-
-
-def _fit(seq, cfg_name, smpl, dev):
-    from uuo_mocap_amd.multimodal import multimodal_video_mocap
-
-    return multimodal_video_mocap(copy.deepcopy(seq.img_smpl), SyntheticMarkers(np.asarray(seq.markers.get_points()).copy(), 30.0),
-                                  dev, packaged_config(cfg_name), offset=0, print_options=[], save_stages=False,
-                                  smpl_inference=smpl)
-
-
-def _vertex_error(out, seq, oracle_smpl):
-    r = oracle_smpl(out["pose_body"].cpu().float(), out["betas"].cpu().float(), out["root_orient"].cpu().float(),
-                    out["trans"].cpu().float())
-    return float((r["vertices"] - torch.from_numpy(seq.gt["verts"])).norm(dim=-1).mean())
 
 
 def test_fit_of_a_capture_with_identity_events(smpl, oracle_smpl, tables, dev, capture, record_property):

@@ -4,18 +4,13 @@ capsule list.  The configurations take turns inside every repeat (alternating ro
 printed.
 python tools/time_capsules.py [--frames 300 --markers 50 --pairs 232]"""
 import argparse
-import os
-import sys
 
 import numpy as np
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from uuo_mocap_amd.body_model import body_capsules, synthetic_smpl  # noqa: E402
-from uuo_mocap_amd.config import packaged_config  # noqa: E402
-from uuo_mocap_amd.engine import ChamferProblem, MarkerProblem  # noqa: E402
-from uuo_mocap_amd.smpl import SmplInference  # noqa: E402
-from uuo_mocap_amd.synthetic import make_sequence  # noqa: E402
+from closure_case import STAGES, stage_case, stage_problems, time_rounds  # (puts the repository on the path: keep it first)
+from uuo_mocap_amd.body_model import body_capsules
+from uuo_mocap_amd.config import packaged_config
 
 
 def main():
@@ -26,21 +21,9 @@ def main():
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--repeats", type=int, default=5)
     a = ap.parse_args()
-    dev = torch.device("cuda:0")
-    tables = synthetic_smpl(0)
-    smpl = SmplInference(dev, tables=tables)
     F, M = a.frames, a.markers
-    seq = make_sequence(tables, seed=0, num_frames=F, num_markers=M)
-    markers = torch.from_numpy(np.nan_to_num(seq.markers.get_points())).float().to(dev)
-    o_pose = seq.img_smpl.pose_body.float().to(dev)
-    o_betas = (seq.img_smpl.betas.sum(0, keepdim=True) / seq.img_smpl.img_mask.sum()).float().to(dev)
-    root = seq.img_smpl.root_orient.float().to(dev)
-    trans = torch.median(markers, dim=1)[0]
-    vids = torch.from_numpy(np.asarray(seq.gt["marker_vids"])).to(torch.int32).to(dev)
-    faces = torch.from_numpy(np.asarray(tables.faces).astype(np.int64))
-    i3 = torch.stack([torch.sort(faces[(faces == int(v)).any(1).nonzero()[0, 0]])[0] for v in vids.cpu()]).to(torch.int32).to(dev)
-    b3 = torch.full((M, 3), 1.0 / 3.0, device=dev)
-    cj, cg, pr = body_capsules(tables)
+    case = stage_case(F, M, torch.device("cuda:0"))
+    cj, cg, pr = body_capsules(case.tables)
     if a.pairs:
         pr = pr[:a.pairs]
     block = {"joints": cj.tolist(), "geom": [[float(v) for v in r] for r in cg], "pairs": pr.tolist()}
@@ -50,22 +33,11 @@ def main():
         for cfg in (caps, both):
             cfg["stages"][k]["capsules"] = block
     labels = (("plain", packaged_config("video_mocap")), ("joint_accel", accel), ("capsules", caps), ("capsules+joint_accel", both))
-    probs, times = {}, {}
-    for label, cfg in labels:
-        probs[label] = {
-            "chamfer": ChamferProblem(smpl, markers, o_pose, o_betas, root, cfg),
-            "marker": MarkerProblem(smpl, markers, o_pose, o_betas, vids, cfg),
-            "marker3": MarkerProblem(smpl, markers, o_pose, o_betas, i3, cfg, bary=b3),
-        }
-    for _ in range(a.repeats):  # alternating rounds: every configuration once per repeat
-        for label, _cfg in labels:
-            for name, p in probs[label].items():
-                x = p.pack(trans, torch.zeros(F, 1, 1, device=dev), o_betas, o_pose) if name == "chamfer" else \
-                    p.pack(o_pose, o_betas, root, trans)
-                times.setdefault((label, name), []).append(p.time_closure(x, iters=a.iters) * 1e3)
+    probs = {label: stage_problems(case.smpl, case, cfg) for label, cfg in labels}
+    times = time_rounds([label for label, _cfg in labels], probs, case, a.repeats, a.iters)
     for label, _cfg in labels:
         line = ["%s %s us (median %.2f)" % (name, " ".join("%.1f" % v for v in times[(label, name)]), np.median(times[(label, name)]))
-                for name in ("chamfer", "marker", "marker3")]
+                for name in STAGES]
         print("closure %-21s F=%d M=%d P=%d  %s" % (label, F, M, len(pr), ";  ".join(line)))
 
 

@@ -7,19 +7,14 @@ of video_mocap.yaml), and with --composed the same fit with video_mocap_rotsmoot
 python tools/time_pose_accel.py [--frames 300 --markers 50] [--fit] [--composed]"""
 import argparse
 import copy
-import os
-import sys
 import time
 
 import numpy as np
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from uuo_mocap_amd.body_model import synthetic_smpl  # noqa: E402
-from uuo_mocap_amd.config import packaged_config  # noqa: E402
-from uuo_mocap_amd.engine import ChamferProblem, MarkerProblem  # noqa: E402
-from uuo_mocap_amd.smpl import SmplInference  # noqa: E402
-from uuo_mocap_amd.synthetic import SyntheticMarkers, make_sequence  # noqa: E402
+from closure_case import STAGES, stage_case, stage_problems, time_rounds  # (puts the repository on the path: keep it first)
+from uuo_mocap_amd.config import packaged_config
+from uuo_mocap_amd.synthetic import SyntheticMarkers
 
 
 def _fit(seq, name, smpl, dev):
@@ -43,19 +38,9 @@ def main():
     ap.add_argument("--composed", action="store_true")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
-    tables = synthetic_smpl(0)
-    smpl = SmplInference(dev, tables=tables)
     F, M = a.frames, a.markers
-    seq = make_sequence(tables, seed=0, num_frames=F, num_markers=M)
-    markers = torch.from_numpy(np.nan_to_num(seq.markers.get_points())).float().to(dev)
-    o_pose = seq.img_smpl.pose_body.float().to(dev)
-    o_betas = (seq.img_smpl.betas.sum(0, keepdim=True) / seq.img_smpl.img_mask.sum()).float().to(dev)
-    root = seq.img_smpl.root_orient.float().to(dev)
-    trans = torch.median(markers, dim=1)[0]
-    vids = torch.from_numpy(np.asarray(seq.gt["marker_vids"])).to(torch.int32).to(dev)
-    faces = torch.from_numpy(np.asarray(tables.faces).astype(np.int64))
-    i3 = torch.stack([torch.sort(faces[(faces == int(v)).any(1).nonzero()[0, 0]])[0] for v in vids.cpu()]).to(torch.int32).to(dev)
-    b3 = torch.full((M, 3), 1.0 / 3.0, device=dev)
+    case = stage_case(F, M, dev)
+    seq, smpl = case.seq, case.smpl
     fused = packaged_config("video_mocap_rotsmooth_fused")
     both = packaged_config("video_mocap_limits")
     both["execution"] = dict(both.get("execution") or {}, pose_accel_fused=True)
@@ -63,25 +48,16 @@ def main():
         both["stages"][k]["losses"]["pose_accel"] = fused["stages"][k]["losses"]["pose_accel"]
     labels = (("plain", packaged_config("video_mocap")), ("joint_limits", packaged_config("video_mocap_limits")),
               ("pose_accel", fused), ("pose_accel+joint_limits", both))
-    probs, times = {}, {}
+    probs = {}
     for label, cfg in labels:
-        probs[label] = {
-            "chamfer": ChamferProblem(smpl, markers, o_pose, o_betas, root, cfg),
-            "marker": MarkerProblem(smpl, markers, o_pose, o_betas, vids, cfg),
-            "marker3": MarkerProblem(smpl, markers, o_pose, o_betas, i3, cfg, bary=b3),
-        }
+        probs[label] = stage_problems(smpl, case, cfg)
         assert all(p.pose_accel_on == label.startswith("pose_accel") for p in probs[label].values())
-    for _ in range(a.repeats):  # alternating rounds: every configuration once per repeat
-        for label, _cfg in labels:
-            for name, p in probs[label].items():
-                x = p.pack(trans, torch.zeros(F, 1, 1, device=dev), o_betas, o_pose) if name == "chamfer" else \
-                    p.pack(o_pose, o_betas, root, trans)
-                times.setdefault((label, name), []).append(p.time_closure(x, iters=a.iters) * 1e3)
+    times = time_rounds([label for label, _cfg in labels], probs, case, a.repeats, a.iters)
     med = {k: float(np.median(v)) for k, v in times.items()}
     for label, _cfg in labels:
         line = ["%s %s us (median %.2f, %+.2f over plain)" % (name, " ".join("%.1f" % v for v in times[(label, name)]),
                                                               med[(label, name)], med[(label, name)] - med[("plain", name)])
-                for name in ("chamfer", "marker", "marker3")]
+                for name in STAGES]
         print("closure %-24s F=%d M=%d  %s" % (label, F, M, ";  ".join(line)))
     if a.fit or a.composed:
         _fit(seq, "video_mocap", smpl, dev)  # warm-up: workspaces, the first launches

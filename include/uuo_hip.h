@@ -155,8 +155,22 @@ int uuo_ring_closest_points(void* stream, uuo_model_t* model, int F, int M, cons
  *   UUO_STAGE_CHAMFER  closure_stage_chamfer   (optimization.py:187-275)  x = [trans 3F | z F | betas 10 | pose 207F]
  *   UUO_STAGE_MARKER   closure_stage_marker_pose (optimization.py:329-394) x = [pose 207F | betas 10 | root 9F | trans 3F]
  *   UUO_STAGE_PART     closure_fit_subtree     (markers/markers_utils.py:454-562) x = [z 1 | trans 3F | betas 10]
+ * and of the root stage (optim_root, optimization.py:21-144: translation, yaw and shape with the body pose held; the reference
+ * cannot run its own -- it reads a config key no config has and an undefined o_betas -- so this is a corrected restatement):
+ *   UUO_STAGE_ROOT         yaw_lock, a yaw per frame          x = [trans 3F | z F | betas 10]
+ *   UUO_STAGE_ROOT_SHARED  constrained_rotation, one yaw      x = [trans 3F | z 1 | betas 10]
+ *     R_f  = Rz(z_f) root_f  (z_0 for every frame in the shared packing; the product as it is, no Gram-Schmidt)
+ *     loss = w_data sum_fm mask_fm min_v |x_fm - v_fv|^2 / sum mask  (all vertices; 0 when sum mask = 0)
+ *          + w_betas mean_l (betas_l - o_betas_l)^2
+ *          + w_tv mean over (F-1) 3 entries of ((trans_{t+1} - trans_t) - (mm_{t+1} - mm_t))^2,  mm_t = mean_m x_tm over ALL
+ *            columns, missing ones (exact zeros) included; F < 2: 0.  w_tv: uuo_fit_set_root_trans_vel
+ *   d_o_pose is the fixed body pose, d_root the input root orientation; w_pose, d_assign and d_subset are not read (the
+ *   whole-body vertex table is the library's own); pose_cache_id must be non-zero (the pose blend is computed once per id);
+ *   w_soft, robust_sigma, w_offsets and every side term of the workspace are refused, and so are lock-step batches
+ *   (uuo_batch_create) and uuo_lbfgs_solve_shared.  d_nn_idx of uuo_closure_eval reports vertex ids.
+ * (3 is not a public value: the library uses it internally.)
  */
-enum { UUO_STAGE_CHAMFER = 0, UUO_STAGE_MARKER = 1, UUO_STAGE_PART = 2 };
+enum { UUO_STAGE_CHAMFER = 0, UUO_STAGE_MARKER = 1, UUO_STAGE_PART = 2, UUO_STAGE_ROOT = 4, UUO_STAGE_ROOT_SHARED = 5 };
 
 typedef struct {
   int32_t stage;             /* UUO_STAGE_* */
@@ -421,7 +435,12 @@ int uuo_fit_surface_corners(uuo_fit_t* fit, void* stream, int32_t* d_corners, fl
  * w_offsets != 0 (an offset per column has no meaning once the column changes identity) and with w_soft != 0, by
  * uuo_lbfgs_solve_shared, and inside lock-step batches (uuo_batch_*). */
 int uuo_fit_set_frame_assign(uuo_fit_t* fit, const int32_t* d_assign_fm);
-/* number of parameters of a stage at (F): 211F+10 / 219F+10 / 3F+11; the marker stage with w_offsets != 0: 219F+10+3M */
+/* The root stages' translation-velocity weight w_tv (stages.root.losses.trans_vel of the reference, optimization.py:106-110).
+ * A setting of the WORKSPACE (0 at creation) that only evaluations of UUO_STAGE_ROOT and UUO_STAGE_ROOT_SHARED read: every
+ * other stage ignores it, so no other problem has to reset it.  w >= 0, finite. */
+int uuo_fit_set_root_trans_vel(uuo_fit_t* fit, float w);
+/* number of parameters of a stage at (F): 211F+10 / 219F+10 / 3F+11; the marker stage with w_offsets != 0: 219F+10+3M; the root
+ * stages: 4F+10 (UUO_STAGE_ROOT) / 3F+11 (UUO_STAGE_ROOT_SHARED) */
 int uuo_problem_num_params(const uuo_problem_t* p);
 
 /* One closure evaluation at d_x: writes loss to d_loss[0] and the flat gradient to d_grad.

@@ -12,6 +12,8 @@ LIB_PATH = os.path.join(_HERE, "libuuo_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "uuo_hip.h")
 
 UUO_STAGE_CHAMFER, UUO_STAGE_MARKER, UUO_STAGE_PART = 0, 1, 2
+# the root stage's two packings: a yaw per frame [trans 3F | z F | betas 10], one yaw [trans 3F | z 1 | betas 10]  (3 is internal)
+UUO_STAGE_ROOT, UUO_STAGE_ROOT_SHARED = 4, 5
 
 
 #: uuo_abi_version() of the library these bindings are written for
@@ -123,6 +125,7 @@ _SIGNATURES = {
     "uuo_assign_segments_argmin": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                            c_void_p, c_void_p]),
     "uuo_fit_set_frame_assign": (c_int, [c_void_p, c_void_p]),
+    "uuo_fit_set_root_trans_vel": (c_int, [c_void_p, c_float]),  # the root stages' translation-velocity weight of the workspace
     "uuo_fit_set_joint_accel": (c_int, [c_void_p, c_float]),  # EXTENSION: joint-acceleration term of the workspace
     "uuo_fit_set_foot_lock": (c_int, [c_void_p, c_float, c_void_p]),  # EXTENSION: foot-lock term of the workspace, its contacts
     # EXTENSION: floor-contact term of the workspace (w_pen, w_con, height, sole vertex ids, k_left, k_right, contacts)

@@ -468,6 +468,11 @@ __device__ __forceinline__ float gmof_q(float sig2, float s) { return sig2 / (si
 // FASSIGN without ITEMS (EXTENSION, marker stage's one-hot closure only; uuo_fit_set_frame_assign): the column's vertex changes
 // with the frame -- item (f, m) reads assign[f][m], an id < 0 is an item of weight 0 (on vertex 0, like every masked item).
 // Nothing else of the item differs.  Separate instantiations: k_bwd_sparse_f / _r_f / _t_f / _r_t_f.
+// ROOT (with PART; UUO_STAGE_ROOT / UUO_STAGE_ROOT_SHARED): the part stage's kernel on ALL vertices.  The launch carries the root
+// stage's own value in a.stage, so the item fetch takes the search's index as the vertex id and weighs the item with the marker
+// mask, as for the chamfer stage; the yaw's gradient d loss / d z_f of the frame stays in slot 1 of its partials (the other
+// instantiations clear the slot for every stage but the part stage), where k_finalize_root picks it up -- per frame, or summed
+// into the one shared entry.  The frame's root is Rz(z_f) root_f as it is (UUO_ROOT_ZSHARED, or pre-multiplied by k_root_yaw).
 // FL: the instantiation is one word of these flags; the names used above and below (PART, NWV, DENSE, ...) are its bits, spelt
 // out in the body's first lines.  BWD_KERNELS, after the body, lists every word that exists.
 enum : unsigned {
@@ -481,6 +486,7 @@ enum : unsigned {
   BWD_FASSIGN = 1u << 7,
   BWD_FLOOR = 1u << 8,
   BWD_WIDE = 1u << 9,  // debug flavour only: the one-array-per-name LDS layout on a general kernel (BWD_WIDE_KERNELS)
+  BWD_ROOT = 1u << 10,  // with BWD_PART: the root stages (BWD_ROOT_KERNELS; not rows of BWD_KERNELS: nothing selects them by facts)
 };
 // The float arrays of a general backward block's LDS, by phase.  (The frame, the tree's tables, w_red, red and the ACCEL window live
 // through all of them and stay outside.)
@@ -534,7 +540,8 @@ template <unsigned FL>
 __device__ __forceinline__ void bwd_body(const BwdArgs& a) {
   constexpr bool PART = (FL & BWD_PART) != 0, DENSE = (FL & BWD_DENSE) != 0, ITEMS = (FL & BWD_ITEMS) != 0;
   constexpr bool ROBUST = (FL & BWD_ROBUST) != 0, ACCEL = (FL & BWD_ACCEL) != 0, OFFS = (FL & BWD_OFFS) != 0;
-  constexpr bool FASSIGN = (FL & BWD_FASSIGN) != 0, FLOOR = (FL & BWD_FLOOR) != 0;
+  constexpr bool FASSIGN = (FL & BWD_FASSIGN) != 0, FLOOR = (FL & BWD_FLOOR) != 0, ROOT = (FL & BWD_ROOT) != 0;
+  static_assert(!ROOT || (PART && !ROBUST), "the root stages run the part stage's plain kernels on all vertices");
   constexpr int NWV = (FL & BWD_ONE_WAVE) ? 1 : BWD_NW;
   static_assert(!FLOOR || (ACCEL && !(FASSIGN && !ITEMS)), "the floor-contact term rides on the temporal instantiations (slot 3 of "
                 "the partials, the frames' FrameLds), outside the per-frame vertex table of the one-hot marker closure");
@@ -1256,7 +1263,7 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a) {
     if constexpr (ITEMS) BWD_FP_STORE(0, red[0] + a.item_loss[f]);  // (the items carry gradients; their frame's loss sum comes beside them)
     else BWD_FP_STORE(0, red[0]);
     BWD_FP_STORE(2, ps);
-    if (a.stage != UUO_STAGE_PART) BWD_FP_STORE(1, 0.f);
+    if (!ROOT && a.stage != UUO_STAGE_PART) BWD_FP_STORE(1, 0.f);
   }
   if constexpr (ACCEL) {
     if (tid == 64) {  // (another wave than the one above) this frame's share of the joint-acceleration term, fixed order
@@ -1370,6 +1377,12 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a) {
     bwd_body<(fl)>(a);                                                                     \
   }
 BWD_KERNELS(BWD_ENTRY, BWD_ENTRY_B)
+// The root stages' two forms of the part stage's kernel (one wave per frame for <= 16 markers, four above).  Not rows of
+// BWD_KERNELS: bwd_select never names them, uuo_closure_eval_impl launches them for UUO_STAGE_ROOT / UUO_STAGE_ROOT_SHARED.
+#define BWD_ROOT_KERNELS(X)                                                        \
+  X(k_bwd_root1, BWD_PART | BWD_ONE_WAVE | BWD_ROOT, 64, BWD_NO_ATTR, BWD_NO_OP)   \
+  X(k_bwd_root, BWD_PART | BWD_ROOT, BWD_NW * 64, BWD_NO_ATTR, BWD_NO_OP)
+BWD_ROOT_KERNELS(BWD_ENTRY)
 
 // the same list as the host sees it
 struct BwdKernel {
@@ -1771,6 +1784,223 @@ __global__ __launch_bounds__(1024) void k_finalize_b(const FinArgs* __restrict__
   finalize_body<1024, false>(a);
 }
 
+// ----------------------------------------------------------------------------------------------------
+// The root stages (UUO_STAGE_ROOT: x = [trans 3F | z F | betas 10], UUO_STAGE_ROOT_SHARED: x = [trans 3F | z 1 | betas 10];
+// reference optimization.py:21-144, restated: include/uuo_hip.h).  The closure is the part stage's cached-pose route on all
+// vertices with the marker mask (k_bwd_root1 / k_bwd_root); what is the root stages' own is here.
+//   k_root_yaw          the per-frame packing's roots M_f = Rz(z_f) root_f, formed with frame_forward's own operations; the frame
+//                       kernels then read them under UUO_ROOT_ZSHARED with a yaw of 0 (Rz(0) is exactly the identity there), and
+//                       the backward's d loss / d z of the frame, <dR_0, E M_f> with E = d Rz / d z at 0, is the per-frame yaw's
+//   k_root_marker_mean  mm_t = mean_m x_tm over all columns, in double, once per public entry (with the marker mask)
+//   k_finalize_root     K_D for these stages: one block, sums in double in an order the indices fix, no atomics (bit-reproducible).
+//                       The frames' partials are summed as finalize_body sums them; the yaw's gradient is written per frame or as
+//                       the frames' sum into the one shared entry; the translation-velocity term
+//                         tvel = ctv sum_{t < F-1, c} r_tc^2,  r_tc = (trans_{t+1,c} - trans_{t,c}) - (mm_{t+1,c} - mm_{t,c})
+//                       adds 2 ctv (r_{t-1,c} - r_{t,c}) to the translation's gradient, which the backward kernel has written
+//                       with the data term alone.  The solver's statistics, the report block and the own-parameter words are
+//                       therefore formed HERE over the gradient as finally written -- the backward kernel's per-frame statistics
+//                       (slots 16..19) were taken before and are not read.
+// ----------------------------------------------------------------------------------------------------
+struct RootFinArgs {
+  int F, shared;                       // shared: one yaw for the sequence (UUO_STAGE_ROOT_SHARED)
+  uuo_gptr<const float> frame_part;    // [F][UUO_FP]: 0 data-loss sum, 1 d loss / d z_f, 4..13 d beta
+  uuo_gptr<const float> trans;         // [F][3] the parameters' translation
+  uuo_gptr<const double> mm;           // [F][3] the markers' mean per frame
+  uuo_gptr<const float> betas, o_betas;
+  double closs;                        // w_data / sum mask (0: no marker present)
+  double cbetas;                       // w_betas / 10
+  double ctv;                          // w_tv / ((F - 1) 3) (0: off, or F < 2)
+  uuo_gptr<float> g_trans, g_z, g_betas, loss;
+  uuo_gptr<const float> dir_trans, dir_z, dir_betas;  // optional: the direction's entries
+  uuo_gptr<double> stats;                              // optional [5], as FinArgs.stats
+  uuo_gptr<unsigned long long> rep_host;               // optional zero-copy report (UuoEvalReport)
+  unsigned long long rep_seq;
+};
+__global__ __launch_bounds__(1024) void k_finalize_root(RootFinArgs a) {
+  __builtin_amdgcn_s_setprio(3);  // latency-bound kernel of a solve chain, as k_finalize
+  __shared__ double sh[32][32];
+  // the threads' five statistics, summed in a fixed order: 32 runs of 32 consecutive threads (wave q takes quantity q; one pad
+  // per run, so that the 32 runs' reads fall into different banks), then the runs (thread q), then thread 0 reads the totals
+  __shared__ double rbuf[5][1056];
+  __shared__ double rruns[5][32];
+  __shared__ double rtot[5];
+  const int tid = threadIdx.x, comp = tid & 31, grp = tid >> 5;
+  const int F = a.F;
+  float pb[10], po[10], pd[10], pdz = 0.f;
+  unsigned long long rep_pre[5] = {0ull, 0ull, 0ull, 0ull, 0ull};
+  if (tid == 0) {  // the tail's inputs, on their way while the partials are summed (finalize_body)
+#pragma unroll
+    for (int l = 0; l < 10; ++l) {
+      pb[l] = a.betas[l];
+      po[l] = a.o_betas[l];
+      pd[l] = a.dir_betas ? a.dir_betas[l] : 0.f;
+    }
+    if (a.shared && a.dir_z) pdz = a.dir_z[0];
+    if (a.stats && a.rep_host) {
+      const unsigned long long* blk = reinterpret_cast<const unsigned long long*>(a.stats.get()) - 1;
+      rep_pre[0] = blk[0];
+#pragma unroll
+      for (int i = 6; i < 10; ++i) rep_pre[i - 5] = blk[i];
+    }
+  }
+  {  // the frames' partials in finalize_body's order: group g takes frames g, g + 32, ..., then the groups in order
+    double acc = 0.0;
+    if (comp < UUO_FP) {
+      for (int f0 = grp; f0 < F; f0 += 32 * 8) {
+        float v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          const int f = f0 + 32 * u;
+          v[u] = (f < F) ? a.frame_part[(size_t)f * UUO_FP + comp] : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) acc += (double)v[u];
+      }
+    }
+    sh[grp][comp] = acc;
+  }
+  __syncthreads();
+  if (tid < 32) {
+    double s = 0.0;
+    for (int g = 0; g < 32; ++g) s += sh[g][tid];
+    sh[0][tid] = s;
+  }
+  __syncthreads();
+  // this thread's entries of the translation (and, per frame, of the yaw): {g.d, sum|g|, g.g, max|g|, sum r^2}
+  double t_sd = 0.0, t_s1 = 0.0, t_s2 = 0.0, t_sm = 0.0, t_tv = 0.0;
+  auto count = [&](float g, const float* dir, int i) {
+    if (dir) t_sd += (double)g * (double)dir[i];
+    t_s1 += fabs((double)g);
+    t_s2 += (double)g * (double)g;
+    t_sm = fmax(t_sm, fabs((double)g));
+  };
+  for (int i = tid; i < 3 * F; i += 1024) {
+    const int t = i / 3;
+    double r_prev = 0.0, r_cur = 0.0;
+    if (a.ctv != 0.0) {  // (block-uniform)
+      const double x0 = (double)a.trans[i], m0 = a.mm[i];
+      if (t >= 1) r_prev = (x0 - (double)a.trans[i - 3]) - (m0 - a.mm[i - 3]);
+      if (t + 1 < F) r_cur = ((double)a.trans[i + 3] - x0) - (a.mm[i + 3] - m0);
+    }
+    const float g = (float)((double)a.g_trans[i] + 2.0 * a.ctv * (r_prev - r_cur));
+    a.g_trans[i] = g;
+    t_tv += r_cur * r_cur;
+    count(g, a.dir_trans.get(), i);
+  }
+  if (!a.shared) {
+    for (int f = tid; f < F; f += 1024) {
+      const float gz = a.frame_part[(size_t)f * UUO_FP + 1];
+      a.g_z[f] = gz;
+      count(gz, a.dir_z.get(), f);
+    }
+  }
+  {
+    const int slot = tid + (tid >> 5);
+    rbuf[0][slot] = t_sd;
+    rbuf[1][slot] = t_s1;
+    rbuf[2][slot] = t_s2;
+    rbuf[3][slot] = t_sm;  // (the maximum of values >= 0)
+    rbuf[4][slot] = t_tv;
+  }
+  __syncthreads();
+  {
+    const int q = tid >> 6, run = tid & 63;  // (q is wave-uniform)
+    if (q < 5 && run < 32) {
+      const double* b = &rbuf[q][run * 33];
+      double r = 0.0;
+#pragma unroll 8
+      for (int u = 0; u < 32; ++u) r = (q == 3) ? fmax(r, b[u]) : r + b[u];
+      rruns[q][run] = r;
+    }
+  }
+  __syncthreads();
+  if (tid < 5) {
+    double r = 0.0;
+#pragma unroll 8
+    for (int u = 0; u < 32; ++u) r = (tid == 3) ? fmax(r, rruns[tid][u]) : r + rruns[tid][u];
+    rtot[tid] = r;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double sd = rtot[0], s1 = rtot[1], s2 = rtot[2], sm = rtot[3];
+    const double tv = rtot[4];
+    if (a.shared) {
+      const float gz = (float)sh[0][1];
+      a.g_z[0] = gz;
+      if (a.dir_z) sd += (double)gz * (double)pdz;
+      s1 += fabs((double)gz);
+      s2 += (double)gz * (double)gz;
+      sm = fmax(sm, fabs((double)gz));
+    }
+    const double own1 = s1, own2 = s2, ownm = sm;  // everything but the shape vector
+    double bsq = 0.0;
+    float gb_local[10];
+#pragma unroll
+    for (int l = 0; l < 10; ++l) {
+      const double diff = (double)pb[l] - (double)po[l];
+      bsq += diff * diff;
+      const float gb = (float)(sh[0][4 + l] + 2.0 * a.cbetas * diff);
+      gb_local[l] = gb;
+      a.g_betas[l] = gb;
+      if (a.dir_betas) sd += (double)gb * (double)pd[l];
+      s1 += fabs((double)gb);
+      s2 += (double)gb * (double)gb;
+      sm = fmax(sm, fabs((double)gb));
+    }
+    const float lossf = (float)((a.closs * sh[0][0] + a.cbetas * bsq) + a.ctv * tv);
+    a.loss[0] = lossf;
+    if (a.stats) {
+      a.stats[0] = (double)lossf;
+      a.stats[1] = sd;
+      a.stats[2] = sm;
+      a.stats[3] = s1;
+      a.stats[4] = s2;
+      if (a.rep_host) {  // the report block, word for word as finalize_body's separate (non-coherent) form writes it
+        const double five[5] = {(double)lossf, sd, sm, s1, s2};
+        a.rep_host[0] = rep_pre[0];
+#pragma unroll
+        for (int i = 0; i < 5; ++i) a.rep_host[1 + i] = (unsigned long long)__double_as_longlong(five[i]);
+#pragma unroll
+        for (int i = 6; i < 10; ++i) a.rep_host[i] = rep_pre[i - 5];
+        a.rep_host[11] = (unsigned long long)__double_as_longlong(ownm);
+        a.rep_host[12] = (unsigned long long)__double_as_longlong(own1);
+        a.rep_host[13] = (unsigned long long)__double_as_longlong(own2);
+#pragma unroll
+        for (int l = 0; l < 10; ++l) a.rep_host[14 + l] = (unsigned long long)__double_as_longlong((double)gb_local[l]);
+        __threadfence_system();
+        __hip_atomic_store(&a.rep_host[10], a.rep_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+      }
+    }
+  }
+}
+__global__ __launch_bounds__(64) void k_root_yaw(int F, const float* __restrict__ z, const float* __restrict__ root,
+                                                 float* __restrict__ out) {
+  const int f = blockIdx.x * 64 + threadIdx.x;
+  if (f >= F) return;
+  float rz[4];
+  rz_entries(z[f], rz);
+  const float* r = root + (size_t)f * 9;
+  float* o = out + (size_t)f * 9;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {  // (frame_forward's Mroot)
+    o[c] = fmaf(rz[1], r[3 + c], rz[0] * r[c]);
+    o[3 + c] = fmaf(rz[3], r[3 + c], rz[2] * r[c]);
+    o[6 + c] = r[6 + c];
+  }
+}
+__global__ __launch_bounds__(256) void k_root_marker_mean(int F, int M, const float* __restrict__ markers, double* __restrict__ mm) {
+  const int i = blockIdx.x * 256 + threadIdx.x;  // one (frame, component) each, the columns in order
+  if (i >= 3 * F) return;
+  const int f = i / 3, c = i - 3 * f;
+  double s = 0.0;
+  for (int m = 0; m < M; ++m) s += (double)markers[((size_t)f * M + m) * 3 + c];
+  mm[i] = s / (double)M;
+}
+__global__ __launch_bounds__(256) void k_root_iota(int n, int32_t* __restrict__ ids) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) ids[i] = i;
+}
+
 // batched launches of this file's kernels (uuo_common.h): 0 = launched, 1 = not one of mine, < 0 = error
 int uuo_batched_launch_closure(int op, hipStream_t s, const void* d_args, int count, int gx, int gy) {
   const BwdKernel* bk = nullptr;  // gy of a part-stage record = waves per frame (1 or BWD_NW; one value per batch: same M)
@@ -1805,6 +2035,8 @@ struct StageLayout {
 // (69 of 211 floats per frame) is then dead weight that the two history passes of every iteration stream for nothing.
 // uuo_stage_compactable decides per solve (it checks the rows against their targets); uuo_lbfgs_solve then runs L-BFGS on
 // n_act = 142 F + 10 (chamfer) / 147 F + 10 (marker: the root's third row has no prior at all) coordinates.
+static bool is_root_stage(int stage) { return stage == UUO_STAGE_ROOT || stage == UUO_STAGE_ROOT_SHARED; }
+static bool stage_known(int stage) { return (stage >= 0 && stage <= 2) || is_root_stage(stage); }
 static StageLayout stage_layout(int stage, int F, bool compact = false) {
   StageLayout s;
   s.n = 0;
@@ -1824,6 +2056,12 @@ static StageLayout stage_layout(int stage, int F, bool compact = false) {
     s.off_trans = 23 * gp * F + 10 + gp * F;
     s.n = 23 * gp * F + 10 + gp * F + 3 * F;
     s.gs_pose = s.gs_root = gp;
+  } else if (is_root_stage(stage)) {  // [trans 3F | z F or 1 | betas 10]: no rotations, so no compact packing
+    const int nz = (stage == UUO_STAGE_ROOT) ? F : 1;
+    s.off_trans = 0;
+    s.off_z = 3 * F;
+    s.off_betas = 3 * F + nz;
+    s.n = 3 * F + nz + 10;
   } else {
     s.off_z = 0;
     s.off_trans = 1;
@@ -1848,7 +2086,7 @@ static StageLayout problem_layout(const uuo_problem_t* p, bool compact = false) 
 }
 
 extern "C" int uuo_problem_num_params(const uuo_problem_t* p) {
-  if (!p || p->F <= 0 || p->stage < 0 || p->stage > 2) return -22;
+  if (!p || p->F <= 0 || !stage_known(p->stage)) return -22;
   return problem_layout(p).n;
 }
 
@@ -1888,6 +2126,7 @@ static int side_terms_check(const uuo_fit* fit, const uuo_problem_t* p) {
   for (const SideTermRow& r : side_term_rows) {
     if (!r.set(fit)) continue;
     const char* not_built = p->stage == UUO_STAGE_PART ? "the part stage"
+                            : is_root_stage(p->stage)  ? "a solve on the root stage (UUO_STAGE_ROOT / UUO_STAGE_ROOT_SHARED)"
                             : p->w_soft != 0.f         ? "the soft-assignment data term (w_soft)"
                                                        : nullptr;
     if (!not_built && !uuo_recorder) continue;
@@ -1935,7 +2174,7 @@ static UuoSideTerms arm_side_terms(const uuo_fit* fit, const uuo_problem_t* p, i
 
 static int validate_problem(const uuo_fit* fit, const uuo_problem_t* p) {
   UUO_REQUIRE(fit && p, "closure: null fit/problem");
-  UUO_REQUIRE(p->stage >= 0 && p->stage <= 2, "closure: unknown stage");
+  UUO_REQUIRE(stage_known(p->stage), "closure: unknown stage");
   UUO_REQUIRE(p->F == fit->F && p->M == fit->M, "closure: problem F/M differ from the workspace");
   UUO_REQUIRE(p->d_markers && p->d_o_pose && p->d_o_betas, "closure: markers / o_pose / o_betas required");
   if (p->stage != UUO_STAGE_MARKER) UUO_REQUIRE(p->d_root != nullptr, "closure: fixed root orientation required");
@@ -1944,6 +2183,12 @@ static int validate_problem(const uuo_fit* fit, const uuo_problem_t* p) {
               "closure: n_corners is 0 / 1 (one-hot placement) or 3 with d_bary (marker stage on a three-corner placement)");
   if (p->stage == UUO_STAGE_PART)
     UUO_REQUIRE(p->d_subset != nullptr && p->n_subset > 0 && p->n_subset <= fit->model->V, "closure: part stage needs a vertex subset");
+  if (is_root_stage(p->stage)) {
+    UUO_REQUIRE(p->pose_cache_id != 0, "closure: the root stage needs a pose cache id (its body pose is fixed: the pose blend is computed once)");
+    UUO_REQUIRE(p->w_soft == 0.f, "closure: the soft-assignment data term (w_soft, extension) is not built on the root stage");
+    UUO_REQUIRE(p->robust_sigma == 0.f, "closure: robust_sigma (Geman-McClure data term, extension) is not built on the root stage");
+    UUO_REQUIRE(!uuo_recorder, "closure: lock-step batches do not carry the root stage (UUO_STAGE_ROOT / UUO_STAGE_ROOT_SHARED)");
+  }
   UUO_REQUIRE(p->w_soft == 0.f || (p->soft_tau > 0.f && p->stage != UUO_STAGE_MARKER), "closure: w_soft (soft-assignment data term, extension) needs soft_tau > 0 and the chamfer or part stage");
   UUO_REQUIRE(p->w_soft == 0.f || p->stage != UUO_STAGE_PART || (p->pose_cache_id != 0 && p->M <= 16),
               "closure: the part stage's soft-assignment term needs a pose cache id and M <= 16");
@@ -2019,16 +2264,46 @@ extern "C" int uuo_fit_set_frame_assign(uuo_fit_t* fit, const int32_t* d_assign_
   return 0;
 }
 
+extern "C" int uuo_fit_set_root_trans_vel(uuo_fit_t* fit, float w) {
+  UUO_REQUIRE(fit, "uuo_fit_set_root_trans_vel: null fit");
+  UUO_REQUIRE(w >= 0.f && w <= 3.0e38f, "uuo_fit_set_root_trans_vel: the weight must be a finite number >= 0");
+  fit->root_tvel = w;
+  return 0;
+}
+
+// the root stages' buffers of a workspace (uuo_common.h), one allocation at the first root problem; the vertex table is filled
+// on `s` (uuo_ensure_mask, the only caller, synchronises it)
+static int root_buffers(uuo_fit* fit, hipStream_t s) {
+  if (fit->root_mm) return 0;
+  const int F = fit->F, V = fit->model->V;
+  const size_t b_mm = ((size_t)F * 3 * sizeof(double) + 255) / 256 * 256, b_m = ((size_t)F * 9 * sizeof(float) + 255) / 256 * 256;
+  char* base = nullptr;
+  UUO_HIP_CHECK(hipMalloc((void**)&base, b_mm + b_m + (size_t)V * sizeof(int32_t)));
+  fit->root_mm = reinterpret_cast<double*>(base);
+  fit->root_m = reinterpret_cast<float*>(base + b_mm);
+  fit->root_ids = reinterpret_cast<int32_t*>(base + b_mm + b_m);
+  hipLaunchKernelGGL(k_root_iota, dim3((V + 255) / 256), dim3(256), 0, s, V, fit->root_ids);
+  UUO_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
 // get_marker_mask + its sum; recomputed at every public entry (markers may have changed under the same pointer)
 int uuo_ensure_mask(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p) {
   int rc = uuo_launch_mask(s, p->F, p->M, p->d_markers, fit->mask, fit->scalars);
   if (rc) return rc;
+  if (is_root_stage(p->stage)) {  // the root stages' own buffers and the markers' mean per frame (the translation-velocity term)
+    rc = root_buffers(fit, s);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_root_marker_mean, dim3((3 * p->F + 255) / 256), dim3(256), 0, s, p->F, p->M, p->d_markers, fit->root_mm);
+    UUO_HIP_CHECK(hipGetLastError());
+  }
   UUO_HIP_CHECK(hipMemcpyAsync(&fit->mask_sum, fit->scalars, sizeof(float), hipMemcpyDeviceToHost, s));
   UUO_HIP_CHECK(hipStreamSynchronize(s));
   return 0;
 }
 
-static UuoPoseSrc stage_pose_src(const uuo_problem_t* p, const StageLayout& lay, const float* x) {
+// (root stages: `fit` gives the per-frame packing its pre-multiplied roots and its yaw of 0 -- stage_pose_src_at fills them)
+static UuoPoseSrc stage_pose_src(const uuo_problem_t* p, const StageLayout& lay, const float* x, const uuo_fit* fit = nullptr) {
   UuoPoseSrc src;
   src.betas = x + lay.off_betas;
   src.betas_stride = 0;
@@ -2045,7 +2320,13 @@ static UuoPoseSrc stage_pose_src(const uuo_problem_t* p, const StageLayout& lay,
     src.norm_body = 1;
     src.root = x + lay.off_root;
     src.root_mode = UUO_ROOT_GS;
-  } else {
+  } else if (p->stage == UUO_STAGE_ROOT) {
+    src.body = p->d_o_pose;
+    src.norm_body = 0;
+    src.root = fit->root_m;
+    src.root_mode = UUO_ROOT_ZSHARED;
+    src.z = fit->zeros16;
+  } else {  // (the part stage and the root stage's shared packing: one yaw, the product as it is)
     src.body = p->d_o_pose;
     src.norm_body = 0;
     src.root = p->d_root;
@@ -2053,6 +2334,17 @@ static UuoPoseSrc stage_pose_src(const uuo_problem_t* p, const StageLayout& lay,
     src.z = x + lay.off_z;
   }
   return src;
+}
+
+// the pose source of an evaluation at x, ready to be read on `s`: the root stage's per-frame packing first forms its roots
+static int stage_pose_src_at(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, const StageLayout& lay, const float* x, UuoPoseSrc* out) {
+  if (p->stage == UUO_STAGE_ROOT) {
+    UUO_REQUIRE(fit->root_m, "closure: the root stage's buffers are missing (uuo_ensure_mask allocates them)");
+    hipLaunchKernelGGL(k_root_yaw, dim3((p->F + 63) / 64), dim3(64), 0, s, p->F, x + lay.off_z, p->d_root, fit->root_m);
+    UUO_HIP_CHECK(hipGetLastError());
+  }
+  *out = stage_pose_src(p, lay, x, fit);
+  return 0;
 }
 
 #ifdef UUO_DEBUG_HOOKS
@@ -2103,7 +2395,11 @@ static int closure_forward(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, 
   const uuo_model* m = fit->model;
   int rc = 0;
   static const int no_cache = UUO_ENV_INT("UUO_PART_NOCACHE", 0);  // comparison only
-  const bool cached = p->stage == UUO_STAGE_PART && p->pose_cache_id != 0 && !no_cache;
+  // the root stages run the part stage's cached-pose routes on the library's whole-body vertex table
+  const bool rootst = is_root_stage(p->stage);
+  const int32_t* const d_subset = rootst ? fit->root_ids : p->d_subset;
+  const int n_subset = rootst ? m->V : p->n_subset;
+  const bool cached = rootst || (p->stage == UUO_STAGE_PART && p->pose_cache_id != 0 && !no_cache);
   if (cached && fit->pose_cache_id != p->pose_cache_id) {
     // first evaluation of a solve whose body pose is constant: C = v_t + P . feat through the MFMA kernel with zero
     // shape, identity skinning transforms and no translation
@@ -2126,15 +2422,15 @@ static int closure_forward(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, 
   if (p->stage == UUO_STAGE_PART && p->w_soft != 0.f && !need_verts) {  // EXTENSION: soft assignment (k_part_soft)
     UUO_REQUIRE(cached && p->M >= 1 && p->M <= 16 && p->soft_tau > 0.f,
                 "closure: the fused soft-assignment part closure needs a pose cache id, 1..16 markers and soft_tau > 0");
-    rc = uuo_launch_pose_prep(m, s, p->F, src, fit->pfaT, fit->A, nullptr, fit->frames, p->d_subset, p->n_subset, fit->part_sb);
+    rc = uuo_launch_pose_prep(m, s, p->F, src, fit->pfaT, fit->A, nullptr, fit->frames, d_subset, n_subset, fit->part_sb);
     if (rc) return rc;
-    return uuo_launch_part_soft(m, s, p->F, p->M, fit->pose_cache, fit->part_sb, fit->A, src.trans, p->d_subset, p->n_subset,
+    return uuo_launch_part_soft(m, s, p->F, p->M, fit->pose_cache, fit->part_sb, fit->A, src.trans, d_subset, n_subset,
                                 p->d_markers, fit->nn, fit->soft_pre, p->w_data, p->w_soft, p->soft_tau);
   }
   if (fused) {
-    rc = uuo_launch_pose_prep(m, s, p->F, src, fit->pfaT, fit->A, nullptr, fit->frames, p->d_subset, p->n_subset, fit->part_sb);
+    rc = uuo_launch_pose_prep(m, s, p->F, src, fit->pfaT, fit->A, nullptr, fit->frames, d_subset, n_subset, fit->part_sb);
     if (rc) return rc;
-    return uuo_launch_part_fwd(m, s, p->F, p->M, fit->pose_cache, fit->part_sb, fit->A, src.trans, p->d_subset, p->n_subset,
+    return uuo_launch_part_fwd(m, s, p->F, p->M, fit->pose_cache, fit->part_sb, fit->A, src.trans, d_subset, n_subset,
                                p->d_markers, fit->nn);
   }
   // The chamfer closure's vertices feed the nearest-vertex SEARCH only (loss and gradient are formed in fp32 on the re-skinned
@@ -2145,7 +2441,7 @@ static int closure_forward(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, 
 #endif
   const int skin16_on = UUO_ENV_INT("UUO_SKIN_F16", UUO_SKIN_F16);  // debug flavour only: the fp32 kernel, for comparison
   const bool skin16 = skin16_on && !cached && !need_verts && !vp_out && p->w_soft == 0.f && p->stage == UUO_STAGE_CHAMFER &&
-                      m->P16 && p->d_subset == nullptr && (m->VP / 16) <= 512 && p->M <= 512;
+                      m->P16 && d_subset == nullptr && (m->VP / 16) <= 512 && p->M <= 512;
   rc = uuo_launch_pose_prep(m, s, p->F, src, fit->pfaT, fit->A, nullptr, fit->frames, nullptr, 0, nullptr, skin16 ? fit->pfa16 : nullptr);
   if (rc) return rc;
   if (cached) {
@@ -2153,17 +2449,17 @@ static int closure_forward(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, 
     // subset order with a box per 16 candidates, then the box-pruned exact search on that compact cloud -- it reports
     // candidate positions (first position on ties) exactly as the brute-force subset search does, at a third of its time
     const int part_brute = UUO_ENV_INT("UUO_PART_BRUTE", 0);  // debug flavour only: the brute-force search, for comparison
-    const int nuc = (p->n_subset + 15) / 16;
-    if (!need_verts && !part_brute && nuc <= 512 && p->M <= 512 && p->n_subset >= 16) {
-      rc = uuo_launch_skin_cached(m, s, p->F, fit->pose_cache, fit->A, src.betas, src.trans, p->d_subset, p->n_subset,
+    const int nuc = (n_subset + 15) / 16;
+    if (!need_verts && !part_brute && nuc <= 512 && p->M <= 512 && n_subset >= 16) {
+      rc = uuo_launch_skin_cached(m, s, p->F, fit->pose_cache, fit->A, src.betas, src.trans, d_subset, n_subset,
                                   fit->verts, fit->bbox);
       if (rc) return rc;
-      return uuo_launch_nn_cull(s, p->F, p->M, p->n_subset, nuc, p->d_markers, fit->verts, fit->bbox, fit->nn, fit->nn_flags);
+      return uuo_launch_nn_cull(s, p->F, p->M, n_subset, nuc, p->d_markers, fit->verts, fit->bbox, fit->nn, fit->nn_flags);
     }
-    rc = uuo_launch_skin_cached(m, s, p->F, fit->pose_cache, fit->A, src.betas, src.trans, p->d_subset, p->n_subset,
+    rc = uuo_launch_skin_cached(m, s, p->F, fit->pose_cache, fit->A, src.betas, src.trans, d_subset, n_subset,
                                 fit->verts);
     if (rc) return rc;
-    return uuo_launch_nn(s, p->F, p->M, m->V, p->d_markers, fit->verts, p->d_subset, p->n_subset, fit->nn);
+    return uuo_launch_nn(s, p->F, p->M, m->V, p->d_markers, fit->verts, d_subset, n_subset, fit->nn);
   }
   const bool cull = (p->d_subset == nullptr) && (m->VP / 16) <= 512 && p->M <= 512;
   {
@@ -2195,7 +2491,8 @@ int uuo_validate_problem(const uuo_fit* fit, const uuo_problem_t* p) { return va
 
 int uuo_closure_forward_at(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, const float* d_x) {
   const StageLayout lay = problem_layout(p);
-  const UuoPoseSrc src = stage_pose_src(p, lay, d_x);
+  UuoPoseSrc src;
+  if (const int rc = stage_pose_src_at(fit, s, p, lay, d_x, &src)) return rc;
   return closure_forward(fit, s, p, src, true);
 }
 
@@ -2295,7 +2592,7 @@ __global__ __launch_bounds__(256) void k_third_rows_differ(int count, const floa
 int uuo_stage_compactable(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, const float* d_x, bool* compact) {
   *compact = false;
   const int off = UUO_ENV_INT("UUO_NO_COMPACT", 0);  // debug flavour only: the full packing, for comparison
-  if (off || p->stage == UUO_STAGE_PART) return 0;
+  if (off || p->stage == UUO_STAGE_PART || is_root_stage(p->stage)) return 0;  // (no rotations among the parameters)
   if (p->w_pose == 0.f) {  // no pose prior: the third rows have no gradient whatever they hold
     *compact = true;
     return 0;
@@ -2351,7 +2648,10 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
   const int F = p->F, M = p->M;
   const StageLayout lay = problem_layout(p);            // the parameters: always the reference's packing
   const StageLayout gl = problem_layout(p, compact);    // gradient and direction: the solver's packing
-  const UuoPoseSrc src = stage_pose_src(p, lay, d_x);
+  UuoPoseSrc src;
+  rc = stage_pose_src_at(fit, s, p, lay, d_x, &src);
+  if (rc) return rc;
+  const bool rootst = is_root_stage(p->stage);
   const bool soft_chamfer = p->stage == UUO_STAGE_CHAMFER && p->w_soft != 0.f;
   bool have_vp = false;
   if (soft_chamfer) {
@@ -2374,7 +2674,7 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
   }
 
   double denom;
-  if (p->stage == UUO_STAGE_CHAMFER)
+  if (p->stage == UUO_STAGE_CHAMFER || rootst)
     denom = (double)fit->mask_sum;  // pytorch3d: div = weights.sum()
   else
     denom = (double)F * (double)M;  // mean over frames and markers
@@ -2397,11 +2697,12 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
               "closure outside lock-step batches");
   a.assign = fassign ? fit->frame_assign : p->d_assign;
   a.subset = p->d_subset;
-  a.raw_pose = (p->stage == UUO_STAGE_PART) ? nullptr : d_x + lay.off_pose;
+  const bool pose_fixed = p->stage == UUO_STAGE_PART || rootst;  // the body pose is an input, not a parameter
+  a.raw_pose = pose_fixed ? nullptr : d_x + lay.off_pose;
   a.o_pose = p->d_o_pose;
   a.raw_root = (p->stage == UUO_STAGE_MARKER) ? d_x + lay.off_root : nullptr;
   a.cg = (float)(2.0 * data_c);
-  a.cpose = (p->stage == UUO_STAGE_PART) ? 0.f : (float)(2.0 * (double)p->w_pose / ((double)F * 207.0));
+  a.cpose = pose_fixed ? 0.f : (float)(2.0 * (double)p->w_pose / ((double)F * 207.0));
   // EXTENSION: latent marker offsets -- the *_o instantiations, d0 = 0 in the data term (the offsets carry the stand-off)
   const bool offs = has_offsets(p);
   UUO_REQUIRE(!offs || !uuo_recorder, "closure: lock-step batches do not carry the latent marker offsets");
@@ -2409,7 +2710,7 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
   // EXTENSION: Geman-McClure data terms run on the *_r instantiations (validate_problem: sigma^2 is a normal fp32 value)
   const bool robust = p->robust_sigma > 0.f;
   a.rs2 = robust ? (float)((double)p->robust_sigma * (double)p->robust_sigma) : 0.f;
-  a.g_pose = (p->stage == UUO_STAGE_PART) ? nullptr : d_grad + gl.off_pose;
+  a.g_pose = pose_fixed ? nullptr : d_grad + gl.off_pose;
   a.g_root = (p->stage == UUO_STAGE_MARKER) ? d_grad + gl.off_root : nullptr;
   a.g_z = (p->stage == UUO_STAGE_CHAMFER) ? d_grad + gl.off_z : nullptr;
   a.g_trans = d_grad + gl.off_trans;
@@ -2423,6 +2724,45 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
   a.off_pose = gl.off_pose; a.off_root = gl.off_root; a.off_z = gl.off_z; a.off_trans = gl.off_trans;
   a.h.gx = F;
   a.h.gy = 1;
+  if (rootst) {
+    // The root stages: the part stage's kernel on all vertices with the marker mask (k_bwd_root1 up to 16 markers, k_bwd_root
+    // above: the forward's one-wave / four-wave split), then their own finalisation.  Side terms: side_terms_check has refused them.
+    UUO_REQUIRE(!uuo_recorder && fit->pose_cache && fit->pose_cache_id == p->pose_cache_id && fit->root_mm,
+                "closure: the root stage runs on its cached pose blend, outside lock-step batches");
+    a.C = fit->pose_cache;
+    if (M <= 16)
+      hipLaunchKernelGGL(k_bwd_root1, dim3(F), dim3(64), 0, s, a);
+    else
+      hipLaunchKernelGGL(k_bwd_root, dim3(F), dim3(BWD_NW * 64), 0, s, a);
+    UUO_HIP_CHECK(hipGetLastError());
+    RootFinArgs ra;
+    std::memset(&ra, 0, sizeof(ra));
+    ra.F = F;
+    ra.shared = p->stage == UUO_STAGE_ROOT_SHARED;
+    ra.frame_part = fit->frame_part;
+    ra.trans = d_x + lay.off_trans;
+    ra.mm = fit->root_mm;
+    ra.betas = d_x + lay.off_betas;
+    ra.o_betas = p->d_o_betas;
+    ra.closs = data_c;
+    ra.cbetas = (double)p->w_betas / 10.0;
+    ra.ctv = (F >= 2) ? (double)fit->root_tvel / ((double)(F - 1) * 3.0) : 0.0;
+    ra.g_trans = d_grad + gl.off_trans;
+    ra.g_z = d_grad + gl.off_z;
+    ra.g_betas = d_grad + gl.off_betas;
+    ra.loss = d_loss;
+    if (d_dir) {
+      ra.dir_trans = d_dir + gl.off_trans;
+      ra.dir_z = d_dir + gl.off_z;
+      ra.dir_betas = d_dir + gl.off_betas;
+    }
+    ra.stats = d_stats;
+    ra.rep_host = (report && d_stats) ? report->host : nullptr;
+    ra.rep_seq = report ? report->seq : 0ull;
+    hipLaunchKernelGGL(k_finalize_root, dim3(1), dim3(1024), 0, s, ra);
+    UUO_HIP_CHECK(hipGetLastError());
+    return 0;
+  }
   FinArgs fa;
   std::memset(&fa, 0, sizeof(fa));
   fa.stage = p->stage; fa.F = F;
@@ -2647,7 +2987,9 @@ extern "C" int uuo_time_closure(uuo_fit_t* fit, void* stream, const uuo_problem_
   float* grad = fit->vecs;  // work vector 0
   rc = uuo_ensure_mask(fit, s, p);
   if (rc) return rc;
-  const UuoPoseSrc src = stage_pose_src(p, lay, d_x);
+  UuoPoseSrc src;
+  rc = stage_pose_src_at(fit, s, p, lay, d_x, &src);
+  if (rc) return rc;
   // warm-up
   rc = dominant_only ? closure_forward(fit, s, p, src, false) : uuo_closure_eval_impl(fit, s, p, d_x, loss, grad, nullptr, nullptr, nullptr);
   if (rc) return rc;

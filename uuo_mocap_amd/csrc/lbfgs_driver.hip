@@ -748,6 +748,7 @@ extern "C" int uuo_fit_destroy(uuo_fit_t* fit) {
   for (UuoUploadedTable* t : {&fit->cap_tab, &fit->lim_tab, &fit->pacc_tab, &fit->gmm_tab}) t->destroy();
   if (fit->upload_stream) (void)hipStreamDestroy(fit->upload_stream);
   if (fit->surf_corners) (void)hipFree(fit->surf_corners);  // (surf_bary is the same allocation)
+  if (fit->root_mm) (void)hipFree(fit->root_mm);            // (root_m and root_ids are the same allocation)
   if (fit->dbg_verts) (void)hipFree(fit->dbg_verts);
   if (fit->ev0) (void)hipEventDestroy(fit->ev0);
   if (fit->ev1) (void)hipEventDestroy(fit->ev1);
@@ -800,6 +801,8 @@ static int shared_prepare(uuo_fit_t* fit, hipStream_t s, const uuo_problem_t* p,
   UUO_REQUIRE(d_x && opt && stats, "uuo_lbfgs_solve_shared: null argument");
   UUO_REQUIRE(opt->max_iter > 0, "uuo_lbfgs_solve_shared: max_iter must be positive");
   UUO_REQUIRE(uuo_recorder == nullptr, "uuo_lbfgs_solve_shared: not inside a lock-step batch");
+  UUO_REQUIRE(p->stage != UUO_STAGE_ROOT && p->stage != UUO_STAGE_ROOT_SHARED,
+              "uuo_lbfgs_solve_shared: shared-betas solves do not carry the root stage (UUO_STAGE_ROOT / UUO_STAGE_ROOT_SHARED)");
   // EXTENSION: the per-evaluation exchange carries the betas' share only, not the latent marker offsets
   UUO_REQUIRE(p->w_offsets == 0.f, "uuo_lbfgs_solve_shared: shared-betas solves do not carry the latent marker offsets (w_offsets, "
               "extension)");

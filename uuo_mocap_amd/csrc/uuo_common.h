@@ -296,6 +296,13 @@ struct uuo_fit {
   float surface_distance = 0.f;
   const int32_t* frame_assign = nullptr;  // EXTENSION: [F][M] per-frame vertex table of the marker stage (uuo_fit_set_frame_assign;
                                           // null = off), the caller's (read at evaluation)
+  // the root stages (UUO_STAGE_ROOT / UUO_STAGE_ROOT_SHARED): the translation-velocity weight (uuo_fit_set_root_trans_vel) and
+  // one allocation made at the first root evaluation: root_ids [V] the whole-body vertex table 0 .. V-1, root_m [F][9] the
+  // pre-multiplied roots Rz(z_f) root_f of the per-frame packing (k_root_yaw), root_mm [F][3] doubles: the markers' mean per frame
+  float root_tvel = 0.f;
+  int32_t* root_ids = nullptr;
+  float* root_m = nullptr;
+  double* root_mm = nullptr;
 };
 
 // ---- dense backward of the skinning (dense_bwd.hip) ---------------------------------------------------------------------

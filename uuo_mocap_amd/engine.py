@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import (EVAL_CALLBACK, UUO_STAGE_CHAMFER, UUO_STAGE_MARKER, UUO_STAGE_PART, UuoLbfgsOptions,
+from ._lib import (EVAL_CALLBACK, UUO_STAGE_CHAMFER, UUO_STAGE_MARKER, UUO_STAGE_PART, UUO_STAGE_ROOT, UUO_STAGE_ROOT_SHARED, UuoLbfgsOptions,
                    UuoLbfgsStats, UuoProblem, UuoReprojectionProblem, check)
 from . import terms
 from .body_model import SmplTables
@@ -172,6 +172,8 @@ def solve_batch(problems, xs, max_iter: int, lr: float = 1.0, tolerance_grad: fl
         raise NotImplementedError(terms.batch_refusal_text("the per-frame vertex table", "tracklets"))
     if any(getattr(p, "surface", False) for p in problems):
         raise NotImplementedError(terms.batch_refusal_text("the point-to-surface chamfer term", "surface_chamfer"))
+    if any(getattr(p, "stage", None) in (UUO_STAGE_ROOT, UUO_STAGE_ROOT_SHARED) for p in problems):
+        raise NotImplementedError("lock-step batches do not carry the root stage (stages.root): solve such problems one by one")
     for p, x in zip(problems, xs):
         assert p.stage == p0.stage and p.F == p0.F and p.M == p0.M and p.model is model
         assert x.is_cuda and x.dtype == torch.float32 and x.numel() == p.n and x.is_contiguous()
@@ -933,6 +935,102 @@ class PartProblem(_StageProblem):
     def unpack(self, x):
         F = self.F
         return x[:1].reshape(1, 1, 1), x[1:3 * F + 1].reshape(F, 3), x[3 * F + 1:].reshape(1, 10)
+
+
+#: the loss keys the root stage's fused closure knows (reference optimization.py:86-117, less what it cannot run)
+ROOT_KEYS = ("full_chamfer", "reg_betas", "trans_vel")
+#: the L-BFGS step of the root stage where stages.root.lr is absent: the chamfer stage's, which optimises the same leaves
+ROOT_DEFAULT_LR = 0.1
+_ROOT_REFUSED = {
+    "root_orient_vel": "its so3_relative_angle is a clamped arc-cosine with no usable gradient (the chamfer stage refuses it too)",
+    "ground": "it stops in a debugger in the reference (optimization.py:114)",
+    "part_chamfer": "the per-part chamfer distance has no fused closure",
+}
+
+
+def root_stage_settings(config: Dict) -> Dict:
+    """stages.root of a config as the root stage runs it: {"shared", "w_data", "w_betas", "w_tvel", "lr", "num_iters"}, or the
+    refusal of what it does not run -- every text names the key, and nothing here touches a device.  `shared`: one yaw for
+    the sequence (constrained_rotation, which the reference tests first), else a yaw per frame (yaw_lock)."""
+    st = config["stages"]["root"]
+    losses = dict(st.get("losses") or {})
+    for key, why in _ROOT_REFUSED.items():
+        if key in losses:
+            raise NotImplementedError("stages.root.losses.%s is not built: %s" % (key, why))
+    extension = set().union(*(t.keys for t in terms.TERMS)) | {terms.SOFT_KEY, terms.SURFACE_KEY}
+    for key in sorted(set(losses) & extension):
+        raise NotImplementedError("stages.root.losses.%s (extension) is not built on the root stage" % key)
+    stage_level = [t.label for t in terms.TERMS if not t.keys] + ["pose_gmm", "keypoints_2d", "joint_limits", "self_penetration",
+                                                                 "pose_accel", "soft_tau", "surface_distance"]
+    for key in stage_level:
+        if st.get(key):
+            raise NotImplementedError("stages.root.%s (extension) is not built on the root stage" % key)
+    unknown = set(losses) - set(ROOT_KEYS)
+    if unknown:
+        raise NotImplementedError("root-stage losses outside the reference's: %s" % sorted(unknown))
+    if not st.get("single_directional", True):
+        raise NotImplementedError("stages.root.single_directional False (the two-directional chamfer distance) is not built")
+    shared = bool(st.get("constrained_rotation", False))
+    if not shared and not st.get("yaw_lock", False):
+        raise NotImplementedError("stages.root with yaw_lock False and constrained_rotation False (a free rotation) is not built: "
+                                  "the reference's branch replaces the root orientation inside the closure and multiplies it "
+                                  "afterwards, so it has no meaning to restate")
+    w = {k: float(losses.get(k, 0.0)) for k in ROOT_KEYS}
+    if any(not (v >= 0.0 and np.isfinite(v)) for v in w.values()):
+        raise ValueError("stages.root.losses: weights must be finite numbers >= 0 (got %s)" % w)
+    return {"shared": shared, "w_data": w["full_chamfer"], "w_betas": w["reg_betas"], "w_tvel": w["trans_vel"],
+            "lr": float(st.get("lr", ROOT_DEFAULT_LR)), "num_iters": int(st["num_iters"])}
+
+
+def _root_refuse_modes(markers, what: str):
+    """The modes the root stage is not built for (before the device is touched)."""
+    from .parallel import frame_shard, shared_betas_reducer
+
+    fs = frame_shard()
+    if fs is not None and fs.active:
+        raise NotImplementedError("%s: frame sharding (parallel.shard_frames) is not built for the root stage" % what)
+    if shared_betas_reducer() is not None:
+        raise NotImplementedError("%s: shared betas (parallel.shared_betas) are not built for the root stage" % what)
+    if not (torch.is_tensor(markers) and markers.is_cuda):
+        raise NotImplementedError("%s: host tensors are refused -- the root stage has a device closure only" % what)
+
+
+class RootProblem(_StageProblem):
+    """optim_root's closure (reference optimization.py:21-144, restated: include/uuo_hip.h): translation, yaw and shape with the
+    body pose held.  x = [trans 3F | z F | betas 10] (yaw_lock) or [trans 3F | z 1 | betas 10] (constrained_rotation).
+    `pose_body` is the fixed body pose, `o_betas` the shape prior's target, `root_orient` the input root orientation."""
+
+    stage = UUO_STAGE_ROOT
+
+    def __init__(self, smpl_inference, markers, pose_body, o_betas, root_orient, config):
+        cfg = root_stage_settings(config)
+        _root_refuse_modes(markers, "RootProblem")
+        self.stage = UUO_STAGE_ROOT_SHARED if cfg["shared"] else UUO_STAGE_ROOT
+        self.shared = cfg["shared"]
+        super().__init__(smpl_inference.device_model, markers, pose_body, o_betas, root_orient, cfg["w_data"], 0.0, cfg["w_betas"])
+        self.problem.pose_cache_id = next(_POSE_CACHE_IDS)  # the body pose is a constant: its pose blend is computed once
+        self.trans_vel = cfg["w_tvel"]
+        self.nz = 1 if self.shared else self.F
+
+    def _arm(self):
+        """Every term of the workspace off (the root stage carries none), then the translation-velocity weight."""
+        super()._arm()
+        check(self.lib.uuo_fit_set_root_trans_vel(self.fit, c_float(self.trans_vel)), "uuo_fit_set_root_trans_vel")
+
+    def solve_shared(self, *args, **kwargs):
+        raise NotImplementedError("shared betas (parallel.shared_betas) are not built for the root stage")
+
+    solve_shared_reference = solve_shared
+
+    def pack(self, trans, z_angle, betas):
+        z = _f32(z_angle, "z").reshape(-1)
+        if z.numel() != self.nz:
+            raise ValueError("RootProblem.pack: %d yaw angle(s) expected (got %d)" % (self.nz, z.numel()))
+        return torch.cat([_f32(trans, "trans").reshape(-1), z, _f32(betas, "betas").reshape(-1)]).contiguous()
+
+    def unpack(self, x):
+        F, nz = self.F, self.nz
+        return x[:3 * F].reshape(F, 3), x[3 * F:3 * F + nz].reshape(nz, 1, 1), x[3 * F + nz:].reshape(1, 10)
 
 
 class ReprojectionProblem:

@@ -3,8 +3,10 @@
 
 Stages (reference :217-677): rigid marker clustering -> part fit (yaw/translation/shape per candidate body
 part) -> for each of `num_root_orient_angles` yaw hypotheses { chamfer L-BFGS -> marker placement -> marker
-L-BFGS } -> best hypothesis by chamfer distance -> final placement + marker L-BFGS.  The reprojection and
-root stages are disabled in every shipped config and are not built."""
+L-BFGS } -> best hypothesis by chamfer distance -> final placement + marker L-BFGS.  The root stage (translation, yaw and
+shape with the pose held; off in video_mocap.yaml, on in video_mocap_root.yaml) runs between the part fit and the hypotheses
+in a corrected form (optimization.optim_root); the full reprojection stage is disabled in every shipped config and not built
+(SURVEY.md 8f)."""
 from __future__ import annotations
 
 import contextlib
@@ -115,16 +117,19 @@ def multimodal_video_mocap(
     exe = markers_utils.merge_execution(config, execution)
     if visualize_fits:
         raise NotImplementedError("visualize_fits renders with pyrender, not built")
-    for key in ("reprojection_full", "root"):
-        # both are disabled in every shipped config and cannot run in the reference as written (reprojection_full calls
-        # optim_reprojection without its img_mask argument, multimodal.py:396-413; optim_root reads an undefined
-        # o_betas and a missing 'lr' key, optimization.py:51,112)
+    for key in ("reprojection_full",):
+        # disabled in every shipped config and unable to run in the reference as written (it calls optim_reprojection without
+        # its img_mask argument, multimodal.py:396-413).  (The root stage, which the reference cannot run either -- optim_root
+        # reads an undefined o_betas and a missing 'lr' key, optimization.py:51,112 -- is built in a corrected form: optim_root.)
         if config["stages"][key]["num_iters"] > 0:
             raise NotImplementedError("stage '%s' is disabled in every shipped config and is not built" % key)
+    run_root = config["stages"]["root"]["num_iters"] > 0
+    if run_root:  # (what the root stage does not run is refused now, before any other stage has worked)
+        optimization.root_stage_settings(config)
     device = torch.device(device)
     if smpl_inference is None:
         smpl_inference = SmplInference(device)
-    stats: Dict = {"part": [], "chamfer": [], "marker": [], "marker_final": [], "timeline": []}
+    stats: Dict = {"part": [], "chamfer": [], "marker": [], "marker_final": [], "timeline": []}  # ("root": when the stage runs)
     t_start = time.perf_counter()
 
     def mark(label: str):  # host-side stage boundaries of this call, seconds since entry (bench.py reports them)
@@ -314,6 +319,17 @@ def multimodal_video_mocap(
 
     if "progress" in print_options:
         print("Stage [root]: optimizing root...")
+    smpl_root = None
+    if run_root:
+        # reference multimodal.py:437-454, with the shape's leaf and its prior target kept apart: the reference passes
+        # betas=o_betas, which would move the prior target of every later stage
+        optimization.optim_root(markers, pose_body=o_pose_body, betas=betas, root_orient=root_orient, trans=trans,
+                                marker_labels=torch.from_numpy(marker_labels).to(device), smpl_inference=smpl_inference,
+                                config=config, verbose=verbose, iter_fn=save_iter_fn, o_betas=o_betas)
+        stats["root"] = dict(optimization.LAST_STATS["root"])
+        smpl_root = {"trans": _np(trans), "root_orient": _np(normalize_rot(root_orient)), "betas": _np(betas[0]),
+                     "pose_body": _np(normalize_rot(o_pose_body))}
+        mark("root")
     pose_body = o_pose_body.clone().requires_grad_(True)
     root_orient = root_orient.detach()
 
@@ -695,6 +711,8 @@ def multimodal_video_mocap(
         output["stages"] = {}
         if config["find_best_part_fits"]:
             output["stages"]["part"] = smpl_part
+        if smpl_root is not None:
+            output["stages"]["root"] = smpl_root
         if run_chamfer:
             output["stages"]["chamfer"] = smpl_chamfer
         if run_marker:

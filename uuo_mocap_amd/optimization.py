@@ -13,7 +13,7 @@ import torch.nn.functional as F
 
 from .device_lbfgs import DeviceLBFGS
 from .config import stage_surface
-from .engine import MARKER_DISTANCE, ChamferProblem, MarkerProblem
+from .engine import MARKER_DISTANCE, ChamferProblem, MarkerProblem, RootProblem, _root_refuse_modes, root_stage_settings
 from .losses import (MarkerLoss, RobustMarkerLoss, chamfer_distance, floor_loss, foot_lock_loss, joint_accel_loss,  # noqa: F401  (re-exported)
                      self_penetration_loss, joint_limit_loss, pose_accel_loss, weighted_pose_prior,
                      robust_weighted_chamfer_distance, soft_weighted_chamfer_distance, surface_chamfer_distance,
@@ -38,10 +38,53 @@ def _printer(tag: str, verbose: bool):
     return lambda i, loss: print(tag, i, float(loss))
 
 
-def optim_root(*args, **kwargs):
-    """reference optimization.py:21-144.  Disabled in every shipped config (stages.root.num_iters: 0) and not
-    runnable as written there (undefined o_betas :112, missing config key 'lr' :51) -- not reproduced."""
-    raise NotImplementedError("optim_root is disabled in every shipped configuration of the reference")
+def optim_root(
+    markers: torch.Tensor,  # [F, M, 3]
+    pose_body: torch.Tensor,  # [F, J-1, 3, 3]
+    betas: torch.Tensor,  # [1, 10]
+    root_orient: torch.Tensor,  # [F, 1, 3, 3]
+    trans: torch.Tensor,  # [F, 3]
+    marker_labels: torch.Tensor,  # [F, M]
+    smpl_inference: SmplInference,
+    config: Dict,
+    verbose: bool = False,
+    iter_fn: Callable = None,
+    o_betas: torch.Tensor = None,
+):
+    """Root stage (reference optimization.py:21-144): L-BFGS over [trans, z_angle, betas] with the body pose held -- a translation
+    per frame, a yaw per frame (yaw_lock) or one yaw for the sequence (constrained_rotation), and the shape.  Mutates trans and
+    betas in place and applies the optimised yaw to root_orient in place (:136-144).  The reference cannot run its own: it reads
+    stages.root.lr, which no config has (here: default 0.1, the chamfer stage's), and an undefined `o_betas` (:112) -- here an
+    argument, None = the value of `betas` at entry.  What its closure cannot run is refused with the key in the text
+    (engine.root_stage_settings), before the device is touched; `marker_labels` is read by part_chamfer alone and unused."""
+    settings = root_stage_settings(config)
+    _root_refuse_modes(markers, "optim_root")
+    target = (betas if o_betas is None else o_betas).detach().clone()
+    prob = RootProblem(smpl_inference, markers, pose_body, target, root_orient, config)
+    z_angle = torch.zeros((prob.nz, root_orient.shape[1], 1), device=root_orient.device)
+    x = prob.pack(trans, z_angle, betas)
+    point_cb = None
+    if iter_fn is not None:
+        pose_np = pose_body.detach().cpu().numpy()
+        root_in = root_orient.detach().cpu()
+
+        def point_cb(i, loss, x_eval):  # what closure_stage_translation hands to iter_fn after every evaluation (:123-131)
+            e_trans, e_z, e_betas = prob.unpack(x_eval)
+            z_root = compute_root_orient_z(e_z.expand(prob.F, 1, 1)) @ root_in
+            iter_fn(stage="root", iteration=i, pose_body=pose_np, betas=e_betas.numpy().copy(), trans=e_trans.numpy().copy(),
+                    root_orient=normalize_rot(z_root).numpy())
+
+    stats = _solve(prob, x, config, "root", settings["lr"], "Root", verbose, point_cb)
+    new_trans, new_z, new_betas = prob.unpack(x)
+    with torch.no_grad():
+        trans.copy_(new_trans)
+        betas.copy_(new_betas)
+        root_orient.requires_grad_(False)
+        root_orient[:] = compute_root_orient_z(new_z.expand(prob.F, 1, 1)) @ root_orient
+    root_orient.requires_grad_(True)
+    LAST_STATS["root"] = stats
+    _tls_stats.root = stats
+    return None
 
 
 def optim_chamfer(

@@ -7,6 +7,7 @@ import itertools
 from uuo_mocap_amd import _lib
 
 CHAMFER, MARKER, PART, UPSTREAM = _lib.UUO_STAGE_CHAMFER, _lib.UUO_STAGE_MARKER, _lib.UUO_STAGE_PART, 3
+ROOTS = (_lib.UUO_STAGE_ROOT, _lib.UUO_STAGE_ROOT_SHARED)
 FACTS = ("stage", "part_cached", "one_wave", "three_corner", "surface", "soft_chamfer", "robust", "temporal", "offs", "fassign",
          "floor")
 REFUSED, UNREACHABLE = "refused", "unreachable"
@@ -38,6 +39,10 @@ def _ladders(stage, part_cached, one_wave, three_corner, surface, soft_chamfer, 
         if part_cached or three_corner or surface or robust or temporal or offs or fassign or floor:
             return UNREACHABLE
         return "k_bwd_dense" if soft_chamfer else "k_bwd_sparse"
+    if stage in ROOTS:  # the part stage's kernel on all vertices, launched by hand before the selector named it; nothing else
+        if part_cached or three_corner or surface or soft_chamfer or robust or temporal or offs or fassign or floor:
+            return UNREACHABLE  # (validate_problem and side_terms_check turn every one of them away)
+        return "k_bwd_root1" if one_wave else "k_bwd_root"
     # facts that are functions of one another: the cached pose blend is the part stage's, the three-corner placement and the
     # latent offsets are the marker stage's, the soft chamfer closure is the chamfer stage's, the floor term is a temporal term
     if (part_cached and stage != PART) or (three_corner and stage != MARKER) or (offs and stage != MARKER) or \
@@ -84,11 +89,14 @@ def test_selector_is_the_ladders_it_replaced():
     rows = _table(dbg)
     names = {n for n, _ in rows}
     reached = set()
-    for stage in (CHAMFER, MARKER, PART, UPSTREAM):
+    for stage in (CHAMFER, MARKER, PART, UPSTREAM) + ROOTS:
         for bits in itertools.product((False, True), repeat=10):
             facts = dict(zip(FACTS, (stage,) + bits))
             want = _ladders(**facts)
             if want == UNREACHABLE:
+                if stage in ROOTS:  # no problem produces it, and the selector does not lean on that
+                    got, detail = _select(dbg, facts)
+                    assert got == REFUSED and "no backward kernel" in detail and "stage %d" % stage in detail, (facts, got, detail)
                 continue
             got, detail = _select(dbg, facts)
             assert got == want, (facts, got, detail)

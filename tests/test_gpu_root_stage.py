@@ -79,6 +79,10 @@ def test_closure_against_float64(smpl, smpl64, tables, dev, record_property, sha
     """Loss within 2e-5 and gradient within gpu_support._check_grad of the float64 restatement at the reported assignment.  F:
     no velocity pair, one pair, the first interior frame, more frames than the finalisation has groups; M: both sides of the
     one-wave / fused-forward boundary (16 | 17)."""
+    _closure_against_float64(smpl, smpl64, tables, dev, record_property, shared, F, M, tvel)
+
+
+def _closure_against_float64(smpl, smpl64, tables, dev, record_property, shared, F, M, tvel):  # noqa: F811
     markers, o_pose, o_betas, root, pert = _case(tables, F, M, 1000 + 10 * F + M)
     mask_sum = int((markers.abs().sum(-1) != 0).sum())
     assert 0 < mask_sum and (mask_sum != F * M or (M == 1 and F == 1))
@@ -99,6 +103,14 @@ def test_closure_against_float64(smpl, smpl64, tables, dev, record_property, sha
         assert ratio >= 0.1, (name, ratio)
     np.testing.assert_allclose(loss, lo, rtol=2e-5, err_msg=name)
     _check_grad(grad.cpu().numpy(), g_ref, _blocks(F, shared), name, record_property)
+
+
+@pytest.mark.parametrize("shared", [False, True])
+def test_finalisation_loops_past_their_first_round(smpl, smpl64, tables, dev, record_property, shared):  # noqa: F811
+    """test_closure_against_float64's asserts at F = 1025, M = 17 with trans_vel on: every loop of k_finalize_root takes a second
+    round there -- the partial sums stride 256 frames, the translation's entries 1024 (3 F > 1024), the per-frame yaw's 1024
+    frames (F > 1024)."""
+    _closure_against_float64(smpl, smpl64, tables, dev, record_property, shared, 1025, 17, W_TVEL)
 
 
 @pytest.mark.parametrize("shared", [False, True])
@@ -168,6 +180,7 @@ def test_shared_packing_agrees_with_a_part_problem_on_all_vertices(smpl, tables,
     same = loss == loss_p and torch.equal(grad, g_part) and torch.equal(nn, nn_p)
     record_property("bit_identical_to_part_M%d" % M, bool(same))
     print("root (shared) against part on all vertices, M = %d: bit-identical %s; loss %.8g / %.8g" % (M, same, loss, loss_p))
+    assert same
     assert torch.equal(nn, nn_p)
     np.testing.assert_allclose(loss, loss_p, rtol=2e-5)
     _check_grad(grad.cpu().numpy(), g_part.cpu().numpy().astype(np.float64), _blocks(F, True), "root_vs_part_M%d" % M,

@@ -102,7 +102,7 @@ extern "C" int uuo_batch_destroy(uuo_batch_t* b) {
 
 extern "C" int uuo_batch_create(uuo_model_t* model, int stage, int F, int M, int B, uuo_batch_t** out) {
   UUO_REQUIRE(model && out, "uuo_batch_create: null argument");
-  UUO_REQUIRE(stage != UUO_STAGE_ROOT && stage != UUO_STAGE_ROOT_SHARED,
+  UUO_REQUIRE(!uuo_is_root_stage(stage),
               "uuo_batch_create: lock-step batches do not carry the root stage (UUO_STAGE_ROOT / UUO_STAGE_ROOT_SHARED)");
   UUO_REQUIRE(stage >= 0 && stage <= 2 && F > 0 && M > 0 && B > 0 && B <= 4096, "uuo_batch_create: bad stage / sizes");
   uuo_batch* b = new uuo_batch();

@@ -120,6 +120,18 @@ struct OffsFinArgs {
   float d0;                    // the prior's stand-off length (marker_distance)
 };
 
+// the root stages' finalize (k_finalize_root; UUO_STAGE_ROOT / UUO_STAGE_ROOT_SHARED): FinArgs as for every stage (cpose is not
+// read; g_z / dir_z: the yaw's F entries, or the shared packing's one) and what is the root stages' own
+struct RootFinArgs {
+  FinArgs fin;
+  int shared;                       // one yaw for the sequence (UUO_STAGE_ROOT_SHARED)
+  uuo_gptr<const float> trans;      // [F][3] the parameters' translation
+  uuo_gptr<const double> mm;        // [F][3] the markers' mean per frame
+  double ctv;                       // w_tv / ((F - 1) 3) (0: off, or F < 2)
+  uuo_gptr<float> g_trans;          // [F][3] in: the data term's gradient (the backward kernel's), out: with the velocity term's
+  uuo_gptr<const float> dir_trans;  // optional: the direction's entries
+};
+
 // the offsets' data gradient of one (marker, component): frames grp, grp + G, ... of the per-item partials, K items per marker
 // summed per frame in fp32, the frames in double, in a fixed order; 16 frames (16 K loads) in flight per round
 template <int K>
@@ -144,6 +156,38 @@ __device__ __forceinline__ double offs_frame_sum(const float* __restrict__ base,
   return acc;
 }
 
+// Five statistics of every thread of a 1024-thread block -- {g.d, sum|g|, g.g, max|g| (of values >= 0), one more sum} -- reduced
+// in a fixed order: 32 runs of 32 consecutive threads (wave q takes quantity q; one pad per run, so that the 32 runs' reads fall
+// into different banks), then the runs (thread q).  After the last barrier tot[] holds the five results.  (Three arrays of the
+// caller's, not one struct: a struct of this size is padded to 16 bytes.)
+__device__ __forceinline__ void fin_reduce5(double (&buf)[5][1056], double (&runs)[5][32], double (&tot)[5], const double (&tv)[5]) {
+  const int tid = threadIdx.x;
+  {
+    const int slot = tid + (tid >> 5);
+#pragma unroll
+    for (int q = 0; q < 5; ++q) buf[q][slot] = tv[q];
+  }
+  __syncthreads();
+  {
+    const int q = tid >> 6, run = tid & 63;  // (q is wave-uniform)
+    if (q < 5 && run < 32) {
+      const double* b = &buf[q][run * 33];
+      double s = 0.0;
+#pragma unroll 8
+      for (int u = 0; u < 32; ++u) s = (q == 3) ? fmax(s, b[u]) : s + b[u];
+      runs[q][run] = s;
+    }
+  }
+  __syncthreads();
+  if (tid < 5) {
+    double s = 0.0;
+#pragma unroll 8
+    for (int u = 0; u < 32; ++u) s = (tid == 3) ? fmax(s, runs[tid][u]) : s + runs[tid][u];
+    tot[tid] = s;
+  }
+  __syncthreads();
+}
+
 // ----------------------------------------------------------------------------------------------------
 // K_D  finalize: sums the per-frame partials in a fixed order (double accumulators), adds the shape
 // prior, writes the loss and the shared-parameter gradients (betas; z for the part stage).
@@ -160,9 +204,16 @@ __device__ __forceinline__ double offs_frame_sum(const float* __restrict__ base,
 // the per-item partials over frames and over a marker's items (no atomics: groups of frames summed in double in a fixed order,
 // then the groups in order); the prior w/M sum_m (|o_m| - d0)^2 adds (2 w/M)(|o_m| - d0) o_m/|o_m| (0 at o_m = 0) and its loss.
 // The offsets' entries join the loss and the fused statistics.  Separate instantiations (k_finalize_o, k_finalize_to).
-template <int NT, bool COHERENT, bool ACCEL = false, bool OFFS = false>
-__device__ __forceinline__ void finalize_body(const FinArgs& a, const OffsFinArgs* ob = nullptr) {
-  static_assert(!OFFS || (NT == 1024 && !COHERENT), "the offsets' reduction is built for the separate 1024-thread finalize");
+// ROOT (UUO_STAGE_ROOT / UUO_STAGE_ROOT_SHARED; k_finalize_root, described at its entry point): `rb` holds the root stages' own.
+// The translation-velocity term joins the translation's gradient and the loss, the yaw's gradient is written per frame or as the
+// frames' sum, and the statistics are formed over the gradient as finally written: slots 16..19 of the partials are not read.
+// The tail's inputs, the frames' sums, the shape prior and the report are the code every instantiation runs.
+template <int NT, bool COHERENT, bool ACCEL = false, bool OFFS = false, bool ROOT = false>
+__device__ __forceinline__ void finalize_body(const FinArgs& a, const OffsFinArgs* ob = nullptr,
+                                              const RootFinArgs* rb = nullptr) {
+  static_assert(!(OFFS || ROOT) || (NT == 1024 && !COHERENT), "the offsets' and the root stages' reductions are built for the separate "
+                "1024-thread finalize");
+  static_assert(!ROOT || (!ACCEL && !OFFS), "the root stages carry no side term and no latent offsets");
   __builtin_amdgcn_s_setprio(3);  // latency-bound kernel: do not queue behind co-resident MFMA waves
   __shared__ double sh[32][32];
   const int tid = threadIdx.x;
@@ -191,7 +242,7 @@ __device__ __forceinline__ void finalize_body(const FinArgs& a, const OffsFinArg
     const int grp = (tid >> 5) + gi * (NT / 32);
     double acc = 0.0;
     if (comp < UUO_FP) {
-      const bool is_max = (comp == 19);
+      const bool is_max = !ROOT && comp == 19;  // (ROOT: slots 16..19 are not read, a plain sum will do)
       for (int f0 = grp; f0 < a.F; f0 += 32 * 8) {  // 8 independent loads in flight per thread
         float v[8];
 #pragma unroll
@@ -212,7 +263,7 @@ __device__ __forceinline__ void finalize_body(const FinArgs& a, const OffsFinArg
   __syncthreads();
   if (tid < 32) {
     double s = 0.0;
-    if (tid == 19) {
+    if (!ROOT && tid == 19) {
       for (int g = 0; g < 32; ++g) s = fmax(s, sh[g][tid]);
     } else {
       for (int g = 0; g < 32; ++g) s += sh[g][tid];
@@ -221,76 +272,116 @@ __device__ __forceinline__ void finalize_body(const FinArgs& a, const OffsFinArg
   }
   __syncthreads();
   // OFFS: {g.d, sum|g|, g.g, max|g|, prior sum (|o| - d0)^2} over the offsets' entries, for thread 0 below
+  // ROOT: {g.d, sum|g|, g.g, max|g|, sum r^2} over the translation's entries and, per frame, the yaw's
   double so_tot[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-  if constexpr (OFFS) {
-    __shared__ double so_grp[1024];
-    __shared__ double so_st[5][32];
-    __shared__ double so_sum[5];
-    const OffsFinArgs& o = *ob;
-    const int C = 3 * o.M, MK = o.M * o.K;
-    double t_sd = 0.0, t_s1 = 0.0, t_s2 = 0.0, t_sm = 0.0, t_pl = 0.0;
-    for (int i0 = 0; i0 < C; i0 += 1024) {  // chunks of <= 1024 entries; G groups of frames per entry
-      const int Cc = min(C - i0, 1024), G = 1024 / Cc;
-      if (tid < G * Cc) {
-        const int grp = tid / Cc, i = i0 + (tid - grp * Cc), mk = i / 3, c = i - 3 * mk;
-        const float* base = o.part.get() + (size_t)mk * o.K * 3 + c;
-        so_grp[tid] = (o.K == 3) ? offs_frame_sum<3>(base, grp, G, a.F, (size_t)MK * 3)
-                                 : offs_frame_sum<1>(base, grp, G, a.F, (size_t)MK * 3);
+  if constexpr (OFFS || ROOT) {
+    __shared__ double rbuf[5][1056], rruns[5][32], rtot[5];
+    double t_sd = 0.0, t_s1 = 0.0, t_s2 = 0.0, t_sm = 0.0, t_pl = 0.0;  // (t_pl: the fifth sum, the prior's or the velocity term's)
+    if constexpr (ROOT) {
+      const RootFinArgs& r = *rb;
+      const int F = a.F;
+      auto count = [&](float g, const float* dir, int i) {
+        if (dir) t_sd += (double)g * (double)dir[i];
+        t_s1 += fabs((double)g);
+        t_s2 += (double)g * (double)g;
+        t_sm = fmax(t_sm, fabs((double)g));
+      };
+      for (int i = tid; i < 3 * F; i += 1024) {
+        const int t = i / 3;
+        double r_prev = 0.0, r_cur = 0.0;
+        if (r.ctv != 0.0) {  // (block-uniform)
+          const double x0 = (double)r.trans[i], m0 = r.mm[i];
+          if (t >= 1) r_prev = (x0 - (double)r.trans[i - 3]) - (m0 - r.mm[i - 3]);
+          if (t + 1 < F) r_cur = ((double)r.trans[i + 3] - x0) - (r.mm[i + 3] - m0);
+        }
+        const float g = (float)((double)r.g_trans[i] + 2.0 * r.ctv * (r_prev - r_cur));
+        r.g_trans[i] = g;
+        t_pl += r_cur * r_cur;
+        count(g, r.dir_trans.get(), i);
       }
-      __syncthreads();
-      if (tid < Cc) {
-        const int i = i0 + tid, mk = i / 3, c = i - 3 * mk;
-        double s = so_grp[tid];
-        for (int grp = 1; grp < G; ++grp) s += so_grp[grp * Cc + tid];
-        const float o0 = o.o[mk * 3], o1 = o.o[mk * 3 + 1], o2 = o.o[mk * 3 + 2];
-        const double r = sqrt((double)o0 * o0 + (double)o1 * o1 + (double)o2 * o2), e = r - (double)o.d0;
-        const double oc = (c == 0) ? o0 : ((c == 1) ? o1 : o2);
-        if (r > 0.0) s += 2.0 * o.cprior * e * oc / r;
-        if (c == 0) t_pl += e * e;
-        const float gf = (float)s;
-        o.g[i] = gf;
-        if (o.dir) t_sd += (double)gf * (double)o.dir[i];
-        t_s1 += fabs((double)gf);
-        t_s2 += (double)gf * (double)gf;
-        t_sm = fmax(t_sm, fabs((double)gf));
+      if (!r.shared) {
+        for (int f = tid; f < F; f += 1024) {
+          const float gz = a.frame_part[(size_t)f * UUO_FP + 1];
+          a.g_z[f] = gz;
+          count(gz, a.dir_z.get(), f);
+        }
       }
-      __syncthreads();
+    } else {
+      // (the chunks' group sums lie in the reduction's buffer: the chunk loop's closing barrier stands between their last read
+      // and fin_reduce5's first write)
+      double* so_grp = &rbuf[0][0];
+      static_assert(sizeof(rbuf) >= 1024 * sizeof(double), "so_grp: one double per thread");
+      const OffsFinArgs& o = *ob;
+      const int C = 3 * o.M, MK = o.M * o.K;
+      for (int i0 = 0; i0 < C; i0 += 1024) {  // chunks of <= 1024 entries; G groups of frames per entry
+        const int Cc = min(C - i0, 1024), G = 1024 / Cc;
+        if (tid < G * Cc) {
+          const int grp = tid / Cc, i = i0 + (tid - grp * Cc), mk = i / 3, c = i - 3 * mk;
+          const float* base = o.part.get() + (size_t)mk * o.K * 3 + c;
+          so_grp[tid] = (o.K == 3) ? offs_frame_sum<3>(base, grp, G, a.F, (size_t)MK * 3)
+                                   : offs_frame_sum<1>(base, grp, G, a.F, (size_t)MK * 3);
+        }
+        __syncthreads();
+        if (tid < Cc) {
+          const int i = i0 + tid, mk = i / 3, c = i - 3 * mk;
+          double s = so_grp[tid];
+          for (int grp = 1; grp < G; ++grp) s += so_grp[grp * Cc + tid];
+          const float o0 = o.o[mk * 3], o1 = o.o[mk * 3 + 1], o2 = o.o[mk * 3 + 2];
+          const double r = sqrt((double)o0 * o0 + (double)o1 * o1 + (double)o2 * o2), e = r - (double)o.d0;
+          const double oc = (c == 0) ? o0 : ((c == 1) ? o1 : o2);
+          if (r > 0.0) s += 2.0 * o.cprior * e * oc / r;
+          if (c == 0) t_pl += e * e;
+          const float gf = (float)s;
+          o.g[i] = gf;
+          if (o.dir) t_sd += (double)gf * (double)o.dir[i];
+          t_s1 += fabs((double)gf);
+          t_s2 += (double)gf * (double)gf;
+          t_sm = fmax(t_sm, fabs((double)gf));
+        }
+        __syncthreads();
+      }
     }
-    // fixed-order reduction of the threads' statistics: 32 runs of 32 threads, then the runs
     const double tv[5] = {t_sd, t_s1, t_s2, t_sm, t_pl};
-    for (int q = 0; q < 5; ++q) {
-      so_grp[tid] = tv[q];
-      __syncthreads();
-      if (tid < 32) {
-        double s = 0.0;
-        for (int u = 0; u < 32; ++u) s = (q == 3) ? fmax(s, so_grp[tid * 32 + u]) : s + so_grp[tid * 32 + u];
-        so_st[q][tid] = s;
-      }
-      __syncthreads();
-    }
-    if (tid < 5) {
-      double s = 0.0;
-      for (int u = 0; u < 32; ++u) s = (tid == 3) ? fmax(s, so_st[tid][u]) : s + so_st[tid][u];
-      so_sum[tid] = s;
-    }
-    __syncthreads();
+    fin_reduce5(rbuf, rruns, rtot, tv);
     if (tid == 0)
-      for (int q = 0; q < 5; ++q) so_tot[q] = so_sum[q];
+      for (int q = 0; q < 5; ++q) so_tot[q] = rtot[q];
   }
   if (tid == 0) {
     double bsq = 0.0, sd = sh[0][16], s1 = sh[0][17], s2 = sh[0][18], sm = sh[0][19];
+    double root_own[3] = {0.0, 0.0, 0.0};
+    float gb_local[10];  // the shape gradient as written, for the report
+    if constexpr (ROOT) {  // the backward kernel's statistics predate the velocity term: these stages' start from their own
+      sd = so_tot[0];
+      s1 = so_tot[1];
+      s2 = so_tot[2];
+      sm = so_tot[3];
+      if (rb->shared) {
+        const float gz = (float)sh[0][1];
+        a.g_z[0] = gz;
+        if (a.dir_z) sd += (double)gz * (double)pdz;
+        s1 += fabs((double)gz);
+        s2 += (double)gz * (double)gz;
+        sm = fmax(sm, fabs((double)gz));
+      }
+      root_own[0] = s1;  // everything but the shape vector
+      root_own[1] = s2;
+      root_own[2] = sm;
+    }
     for (int l = 0; l < 10; ++l) {
       const double diff = (double)pb[l] - (double)po[l];
       bsq += diff * diff;
       const float gb = (float)(sh[0][4 + l] + 2.0 * a.cbetas * diff);
       a.g_betas[l] = gb;
+      if constexpr (ROOT) gb_local[l] = gb;  // (the same bits as the recomputation below, which costs this closure 0.3 us: 4aa)
       if (a.dir_betas) sd += (double)gb * (double)pd[l];
       s1 += fabs((double)gb);
       s2 += (double)gb * (double)gb;
       sm = fmax(sm, fabs((double)gb));
     }
     float lossf;
-    if constexpr (OFFS) {
+    if constexpr (ROOT) {
+      lossf = (float)((a.closs * sh[0][0] + a.cbetas * bsq) + rb->ctv * so_tot[4]);
+    } else if constexpr (OFFS) {
       sd += so_tot[0];
       s1 += so_tot[1];
       s2 += so_tot[2];
@@ -306,14 +397,20 @@ __device__ __forceinline__ void finalize_body(const FinArgs& a, const OffsFinArg
     // the statistics of this problem's OWN parameters (everything but the shape vector), for solves that share the betas
     // with other ranks (uuo_lbfgs_solve_shared: the betas' gradient is summed over the ranks before it enters any norm)
     double own1 = sh[0][17], own2 = sh[0][18], ownm = sh[0][19];
+    if constexpr (ROOT) {
+      own1 = root_own[0];
+      own2 = root_own[1];
+      ownm = root_own[2];
+    }
     if constexpr (OFFS) {
       own1 += so_tot[1];
       own2 += so_tot[2];
       ownm = fmax(ownm, so_tot[3]);
     }
-    float gb_local[10];
+    if constexpr (!ROOT) {
 #pragma unroll
-    for (int l = 0; l < 10; ++l) gb_local[l] = (float)(sh[0][4 + l] + 2.0 * a.cbetas * ((double)pb[l] - (double)po[l]));
+      for (int l = 0; l < 10; ++l) gb_local[l] = (float)(sh[0][4 + l] + 2.0 * a.cbetas * ((double)pb[l] - (double)po[l]));
+    }
     if (a.stage == UUO_STAGE_PART) {
       const float gz = (float)sh[0][1];
       a.g_z[0] = gz;
@@ -468,7 +565,8 @@ __device__ __forceinline__ float gmof_q(float sig2, float s) { return sig2 / (si
 // FASSIGN without ITEMS (EXTENSION, marker stage's one-hot closure only; uuo_fit_set_frame_assign): the column's vertex changes
 // with the frame -- item (f, m) reads assign[f][m], an id < 0 is an item of weight 0 (on vertex 0, like every masked item).
 // Nothing else of the item differs.  Separate instantiations: k_bwd_sparse_f / _r_f / _t_f / _r_t_f.
-// ROOT (with PART; UUO_STAGE_ROOT / UUO_STAGE_ROOT_SHARED): the part stage's kernel on ALL vertices.  The launch carries the root
+// ROOT (with PART; UUO_STAGE_ROOT / UUO_STAGE_ROOT_SHARED; k_bwd_root1 / k_bwd_root, the rows BWD_ROUTE_ROOT selects): the part
+// stage's kernel on ALL vertices.  The launch carries the root
 // stage's own value in a.stage, so the item fetch takes the search's index as the vertex id and weighs the item with the marker
 // mask, as for the chamfer stage; the yaw's gradient d loss / d z_f of the frame stays in slot 1 of its partials (the other
 // instantiations clear the slot for every stage but the part stage), where k_finalize_root picks it up -- per frame, or summed
@@ -486,7 +584,7 @@ enum : unsigned {
   BWD_FASSIGN = 1u << 7,
   BWD_FLOOR = 1u << 8,
   BWD_WIDE = 1u << 9,  // debug flavour only: the one-array-per-name LDS layout on a general kernel (BWD_WIDE_KERNELS)
-  BWD_ROOT = 1u << 10,  // with BWD_PART: the root stages (BWD_ROOT_KERNELS; not rows of BWD_KERNELS: nothing selects them by facts)
+  BWD_ROOT = 1u << 10,  // with BWD_PART: the root stages (bwd_select names them by BwdFacts.stage)
 };
 // The float arrays of a general backward block's LDS, by phase.  (The frame, the tree's tables, w_red, red and the ACCEL window live
 // through all of them and stay outside.)
@@ -1366,7 +1464,10 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a) {
   XB(k_bwd_part, BWD_PART, BWD_NW * 64, BWD_NO_ATTR, UUO_OP_BWD_PART, k_bwd_part_b)                                               \
   /* EXTENSION: the four part-stage forms with the Geman-McClure data term */                                                    \
   XB(k_bwd_part1_r, BWD_PART | BWD_ONE_WAVE | BWD_ROBUST, 64, BWD_NO_ATTR, UUO_OP_BWD_PART_R, k_bwd_part1_b_r)                    \
-  XB(k_bwd_part_r, BWD_PART | BWD_ROBUST, BWD_NW * 64, BWD_NO_ATTR, UUO_OP_BWD_PART_R, k_bwd_part_b_r)
+  XB(k_bwd_part_r, BWD_PART | BWD_ROBUST, BWD_NW * 64, BWD_NO_ATTR, UUO_OP_BWD_PART_R, k_bwd_part_b_r)                            \
+  /* the root stages: the part stage's two plain forms on all vertices with the marker mask (no lock-step batch forms) */        \
+  X(k_bwd_root1, BWD_PART | BWD_ONE_WAVE | BWD_ROOT, 64, BWD_NO_ATTR, BWD_NO_OP)                                                  \
+  X(k_bwd_root, BWD_PART | BWD_ROOT, BWD_NW * 64, BWD_NO_ATTR, BWD_NO_OP)
 
 #define BWD_ENTRY(name, fl, nt, attr, op) \
   __global__ __launch_bounds__(nt) attr void name(BwdArgs a) { bwd_body<(fl)>(a); }
@@ -1377,12 +1478,6 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a) {
     bwd_body<(fl)>(a);                                                                     \
   }
 BWD_KERNELS(BWD_ENTRY, BWD_ENTRY_B)
-// The root stages' two forms of the part stage's kernel (one wave per frame for <= 16 markers, four above).  Not rows of
-// BWD_KERNELS: bwd_select never names them, uuo_closure_eval_impl launches them for UUO_STAGE_ROOT / UUO_STAGE_ROOT_SHARED.
-#define BWD_ROOT_KERNELS(X)                                                        \
-  X(k_bwd_root1, BWD_PART | BWD_ONE_WAVE | BWD_ROOT, 64, BWD_NO_ATTR, BWD_NO_OP)   \
-  X(k_bwd_root, BWD_PART | BWD_ROOT, BWD_NW * 64, BWD_NO_ATTR, BWD_NO_OP)
-BWD_ROOT_KERNELS(BWD_ENTRY)
 
 // the same list as the host sees it
 struct BwdKernel {
@@ -1420,8 +1515,9 @@ struct BwdFacts {
   bool robust, temporal, offs, fassign, floor;
 };
 // the routes in the order in which uuo_closure_eval_impl tries them
-enum BwdRoute { BWD_ROUTE_PART, BWD_ROUTE_THREE_CORNER, BWD_ROUTE_SURFACE, BWD_ROUTE_DENSE, BWD_ROUTE_GENERAL };
+enum BwdRoute { BWD_ROUTE_ROOT, BWD_ROUTE_PART, BWD_ROUTE_THREE_CORNER, BWD_ROUTE_SURFACE, BWD_ROUTE_DENSE, BWD_ROUTE_GENERAL };
 static BwdRoute bwd_route(const BwdFacts& k) {
+  if (uuo_is_root_stage(k.stage)) return BWD_ROUTE_ROOT;
   if (k.part_cached) return BWD_ROUTE_PART;
   if (k.three_corner) return BWD_ROUTE_THREE_CORNER;
   if (k.surface) return BWD_ROUTE_SURFACE;
@@ -1431,6 +1527,7 @@ static unsigned bwd_flags(const BwdFacts& k) {
   const unsigned r = k.robust ? BWD_ROBUST : 0u, t = k.temporal ? BWD_ACCEL : 0u, o = k.offs ? BWD_OFFS : 0u;
   const unsigned fa = k.fassign ? BWD_FASSIGN : 0u, fl = k.floor ? BWD_FLOOR : 0u;
   switch (bwd_route(k)) {
+    case BWD_ROUTE_ROOT: return BWD_PART | BWD_ROOT | (k.one_wave ? BWD_ONE_WAVE : 0u);  // (the part stage's one-wave split)
     case BWD_ROUTE_PART: return BWD_PART | (k.one_wave ? BWD_ONE_WAVE : 0u) | r;  // (nothing else reaches the part kernels)
     case BWD_ROUTE_THREE_CORNER: return BWD_ITEMS | t | o | fl;                   // (robust: k_bary_fwd* carries it)
     case BWD_ROUTE_SURFACE: return BWD_ITEMS | BWD_FASSIGN | t | fl;              // (robust: k_surf_fwd* carries it)
@@ -1440,11 +1537,14 @@ static unsigned bwd_flags(const BwdFacts& k) {
 }
 // The row of bwd_kernels for these facts, by exact match of the flag word: a combination nobody instantiated is an error, never
 // another kernel.  uuo_closure_eval_impl has refused, with messages of their own, a per-frame vertex table outside the marker
-// stage's plain one-hot closure and a surface term outside the chamfer stage's hard assignment before it gets here; both are
-// refused here as well, so that the mapping does not lean on that.
+// stage's plain one-hot closure and a surface term outside the chamfer stage's hard assignment before it gets here, and
+// validate_problem and side_terms_check everything but the plain closure on a root stage; all are refused here as well, so that
+// the mapping does not lean on that.
 static int bwd_select(const BwdFacts& k, const BwdKernel** out) {
   const bool refused = (k.fassign && (k.stage != UUO_STAGE_MARKER || k.three_corner || k.offs || k.floor)) ||
-                       (bwd_route(k) == BWD_ROUTE_SURFACE && (k.stage != UUO_STAGE_CHAMFER || k.dense));
+                       (bwd_route(k) == BWD_ROUTE_SURFACE && (k.stage != UUO_STAGE_CHAMFER || k.dense)) ||
+                       (bwd_route(k) == BWD_ROUTE_ROOT && (k.part_cached || k.three_corner || k.surface || k.dense || k.robust ||
+                                                           k.temporal || k.offs || k.fassign || k.floor));
   const unsigned fl = bwd_flags(k);
   *out = nullptr;
   if (!refused)
@@ -1793,185 +1893,17 @@ __global__ __launch_bounds__(1024) void k_finalize_b(const FinArgs* __restrict__
 //                       the backward's d loss / d z of the frame, <dR_0, E M_f> with E = d Rz / d z at 0, is the per-frame yaw's
 //   k_root_marker_mean  mm_t = mean_m x_tm over all columns, in double, once per public entry (with the marker mask)
 //   k_finalize_root     K_D for these stages: one block, sums in double in an order the indices fix, no atomics (bit-reproducible).
-//                       The frames' partials are summed as finalize_body sums them; the yaw's gradient is written per frame or as
-//                       the frames' sum into the one shared entry; the translation-velocity term
+//                       An instantiation of finalize_body (ROOT): the tail's inputs, the frames' sums, the shape prior and the
+//                       report are its code; the root stages' own are the yaw's gradient, written per frame or as the frames'
+//                       sum into the one shared entry, and the translation-velocity term
 //                         tvel = ctv sum_{t < F-1, c} r_tc^2,  r_tc = (trans_{t+1,c} - trans_{t,c}) - (mm_{t+1,c} - mm_{t,c})
-//                       adds 2 ctv (r_{t-1,c} - r_{t,c}) to the translation's gradient, which the backward kernel has written
+//                       which adds 2 ctv (r_{t-1,c} - r_{t,c}) to the translation's gradient -- the backward kernel has written it
 //                       with the data term alone.  The solver's statistics, the report block and the own-parameter words are
 //                       therefore formed HERE over the gradient as finally written -- the backward kernel's per-frame statistics
 //                       (slots 16..19) were taken before and are not read.
 // ----------------------------------------------------------------------------------------------------
-struct RootFinArgs {
-  int F, shared;                       // shared: one yaw for the sequence (UUO_STAGE_ROOT_SHARED)
-  uuo_gptr<const float> frame_part;    // [F][UUO_FP]: 0 data-loss sum, 1 d loss / d z_f, 4..13 d beta
-  uuo_gptr<const float> trans;         // [F][3] the parameters' translation
-  uuo_gptr<const double> mm;           // [F][3] the markers' mean per frame
-  uuo_gptr<const float> betas, o_betas;
-  double closs;                        // w_data / sum mask (0: no marker present)
-  double cbetas;                       // w_betas / 10
-  double ctv;                          // w_tv / ((F - 1) 3) (0: off, or F < 2)
-  uuo_gptr<float> g_trans, g_z, g_betas, loss;
-  uuo_gptr<const float> dir_trans, dir_z, dir_betas;  // optional: the direction's entries
-  uuo_gptr<double> stats;                              // optional [5], as FinArgs.stats
-  uuo_gptr<unsigned long long> rep_host;               // optional zero-copy report (UuoEvalReport)
-  unsigned long long rep_seq;
-};
 __global__ __launch_bounds__(1024) void k_finalize_root(RootFinArgs a) {
-  __builtin_amdgcn_s_setprio(3);  // latency-bound kernel of a solve chain, as k_finalize
-  __shared__ double sh[32][32];
-  // the threads' five statistics, summed in a fixed order: 32 runs of 32 consecutive threads (wave q takes quantity q; one pad
-  // per run, so that the 32 runs' reads fall into different banks), then the runs (thread q), then thread 0 reads the totals
-  __shared__ double rbuf[5][1056];
-  __shared__ double rruns[5][32];
-  __shared__ double rtot[5];
-  const int tid = threadIdx.x, comp = tid & 31, grp = tid >> 5;
-  const int F = a.F;
-  float pb[10], po[10], pd[10], pdz = 0.f;
-  unsigned long long rep_pre[5] = {0ull, 0ull, 0ull, 0ull, 0ull};
-  if (tid == 0) {  // the tail's inputs, on their way while the partials are summed (finalize_body)
-#pragma unroll
-    for (int l = 0; l < 10; ++l) {
-      pb[l] = a.betas[l];
-      po[l] = a.o_betas[l];
-      pd[l] = a.dir_betas ? a.dir_betas[l] : 0.f;
-    }
-    if (a.shared && a.dir_z) pdz = a.dir_z[0];
-    if (a.stats && a.rep_host) {
-      const unsigned long long* blk = reinterpret_cast<const unsigned long long*>(a.stats.get()) - 1;
-      rep_pre[0] = blk[0];
-#pragma unroll
-      for (int i = 6; i < 10; ++i) rep_pre[i - 5] = blk[i];
-    }
-  }
-  {  // the frames' partials in finalize_body's order: group g takes frames g, g + 32, ..., then the groups in order
-    double acc = 0.0;
-    if (comp < UUO_FP) {
-      for (int f0 = grp; f0 < F; f0 += 32 * 8) {
-        float v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          const int f = f0 + 32 * u;
-          v[u] = (f < F) ? a.frame_part[(size_t)f * UUO_FP + comp] : 0.f;
-        }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) acc += (double)v[u];
-      }
-    }
-    sh[grp][comp] = acc;
-  }
-  __syncthreads();
-  if (tid < 32) {
-    double s = 0.0;
-    for (int g = 0; g < 32; ++g) s += sh[g][tid];
-    sh[0][tid] = s;
-  }
-  __syncthreads();
-  // this thread's entries of the translation (and, per frame, of the yaw): {g.d, sum|g|, g.g, max|g|, sum r^2}
-  double t_sd = 0.0, t_s1 = 0.0, t_s2 = 0.0, t_sm = 0.0, t_tv = 0.0;
-  auto count = [&](float g, const float* dir, int i) {
-    if (dir) t_sd += (double)g * (double)dir[i];
-    t_s1 += fabs((double)g);
-    t_s2 += (double)g * (double)g;
-    t_sm = fmax(t_sm, fabs((double)g));
-  };
-  for (int i = tid; i < 3 * F; i += 1024) {
-    const int t = i / 3;
-    double r_prev = 0.0, r_cur = 0.0;
-    if (a.ctv != 0.0) {  // (block-uniform)
-      const double x0 = (double)a.trans[i], m0 = a.mm[i];
-      if (t >= 1) r_prev = (x0 - (double)a.trans[i - 3]) - (m0 - a.mm[i - 3]);
-      if (t + 1 < F) r_cur = ((double)a.trans[i + 3] - x0) - (a.mm[i + 3] - m0);
-    }
-    const float g = (float)((double)a.g_trans[i] + 2.0 * a.ctv * (r_prev - r_cur));
-    a.g_trans[i] = g;
-    t_tv += r_cur * r_cur;
-    count(g, a.dir_trans.get(), i);
-  }
-  if (!a.shared) {
-    for (int f = tid; f < F; f += 1024) {
-      const float gz = a.frame_part[(size_t)f * UUO_FP + 1];
-      a.g_z[f] = gz;
-      count(gz, a.dir_z.get(), f);
-    }
-  }
-  {
-    const int slot = tid + (tid >> 5);
-    rbuf[0][slot] = t_sd;
-    rbuf[1][slot] = t_s1;
-    rbuf[2][slot] = t_s2;
-    rbuf[3][slot] = t_sm;  // (the maximum of values >= 0)
-    rbuf[4][slot] = t_tv;
-  }
-  __syncthreads();
-  {
-    const int q = tid >> 6, run = tid & 63;  // (q is wave-uniform)
-    if (q < 5 && run < 32) {
-      const double* b = &rbuf[q][run * 33];
-      double r = 0.0;
-#pragma unroll 8
-      for (int u = 0; u < 32; ++u) r = (q == 3) ? fmax(r, b[u]) : r + b[u];
-      rruns[q][run] = r;
-    }
-  }
-  __syncthreads();
-  if (tid < 5) {
-    double r = 0.0;
-#pragma unroll 8
-    for (int u = 0; u < 32; ++u) r = (tid == 3) ? fmax(r, rruns[tid][u]) : r + rruns[tid][u];
-    rtot[tid] = r;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    double sd = rtot[0], s1 = rtot[1], s2 = rtot[2], sm = rtot[3];
-    const double tv = rtot[4];
-    if (a.shared) {
-      const float gz = (float)sh[0][1];
-      a.g_z[0] = gz;
-      if (a.dir_z) sd += (double)gz * (double)pdz;
-      s1 += fabs((double)gz);
-      s2 += (double)gz * (double)gz;
-      sm = fmax(sm, fabs((double)gz));
-    }
-    const double own1 = s1, own2 = s2, ownm = sm;  // everything but the shape vector
-    double bsq = 0.0;
-    float gb_local[10];
-#pragma unroll
-    for (int l = 0; l < 10; ++l) {
-      const double diff = (double)pb[l] - (double)po[l];
-      bsq += diff * diff;
-      const float gb = (float)(sh[0][4 + l] + 2.0 * a.cbetas * diff);
-      gb_local[l] = gb;
-      a.g_betas[l] = gb;
-      if (a.dir_betas) sd += (double)gb * (double)pd[l];
-      s1 += fabs((double)gb);
-      s2 += (double)gb * (double)gb;
-      sm = fmax(sm, fabs((double)gb));
-    }
-    const float lossf = (float)((a.closs * sh[0][0] + a.cbetas * bsq) + a.ctv * tv);
-    a.loss[0] = lossf;
-    if (a.stats) {
-      a.stats[0] = (double)lossf;
-      a.stats[1] = sd;
-      a.stats[2] = sm;
-      a.stats[3] = s1;
-      a.stats[4] = s2;
-      if (a.rep_host) {  // the report block, word for word as finalize_body's separate (non-coherent) form writes it
-        const double five[5] = {(double)lossf, sd, sm, s1, s2};
-        a.rep_host[0] = rep_pre[0];
-#pragma unroll
-        for (int i = 0; i < 5; ++i) a.rep_host[1 + i] = (unsigned long long)__double_as_longlong(five[i]);
-#pragma unroll
-        for (int i = 6; i < 10; ++i) a.rep_host[i] = rep_pre[i - 5];
-        a.rep_host[11] = (unsigned long long)__double_as_longlong(ownm);
-        a.rep_host[12] = (unsigned long long)__double_as_longlong(own1);
-        a.rep_host[13] = (unsigned long long)__double_as_longlong(own2);
-#pragma unroll
-        for (int l = 0; l < 10; ++l) a.rep_host[14 + l] = (unsigned long long)__double_as_longlong((double)gb_local[l]);
-        __threadfence_system();
-        __hip_atomic_store(&a.rep_host[10], a.rep_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-      }
-    }
-  }
+  finalize_body<1024, false, false, false, true>(a.fin, nullptr, &a);
 }
 __global__ __launch_bounds__(64) void k_root_yaw(int F, const float* __restrict__ z, const float* __restrict__ root,
                                                  float* __restrict__ out) {
@@ -2035,8 +1967,7 @@ struct StageLayout {
 // (69 of 211 floats per frame) is then dead weight that the two history passes of every iteration stream for nothing.
 // uuo_stage_compactable decides per solve (it checks the rows against their targets); uuo_lbfgs_solve then runs L-BFGS on
 // n_act = 142 F + 10 (chamfer) / 147 F + 10 (marker: the root's third row has no prior at all) coordinates.
-static bool is_root_stage(int stage) { return stage == UUO_STAGE_ROOT || stage == UUO_STAGE_ROOT_SHARED; }
-static bool stage_known(int stage) { return (stage >= 0 && stage <= 2) || is_root_stage(stage); }
+static bool stage_known(int stage) { return (stage >= 0 && stage <= 2) || uuo_is_root_stage(stage); }
 static StageLayout stage_layout(int stage, int F, bool compact = false) {
   StageLayout s;
   s.n = 0;
@@ -2056,7 +1987,7 @@ static StageLayout stage_layout(int stage, int F, bool compact = false) {
     s.off_trans = 23 * gp * F + 10 + gp * F;
     s.n = 23 * gp * F + 10 + gp * F + 3 * F;
     s.gs_pose = s.gs_root = gp;
-  } else if (is_root_stage(stage)) {  // [trans 3F | z F or 1 | betas 10]: no rotations, so no compact packing
+  } else if (uuo_is_root_stage(stage)) {  // [trans 3F | z F or 1 | betas 10]: no rotations, so no compact packing
     const int nz = (stage == UUO_STAGE_ROOT) ? F : 1;
     s.off_trans = 0;
     s.off_z = 3 * F;
@@ -2125,10 +2056,10 @@ static UuoSideTerms side_terms_on(const uuo_fit* fit, const uuo_problem_t* p) {
 static int side_terms_check(const uuo_fit* fit, const uuo_problem_t* p) {
   for (const SideTermRow& r : side_term_rows) {
     if (!r.set(fit)) continue;
-    const char* not_built = p->stage == UUO_STAGE_PART ? "the part stage"
-                            : is_root_stage(p->stage)  ? "a solve on the root stage (UUO_STAGE_ROOT / UUO_STAGE_ROOT_SHARED)"
-                            : p->w_soft != 0.f         ? "the soft-assignment data term (w_soft)"
-                                                       : nullptr;
+    const char* not_built = p->stage == UUO_STAGE_PART    ? "the part stage"
+                            : uuo_is_root_stage(p->stage) ? "a solve on the root stage (UUO_STAGE_ROOT / UUO_STAGE_ROOT_SHARED)"
+                            : p->w_soft != 0.f            ? "the soft-assignment data term (w_soft)"
+                                                          : nullptr;
     if (!not_built && !uuo_recorder) continue;
     const std::string named = std::string(r.subject) + " (" + r.setter + ", extension)";
     uuo_set_error(not_built ? "closure: " + named + " " + r.verb + " not built for " + not_built
@@ -2183,7 +2114,7 @@ static int validate_problem(const uuo_fit* fit, const uuo_problem_t* p) {
               "closure: n_corners is 0 / 1 (one-hot placement) or 3 with d_bary (marker stage on a three-corner placement)");
   if (p->stage == UUO_STAGE_PART)
     UUO_REQUIRE(p->d_subset != nullptr && p->n_subset > 0 && p->n_subset <= fit->model->V, "closure: part stage needs a vertex subset");
-  if (is_root_stage(p->stage)) {
+  if (uuo_is_root_stage(p->stage)) {
     UUO_REQUIRE(p->pose_cache_id != 0, "closure: the root stage needs a pose cache id (its body pose is fixed: the pose blend is computed once)");
     UUO_REQUIRE(p->w_soft == 0.f, "closure: the soft-assignment data term (w_soft, extension) is not built on the root stage");
     UUO_REQUIRE(p->robust_sigma == 0.f, "closure: robust_sigma (Geman-McClure data term, extension) is not built on the root stage");
@@ -2291,7 +2222,7 @@ static int root_buffers(uuo_fit* fit, hipStream_t s) {
 int uuo_ensure_mask(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p) {
   int rc = uuo_launch_mask(s, p->F, p->M, p->d_markers, fit->mask, fit->scalars);
   if (rc) return rc;
-  if (is_root_stage(p->stage)) {  // the root stages' own buffers and the markers' mean per frame (the translation-velocity term)
+  if (uuo_is_root_stage(p->stage)) {  // the root stages' own buffers and the markers' mean per frame (the translation-velocity term)
     rc = root_buffers(fit, s);
     if (rc) return rc;
     hipLaunchKernelGGL(k_root_marker_mean, dim3((3 * p->F + 255) / 256), dim3(256), 0, s, p->F, p->M, p->d_markers, fit->root_mm);
@@ -2396,7 +2327,7 @@ static int closure_forward(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, 
   int rc = 0;
   static const int no_cache = UUO_ENV_INT("UUO_PART_NOCACHE", 0);  // comparison only
   // the root stages run the part stage's cached-pose routes on the library's whole-body vertex table
-  const bool rootst = is_root_stage(p->stage);
+  const bool rootst = uuo_is_root_stage(p->stage);
   const int32_t* const d_subset = rootst ? fit->root_ids : p->d_subset;
   const int n_subset = rootst ? m->V : p->n_subset;
   const bool cached = rootst || (p->stage == UUO_STAGE_PART && p->pose_cache_id != 0 && !no_cache);
@@ -2592,7 +2523,7 @@ __global__ __launch_bounds__(256) void k_third_rows_differ(int count, const floa
 int uuo_stage_compactable(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, const float* d_x, bool* compact) {
   *compact = false;
   const int off = UUO_ENV_INT("UUO_NO_COMPACT", 0);  // debug flavour only: the full packing, for comparison
-  if (off || p->stage == UUO_STAGE_PART || is_root_stage(p->stage)) return 0;  // (no rotations among the parameters)
+  if (off || p->stage == UUO_STAGE_PART || uuo_is_root_stage(p->stage)) return 0;  // (no rotations among the parameters)
   if (p->w_pose == 0.f) {  // no pose prior: the third rows have no gradient whatever they hold
     *compact = true;
     return 0;
@@ -2651,7 +2582,7 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
   UuoPoseSrc src;
   rc = stage_pose_src_at(fit, s, p, lay, d_x, &src);
   if (rc) return rc;
-  const bool rootst = is_root_stage(p->stage);
+  const bool rootst = uuo_is_root_stage(p->stage);
   const bool soft_chamfer = p->stage == UUO_STAGE_CHAMFER && p->w_soft != 0.f;
   bool have_vp = false;
   if (soft_chamfer) {
@@ -2724,45 +2655,6 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
   a.off_pose = gl.off_pose; a.off_root = gl.off_root; a.off_z = gl.off_z; a.off_trans = gl.off_trans;
   a.h.gx = F;
   a.h.gy = 1;
-  if (rootst) {
-    // The root stages: the part stage's kernel on all vertices with the marker mask (k_bwd_root1 up to 16 markers, k_bwd_root
-    // above: the forward's one-wave / four-wave split), then their own finalisation.  Side terms: side_terms_check has refused them.
-    UUO_REQUIRE(!uuo_recorder && fit->pose_cache && fit->pose_cache_id == p->pose_cache_id && fit->root_mm,
-                "closure: the root stage runs on its cached pose blend, outside lock-step batches");
-    a.C = fit->pose_cache;
-    if (M <= 16)
-      hipLaunchKernelGGL(k_bwd_root1, dim3(F), dim3(64), 0, s, a);
-    else
-      hipLaunchKernelGGL(k_bwd_root, dim3(F), dim3(BWD_NW * 64), 0, s, a);
-    UUO_HIP_CHECK(hipGetLastError());
-    RootFinArgs ra;
-    std::memset(&ra, 0, sizeof(ra));
-    ra.F = F;
-    ra.shared = p->stage == UUO_STAGE_ROOT_SHARED;
-    ra.frame_part = fit->frame_part;
-    ra.trans = d_x + lay.off_trans;
-    ra.mm = fit->root_mm;
-    ra.betas = d_x + lay.off_betas;
-    ra.o_betas = p->d_o_betas;
-    ra.closs = data_c;
-    ra.cbetas = (double)p->w_betas / 10.0;
-    ra.ctv = (F >= 2) ? (double)fit->root_tvel / ((double)(F - 1) * 3.0) : 0.0;
-    ra.g_trans = d_grad + gl.off_trans;
-    ra.g_z = d_grad + gl.off_z;
-    ra.g_betas = d_grad + gl.off_betas;
-    ra.loss = d_loss;
-    if (d_dir) {
-      ra.dir_trans = d_dir + gl.off_trans;
-      ra.dir_z = d_dir + gl.off_z;
-      ra.dir_betas = d_dir + gl.off_betas;
-    }
-    ra.stats = d_stats;
-    ra.rep_host = (report && d_stats) ? report->host : nullptr;
-    ra.rep_seq = report ? report->seq : 0ull;
-    hipLaunchKernelGGL(k_finalize_root, dim3(1), dim3(1024), 0, s, ra);
-    UUO_HIP_CHECK(hipGetLastError());
-    return 0;
-  }
   FinArgs fa;
   std::memset(&fa, 0, sizeof(fa));
   fa.stage = p->stage; fa.F = F;
@@ -2770,13 +2662,13 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
   fa.betas = d_x + lay.off_betas;
   fa.o_betas = p->d_o_betas;
   fa.closs = data_c;
-  fa.cpose = (p->stage == UUO_STAGE_PART) ? 0.0 : (double)p->w_pose / ((double)F * 207.0);
+  fa.cpose = pose_fixed ? 0.0 : (double)p->w_pose / ((double)F * 207.0);
   fa.cbetas = (double)p->w_betas / 10.0;
   fa.g_betas = d_grad + gl.off_betas;
-  fa.g_z = (p->stage == UUO_STAGE_PART) ? d_grad + gl.off_z : nullptr;
+  fa.g_z = pose_fixed ? d_grad + gl.off_z : nullptr;  // (the part and the root stages: the yaw is the finalisation's)
   fa.loss = d_loss;
   fa.dir_betas = d_dir ? d_dir + gl.off_betas : nullptr;
-  fa.dir_z = (d_dir && p->stage == UUO_STAGE_PART) ? d_dir + gl.off_z : nullptr;
+  fa.dir_z = (d_dir && pose_fixed) ? d_dir + gl.off_z : nullptr;
   fa.stats = d_stats;
   fa.rep_host = (report && d_stats) ? report->host : nullptr;
   fa.rep_seq = report ? report->seq : 0ull;
@@ -2824,7 +2716,12 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
     return 0;
   };
   const BwdRoute route = bwd_route(k);
-  if (route == BWD_ROUTE_PART) {
+  if (route == BWD_ROUTE_ROOT) {
+    // the part stage's kernel on all vertices with the marker mask, then the root stages' own finalisation (k_finalize_root)
+    UUO_REQUIRE(!uuo_recorder && fit->pose_cache && fit->pose_cache_id == p->pose_cache_id && fit->root_mm,
+                "closure: the root stage runs on its cached pose blend, outside lock-step batches");
+    a.C = fit->pose_cache;
+  } else if (route == BWD_ROUTE_PART) {
     a.C = fit->pose_cache;
     a.pre = soft ? fit->soft_pre : nullptr;
   } else if (route == BWD_ROUTE_THREE_CORNER) {
@@ -2940,7 +2837,8 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
   rc = bwd_select(k, &bk);
   if (rc) return rc;
 #ifdef UUO_DEBUG_HOOKS
-  if (UUO_ENV_INT("UUO_BWD_WIDE_LDS", 0)) {  // debug flavour only: the same instantiation on the former LDS layout, for comparison
+  // debug flavour only: the same instantiation on the former LDS layout, for comparison (the root stages never read the knob)
+  if (UUO_ENV_INT("UUO_BWD_WIDE_LDS", 0) && route != BWD_ROUTE_ROOT) {
     const BwdKernel* wide = nullptr;
     for (const BwdKernel& row : bwd_wide_kernels)
       if (row.flags == (bk->flags | BWD_WIDE)) wide = &row;
@@ -2952,13 +2850,26 @@ int uuo_closure_eval_impl(uuo_fit* fit, hipStream_t s, const uuo_problem_t* p, c
   if (bk->op == BWD_NO_OP || !uuo_record(bk->op, F, (bk->flags & BWD_PART) ? bk->threads / 64 : 1, a))
     hipLaunchKernelGGL((bk->kernel), dim3(F), dim3(bk->threads), 0, s, a);
   UUO_HIP_CHECK(hipGetLastError());
+  // the one finalisation launch (none: the backward kernel's last block has done it)
   if (!fin_fused) {
-    if (offs)
+    if (offs) {
       hipLaunchKernelGGL(temporal ? k_finalize_to : k_finalize_o, dim3(1), dim3(1024), 0, s, fa, oa);
-    else if (temporal)
+    } else if (temporal) {
       hipLaunchKernelGGL(k_finalize_t, dim3(1), dim3(1024), 0, s, fa);
-    else if (!uuo_record(UUO_OP_FIN, 1, 1, fa))
+    } else if (route == BWD_ROUTE_ROOT) {
+      RootFinArgs ra;
+      std::memset(&ra, 0, sizeof(ra));
+      ra.fin = fa;
+      ra.shared = p->stage == UUO_STAGE_ROOT_SHARED;
+      ra.trans = d_x + lay.off_trans;
+      ra.mm = fit->root_mm;
+      ra.ctv = (F >= 2) ? (double)fit->root_tvel / ((double)(F - 1) * 3.0) : 0.0;
+      ra.g_trans = d_grad + gl.off_trans;
+      ra.dir_trans = d_dir ? d_dir + gl.off_trans : nullptr;
+      hipLaunchKernelGGL(k_finalize_root, dim3(1), dim3(1024), 0, s, ra);
+    } else if (!uuo_record(UUO_OP_FIN, 1, 1, fa)) {
       hipLaunchKernelGGL(k_finalize, dim3(1), dim3(1024), 0, s, fa);
+    }
     UUO_HIP_CHECK(hipGetLastError());
   }
 

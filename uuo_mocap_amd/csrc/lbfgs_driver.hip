@@ -801,7 +801,7 @@ static int shared_prepare(uuo_fit_t* fit, hipStream_t s, const uuo_problem_t* p,
   UUO_REQUIRE(d_x && opt && stats, "uuo_lbfgs_solve_shared: null argument");
   UUO_REQUIRE(opt->max_iter > 0, "uuo_lbfgs_solve_shared: max_iter must be positive");
   UUO_REQUIRE(uuo_recorder == nullptr, "uuo_lbfgs_solve_shared: not inside a lock-step batch");
-  UUO_REQUIRE(p->stage != UUO_STAGE_ROOT && p->stage != UUO_STAGE_ROOT_SHARED,
+  UUO_REQUIRE(!uuo_is_root_stage(p->stage),
               "uuo_lbfgs_solve_shared: shared-betas solves do not carry the root stage (UUO_STAGE_ROOT / UUO_STAGE_ROOT_SHARED)");
   // EXTENSION: the per-evaluation exchange carries the betas' share only, not the latent marker offsets
   UUO_REQUIRE(p->w_offsets == 0.f, "uuo_lbfgs_solve_shared: shared-betas solves do not carry the latent marker offsets (w_offsets, "

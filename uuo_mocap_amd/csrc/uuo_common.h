@@ -22,6 +22,9 @@
 
 void uuo_set_error(const std::string& msg);
 
+// the root stages: translation, yaw and shape with the body pose held (include/uuo_hip.h)
+inline bool uuo_is_root_stage(int stage) { return stage == UUO_STAGE_ROOT || stage == UUO_STAGE_ROOT_SHARED; }
+
 // Ablation / comparison knobs (kernel variants, phase cut-offs) and the uuo_debug_* hooks exist only in the debug
 // flavour of the library (libuuo_hip_debug.so, built with -DUUO_DEBUG_HOOKS and loaded by tests/ and tools/ only).
 // The shipped libuuo_hip.so reads no environment variable and exports nothing outside include/uuo_hip.h.
